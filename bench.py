@@ -13,7 +13,9 @@ Protocol: [K cold steps, timed separately -> cold_ms_per_step] -> burn-in (>= --
 counted steps run at the clocks a training loop sees, not at the clocks of an idle device) -> W warm-up
 steps -> barrier + device sync -> EXACTLY K timed steps -> device sync + barrier; max over ranks.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON result line on stdout, last: the contract fields (metric, value, unit, n_gpus, steps, warmup, ms_per_step, ...)
+and the headline roofline (bound, achieved, peak, unit, frac, kernel_avg_ms) -- a short line that survives the tail of a log.  Before it,
+the FULL record goes to stderr as one JSON line: the same fields plus
   roofline             -- bound "mfma": `achieved` = the ALGORITHMIC f16 flops of one launch (SURVEY.md 8(d) MFMA clause: every
                           ordered pair at the K = 16 of the fp16-split filter, 2 * 2BNM * 16 = 34.36 GFLOP) / the dominant
                           kernel's average duration in THIS run (HIP events on its stream), `peak` 2500 TF dense f16,
@@ -33,6 +35,11 @@ Rank 0 prints ONE JSON line with the contract fields plus
                           edge_loss, laplacian_loss; forward and forward+backward)
   cpu_baseline         -- the oracle's KD-tree twin of the reference CPU path, timed on this host (N=1 only)
 Everything beyond the timed K steps runs after them (N=1, rank 0) and does not enter `value`.
+
+--dump-outputs DIR: rank 0 writes what the timed path returned in its last step -- the Float32 loss of chamfer_distance(A, B), the
+global loss with N GPUs, read back right after the K steps (`--launcher inproc`: one more evaluation of the same step) -- as
+DIR/loss.npy (float32, shape (1,)).  The inputs are the seeded synthetic clouds above, identical from run to run, so two builds can
+be compared output for output.
 
 N > 1 (one process per GPU): NO torch in this file.  torchrun only exports RANK / WORLD_SIZE / MASTER_*; the library
 bootstraps its own RCCL communicator (fx3d_comm_bootstrap over tcp://MASTER_ADDR:MASTER_PORT+1), the data-plane
@@ -135,6 +142,34 @@ def live_pmc_traffic(timeout_s=120):
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     return out
+
+
+RESULT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+               "dtype", "data", "loss", "launcher", "scaling_efficiency", "cold_ms_per_step", "stream_event_ms_per_step")
+RESULT_ROOFLINE_KEYS = ("bound", "achieved", "peak", "unit", "frac", "kernel_avg_ms")
+
+
+def emit(out):
+    """The full record as one JSON line on stderr, then the short result line (RESULT_KEYS, the workload, the headline roofline) as
+    the last line on stdout."""
+    import ctypes as C
+    try:  # C stdio of the loaded libraries first (RCCL prints its NCCL_DEBUG=VERSION banner there): the JSON goes last
+        C.CDLL(None).fflush(None)
+    except Exception:  # noqa: BLE001
+        pass
+    print(json.dumps(out), file=sys.stderr, flush=True)
+    line = {k: out[k] for k in RESULT_KEYS if k in out}
+    line["workload"] = out["config"]["workload"]
+    line["roofline"] = {k: out["roofline"].get(k) for k in RESULT_ROOFLINE_KEYS}
+    line["full_record"] = "stderr"
+    print(json.dumps(line), flush=True)
+
+
+def dump_outputs(dirname, loss):
+    """--dump-outputs: what the timed path returned in its last step (chamfer_distance's Float32 loss) as DIR/loss.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss.npy"), np.array([loss], dtype=np.float32))
 
 
 def self_launch(n):
@@ -258,6 +293,8 @@ def run_inproc(args, why, value_1=None):
     md.synchronize()
     t1 = time.perf_counter()
     _lib.call("fx3d_profile_enable", 0)
+    if args.dump_outputs:   # the timed steps leave the loss on the devices without a read-back: one more evaluation of the same step
+        dump_outputs(args.dump_outputs, md.chamfer_distance(xs, ys, Bg))
     avg, mn, mx, cnt = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
     _lib.call("fx3d_profile_kernel_stats", b"nn1", C.byref(avg), C.byref(mn), C.byref(mx), C.byref(cnt))
     elapsed = t1 - t0
@@ -282,11 +319,7 @@ def run_inproc(args, why, value_1=None):
         "comm": {"nranks": n, "rccl_version": info["rccl_version"], "backend": "fx3d_comm_init_all (ncclCommInitAll) + fx3d_chamfer_fwd_multi",
                  "devices": [{"index": d, "pci_bus_id": ids[d][0], "device_uuid": ids[d][1]} for d in range(n)], "distinct_devices": len(set(ids))},
     }
-    try:
-        C.CDLL(None).fflush(None)
-    except Exception:  # noqa: BLE001
-        pass
-    print(json.dumps(out), flush=True)
+    emit(out)
     md.close()
     return 0
 
@@ -317,10 +350,14 @@ def main():
                          "RCCL communicator bootstrapped over TCP; `inproc` = ONE process driving the N devices through "
                          "fx3d_comm_init_all / fx3d_chamfer_fwd_multi (ncclCommInitAll, a worker thread per device) -- also the "
                          "FALLBACK rank 0 takes by itself when the process-per-GPU bootstrap fails (the line then says so)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss of the last timed step as DIR/loss.npy (float32), for comparing two builds")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit(f"[bench] --gpus {args.gpus}: need >= 1")
+    if args.steps < 1:
+        raise SystemExit(f"[bench] --steps {args.steps}: need >= 1")
     if args.launcher == "inproc" and (args.gpus > 1 or args.force_dist):
         if int(os.environ.get("RANK", "0")) != 0:   # under torchrun: rank 0 drives every device, the other ranks have nothing to do
             return
@@ -599,6 +636,8 @@ def main():
         return
 
     elapsed, loss = res["elapsed"], res["loss"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss)
     pairs_per_step = Bg * NPTS * MPTS
     value = pairs_per_step * args.steps / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
@@ -703,11 +742,7 @@ def main():
         out["hbm_bound_kernels"] = hbm_bound_kernels()
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(fx)
-    try:  # C stdio of the loaded libraries first (RCCL prints its NCCL_DEBUG=VERSION banner there): the JSON goes last
-        C.CDLL(None).fflush(None)
-    except Exception:  # noqa: BLE001
-        pass
-    print(json.dumps(out), flush=True)
+    emit(out)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -1088,11 +1088,12 @@ def test_sample_points_pair_is_two_sample_points(gpu_fx):
 
 
 @pytest.mark.gpu
-def test_bench_line_force_dist_equals_plain_and_roofline_is_a_fraction(gpu_fx):
+def test_bench_line_force_dist_equals_plain_and_roofline_is_a_fraction(gpu_fx, tmp_path):
     """(a) the bench line's `roofline.frac` is the fraction of the bound it names (f16 MFMA pipe, peak 2500 TF;
     no field called *frac above 1; the algorithmic-fp32 figure only as a named extra); (b) `--gpus 1 --force-dist` (RCCL
     communicator + collectives at world size 1) reports the same loss, n_gpus and workload as the plain line; (c) `--gpus 2`
-    on this one-GPU box ends non-zero without printing a line."""
+    on this one-GPU box ends non-zero without printing a line.  The short result line (last on stdout) repeats the full
+    record's (stderr) contract fields; --dump-outputs writes the loss of the last timed step."""
     import json
     import subprocess
     import sys
@@ -1103,8 +1104,21 @@ def test_bench_line_force_dist_equals_plain_and_roofline_is_a_fraction(gpu_fx):
     def line(extra):
         r = subprocess.run([sys.executable, bench, "--gpus", "1"] + common + extra, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
-        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    plain, forced = line([]), line(["--force-dist", "--mode", "serial"])
+        short = json.loads(r.stdout.splitlines()[-1])
+        full = json.loads([ln for ln in r.stderr.splitlines() if ln.startswith("{")][-1])
+        assert len(r.stdout.splitlines()[-1]) < 1500
+        for k, v in short.items():
+            if k == "roofline":
+                assert v == {q: full["roofline"][q] for q in v} and set(v) >= {"bound", "achieved", "peak", "unit", "frac"}
+            elif k == "workload":
+                assert v == full["config"]["workload"]
+            elif k != "full_record":
+                assert v == full[k], k
+        assert short["steps"] == 20 and short["ms_per_step"] > 0
+        return full
+    plain, forced = line(["--dump-outputs", str(tmp_path)]), line(["--force-dist", "--mode", "serial"])
+    dumped = np.load(tmp_path / "loss.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (1,) and dumped[0] == np.float32(plain["loss"])
     for out in (plain, forced):
         roof = out["roofline"]
         assert out["n_gpus"] == 1 and roof["bound"] == "mfma" and roof["peak"] == 2500.0 and roof["unit"] == "TFLOP/s"

@@ -4,7 +4,7 @@ and checks, for every instruction inside an inline-asm block, that no VGPR it RE
 required wait states earlier (CDNA3/4 ISA: an XDL write of VGPRs followed by a VALU read needs 5 / 11 / 19 wait states for
 2- / 8- / 16-pass MFMAs -- one wait state = one issue slot of four cycles, an MFMA keeps the matrix pipe for `passes` of them; the kernels use the 8-pass v_mfma_f32_32x32x16_f16 and the 16-pass v_mfma_f32_32x32x2_f32).
 Instructions the compiler emitted itself are covered by its own hazard recogniser and are not checked.  CPU only (hipcc
-cross-compiles); the assembly is cached under /tmp by source hash."""
+cross-compiles); the assembly is cached by source hash in the library's build directory (flux3d.jl_amd/lib/isa)."""
 import hashlib
 import os
 import re
@@ -26,9 +26,13 @@ def _assembly(name):
     h = hashlib.sha256()
     for f in (src, os.path.join(CSRC, "fx3d_common.h"), os.path.join(ROOT, "include", "flux3d_hip.h")):
         h.update(open(f, "rb").read())
-    out = f"/tmp/fx3d_isa_{name}_{h.hexdigest()[:16]}.s"
+    cache = os.path.join(ROOT, "flux3d.jl_amd", "lib", "isa")
+    os.makedirs(cache, exist_ok=True)
+    out = os.path.join(cache, f"{name}_{h.hexdigest()[:16]}.s")
     if not os.path.exists(out):
-        subprocess.run([HIPCC] + FLAGS + [src, "-o", out], check=True, capture_output=True, cwd=CSRC, timeout=600)
+        tmp = f"{out}.{os.getpid()}.tmp"
+        subprocess.run([HIPCC] + FLAGS + [src, "-o", tmp], check=True, capture_output=True, cwd=CSRC, timeout=600)
+        os.replace(tmp, out)
     return open(out).read()
 
 
