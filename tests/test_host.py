@@ -347,3 +347,28 @@ def test_vertex_face_table_and_the_oracles_sampling_adjoint(fx, oracle):
     base = np.asfortranarray(rng.standard_normal(got.shape).astype(np.float32))
     assert np.allclose(oracle.sample_points_bwd(m.get_faces_padded().astype(np.int64) - 1, m._faces_len, m.V, fi, r1, r2, gout, base=base),
                        exp + base, rtol=1e-4, atol=1e-5)
+
+
+def test_fuzz_prune_draws_only_pruned_shapes(fx):
+    """tools/fuzz_prune.py sweeps the PRUNED launch of nn1_f16_kernel: its shape sampler redraws until the plan asks for the
+    blocks' scratch (fx3d_chamfer_workspace_bytes larger with nn1_prune = 1 than with 0; the library plans without a device).
+    Its earlier fixed list of B (1 ... 17) pruned one draw in forty."""
+    import ctypes as C
+    import sys
+    import time
+    from flux3d_jl_amd import _lib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fuzz_prune
+
+    def ws(N, M, B, v):
+        n = C.c_size_t(0)
+        with _lib.option("nn1_prune", v):
+            _lib.call("fx3d_chamfer_workspace_bytes", N, M, B, 3, C.byref(n))
+        return n.value
+
+    rng = np.random.default_rng(3)
+    t0 = time.time()
+    shapes = [fuzz_prune.prune_shape(rng) for _ in range(200)]
+    assert time.time() - t0 < 5.0
+    assert all(ws(N, M, B, 1) > ws(N, M, B, 0) for N, M, B in shapes)
+    assert any(N != M for N, M, _ in shapes) and len({B for _, _, B in shapes}) >= 3
