@@ -27,7 +27,7 @@ from .transforms import (EPS, compute_faces_areas_list, compute_faces_areas_pack
 from .fit import FitStepGraph, Momentum, loss_dolphin  # noqa: E402
 from .graph import (create_knn_graph, edge_features, edge_features_grad, edgeconv_graph, knn,  # noqa: E402
                     knn_gather)
-from .conversions import pointcloud_to_voxel  # noqa: E402
+from .conversions import pointcloud_to_voxel, trimesh_to_voxel  # noqa: E402
 from . import synth  # noqa: E402
 
 use_hip = [functional()]  # the `Flux3D.use_cuda[]` analogue (src/Flux3D.jl:52-61)

@@ -27,7 +27,7 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  get_faces_list, get_edges_packed, get_laplacian_packed,
                  compute_faces_areas_packed, compute_faces_areas_padded,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
-                 _padded_to_list, _padded_to_packed, offset!
+                 _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel
 using SparseArrays: SparseMatrixCSC, findnz
 import Zygote
 
@@ -574,6 +574,27 @@ function pointcloud_to_voxel(p::PointCloud, res::Int = 32)
     return vox
 end
 
+# trimesh_to_voxel (src/conversions.jl:133-207) for HipArray meshes -> (res,res,res,B) Float32 0/1, bit-identical to the
+# reference's `_voxelize` (x indexes the first dimension).  The reference's own `VoxelGrid(m::TriMesh, res)` (:74-77) and
+# `TriMeshToVoxelGrid` (src/transforms/transforms.jl:340-355) call it, so they run on the device for a `hip(m)` mesh (the
+# reference's host loop would `setindex!` into a HipArray, which raises).  A mesh with zero extent or a NaN / Inf coordinate
+# throws, as the reference's `round(Int, NaN)` does; the library counts such meshes on the device.
+function trimesh_to_voxel(m::TriMesh{Float32,R,HipArray}, res::Int = 32) where {R}
+    1 <= res <= 1024 || throw(ArgumentError("trimesh_to_voxel: resolution must lie in [1, 1024]"))
+    verts = get_verts_padded(m)::HipArray{Float32,3}
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_trimesh_voxel_workspace_bytes(m.V::Int32, m.F::Int32, m.N::Int32, res::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[]); vox = HipArray{Float32}(undef, res, res, res, m.N)
+    bad = fill!(HipArray{UInt32}(undef, 1), 0)
+    faces, flen = m.F > 0 ? (faces_padded_dev(m).ptr, faces_len_dev(m).ptr) : (C_NULL, C_NULL)
+    check(@ccall LIB.fx3d_trimesh_to_voxel(verts.ptr::Ptr{Cvoid}, m.V::Int32, verts_len_dev(m).ptr::Ptr{Cvoid}, faces::Ptr{Cvoid},
+                                           m.F::Int32, flen::Ptr{Cvoid}, m.N::Int32, res::Int32, vox.ptr::Ptr{Cvoid},
+                                           bad.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    nbad = unhip(bad)[1]
+    nbad == 0 || throw(ArgumentError("trimesh_to_voxel: $nbad of $(m.N) meshes have zero extent or a non-finite coordinate"))
+    return vox
+end
+
 # ---- TriMesh device mirrors: int32 0-based copies of the host integer data (cached per mesh) ---
 const _mirror = WeakKeyDict{Any,Dict{Symbol,Any}}()
 mirror(m::TriMesh) = get!(() -> Dict{Symbol,Any}(), _mirror, m)
@@ -610,6 +631,7 @@ function index_convert(a::HipArray{R}; base::Integer = 1, clamp_pad::Bool = fals
 end
 faces_padded_dev(m) = get!(() -> index_upload(get_faces_padded(m); clamp_pad = true, limit = m.V), mirror(m), :faces_padded)
 faces_len_dev(m) = get!(() -> hip(Int32.(m._faces_len)), mirror(m), :faces_len)
+verts_len_dev(m) = get!(() -> hip(Int32.(m._verts_len)), mirror(m), :verts_len)   # every vertex, also those no face uses
 faces_packed_dev(m) = get!(() -> index_upload(get_faces_packed(m); limit = sum(m._verts_len)), mirror(m), :faces_packed)
 edges_dev(m) = get!(() -> index_upload(get_edges_packed(m); limit = sum(m._verts_len)), mirror(m), :edges)          # (E,2) column-major
 # vertex -> (face, corner) table of the padded batch (fx3d_build_vertex_faces): what the ordered -- atomic-free, bit-reproducible --

@@ -383,7 +383,7 @@ class TriMesh:
 
     # ---- device mirrors of the integer data ---------------------------------------------------------
     def dev(self, name):
-        """Cached device copies: faces_packed / faces_padded / faces_len (int32 0-based), edges
+        """Cached device copies: faces_packed / faces_padded / faces_len / nverts (int32 0-based), edges
         (E,2) int32 0-based, lap_rowptr / lap_colind / lap_vals, and verts_* float32."""
         store = self._dev if name.startswith("verts") else self._topo_dev
         if name in store:
@@ -399,6 +399,8 @@ class TriMesh:
             arr = index_upload(self.get_faces_padded(), b, clamp_pad=True, limit=int(self.V))
         elif name == "faces_len":
             arr = DeviceArray.from_host(self._faces_len.astype(np.int32))
+        elif name == "nverts":  # per-mesh vertex counts (B) int32 (not "verts_len": names starting with "verts" are vertex mirrors)
+            arr = DeviceArray.from_host(self._verts_len.astype(np.int32))
         elif name == "edges":
             arr = index_upload(self.get_edges_packed(), b, limit=int(np.sum(self._verts_len)))
         elif name in ("vf_rowptr", "vf_ent"):  # vertex -> (face, corner) table of the ordered sampling adjoint (padded batch)

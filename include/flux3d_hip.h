@@ -517,6 +517,21 @@ FX3D_API fx3d_status fx3d_voxel_workspace_bytes(int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_pointcloud_to_voxel(const float *points, int32_t N, int32_t B, int32_t res,
                                               float *voxels, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- trimesh_to_voxel (src/conversions.jl:133-207) -------------------------------------------------
+ * Padded meshes (the sampler's convention): verts_padded (3,Vmax,B) Float32, verts_len (B) int32 (every vertex counts,
+ * also those no face uses), faces_padded (3,Fmax,B) int32 0-based mesh-local, faces_len (B) int32 -- all device.
+ * voxels (res,res,res,B) Float32 0/1, overwritten: the x coordinate indexes the FIRST dimension (ix + res*(iy + res*iz)),
+ * unlike fx3d_pointcloud_to_voxel.  Bit-identical to the reference's _voxelize (midpoint subdivision until every side^2
+ * <= (1/res)^2, then trunc(p * (res-1))).  A mesh the reference cannot voxelise (zero extent, a NaN / Inf coordinate,
+ * no vertices, a face id outside [0, verts_len)) is COUNTED in *bad_dev (optional, caller-zeroed device counter) and its
+ * grid stays zero.  1 <= res <= 1024.  No host synchronisation (graph-capturable).
+ * ws: fx3d_trimesh_voxel_workspace_bytes(Vmax, Fmax, B, res). */
+FX3D_API fx3d_status fx3d_trimesh_voxel_workspace_bytes(int32_t Vmax, int32_t Fmax, int32_t B, int32_t res, size_t *bytes);
+FX3D_API fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vmax, const int32_t *verts_len,
+                                           const int32_t *faces_padded, int32_t Fmax, const int32_t *faces_len,
+                                           int32_t B, int32_t res, float *voxels, uint32_t *bad_dev,
+                                           void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 /* The loss in the REFERENCE's own arithmetic, from the forward's NN indices: `mean((A .- B[:, nn]).^2) * 3.0f0` with
  * Base's Float32 pairwise sum (blocks of 1024, the materialised (D,N,B) array in column-major order;
  * src/metrics/pcloud.jl:47-50) -- bit for bit oracle/flux3d_oracle.c: fx3d_oracle_chamfer_loss_pairwise.  fx3d_chamfer_fwd
