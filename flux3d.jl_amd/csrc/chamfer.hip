@@ -1963,12 +1963,14 @@ __global__ __launch_bounds__(kTyThreads) void nn1_tiny_kernel(Nn1Params p) {
 
 // Generic dimension (D == 1 or D > 3): one thread per query, candidates read through L1/L2.
 // Correct for any D; not the tuned path (the chamfer configs are all D = 3).
+// 1-D grid of p.tiles blocks per cloud: 2B clouds on the grid's y dimension would stop at maxGridSize[1] = 65536
+// (B = 32768), which check_shapes does not bound.
 __global__ __launch_bounds__(kThreads) void nn1_generic_kernel(Nn1Params p, int D) {
-    const int c = blockIdx.y;
+    const int c = blockIdx.x / p.tiles;
     const int dir = c >= p.B ? 1 : 0;
     const int b = dir ? c - p.B : c;
     const int NQ = dir ? p.M : p.N, NC = dir ? p.N : p.M;
-    const int tile = blockIdx.x;
+    const int tile = blockIdx.x - c * p.tiles;
     const float *__restrict__ qb = (dir ? p.y : p.x) + (size_t)b * NQ * D;
     const float *__restrict__ cb = (dir ? p.x : p.y) + (size_t)b * NC * D;
     const int i = tile * kThreads + threadIdx.x;
@@ -2077,6 +2079,17 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
     const int maxc0 = N > M ? N : M;
     const int clouds8 = (2 * B + 7) / 8;
     pl.nsplit = 1;
+    if (D != 2 && D != 3) {
+        // nn1_generic_kernel: one query per thread, 256-query tiles, no LDS staging
+        pl.R = 1;
+        pl.tiles_x = (N + kThreads - 1) / kThreads;
+        pl.tiles_y = (M + kThreads - 1) / kThreads;
+        pl.tiles = pl.tiles_x > pl.tiles_y ? pl.tiles_x : pl.tiles_y;
+        pl.chunk = 0;
+        pl.lds_bytes = 0;
+        pl.grid = 2 * B * pl.tiles;  // (< 2^30: check_shapes)
+        return pl;
+    }
     if (pl.variant == 3 && 2ll * B * (long long)N * M <= 1000000ll * opt(OPT_NN1_TINY_MPAIRS)) {
         // small problem: the exact kernel without statistics / image (C1, the reference harness's n <= 1024).  Two queries per
         // lane once 16-query blocks would be more than two rounds of the chip
@@ -2105,7 +2118,7 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
         int chunk = (maxc0 + kTile - 1) / kTile * kTile;
         if (chunk > kChunkMax) chunk = kChunkMax;
         pl.chunk = chunk;
-        pl.lds_bytes = (size_t)chunk * (D <= 3 ? D : 0) * sizeof(float);
+        pl.lds_bytes = (size_t)chunk * D * sizeof(float);
         pl.grid = clouds8 * 8 * pl.tiles;
         return pl;
     }
@@ -2299,22 +2312,15 @@ fx3d_status run_nn1(const float *x, int N, const float *y, int M, int B, int D, 
     ProfileScope prof("nn1", st);
     if (D == 3) return want_idx ? launch_small<3, true>(p, pl, st) : launch_small<3, false>(p, pl, st);
     if (D == 2) return want_idx ? launch_small<2, true>(p, pl, st) : launch_small<2, false>(p, pl, st);
-    // generic D: tiles are 256 queries per block
-    Nn1Params g = p;
-    g.tiles_x = (N + kThreads - 1) / kThreads;
-    g.tiles_y = (M + kThreads - 1) / kThreads;
-    g.tiles = g.tiles_x > g.tiles_y ? g.tiles_x : g.tiles_y;
-    hipLaunchKernelGGL(nn1_generic_kernel, dim3(g.tiles, 2 * B), dim3(kThreads), 0, st, g, D);
+    hipLaunchKernelGGL(nn1_generic_kernel, dim3(pl.grid), dim3(kThreads), 0, st, p, D);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
 
-// tiles used for the partial-sum layout (generic path uses 256-query tiles)
-void partial_layout(const Plan &pl, int N, int M, int D, int *tiles, int *tx, int *ty) {
-    if (D == 2 || D == 3) { *tiles = pl.tiles; *tx = pl.tiles_x; *ty = pl.tiles_y; return; }
-    *tx = (N + kThreads - 1) / kThreads;
-    *ty = (M + kThreads - 1) / kThreads;
-    *tiles = *tx > *ty ? *tx : *ty;
+// the kernel a plan launches (fx3d_nn1_plan_describe)
+const char *plan_kernel_name(const Plan &pl, int D) {
+    if (D != 2 && D != 3) return "generic";
+    return pl.variant == 3 ? "f16" : pl.variant == 4 ? "tiny" : "small_d";
 }
 
 }  // namespace
@@ -2406,8 +2412,9 @@ fx3d_status fx3d_nn1_plan_describe(int32_t N, int32_t M, int32_t B, int32_t D, c
     FX3D_REQUIRE(buf && n > 0, "fx3d_nn1_plan_describe: null buffer");
     FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0, "fx3d_nn1_plan_describe: empty problem");
     const Plan pl = make_plan(N, M, B, D);
-    snprintf(buf, n, "variant=%d threads=%d chunk=%d nsplit=%d tpb=%d tpb_y=%d tiles_x=%d tiles_y=%d grid=%d tail=%d lds=%zu",
-             pl.variant, pl.threads, pl.chunk, pl.nsplit, pl.tpb, pl.tpb_y, pl.tiles_x, pl.tiles_y, pl.grid, pl.tail, pl.lds_bytes);
+    snprintf(buf, n, "variant=%d threads=%d chunk=%d nsplit=%d tpb=%d tpb_y=%d tiles_x=%d tiles_y=%d grid=%d tail=%d lds=%zu R=%d kernel=%s",
+             pl.variant, pl.threads, pl.chunk, pl.nsplit, pl.tpb, pl.tpb_y, pl.tiles_x, pl.tiles_y, pl.grid, pl.tail, pl.lds_bytes, pl.R,
+             plan_kernel_name(pl, D));
     return FX3D_OK;
 }
 
@@ -2415,9 +2422,7 @@ fx3d_status fx3d_chamfer_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_
     FX3D_REQUIRE(bytes, "fx3d_chamfer_workspace_bytes: null output");
     FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0, "fx3d_chamfer_workspace_bytes: empty input");
     const Plan pl = make_plan(N, M, B, D);
-    int tiles, tx, ty;
-    partial_layout(pl, N, M, D, &tiles, &tx, &ty);
-    *bytes = ((size_t)2 * B * tiles + 2) * sizeof(double);
+    *bytes = ((size_t)2 * B * pl.tiles + 2) * sizeof(double);
     if (const size_t ps = prune_scratch_bytes(pl, N, M, D)) *bytes = ((*bytes + 255) & ~(size_t)255) + ps;  // (a smaller workspace still runs: without pruning)
     if (pl.nsplit > 1) {  // split run: 256-query finalize tiles + the per-query merge slots
         const int maxq = N > M ? N : M;
@@ -2443,8 +2448,7 @@ static fx3d_status chamfer_common(const float *x, int N, const float *y, int M, 
     fx3d_status rc = check_shapes(fn, x, N, y, M, B, D);
     if (rc) return rc;
     const Plan pl = make_plan(N, M, B, D);
-    int tiles, tx, ty;
-    partial_layout(pl, N, M, D, &tiles, &tx, &ty);
+    const int tiles = pl.tiles, tx = pl.tiles_x, ty = pl.tiles_y;
     size_t need = ((size_t)2 * B * tiles + 2) * sizeof(double);
     const int maxq = N > M ? N : M;
     const int tiles_f = (maxq + kThreads - 1) / kThreads;

@@ -254,6 +254,45 @@ def test_option_api_without_a_gpu(fx):
                 assert name in known, f"{os.path.basename(path)} cites option {name}, which the library does not have"
 
 
+def test_exact_nn1_plan_without_a_gpu(fx):
+    """make_plan for the exact loop (D = 2, D = 3 under nn1_variant = 0) and for generic D queries no device: R by the total
+    query count B (N + M) (4 from 524 288, 2 from 262 144), one LDS chunk of the larger cloud rounded up to 32 candidates and at
+    most 4096, 256 R-query tiles, a grid of 8-cloud slots; the generic kernel's 256-query tiles on a 1-D grid.  Also the
+    shapes tests/test_gpu_exact_nn1.py claims."""
+    from flux3d_jl_amd import _lib
+    from test_gpu_exact_nn1 import EXACT_SHAPES, GENERIC_DIMS, GENERIC_SHAPES, assert_exact_plan, assert_generic_plan, plan_of
+
+    def exact(N, M, B, D=2):
+        p = plan_of(N, M, B, D)
+        assert p["kernel"] == "small_d" and p["variant"] == "0" and p["lds"] == str(int(p["chunk"]) * D * 4), p
+        return int(p["R"]), int(p["chunk"]), int(p["tiles_x"]), int(p["tiles_y"]), int(p["grid"])
+
+    assert exact(1, 262142, 1)[0] == 1 and exact(2, 262142, 1)[0] == 2                     # 262 143 / 262 144 queries
+    assert exact(128, 1919, 256)[0] == 2 and exact(128, 1920, 256)[0] == 4                  # 524 032 / 524 288
+    assert exact(1024, 1024, 256) == (4, 1024, 1, 1, 512)
+    assert exact(1024, 1024, 128) == (2, 1024, 2, 2, 512)
+    assert exact(600, 9000, 56) == (4, 4096, 1, 9, 14 * 8 * 9)
+    assert exact(300, 411, 3) == (1, 416, 2, 2, 8 * 2)                                    # chunk: 411 rounded up to 32
+    assert exact(4096, 100, 1)[1] == 4096 and exact(4097, 100, 1)[1] == 4096 and exact(31, 33, 1)[1] == 64
+    assert exact(257, 1, 1)[2:4] == (2, 1) and exact(1, 256, 1)[2:4] == (1, 1)
+    with _lib.option("nn1_variant", 0):
+        assert exact(1024, 1024, 256, 3) == (4, 1024, 1, 1, 512)
+        for (N, M, B) in EXACT_SHAPES:
+            assert_exact_plan(N, M, B, 3)
+    for (N, M, B) in EXACT_SHAPES:
+        assert_exact_plan(N, M, B, 2)
+    for D in GENERIC_DIMS:
+        for (N, M, B) in GENERIC_SHAPES:
+            assert_generic_plan(N, M, B, D)
+        p = plan_of(2000, 2000, 64, D)
+        assert (p["tiles_x"], p["tiles_y"], p["grid"], p["chunk"], p["lds"]) == ("8", "8", "1024", "0", "0"), p
+    assert_generic_plan(4, 4, 40000, 5)                                                   # 80 000 blocks on the grid's x
+    assert plan_of(256, 257, 1, 4)["tiles_y"] == "2" and plan_of(256, 257, 1, 4)["tiles_x"] == "1"
+    # (the keys before R= keep their places: tools/nn1_plan_sweep.py reads fields 2 .. 8 of the line)
+    assert list(plan_of(1024, 1024, 8, 2)) == ["variant", "threads", "chunk", "nsplit", "tpb", "tpb_y", "tiles_x", "tiles_y", "grid",
+                                               "tail", "lds", "R", "kernel"]
+
+
 def test_knn_scratch_plan_without_a_gpu(fx):
     """fx3d_knn_workspace_bytes is a function of the shape, the CU count (256 when no device is visible) and the options: zero for the
     BASELINE D = 3 shape, the pre-pass slabs for C4', slice lists for few clouds with many rows, slices + flags + the interleaved copy
