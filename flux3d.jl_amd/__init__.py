@@ -15,7 +15,7 @@ _lib.load()  # fail loudly (ImportError) if the HIP library has not been built
 from ._lib import Flux3DHipError, LIB_PATH  # noqa: E402
 from .device import (DeviceArray, Event, Graph, Stream, cpu, current_stream, device_count, device_identity,  # noqa: E402
                      device_name, empty_cache, functional, gpu, set_device, stream, synchronize)
-from .rep import (PointCloud, TriMesh, get_edges_packed, get_edges_to_key, get_faces_list,  # noqa: E402
+from .rep import (PointCloud, TriMesh, VoxelGrid, get_edges_packed, get_edges_to_key, get_faces_list,  # noqa: E402
                   get_faces_packed, get_faces_padded, get_faces_to_edges_packed,
                   get_laplacian_packed, get_verts_list, get_verts_packed, get_verts_padded,
                   load_obj, load_off, load_trimesh, npoints)
@@ -27,7 +27,8 @@ from .transforms import (EPS, compute_faces_areas_list, compute_faces_areas_pack
 from .fit import FitStepGraph, Momentum, loss_dolphin  # noqa: E402
 from .graph import (create_knn_graph, edge_features, edge_features_grad, edgeconv_graph, knn,  # noqa: E402
                     knn_gather)
-from .conversions import pointcloud_to_voxel, trimesh_to_voxel  # noqa: E402
+from .conversions import (pointcloud_from_voxels, pointcloud_to_voxel, trimesh_from_pointcloud,  # noqa: E402
+                          trimesh_from_voxels, trimesh_to_voxel, voxel_to_trimesh)
 from . import synth  # noqa: E402
 
 use_hip = [functional()]  # the `Flux3D.use_cuda[]` analogue (src/Flux3D.jl:52-61)

@@ -122,6 +122,9 @@ SIGNATURES = {
     "fx3d_pointcloud_to_voxel": [vp, c_i32, c_i32, c_i32, vp, vp, sz, vp],
     "fx3d_trimesh_voxel_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_trimesh_to_voxel": [vp, c_i32, vp, vp, c_i32, vp, c_i32, c_i32, vp, vp, vp, sz, vp],
+    "fx3d_voxel_mesh_workspace_bytes": [c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_voxel_mesh_count": [vp, c_i32, c_i32, c_f32, vp, vp, vp, sz, vp],
+    "fx3d_voxel_mesh_emit": [c_i32, c_i32, c_i64, vp, vp, c_i32, vp, sz, vp],
     "fx3d_lincomb": [c_i64, c_f32, vp, c_f32, vp, c_f32, vp, vp, vp],
     "fx3d_momentum_step": [c_i64, c_f32, c_f32, vp, vp, vp, vp],
     "fx3d_momentum_step_offset": [c_i64, c_f32, c_f32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp],

@@ -27,11 +27,13 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  get_faces_list, get_edges_packed, get_laplacian_packed,
                  compute_faces_areas_packed, compute_faces_areas_padded,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
-                 _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel
+                 _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel,
+                 voxel_to_trimesh, VoxelGrid
 using SparseArrays: SparseMatrixCSC, findnz
 import Zygote
 
 export HipArray, hip, unhip, use_hip, knn_graph, edgeconv_graph, pointcloud_to_voxel
+export trimesh_from_voxels, pointcloud_from_voxels
 
 const LIB = get(ENV, "FLUX3D_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libflux3d_hip.so"))
 const Stream = Ptr{Cvoid}
@@ -594,6 +596,49 @@ function trimesh_to_voxel(m::TriMesh{Float32,R,HipArray}, res::Int = 32) where {
     nbad == 0 || throw(ArgumentError("trimesh_to_voxel: $nbad of $(m.N) meshes have zero extent or a non-finite coordinate"))
     return vox
 end
+
+# voxel_to_trimesh (src/conversions.jl:209-232) for HipArray grids with algo :Exact (_voxel_exact, :246-349): the surface
+# cubes of every grid, vertices bit-identical to the reference's (v ./ maximum(v)) and left on the device, faces the
+# reference's UInt32 1-based host arrays (a pure function of the cube count).  The reference's own TriMesh(v::VoxelGrid),
+# PointCloud(v::VoxelGrid, n), TriMesh(p::PointCloud, res) and the VoxelGridTo* transforms call it, so they run on the
+# device for a HipArray grid.  A grid with an element outside [0, 1] or NaN, or without a surviving cell, throws as the
+# reference does.  Host grids and the Meshing.jl algos go to the reference's method on a host copy.  One host
+# synchronisation per call (the B cube counts).
+const _CUBE_FACES = UInt32[1, 7, 5, 1, 3, 7, 1, 4, 3, 1, 2, 4, 3, 8, 7, 3, 4, 8, 5, 7, 8, 5, 8, 6, 1, 5, 6, 1, 6, 2, 2, 6, 8, 2, 8, 4]
+cube_faces(K::Integer) = reshape(repeat(_CUBE_FACES, K) .+ UInt32.(8 .* repeat(0:K-1; inner = 36)), 3, :)
+function voxel_to_trimesh(v::VoxelGrid, thresh::Number, algo::Symbol)
+    vox = v.voxels
+    (vox isa HipArray{Float32,4} && algo == :Exact) ||
+        return invoke(voxel_to_trimesh, Tuple{VoxelGrid,Any,Any}, VoxelGrid(unhip(vox)), thresh, algo)
+    res, B = size(vox, 1), size(vox, 4)
+    (size(vox, 2) == res && size(vox, 3) == res) || throw(DimensionMismatch("voxel_to_trimesh: grids must be cubic"))
+    1 <= res <= 1024 || throw(ArgumentError("voxel_to_trimesh: resolution must lie in [1, 1024]"))
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_voxel_mesh_workspace_bytes(res::Int32, B::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[]); counts = HipArray{Int64}(undef, 2B)   # K (B) then the invalid-element counts (B UInt32)
+    check(@ccall LIB.fx3d_voxel_mesh_count(vox.ptr::Ptr{Cvoid}, res::Int32, B::Int32, Float32(thresh)::Float32,
+                                           counts.ptr::Ptr{Cvoid}, (counts.ptr + 8B)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid},
+                                           length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    h = unhip(counts)
+    K, nbad = h[1:B], reinterpret(UInt32, h[B+1:2B])[1:B]
+    i = findfirst(!iszero, nbad)
+    i === nothing || error("invalid VoxelGrid, found element which is not between [0,1] (grid $i)")
+    i = findfirst(iszero, K)
+    i === nothing || throw(ArgumentError("voxel_to_trimesh: grid $i has no surface cell (the reference's maximum of an empty array throws)"))
+    all(8 .* K .< 2^31) || throw(ArgumentError("voxel_to_trimesh: more than 2^31 vertices in one grid"))
+    total = sum(K)
+    packed = HipArray{Float32}(undef, 3, 8total)
+    check(@ccall LIB.fx3d_voxel_mesh_emit(res::Int32, B::Int32, total::Int64, packed.ptr::Ptr{Cvoid}, C_NULL::Ptr{Cvoid},
+                                          0::Int32, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    offs = cumsum([0; K])
+    verts = HipArray{Float32,2}[packed[:, 8offs[b]+1:8offs[b+1]] for b in 1:B]
+    return verts, Array{UInt32,2}[cube_faces(k) for k in K]
+end
+# TriMesh(v::VoxelGrid; thresh, algo) (src/conversions.jl:28-31) and PointCloud(v::VoxelGrid, n; thresh, algo) (:56-67)
+trimesh_from_voxels(v::VoxelGrid; thresh::Number = 0.5f0, algo = :MarchingCubes) =
+    TriMesh(voxel_to_trimesh(v, Float32(thresh), algo)...)
+pointcloud_from_voxels(v::VoxelGrid, npoints::Int = 1000; thresh::Number = 0.5f0, algo = :MarchingCubes) =
+    PointCloud(sample_points(trimesh_from_voxels(v; thresh = thresh, algo = algo), npoints))
 
 # ---- TriMesh device mirrors: int32 0-based copies of the host integer data (cached per mesh) ---
 const _mirror = WeakKeyDict{Any,Dict{Symbol,Any}}()

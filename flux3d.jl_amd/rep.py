@@ -6,6 +6,7 @@
   meshes in list / packed ``(3, sumV)`` / padded ``(3, Vmax, B)`` form with the same lazy validity
   flags; faces are integer and stay on the host in the reference (:87-97) -- here they also get a
   cached int32 0-based device mirror because the kernels gather through them.
+* ``VoxelGrid``    -- src/rep/voxels.jl:21-55: ``voxels`` is ``(N, N, N, B)`` Float32 (a 3-D grid is lifted to B = 1).
 
 Faces keep the reference's 1-based numbering at this level (``index_base=1``), so fixtures copied
 from the reference's tests read the same; the C ABI takes 0-based int32.
@@ -76,6 +77,45 @@ class PointCloud:
 def npoints(p):
     """npoints(p::PointCloud), src/rep/pcloud.jl:84."""
     return p.points.shape[1]
+
+
+class VoxelGrid:
+    """VoxelGrid(voxels) -- src/rep/voxels.jl:21-55: ``voxels`` is ``(N, N, N, B)`` Float32 (column-major, an F-ordered
+    numpy array or a :class:`DeviceArray`); a 3-D array is lifted to ``B = 1``.  Unlike the reference, a grid that is not
+    cubic or not 3-D / 4-D is refused here (every consumer of the reference's grids assumes res^3)."""
+
+    def __init__(self, voxels):
+        if isinstance(voxels, VoxelGrid):
+            voxels = voxels.voxels
+        if is_device(voxels):
+            if voxels.dtype != np.float32:
+                raise TypeError("VoxelGrid device storage must be Float32")
+            v = voxels.reshape(voxels.shape + (1,)) if voxels.ndim == 3 else voxels
+        else:
+            v = _f32(voxels)
+            if v.ndim == 3:  # (N,N,N) -> (N,N,N,1), src/rep/voxels.jl:34-37
+                v = v.reshape(v.shape + (1,), order="F")
+        if v.ndim != 4 or not v.shape[0] == v.shape[1] == v.shape[2]:
+            raise ValueError(f"VoxelGrid needs (N,N,N) or (N,N,N,B) voxels, got shape {tuple(voxels.shape)}")
+        self.voxels = v
+
+    def __getitem__(self, index):  # v[i] -> voxels[:, :, :, i]  (:43), 0-based here
+        vox = self.voxels.to_host() if is_device(self.voxels) else self.voxels
+        return vox[:, :, :, index]
+
+    @property
+    def on_device(self):
+        return is_device(self.voxels)
+
+    def _to_device(self):
+        return self if self.on_device else VoxelGrid(DeviceArray.from_host(self.voxels))
+
+    def _to_host(self):
+        return VoxelGrid(self.voxels.to_host()) if self.on_device else self
+
+    def __repr__(self):
+        return (f"VoxelGrid{{Float32}} Structure:\n    Batch size: {self.voxels.shape[3]}\n"
+                f"    Voxels features: {self.voxels.shape[0]}\n    Storage type: {type(self.voxels).__name__}")
 
 
 # ------------------------------------------------------------------------------------ converters
@@ -213,6 +253,43 @@ class TriMesh:
         self._dev = {}
         if self._device:
             self._dev["verts_packed"] = DeviceArray.from_host(self.get_verts_packed_host())
+
+    @property
+    def _faces_list(self):
+        """Host face lists; a mesh born on the device (:meth:`_from_device`) builds them on first use."""
+        fl = self.__dict__.get("_faces_list_")
+        if fl is None:
+            fl = self.__dict__["_faces_list_"] = self._faces_builder()
+        return fl
+
+    @_faces_list.setter
+    def _faces_list(self, value):
+        self.__dict__["_faces_list_"] = value
+
+    @classmethod
+    def _from_device(cls, verts_packed, verts_len, faces_len, faces_builder, faces_dtype=np.uint32):
+        """A device mesh whose vertices were written by a kernel: ``verts_packed`` (3, sum(verts_len)) Float32 device
+        array becomes the mesh's packed vertices as it is (no host round trip).  ``faces_builder()`` returns the host face
+        lists (1-based, ``faces_dtype``) when they are first needed."""
+        m = cls.__new__(cls)
+        m._device = True
+        m.R = np.dtype(faces_dtype)
+        m.index_base = 1
+        m._faces_builder = faces_builder
+        m._verts_len = np.asarray(verts_len, dtype=np.int64)
+        m._faces_len = np.asarray(faces_len, dtype=np.int64)
+        m.N = len(m._verts_len)
+        m.V = int(m._verts_len.max())
+        m.F = int(m._faces_len.max())
+        m.equalised = bool(np.all(m._verts_len == m.V) and np.all(m._faces_len == m.F))
+        m.verts_aliased = bool(np.all(m._verts_len == m.V))
+        m.valid = m._faces_len > 0
+        m.offset = -1
+        m._verts_list, m._verts_packed, m._verts_padded = None, None, None
+        m._verts_packed_valid = m._verts_padded_valid = m._verts_list_valid = False
+        m._topo, m._topo_dev = {}, {}
+        m._dev = {"verts_packed": verts_packed}
+        return m
 
     def _topo_prop(name):  # noqa: N805  (attribute backed by the shared topology dict)
         return property(lambda self: self._topo.get(name), lambda self, v: self._topo.__setitem__(name, v))

@@ -533,6 +533,27 @@ FX3D_API fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vm
                                            int32_t B, int32_t res, float *voxels, uint32_t *bad_dev,
                                            void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- voxel_to_trimesh with algo :Exact (src/conversions.jl:209-232, 246-349) --------------------------
+ * Two phases, because the output size depends on the data.  voxels (res,res,res,B) Float32 device, the first dimension
+ * is x (the reference's CartesianIndices order).  1 <= res <= 1024.
+ * fx3d_voxel_mesh_count: binarises `v >= thresh` (thresh is the reference's Float32(thresh)), clears interior cells
+ *   (res >= 3: all six face neighbours set in the un-eroded grid, indices in 2:res-1) and counts the survivors.
+ *   cubes_dev (B) int64: K of every grid.  bad_dev (B) uint32: elements outside [0, 1] or NaN per grid (the reference
+ *   throws for a grid with any, and for K = 0).  Both are overwritten.  The workspace keeps what fx3d_voxel_mesh_emit needs.
+ * fx3d_voxel_mesh_emit: consumes the workspace of the last fx3d_voxel_mesh_count with the same res and B (same stream).
+ *   verts_packed (3, 8*sum K) Float32: grid after grid, cube after cube in column-major cell order, the reference's 8
+ *   vertices of each cube divided by the grid's largest coordinate (a correctly rounded Float32 division).
+ *   max_cubes: capacity of verts_packed in cubes (24 floats each); cubes beyond it are not written.
+ *   faces_padded (3,Fmax,B) int32 0-based mesh-local, optional (NULL: none): cube j of a grid gets the reference's 12
+ *   faces + 8j; entries behind a grid's 12 K faces are 0.  A grid with 12 K > Fmax gets no faces.  8 K must stay below
+ *   2^31 (int32 face ids).  No entry point synchronises the host.  ws: fx3d_voxel_mesh_workspace_bytes(res, B). */
+FX3D_API fx3d_status fx3d_voxel_mesh_workspace_bytes(int32_t res, int32_t B, size_t *bytes);
+FX3D_API fx3d_status fx3d_voxel_mesh_count(const float *voxels, int32_t res, int32_t B, float thresh, int64_t *cubes_dev,
+                                           uint32_t *bad_dev, void *ws, size_t ws_bytes, fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_voxel_mesh_emit(int32_t res, int32_t B, int64_t max_cubes, float *verts_packed,
+                                          int32_t *faces_padded, int32_t Fmax, void *ws, size_t ws_bytes,
+                                          fx3d_stream_t s);
+
 /* The loss in the REFERENCE's own arithmetic, from the forward's NN indices: `mean((A .- B[:, nn]).^2) * 3.0f0` with
  * Base's Float32 pairwise sum (blocks of 1024, the materialised (D,N,B) array in column-major order;
  * src/metrics/pcloud.jl:47-50) -- bit for bit oracle/flux3d_oracle.c: fx3d_oracle_chamfer_loss_pairwise.  fx3d_chamfer_fwd
