@@ -24,6 +24,9 @@ from .metrics import (chamfer_distance, chamfer_distance_grad, chamfer_loss_pair
                       sampling_adjoint_is_ordered)
 from .transforms import (EPS, compute_faces_areas_list, compute_faces_areas_packed,  # noqa: E402
                          compute_faces_areas_padded, lincomb, offset, sample_points, sample_points_grad, sample_points_pair)
+from .normals import (compute_faces_normals_grad, compute_faces_normals_list, compute_faces_normals_packed,  # noqa: E402
+                      compute_faces_normals_padded, compute_verts_normals_grad, compute_verts_normals_list,
+                      compute_verts_normals_packed, compute_verts_normals_padded)
 from .fit import FitStepGraph, Momentum, loss_dolphin  # noqa: E402
 from .graph import (create_knn_graph, edge_features, edge_features_grad, edgeconv_graph, knn,  # noqa: E402
                     knn_gather)

@@ -104,6 +104,11 @@ SIGNATURES = {
     "fx3d_index_upload": [vp, c_i32, c_i32, c_i64, c_i32, c_i64, vp, vp, vp, sz, vp],
     "fx3d_faces_areas_packed": [vp, c_i64, vp, c_i64, vp, vp],
     "fx3d_faces_areas_padded": [vp, c_i32, vp, c_i32, vp, c_i32, vp, vp],
+    "fx3d_normals_workspace_bytes": [c_i64, c_i64, C.POINTER(sz)],
+    "fx3d_verts_normals_packed": [vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp],
+    "fx3d_verts_normals_bwd": [vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp, c_i32, vp, sz, vp],
+    "fx3d_faces_normals_packed": [vp, c_i64, vp, c_i64, vp, vp],
+    "fx3d_faces_normals_bwd": [vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i32, vp, sz, vp],
     "fx3d_sample_points_explicit": [vp, c_i32, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp],
     "fx3d_sample_points_workspace_bytes": [c_i32, c_i32, C.POINTER(sz)],
     "fx3d_sample_points": [vp, c_i32, vp, c_i32, vp, c_i32, c_i32, c_f64, c_u64, vp, vp, vp, vp,

@@ -26,6 +26,7 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  get_verts_packed, get_verts_padded, get_verts_list, get_faces_packed, get_faces_padded,
                  get_faces_list, get_edges_packed, get_laplacian_packed,
                  compute_faces_areas_packed, compute_faces_areas_padded,
+                 compute_verts_normals_packed, compute_faces_normals_packed,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
                  _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel,
                  voxel_to_trimesh, VoxelGrid
@@ -691,6 +692,17 @@ function vertex_faces_dev(m)
         (hip(rowptr), hip(ent))
     end
 end
+# the same table over the PACKED faces (B = 1, Vmax = sum V, Fmax = sum F): what the normals' kernels walk
+function vertex_faces_packed_dev(m)
+    get!(mirror(m), :vertex_faces_packed) do
+        fp = Int32.(Int64.(get_faces_packed(m)) .- 1)                   # (3, sum F) 0-based global ids
+        V = Int(sum(m._verts_len)); F = size(fp, 2)
+        rowptr = Vector{Int32}(undef, V + 1); ent = Vector{Int32}(undef, 3 * F)
+        check(@ccall LIB.fx3d_build_vertex_faces(fp::Ptr{Int32}, Int32[F]::Ptr{Int32}, V::Int32, F::Int32, 1::Int32,
+                                                 rowptr::Ptr{Int32}, ent::Ptr{Int32})::Int32)
+        (hip(rowptr), hip(ent))
+    end
+end
 function laplacian_csr_dev(m)
     get!(mirror(m), :lap) do
         # CSR of L == CSC of L' ; build from the reference's own cached SparseMatrixCSC (src/rep/mesh.jl:559-565)
@@ -1221,6 +1233,62 @@ function compute_faces_areas_padded(m::TriMesh{Float32,R,HipArray}; eps::Number 
                                              faces_len_dev(m).ptr::Ptr{Cvoid}, m.N::Int32, out.ptr::Ptr{Cvoid},
                                              DEFAULT_STREAM::Stream)::Int32)
     return out
+end
+# compute_verts_normals_packed / compute_faces_normals_packed (src/rep/mesh.jl:589-621, 689-699) on HipArray meshes, with their
+# adjoints w.r.t. the packed vertices.  The vertex normals are the reference's CPU result -- per corner row, the cross product of
+# the LAST face holding the vertex there (`A[:, I] = A[:, I] + X` with repeated I) -- bit for bit, not the documented area-weighted
+# sum (include/flux3d_hip.h).  The padded and list forms (:640-670, :719-746) are the reference's own code over these methods
+# (_packed_to_padded / _packed_to_list above, with the _packed_to_padded adjoint).
+function verts_normals_dev(m::TriMesh{Float32,R,HipArray}, mask) where {R}
+    verts = get_verts_packed(m)::HipArray{Float32,2}; faces = faces_packed_dev(m); rowptr, ent = vertex_faces_packed_dev(m)
+    out = HipArray{Float32}(undef, size(verts)...)
+    check(@ccall LIB.fx3d_verts_normals_packed(verts.ptr::Ptr{Cvoid}, size(verts, 2)::Int64, faces.ptr::Ptr{Cvoid},
+                                               size(faces, 2)::Int64, rowptr.ptr::Ptr{Cvoid}, ent.ptr::Ptr{Cvoid},
+                                               out.ptr::Ptr{Cvoid}, (mask === nothing ? C_NULL : mask.ptr)::Ptr{Cvoid},
+                                               DEFAULT_STREAM::Stream)::Int32)
+    return out
+end
+compute_verts_normals_packed(m::TriMesh{Float32,R,HipArray}) where {R} = verts_normals_dev(m, nothing)
+function normals_workspace(V::Integer, F::Integer)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_normals_workspace_bytes(Int64(V)::Int64, Int64(F)::Int64, nb::Ref{Csize_t})::Int32)
+    return workspace(nb[])
+end
+Zygote.@adjoint function compute_verts_normals_packed(m::TriMesh{Float32,R,HipArray}) where {R}
+    mask = HipArray{UInt8}(undef, 3, size(faces_packed_dev(m), 2))   # (f, r) wins for its vertex: written whole by the forward
+    out = verts_normals_dev(m, mask)
+    function back(g)
+        verts = get_verts_packed(m)::HipArray{Float32,2}; faces = faces_packed_dev(m); rowptr, ent = vertex_faces_packed_dev(m)
+        gv = HipArray{Float32}(undef, size(verts)...)
+        ws = normals_workspace(size(verts, 2), size(faces, 2))
+        check(@ccall LIB.fx3d_verts_normals_bwd(verts.ptr::Ptr{Cvoid}, size(verts, 2)::Int64, faces.ptr::Ptr{Cvoid},
+                                                size(faces, 2)::Int64, rowptr.ptr::Ptr{Cvoid}, ent.ptr::Ptr{Cvoid},
+                                                mask.ptr::Ptr{Cvoid}, hip(g).ptr::Ptr{Cvoid}, gv.ptr::Ptr{Cvoid}, 0::Int32,
+                                                ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+        return ((_verts_packed = gv,),)
+    end
+    return out, back
+end
+function compute_faces_normals_packed(m::TriMesh{Float32,R,HipArray}) where {R}
+    verts = get_verts_packed(m)::HipArray{Float32,2}; faces = faces_packed_dev(m)
+    out = HipArray{Float32}(undef, 3, size(faces, 2))
+    check(@ccall LIB.fx3d_faces_normals_packed(verts.ptr::Ptr{Cvoid}, size(verts, 2)::Int64, faces.ptr::Ptr{Cvoid},
+                                               size(faces, 2)::Int64, out.ptr::Ptr{Cvoid}, DEFAULT_STREAM::Stream)::Int32)
+    return out
+end
+Zygote.@adjoint function compute_faces_normals_packed(m::TriMesh{Float32,R,HipArray}) where {R}
+    out = compute_faces_normals_packed(m)
+    function back(g)
+        verts = get_verts_packed(m)::HipArray{Float32,2}; faces = faces_packed_dev(m); rowptr, ent = vertex_faces_packed_dev(m)
+        gv = HipArray{Float32}(undef, size(verts)...)
+        ws = normals_workspace(size(verts, 2), size(faces, 2))
+        check(@ccall LIB.fx3d_faces_normals_bwd(verts.ptr::Ptr{Cvoid}, size(verts, 2)::Int64, faces.ptr::Ptr{Cvoid},
+                                                size(faces, 2)::Int64, rowptr.ptr::Ptr{Cvoid}, ent.ptr::Ptr{Cvoid},
+                                                hip(g).ptr::Ptr{Cvoid}, gv.ptr::Ptr{Cvoid}, 0::Int32, ws.ptr::Ptr{Cvoid},
+                                                length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+        return ((_verts_packed = gv,),)
+    end
+    return out, back
 end
 # _sample_points for given draws (src/transforms/mesh_func.jl:60-82): face_idx (n,B) Int32 0-based, r1, r2 (n,B)
 function sample_points_explicit(m::TriMesh{Float32,R,HipArray}, verts::HipArray{Float32,3}, face_idx::HipArray{Int32,2},

@@ -107,6 +107,25 @@ end
         @test gradient(x -> chamfer_distance(x, x), dm) isa Tuple
     end
 
+    @testset "normals (test/rep.jl:224-330): the CPU method's result, bit for bit, and its adjoint" begin
+        m = load_trimesh(joinpath(ASSETS, "teapot.obj"), joinpath(ASSETS, "sphere.obj"))
+        dm = hip(m)
+        for f in (Flux3D.compute_verts_normals_packed, Flux3D.compute_faces_normals_packed)
+            n = f(dm)
+            @test n isa HipArray{Float32,2}
+            @test reinterpret(UInt32, unhip(n)) == reinterpret(UInt32, f(m))   # last write wins on the CPU; same on the device
+            @test unhip(f(dm)) == unhip(n)
+        end
+        for f in (Flux3D.compute_verts_normals_padded, Flux3D.compute_faces_normals_padded)
+            @test unhip(f(dm)) == f(m)
+        end
+        for f in (Flux3D.compute_verts_normals_list, Flux3D.compute_faces_normals_list)
+            @test unhip.(f(dm)) == f(m)
+        end
+        @test gradient(x -> sum(Flux3D.compute_verts_normals_packed(x)), dm) isa Tuple
+        @test gradient(x -> sum(Flux3D.compute_faces_normals_packed(x)), dm) isa Tuple
+    end
+
     @testset "the tutorial's iteration in five launches (examples/fit_mesh.jl:78-110): passengers = separate calls, bit for bit" begin
         src = hip(load_trimesh(joinpath(ASSETS, "sphere.obj"))); tgt = hip(load_trimesh(joinpath(ASSETS, "teapot.obj")))
         nv = size(get_verts_packed(src), 2)

@@ -461,7 +461,8 @@ class TriMesh:
     # ---- device mirrors of the integer data ---------------------------------------------------------
     def dev(self, name):
         """Cached device copies: faces_packed / faces_padded / faces_len / nverts (int32 0-based), edges
-        (E,2) int32 0-based, lap_rowptr / lap_colind / lap_vals, and verts_* float32."""
+        (E,2) int32 0-based, lap_rowptr / lap_colind / lap_vals, the vertex -> (face, corner) tables vf_rowptr / vf_ent
+        (padded batch) and vf_packed_rowptr / vf_packed_ent (packed faces), and verts_* float32."""
         store = self._dev if name.startswith("verts") else self._topo_dev
         if name in store:
             return store[name]
@@ -491,6 +492,16 @@ class TriMesh:
                       rowptr.ctypes.data, ent.ctypes.data)
             store["vf_rowptr"] = DeviceArray.from_host(rowptr)
             store["vf_ent"] = DeviceArray.from_host(ent)
+            return store[name]
+        elif name in ("vf_packed_rowptr", "vf_packed_ent"):  # the same table over the PACKED faces, for the normals
+            fp = np.asfortranarray(self.get_faces_packed().astype(np.int64) - b).astype(np.int32)  # one mesh, sum V / sum F
+            V, F = int(np.sum(self._verts_len)), fp.shape[1]
+            rowptr = np.zeros(V + 1, np.int32)
+            ent = np.zeros(3 * F, np.int32)
+            fl = np.array([F], np.int32)
+            _lib.call("fx3d_build_vertex_faces", fp.ctypes.data, fl.ctypes.data, V, F, 1, rowptr.ctypes.data, ent.ctypes.data)
+            store["vf_packed_rowptr"] = DeviceArray.from_host(rowptr)
+            store["vf_packed_ent"] = DeviceArray.from_host(ent)
             return store[name]
         elif name in ("lap_rowptr", "lap_colind", "lap_vals"):
             rowptr, colind, vals = self.get_laplacian_packed()

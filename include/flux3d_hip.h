@@ -345,6 +345,50 @@ FX3D_API fx3d_status fx3d_faces_areas_padded(const float *verts_padded, int32_t 
                                              const int32_t *faces_len, int32_t B, float *areas,
                                              fx3d_stream_t s);
 
+/* ---- vertex and face normals (src/rep/mesh.jl:589-621, 689-699) and their adjoints w.r.t. verts_packed ----------------
+ * verts (3,V) packed, faces (3,F) packed global 0-based ids (V = sum V_i, F = sum F_i).  vf_rowptr (V+1) / vf_ent (3F): device
+ * copies of fx3d_build_vertex_faces' tables of the PACKED faces (B = 1, Vmax = V, Fmax = F): entries face * 4 + corner,
+ * ascending per vertex.  c_r(f) = _lg_cross(p[r+1] - p[r], p[r+2] - p[r]) over face f's corners p[0..2], taken cyclically
+ * (r = 0: the operand order of the face areas).  All arithmetic is unfused Float32.
+ * Definition (what the reference computes on the CPU, not what its docstring says): each of the three statements
+ * `vertex_normals[:, faces[r, :]] += c_r` lowers to `A[:, I] = A[:, I] + X`, which is LAST WRITE WINS when I repeats a vertex.
+ * So the raw normal of vertex v is ((+0 + c_0(w_0)) + c_1(w_1)) + c_2(w_2), where w_r is the highest-numbered face whose
+ * corner r is v and a term is skipped when v is never corner r -- not a sum over all adjacent faces.  It then goes through
+ * _normalize (src/rep/utils.jl:23-29): n = raw ./ max(s, 1f-6), s = sqrt((x*x + y*y) + z*z), where Julia's max returns NaN for
+ * a NaN s.  Vertices in no face and degenerate faces give 0; -0 components become +0 for vertex normals (the +0 start) and stay
+ * -0 for face normals, which are _normalize(c_0(f)).  Results are the same bits on every run and for every launch grid.
+ * Adjoints: the exact derivative of the forward AS COMPUTED (the winners are fixed by the topology).  Per normal (vertex, or
+ * face), g_raw = (g - n * ((n.x*g.x + n.y*g.y) + n.z*g.z)) / s  (component-wise: g.x - (n.x * dot), then / s)  when s > 1f-6,
+ * otherwise (eps is the max, or s is NaN) g / 1f-6.  Then vertex u walks its table entries (f, t) in ascending order and, for
+ * r = 0, 1, 2 whose role counts -- (f, r) is its owner's winner (vertex normals), r = 0 (face normals) -- adds corner t's term
+ * of c_r(f)'s Jacobian transpose at g_raw of the role's owner (vertex faces[r, f] / face f): with a = p[r+1] - p[r],
+ * b = p[r+2] - p[r], corner r+1 gets cross(b, g), corner r+2 gets cross(g, a), corner r -(cross(b, g) + cross(g, a)),
+ * component by component.  The sum starts from gverts[u] (accumulate != 0) or +0, one term at a time: acc.x = acc.x + term.x.
+ * This is not a claim about what Zygote returns through the reference's Buffer when corner rows repeat.
+ * No float atomics, no memset, no host synchronisation: every launch can be captured into a graph.
+ *
+ * fx3d_verts_normals_packed: normals (3,V).  winner_mask (3,F) bytes, optional (NULL: not written): byte 3 f + r is 1 when
+ *   (f, r) is the winner of vertex faces[r, f], else 0 -- every byte is written.  It depends on the topology only.
+ * fx3d_verts_normals_bwd: gout (3,V) -> gverts (3,V); winner_mask from fx3d_verts_normals_packed on the same faces.
+ * fx3d_faces_normals_packed (src/rep/mesh.jl:689-699): normals (3,F).  One launch, face-parallel.
+ * fx3d_faces_normals_bwd: gout (3,F) -> gverts (3,V).
+ * The adjoints are two launches each (g_raw into ws, then the gather): ws of fx3d_normals_workspace_bytes(V, F), device.
+ * padded / list forms (:640-670, :719-746): fx3d_packed_to_padded of the packed result with verts_len / faces_len.
+ * V < 2^31, F < 2^29. */
+FX3D_API fx3d_status fx3d_normals_workspace_bytes(int64_t V, int64_t F, size_t *bytes);
+FX3D_API fx3d_status fx3d_verts_normals_packed(const float *verts, int64_t V, const int32_t *faces, int64_t F,
+                                               const int32_t *vf_rowptr, const int32_t *vf_ent, float *normals,
+                                               uint8_t *winner_mask, fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_verts_normals_bwd(const float *verts, int64_t V, const int32_t *faces, int64_t F,
+                                            const int32_t *vf_rowptr, const int32_t *vf_ent, const uint8_t *winner_mask,
+                                            const float *gout, float *gverts, int32_t accumulate, void *ws, size_t ws_bytes,
+                                            fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_faces_normals_packed(const float *verts, int64_t V, const int32_t *faces, int64_t F,
+                                               float *normals, fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_faces_normals_bwd(const float *verts, int64_t V, const int32_t *faces, int64_t F,
+                                            const int32_t *vf_rowptr, const int32_t *vf_ent, const float *gout, float *gverts,
+                                            int32_t accumulate, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 /* _sample_points + _rand_barycentric_coords (src/transforms/mesh_func.jl:60-82) with the random
  * draws supplied: face_idx (n,B) int32 mesh-local 0-based, r1,r2 (n,B) in [0,1).  out (3,n,B). */
 FX3D_API fx3d_status fx3d_sample_points_explicit(const float *verts_padded, int32_t Vmax,
