@@ -2208,8 +2208,6 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
     return pl;
 }
 
-size_t partials_count(const Plan &pl, int B) { return (size_t)2 * B * pl.tiles; }
-
 // Spatial pruning (nn1_f16_kernel<.., PRUNE>): one-chunk plans of the fp16 kernel without split or tail, clouds of at least 1024
 // points.  Rows of scratch per block: the candidate cloud in image order + the block's window of the query cloud.
 constexpr size_t kHBoxBytes = 64 * 2 * sizeof(float4) + kHGroupsMax * 32;  // LDS: the lane tiles' boxes + the query groups' boxes

@@ -243,17 +243,6 @@ __device__ __forceinline__ double wave_sum_l63_f64(double v) {  // fixed order: 
     v = ((threadIdx.x >> 5) & 1) ? v + b : v;
     return v;
 }
-__device__ __forceinline__ float wave_sum_f(float v) {  // the same butterfly with adds (fixed order: deterministic)
-    v = v + dpp_mov<0xB1>(v);
-    v = v + dpp_mov<0x4E>(v);
-    v = v + dpp_mov<0x141>(v);
-    v = v + dpp_mov<0x140>(v);
-    const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-    const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-    const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-    return (a + b) + (c + d);
-}
 
 
 // The robust-range rounds run when cinf^2 > kRobustGate * variance (the farthest point more than 8 sigma out; the sampled
@@ -327,17 +316,6 @@ __device__ __forceinline__ float4 robust_range3(const float *__restrict__ cb, in
         }
     }
     return float4{mu[0], mu[1], mu[2], rng};
-}
-
-// Sum `n` doubles written by a previous kernel, single block of 256, fixed order.
-// (file-local copy per translation unit: no relocatable device code needed)
-__global__ static void reduce_partials_kernel(const double *__restrict__ partials, int64_t n,
-                                              double *__restrict__ out) {
-    __shared__ double sm[4];
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) acc += partials[i];
-    double r = block_sum<256>(acc, sm);
-    if (threadIdx.x == 0) out[0] = r;
 }
 
 }  // namespace fx3d

@@ -17,8 +17,8 @@
 //                                                  base (k+drop <= 32, M >= 64), compact (<= 48, two blocks per CU), wide (<= 64);
 //                                                  FEAT: EdgeConv's cat(X, KNN - X) written by the same kernel
 //   knn_pre_*_kernel                               fx3d_knn_ws: per-cloud statistics + fp16 image built once (feature space)
-//   knn_mfma_kernel<DK, F16, SPLIT, PRE>           4 <= D <= 128, k+drop <= 32, M >= 64: GEMM filter (fp16 rounded halves, 2-way
-//                                                  fp16 split, or Float32) + exact re-scan, medium path for crowded bands
+//   knn_mfma_kernel<DK, F16, PRE>                  4 <= D <= 128, k+drop <= 32, M >= 64: GEMM filter (fp16 rounded halves or
+//                                                  Float32) + exact re-scan, medium path for crowded bands
 //   edge_features_*_kernel                         cat(X, KNN - X) + permute for any F, and the @nograd adjoint
 //   knn_interleave_kernel / knn_merge_slices_kernel  fx3d_knn_ws: candidate slices as virtual clouds (few clouds with many rows;
 //                                                  k+drop in 33 ... 128 in feature space: 32 nearest per slice, verified merge)

@@ -131,11 +131,6 @@ __device__ __forceinline__ float vmin_acc(float a, float b) {  // v_min_f32 on a
     return r;
 }
 
-// branch-free (distance, index) comparison, 0 / 1
-__device__ __forceinline__ int key_less_bf(float d, int j, float od, int oj) {
-    return (int)(d < od) | ((int)(d == od) & (int)(j < oj));
-}
-
 // Exact top-kk of ONE query by the whole wave -- the fallback of the matrix-core kernels (queries whose filter is
 // unusable or whose survivor lists overflow: heavy ties, degenerate clouds).  Same scheme as knn_wave_d3_kernel:
 // per 1024-candidate chunk 16 exact distances per lane, threshold = kk-th smallest lane minimum (first chunk) or the

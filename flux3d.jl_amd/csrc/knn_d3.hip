@@ -700,16 +700,6 @@ __global__ __launch_bounds__(C::T) void knn_f16_d3_kernel(const float *__restric
     KNN_PROBE_MARK(11);
 }
 
-// dynamic LDS of geometry C for a cloud of M candidates without the optional parts (raw coordinates, medium-path scratch)
-template <class C>
-size_t knn_f16_d3_core_lds(int M) {
-    int CH = (M + 63) / 64 * 64;
-    if (CH > kTChunk) CH = kTChunk;
-    size_t img = (size_t)CH * 32;
-    const size_t keys = (size_t)C::G * 32 * C::KS * 8;
-    if (img < keys) img = keys;
-    return img + (size_t)C::W * C::CAP * 64 * 4 + (size_t)C::G * 32 * 8 * 4;
-}
 template <class C, int COMPACT = 0>  // COMPACT = blocks per CU the allocation is held to (0: one block, the whole CU)
 fx3d_status launch_knn_f16_d3_geom(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx,
                                    float *dist, hipStream_t st, float *feat, int layout, int xdiv) {

@@ -21,9 +21,8 @@ namespace {
 // In the exact phase all eight waves work: the four lanes of a query (two halves x consumer/producer) split its
 // survivors; candidate and query rows are gathered from L2.
 // Template modes: F16 = false: the Float32 GEMM above.  F16 = true (default for D % 4 == 0, M <= 4096): the cloud is
-// centred per dimension and scaled by a power of two, operands are fp16; SPLIT = false (default) uses the rounded halves
-// alone (one v_mfma_f32_32x32x16_f16 per K block, band 2^-10 (|q~|^2 + C~max^2)), SPLIT = true the 2-way split
-// hi*hi + lo*hi + hi*lo (band 2^-18).  Producers convert while staging.
+// centred per dimension and scaled by a power of two, operands are the rounded fp16 halves (one v_mfma_f32_32x32x16_f16
+// per K block, band 2^-10 (|q~|^2 + C~max^2)).  Producers convert while staging.
 // Queries whose band holds more candidates than the key arrays (60) but whose lane lists are intact take the medium
 // path (exact selection among their own survivors, up to kMMedCap); the rest of the leftovers the full exact merge.
 // PRE (fx3d_knn_ws, the pre-pass has built the cloud's fp16 image): both waves of a pair run the filter (DUAL, 128 group minima per
@@ -38,14 +37,12 @@ constexpr int kMKeyCap = 64;      // survivors per query handled by the fast pat
 constexpr int kMMedCap = 512;     // ... by the medium path: exact selection among the query's own survivors
 constexpr int kMKeyStride = 68;   // row stride of the key arrays in words: 32 queries x b128 reads without bank conflicts
 
-// fp16-split staging of a candidate chunk (producer side, F16 filter): unit = (row, group of 8 dimensions).
-// A thread converts two float4 of a row (scaled by sc) into one hi piece and one lo piece of 8 halves each.
-// LDS row: pieces [0, PPR/2) = hi of dimension groups, [PPR/2, PPR) = lo; piece c of row r sits at (c + r) mod PPR.
-// (row, group) units per producer thread and chunk: CH * (DP/8) <= units * 256.  The single-piece image is half
-// the size, so its chunks can be twice as long (fewer steps: a step cannot be shorter than the latency of the
-// global loads issued one step ahead)
-constexpr int kMUnitsSplit = 5, kMUnitsSingle = 6;
-template <int DK, int kMUnits>
+// fp16 staging of a candidate chunk (producer side, F16 filter): unit = (row, group of 8 dimensions).
+// A thread converts two float4 of a row (scaled by sc) into one piece of 8 halves.
+// (row, group) units per producer thread and chunk: CH * (DP/8) <= kMUnits * 256, which bounds the chunk length (long
+// chunks mean fewer steps: a step cannot be shorter than the latency of the global loads issued one step ahead)
+constexpr int kMUnits = 6;
+template <int DK>
 __device__ __forceinline__ void knn_f16_load_chunk(const float *__restrict__ yb, int D, int j0, int cn, int CH, int ptid,
                                                    float4 (&reg)[kMUnits][2]) {
     constexpr int DP = DK * 32, G = DP / 8;
@@ -72,7 +69,7 @@ __device__ __forceinline__ void knn_f16_load_chunk(const float *__restrict__ yb,
         if (!(ok && 8 * g + 4 < D)) reg[u][1] = zero4;
     }
 }
-// fp16 single-piece image (SPLIT = false): rows of PPI = DP/8 pieces (16 bytes = 8 halves); piece c of row r sits
+// fp16 image: rows of PPI = DP/8 pieces (16 bytes = 8 halves); piece c of row r sits
 // at (c + r / RPB) mod PPI, RPB = rows per 256 bytes, so that 16 consecutive rows cover all LDS banks.
 template <int PPI>
 __device__ __forceinline__ int knn_hpiece_off(int row, int c) {
@@ -85,11 +82,11 @@ template <int CTRL>
 __device__ __forceinline__ float knn_dpp(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
-template <int DK, bool SPLIT, int kMUnits>
+template <int DK>
 __device__ __forceinline__ void knn_f16_store_chunk(float *img, int CH, int cn, float sc, const float *mu_lds, int ptid,
                                                     const float4 (&reg)[kMUnits][2], float *norms, float *norms_m,
                                                     const float *acoef_lds, float &tmax, bool &tnan) {
-    constexpr int DP = DK * 32, G = DP / 8, PPR = DK * 8;
+    constexpr int DP = DK * 32, G = DP / 8;
     static_assert(kMProd % G == 0, "a producer thread always converts the same group of eight dimensions");
     static_assert(G == 4 || G == 8 || G == 16, "the row sum below");
     // (centre and error coefficient are re-read from LDS per call: holding them in registers across the chunk loop spills)
@@ -106,23 +103,14 @@ __device__ __forceinline__ void knn_f16_store_chunk(float *img, int CH, int cn, 
         const float v[8] = {(reg[u][0].x - mu8[0]) * sc, (reg[u][0].y - mu8[1]) * sc, (reg[u][0].z - mu8[2]) * sc,
                             (reg[u][0].w - mu8[3]) * sc, (reg[u][1].x - mu8[4]) * sc, (reg[u][1].y - mu8[5]) * sc,
                             (reg[u][1].z - mu8[6]) * sc, (reg[u][1].w - mu8[7]) * sc};
-        kh8 hi, lo;
+        kh8 hi;
         float part = 0.0f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const _Float16 hh_ = (_Float16)v[e];
-            hi[e] = hh_;
-            if (SPLIT) lo[e] = (_Float16)(v[e] - (float)hh_);
+            hi[e] = (_Float16)v[e];
             part = __builtin_fmaf(v[e], v[e], part);
         }
-        if (un < CH * G) {
-            if (SPLIT) {
-                *reinterpret_cast<kh8 *>(img + knn_piece_off<DK>(row, g)) = hi;
-                *reinterpret_cast<kh8 *>(img + knn_piece_off<DK>(row, PPR / 2 + g)) = lo;
-            } else {
-                *reinterpret_cast<kh8 *>(img + knn_hpiece_off<G>(row, g)) = hi;
-            }
-        }
+        if (un < CH * G) *reinterpret_cast<kh8 *>(img + knn_hpiece_off<G>(row, g)) = hi;
         if (norms) {  // wave-uniform
             // sum over the row's G lanes by DPP (VALU speed; the same tree as an xor butterfly in the row's first lane,
             // the only one that uses it)
@@ -486,7 +474,7 @@ __device__ __forceinline__ void knn_pre_stage_norms(const float *__restrict__ gn
                                                  (__attribute__((address_space(3))) void *)(ndn + (size_t)i * 256), 16, 0, 0);
         }
 }
-// producer wave pw brings chunk [j0, j0 + CH) of the pre-pass image into `img` (single-piece layout of knn_hpiece_off: the
+// producer wave pw brings chunk [j0, j0 + CH) of the pre-pass image into `img` (the layout of knn_hpiece_off: the
 // rotation sits on the source address) and, in phase A, its norms into the block's norm arrays -- direct-to-LDS loads only
 template <int DK, bool WAIT = true>
 __device__ __forceinline__ void knn_pre_stage_chunk(const _Float16 *__restrict__ gimg, const float *__restrict__ gnup,
@@ -520,7 +508,7 @@ __device__ __forceinline__ void knn_pre_stage_chunk(const _Float16 *__restrict__
     }
 }
 
-template <int DK, bool F16, bool SPLIT, bool PRE = false>
+template <int DK, bool F16, bool PRE = false>
 __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__restrict__ x, int N,
                                                              const float *__restrict__ y, int M, int B, int D,
                                                              int k, int drop, int32_t *__restrict__ idx,
@@ -531,7 +519,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
     constexpr int PPR = DK * 8;      // 16-byte pieces per candidate row
     constexpr int NT = DP / 8;       // b128 operand fetches per tile and half
     constexpr int NB16 = DP / 16;    // K blocks of the fp16 filter
-    constexpr int RSI = (F16 && !SPLIT) ? DP / 2 : DP;  // image row stride in floats (single-piece fp16: hi halves only)
+    constexpr int RSI = F16 ? DP / 2 : DP;  // image row stride in floats (fp16: halves)
     constexpr int PPI = RSI / 4;     // 16-byte pieces per image row
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int buf_floats = CH * RSI + CH;                                  // image [CH][RSI] + norms [CH]
@@ -588,7 +576,8 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
     const bool vec4x = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(xb) & 15) == 0);
     const int nchunk = (M + CH - 1) / CH;
     // filter error per unit of (candidate norm + query norm), scaled units: fp32 accumulation + centring + the oracle's own
-    // rounding 8 (4D + 8) u (4x head-room), operand representation 2^-10 (rounded halves) or 2^-18 (2-way split)
+    // rounding 8 (4D + 8) u (4x head-room), operand representation 2^-10 (rounded halves; the Float32 GEMM, which
+    // never reads it, parks 2^-18)
     float *nallm = two_norms ? nall + (size_t)nchunk * CH : nullptr;  // [nchunk*CH] norms for the phase-B test
     KNN_PROBE_MARK(0);
 
@@ -596,7 +585,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
         *cmax = 0u;
         cmax[2] = 0u;  // F16: a mean far from the middle of its range was seen (scale pass)
         cmax[3] = 0u;  // F16: bulk radius of a cloud centred on its medians (0: not in use)
-        const float aq = 8.0f * (float)(4 * D + 8) * 0x1p-24f + (SPLIT ? 0x1p-18f : 0x1.01p-10f);
+        const float aq = 8.0f * (float)(4 * D + 8) * 0x1p-24f + (F16 ? 0x1.01p-10f : 0x1p-18f);
         // candidate side: + its share of the subnormal floor, + the rounding of n (1 +- A); parked in LDS (cmax[1])
         reinterpret_cast<float *>(cmax)[1] = aq * 1.01f + 0x1p-26f * sqrtf((float)D) + 0x1p-23f;
     }
@@ -773,7 +762,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
         }
         __syncthreads();
         if (tid == 0 && funit < 1.0f) {
-            const float aq = 8.0f * (float)(4 * D + 8) * 0x1p-24f + (SPLIT ? 0x1p-18f : 0x1.01p-10f);
+            const float aq = 8.0f * (float)(4 * D + 8) * 0x1p-24f + 0x1.01p-10f;
             reinterpret_cast<float *>(cmax)[1] = aq * 1.01f + 0x1p-26f * sqrtf((float)D) / funit + 0x1p-23f;
         }
         // from here on: bits of the largest SCALED squared norm.  A cloud whose extent lets exact Float32 distances overflow
@@ -784,11 +773,11 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
 
     // ---- B operand: the wave's 32 query rows, staged through LDS (coalesced), then -2 q in registers ------------
     float4 a[NT];            // f32 filter: -2 q, this lane's half of the permuted reduction dimension
-    kh8 ah[NB16], al[NB16];  // fp16 filter: hi / lo halves of -2 sc q, 8 dimensions per K block and half-wave
+    kh8 ah[NB16];            // fp16 filter: halves of -2 sc q, 8 dimensions per K block and half-wave
     float qn = 0.0f;
     bool qok = true;
     if (early) {
-        // K block bb covers dimensions 16 bb + 8 h + [0, 8) in half-wave h: hi halves of -2 sc (q - mu), every piece read from memory
+        // K block bb covers dimensions 16 bb + 8 h + [0, 8) in half-wave h: halves of -2 sc (q - mu), every piece read from memory
         // (16 bytes of the lane's own row -- rows beyond N read row N - 1 and are never used -- and of the pre-pass header's centre,
         // zero beyond D); all loads in flight together
         const float *qg = xb + (size_t)(qi < N ? qi : N - 1) * D;
@@ -854,7 +843,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
         if (F16) {
-            // K block bb covers dimensions 16 bb + 8 h + [0, 8) in half-wave h: hi and lo halves of -2 sc q
+            // K block bb covers dimensions 16 bb + 8 h + [0, 8) in half-wave h: halves of -2 sc q
             float amax = 0.0f;
 #pragma unroll
             for (int bb = 0; bb < NB16; ++bb) {
@@ -867,9 +856,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
                     qn = qn + qs_ * qs_;
                     const float av = -2.0f * qs_;
                     amax = fmaxf(amax, fabsf(av));
-                    const _Float16 hh_ = (_Float16)av;
-                    ah[bb][e] = hh_;
-                    if (SPLIT) al[bb][e] = (_Float16)(av - (float)hh_);
+                    ah[bb][e] = (_Float16)av;
                 }
             }
             amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
@@ -893,7 +880,6 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
 
     // ---- chunk schedule: phase A walks the chunks forwards, phase B backwards (its first chunk is resident) ----
     const int nstep = 2 * nchunk;
-    constexpr int kMUnits = SPLIT ? kMUnitsSplit : kMUnitsSingle;
     float4 preg[kMUnits][2];  // F16 producers: the chunk after next, loaded one step ahead
     float pmax = 0.0f;        // F16 producers: largest scaled norm seen
     bool pnan = false;
@@ -912,8 +898,8 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
         }
     } else if (F16) {
         if (!consumer) {
-            knn_f16_load_chunk<DK, kMUnits>(yb, D, 0, M < CH ? M : CH, CH, ptid, preg);
-            knn_f16_store_chunk<DK, SPLIT, kMUnits>(sm, CH, M < CH ? M : CH, sc, mu, ptid, preg, nall, nallm, reinterpret_cast<const float *>(cmax + 1), pmax, pnan);
+            knn_f16_load_chunk<DK>(yb, D, 0, M < CH ? M : CH, CH, ptid, preg);
+            knn_f16_store_chunk<DK>(sm, CH, M < CH ? M : CH, sc, mu, ptid, preg, nall, nallm, reinterpret_cast<const float *>(cmax + 1), pmax, pnan);
             if (nchunk == 1) {
 #pragma unroll
                 for (int m = 1; m < 64; m <<= 1) pmax = fmaxf(pmax, __shfl_xor(pmax, m, 64));
@@ -922,7 +908,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
             }
             if (nevents > 1) {
                 const int c1 = 1 < nchunk ? 1 : 2 * nchunk - 3;
-                knn_f16_load_chunk<DK, kMUnits>(yb, D, c1 * CH, (M - c1 * CH) < CH ? (M - c1 * CH) : CH, CH, ptid, preg);
+                knn_f16_load_chunk<DK>(yb, D, c1 * CH, (M - c1 * CH) < CH ? (M - c1 * CH) : CH, CH, ptid, preg);
             }
             stage_ev = 1;
         }
@@ -991,8 +977,8 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
                 // compare: its staging leaves the rows beyond the cloud's end unwritten -- norm +inf, stale pieces -- and inf + NaN has
                 // no usable sign; the fp16 images are zero there.)
                 const float tsub = (F16 && phase) ? thr : 0.0f;
-                if (F16 && !SPLIT && PRE) {  // (without the pre-pass the producers' staging registers leave no room: 68 spills)
-                    // single-piece fp16 filter: TWO pairs of tiles per iteration -- the second pair's operand fetches and MFMAs are
+                if (F16 && PRE) {  // (without the pre-pass the producers' staging registers leave no room: 68 spills)
+                    // fp16 filter: TWO pairs of tiles per iteration -- the second pair's operand fetches and MFMAs are
                     // issued before the first pair's results are folded, so the fold (VALU) of one overlaps the matrix work of the
                     // other and one round of LDS latency serves four tiles (a lone consumer wave per SIMD hides nothing otherwise).
                     // One instantiation per phase (round 4): phase A's accumulators ARE the norm loads' destinations (no VALU) and two
@@ -1071,28 +1057,8 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
                         acc0[4 * g] = n0.x - tsub; acc0[4 * g + 1] = n0.y - tsub; acc0[4 * g + 2] = n0.z - tsub; acc0[4 * g + 3] = n0.w - tsub;
                         acc1[4 * g] = n1.x - tsub; acc1[4 * g + 1] = n1.y - tsub; acc1[4 * g + 2] = n1.z - tsub; acc1[4 * g + 3] = n1.w - tsub;
                     }
-                    if (F16 && SPLIT) {
-                        // A = candidate pieces (rows), B = query pieces (columns); hi*hi + lo*hi + hi*lo
-                        kh8 h0[NB16], l0[NB16], h1[NB16], l1[NB16];
-#pragma unroll
-                        for (int bb = 0; bb < NB16; ++bb) {
-                            const int ph = ((2 * bb + h + jl) & (PPR - 1)) * 4, pl = ((PPR / 2 + 2 * bb + h + jl) & (PPR - 1)) * 4;
-                            h0[bb] = *reinterpret_cast<const kh8 *>(c0 + ph);
-                            l0[bb] = *reinterpret_cast<const kh8 *>(c0 + pl);
-                            h1[bb] = *reinterpret_cast<const kh8 *>(c1 + ph);
-                            l1[bb] = *reinterpret_cast<const kh8 *>(c1 + pl);
-                        }
-#pragma unroll
-                        for (int bb = 0; bb < NB16; ++bb) {
-                            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(h0[bb], ah[bb], acc0, 0, 0, 0);
-                            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1[bb], ah[bb], acc1, 0, 0, 0);
-                            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(l0[bb], ah[bb], acc0, 0, 0, 0);
-                            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(l1[bb], ah[bb], acc1, 0, 0, 0);
-                            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(h0[bb], al[bb], acc0, 0, 0, 0);
-                            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1[bb], al[bb], acc1, 0, 0, 0);
-                        }
-                    } else if (F16) {
-                        // single-piece filter: one MFMA per K block and tile on the rounded (hi) halves
+                    if (F16) {
+                        // one MFMA per K block and tile on the rounded halves
                         constexpr int RPB = PPI >= 16 ? 1 : 16 / PPI;
                         kh8 h0[NB16], h1[NB16];
 #pragma unroll
@@ -1162,7 +1128,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
                                         nallm ? nallm + (size_t)ci_next * CH : nullptr, phase_a, wv - kMWaves, lane);
             } else if (F16) {
                 // the registers hold chunk ci_next (loaded one step ago); then fetch the chunk after it
-                knn_f16_store_chunk<DK, SPLIT, kMUnits>(img, CH, cnn, sc, mu, ptid, preg, stage_ev < nchunk ? nall + (size_t)stage_ev * CH : nullptr,
+                knn_f16_store_chunk<DK>(img, CH, cnn, sc, mu, ptid, preg, stage_ev < nchunk ? nall + (size_t)stage_ev * CH : nullptr,
                                         stage_ev < nchunk && nallm ? nallm + (size_t)stage_ev * CH : nullptr,
                                         reinterpret_cast<const float *>(cmax + 1), pmax, pnan);
                 if (stage_ev == nchunk - 1) {  // last phase-A chunk: publish this wave's maximum norm
@@ -1174,7 +1140,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
                 ++stage_ev;
                 if (stage_ev < nevents) {
                     const int cnx = stage_ev < nchunk ? stage_ev : 2 * nchunk - 2 - stage_ev;
-                    knn_f16_load_chunk<DK, kMUnits>(yb, D, cnx * CH, (M - cnx * CH) < CH ? (M - cnx * CH) : CH, CH, ptid, preg);
+                    knn_f16_load_chunk<DK>(yb, D, cnx * CH, (M - cnx * CH) < CH ? (M - cnx * CH) : CH, CH, ptid, preg);
                 }
             } else {
                 const bool phase_a = nstep1 < nchunk;
@@ -1260,14 +1226,13 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
             }
             float eps;
             if (F16) {
-                // scaled units (c~ = sc c, |c~| < 1; qn = |sc q|^2): split representation 3 2^-22 |a~||c~|, fp32
-                // accumulation of the 3D exact products (3D+1) u, the oracle's own (D+2) u, fp16 underflow floor
-                // single piece: the rounded operands differ by 2^-11 relative each, sum |c~_d a_d| <= 2 |c~||q~| <= qn + c2
+                // scaled units (c~ = sc c, |c~| < 1; qn = |sc q|^2): the rounded operands differ by 2^-11 relative each,
+                // sum |c~_d a_d| <= 2 |c~||q~| <= qn + c2; fp32 accumulation, the oracle's own (D+2) u, fp16 underflow floor
                 // |F^ - (sc^2 d_oracle - qn)| <= A (n_c + qn) + floor for candidate c with scaled norm n_c (A = acoef_q).
                 // two_norms: the candidate's share A n_c is already inside the norms (upwards in phase A, downwards
                 // in phase B), the query keeps B_q = A qn + floor_q: a far candidate no longer widens everybody's
                 // band.  Otherwise n_c <= c2 for all of them.
-                const float acoef_q = 8.0f * (float)(4 * D + 8) * 0x1p-24f + (SPLIT ? 0x1p-18f : 0x1.01p-10f);
+                const float acoef_q = 8.0f * (float)(4 * D + 8) * 0x1p-24f + 0x1.01p-10f;
                 const float floor_q = 0x1p-24f * sqrtf((float)D) * (qn / funit + 2.0f * funit);
                 eps = two_norms ? acoef_q * qn + floor_q : acoef_q * (qn + c2) + floor_q + 0x1p-26f * sqrtf((float)D) * c2 / funit;
                 eps = (qok && c2 == c2) ? eps : INFINITY;  // c2 is NaN for a non-finite / overflow-prone cloud (scale pass)
@@ -1281,10 +1246,10 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
             // D + 1 roundings: against the compare form the result moves by at most (D + 1) u (2 n_c + |thr| + 2 sum |products|)
             // (65 u (4 n_c + 2 qn + |thr|) at D = 64), u = 2^-24.  The candidate's and the query's own shares sit inside the budget the
             // filter already grants them (8 (4 D + 8) u = 2112 u each at D = 64, of which the compare form uses ~130 u); the threshold's share,
-            // (K + 1) u |thr| with K = D products (3 D for the split filter), is added here four times over -- at D = 64 2^-16 |thr|,
+            // (K + 1) u |thr| with K = D products (K = 3 D on the Float32 GEMM, whose compare form does not need it), is added here four times over -- at D = 64 2^-16 |thr|,
             // 1/64 of the band of a candidate at the boundary (its norm is of the threshold's size) -- and it makes the test strict
             // (a candidate at the threshold gives a negative result, never +-0).
-            thr = thr + (4.0f * (float)((SPLIT ? 3 : 1) * D + 1) * 0x1p-24f) * (fabsf(thr) + qn);
+            thr = thr + (4.0f * (float)((F16 ? 1 : 3) * D + 1) * 0x1p-24f) * (fabsf(thr) + qn);
         }
     }
     KNN_PROBE_MARK(20);
@@ -1883,19 +1848,19 @@ size_t knn_pre_bytes(int M, int B, int D) {
 bool knn_pre_shape_ok(int M, int D, int kk) {
     return D >= 4 && D <= 128 && kk <= 32 && M >= 64 && M <= 4096 && D % 4 == 0 && kPreThreads % (D / 4) == 0 && D / 4 <= 32;
 }
-// the shapes fx3d_knn_ws serves with the pre-pass: the single-piece fp16 filter (the default of knn_mfma_kernel)
+// the shapes fx3d_knn_ws serves with the pre-pass: the fp16 filter (the default of knn_mfma_kernel)
 bool knn_pre_eligible(const float *x, const float *y, int M, int D, int kk) {
     if (!knn_pre_shape_ok(M, D, kk)) return false;
     if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) != 0) return false;
     return !(opt(OPT_KNN_NO_MFMA) || opt(OPT_KNN_NO_PREPASS));
 }
 
-template <int DK, bool F16, bool SPLIT>
+template <int DK, bool F16>
 fx3d_status launch_knn_mfma_dk(const float *x, int N, const float *y, int M, int B, int D, int k, int drop,
                                int32_t *idx, float *dist, hipStream_t st, void *pre_ws = nullptr, int xdiv = 1) {
-    constexpr int DP = DK * 32, RS = DP + 4, RSI = (F16 && !SPLIT) ? DP / 2 : DP;
+    constexpr int DP = DK * 32, RS = DP + 4, RSI = F16 ? DP / 2 : DP;
     // list lengths + per-query counters + cmax + per-dimension centre + per-stage survivor counts ...
-    const bool use_pre = pre_ws != nullptr && F16 && !SPLIT;
+    const bool use_pre = pre_ws != nullptr && F16;
     const size_t small = (size_t)kMWaves * 64 * 4 + (size_t)3 * kMWaves * 32 * 4 + 64 + (size_t)DP * 4 + (size_t)kMWaves * 32 * 8;
     static_assert(kMWaves * 32 * 33 * 8 + 2 * kMWaves * 128 * 4 <= kMWaves * kMLCap * 64 * 4, "rank slots + fallback scratch alias the mask lists");
     const int keep_norms = M <= 4096;  // all candidate norms stay in LDS: phase B does not recompute them
@@ -1910,7 +1875,6 @@ fx3d_status launch_knn_mfma_dk(const float *x, int N, const float *y, int M, int
     const size_t budget = 150 * 1024 - fixed;                                  // floats*4 for the two chunk buffers
     int CH = (int)(budget / 2 / ((size_t)RSI * 4 + 4)) / 64 * 64;
     if (CH > 256) CH = 256;
-    constexpr int kMUnits = SPLIT ? kMUnitsSplit : kMUnitsSingle;
     if (F16 && !use_pre && CH > kMUnits * kMProd * 8 / DP / 64 * 64) CH = kMUnits * kMProd * 8 / DP / 64 * 64;  // producer register budget
     const int mpad = (M + 63) / 64 * 64;
     if (CH > mpad) CH = mpad;
@@ -1952,7 +1916,7 @@ fx3d_status launch_knn_mfma_dk(const float *x, int N, const float *y, int M, int
             if (img * 4 + small + need > lds) lds = img * 4 + small + need;
         }
     }
-    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_mfma_kernel<DK, F16, SPLIT>), 152 * 1024, "knn_mfma_kernel");
+    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_mfma_kernel<DK, F16>), 152 * 1024, "knn_mfma_kernel");
     if (arc != FX3D_OK) return arc;
     FX3D_REQUIRE(lds <= 152 * 1024, "fx3d_knn: internal LDS plan exceeds the CU (D=%d)", D);
     const int qpb = kMWaves * 32;
@@ -1965,13 +1929,13 @@ fx3d_status launch_knn_mfma_dk(const float *x, int N, const float *y, int M, int
         hipLaunchKernelGGL((knn_pre_image_kernel<DK>), dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, two_norms, pre);
     }
     if (use_pre) {
-        const fx3d_status arc2 = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_mfma_kernel<DK, F16, SPLIT, F16 && !SPLIT>), 152 * 1024,
+        const fx3d_status arc2 = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_mfma_kernel<DK, F16, F16>), 152 * 1024,
                                                     "knn_mfma_kernel<pre>");
         if (arc2 != FX3D_OK) return arc2;
-        hipLaunchKernelGGL((knn_mfma_kernel<DK, F16, SPLIT, F16 && !SPLIT>), dim3(nbx * bpad), dim3(kMThreads), lds, st, x, N, y, M, B, D,
+        hipLaunchKernelGGL((knn_mfma_kernel<DK, F16, F16>), dim3(nbx * bpad), dim3(kMThreads), lds, st, x, N, y, M, B, D,
                            k, drop, idx, dist, CH, (int)img, keep_norms, two_norms, srl, pre_ws, xdiv, csl, 1);
     } else
-        hipLaunchKernelGGL((knn_mfma_kernel<DK, F16, SPLIT>), dim3(nbx * bpad), dim3(kMThreads), lds, st, x, N, y, M, B, D,
+        hipLaunchKernelGGL((knn_mfma_kernel<DK, F16>), dim3(nbx * bpad), dim3(kMThreads), lds, st, x, N, y, M, B, D,
                            k, drop, idx, dist, CH, (int)img, keep_norms, two_norms, srl, nullptr, xdiv, csl, 0);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
@@ -1980,20 +1944,20 @@ fx3d_status launch_knn_mfma_dk(const float *x, int N, const float *y, int M, int
 fx3d_status launch_knn_mfma(const float *x, int N, const float *y, int M, int B, int D, int k, int drop, int32_t *idx,
                             float *dist, hipStream_t st, void *pre_ws = nullptr, int xdiv = 1) {
     const int dk = (D + 31) / 32;
-    // fp16-split filter: needs 16-byte loads (D % 4 == 0, aligned clouds) and all norms in LDS up front
+    // fp16 filter: needs 16-byte loads (D % 4 == 0, aligned clouds) and all norms in LDS up front
     const bool f16 = D % 4 == 0 && M <= 4096 && ((reinterpret_cast<uintptr_t>(y) & 15) == 0) &&
                      ((size_t)M * D * 4) % 16 == 0;
     if (f16) {
         switch (dk) {
-            case 1: return launch_knn_mfma_dk<1, true, false>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-            case 2: return launch_knn_mfma_dk<2, true, false>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-            default: return launch_knn_mfma_dk<4, true, false>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
+            case 1: return launch_knn_mfma_dk<1, true>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
+            case 2: return launch_knn_mfma_dk<2, true>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
+            default: return launch_knn_mfma_dk<4, true>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
         }
     }
     switch (dk) {
-        case 1: return launch_knn_mfma_dk<1, false, true>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
-        case 2: return launch_knn_mfma_dk<2, false, true>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
-        default: return launch_knn_mfma_dk<4, false, true>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
+        case 1: return launch_knn_mfma_dk<1, false>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
+        case 2: return launch_knn_mfma_dk<2, false>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
+        default: return launch_knn_mfma_dk<4, false>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
     }
 }
 

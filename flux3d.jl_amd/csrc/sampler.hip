@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kCdfThreads) void face_cdf_kernel(const float *__re
     __syncthreads();
     CDF_MARK(5);
     // chunk offsets inside their group (exclusive, in place) + the group totals; then the same one level up.  The fix-up column
-    // lies in the last chunk (Fp = roundup32(Fmax)): no offset depends on that chunk's own total -- only its local prefixes change.
+    // lies in the last chunk (Fp = Fmax rounded up to a multiple of kChunk): no offset depends on that chunk's own total -- only its local prefixes change.
     if (threadIdx.x < kChunk) t1[threadIdx.x] = threadIdx.x < ng ? chain32_excl(t0 + threadIdx.x * kChunk) : 0.0;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -545,8 +545,6 @@ int grid_for(long long n) {
     if (g > 2048) g = 2048;
     return (int)g;
 }
-
-inline int roundup32(int v) { return (v + kChunk - 1) / kChunk * kChunk; }
 
 size_t ws_bytes_needed(int Fmax, int B) {
     const size_t cdf = sizeof(double) * (size_t)B * CdfWs::make(Fmax).stride;

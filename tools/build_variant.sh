@@ -13,4 +13,4 @@ SRC=$UNIT.hip; [ -f $SRC ] || SRC=$UNIT.cpp
   -mllvm -amdgpu-mfma-vgpr-form -I../../include -Wno-unused-function $EXTRA -x hip -c $SRC -o /tmp/fxv_$NAME/$UNIT.o -save-temps=obj 2>/dev/null
 OBJS=$(ls ../lib/obj/*.o | grep -v "/$UNIT.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/libflux3d_hip_$NAME.so $OBJS /tmp/fxv_$NAME/$UNIT.o -ldl
-grep -E "^\s+\.(vgpr_count|vgpr_spill_count|name):" /tmp/fxv_$NAME/*gfx950.s | paste - - - | grep -v reduce_partials | sed "s/^/[$NAME] /"
+grep -E "^\s+\.(vgpr_count|vgpr_spill_count|name):" /tmp/fxv_$NAME/*gfx950.s | paste - - - | sed "s/^/[$NAME] /"
