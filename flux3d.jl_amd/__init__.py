@@ -23,7 +23,12 @@ from .metrics import (chamfer_distance, chamfer_distance_grad, chamfer_loss_pair
                       laplacian_loss, laplacian_loss_grad, mesh_losses, mesh_losses_grad, MeshReg, nearest_neighbors,
                       sampling_adjoint_is_ordered)
 from .transforms import (EPS, compute_faces_areas_list, compute_faces_areas_packed,  # noqa: E402
-                         compute_faces_areas_padded, lincomb, offset, sample_points, sample_points_grad, sample_points_pair)
+                         compute_faces_areas_padded, lincomb, offset, sample_points, sample_points_grad, sample_points_pair,
+                         normalize, normalize_, scale, scale_, rotate, rotate_, realign, realign_, translate, translate_,
+                         segment_minmax, target_bounds, transform_plan, AbstractTransform, Chain, ScalePointCloud,
+                         RotatePointCloud, ReAlignPointCloud, NormalizePointCloud, ScaleTriMesh, RotateTriMesh, ReAlignTriMesh,
+                         NormalizeTriMesh, TranslateTriMesh, OffsetTriMesh, TriMeshToVoxelGrid, PointCloudToVoxelGrid,
+                         VoxelGridToTriMesh, PointCloudToTriMesh, TriMeshToPointCloud, VoxelGridToPointCloud)
 from .normals import (compute_faces_normals_grad, compute_faces_normals_list, compute_faces_normals_packed,  # noqa: E402
                       compute_faces_normals_padded, compute_verts_normals_grad, compute_verts_normals_list,
                       compute_verts_normals_packed, compute_verts_normals_padded)

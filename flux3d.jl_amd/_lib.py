@@ -109,6 +109,13 @@ SIGNATURES = {
     "fx3d_verts_normals_bwd": [vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp, c_i32, vp, sz, vp],
     "fx3d_faces_normals_packed": [vp, c_i64, vp, c_i64, vp, vp],
     "fx3d_faces_normals_bwd": [vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i32, vp, sz, vp],
+    "fx3d_transform_plan_describe": [c_i32, c_i64, c_i32, C.c_char_p, sz],
+    "fx3d_transform_workspace_bytes": [c_i32, c_i64, c_i32, C.POINTER(sz)],
+    "fx3d_segment_minmax": [vp, c_i32, c_i64, c_i32, vp, c_i32, vp, vp, vp, sz, vp],
+    "fx3d_normalize": [vp, c_i32, c_i64, c_i32, vp, c_i32, vp, vp, vp, vp, sz, vp],
+    "fx3d_realign": [vp, c_i32, c_i64, c_i32, vp, vp, vp, vp, vp, vp, vp],
+    "fx3d_rotate": [vp, c_i64, c_i64, c_i32, vp, vp, vp, vp, vp],
+    "fx3d_scale_translate": [vp, c_i64, c_i32, vp, vp, vp],
     "fx3d_sample_points_explicit": [vp, c_i32, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp],
     "fx3d_sample_points_workspace_bytes": [c_i32, c_i32, C.POINTER(sz)],
     "fx3d_sample_points": [vp, c_i32, vp, c_i32, vp, c_i32, c_i32, c_f64, c_u64, vp, vp, vp, vp,

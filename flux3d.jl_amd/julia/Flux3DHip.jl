@@ -29,12 +29,13 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  compute_verts_normals_packed, compute_faces_normals_packed,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
                  _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel,
-                 voxel_to_trimesh, VoxelGrid
+                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!
 using SparseArrays: SparseMatrixCSC, findnz
 import Zygote
 
 export HipArray, hip, unhip, use_hip, knn_graph, edgeconv_graph, pointcloud_to_voxel
 export trimesh_from_voxels, pointcloud_from_voxels
+export normalize_pointcloud!, scale_pointcloud!, rotate_pointcloud!, realign_pointcloud!, transform_plan
 
 const LIB = get(ENV, "FLUX3D_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libflux3d_hip.so"))
 const Stream = Ptr{Cvoid}
@@ -1316,5 +1317,159 @@ function build_laplacian_csr(edges::Matrix{Int64}, V::Integer; index_base::Integ
                                               colind::Ptr{Int32}, vals::Ptr{Float32}, nnz::Ref{Int64})::Int32)
     return rowptr, colind[1:nnz[]], vals[1:nnz[]]
 end
+
+
+# ---- transforms (src/transforms/pcloud_func.jl, src/transforms/mesh_func.jl:99-399) ------------------------------------------
+# TriMesh{Float32,R,HipArray}: methods of the reference's own normalize! / scale! / rotate! / realign! / translate!, so its
+# non-`!` forms (deepcopy, then `!`) and the transform structs (src/transforms/transforms.jl) reach them unchanged.  PointCloud
+# is not parametric in its storage: exported device functions, as pointcloud_to_voxel.  Maps are bit for bit the restatement
+# tests/transforms_ref.py; the statistics follow include/flux3d_hip.h.  Argument checks are the reference's, before any launch.
+# Normals are left as they are.
+seg_off_dev(m) = get!(() -> hip(Int64[0; cumsum(Int64.(m._verts_len))]), mirror(m), :seg_off)
+function transform_plan(D::Integer, n_max::Integer, B::Integer)
+    buf = Vector{UInt8}(undef, 256)
+    check(@ccall LIB.fx3d_transform_plan_describe(Int32(D)::Int32, Int64(n_max)::Int64, Int32(B)::Int32, buf::Ptr{UInt8},
+                                                  length(buf)::Csize_t)::Int32)
+    return unsafe_string(pointer(buf))
+end
+function transform_workspace(D::Integer, n_max::Integer, B::Integer)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_transform_workspace_bytes(Int32(D)::Int32, Int64(n_max)::Int64, Int32(B)::Int32,
+                                                    nb::Ref{Csize_t})::Int32)
+    return workspace(nb[])
+end
+function _normalize_dev(x::HipArray{Float32}, D::Integer, n_max::Integer, B::Integer, off, mode::Integer)
+    y = HipArray{Float32}(undef, size(x)...)
+    ws = transform_workspace(D, n_max, B)
+    check(@ccall LIB.fx3d_normalize(x.ptr::Ptr{Cvoid}, Int32(D)::Int32, Int64(n_max)::Int64, Int32(B)::Int32,
+                                    (off === nothing ? C_NULL : off.ptr)::Ptr{Cvoid}, Int32(mode)::Int32, y.ptr::Ptr{Cvoid},
+                                    C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                    DEFAULT_STREAM::Stream)::Int32)
+    return y
+end
+function _scale_translate_dev(x::HipArray{Float32}, mode::Integer, v::Vector{Float32})
+    y = HipArray{Float32}(undef, size(x)...)
+    check(@ccall LIB.fx3d_scale_translate(x.ptr::Ptr{Cvoid}, Int64(length(x))::Int64, Int32(mode)::Int32, v::Ptr{Float32},
+                                          y.ptr::Ptr{Cvoid}, DEFAULT_STREAM::Stream)::Int32)
+    return y
+end
+function _rotate_dev(x::HipArray{Float32}, ncols::Integer, n_max::Integer, B::Integer, off, rotmat::AbstractArray{Float32})
+    y = HipArray{Float32}(undef, size(x)...)
+    host = ndims(rotmat) == 2 ? Vector{Float32}(vec(rotmat)) : nothing
+    dev = ndims(rotmat) == 3 ? hip(Array{Float32}(rotmat)) : nothing
+    check(@ccall LIB.fx3d_rotate(x.ptr::Ptr{Cvoid}, Int64(ncols)::Int64, Int64(n_max)::Int64, Int32(B)::Int32,
+                                 (off === nothing ? C_NULL : off.ptr)::Ptr{Cvoid},
+                                 (host === nothing ? Ptr{Float32}(C_NULL) : pointer(host))::Ptr{Float32},
+                                 (dev === nothing ? C_NULL : dev.ptr)::Ptr{Cvoid}, y.ptr::Ptr{Cvoid}, DEFAULT_STREAM::Stream)::Int32)
+    return y
+end
+function _minmax_dev(x::HipArray{Float32}, D::Integer, n_max::Integer, B::Integer, off, pad_zero::Bool)
+    n_max > 0 || throw(ArgumentError("reducing over an empty collection is not allowed"))
+    mn = HipArray{Float32}(undef, D, B); mx = HipArray{Float32}(undef, D, B)
+    ws = transform_workspace(D, n_max, B)
+    check(@ccall LIB.fx3d_segment_minmax(x.ptr::Ptr{Cvoid}, Int32(D)::Int32, Int64(n_max)::Int64, Int32(B)::Int32,
+                                         (off === nothing ? C_NULL : off.ptr)::Ptr{Cvoid}, Int32(pad_zero)::Int32,
+                                         mn.ptr::Ptr{Cvoid}, mx.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                         DEFAULT_STREAM::Stream)::Int32)
+    return mn, mx
+end
+function _realign_dev(x::HipArray{Float32}, D::Integer, n_max::Integer, B::Integer, off, pad_zero::Bool,
+                      tgt_min::AbstractArray{Float32,2}, tgt_max::AbstractArray{Float32,2})
+    smin, smax = _minmax_dev(x, D, n_max, B, off, pad_zero)
+    tmin = hip(Array{Float32}(tgt_min)); tmax = hip(Array{Float32}(tgt_max))
+    y = HipArray{Float32}(undef, size(x)...)
+    check(@ccall LIB.fx3d_realign(x.ptr::Ptr{Cvoid}, Int32(D)::Int32, Int64(n_max)::Int64, Int32(B)::Int32,
+                                  (off === nothing ? C_NULL : off.ptr)::Ptr{Cvoid}, smin.ptr::Ptr{Cvoid}, smax.ptr::Ptr{Cvoid},
+                                  tmin.ptr::Ptr{Cvoid}, tmax.ptr::Ptr{Cvoid}, y.ptr::Ptr{Cvoid}, DEFAULT_STREAM::Stream)::Int32)
+    return y
+end
+_mesh_dims(m) = (3, Int(maximum(m._verts_len)), length(m._verts_len))
+
+# normalize!(m) (mesh_func.jl:99-113): (x - c) / max(s, EPS) per mesh, without the padding _correction (include/flux3d_hip.h)
+function normalize!(m::TriMesh{Float32,R,HipArray}) where {R}
+    D, V, B = _mesh_dims(m)
+    m._verts_packed = _normalize_dev(get_verts_packed(m)::HipArray{Float32,2}, D, V, B, seg_off_dev(m), 1)
+    return m
+end
+# scale!(m, factor) (mesh_func.jl:154-160); the (3,) form (:162-169) always throws in the reference and is left to it
+function scale!(m::TriMesh{Float32,R,HipArray}, factor::Float32) where {R}
+    (factor > 0.0) || error("factor must be greater than 0.0")
+    m._verts_packed = _scale_translate_dev(get_verts_packed(m)::HipArray{Float32,2}, 0, Float32[factor, 0, 0])
+    return m
+end
+# rotate!(m, rotmat) (mesh_func.jl:221-235): one (3,3) matrix, or (3,3,B) per mesh
+function rotate!(m::TriMesh{Float32,R,HipArray}, rotmat::AbstractArray{Float32,2}) where {R}
+    size(rotmat) == (3, 3) || error("rotmat must be (3, 3) array, but instead got $(size(rotmat)) array")
+    D, V, B = _mesh_dims(m)
+    x = get_verts_packed(m)::HipArray{Float32,2}
+    m._verts_packed = _rotate_dev(x, size(x, 2), V, B, seg_off_dev(m), rotmat)
+    return m
+end
+function rotate!(m::TriMesh{Float32,R,HipArray}, rotmat::AbstractArray{Float32,3}) where {R}
+    size(rotmat) == (3, 3, m.N) || error("rotmat must be (3, 3, $(m.N)) array, but instead got $(size(rotmat)) array")
+    D, V, B = _mesh_dims(m)
+    x = get_verts_packed(m)::HipArray{Float32,2}
+    m._verts_packed = _rotate_dev(x, size(x, 2), V, B, seg_off_dev(m), rotmat)
+    return m
+end
+# realign!(src, tgt_min, tgt_max) (mesh_func.jl:276-289): min / max over verts_padded, so a shorter mesh takes +0.0
+function realign!(src::TriMesh{Float32,R,HipArray}, tgt_min::AbstractArray{Float32,2}, tgt_max::AbstractArray{Float32,2}) where {R}
+    size(tgt_min) == size(tgt_max) == (3, 1) || throw(DimensionMismatch("a (3, 1) target box is needed"))
+    D, V, B = _mesh_dims(src)
+    src._verts_packed = _realign_dev(get_verts_packed(src)::HipArray{Float32,2}, D, V, B, seg_off_dev(src), true,
+                                     unhip_box(tgt_min), unhip_box(tgt_max))
+    return src
+end
+# realign!(src, tgt::TriMesh, index) (mesh_func.jl:297-298) reaches realign!(src, ::AbstractArray{Float32,2}) with a HipArray
+function realign!(src::TriMesh{Float32,R,HipArray}, tgt::HipArray{Float32,2}) where {R}
+    tmin, tmax = _minmax_dev(tgt, size(tgt, 1), size(tgt, 2), 1, nothing, false)
+    return realign!(src, unhip(tmin), unhip(tmax))
+end
+unhip_box(a::HipArray) = unhip(a)
+unhip_box(a::AbstractArray) = a
+# translate!(m, vector) (mesh_func.jl:329-339)
+function translate!(m::TriMesh{Float32,R,HipArray}, vector::AbstractArray{Float32}) where {R}
+    (size(vector) == (3,)) || error("vector must be (3, ), but instead got $(size(vector)) array")
+    m._verts_packed = _scale_translate_dev(get_verts_packed(m)::HipArray{Float32,2}, 1, Vector{Float32}(vector))
+    return m
+end
+
+# PointCloud with HipArray points (pcloud_func.jl): the `!` forms, as exported device functions
+function normalize_pointcloud!(p::PointCloud)
+    x = p.points::HipArray{Float32,3}
+    D, N, B = size(x)
+    p.points = _normalize_dev(x, D, N, B, nothing, 0)
+    return p
+end
+function scale_pointcloud!(p::PointCloud, factor::Number)
+    f = Float32(factor)
+    (f > 0.0) || error("factor must be greater than 0.0")
+    p.points = _scale_translate_dev(p.points::HipArray{Float32,3}, 0, Float32[f, 0, 0])
+    return p
+end
+function rotate_pointcloud!(p::PointCloud, rotmat::AbstractArray{<:Number})
+    x = p.points::HipArray{Float32,3}
+    D, N, B = size(x)
+    R = Float32.(rotmat)
+    ndims(R) == 2 && (size(R) == (3, 3) || error("rotmat must be (3, 3) array, but instead got $(size(R)) array"))
+    ndims(R) == 3 && (size(R) == (3, 3, B) || error("rotmat must be (3, 3, $(B)) array, but instead got $(size(R)) array"))
+    D == 3 || error("dimension of points in PointCloud must be 3")
+    p.points = _rotate_dev(x, N * B, N, B, nothing, R)
+    return p
+end
+function realign_pointcloud!(p::PointCloud, tgt_min::AbstractArray{<:Number,2}, tgt_max::AbstractArray{<:Number,2})
+    x = p.points::HipArray{Float32,3}
+    D, N, B = size(x)
+    D == size(tgt_max, 1) || error("source and target pointcloud dimension mismatch")
+    p.points = _realign_dev(x, D, N, B, nothing, false, Float32.(unhip_box(tgt_min)), Float32.(unhip_box(tgt_max)))
+    return p
+end
+function realign_pointcloud!(p::PointCloud, tgt::PointCloud, index::Number = 1)
+    t = tgt.points::HipArray{Float32,3}
+    D, N, B = size(t)
+    tmin, tmax = _minmax_dev(hip(unhip(t)[:, :, Int(index)]), D, N, 1, nothing, false)   # tgt[index] (pcloud_func.jl:221-224)
+    return realign_pointcloud!(p, unhip(tmin), unhip(tmax))
+end
+
 
 end # module

@@ -13,11 +13,12 @@
 using Test, Statistics
 using Flux3D
 using Flux3D: chamfer_distance, laplacian_loss, edge_loss, sample_points, load_trimesh, get_verts_packed, get_edges_packed,
-              get_verts_padded, TriMesh, PointCloud
+              get_verts_padded, get_verts_list, TriMesh, PointCloud, ScaleTriMesh
 using Zygote: gradient
 
 include(joinpath(@__DIR__, "Flux3DHip.jl"))
 using .Flux3DHip: hip, unhip, HipArray, use_hip, knn_graph
+using .Flux3DHip: normalize_pointcloud!, scale_pointcloud!, rotate_pointcloud!, realign_pointcloud!, transform_plan
 
 const ASSETS = get(ENV, "FLUX3D_TEST_ASSETS", joinpath(dirname(pathof(Flux3D)), "..", "test", "assets"))
 
@@ -105,6 +106,40 @@ end
         loss = chamfer_distance(dm, dm)
         @test all(isapprox.(loss, 0, rtol = 1e-5, atol = 1e-2))
         @test gradient(x -> chamfer_distance(x, x), dm) isa Tuple
+    end
+
+    @testset "transforms (test/transforms/mesh_func.jl, pcloud_func.jl) on hip(m) and device clouds" begin
+        m = load_trimesh(joinpath(ASSETS, "teapot.obj"), joinpath(ASSETS, "sphere.obj"))
+        v = get_verts_packed(m)
+        dm = hip(m)
+        @test unhip(get_verts_packed(Flux3D.scale(Flux3D.scale(dm, 2.0), 0.5))) == v
+        rotmat = 2 .* one(rand(Float32, 3, 3))
+        @test all(isapprox.(unhip(get_verts_packed(Flux3D.rotate(Flux3D.rotate(dm, rotmat), inv(rotmat)))), v, rtol = 1e-5, atol = 1e-5))
+        @test all(isapprox.(unhip(get_verts_packed(Flux3D.translate(Flux3D.translate(dm, 1.0), -1.0))), v, rtol = 1e-5, atol = 1e-5))
+        n = Flux3D.normalize(dm)
+        @test n isa TriMesh && get_verts_packed(dm) isa HipArray
+        for x in unhip.(get_verts_list(n))
+            @test all(isapprox.(mean(x; dims = 2), 0, rtol = 1e-5, atol = 1e-5))
+            @test all(isapprox.(std(x; dims = 2), 1, rtol = 1e-5, atol = 1e-5))
+        end
+        tgt = Flux3D.scale(dm, 2.0)
+        r = Flux3D.realign(dm, tgt)
+        @test r isa TriMesh
+        @test_throws ErrorException Flux3D.scale!(hip(m), -1.0)
+        @test_throws TypeError Flux3D.scale!(hip(m), [1.0, 1.0, 1.0])
+        @test unhip(get_verts_packed(ScaleTriMesh(2.0; inplace = false)(dm))) == 2 .* v
+        p = PointCloud(hip(rand(Float32, 3, 8, 2)))
+        x = unhip(p.points)
+        normalize_pointcloud!(p)
+        @test all(isapprox.(mean(unhip(p.points); dims = 2), 0, rtol = 1e-5, atol = 1e-5))
+        q = PointCloud(hip(x))
+        @test unhip(scale_pointcloud!(scale_pointcloud!(q, 2.0), 0.5).points) == x
+        @test all(isapprox.(unhip(rotate_pointcloud!(rotate_pointcloud!(q, rotmat), inv(rotmat)).points), x, rtol = 1e-5, atol = 1e-5))
+        t = PointCloud(hip(rand(Float32, 3, 8, 1)))
+        s = realign_pointcloud!(PointCloud(hip(x)), t)
+        tp = unhip(t.points)
+        @test all(maximum(tp, dims = 2) .>= unhip(s.points) .>= minimum(tp, dims = 2))
+        @test startswith(transform_plan(3, 1024, 32), "plan=fused")
     end
 
     @testset "normals (test/rep.jl:224-330): the CPU method's result, bit for bit, and its adjoint" begin

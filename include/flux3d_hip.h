@@ -160,6 +160,59 @@ FX3D_API fx3d_status fx3d_chamfer_finalize_many(const double *sums_dev, int32_t 
                                                 int64_t B_global, int32_t D, float w1, float w2,
                                                 float *losses_dev, fx3d_stream_t s);
 
+/* ---- PointCloud / TriMesh transforms (src/transforms/pcloud_func.jl, src/transforms/mesh_func.jl:99-399) ----------------
+ * Segments: x is a (D, ncols) column-major Float32 stream of B segments.  seg_off == NULL: DENSE (D, n_max, B), segment b is
+ * columns [b n_max, (b+1) n_max) (a PointCloud).  Otherwise PACKED: seg_off is a device int64 array of B+1 prefix sums of the
+ * per-mesh vertex counts, segment b is columns [seg_off[b], seg_off[b+1]), and n_max is the longest segment (a TriMesh's
+ * (3, sum V), n_max = Vmax).  Outputs have the input's shape; y == x is allowed.
+ * Statistics of normalize, the contract (the reference's own orders -- a sequential Float32 chain on the CPU, another tree
+ * with CUDA -- are not targets): over the n real points of a segment (n = N for a cloud, n = verts_len[b] for a mesh; the
+ * reference's `_correction` only undoes its zero padding),
+ *   c = Float32(sum x / n)  with the sum in Float64,
+ *   s = Float32(sqrt(sum (x - c)^2 / (n - 1)))  in Float64, with c the Float32 centroid (the reference passes it as `mean =`).
+ * The device result is within 1 ulp of these values and is the same bits on every run: the summation order is a function
+ * of (D, n_max, B) alone (per-chunk Float64 sums and centred sums, a fixed block tree, no float atomics).  n = 1 gives
+ * s = NaN (0/0), and so NaN output, in both forms, like the reference.
+ * Plan (fx3d_transform_plan_describe): chunk = 16384 / D columns; nchunks = ceil(n_max / chunk).  nchunks <= 1: FUSED, one
+ * block per segment, statistics and map in one launch, no workspace.  Otherwise TWO LAUNCHES: per-chunk partials into ws
+ * (fx3d_transform_workspace_bytes), then a map launch that folds its segment's partials.  No host synchronisation: every
+ * entry point can be captured into a graph.  D <= 1024 for normalize, realign and segment_minmax. */
+#define FX3D_NORMALIZE_EPS_ADD 0 /* PointCloud: (x - c) / (s + EPS)            src/transforms/pcloud_func.jl:16-22 */
+#define FX3D_NORMALIZE_EPS_MAX 1 /* TriMesh:    (x - c) / max(s, EPS), Julia's max (NaN wins)   mesh_func.jl:99-113 */
+#define FX3D_SCALE 0             /* y = factor * x       (lmul!, pcloud_func.jl:62-66, mesh_func.jl:154-160) */
+#define FX3D_TRANSLATE 1         /* y = x + t[row]       (mesh_func.jl:331-339), D = 3 */
+FX3D_API fx3d_status fx3d_transform_plan_describe(int32_t D, int64_t n_max, int32_t B, char *buf, size_t n);
+FX3D_API fx3d_status fx3d_transform_workspace_bytes(int32_t D, int64_t n_max, int32_t B, size_t *bytes);
+/* minimum / maximum(x, dims = 2) per segment with Julia's min / max (NaN propagates, min(-0.0, 0.0) = -0.0,
+ * max(-0.0, 0.0) = 0.0): min_out, max_out (D, B) device.  pad_zero != 0: every segment shorter than n_max also takes +0.0
+ * into both (realign!(::TriMesh) reduces over verts_padded, mesh_func.jl:281-283).  n_max == 0 is an error (Julia throws on
+ * an empty reduction, pcloud_func.jl:215-216).  ws: fx3d_transform_workspace_bytes. */
+FX3D_API fx3d_status fx3d_segment_minmax(const float *x, int32_t D, int64_t n_max, int32_t B, const int64_t *seg_off,
+                                         int32_t pad_zero, float *min_out, float *max_out, void *ws, size_t ws_bytes,
+                                         fx3d_stream_t s);
+/* normalize! (pcloud_func.jl:16-22 with mode EPS_ADD, mesh_func.jl:99-113 with mode EPS_MAX): y = (x - c) / (s + EPS) or
+ * (x - c) / max(s, EPS), c and s per (row, segment) as stated above.  centroid_out, scale_out: optional (D, B) device copies
+ * of c and s.  ws: fx3d_transform_workspace_bytes. */
+FX3D_API fx3d_status fx3d_normalize(const float *x, int32_t D, int64_t n_max, int32_t B, const int64_t *seg_off, int32_t mode,
+                                    float *y, float *centroid_out, float *scale_out, void *ws, size_t ws_bytes, fx3d_stream_t s);
+/* realign! (pcloud_func.jl:206-218, mesh_func.jl:276-289): y = ((x - smin) / ((smax - smin) + EPS)) * (tmax - tmin) + tmin,
+ * unfused, in that bracketing; src_min / src_max (D, B) device (fx3d_segment_minmax), tgt_min / tgt_max (D) device. */
+FX3D_API fx3d_status fx3d_realign(const float *x, int32_t D, int64_t n_max, int32_t B, const int64_t *seg_off,
+                                  const float *src_min, const float *src_max, const float *tgt_min, const float *tgt_max,
+                                  float *y, fx3d_stream_t s);
+/* rotate! (pcloud_func.jl:120-137, mesh_func.jl:221-235): y[:, j] = transpose(R) * x[:, j] with D = 3, evaluated as
+ * y_i = (R[0,i] x0 + R[1,i] x1) + R[2,i] x2 in Float32, unfused, in that order (R column-major, R[k,i] at k + 3 i).  The
+ * reference goes through BLAS (`*`, batched_mul), whose order is not pinned.  Exactly one of: rotmat_host, 9 floats read during
+ * the call (one matrix for the whole batch, passed to the kernel by value); rotmat_dev, (3, 3, B) device, the matrix of each
+ * column's segment.  ncols: columns of x (dense: n_max * B). */
+FX3D_API fx3d_status fx3d_rotate(const float *x, int64_t ncols, int64_t n_max, int32_t B, const int64_t *seg_off,
+                                 const float *rotmat_host, const float *rotmat_dev, float *y, fx3d_stream_t s);
+/* scale! / translate! over a flat stream of n floats (pcloud_func.jl:62-66, mesh_func.jl:154-160, 331-339): mode FX3D_SCALE,
+ * y = vec_host[0] * x; mode FX3D_TRANSLATE, y[i] = x[i] + vec_host[i % 3] (D = 3, n % 3 == 0).  vec_host is read during the
+ * call and passed to the kernel by value.  Argument checks on factor and vector are the caller's (the reference's errors). */
+FX3D_API fx3d_status fx3d_scale_translate(const float *x, int64_t n, int32_t mode, const float *vec_host, float *y,
+                                          fx3d_stream_t s);
+
 /* _chamfer_distance(A,B,w1,w2) forward in one call (src/metrics/pcloud.jl:39-52). loss_dev
  * device float; loss_host optional host float (non-NULL => stream is synchronised). */
 FX3D_API fx3d_status fx3d_chamfer_fwd(const float *x, int32_t N, const float *y, int32_t M,
