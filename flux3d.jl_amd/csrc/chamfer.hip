@@ -1,4 +1,6 @@
-// Nearest-neighbour + chamfer forward kernels (gfx950).  (The adjoints live in chamfer_bwd.hip.)
+// Nearest-neighbour + chamfer forward: the fp16-filter kernel (gfx950).  (The exact kernels live in nn1_exact.hip, the launch
+// plan, the workspace layout, the drivers and the C entry points in chamfer_host.hip, what they share in nn1_common.h, the adjoints
+// in chamfer_bwd.hip.  This file is the source the nn1 kernel is built from: no host path beyond the two launchers at its end.)
 //
 // Replaces _nearest_neighbors(::CuArray,::CuArray) + the gather / mean of _chamfer_distance (src/metrics/pcloud.jl:39-52,
 // 72-86): the reference materialises the (N,M,B) matrix and runs two argmin passes over it; here every cloud is read from HBM
@@ -7,11 +9,11 @@
 //   d = ((dx dx) + dy dy) + dz dz  in Float32, no fused multiply-add (-ffp-contract=off), ordered like Julia's `isless`,
 //   lowest index on ties  ==  oracle/flux3d_oracle.c: nn1_dir.
 //
-// Kernels, by the launch plan's choice (make_plan; fx3d_nn1_plan_describe prints it):
+// Kernels of the family, by the launch plan's choice (chamfer_host.hip: make_plan; fx3d_nn1_plan_describe prints it):
 //   * nn1_f16_kernel (D = 3, the default) -- FILTER on the matrix cores, exact re-scan of what survives.  The
 //     argmin of the distance is the argmin of t = |c'|^2 - 2 q'.c' (cloud centred on its mean, scaled by a power of two), a
 //     K = 16 inner product of 2-way fp16 splits: ONE v_mfma_f32_32x32x16_f16 per 32 x 32 pairs, 8 v_min3 fold 16 rows, a few
-//     VALU ops track each lane's three smallest lane tiles; every candidate inside the error band of the running minimum goes
+//     VALU ops track each lane's five smallest 32-candidate blocks; every candidate inside the error band of the running minimum goes
 //     to a wave-cooperative exact phase (the oracle's arithmetic, 64-bit LDS atomicMin on (distance bits, index)).  1024-thread
 //     blocks share one fp16 image of up to 4096 candidates (128 KiB of LDS), 512 queries per pass, XCD-aware block ids
 //     (block L runs on XCD L % 8: a cloud's blocks share that XCD's L2); larger clouds run in chunks, or as candidate SUBSETS
@@ -19,18 +21,12 @@
 //     range + exact side list for far outliers; a per-query power-of-two scale for queries far outside the cloud.  The loss is
 //     finalised in the same launch (Float64 partials, agent-scope ticket, fixed summation order).  Bound by the matrix pipe +
 //     the VALU fold behind it: roofline.frac 0.27 of the dense f16 peak.
-//   * nn1_tiny_kernel (D = 3, problems below ~24 M pair evaluations) -- the exact loop with candidates broadcast along DPP
-//     rows: no statistics, no image, no barrier before the arithmetic.
-//   * nn1_small_d_kernel<DIM, R> (D = 2, and D = 3 under option nn1_variant = 0: the A/B reference) -- the exact VALU loop of
-//     round 1: candidates staged through LDS as structure-of-arrays, tiles of 32 folded by v_min3, the winning tile re-scanned
-//     with the reference's strict `<`.
-//   * nn1_generic_kernel (any other D).
-#include <atomic>
+//   * nn1_tiny_kernel, nn1_small_d_kernel, nn1_generic_kernel -- the exact loops (small D = 3 problems; D = 2 and the A/B
+//     reference; any other D): nn1_exact.hip.
+// nn1_split_finalize_kernel (below the fp16 kernel) unpacks the rows of a candidate-split run that did not merge them itself.
 #include <cmath>
-#include <cstdlib>
-#include <mutex>
 
-#include "fx3d_common.h"
+#include "nn1_common.h"
 
 using namespace fx3d;
 
@@ -56,210 +52,6 @@ __device__ unsigned long long g_probe3[16 * 16 * 8];   // per WAVE stamps of the
 #endif
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kTile = 32;       // candidates per min3 tile
-constexpr int kChunkMax = 4096; // candidates staged in LDS at once (DIM*16 KiB)
-
-struct Nn1Params {
-    const float *x;  // (D,N,B)
-    const float *y;  // (D,M,B)
-    int N, M, B;
-    int32_t *idx_x, *idx_y;  // optional
-    float *dmin_x, *dmin_y;  // optional
-    double *partials;        // [2*Bpad8... ] one per (cloud, tile); optional
-    int tiles;               // max(tiles_x, tiles_y)
-    int tiles_x, tiles_y;
-    int chunk;               // LDS chunk capacity (multiple of kTile)
-    int tpb;                 // fp16 variant: query-tile passes per block (>1 only for one-chunk clouds), x -> y direction
-    int tpb_y;               // ... y -> x direction (clouds of different sizes: the plan balances the two directions' blocks)
-    // fused finalisation (fp16 variant): the last block to arrive reduces the partials in fixed order
-    unsigned int *ticket;    // library-owned arrival counter, zero between launches; nullptr = no fusion
-    unsigned int nvalid;     // number of blocks that deliver a partial
-    double *sums_out;        // [2] optional
-    float *loss_out;         // optional
-    float w1, w2;
-    long long Bg;
-    // candidate split (few, large clouds): blocks of one query tile take different chunk subsets and
-    // merge per query through 64-bit atomics in global scratch; nn1_split_finalize_kernel unpacks
-    int nsplit;                  // 1 = off
-    unsigned long long *gres;    // [nsplit][2B][qstride] packed (d_bits << 32 | index): every split block stores its own row (no init, no atomics)
-    int qstride;
-    int fuse_split;              // 1: the last block of a query tile's chunk subsets merges their rows itself (arrival counters in the ticket slot's spare words)
-    int tail;                    // > 0: a cloud of chunk + (1 .. tail) points is ONE chunk + a tail every query evaluates exactly
-    // spatial pruning (round 6, nn1_f16_kernel<.., PRUNE = true>): per-block scratch in the caller's workspace -- the block's candidate
-    // cloud in image order and its window of the query cloud in processing order, as (x, y, z, original index) rows
-    float4 *pscr;                // nullptr: the launch runs the PRUNE = false instantiation
-    int pscr_stride;             // rows per block: kHChunkMax candidates + the query window (passes x 512 + kHTail)
-};
-
-__device__ __forceinline__ float min3f(float a, float b, float c) {
-    return __builtin_fminf(__builtin_fminf(a, b), c);
-}
-
-template <int DIM>
-__device__ __forceinline__ float sqd(const float (&q)[DIM], const float (&c)[DIM]) {
-    float t0 = q[0] - c[0];
-    float s = t0 * t0;
-#pragma unroll
-    for (int d = 1; d < DIM; ++d) {
-        float t = q[d] - c[d];
-        s = s + t * t;
-    }
-    return s;
-}
-
-// Order of distances = the oracle's (oracle/flux3d_oracle.c: fless): Julia's isless on Float32 -- ascending, every NaN
-// after +Inf, all NaNs equal -- then the lower index.  Squared distances are >= +0 or NaN, so the order is the unsigned
-// order of the bit patterns once NaNs are canonical; finite data never produces a NaN distance (at worst +Inf), and
-// the hot paths below only pay for this on data that is not finite.
-__device__ __forceinline__ bool fless(float a, float b) { return (a < b) || (b != b && a == a); }
-__device__ __forceinline__ unsigned int dist_key(float d) { return d != d ? 0x7fc00000u : __builtin_bit_cast(unsigned int, d); }
-
-// exact scan of a whole cloud in that order (the rare exit of the exact-loop kernels: no distance below +Inf)
-template <int DIM>
-__device__ __forceinline__ void nn1_scan_isless(const float (&q)[DIM], const float *__restrict__ cb, int NC, float &best, int &bi) {
-    float c0[DIM];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) c0[d] = cb[d];
-    best = sqd<DIM>(q, c0);
-    bi = 0;
-    for (int j = 1; j < NC; ++j) {
-        float cc[DIM];
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) cc[d] = cb[(size_t)j * DIM + d];
-        const float dd = sqd<DIM>(q, cc);
-        if (fless(dd, best)) { best = dd; bi = j; }
-    }
-}
-
-template <int DIM, int R, bool WANT_IDX>
-__global__ __launch_bounds__(kThreads) void nn1_small_d_kernel(Nn1Params p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-
-    // ---- XCD-aware decode of the linear block id -> (cloud c, query tile) ------------------
-    const int L = blockIdx.x;
-    const int xcd = L & 7, slot = L >> 3;
-    const int c = (slot / p.tiles) * 8 + xcd;  // cloud id in [0, 2B): dir = c / B
-    const int tile = slot % p.tiles;
-    if (c >= 2 * p.B) return;
-    const int dir = c >= p.B ? 1 : 0;
-    const int b = dir ? c - p.B : c;
-    const int NQ = dir ? p.M : p.N;  // queries
-    const int NC = dir ? p.N : p.M;  // candidates
-    if (tile >= (dir ? p.tiles_y : p.tiles_x)) return;
-    const float *__restrict__ qb = (dir ? p.y : p.x) + (size_t)b * NQ * DIM;
-    const float *__restrict__ cb = (dir ? p.x : p.y) + (size_t)b * NC * DIM;
-
-    const int tid = threadIdx.x;
-    const int CH = p.chunk;
-    const int CH4 = CH >> 2;
-    const float4 *lds4 = reinterpret_cast<const float4 *>(lds);
-
-    // ---- queries into registers (out-of-range lanes clamp to the last point) ---------------
-    float q[R][DIM];
-    int qi[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        qi[r] = tile * (kThreads * R) + r * kThreads + tid;
-        const int qc = qi[r] < NQ ? qi[r] : NQ - 1;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) q[r][d] = qb[(size_t)qc * DIM + d];
-    }
-
-    float best[R];
-    int btile[R], bidx[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) { best[r] = INFINITY; btile[r] = -1; bidx[r] = 0; }
-
-    for (int j0 = 0; j0 < NC; j0 += CH) {
-        const int cnt = (NC - j0) < CH ? (NC - j0) : CH;
-        const int cnt_pad = (cnt + kTile - 1) / kTile * kTile;
-        if (j0 > 0) __syncthreads();
-        // ---- stage chunk: AoS global stream -> SoA LDS (coalesced dword reads) -------------
-        for (int e = tid; e < cnt * DIM; e += kThreads) {
-            const float v = cb[(size_t)j0 * DIM + e];
-            const int pt = e / DIM, cc = e - pt * DIM;
-            lds[cc * CH + pt] = v;
-        }
-        for (int e = cnt + tid; e < cnt_pad; e += kThreads) {
-#pragma unroll
-            for (int d = 0; d < DIM; ++d) lds[d * CH + e] = INFINITY;
-        }
-        __syncthreads();
-
-        const int ntile = cnt_pad / kTile;
-        const int tile_base = j0 / kTile;  // CH is a multiple of kTile
-        for (int t = 0; t < ntile; ++t) {
-            float tm[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) tm[r] = INFINITY;
-#pragma unroll
-            for (int jj = 0; jj < kTile; jj += 4) {
-                float4 cv[DIM];
-#pragma unroll
-                for (int d = 0; d < DIM; ++d)  // float4 units: CH % 32 == 0 => always ds_read_b128
-                    cv[d] = lds4[d * CH4 + t * (kTile / 4) + jj / 4];
-                float c0[DIM], c1[DIM], c2[DIM], c3[DIM];
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) { c0[d] = cv[d].x; c1[d] = cv[d].y; c2[d] = cv[d].z; c3[d] = cv[d].w; }
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const float d0 = sqd<DIM>(q[r], c0), d1 = sqd<DIM>(q[r], c1);
-                    const float d2 = sqd<DIM>(q[r], c2), d3 = sqd<DIM>(q[r], c3);
-                    tm[r] = min3f(tm[r], d0, d1);
-                    tm[r] = min3f(tm[r], d2, d3);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const bool better = tm[r] < best[r];  // strict: first tile holding the minimum
-                best[r] = better ? tm[r] : best[r];
-                btile[r] = better ? tile_base + t : btile[r];
-            }
-        }
-
-        if (WANT_IDX) {
-            // ---- exact argmin: re-scan the winning tile while its chunk is still in LDS ----
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (btile[r] >= tile_base) {  // improved within this chunk
-                    const int off = (btile[r] - tile_base) * kTile;
-                    float cur = INFINITY;
-                    int ci = 0;
-                    for (int jj = 0; jj < kTile; ++jj) {
-                        float cc[DIM];
-#pragma unroll
-                        for (int d = 0; d < DIM; ++d) cc[d] = lds[d * CH + off + jj];
-                        const float dd = sqd<DIM>(q[r], cc);
-                        if (dd < cur) { cur = dd; ci = jj; }
-                    }
-                    bidx[r] = j0 + off + ci;
-                }
-            }
-        }
-    }
-
-    // ---- outputs ------------------------------------------------------------------------------
-    int32_t *idx_out = dir ? p.idx_y : p.idx_x;
-    float *dmin_out = dir ? p.dmin_y : p.dmin_x;
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (qi[r] < NQ) {
-            // nothing below +Inf (overflowing or non-finite coordinates): min3 / `<` skipped every candidate
-            if (!(best[r] < INFINITY)) nn1_scan_isless<DIM>(q[r], cb, NC, best[r], bidx[r]);
-            if (WANT_IDX && idx_out) idx_out[(size_t)b * NQ + qi[r]] = bidx[r];
-            if (dmin_out) dmin_out[(size_t)b * NQ + qi[r]] = best[r];
-            acc += (double)best[r];
-        }
-    }
-    if (p.partials) {
-        __shared__ double sm[kThreads / 64];
-        const double tot = block_sum<kThreads>(acc, sm);
-        if (tid == 0) p.partials[(size_t)c * p.tiles + tile] = tot;
-    }
-}
 
 // four consecutive points (12 floats) as three 16-byte loads; needs 16-B aligned base and p0 % 4 == 0
 __device__ __forceinline__ void load4pts(const float *__restrict__ base, int p0, float (&px)[4],
@@ -293,85 +85,6 @@ __device__ __forceinline__ void load4pts(const float *__restrict__ base, int p0,
 //   32-candidate block; the two half-waves are merged through the per-query LDS slot.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ float chamfer_loss_from_sums(double sa, double sb, int N, int M, int D,
-                                                        long long Bg, float w1, float w2);
-
-// The tail of a launch with fused finalisation, run by the FIRST WAVE of every block after the block's sum `tot` has
-// arrived in its lane 0: publish the partial (8-byte agent-scope store -> drain -> relaxed ticket), and the last arriver
-// reduces all partials in a fixed order and writes the sums / the loss.  That reduction is the launch's tail -- every
-// other CU is idle by then --, so it is one wave, all its loads in flight together (four per lane and direction), DPP
-// double adds, no barrier, 32-bit index math (the block-wide version with two barrier rounds and 64-bit divisions took
-// 6.0 k cycles from ticket to end at C2; this one 2.3 k).  `slot`: this block's entry; rows of `stride` entries per
-// (direction, cloud), the first tiles_x / tiles_y of a row are valid.
-// MEMORY-ORDER NOTE (applies to this hand-off and to the fused split merge further down).  The protocol is
-//   producer:  agent-scope RELAXED atomic stores of the data (sc1: they go THROUGH the XCD's L2 to memory) -> s_waitcnt vmcnt(0) (the
-//              stores have left the CU and are acknowledged) -> relaxed agent-scope fetch_add on the counter
-//   consumer:  the last arriver's relaxed agent-scope atomic LOADS of the data (sc1: served from memory / the coherent fabric,
-//              never from a stale line of its own XCD's L2)
-// i.e. ordering by completion (waitcnt) + coherence by the access kind, not by release / acquire fences.  It is outside the HIP /
-// LLVM memory model on purpose: an agent-scope RELEASE on gfx942 / gfx950 is `buffer_wbl2 sc1` -- a write-back of the WHOLE L2 of
-// the XCD -- and was measured at 32 -> 94 us on the split runs (round 5); with the pruning scratch of round 6 dirty in L2 (21 MB per
-// launch) it would cost more.  The `asm volatile("s_waitcnt vmcnt(0)" ::: "memory")` is both the hardware wait and the compiler
-// barrier (no store may sink below it, no load of the counter may rise above it).  The assumption -- sc1 stores are visible to sc1
-// loads of every XCD once vmcnt has drained -- is MI355X_MICROARCH.md's "valid forms" table; the library is built for gfx950 only:
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "chamfer.hip: the relaxed-atomic + s_waitcnt hand-off between blocks is validated on gfx950 only (see the note above)"
-#endif
-struct FinalizeArgs {
-    unsigned long long *pp;
-    unsigned int *ticket;
-    unsigned int nvalid;
-    int B, stride, tiles_x, tiles_y;
-    double *sums_out;
-    float *loss_out;
-    int N, M;
-    long long Bg;
-    float w1, w2;
-};
-__device__ __forceinline__ int fused_finalize_wave0(const FinalizeArgs &f, size_t slot, double tot, int lane) {
-    int last = 0;
-    if (lane == 0) {
-        __hip_atomic_store(&f.pp[slot], __builtin_bit_cast(unsigned long long, tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int old = __hip_atomic_fetch_add(f.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = old == f.nvalid - 1;
-    }
-    last = __builtin_amdgcn_readfirstlane(last);
-    if (!last) return 0;
-    // lane l sums entries l, l + 64, ... of a direction in order (four of each direction in flight), then the DPP tree
-    double a[2] = {0.0, 0.0};
-    const unsigned int n0 = (unsigned int)f.B * (unsigned int)f.tiles_x, n1 = (unsigned int)f.B * (unsigned int)f.tiles_y;  // (< 2^30: check_shapes)
-    for (unsigned int k0 = lane; k0 < n0 || k0 < n1; k0 += 64 * 4) {
-        unsigned long long v[2][4];
-#pragma unroll
-        for (int dd = 0; dd < 2; ++dd)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const unsigned int nt = dd ? f.tiles_y : f.tiles_x;
-                const unsigned int k = k0 + 64 * u, kc = k < (dd ? n1 : n0) ? k : 0;
-                // (directions of equal tile counts -- the usual case -- : rows are dense, no division)
-                const size_t e = nt == (unsigned int)f.stride ? (size_t)dd * f.B * f.stride + kc : ((size_t)(dd * f.B) + kc / nt) * f.stride + kc % nt;
-                v[dd][u] = __hip_atomic_load(&f.pp[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-        for (int dd = 0; dd < 2; ++dd)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (k0 + 64 * u < (dd ? n1 : n0)) a[dd] += __builtin_bit_cast(double, v[dd][u]);
-    }
-    const double t0 = wave_sum_l63_f64(a[0]), t1 = wave_sum_l63_f64(a[1]);
-    if (lane == 63) {
-        if (f.sums_out) { f.sums_out[0] = t0; f.sums_out[1] = t1; }
-        if (f.loss_out) *f.loss_out = chamfer_loss_from_sums(t0, t1, f.N, f.M, 3, f.Bg, f.w1, f.w2);
-        __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for reuse
-    }
-    return 1;
-}
-constexpr int kHThreads = 1024;   // 16 waves share one LDS image: 1 block per CU, 4 waves per SIMD
-#ifndef FX3D_HLT
-#define FX3D_HLT 2
-#endif
-constexpr int kHLT = FX3D_HLT;    // 32-candidate blocks per lane tile (lane sees 16 rows of each)
 #ifndef FX3D_HFIFO
 #define FX3D_HFIFO 5
 #endif
@@ -382,7 +95,6 @@ constexpr int kHFifo = FX3D_HFIFO;  // minima tracked per lane and pass (round 6
                                     // collinear A == B input at n = 16384: 68.4 -> 55.0 us, a 1/16 lattice A == B at C2's shape 109 -> 88;
                                     // uniform C2 unchanged, 51.0 -> 50.5 .. 50.9 on one box: the extra v_med3 per lane tile hides under the MFMAs);
                                     // five / six cost uniform C2 0.5 - 1.4 us and make the A != B lattice slower (99 -> 122 / 129 us)
-constexpr int kHChunkMax = 4096;  // 32 B per candidate => 128 KiB
 #ifndef FX3D_HRUNS_FROM
 #define FX3D_HRUNS_FROM 16
 #endif
@@ -395,9 +107,6 @@ constexpr int kHRunCap = FX3D_HRUNCAP;        // the retry pass's list of RUN it
                                     // appends at most 256, the list is drained when fewer are free
 constexpr int kHItemCap = 64 * kHFifo > kHRunCap ? 64 * kHFifo : kHRunCap;  // (the FIFO path never overflows its 64 * kHFifo)
 constexpr int kHFarCap = 64;      // far candidates kept on the exact side list; more: the chunk falls back to exact scans
-constexpr int kHTail = 64;        // a cloud of up to kHChunkMax + kHTail points stays one LDS image: the last <= 64 candidates are
-                                  // compared exactly by every query (N = M = 4097 was 2.1 x N = M = 4096: two half-empty chunks,
-                                  // three rounds of blocks), and <= 64 queries beyond a block's passes are one more pass of one wave
 #ifndef FX3D_HBLKTRACK
 #define FX3D_HBLKTRACK 1
 #endif
@@ -434,7 +143,6 @@ __device__ const unsigned short kHilbertCell[512] = {
     199, 198, 134, 135, 143, 142, 206, 207, 215, 223, 159, 151, 150, 158, 222, 214, 213, 221, 220, 212, 148, 156, 157, 149, 141, 205, 204, 140, 132, 196, 197, 133,
     69, 5, 4, 68, 76, 12, 13, 77, 85, 93, 92, 84, 20, 28, 29, 21, 22, 30, 94, 86, 87, 95, 31, 23, 15, 14, 78, 79, 71, 70, 6, 7,
 };
-constexpr int kHGroupsMax = 8 * 16 + 2 + 1;  // (PRUNE) 32-query groups of a block's window: up to eight passes + the folded remainder; + one slot: the query cloud's box
 constexpr size_t kHScratchBytes = (kHThreads / 64) * (32 * 8 + kHItemCap * 2 + 32 * 3 * 4) + 64 * 32;  // + 2 pad blocks
 
 // plain v_min_f32 (fminf() also emits a canonicalising v_max in IEEE mode; the filter values are never
@@ -1780,790 +1488,36 @@ __global__ __launch_bounds__(kThreads) void nn1_split_finalize_kernel(Nn1Params 
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// nn1_tiny_kernel (D = 3, round 4): the exact loop for SMALL problems -- 2 B N M below a few ten million pair evaluations
-// (C1, the reference harness's n <= 4096: benchmarks/metrics.jl:40) -- where nn1_f16_kernel's per-cloud statistics, image
-// and 1024-thread blocks are all overhead (C1 17.6 us, n = 64: 13.7 us; an empty launch is ~6 us).  No statistics, no
-// image, no filter, no LDS staging, no barrier before the arithmetic: a 256-thread block owns 16 R queries and ALL
-// candidates of their cloud.  Lane l of wave w holds query l & 15 (+ 16 r) and works on candidate slice s = 4 w + (l >> 4)
-// of 16 contiguous slices.  The slice is consumed in groups of 16 candidates: lane l LOADS candidate (l & 15) of the group
-// (one 12-byte global load per lane and 16 pairs; consecutive lanes, consecutive points) and every lane of the 16-lane
-// row reads it through the DPP row broadcast of the subtraction itself (v_subrev_f32_dpp row_newbcast:i: no move, no LDS):
-// 8 VALU per pair for the oracle's unfused ((dx dx) + dy dy) + dz dz, 8 v_min3 per group of 16, 3 for (best, best group)
-// with a strict `<`.  The winning group is re-scanned for the FIRST candidate that attains the minimum, so a lane's
-// result is its slice's (distance, lowest index); the 16 slices of a query meet in a 64-bit LDS atomicMin on
-// (distance bits << 32 | index) -- the oracle's order (isless, then the lower index; no NaN passes `<`, a query without
-// any distance below +Inf takes nn1_scan_isless).  Loss: per-block Float64 partial + nn1_f16_kernel's fused finalisation.
-constexpr int kTyThreads = 256;
-constexpr int kTyQ = 16;                      // queries per 16-lane row
-constexpr int kTySl = 16;                     // candidate slices per block (4 per wave, one per DPP row)
-constexpr int kTyG = 16;                      // candidates per group (one per lane of a row)
-
-template <int I>
-__device__ __forceinline__ float row_bcast(float v) {  // lane (l & ~15) + I of every 16-lane row, read by the consuming instruction's DPP operand
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + I, 0xF, 0xF, false));
-}
-template <int I>
-__device__ __forceinline__ float tiny_d(const float (&q)[3], float cx, float cy, float cz) {
-    const float t0 = q[0] - row_bcast<I>(cx), t1 = q[1] - row_bcast<I>(cy), t2 = q[2] - row_bcast<I>(cz);
-    return ((t0 * t0) + (t1 * t1)) + (t2 * t2);
-}
-__device__ __forceinline__ void tiny_group(const float (&q)[3], float cx, float cy, float cz, float (&d)[kTyG]) {
-    d[0] = tiny_d<0>(q, cx, cy, cz); d[1] = tiny_d<1>(q, cx, cy, cz); d[2] = tiny_d<2>(q, cx, cy, cz); d[3] = tiny_d<3>(q, cx, cy, cz);
-    d[4] = tiny_d<4>(q, cx, cy, cz); d[5] = tiny_d<5>(q, cx, cy, cz); d[6] = tiny_d<6>(q, cx, cy, cz); d[7] = tiny_d<7>(q, cx, cy, cz);
-    d[8] = tiny_d<8>(q, cx, cy, cz); d[9] = tiny_d<9>(q, cx, cy, cz); d[10] = tiny_d<10>(q, cx, cy, cz); d[11] = tiny_d<11>(q, cx, cy, cz);
-    d[12] = tiny_d<12>(q, cx, cy, cz); d[13] = tiny_d<13>(q, cx, cy, cz); d[14] = tiny_d<14>(q, cx, cy, cz); d[15] = tiny_d<15>(q, cx, cy, cz);
-}
-
-// kTyPF = groups in flight per lane (4; 1 for clouds of <= 256 candidates: a quarter of the code -- the smallest launches are
-// eight blocks on eight cold instruction caches).
-template <int R, int kTyPF, bool WANT_IDX>
-__global__ __launch_bounds__(kTyThreads) void nn1_tiny_kernel(Nn1Params p) {
-    __shared__ unsigned long long slot[2][kTyQ * R];
-    const int tiles = p.tiles;
-    const int c = blockIdx.x / tiles, btile = blockIdx.x - c * tiles;   // cloud id in [0, 2B): dir = c / B
-    const int dir = c >= p.B ? 1 : 0;
-    const int b = dir ? c - p.B : c;
-    const int NQ = dir ? p.M : p.N, NC = dir ? p.N : p.M;
-    if (btile >= (dir ? p.tiles_y : p.tiles_x)) return;
-    const float *__restrict__ qb = (dir ? p.y : p.x) + (size_t)b * NQ * 3;
-    const float *__restrict__ cb = (dir ? p.x : p.y) + (size_t)b * NC * 3;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ql = lane & 15, s = wave * 4 + (lane >> 4);
-    // slice s = candidates [s L, (s + 1) L), L a multiple of 16; this lane loads candidate jl + 16 g of group g
-    const int L = ((NC + kTySl - 1) / kTySl + kTyG - 1) / kTyG * kTyG;
-    const int ngroups = L / kTyG;
-    const int jl = s * L + ql;
-    auto load_group = [&](int g, float &cx, float &cy, float &cz) {
-        const int j = jl + kTyG * g;
-        const bool ok = g < ngroups && j < NC;
-        const P3 t = *reinterpret_cast<const P3 *>(cb + 3ll * (ok ? j : 0));
-        cx = ok ? t.x : INFINITY; cy = ok ? t.y : INFINITY; cz = ok ? t.z : INFINITY;   // padding at +Inf: never below anything
-    };
-    float cur[kTyPF][3], nxt[kTyPF][3];
-#pragma unroll
-    for (int u = 0; u < kTyPF; ++u) load_group(u, cur[u][0], cur[u][1], cur[u][2]);
-    const bool resident = ngroups <= kTyPF;   // the lane's share of the cloud stays in registers across the block's query tiles
-    if (tid < 2 * kTyQ * R) (&slot[0][0])[tid] = ~0ull;
-    __syncthreads();
-
-    // a block takes p.tpb consecutive query tiles of its cloud (one partial sum, one arrival at the ticket per BLOCK: with a
-    // block per tile the 1024+ same-address atomics and the last arriver's pass over as many partials were the launch's tail)
-    const int raw_tiles = (NQ + kTyQ * R - 1) / (kTyQ * R);
-    int32_t *idx_out = dir ? p.idx_y : p.idx_x;
-    float *dmin_out = dir ? p.dmin_y : p.dmin_x;
-    double acc = 0.0;
-    auto load_queries = [&](int tile, float (&qq)[R][3]) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int qi = tile * (kTyQ * R) + r * kTyQ + ql;
-            const P3 t = *reinterpret_cast<const P3 *>(qb + 3ll * (qi < NQ ? qi : NQ - 1));
-            qq[r][0] = t.x; qq[r][1] = t.y; qq[r][2] = t.z;
-        }
-    };
-    float qn[R][3];
-    load_queries(btile * p.tpb, qn);
-    for (int tt = 0; tt < p.tpb; ++tt) {
-        const int tile = btile * p.tpb + tt;
-        if (tile >= raw_tiles) break;   // (block-uniform)
-        float q[R][3];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { q[r][0] = qn[r][0]; q[r][1] = qn[r][1]; q[r][2] = qn[r][2]; }
-        if (tt + 1 < p.tpb) load_queries(tile + 1, qn);   // the next tile's queries travel while this one is evaluated
-        if (!resident && tt > 0) {
-#pragma unroll
-            for (int u = 0; u < kTyPF; ++u) load_group(u, cur[u][0], cur[u][1], cur[u][2]);
-        }
-        float best[R];
-        int bg[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { best[r] = INFINITY; bg[r] = 0; }
-        for (int g0 = 0; g0 < ngroups; g0 += kTyPF) {
-            if (g0 + kTyPF < ngroups) {
-#pragma unroll
-                for (int u = 0; u < kTyPF; ++u) load_group(g0 + kTyPF + u, nxt[u][0], nxt[u][1], nxt[u][2]);
-            }
-#pragma unroll
-            for (int u = 0; u < kTyPF; ++u) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    float d[kTyG];
-                    tiny_group(q[r], cur[u][0], cur[u][1], cur[u][2], d);
-                    float m = min3f(d[0], d[1], d[2]);
-                    m = min3f(m, d[3], d[4]);
-                    m = min3f(m, d[5], d[6]);
-                    m = min3f(m, d[7], d[8]);
-                    m = min3f(m, d[9], d[10]);
-                    m = min3f(m, d[11], d[12]);
-                    m = min3f(m, d[13], d[14]);
-                    m = __builtin_fminf(m, d[15]);
-                    const bool better = m < best[r];  // strict: the first group that holds the lane's minimum
-                    best[r] = better ? m : best[r];
-                    if (WANT_IDX) bg[r] = better ? g0 + u : bg[r];
-                }
-            }
-            if (g0 + kTyPF < ngroups) {
-#pragma unroll
-                for (int u = 0; u < kTyPF; ++u) { cur[u][0] = nxt[u][0]; cur[u][1] = nxt[u][1]; cur[u][2] = nxt[u][2]; }
-            }
-        }
-        unsigned long long *sl = slot[tt & 1];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            int bi = 0;
-            if (WANT_IDX) {
-                // the FIRST candidate of the lane's winning group that attains the minimum.  The winning groups differ lane by
-                // lane, so every lane reads the 16 candidates of its own (16 loads in flight, L1 / L2 hits)
-                float d[kTyG];
-#pragma unroll
-                for (int i = 0; i < kTyG; ++i) {
-                    const int j = s * L + kTyG * bg[r] + i;
-                    const P3 t = *reinterpret_cast<const P3 *>(cb + 3ll * (j < NC ? j : 0));
-                    const float t0 = q[r][0] - t.x, t1 = q[r][1] - t.y, t2 = q[r][2] - t.z;
-                    d[i] = j < NC ? ((t0 * t0) + (t1 * t1)) + (t2 * t2) : INFINITY;
-                }
-#pragma unroll
-                for (int i = kTyG - 1; i >= 0; --i)
-                    if (d[i] == best[r]) bi = s * L + kTyG * bg[r] + i;
-            }
-            if (best[r] < INFINITY)
-                atomicMin(&sl[r * kTyQ + ql], ((unsigned long long)__builtin_bit_cast(unsigned int, best[r]) << 32) | (unsigned int)bi);
-        }
-        __syncthreads();
-        // the first wave writes the tile's results (16 R <= 32 queries) and returns the slots to "empty"; the other buffer
-        // takes the next tile's minima meanwhile (this buffer is used again two tiles on, behind the next barrier)
-        const int qidx = tile * (kTyQ * R) + tid;
-        if (tid < kTyQ * R) {
-            const unsigned long long k = sl[tid];
-            sl[tid] = ~0ull;
-            if (qidx < NQ) {
-                float dd = __builtin_bit_cast(float, (unsigned int)(k >> 32));
-                int ii = (int)(unsigned int)k;
-                if (k == ~0ull) {  // nothing below +Inf (non-finite or overflowing coordinates): the exact scan in isless order
-                    const P3 t = *reinterpret_cast<const P3 *>(qb + 3ll * qidx);
-                    const float qq[3] = {t.x, t.y, t.z};
-                    nn1_scan_isless<3>(qq, cb, NC, dd, ii);
-                }
-                if (WANT_IDX && idx_out) idx_out[(size_t)b * NQ + qidx] = ii;
-                if (dmin_out) dmin_out[(size_t)b * NQ + qidx] = dd;
-                acc += (double)dd;
-            }
-        }
-    }
-    if (tid >= 64 || !p.partials) return;
-    const double tot = __shfl(wave_sum_l63_f64(acc), 63);   // fixed order: deterministic
-    if (!p.ticket) {
-        if (tid == 0) p.partials[(size_t)c * tiles + btile] = tot;
-        return;
-    }
-    const FinalizeArgs fa{reinterpret_cast<unsigned long long *>(p.partials), p.ticket, p.nvalid, p.B, tiles, p.tiles_x, p.tiles_y,
-                          p.sums_out, p.loss_out, p.N, p.M, p.Bg, p.w1, p.w2};
-    (void)fused_finalize_wave0(fa, (size_t)c * tiles + btile, tot, tid);
-}
-
-// Generic dimension (D == 1 or D > 3): one thread per query, candidates read through L1/L2.
-// Correct for any D; not the tuned path (the chamfer configs are all D = 3).
-// 1-D grid of p.tiles blocks per cloud: 2B clouds on the grid's y dimension would stop at maxGridSize[1] = 65536
-// (B = 32768), which check_shapes does not bound.
-__global__ __launch_bounds__(kThreads) void nn1_generic_kernel(Nn1Params p, int D) {
-    const int c = blockIdx.x / p.tiles;
-    const int dir = c >= p.B ? 1 : 0;
-    const int b = dir ? c - p.B : c;
-    const int NQ = dir ? p.M : p.N, NC = dir ? p.N : p.M;
-    const int tile = blockIdx.x - c * p.tiles;
-    const float *__restrict__ qb = (dir ? p.y : p.x) + (size_t)b * NQ * D;
-    const float *__restrict__ cb = (dir ? p.x : p.y) + (size_t)b * NC * D;
-    const int i = tile * kThreads + threadIdx.x;
-    double acc = 0.0;
-    if (i < NQ) {
-        float best = 0.0f;
-        int bi = 0;
-        const float *a = qb + (size_t)i * D;
-        for (int j = 0; j < NC; ++j) {
-            const float *cc = cb + (size_t)j * D;
-            float s = 0.0f;
-            for (int d = 0; d < D; ++d) { float t = a[d] - cc[d]; s = s + t * t; }
-            if (j == 0 || fless(s, best)) { best = s; bi = j; }
-        }
-        int32_t *idx_out = dir ? p.idx_y : p.idx_x;
-        float *dmin_out = dir ? p.dmin_y : p.dmin_x;
-        if (idx_out) idx_out[(size_t)b * NQ + i] = bi;
-        if (dmin_out) dmin_out[(size_t)b * NQ + i] = best;
-        acc = (double)best;
-    }
-    if (p.partials) {
-        __shared__ double sm[kThreads / 64];
-        const double tot = block_sum<kThreads>(acc, sm);
-        // blocks past this direction's tile count still write (zero) so the reduce is uniform
-        if (threadIdx.x == 0) p.partials[(size_t)c * p.tiles + tile] = tot;
-    }
-}
-
-// Fixed-order reduction of the per-block partials into sums[0..1] (+ optional loss).
-struct FinalizeParams {
-    const double *partials;
-    int B, tiles, tiles_x, tiles_y;
-    double *sums;  // [2]
-    // optional loss (loss != nullptr)
-    float *loss;
-    int N, M, D;
-    long long Bg;
-    float w1, w2;
-};
-
-__device__ __forceinline__ float chamfer_loss_from_sums(double sa, double sb, int N, int M, int D,
-                                                        long long Bg, float w1, float w2) {
-    // mean(...) * 3.0f0, src/metrics/pcloud.jl:47-48 ; w1*dA + w2*dB, :50
-    const float dA = (float)(sa / ((double)D * (double)N * (double)Bg)) * 3.0f;
-    const float dB = (float)(sb / ((double)D * (double)M * (double)Bg)) * 3.0f;
-    return (w1 * dA) + (w2 * dB);
-}
-
-__global__ __launch_bounds__(kThreads) void chamfer_finalize_partials_kernel(FinalizeParams f) {
-    __shared__ double sm[kThreads / 64];
-    double tot[2];
-    for (int dir = 0; dir < 2; ++dir) {
-        const int nt = dir ? f.tiles_y : f.tiles_x;
-        const long long n = (long long)f.B * nt;
-        double acc = 0.0;
-        for (long long k = threadIdx.x; k < n; k += kThreads) {
-            const int b = (int)(k / nt), t = (int)(k % nt);
-            acc += f.partials[((size_t)(dir * f.B + b)) * f.tiles + t];
-        }
-        __syncthreads();
-        tot[dir] = block_sum<kThreads>(acc, sm);
-    }
-    if (threadIdx.x == 0) {
-        if (f.sums) { f.sums[0] = tot[0]; f.sums[1] = tot[1]; }
-        if (f.loss) *f.loss = chamfer_loss_from_sums(tot[0], tot[1], f.N, f.M, f.D, f.Bg, f.w1, f.w2);
-    }
-}
-
-__global__ void chamfer_loss_kernel(const double *sums, int N, int M, int D, long long Bg,
-                                    float w1, float w2, float *loss) {
-    if (threadIdx.x == 0 && blockIdx.x == 0)
-        *loss = chamfer_loss_from_sums(sums[0], sums[1], N, M, D, Bg, w1, w2);
-}
-
-__global__ void chamfer_loss_many_kernel(const double *sums, int count, int N, int M, int D, long long Bg,
-                                         float w1, float w2, float *loss) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) loss[i] = chamfer_loss_from_sums(sums[2 * i], sums[2 * i + 1], N, M, D, Bg, w1, w2);
-}
-
-struct Plan {
-    int R, tiles_x, tiles_y, tiles, chunk, grid;
-    size_t lds_bytes;
-    int variant;  // 0 = exact hot loop (D = 2, and D = 3 under FX3D_NN1_VARIANT=0), 3 = fp16-split MFMA filter + exact re-scan,
-                  // 4 = nn1_tiny_kernel (D = 3, small problems: exact, no per-cloud statistics / image)
-    int threads, tpb, tpb_y;  // tpb: passes per block of the x -> y direction, tpb_y: of y -> x
-    int nsplit;  // fp16 variant: chunk subsets per query tile (multi-chunk clouds with too few blocks)
-    int tail;    // fp16 variant: kHTail when clouds of chunk + (1 .. kHTail) points run as one chunk + an exact tail
-};
-
-// option nn1_variant = 0 selects the exact VALU loop for D = 3 (A/B measurements; the f32 VALU / MFMA filter variants
-// of round 1 are in the history: DESIGN.md 3.1 "ladder").
-int nn1_variant() { return opt(OPT_NN1_VARIANT) == 0 ? 0 : 3; }
-
-Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
-    Plan pl{};
-    const long long work = (long long)B * ((long long)N + M);  // total queries, both directions
-    pl.variant = D == 3 ? nn1_variant() : 0;
-    pl.threads = pl.variant == 3 ? kHThreads : kThreads;
-    // exact loop: R queries per thread -- enough blocks to fill 256 CUs x ~2 blocks, but as much register
-    // blocking (LDS-read amortisation, ILP) as the problem size allows.
-    int R = 4;
-    while (R > 1 && work / (kThreads * R) < 512) R >>= 1;
-    pl.R = R;
-    pl.tpb = pl.tpb_y = 1;
-    const int maxc0 = N > M ? N : M;
-    const int clouds8 = (2 * B + 7) / 8;
-    pl.nsplit = 1;
-    if (D != 2 && D != 3) {
-        // nn1_generic_kernel: one query per thread, 256-query tiles, no LDS staging
-        pl.R = 1;
-        pl.tiles_x = (N + kThreads - 1) / kThreads;
-        pl.tiles_y = (M + kThreads - 1) / kThreads;
-        pl.tiles = pl.tiles_x > pl.tiles_y ? pl.tiles_x : pl.tiles_y;
-        pl.chunk = 0;
-        pl.lds_bytes = 0;
-        pl.grid = 2 * B * pl.tiles;  // (< 2^30: check_shapes)
-        return pl;
-    }
-    if (pl.variant == 3 && 2ll * B * (long long)N * M <= 1000000ll * opt(OPT_NN1_TINY_MPAIRS)) {
-        // small problem: the exact kernel without statistics / image (C1, the reference harness's n <= 1024).  Two queries per
-        // lane once 16-query blocks would be more than two rounds of the chip
-        pl.variant = 4;
-        pl.threads = kTyThreads;
-        const int cus = device_cus();
-        pl.R = work / kTyQ > 2ll * cus ? 2 : 1;
-        const int per = kTyQ * pl.R;
-        const int rx = (N + per - 1) / per, ry = (M + per - 1) / per;   // query tiles per cloud and direction
-        int tpb = 1;                                                     // consecutive tiles per block: at most ~2 blocks per CU
-        while ((long long)B * ((rx + tpb - 1) / tpb + (ry + tpb - 1) / tpb) > 2ll * cus && tpb < (rx > ry ? rx : ry)) tpb *= 2;
-        pl.tpb = pl.tpb_y = tpb;
-        pl.tiles_x = (rx + tpb - 1) / tpb;
-        pl.tiles_y = (ry + tpb - 1) / tpb;
-        pl.tiles = pl.tiles_x > pl.tiles_y ? pl.tiles_x : pl.tiles_y;
-        pl.chunk = 0;
-        pl.lds_bytes = 0;
-        pl.grid = 2 * B * pl.tiles;
-        return pl;
-    }
-    if (pl.variant == 0) {
-        const int per_block = kThreads * R;
-        pl.tiles_x = (N + per_block - 1) / per_block;
-        pl.tiles_y = (M + per_block - 1) / per_block;
-        pl.tiles = pl.tiles_x > pl.tiles_y ? pl.tiles_x : pl.tiles_y;
-        int chunk = (maxc0 + kTile - 1) / kTile * kTile;
-        if (chunk > kChunkMax) chunk = kChunkMax;
-        pl.chunk = chunk;
-        pl.lds_bytes = (size_t)chunk * D * sizeof(float);
-        pl.grid = clouds8 * 8 * pl.tiles;
-        return pl;
-    }
-    // nn1_f16_kernel: choose (candidate chunk size, chunks per block, 512-query passes per block) by a small
-    // cost model in microseconds, measured at C2 (tools/nn1_probe.hip): bounding box 2.8 per 4096 candidates of
-    // the cloud, image 5.0 per 4096 of the chunk, one pass (filter + exact) 9.7 per 4096, 256 resident blocks.
-    // A block either walks all chunks serially (one pass per block: the per-query slot lives in LDS) or takes
-    // ONE chunk of a split run (any number of passes; the subsets' rows merge in the same launch since round 5).  A split
-    // plan is charged 8 us: no longer a second launch, a FITTED constant -- swept 8 / 5 / 3 over tools/nn1_shapes_time.py's
-    // shapes on one box, only 8 x 8192 x 8192 changes plan, and the lower charges pick the slower one (62 us against 55.5:
-    // the model under-prices 2048-candidate images run four passes each).  Few large clouds want many small chunks, many
-    // small clouds want passes.
-    const int cmax = kHChunkMax, gran = 32 * kHLT;
-    const int ncu = device_cus();  // blocks resident at once: one per CU (256 on an MI355X in SPX mode)
-    // a larger cloud of at most cmax + kHTail points is planned (and run) as ONE chunk of cmax with an exact tail
-    int maxc = maxc0, b_chunk = 0, b_tpb = 1, b_split = 1;
-    auto search = [&](int mc) {  // mc: the candidates that go through LDS images
-        maxc = mc;
-        const int cminc = (maxc + cmax - 1) / cmax;
-        double best = 1e30;
-        b_chunk = (maxc + gran - 1) / gran * gran < cmax ? (maxc + gran - 1) / gran * gran : cmax; b_tpb = 1; b_split = 1;
-        for (int nch = cminc; nch <= cminc * 8 && nch <= 64; ++nch) {
-            int ch = ((maxc + nch - 1) / nch + gran - 1) / gran * gran;
-            if (ch > cmax) continue;
-            const int anch = (maxc + ch - 1) / ch;
-            for (int split = 0; split < 2; ++split) {
-                if (split && (!allow_split || anch == 1 || opt(OPT_NN1_NOSPLIT))) continue;
-                for (int tpb = 1; tpb <= 8; tpb *= 2) {
-                    if (!split && anch > 1 && tpb > 1) continue;
-                    const long long tiles = ((long long)maxc + 512 * tpb - 1) / (512 * tpb);
-                    const long long blocks = 2ll * B * tiles * (split ? anch : 1);
-                    const double per_chunk = 5.0 * ch / 4096.0 + 0.5 + tpb * (9.7 * ch / 4096.0 + 0.8);
-                    const double t_block = 2.8 * maxc / 4096.0 + (split ? 1 : anch) * per_chunk;
-                    const double rounds = (double)((blocks + ncu - 1) / ncu);
-                    const double t = rounds * t_block + (split ? 8.0 : 0.0);
-                    if (t < best - 1e-9) { best = t; b_chunk = ch; b_tpb = tpb; b_split = split ? anch : 1; }
-                }
-            }
-        }
-    };
-    // a cloud of cmax + (1 .. kHTail) points: planned as cmax; kept if that plan is ONE chunk of cmax per block (then the kernel
-    // runs the tail exactly), otherwise planned again at its true size
-    pl.tail = 0;
-    if (maxc0 > cmax && maxc0 - cmax <= kHTail) {
-        search(cmax);
-        if (b_split == 1 && b_chunk == cmax) pl.tail = kHTail;
-    }
-    if (!pl.tail) search(maxc0);
-    pl.chunk = b_chunk;
-    pl.tpb = pl.tpb_y = b_tpb;
-    pl.nsplit = b_split;
-    pl.lds_bytes = (size_t)pl.chunk * 8 * sizeof(float) + kHScratchBytes;
-    if (N != M && b_split == 1 && maxc <= b_chunk) {
-        // clouds of different sizes, one chunk each: the direction whose CANDIDATES are the large cloud has few, heavy blocks
-        // (N = 4096 against M = 1024 at B = 32: 32 blocks as long as C2's on 32 CUs while the rest of the chip idles) -- the
-        // passes per block are chosen per direction: t = the slower direction's block, or the chip's throughput if the
-        // blocks of both do not fit at once (same unit costs as above)
-        double bt = 1e30;
-        for (int ta = 1; ta <= 8; ta *= 2)
-            for (int tb = 1; tb <= 8; tb *= 2) {
-                const double blk_a = 2.8 * M / 4096.0 + 5.0 * M / 4096.0 + 0.5 + ta * (9.7 * M / 4096.0 + 0.8);  // x -> y: candidates y
-                const double blk_b = 2.8 * N / 4096.0 + 5.0 * N / 4096.0 + 0.5 + tb * (9.7 * N / 4096.0 + 0.8);  // y -> x: candidates x
-                const double na = (double)B * ((N + 512 * ta - 1) / (512 * ta)), nb = (double)B * ((M + 512 * tb - 1) / (512 * tb));
-                const double thr = (na * blk_a + nb * blk_b) / (double)ncu;
-                double t = blk_a > blk_b ? blk_a : blk_b;
-                t = t > thr ? t : thr;
-                // the grid has max(tiles) slots per (cloud, direction): more than one round of them delays the heavy direction's blocks
-                const long long tmax = (N + 512 * ta - 1) / (512 * ta) > (M + 512 * tb - 1) / (512 * tb) ? (N + 512 * ta - 1) / (512 * ta) : (M + 512 * tb - 1) / (512 * tb);
-                t += 1.0 * (double)((2ll * B * tmax + ncu - 1) / ncu - 1);
-                if (t < bt - 1e-9) { bt = t; pl.tpb = ta; pl.tpb_y = tb; }
-            }
-    }
-    // one-chunk plans: a remainder of <= kHTail queries beyond a direction's last full tile is one more pass of that tile's block
-    // (one wave busy for ~6 us) instead of a block of its own (prologue + a pass: a second round of blocks at N = 4097)
-    const bool fold = b_split == 1 && maxc <= b_chunk;
-    auto ntiles = [&](int nq, int tpb) {
-        const int per = 512 * tpb;
-        int t = (nq + per - 1) / per;
-        if (fold && t > 1 && nq - (t - 1) * per <= kHTail) --t;
-        return t;
-    };
-    pl.tiles_x = ntiles(N, pl.tpb);
-    pl.tiles_y = ntiles(M, pl.tpb_y);
-    pl.tiles = pl.tiles_x > pl.tiles_y ? pl.tiles_x : pl.tiles_y;
-    pl.grid = clouds8 * 8 * pl.tiles * pl.nsplit;
-    if (2 * B < 8) pl.grid = 2 * B * pl.tiles * pl.nsplit;  // plain block order (see kernel)
-    return pl;
-}
-
-// Spatial pruning (nn1_f16_kernel<.., PRUNE>): one-chunk plans of the fp16 kernel without split or tail, clouds of at least 1024
-// points.  Rows of scratch per block: the candidate cloud in image order + the block's window of the query cloud.
-constexpr size_t kHBoxBytes = 64 * 2 * sizeof(float4) + kHGroupsMax * 32;  // LDS: the lane tiles' boxes + the query groups' boxes
-int prune_rows_per_block(const Plan &pl, int N, int M, int D) {
-    const int maxc = N > M ? N : M;
-    if (D != 3 || pl.variant != 3 || pl.nsplit != 1 || pl.tail != 0 || maxc > pl.chunk || maxc < 1024 || !opt(OPT_NN1_PRUNE)) return 0;
-    if ((pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 16 + 2 > kHGroupsMax - 1) return 0;  // (the query groups' boxes: LDS for eight passes per block)
-    // one pass per block does not repay the sort (measured at B = 8 .. 16 x 4096: 36 against 30 us; two passes -- C2 -- 46 against 53)
-    if ((pl.tpb < pl.tpb_y ? pl.tpb : pl.tpb_y) < 2) return 0;
-    return kHChunkMax + (pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 512 + kHTail;
-}
-size_t prune_scratch_bytes(const Plan &pl, int N, int M, int D) {
-    return (size_t)prune_rows_per_block(pl, N, M, D) * pl.grid * sizeof(float4);
-}
-
-template <int DIM, bool WANT_IDX>
-fx3d_status launch_small(const Nn1Params &p, const Plan &pl, hipStream_t st) {
-    if (pl.variant == 4) {
-        if (DIM == 3) {
-            const bool small = (p.N > p.M ? p.N : p.M) <= kTySl * kTyG;   // both directions' candidates are one group per slice
-            if (pl.R == 2 && small) hipLaunchKernelGGL((nn1_tiny_kernel<2, 1, WANT_IDX>), dim3(pl.grid), dim3(kTyThreads), 0, st, p);
-            else if (pl.R == 2) hipLaunchKernelGGL((nn1_tiny_kernel<2, 4, WANT_IDX>), dim3(pl.grid), dim3(kTyThreads), 0, st, p);
-            else if (small) hipLaunchKernelGGL((nn1_tiny_kernel<1, 1, WANT_IDX>), dim3(pl.grid), dim3(kTyThreads), 0, st, p);
-            else hipLaunchKernelGGL((nn1_tiny_kernel<1, 4, WANT_IDX>), dim3(pl.grid), dim3(kTyThreads), 0, st, p);
-        }
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
-    }
-    if (pl.variant == 3) {
-        if (DIM == 3) {
-            // > 64 KiB of dynamic LDS needs an explicit opt-in (static LDS of the kernel: < 1 KiB)
-            const void *kfn = p.pscr ? reinterpret_cast<const void *>(&nn1_f16_kernel<WANT_IDX, false, true>)
-                              : p.fuse_split ? reinterpret_cast<const void *>(&nn1_f16_kernel<WANT_IDX, true>)
-                                             : reinterpret_cast<const void *>(&nn1_f16_kernel<WANT_IDX, false>);
-            const fx3d_status arc = ensure_dynamic_lds(kfn, (int)(kHChunkMax * 32 + kHScratchBytes + (p.pscr ? kHBoxBytes : 0)), "nn1_f16_kernel");
-            if (arc != FX3D_OK) return arc;
-            if (p.pscr) hipLaunchKernelGGL((nn1_f16_kernel<WANT_IDX, false, true>), dim3(pl.grid), dim3(kHThreads), pl.lds_bytes + kHBoxBytes, st, p);
-            else if (p.fuse_split) hipLaunchKernelGGL((nn1_f16_kernel<WANT_IDX, true>), dim3(pl.grid), dim3(kHThreads), pl.lds_bytes, st, p);
-            else hipLaunchKernelGGL((nn1_f16_kernel<WANT_IDX, false>), dim3(pl.grid), dim3(kHThreads), pl.lds_bytes, st, p);
-        }
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
-    }
-    switch (pl.R) {
-        case 4:
-            hipLaunchKernelGGL((nn1_small_d_kernel<DIM, 4, WANT_IDX>), dim3(pl.grid), dim3(kThreads), pl.lds_bytes, st, p);
-            break;
-        case 2:
-            hipLaunchKernelGGL((nn1_small_d_kernel<DIM, 2, WANT_IDX>), dim3(pl.grid), dim3(kThreads), pl.lds_bytes, st, p);
-            break;
-        default:
-            hipLaunchKernelGGL((nn1_small_d_kernel<DIM, 1, WANT_IDX>), dim3(pl.grid), dim3(kThreads), pl.lds_bytes, st, p);
-            break;
-    }
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-fx3d_status check_shapes(const char *fn, const void *x, int N, const void *y, int M, int B, int D) {
-    FX3D_REQUIRE(x && y, "%s: null input pointer", fn);
-    FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0, "%s: empty input (N=%d M=%d B=%d D=%d)", fn, N, M, B, D);
-    FX3D_REQUIRE((long long)B * 2 * (((long long)(N > M ? N : M) + 255) / 256) < (1ll << 30),
-                 "%s: problem too large for one launch", fn);
-    return FX3D_OK;
-}
-
-constexpr long long kSplitFuseMax = 255;  // tile counters of a fused split run: the 15 spare words of each of a ticket slot's 17 lines
-struct Fused {
-    unsigned int *ticket;
-    unsigned int nvalid;
-    double *sums_out;
-    float *loss_out;
-    float w1, w2;
-    long long Bg;
-};
-
-fx3d_status run_nn1(const float *x, int N, const float *y, int M, int B, int D, int32_t *idx_x,
-                    int32_t *idx_y, float *dmin_x, float *dmin_y, double *partials,
-                    const Plan &pl, hipStream_t st, const Fused *fu = nullptr,
-                    unsigned long long *gres = nullptr, int qstride = 0, float4 *pscr = nullptr) {
-    Nn1Params p{};
-    p.pscr = pscr;
-    p.pscr_stride = pscr ? prune_rows_per_block(pl, N, M, D) : 0;
-    if (!p.pscr_stride) p.pscr = nullptr;
-    p.nsplit = gres ? pl.nsplit : 1;
-    p.gres = gres;
-    p.qstride = qstride;
-    p.fuse_split = gres && fu && fu->ticket ? 1 : 0;  // (the caller checked that the tile counters fit the ticket slot)
-    if (fu) {
-        p.ticket = fu->ticket; p.nvalid = fu->nvalid; p.sums_out = fu->sums_out; p.loss_out = fu->loss_out;
-        p.w1 = fu->w1; p.w2 = fu->w2; p.Bg = fu->Bg;
-    }
-    p.x = x; p.y = y; p.N = N; p.M = M; p.B = B;
-    p.idx_x = idx_x; p.idx_y = idx_y; p.dmin_x = dmin_x; p.dmin_y = dmin_y;
-    p.partials = partials;
-    p.tiles = pl.tiles; p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.chunk = pl.chunk;
-    p.tpb = pl.tpb; p.tpb_y = pl.tpb_y;
-    p.tail = pl.tail;
-    const bool want_idx = idx_x || idx_y;
-    ProfileScope prof("nn1", st);
-    if (D == 3) return want_idx ? launch_small<3, true>(p, pl, st) : launch_small<3, false>(p, pl, st);
-    if (D == 2) return want_idx ? launch_small<2, true>(p, pl, st) : launch_small<2, false>(p, pl, st);
-    hipLaunchKernelGGL(nn1_generic_kernel, dim3(pl.grid), dim3(kThreads), 0, st, p, D);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-// the kernel a plan launches (fx3d_nn1_plan_describe)
-const char *plan_kernel_name(const Plan &pl, int D) {
-    if (D != 2 && D != 3) return "generic";
-    return pl.variant == 3 ? "f16" : pl.variant == 4 ? "tiny" : "small_d";
-}
-
 }  // namespace
 
-// Library-owned arrival counters for the fused finalisation: zeroed once at allocation, every launch returns its
-// counter to zero.  EAGER launches take one of kTickets slots round robin (two launches share a slot only if more than
-// kTickets launches are simultaneously in flight).  A launch recorded by a STREAM CAPTURE bakes its slot's address into
-// the graph for good, so it gets a slot of its own that is never handed out again: replays of the graph (ordered on
-// their stream) are its only users, and no eager launch 1024 k launches later can share the counter.
 namespace fx3d {
-static constexpr int kTickets = 1024;      // eager, round robin
-static constexpr int kCapChunk = 4096;     // capture-owned slots per allocation
-// A slot is kTicketStride words: the arrival counter itself at [0] and, 64 bytes apart, the 16 first-level counters of the
-// two-level arrival (fx3d_common.h: ticket_arrive_last) that launches of many blocks use.
-unsigned int *ticket_slot(fx3d_status *rc, hipStream_t st) {
-    static std::mutex mu;
-    static std::atomic<unsigned int *> pools[64];
-    // capture-owned slots: the chunk in use and a spare.  Allocation + zeroing are not legal while a stream captures
-    // (hipMemset synchronises), so both happen on EAGER calls: the first call of the process sets up the chunk, an
-    // eager call that sees it more than half used sets up the spare.  Chunks are never freed: graphs hold their addresses.
-    static unsigned int *cap_chunk[64] = {nullptr}, *cap_spare[64] = {nullptr};
-    static std::atomic<int> cap_used[64];
-    static std::atomic<unsigned int> next{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { *rc = FX3D_ERR_HIP; return nullptr; }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (st && hipStreamIsCapturing(st, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-    auto fresh = [&](size_t n) -> unsigned int * {
-        unsigned int *pnew = nullptr;
-        if (hipMalloc(&pnew, n * sizeof(unsigned int)) != hipSuccess || hipMemset(pnew, 0, n * sizeof(unsigned int)) != hipSuccess) {
-            set_error("ticket pool allocation failed");
-            *rc = FX3D_ERR_OOM;
-            return nullptr;
-        }
-        return pnew;
-    };
-    if (cs == hipStreamCaptureStatusActive) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (cap_chunk[dev] && cap_used[dev].load() == kCapChunk && cap_spare[dev]) {
-            cap_chunk[dev] = cap_spare[dev];
-            cap_spare[dev] = nullptr;
-            cap_used[dev].store(0);
-        }
-        if (!cap_chunk[dev] || cap_used[dev].load() == kCapChunk) {
-            set_error("no capture-owned arrival counter left: run the captured sequence once eagerly before capturing "
-                      "(the library sets its counters up on eager calls)");
-            *rc = FX3D_ERR_HIP;
-            return nullptr;
-        }
-        return cap_chunk[dev] + (size_t)cap_used[dev].fetch_add(1) * kTicketStride;
-    }
-    unsigned int *pool = pools[dev].load(std::memory_order_acquire);
-    if (!pool || !cap_chunk[dev] || (cap_used[dev].load() > kCapChunk / 2 && !cap_spare[dev])) {
-        std::lock_guard<std::mutex> lk(mu);
-        pool = pools[dev].load(std::memory_order_relaxed);
-        if (!pool) {
-            pool = fresh((size_t)kTickets * kTicketStride);
-            if (!pool) return nullptr;
-            pools[dev].store(pool, std::memory_order_release);
-        }
-        if (!cap_chunk[dev]) {
-            cap_chunk[dev] = fresh((size_t)kCapChunk * kTicketStride);
-            if (!cap_chunk[dev]) return nullptr;
-            cap_used[dev].store(0);
-        } else if (cap_used[dev].load() > kCapChunk / 2 && !cap_spare[dev]) {
-            cap_spare[dev] = fresh((size_t)kCapChunk * kTicketStride);
-            if (!cap_spare[dev]) return nullptr;
-        }
-    }
-    return pool + (size_t)(next.fetch_add(1) % kTickets) * kTicketStride;
+
+size_t nn1_f16_lds_bytes(int chunk) { return (size_t)chunk * 8 * sizeof(float) + kHScratchBytes; }
+
+constexpr size_t kHBoxBytes = 64 * 2 * sizeof(float4) + kHGroupsMax * 32;  // (PRUNE) LDS: the lane tiles' boxes + the query groups' boxes
+
+// The instantiation a launch runs: pruned when it has scratch (p.pscr), else with the subsets' merge when it was asked for.
+template <bool WANT_IDX>
+static fx3d_status launch_f16(const Nn1Params &p, int grid, size_t lds_bytes, hipStream_t st) {
+    void (*const kfn)(Nn1Params) = p.pscr ? &nn1_f16_kernel<WANT_IDX, false, true>
+                                   : p.fuse_split ? &nn1_f16_kernel<WANT_IDX, true> : &nn1_f16_kernel<WANT_IDX, false>;
+    const size_t box = p.pscr ? kHBoxBytes : 0;
+    // > 64 KiB of dynamic LDS needs an explicit opt-in (static LDS of the kernel: < 1 KiB)
+    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(kfn), (int)(nn1_f16_lds_bytes(kHChunkMax) + box), "nn1_f16_kernel");
+    if (arc != FX3D_OK) return arc;
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kHThreads), lds_bytes + box, st, p);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
 }
+
+fx3d_status nn1_f16_launch(const Nn1Params &p, int grid, size_t lds_bytes, hipStream_t st) {
+    return p.idx_x || p.idx_y ? launch_f16<true>(p, grid, lds_bytes, st) : launch_f16<false>(p, grid, lds_bytes, st);
+}
+
+fx3d_status nn1_split_finalize_launch(const Nn1Params &p, int tiles_f, hipStream_t st) {
+    hipLaunchKernelGGL(nn1_split_finalize_kernel, dim3(tiles_f, 2 * p.B), dim3(kThreads), 0, st, p, tiles_f);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
 }  // namespace fx3d
-
-extern "C" {
-
-fx3d_status fx3d_nn1(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D,
-                     int32_t *idx_x, int32_t *idx_y, float *dmin_x, float *dmin_y,
-                     fx3d_stream_t s) {
-    fx3d_status rc = check_shapes("fx3d_nn1", x, N, y, M, B, D);
-    if (rc) return rc;
-    Plan pl = make_plan(N, M, B, D);
-    if (pl.nsplit > 1) {  // no scratch at this entry point: plan without the split option
-        pl = make_plan(N, M, B, D, false);
-    }
-    return run_nn1(x, N, y, M, B, D, idx_x, idx_y, dmin_x, dmin_y, nullptr, pl, as_stream(s));
-}
-
-fx3d_status fx3d_nn1_plan_describe(int32_t N, int32_t M, int32_t B, int32_t D, char *buf, size_t n) {
-    FX3D_REQUIRE(buf && n > 0, "fx3d_nn1_plan_describe: null buffer");
-    FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0, "fx3d_nn1_plan_describe: empty problem");
-    const Plan pl = make_plan(N, M, B, D);
-    snprintf(buf, n, "variant=%d threads=%d chunk=%d nsplit=%d tpb=%d tpb_y=%d tiles_x=%d tiles_y=%d grid=%d tail=%d lds=%zu R=%d kernel=%s",
-             pl.variant, pl.threads, pl.chunk, pl.nsplit, pl.tpb, pl.tpb_y, pl.tiles_x, pl.tiles_y, pl.grid, pl.tail, pl.lds_bytes, pl.R,
-             plan_kernel_name(pl, D));
-    return FX3D_OK;
-}
-
-fx3d_status fx3d_chamfer_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, size_t *bytes) {
-    FX3D_REQUIRE(bytes, "fx3d_chamfer_workspace_bytes: null output");
-    FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0, "fx3d_chamfer_workspace_bytes: empty input");
-    const Plan pl = make_plan(N, M, B, D);
-    *bytes = ((size_t)2 * B * pl.tiles + 2) * sizeof(double);
-    if (const size_t ps = prune_scratch_bytes(pl, N, M, D)) *bytes = ((*bytes + 255) & ~(size_t)255) + ps;  // (a smaller workspace still runs: without pruning)
-    if (pl.nsplit > 1) {  // split run: 256-query finalize tiles + the per-query merge slots
-        const int maxq = N > M ? N : M;
-        const int tiles_f = (maxq + kThreads - 1) / kThreads;
-        *bytes = ((size_t)2 * B * tiles_f + 2) * sizeof(double) + (size_t)pl.nsplit * 2 * B * maxq * sizeof(unsigned long long);
-    }
-    return FX3D_OK;
-}
-
-
-}  // extern "C"
-
-namespace fx3d {
-fx3d_status chamfer_check_shapes(const char *fn, const void *x, int N, const void *y, int M, int B, int D) { return check_shapes(fn, x, N, y, M, B, D); }
-}
-
-extern "C" {
-
-static fx3d_status chamfer_common(const float *x, int N, const float *y, int M, int B, int D,
-                                  double *sums_dev, float *loss_dev, long long Bg, float w1,
-                                  float w2, int32_t *idx_x, int32_t *idx_y, void *ws,
-                                  size_t ws_bytes, hipStream_t st, const char *fn) {
-    fx3d_status rc = check_shapes(fn, x, N, y, M, B, D);
-    if (rc) return rc;
-    const Plan pl = make_plan(N, M, B, D);
-    const int tiles = pl.tiles, tx = pl.tiles_x, ty = pl.tiles_y;
-    size_t need = ((size_t)2 * B * tiles + 2) * sizeof(double);
-    const int maxq = N > M ? N : M;
-    const int tiles_f = (maxq + kThreads - 1) / kThreads;
-    if (pl.nsplit > 1)
-        need = ((size_t)2 * B * tiles_f + 2) * sizeof(double) + (size_t)pl.nsplit * 2 * B * maxq * sizeof(unsigned long long);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: workspace too small (%zu < %zu bytes)", fn, ws ? ws_bytes : (size_t)0, need);
-        return FX3D_ERR_WORKSPACE;
-    }
-    double *partials = reinterpret_cast<double *>(ws);
-    if (pl.nsplit > 1) {
-        // few large clouds: chunk subsets run in parallel blocks, each stores its per-query result row in gres (plain
-        // stores: no memset node, no atomics), the finalize kernel merges the rows
-        unsigned long long *gres = reinterpret_cast<unsigned long long *>(partials + (size_t)2 * B * tiles_f + 2);
-        if (2ll * B * pl.tiles <= kSplitFuseMax) {
-            // one launch: the last chunk subset of every query tile merges (tile counters in the ticket slot's spare words), the
-            // last of those blocks reduces the partials (layout of the one-chunk path: pl.tiles entries per (direction, cloud))
-            fx3d_status trc = FX3D_OK;
-            unsigned int *ticket = ticket_slot(&trc, st);
-            if (!ticket) return trc;
-            Fused fu{ticket, (unsigned int)((long long)B * pl.tiles_x + (long long)B * pl.tiles_y),
-                     sums_dev ? sums_dev : partials + (size_t)2 * B * tiles_f, loss_dev, w1, w2, Bg};
-            return run_nn1(x, N, y, M, B, D, idx_x, idx_y, nullptr, nullptr, partials, pl, st, &fu, gres, maxq);
-        }
-        rc = run_nn1(x, N, y, M, B, D, nullptr, nullptr, nullptr, nullptr, nullptr, pl, st, nullptr, gres, maxq);
-        if (rc) return rc;
-        Nn1Params fp{};
-        fp.N = N; fp.M = M; fp.B = B; fp.idx_x = idx_x; fp.idx_y = idx_y; fp.partials = partials;
-        fp.gres = gres; fp.qstride = maxq; fp.nsplit = pl.nsplit; fp.chunk = pl.chunk;
-        // (split runs exist for D == 3 only) the last block of the unpack kernel reduces the partials: no finalize launch
-        fx3d_status trc = FX3D_OK;
-        unsigned int *ticket = ticket_slot(&trc, st);
-        if (!ticket) return trc;
-        fp.ticket = ticket; fp.nvalid = (unsigned int)((long long)tiles_f * 2 * B);
-        fp.tiles_x = (N + kThreads - 1) / kThreads; fp.tiles_y = (M + kThreads - 1) / kThreads;
-        fp.sums_out = sums_dev ? sums_dev : partials + (size_t)2 * B * tiles_f;
-        fp.loss_out = loss_dev; fp.w1 = w1; fp.w2 = w2; fp.Bg = Bg;
-        hipLaunchKernelGGL(nn1_split_finalize_kernel, dim3(tiles_f, 2 * B), dim3(kThreads), 0, st, fp, tiles_f);
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
-    }
-    if ((pl.variant == 3 || pl.variant == 4) && D == 3) {  // one launch: the last block reduces the partials
-        fx3d_status trc = FX3D_OK;
-        unsigned int *ticket = ticket_slot(&trc, st);
-        if (!ticket) return trc;
-        Fused fu{ticket, (unsigned int)((long long)B * tx + (long long)B * ty),
-                 sums_dev ? sums_dev : partials + (size_t)2 * B * tiles, loss_dev, w1, w2, Bg};
-        // spatial pruning when the workspace holds the blocks' scratch behind the partial sums (fx3d_chamfer_workspace_bytes asks for it)
-        float4 *pscr = nullptr;
-        const size_t poff = (need + 255) & ~(size_t)255, ps = prune_scratch_bytes(pl, N, M, D);
-        if (ps && ws_bytes >= poff + ps) pscr = reinterpret_cast<float4 *>(static_cast<char *>(ws) + poff);
-        return run_nn1(x, N, y, M, B, D, idx_x, idx_y, nullptr, nullptr, partials, pl, st, &fu, nullptr, 0, pscr);
-    }
-    rc = run_nn1(x, N, y, M, B, D, idx_x, idx_y, nullptr, nullptr, partials, pl, st);
-    if (rc) return rc;
-    FinalizeParams f{};
-    f.partials = partials; f.B = B; f.tiles = tiles; f.tiles_x = tx; f.tiles_y = ty;
-    f.sums = sums_dev ? sums_dev : partials + (size_t)2 * B * tiles;
-    f.loss = loss_dev; f.N = N; f.M = M; f.D = D; f.Bg = Bg; f.w1 = w1; f.w2 = w2;
-    hipLaunchKernelGGL(chamfer_finalize_partials_kernel, dim3(1), dim3(kThreads), 0, st, f);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-}  // extern "C"
-
-namespace fx3d {  // the forward driver, for the value-and-gradient entry point in chamfer_bwd.hip
-fx3d_status chamfer_forward(const float *x, int N, const float *y, int M, int B, int D, float *loss_dev, long long Bg, float w1,
-                            float w2, int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes, hipStream_t st, const char *fn) {
-    return chamfer_common(x, N, y, M, B, D, nullptr, loss_dev, Bg, w1, w2, idx_x, idx_y, ws, ws_bytes, st, fn);
-}
-}
-
-extern "C" {
-
-fx3d_status fx3d_chamfer_sums(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
-                              int32_t D, double *sums_dev, int32_t *idx_x, int32_t *idx_y,
-                              void *ws, size_t ws_bytes, fx3d_stream_t s) {
-    FX3D_REQUIRE(sums_dev, "fx3d_chamfer_sums: null sums_dev");
-    return chamfer_common(x, N, y, M, B, D, sums_dev, nullptr, B, 1.f, 1.f, idx_x, idx_y, ws,
-                          ws_bytes, as_stream(s), "fx3d_chamfer_sums");
-}
-
-fx3d_status fx3d_chamfer_finalize(const double *sums_dev, int32_t N, int32_t M, int64_t B_global,
-                                  int32_t D, float w1, float w2, float *loss_dev,
-                                  fx3d_stream_t s) {
-    FX3D_REQUIRE(sums_dev && loss_dev, "fx3d_chamfer_finalize: null pointer");
-    FX3D_REQUIRE(N > 0 && M > 0 && B_global > 0 && D > 0, "fx3d_chamfer_finalize: bad sizes");
-    hipLaunchKernelGGL(chamfer_loss_kernel, dim3(1), dim3(64), 0, as_stream(s), sums_dev, N, M, D,
-                       (long long)B_global, w1, w2, loss_dev);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-fx3d_status fx3d_chamfer_finalize_many(const double *sums_dev, int32_t count, int32_t N, int32_t M, int64_t B_global,
-                                       int32_t D, float w1, float w2, float *losses_dev, fx3d_stream_t s) {
-    FX3D_REQUIRE(sums_dev && losses_dev, "fx3d_chamfer_finalize_many: null pointer");
-    FX3D_REQUIRE(count > 0 && N > 0 && M > 0 && B_global > 0 && D > 0, "fx3d_chamfer_finalize_many: bad sizes");
-    hipLaunchKernelGGL(chamfer_loss_many_kernel, dim3((count + 63) / 64), dim3(64), 0, as_stream(s), sums_dev, count, N, M,
-                       D, (long long)B_global, w1, w2, losses_dev);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-fx3d_status fx3d_chamfer_fwd(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
-                             int32_t D, float w1, float w2, float *loss_dev, float *loss_host,
-                             int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes,
-                             fx3d_stream_t s) {
-    FX3D_REQUIRE(loss_dev, "fx3d_chamfer_fwd: null loss_dev");
-    fx3d_status rc = chamfer_common(x, N, y, M, B, D, nullptr, loss_dev, B, w1, w2, idx_x, idx_y,
-                                    ws, ws_bytes, as_stream(s), "fx3d_chamfer_fwd");
-    if (rc) return rc;
-    if (loss_host) {
-        FX3D_HIP(hipMemcpyAsync(loss_host, loss_dev, sizeof(float), hipMemcpyDeviceToHost, as_stream(s)));
-        FX3D_HIP(hipStreamSynchronize(as_stream(s)));
-    }
-    return FX3D_OK;
-}
-
-}  // extern "C"

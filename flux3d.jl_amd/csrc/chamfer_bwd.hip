@@ -799,7 +799,7 @@ fx3d_status fx3d_chamfer_fwd_bwd(const float *x, int32_t N, const float *y, int3
     int32_t *iy = ix + (size_t)B * N;
     if (idx_x) ix = idx_x;
     if (idx_y) iy = idx_y;
-    rc = chamfer_forward(x, N, y, M, B, D, loss_dev, (long long)B_global, w1, w2, ix, iy, ws, fwd, as_stream(s),
+    rc = chamfer_forward(x, N, y, M, B, D, nullptr, loss_dev, (long long)B_global, w1, w2, ix, iy, ws, fwd, as_stream(s),
                          "fx3d_chamfer_fwd_bwd");
     if (rc) return rc;
     rc = fx3d_chamfer_bwd(x, N, y, M, B, D, ix, iy, w1, w2, gout, B_global, gx, gy, s);

@@ -40,18 +40,20 @@ inline hipStream_t as_stream(fx3d_stream_t s) { return reinterpret_cast<hipStrea
 
 // Opt a kernel in to more than 64 KiB of dynamic LDS, once per (kernel, device): the attribute is per device, and
 // a process may drive several (runtime.hip).
-// Library-owned arrival counter for a fused "last block finalises" reduction: zero at hand-out, the kernel returns
-// it to zero (chamfer.hip).  A launch that `st` is capturing into a graph gets a slot of its own, never reused.
-// nullptr + *rc on allocation failure.
+// Library-owned arrival counter for a fused "last block finalises" reduction (runtime.hip): zero at hand-out, the kernel
+// returns it to zero (nn1_common.h: fused_finalize_wave0; mesh.hip).  A launch that `st` is capturing into a graph gets a
+// slot of its own, never reused.  nullptr + *rc on allocation failure.
 unsigned int *ticket_slot(fx3d_status *rc, hipStream_t st);
 // Words per ticket slot: the arrival counter at [0] + 16 first-level counters, one per 64-byte line (ticket_arrive_last).
 constexpr int kTicketGroups = 16;
 constexpr int kTicketStride = 16 * (kTicketGroups + 1);
 fx3d_status ensure_dynamic_lds(const void *kernel, int bytes, const char *name);
-// chamfer.hip's argument check and forward driver (loss with batch size Bg, optional indices), for chamfer_bwd.hip
+// chamfer_host.hip's argument check and forward driver (the two sums and / or the loss with batch size Bg, optional indices), for
+// chamfer_bwd.hip and chamfer_pairwise.hip
 fx3d_status chamfer_check_shapes(const char *fn, const void *x, int N, const void *y, int M, int B, int D);
-fx3d_status chamfer_forward(const float *x, int N, const float *y, int M, int B, int D, float *loss_dev, long long Bg, float w1,
-                            float w2, int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes, hipStream_t st, const char *fn);
+fx3d_status chamfer_forward(const float *x, int N, const float *y, int M, int B, int D, double *sums_dev, float *loss_dev,
+                            long long Bg, float w1, float w2, int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes,
+                            hipStream_t st, const char *fn);
 // compute units of the calling thread's current device (cached per device; 256 on an MI355X in SPX mode, fewer in the
 // partitioned modes): the launch plans size their rounds of blocks with it instead of a constant
 int device_cus();

@@ -412,4 +412,71 @@ fx3d_status ensure_dynamic_lds(const void *kernel, int bytes, const char *name) 
     done.insert({kernel, dev});
     return FX3D_OK;
 }
+
+// Library-owned arrival counters for the fused finalisation: zeroed once at allocation, every launch returns its
+// counter to zero.  EAGER launches take one of kTickets slots round robin (two launches share a slot only if more than
+// kTickets launches are simultaneously in flight).  A launch recorded by a STREAM CAPTURE bakes its slot's address into
+// the graph for good, so it gets a slot of its own that is never handed out again: replays of the graph (ordered on
+// their stream) are its only users, and no eager launch 1024 k launches later can share the counter.
+static constexpr int kTickets = 1024;      // eager, round robin
+static constexpr int kCapChunk = 4096;     // capture-owned slots per allocation
+// A slot is kTicketStride words: the arrival counter itself at [0] and, 64 bytes apart, the 16 first-level counters of the
+// two-level arrival (fx3d_common.h: ticket_arrive_last) that launches of many blocks use.
+unsigned int *ticket_slot(fx3d_status *rc, hipStream_t st) {
+    static std::mutex mu;
+    static std::atomic<unsigned int *> pools[64];
+    // capture-owned slots: the chunk in use and a spare.  Allocation + zeroing are not legal while a stream captures
+    // (hipMemset synchronises), so both happen on EAGER calls: the first call of the process sets up the chunk, an
+    // eager call that sees it more than half used sets up the spare.  Chunks are never freed: graphs hold their addresses.
+    static unsigned int *cap_chunk[64] = {nullptr}, *cap_spare[64] = {nullptr};
+    static std::atomic<int> cap_used[64];
+    static std::atomic<unsigned int> next{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { *rc = FX3D_ERR_HIP; return nullptr; }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st && hipStreamIsCapturing(st, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+    auto fresh = [&](size_t n) -> unsigned int * {
+        unsigned int *pnew = nullptr;
+        if (hipMalloc(&pnew, n * sizeof(unsigned int)) != hipSuccess || hipMemset(pnew, 0, n * sizeof(unsigned int)) != hipSuccess) {
+            set_error("ticket pool allocation failed");
+            *rc = FX3D_ERR_OOM;
+            return nullptr;
+        }
+        return pnew;
+    };
+    if (cs == hipStreamCaptureStatusActive) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (cap_chunk[dev] && cap_used[dev].load() == kCapChunk && cap_spare[dev]) {
+            cap_chunk[dev] = cap_spare[dev];
+            cap_spare[dev] = nullptr;
+            cap_used[dev].store(0);
+        }
+        if (!cap_chunk[dev] || cap_used[dev].load() == kCapChunk) {
+            set_error("no capture-owned arrival counter left: run the captured sequence once eagerly before capturing "
+                      "(the library sets its counters up on eager calls)");
+            *rc = FX3D_ERR_HIP;
+            return nullptr;
+        }
+        return cap_chunk[dev] + (size_t)cap_used[dev].fetch_add(1) * kTicketStride;
+    }
+    unsigned int *pool = pools[dev].load(std::memory_order_acquire);
+    if (!pool || !cap_chunk[dev] || (cap_used[dev].load() > kCapChunk / 2 && !cap_spare[dev])) {
+        std::lock_guard<std::mutex> lk(mu);
+        pool = pools[dev].load(std::memory_order_relaxed);
+        if (!pool) {
+            pool = fresh((size_t)kTickets * kTicketStride);
+            if (!pool) return nullptr;
+            pools[dev].store(pool, std::memory_order_release);
+        }
+        if (!cap_chunk[dev]) {
+            cap_chunk[dev] = fresh((size_t)kCapChunk * kTicketStride);
+            if (!cap_chunk[dev]) return nullptr;
+            cap_used[dev].store(0);
+        } else if (cap_used[dev].load() > kCapChunk / 2 && !cap_spare[dev]) {
+            cap_spare[dev] = fresh((size_t)kCapChunk * kTicketStride);
+            if (!cap_spare[dev]) return nullptr;
+        }
+    }
+    return pool + (size_t)(next.fetch_add(1) % kTickets) * kTicketStride;
+}
 }  // namespace fx3d

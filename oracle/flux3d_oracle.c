@@ -87,7 +87,7 @@ FX_API int fx3d_oracle_nn1(const float *x, int N, const float *y, int M, int B, 
  *   w1*dist_A_to_B + w2*dist_B_to_A
  * Element squares are Float32; the mean is accumulated here in double, where the reference's `mean` is a
  * Float32 pairwise sum (Base.mean -> sum / n): the two differ by O(log2(n) * 2^-24) relative, inside the 1e-5 of
- * north_star; fx3d_chamfer_finalize (csrc/chamfer.hip) follows THIS definition (double sums, one rounding). */
+ * north_star; fx3d_chamfer_finalize (csrc/chamfer_host.hip) follows THIS definition (double sums, one rounding). */
 FX_API int fx3d_oracle_chamfer_fwd(const float *x, int N, const float *y, int M, int B, int D,
                                    float w1, float w2, float *loss, int32_t *idx_x,
                                    int32_t *idx_y, double *sums /* [2] optional */) {
@@ -124,7 +124,7 @@ FX_API int fx3d_oracle_chamfer_fwd(const float *x, int N, const float *y, int M,
  * Caveat (stated, not hidden): the leaf loop of Base carries @simd, so a Julia build may re-associate a leaf's sum into as
  * many partial sums as its target's vector width x unroll factor; this restatement is the un-vectorised definition, which is
  * what `julia -O0` / a scalar target computes.  The PRODUCT's default (fx3d_chamfer_fwd) stays the Float64 sum above -- one
- * rounding, order independent to 2^-53 --; fx3d_chamfer_loss_pairwise_f32 (csrc/chamfer.hip) reproduces THIS function bit
+ * rounding, order independent to 2^-53 --; fx3d_chamfer_loss_pairwise_f32 (csrc/chamfer_pairwise.hip) reproduces THIS function bit
  * for bit from the indices. */
 static float pairwise_sum_f32(const float *a, size_t ifirst, size_t ilast) { /* inclusive, 0-based */
     if (ifirst == ilast) return a[ifirst];

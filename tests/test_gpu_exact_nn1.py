@@ -1,4 +1,4 @@
-"""GPU parity of the two exact nearest-neighbour kernels that are not the default D = 3 path (csrc/chamfer.hip):
+"""GPU parity of the two exact nearest-neighbour kernels that are not the default D = 3 path (csrc/nn1_exact.hip):
 
   * nn1_small_d_kernel<DIM, R, WANT_IDX>: every D = 2 cloud, and D = 3 under option nn1_variant = 0.  Candidates are staged
     through LDS in chunks of at most kChunkMax = 4096 (the last one padded with +Inf to a multiple of 32), tiles of 32 are

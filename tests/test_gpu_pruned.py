@@ -1,6 +1,6 @@
 """GPU parity of the spatially pruned nearest-neighbour launch (nn1_f16_kernel<.., PRUNE = true>, csrc/chamfer.hip): the
 candidates in a Hilbert-ordered LDS image, a bounding box per 64-row lane tile, waves that skip the tiles which cannot hold a
-nearest neighbour.  Only chamfer_common prunes (fx3d_chamfer_fwd / _sums / _fwd_bwd, with the blocks' scratch in the workspace),
+nearest neighbour.  Only chamfer_forward (csrc/chamfer_host.hip) prunes (fx3d_chamfer_fwd / _sums / _fwd_bwd, with the blocks' scratch in the workspace),
 and only at shapes with two or more query passes per block in both directions (prune_rows_per_block): B >= 17 at 4096 points,
 B = 128 at 1024.  Every test first checks that its shape still takes the pruned launch, so a plan change fails here instead
 of quietly testing the unpruned kernel.

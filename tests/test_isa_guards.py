@@ -4,7 +4,9 @@ and checks, for every instruction inside an inline-asm block, that no VGPR it RE
 required wait states earlier (CDNA3/4 ISA: an XDL write of VGPRs followed by a VALU read needs 5 / 11 / 19 wait states for
 2- / 8- / 16-pass MFMAs -- one wait state = one issue slot of four cycles, an MFMA keeps the matrix pipe for `passes` of them; the kernels use the 8-pass v_mfma_f32_32x32x16_f16 and the 16-pass v_mfma_f32_32x32x2_f32).
 Instructions the compiler emitted itself are covered by its own hazard recogniser and are not checked.  CPU only (hipcc
-cross-compiles); the assembly is cached by source hash in the library's build directory (flux3d.jl_amd/lib/isa)."""
+cross-compiles); the assembly is cached in the library's build directory (flux3d.jl_amd/lib/isa) by a hash of the source, every
+header under csrc/ and the public header."""
+import glob
 import hashlib
 import os
 import re
@@ -24,7 +26,7 @@ NEED = {2: 5, 4: 7, 8: 11, 16: 19}
 def _assembly(name):
     src = os.path.join(CSRC, name)
     h = hashlib.sha256()
-    for f in (src, os.path.join(CSRC, "fx3d_common.h"), os.path.join(ROOT, "include", "flux3d_hip.h")):
+    for f in [src] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "flux3d_hip.h")]:
         h.update(open(f, "rb").read())
     cache = os.path.join(ROOT, "flux3d.jl_amd", "lib", "isa")
     os.makedirs(cache, exist_ok=True)

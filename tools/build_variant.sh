@@ -2,6 +2,9 @@
 # One translation unit rebuilt with extra flags and linked with the other objects of the in-place build into
 # flux3d.jl_amd/lib/libflux3d_hip_<name>.so (for tools/ab_two_libs.sh / FX3D_HIP_LIB):
 #   bash tools/build_variant.sh <name> <unit, e.g. chamfer_bwd> "<extra hipcc flags>"
+# The chamfer forward is three units: `chamfer` holds nn1_f16_kernel with its -D FX3D_H* knobs, `nn1_exact` the exact kernels,
+# `chamfer_host` the planner (make_plan), the workspace layout and the entry points.  (-DFX3D_HLT is read by the planner too:
+# nn1_common.h.)
 set -e
 NAME=$1; UNIT=$2; EXTRA=$3
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -1,6 +1,6 @@
 """Forced launch plans of the fp16 1-NN kernel at the fit iteration's chamfer shapes (N = M = 5000 surface samples, B = 1 and 8):
 a library whose planner reads FX3D_NN1_FORCE_PLAN="chunks split passes" (the eleven-line patch of make_plan's search loop kept at the
-end of this file: apply, `bash tools/build_variant.sh sweep chamfer "-DFX3D_PLAN_SWEEP"`, run with FX3D_HIP_LIB=.../libflux3d_hip_sweep.so; the
+end of this file: apply, `bash tools/build_variant.sh sweep chamfer_host "-DFX3D_PLAN_SWEEP"`, run with FX3D_HIP_LIB=.../libflux3d_hip_sweep.so; the
 shipped planner has no such switch).  Min of single calls between events (us; the wrapper's allocations and ~4.4 us of call overhead
 included).  Result (profiles/r06_v13_nn1_plan_sweep.txt): the planner's own choices -- 12 subsets of 448 candidates at one mesh, 3 x 1728
 with two passes at eight -- are the fastest plans of the kernel at both shapes."""
@@ -51,11 +51,11 @@ for nb in (1, 8):
 
 
 PLANNER_PATCH = r"""
-diff --git a/flux3d.jl_amd/csrc/chamfer.hip b/flux3d.jl_amd/csrc/chamfer.hip
-index 3da777b..9acd76e 100644
---- a/flux3d.jl_amd/csrc/chamfer.hip
-+++ b/flux3d.jl_amd/csrc/chamfer.hip
-@@ -2109,6 +2109,10 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
+diff --git a/flux3d.jl_amd/csrc/chamfer_host.hip b/flux3d.jl_amd/csrc/chamfer_host.hip
+index a1b8477..6eabe44 100644
+--- a/flux3d.jl_amd/csrc/chamfer_host.hip
++++ b/flux3d.jl_amd/csrc/chamfer_host.hip
+@@ -154,6 +154,10 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
          const int cminc = (maxc + cmax - 1) / cmax;
          double best = 1e30;
          b_chunk = (maxc + gran - 1) / gran * gran < cmax ? (maxc + gran - 1) / gran * gran : cmax; b_tpb = 1; b_split = 1;
@@ -66,14 +66,14 @@ index 3da777b..9acd76e 100644
          for (int nch = cminc; nch <= cminc * 8 && nch <= 64; ++nch) {
              int ch = ((maxc + nch - 1) / nch + gran - 1) / gran * gran;
              if (ch > cmax) continue;
-@@ -2117,6 +2121,9 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
+@@ -162,6 +166,9 @@ Plan make_plan(int N, int M, int B, int D, bool allow_split = true) {
                  if (split && (!allow_split || anch == 1 || opt(OPT_NN1_NOSPLIT))) continue;
                  for (int tpb = 1; tpb <= 8; tpb *= 2) {
                      if (!split && anch > 1 && tpb > 1) continue;
 +#ifdef FX3D_PLAN_SWEEP
 +                    if (f_nch && (nch != f_nch || split != f_split || tpb != f_tpb)) continue;
 +#endif
-                     const long long tiles = ((long long)maxc + 512 * tpb - 1) / (512 * tpb);
+                     const long long tiles = ceil_div(maxc, 512 * tpb);
                      const long long blocks = 2ll * B * tiles * (split ? anch : 1);
-                     const double per_chunk = 5.0 * ch / 4096.0 + 0.5 + tpb * (9.7 * ch / 4096.0 + 0.8);
+                     const double t_block = block_us(maxc, ch, split ? 1 : anch, tpb);
 """

@@ -1,4 +1,5 @@
-// Phase-level timing of the nn1 kernels at BASELINE config 2 (B=32, N=M=4096): includes chamfer.hip
+// Phase-level timing of the nn1 kernels at BASELINE config 2 (B=32, N=M=4096): includes the chamfer forward's units
+// (chamfer.hip: the kernel; nn1_exact.hip, chamfer_host.hip: what fx3d_chamfer_fwd needs around it) into one translation unit
 // with FX3D_PROBE so the kernel stores s_memtime stamps per block.  Build:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DFX3D_PROBE -I include -I flux3d.jl_amd/csrc \
 //         tools/nn1_probe.hip flux3d.jl_amd/csrc/runtime.hip -o tools/nn1_probe
@@ -6,6 +7,8 @@
 #define FX3D_CHAMFER_SRC "../flux3d.jl_amd/csrc/chamfer.hip"
 #endif
 #include FX3D_CHAMFER_SRC
+#include "../flux3d.jl_amd/csrc/nn1_exact.hip"
+#include "../flux3d.jl_amd/csrc/chamfer_host.hip"
 
 #include <algorithm>
 #include <cstdio>
