@@ -1,0 +1,430 @@
+// PointNet inference (gfx950): (m::PointNet)(X) of src/models/pointnet.jl:62-85 in test mode, Float32, forward only.
+// include/flux3d_hip.h states the network, the arithmetic and the parameter layout; this file is how they are computed.
+//
+// Every contraction is one accumulator per output element that walks the input channels upwards with one rounding per
+// step: acc = fmaf(x[c], W[c,o], acc) from +0.0f.  v_mfma_f32_32x32x2_f32 is that chain (two steps per instruction, the
+// lower k first), so the 1x1 convolutions with 64 or 128 input channels run on it; the 3-channel ones (no multiple of the
+// instruction's k: padding with zeros would turn an Inf weight into NaN) and the dense heads run the same chain as v_fma_f32.
+// No split of a contraction over waves or blocks, no float atomics: the bits do not depend on the launch shape.
+//
+// Two kernels, three rounds (stn, fstn, feat):
+//   pointnet_points_kernel<MODE>: one block = 64 points of one cloud, 4 waves.  The tile's activations live in two
+//     (64 x 128) LDS images (row stride 130 floats: the A-operand reads of a 32-point tile fall on 64 distinct banks; the
+//     epilogue's stores, 32 consecutive channels per lane half with the halves 4 rows = 8 banks apart, overlap on 24 banks).  A wave owns slabs of 32 output channels and computes them for both 32-point halves of the tile from
+//     one stream of weights: lane (h, j) reads row j of the slab, W[4q .. 4q+3, o] per step (the (Cin, Cout) column-major
+//     layout makes that 16 contiguous bytes), and feeds elements h and 2 + h to two consecutive k-steps.  The epilogue
+//     (bias, relu, BatchNorm in the order of the layer) runs on the accumulators: a lane holds ONE channel and 16 points
+//     per half.  The last layer (128 -> 1024) is never stored: each slab is reduced to the tile's maximum per channel
+//     (Julia's max) and written to the workspace with plain stores.
+//     MODE 0 = stn (X -> 64 -> 128 -> 1024), 1 = fstn (X * T -> conv_block1 -> stored as h (64, N, B) -> 64 -> 128 -> 1024),
+//     2 = feat (h * F -> 128 -> 1024, no relu on the last).
+//   pointnet_head_kernel<FEAT>: one block per cloud folds the per-tile maxima, then the dense layers with one thread per
+//     output element (W (out, in) column-major: consecutive threads read consecutive weights), BatchNorm, and for the
+//     classifier relu + softmax.  stn / fstn write their (K, K) matrix already transposed (T[i,j] = d[j + K i] at i + K j),
+//     which is the (Cin, Cout) layout of a convolution: the per-cloud transform is one more bias-free layer of the point kernel.
+#include <cmath>
+
+#include "fx3d_common.h"
+
+using namespace fx3d;
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kTile = 64;          // points per block
+constexpr int kLd = 130;           // LDS row stride of an activation image (floats)
+constexpr int kPtThreads = 256;    // 4 waves
+constexpr int kHeadThreads = 1024;
+constexpr int kFeat = 1024;        // channels of the pooled feature
+constexpr float kBnEps = 1e-5f;    // BatchNorm's default epsilon, 1f-5
+constexpr size_t kPtLds = (size_t)(2 * kTile * kLd + 2 * kTile * 3) * sizeof(float);
+
+struct __attribute__((packed, aligned(4))) W4 { float x, y, z, w; };  // four consecutive weights, 4-byte aligned
+
+struct Bn { const float *g, *b, *m, *v; };
+struct Conv { const float *W, *b; Bn bn; };
+struct Dense { const float *W, *b; };
+
+enum Epi { kNone, kReluBn, kBnRelu, kBnOnly };
+
+// Julia's max on IEEE floats: NaN propagates, -0.0 < +0.0 (as transforms.hip)
+__device__ __forceinline__ float jmax(float x, float y) {
+    return ((y > x) || (!signbit(y) && signbit(x))) ? (isnan(x) ? x : y) : (isnan(y) ? y : x);
+}
+__device__ __forceinline__ float relu(float v) { return jmax(0.0f, v); }  // max(zero(v), v)
+__device__ __forceinline__ float batchnorm(float v, float g, float be, float mu, float sd) { return (g * ((v - mu) / sd)) + be; }
+
+template <int EPI>
+__device__ __forceinline__ float epilogue(float acc, float bias, float g, float be, float mu, float sd) {
+    if (EPI == kNone) return acc;
+    float v = acc + bias;
+    if (EPI == kReluBn) v = relu(v);
+    v = batchnorm(v, g, be, mu, sd);
+    if (EPI == kBnRelu) v = relu(v);
+    return v;
+}
+
+// out[p][o] = epilogue(sum_c in[p][c] W[c + CIN o]) for the 64 points of the tile and o < cout (a multiple of 32), on the
+// f32 MFMA.  FINAL: nothing is stored; tmax[o] = max over the tile's first `nvalid` points.  All 4 waves call it.
+template <int CIN, int EPI, bool FINAL>
+__device__ __forceinline__ void conv_mfma(const float *in, float *out, int cout, const float *__restrict__ W,
+                                          const float *__restrict__ bias, const Bn bn, int nvalid, float *__restrict__ tmax) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const float *a0 = in + j * kLd + h, *a1 = a0 + 32 * kLd;
+    for (int sl = wave; sl < cout / 32; sl += kPtThreads / 64) {
+        const int o = sl * 32 + j;
+        const float *wrow = W + (size_t)CIN * o;
+        f32x16 acc0 = {0}, acc1 = {0};
+#pragma unroll 4
+        for (int q = 0; q < CIN / 4; ++q) {
+            const W4 w = *reinterpret_cast<const W4 *>(wrow + 4 * q);
+            const float b0 = h ? w.y : w.x, b1 = h ? w.w : w.z;  // k = 4q + h, then k = 4q + 2 + h
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[4 * q], b0, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[4 * q], b0, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[4 * q + 2], b1, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[4 * q + 2], b1, acc1, 0, 0, 0);
+        }
+        float bi = 0.0f, g = 0.0f, be = 0.0f, mu = 0.0f, sd = 1.0f;
+        if (EPI != kNone) {
+            bi = bias[o]; g = bn.g[o]; be = bn.b[o]; mu = bn.m[o];
+            sd = sqrtf(bn.v[o] + kBnEps);
+        }
+        float m = __int_as_float(0xff800000);  // -Inf: neutral for Julia's max
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int p = (r & 3) + 8 * (r >> 2) + 4 * h;  // the accumulator's row: the point within its 32-point half
+            const float v0 = epilogue<EPI>(acc0[r], bi, g, be, mu, sd), v1 = epilogue<EPI>(acc1[r], bi, g, be, mu, sd);
+            if (FINAL) {
+                if (p < nvalid) m = jmax(m, v0);
+                if (p + 32 < nvalid) m = jmax(m, v1);
+            } else {
+                out[p * kLd + o] = v0;
+                out[(p + 32) * kLd + o] = v1;
+            }
+        }
+        if (FINAL) {
+            m = jmax(m, __shfl_xor(m, 32, 64));
+            if (h == 0) tmax[o] = m;
+        }
+    }
+}
+
+// the same for 3 input channels held as xs[p][3], cout <= 64: one v_fma_f32 chain per (point, channel)
+template <int EPI>
+__device__ __forceinline__ void conv3(const float *xs, float *out, int ld, int cout, const float *__restrict__ W,
+                                      const float *__restrict__ bias, const Bn bn) {
+    for (int idx = threadIdx.x; idx < kTile * cout; idx += kPtThreads) {
+        const int p = idx / cout, o = idx - p * cout;
+        float acc = 0.0f;
+        acc = fmaf(xs[p * 3 + 0], W[3 * o + 0], acc);
+        acc = fmaf(xs[p * 3 + 1], W[3 * o + 1], acc);
+        acc = fmaf(xs[p * 3 + 2], W[3 * o + 2], acc);
+        if (EPI == kNone) out[p * ld + o] = acc;
+        else out[p * ld + o] = epilogue<EPI>(acc, bias[o], bn.g[o], bn.b[o], bn.m[o], sqrtf(bn.v[o] + kBnEps));
+    }
+}
+
+struct PointArgs {
+    const float *x;   // (3, N, B): MODE 0, 1
+    float *h;         // workspace (64, N, B): written by MODE 1, read by MODE 2
+    const float *tf;  // the cloud's transform, (3, 3, B) for MODE 1, (64, 64, B) for MODE 2
+    Conv c0;          // MODE 1: conv_block1
+    Conv c1, c2, c3;  // the round's convolutions (MODE 2: c2, c3)
+    float *tmax;      // (1024, ntiles, B)
+    int N, ntiles;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(kPtThreads) void pointnet_points_kernel(const PointArgs a) {
+    extern __shared__ float lds[];
+    float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
+    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int p0 = tile * kTile;
+    const int nvalid = min(kTile, a.N - p0);
+    float *tmax = a.tmax + ((size_t)b * a.ntiles + tile) * kFeat;
+    // rows beyond the cloud's last point are zeros: they are computed and take part in nothing
+    if (MODE != 2) {
+        const float *xb = a.x + ((size_t)b * a.N + p0) * 3;
+        for (int i = tid; i < kTile * 3; i += kPtThreads) xs[i] = i < nvalid * 3 ? xb[i] : 0.0f;
+    } else {
+        const float *hb = a.h + ((size_t)b * a.N + p0) * 64;
+        for (int i = tid; i < kTile * 64; i += kPtThreads) bufA[(i >> 6) * kLd + (i & 63)] = i < nvalid * 64 ? hb[i] : 0.0f;
+    }
+    __syncthreads();
+    if (MODE == 0) {
+        conv3<kReluBn>(xs, bufA, kLd, 64, a.c1.W, a.c1.b, a.c1.bn);
+        __syncthreads();
+        conv_mfma<64, kReluBn, false>(bufA, bufB, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_mfma<128, kReluBn, true>(bufB, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+    } else if (MODE == 1) {
+        conv3<kNone>(xs, xt, 3, 3, a.tf + (size_t)b * 9, nullptr, Bn{});
+        __syncthreads();
+        conv3<kBnRelu>(xt, bufA, kLd, 64, a.c0.W, a.c0.b, a.c0.bn);
+        __syncthreads();
+        float *hb = a.h + ((size_t)b * a.N + p0) * 64;
+        for (int i = tid; i < nvalid * 64; i += kPtThreads) hb[i] = bufA[(i >> 6) * kLd + (i & 63)];
+        conv_mfma<64, kReluBn, false>(bufA, bufB, 64, a.c1.W, a.c1.b, a.c1.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_mfma<128, kReluBn, true>(bufA, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+    } else {
+        conv_mfma<64, kNone, false>(bufA, bufB, 64, a.tf + (size_t)b * 4096, nullptr, Bn{}, nvalid, nullptr);
+        __syncthreads();
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_mfma<128, kBnOnly, true>(bufA, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+    }
+}
+
+struct HeadArgs {
+    const float *tmax;  // (1024, ntiles, B)
+    int ntiles;
+    Dense d1, d2, d3;   // 1024 -> 512, 512 -> 256, 256 -> n3
+    Bn bn1, bn2;        // FEAT: BatchNorm(512) after d1; both: BatchNorm(256) after d2
+    int n3, K;          // outputs of d3; stn / fstn: n3 = K K
+    float *mat, *mat_user;  // stn / fstn: (K, K, B) in the workspace and, optionally, the caller's copy
+    float *pooled;          // FEAT, optional: (1024, B)
+    float *logits, *probs;  // FEAT: (n3, B) each; logits is the caller's array or the workspace
+};
+
+// x[0 .. n) in LDS, W (nout, n) column-major: acc = fmaf(x[i], W[o, i], acc) upwards from +0.0f
+__device__ __forceinline__ float dense_chain(const float *x, int n, const float *__restrict__ W, int nout, int o) {
+    float acc = 0.0f;
+    const float *w = W + o;
+#pragma unroll 8
+    for (int i = 0; i < n; ++i) acc = fmaf(x[i], w[(size_t)nout * i], acc);
+    return acc;
+}
+
+template <bool FEAT>
+__global__ __launch_bounds__(kHeadThreads) void pointnet_head_kernel(const HeadArgs a) {
+    __shared__ float v0[kFeat], v1[512], v2[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    {
+        const float *t = a.tmax + (size_t)b * a.ntiles * kFeat + tid;
+        float m = t[0];
+        for (int k = 1; k < a.ntiles; ++k) m = jmax(m, t[(size_t)k * kFeat]);
+        v0[tid] = m;
+        if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + tid] = m;
+    }
+    __syncthreads();
+    if (tid < 512) {
+        float v = relu(dense_chain(v0, kFeat, a.d1.W, 512, tid) + a.d1.b[tid]);
+        if (FEAT) v = batchnorm(v, a.bn1.g[tid], a.bn1.b[tid], a.bn1.m[tid], sqrtf(a.bn1.v[tid] + kBnEps));
+        v1[tid] = v;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        const float v = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
+        v2[tid] = batchnorm(v, a.bn2.g[tid], a.bn2.b[tid], a.bn2.m[tid], sqrtf(a.bn2.v[tid] + kBnEps));
+    }
+    __syncthreads();
+    for (int o = tid; o < a.n3; o += kHeadThreads) {
+        const float v = dense_chain(v2, 256, a.d3.W, a.n3, o) + a.d3.b[o];
+        if (FEAT) {
+            a.logits[(size_t)b * a.n3 + o] = relu(v);
+        } else {
+            const size_t at = (size_t)b * a.n3 + (o / a.K) + (size_t)a.K * (o % a.K);
+            a.mat[at] = v;
+            if (a.mat_user) a.mat_user[at] = v;
+        }
+    }
+    if (FEAT) {
+        __syncthreads();  // the block's logits are in memory
+        float *z = a.logits + (size_t)b * a.n3, *pr = a.probs + (size_t)b * a.n3;
+        __shared__ float zmax, esum;
+        if (tid == 0) {
+            float m = z[0];
+            for (int i = 1; i < a.n3; ++i) m = jmax(m, z[i]);
+            zmax = m;
+        }
+        __syncthreads();
+        for (int o = tid; o < a.n3; o += kHeadThreads) pr[o] = expf(z[o] - zmax);
+        __syncthreads();
+        if (tid == 0) {
+            float s = 0.0f;
+            for (int i = 0; i < a.n3; ++i) s = s + pr[i];  // in class order
+            esum = s;
+        }
+        __syncthreads();
+        for (int o = tid; o < a.n3; o += kHeadThreads) pr[o] = pr[o] / esum;
+    }
+}
+
+// ---- the flat parameter buffer, layer by layer in forward order (flux3d_hip.h) ------------------------------------------
+struct Cursor {
+    const float *base;
+    long long at;
+    const float *take(long long n) {
+        const float *p = base ? base + at : nullptr;
+        at += n;
+        return p;
+    }
+    Conv conv(int cin, int cout) {
+        Conv c{};
+        c.W = take((long long)cin * cout);
+        c.b = take(cout);
+        return c;
+    }
+    Bn bn(int c) {
+        Bn r;
+        r.g = take(c); r.b = take(c); r.m = take(c); r.v = take(c);
+        return r;
+    }
+    Dense dense(int in, int out) {
+        Dense d;
+        d.W = take((long long)in * out);
+        d.b = take(out);
+        return d;
+    }
+};
+
+struct Stn { Conv c1, c2, c3; Dense d1, d2, d3; Bn bn; };
+struct Net {
+    Stn stn, fstn;
+    Conv block1, f1, f2;
+    Dense fd1, fd2, cls;
+    Bn fbn1, fbn2;
+    long long count;
+};
+
+Stn layout_stn(Cursor &c, int K) {
+    Stn s;
+    s.c1 = c.conv(K, 64);     s.c1.bn = c.bn(64);
+    s.c2 = c.conv(64, 128);   s.c2.bn = c.bn(128);
+    s.c3 = c.conv(128, 1024); s.c3.bn = c.bn(1024);
+    s.d1 = c.dense(1024, 512);
+    s.d2 = c.dense(512, 256);
+    s.bn = c.bn(256);
+    s.d3 = c.dense(256, K * K);
+    return s;
+}
+
+Net layout(const float *params, int num_classes) {
+    Cursor c{params, 0};
+    Net n;
+    n.stn = layout_stn(c, 3);
+    n.block1 = c.conv(3, 64);   n.block1.bn = c.bn(64);
+    n.fstn = layout_stn(c, 64);
+    n.f1 = c.conv(64, 128);     n.f1.bn = c.bn(128);
+    n.f2 = c.conv(128, 1024);   n.f2.bn = c.bn(1024);
+    n.fd1 = c.dense(1024, 512); n.fbn1 = c.bn(512);
+    n.fd2 = c.dense(512, 256);  n.fbn2 = c.bn(256);
+    n.cls = c.dense(256, num_classes);
+    n.count = c.at;
+    return n;
+}
+
+// the workspace: h (64, N, B) | per-tile maxima (1024, ntiles, B) | T (3, 3, B) | F (64, 64, B) | logits (num_classes, B)
+struct WsPlan { size_t h, tmax, T, F, logits, total; int ntiles; };
+WsPlan ws_plan(int N, int B, int nc) {
+    WsPlan w;
+    w.ntiles = (N + kTile - 1) / kTile;
+    size_t at = 0;
+    auto put = [&](size_t floats) { const size_t o = at; at += (floats * sizeof(float) + 255) & ~(size_t)255; return o; };
+    w.h = put((size_t)64 * N * B);
+    w.tmax = put((size_t)kFeat * w.ntiles * B);
+    w.T = put((size_t)9 * B);
+    w.F = put((size_t)4096 * B);
+    w.logits = put((size_t)nc * B);
+    w.total = at;
+    return w;
+}
+
+fx3d_status check_sizes(const char *fn, int32_t N, int32_t B, int32_t nc) {
+    FX3D_REQUIRE(nc >= 1 && nc <= (1 << 20), "%s: num_classes must be in [1, 2^20], got %d", fn, nc);
+    FX3D_REQUIRE(N >= 1 && B >= 1, "%s: N and B must be positive, got N=%d B=%d", fn, N, B);
+    FX3D_REQUIRE(B <= 65535, "%s: B must be at most 65535, got %d", fn, B);
+    FX3D_REQUIRE((long long)N * B <= (1ll << 31), "%s: N * B must be at most 2^31, got %lld", fn, (long long)N * B);
+    return FX3D_OK;
+}
+
+template <int MODE>
+fx3d_status launch_points(const PointArgs &a, int B, hipStream_t st) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&pointnet_points_kernel<MODE>), (int)kPtLds,
+                                              "pointnet_points_kernel");
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof("pointnet_points", st);
+    hipLaunchKernelGGL(pointnet_points_kernel<MODE>, dim3(a.ntiles, B), dim3(kPtThreads), kPtLds, st, a);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+template <bool FEAT>
+fx3d_status launch_head(const HeadArgs &a, int B, hipStream_t st) {
+    ProfileScope prof("pointnet_head", st);
+    hipLaunchKernelGGL(pointnet_head_kernel<FEAT>, dim3(B), dim3(kHeadThreads), 0, st, a);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+HeadArgs stn_head(const Stn &s, int K, const float *tmax, int ntiles, float *mat, float *mat_user) {
+    HeadArgs h{};
+    h.tmax = tmax; h.ntiles = ntiles;
+    h.d1 = s.d1; h.d2 = s.d2; h.d3 = s.d3; h.bn2 = s.bn;
+    h.n3 = K * K; h.K = K; h.mat = mat; h.mat_user = mat_user;
+    return h;
+}
+
+}  // namespace
+
+extern "C" {
+
+fx3d_status fx3d_pointnet_param_count(int32_t num_classes, int64_t *count) {
+    FX3D_REQUIRE(count != nullptr, "fx3d_pointnet_param_count: count is NULL");
+    FX3D_REQUIRE(num_classes >= 1 && num_classes <= (1 << 20), "fx3d_pointnet_param_count: num_classes must be in [1, 2^20], got %d",
+                 num_classes);
+    *count = layout(nullptr, num_classes).count;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_pointnet_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes) {
+    FX3D_REQUIRE(bytes != nullptr, "fx3d_pointnet_workspace_bytes: bytes is NULL");
+    const fx3d_status rc = check_sizes("fx3d_pointnet_workspace_bytes", N, B, num_classes);
+    if (rc != FX3D_OK) return rc;
+    *bytes = ws_plan(N, B, num_classes).total;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_classes, const float *x, int32_t N, int32_t B,
+                                  float *probs, float *logits, float *stn, float *fstn, float *pooled, void *ws,
+                                  size_t ws_bytes, fx3d_stream_t s) {
+    const char *fn = "fx3d_pointnet_forward";
+    FX3D_REQUIRE(params_dev && x && probs && ws, "%s: params_dev, x, probs and ws must not be NULL", fn);
+    const fx3d_status rc = check_sizes(fn, N, B, num_classes);
+    if (rc != FX3D_OK) return rc;
+    const WsPlan w = ws_plan(N, B, num_classes);
+    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_pointnet_workspace_bytes says %zu", fn, ws_bytes, w.total);
+    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", fn);
+    const Net n = layout(params_dev, num_classes);
+    hipStream_t st = as_stream(s);
+    char *wsb = static_cast<char *>(ws);
+    float *h = reinterpret_cast<float *>(wsb + w.h), *tmax = reinterpret_cast<float *>(wsb + w.tmax);
+    float *T = reinterpret_cast<float *>(wsb + w.T), *F = reinterpret_cast<float *>(wsb + w.F);
+    float *lg = logits ? logits : reinterpret_cast<float *>(wsb + w.logits);
+
+    PointArgs p{};
+    p.x = x; p.h = h; p.tmax = tmax; p.N = N; p.ntiles = w.ntiles;
+    fx3d_status r;
+    // stn: the (3, 3) input transform of every cloud
+    p.c1 = n.stn.c1; p.c2 = n.stn.c2; p.c3 = n.stn.c3;
+    if ((r = launch_points<0>(p, B, st)) != FX3D_OK) return r;
+    if ((r = launch_head<false>(stn_head(n.stn, 3, tmax, w.ntiles, T, stn), B, st)) != FX3D_OK) return r;
+    // input transform, conv_block1 (kept as h), fstn: the (64, 64) feature transform
+    p.tf = T; p.c0 = n.block1; p.c1 = n.fstn.c1; p.c2 = n.fstn.c2; p.c3 = n.fstn.c3;
+    if ((r = launch_points<1>(p, B, st)) != FX3D_OK) return r;
+    if ((r = launch_head<false>(stn_head(n.fstn, 64, tmax, w.ntiles, F, fstn), B, st)) != FX3D_OK) return r;
+    // feature transform, feat, cls, softmax
+    p.tf = F; p.c2 = n.f1; p.c3 = n.f2;
+    if ((r = launch_points<2>(p, B, st)) != FX3D_OK) return r;
+    HeadArgs hd{};
+    hd.tmax = tmax; hd.ntiles = w.ntiles;
+    hd.d1 = n.fd1; hd.bn1 = n.fbn1; hd.d2 = n.fd2; hd.bn2 = n.fbn2; hd.d3 = n.cls;
+    hd.n3 = num_classes; hd.K = 1; hd.pooled = pooled; hd.logits = lg; hd.probs = probs;
+    return launch_head<true>(hd, B, st);
+}
+
+}  // extern "C"

@@ -29,7 +29,7 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  compute_verts_normals_packed, compute_faces_normals_packed,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
                  _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel,
-                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!
+                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!, PointNet
 using SparseArrays: SparseMatrixCSC, findnz
 import Zygote
 
@@ -1470,6 +1470,65 @@ function realign_pointcloud!(p::PointCloud, tgt::PointCloud, index::Number = 1)
     tmin, tmax = _minmax_dev(hip(unhip(t)[:, :, Int(index)]), D, N, 1, nothing, false)   # tgt[index] (pcloud_func.jl:221-224)
     return realign_pointcloud!(p, unhip(tmin), unhip(tmax))
 end
+
+# ---- PointNet inference: (m::PointNet)(X) (src/models/pointnet.jl:62-85) in test mode ------------------------------------
+# The Flux layers' arrays are flattened, in forward order, into the one Float32 buffer fx3d_pointnet_forward reads
+# (include/flux3d_hip.h "PointNet inference": conv weight (1, Cin, Cout) then bias; BatchNorm gamma, beta, mu, sigma2; dense
+# weight (out, in) then bias -- Julia's column-major order is the library's).  They are flattened on every call: the model is
+# mutable (training steps on the host change it).  BatchNorm's running statistics are used and Dropout is the identity,
+# which is what a plain call outside a gradient computes; logits, both transforms and the pooled feature are bit for bit
+# the definition in the header, not Flux's BLAS sums.
+_dense_wb(d) = hasproperty(d, :weight) ? (d.weight, d.bias) : (d.W, d.b)   # Flux >= 0.12 : Flux <= 0.11
+_flat!(out::Vector{Float32}, a) = append!(out, vec(Float32.(collect(a))))
+_flat_conv!(out, c) = (_flat!(out, c.weight); _flat!(out, c.bias))
+_flat_bn!(out, b) = (_flat!(out, b.γ); _flat!(out, b.β); _flat!(out, b.μ); _flat!(out, b.σ²))
+_flat_dense!(out, d) = (wb = _dense_wb(d); _flat!(out, wb[1]); _flat!(out, wb[2]))
+function _flat_stn!(out, s)   # stnKD (src/models/pointnet.jl:3-20): Conv, BN three times, two closures, Dense, Dense, BN, Dense
+    for i in (1, 3, 5)
+        _flat_conv!(out, s[i]); _flat_bn!(out, s[i + 1])
+    end
+    _flat_dense!(out, s[9]); _flat_dense!(out, s[10]); _flat_bn!(out, s[11]); _flat_dense!(out, s[12])
+    return out
+end
+function pointnet_params(m::PointNet)
+    out = Float32[]
+    _flat_stn!(out, m.stn)
+    _flat_conv!(out, m.conv_block1[1]); _flat_bn!(out, m.conv_block1[2])       # conv_bn_block (src/models/utils.jl:1-3)
+    _flat_stn!(out, m.fstn)
+    f = m.feat                                                                  # src/models/pointnet.jl:45-57
+    _flat_conv!(out, f[1]); _flat_bn!(out, f[2]); _flat_conv!(out, f[3]); _flat_bn!(out, f[4])
+    _flat_dense!(out, f[7]); _flat_bn!(out, f[8]); _flat_dense!(out, f[9]); _flat_bn!(out, f[11])
+    _flat_dense!(out, m.cls)
+    return out
+end
+function pointnet_forward(m::PointNet, X::HipArray{Float32,3}; intermediates::Bool = false)
+    size(X, 1) == 3 || error("PointNet takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    (N >= 1 && B >= 1) || error("PointNet needs at least one point and one cloud")
+    nc = size(_dense_wb(m.cls)[1], 1)
+    size(_dense_wb(m.fstn[12])[1], 1) == 64 * 64 ||
+        error("PointNet(num_classes, K) needs K = 64: conv_block1 has 64 output channels whatever K is (src/models/pointnet.jl:41-60)")
+    params = pointnet_params(m)
+    cnt = Ref{Int64}(0)
+    check(@ccall LIB.fx3d_pointnet_param_count(Int32(nc)::Int32, cnt::Ref{Int64})::Int32)
+    length(params) == cnt[] || error("PointNet has $(length(params)) parameters, the library expects $(cnt[])")
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_pointnet_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(nc)::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    probs = HipArray{Float32}(undef, nc, B)
+    logits = intermediates ? HipArray{Float32}(undef, nc, B) : nothing
+    stn = intermediates ? HipArray{Float32}(undef, 3, 3, B) : nothing
+    fstn = intermediates ? HipArray{Float32}(undef, 64, 64, B) : nothing
+    pooled = intermediates ? HipArray{Float32}(undef, 1024, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_pointnet_forward(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, X.ptr::Ptr{Cvoid}, Int32(N)::Int32, Int32(B)::Int32,
+                                           probs.ptr::Ptr{Cvoid}, opt(logits)::Ptr{Cvoid}, opt(stn)::Ptr{Cvoid},
+                                           opt(fstn)::Ptr{Cvoid}, opt(pooled)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid},
+                                           length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    return intermediates ? (probs = probs, logits = logits, stn = stn, fstn = fstn, pooled = pooled) : probs
+end
+(m::PointNet)(X::HipArray{Float32,3}) = pointnet_forward(m, X)
 
 
 end # module

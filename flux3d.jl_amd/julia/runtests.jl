@@ -184,4 +184,20 @@ end
         @test unhip(out_a) == unhip(sep)
         @test unhip(g2) == unhip(g1) && unhip(x2) == unhip(x1) && unhip(v2) == unhip(v1) && unhip(o2) == unhip(o1)
     end
+
+    @testset "PointNet (test/models.jl:5-22) on a device batch" begin
+        x_test = rand(Float32, 3, 64, 2)
+        for num_classes in [10, 40]
+            model = Flux3D.PointNet(num_classes)
+            y_test = model(hip(x_test))
+            @test y_test isa AbstractArray
+            @test size(y_test) == (num_classes, size(x_test, 3))
+            y = unhip(y_test)
+            @test all(isapprox.(sum(y, dims = 1), 1f0, atol = 1f-5))
+            @test isapprox(y, Flux3D.Flux.testmode!(model)(x_test), rtol = 1f-3)     # Flux's BLAS sums: close, not equal
+            r = Flux3DHip.pointnet_forward(model, hip(x_test); intermediates = true)
+            @test size(r.stn) == (3, 3, 2) && size(r.fstn) == (64, 64, 2) && size(r.pooled) == (1024, 2)
+            @test unhip(Flux3DHip.pointnet_forward(model, hip(x_test))) == y              # the same bits on every run
+        end
+    end
 end

@@ -762,6 +762,45 @@ FX3D_API fx3d_status fx3d_build_laplacian_csr(const int64_t *edges, int64_t E, i
                                               int32_t index_base, int32_t *rowptr,
                                               int32_t *colind, float *vals, int64_t *nnz_out);
 
+/* ---- PointNet inference: (m::PointNet)(X) (src/models/pointnet.jl:62-85) in test mode -----------------------------
+ * Forward only, Float32: BatchNorm uses its running statistics, Dropout is the identity.  x (3,N,B) device; point n of
+ * cloud b has channels x[:,n,b].  PointNet(num_classes, 64): the reference's conv_block1 is fixed at 64 channels, so no
+ * other K works there (src/models/pointnet.jl:41-60).  In the order the layers run (stnKD: :3-20, conv_bn_block:
+ * src/models/utils.jl:1-3):
+ *   stn   = stnKD(3):  conv 3->64, relu, BN . conv 64->128, relu, BN . conv 128->1024, relu, BN . max over the N points .
+ *                      dense 1024->512, relu . dense 512->256, relu . BN(256) . dense 256->9;
+ *                      T (3,3,B), T[i,j,b] = d[j + 3 i] (the reshape is column-major, then the transpose; no identity added)
+ *   x'[j] = sum_i x[i] T[i,j,b] per point
+ *   conv_block1:       conv 3->64, BN, relu (this order)                                   -> h (N,64,B)
+ *   fstn  = stnKD(64): as stn with 64 input channels and a last dense 256->4096;  F (64,64,B), F[i,j,b] = d[j + 64 i]
+ *   h'[j] = sum_i h[i] F[i,j,b] per point
+ *   feat:              conv 64->128, relu, BN . conv 128->1024 (no activation), BN . max over N (= pooled (1024,B)) .
+ *                      dense 1024->512, relu . BN(512) . dense 512->256, relu . (Dropout) . BN(256)
+ *   cls:               dense 256->num_classes, relu (before the softmax, :58) = logits . softmax over the classes = probs
+ * Arithmetic (the contract; tests/pointnet_ref.py restates it on the host):
+ *   contraction (conv, dense, both transforms): acc = +0.0f; for c ascending: acc = fmaf(x[c], W[c,o], acc); conv and dense
+ *     then add the bias with one Float32 addition and apply the activation (Flux: sigma.(W*x .+ b));
+ *   relu = Julia's max(0, v): NaN stays NaN, relu(-0.0) = +0.0;
+ *   BatchNorm, eps = 1f-5: (gamma * ((v - mu) / sqrt(var + eps))) + beta, every operation rounded to Float32, division
+ *     and square root correctly rounded;
+ *   max over the points = Julia's max (NaN wins, max(-0.0, +0.0) = +0.0): order-free;
+ *   softmax: e = exp(z - max z), e / sum e with the sum in class order; exp is not pinned to a bit pattern.
+ * logits, stn, fstn and pooled are bit-identical to that restatement and from run to run, whatever N, B and the launch
+ * shape: one accumulator per output element, no contraction split over waves or blocks, no float atomics.
+ * params_dev: ONE flat device Float32 buffer, the layers' arrays in forward order -- stn, conv_block1, fstn, feat, cls --,
+ *   each layer as:  conv  W (Cin,Cout) column-major (Flux's (1,Cin,Cout)), then b (Cout);
+ *                   BatchNorm  gamma, beta, mu, var (C each);
+ *                   dense  W (out,in) column-major, then b (out).
+ *   fx3d_pointnet_param_count(num_classes) is its length in floats.
+ * probs (num_classes,B) is required; logits (num_classes,B), stn (3,3,B), fstn (64,64,B), pooled (1024,B) are optional
+ * (NULL: not written).  Six launches on `s`, no host synchronisation, no host memory read after the argument check
+ * (graph-capturable).  ws: fx3d_pointnet_workspace_bytes(N, B, num_classes), 16-byte aligned. */
+FX3D_API fx3d_status fx3d_pointnet_param_count(int32_t num_classes, int64_t *count);
+FX3D_API fx3d_status fx3d_pointnet_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_classes, const float *x, int32_t N,
+                                           int32_t B, float *probs, float *logits, float *stn, float *fstn,
+                                           float *pooled, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
