@@ -6,41 +6,29 @@
 // CPU path's arithmetic (Float32 sum of squared differences in dimension order, unfused), so the
 // index lists are bit-identical to oracle/flux3d_oracle.c:fx3d_oracle_knn.
 //
-// Kernels, in file order (dispatch in launch_knn / fx3d_edgeconv_graph at the end of the file):
-//   knn_wave_d3_kernel / knn_wave_generic_kernel   one wave per query, exact distances: every shape the two below do not take
-//   knn_exact_bruteforce / knn_rank_ties4          wave-cooperative exact selection / tie re-rank shared by all kernels
-//   knn_gather[4]_kernel                           X[:, idx] (src/models/dgcnn.jl:6)
+// This unit, in file order (the other units of the family: knn_d3.hip, knn_mfma.hip; what they share: knn_common.h):
+//   knn_wave_d3_kernel / knn_wave_generic_kernel   one wave per query, exact distances: every shape the kernels below do not take
 //   knn_select_kernel                              any k + drop <= M, any D (M <= 36864): all keys of a query in LDS, radix select;
 //                                                  also the fallback of the verified slice merge (flagged queries only)
-//   knn_tau_8of16                                  tau of the matrix-core kernels from 128 group minima per query (shared, round 4)
-//   knn_f16_d3_kernel<FEAT, K3Geom>                D = 3: fp16-split matrix-core filter + exact re-scan in three geometries --
-//                                                  base (k+drop <= 32, M >= 64), compact (<= 48, two blocks per CU), wide (<= 64);
-//                                                  FEAT: EdgeConv's cat(X, KNN - X) written by the same kernel
-//   knn_pre_*_kernel                               fx3d_knn_ws: per-cloud statistics + fp16 image built once (feature space)
-//   knn_mfma_kernel<DK, F16, PRE>                  4 <= D <= 128, k+drop <= 32, M >= 64: GEMM filter (fp16 rounded halves or
-//                                                  Float32) + exact re-scan, medium path for crowded bands
-//   edge_features_*_kernel                         cat(X, KNN - X) + permute for any F, and the @nograd adjoint
 //   knn_interleave_kernel / knn_merge_slices_kernel  fx3d_knn_ws: candidate slices as virtual clouds (few clouds with many rows;
 //                                                  k+drop in 33 ... 128 in feature space: 32 nearest per slice, verified merge)
-// (round 5: one translation unit per kernel family -- knn_d3.hip, knn_mfma.hip; the shared helpers in knn_common.h)
+//   knn_route / knn_slices / KnnScratch::plan      the host decisions, one owner each: which kernel a shape takes, how many
+//                                                  candidate slices, the layout of the scratch
+//   launch_knn_select / launch_knn                 the launches of this unit's kernels; the matrix-core kernels are launched by
+//                                                  their units (knn_d3_launch, knn_mfma_launch)
+//   fx3d_knn / fx3d_knn_workspace_bytes / fx3d_knn_ws / fx3d_edgeconv_graph   the C entry points
+// Elsewhere:
+//   knn_common.h       knn_exact_bruteforce / knn_rank_ties[4] / knn_tau_8of16: the wave-cooperative exact selection, tie re-rank and
+//                      tau bound the matrix-core kernels share; the shape predicates
+//   knn_d3.hip         knn_f16_d3_kernel<FEAT, K3Geom>: D = 3, fp16-split matrix-core filter + exact re-scan in three geometries --
+//                      base (k+drop <= 32, M >= 64), compact (<= 48, two blocks per CU), wide (<= 64); FEAT: EdgeConv's
+//                      cat(X, KNN - X) written by the same kernel
+//   knn_mfma.hip       knn_pre_*_kernel (fx3d_knn_ws: per-cloud statistics + fp16 image built once) and knn_mfma_kernel<DK, F16, PRE>:
+//                      4 <= D <= 128, k+drop <= 32, M >= 64: GEMM filter (fp16 rounded halves or Float32) + exact re-scan
+//   edge_features.hip  knn_gather[4]_kernel, edge_features_*_kernel: X[:, idx], cat(X, KNN - X) + permute for any F, the adjoint
 #include "knn_common.h"
 
 namespace {
-
-#ifndef FX3D_KNN_ONE_TU  // (tools/knn_probe.hip includes the three units into one: the names below are then the units' own)
-// the other units' entry points under the names the dispatch below was written with
-inline fx3d_status launch_knn_f16_d3(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx, float *dist,
-                                     hipStream_t st, float *feat = nullptr, int layout = 0, int xdiv = 1) {
-    return knn_d3_launch(x, N, y, M, B, k, drop, idx, dist, st, feat, layout, xdiv);
-}
-inline fx3d_status launch_knn_mfma(const float *x, int N, const float *y, int M, int B, int D, int k, int drop, int32_t *idx, float *dist,
-                                   hipStream_t st, void *pre_ws = nullptr, int xdiv = 1) {
-    return knn_mfma_launch(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-}
-inline bool knn_pre_shape_ok(int M, int D, int kk) { return knn_mfma_pre_shape_ok(M, D, kk); }
-inline bool knn_pre_eligible(const float *x, const float *y, int M, int D, int kk) { return knn_mfma_pre_eligible(x, y, M, D, kk); }
-inline size_t knn_pre_bytes(int M, int B, int D) { return knn_mfma_pre_bytes(M, B, D); }
-#endif
 
 __global__ __launch_bounds__(kWThreads) void knn_wave_d3_kernel(const float *__restrict__ x, int N,
                                                                 const float *__restrict__ y, int M, int B,
@@ -517,188 +505,6 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float *__restrict
     knn_select_wave(keys, M, Mpad, lcap, N, b, qi, k, drop, lane, idx, dist);
 }
 
-// out[(((b*N+i)*k + r)*F + f] = x[(b*N + idx[(b*N+i)*k + r])*F + f]
-__global__ __launch_bounds__(kThreads) void knn_gather_kernel(const float *__restrict__ x, int N, int B,
-                                                              int F, int k,
-                                                              const int32_t *__restrict__ idx,
-                                                              float *__restrict__ out) {
-    const long long total = (long long)B * N * k * F;
-    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (long long)gridDim.x * kThreads) {
-        const long long row = e / F;  // (b*N+i)*k + r
-        const int f = (int)(e - row * F);
-        const long long bn = row / k;
-        const int b = (int)(bn / N);
-        const int j = idx[row];
-        out[e] = x[((size_t)b * N + j) * F + f];
-    }
-}
-
-
-
-constexpr size_t kStreamingStoreBytes = (size_t)192 << 20;
-template <bool NT>
-__global__ __launch_bounds__(kThreads) void knn_gather4_kernel(const float *__restrict__ x, int N, int B, int F4, int k,
-                                                               const int32_t *__restrict__ idx, float *__restrict__ out) {
-    const long long total = (long long)B * N * k * F4;
-    const f32x4v *x4 = reinterpret_cast<const f32x4v *>(x);
-    f32x4v *o4 = reinterpret_cast<f32x4v *>(out);
-    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (long long)gridDim.x * kThreads) {
-        const long long row = e / F4;  // (b*N+i)*k + r
-        const int f = (int)(e - row * F4);
-        const int b = (int)(row / k / N);
-        const f32x4v v = x4[((size_t)b * N + idx[row]) * F4 + f];
-        if (NT) __builtin_nontemporal_store(v, o4 + e);
-        else o4[e] = v;
-    }
-}
-
-// ---- EdgeConv graph features (src/models/dgcnn.jl:36-51): cat(X, KNNGraph - X, dims=1) in one pass --------
-// layout 0: out (2F,K,N,B) as the reference holds it after `cat(..., dims = 1)` (:45)
-__global__ __launch_bounds__(kThreads) void edge_features_cat_kernel(const float *__restrict__ x, int N, int B,
-                                                                     int F, int k,
-                                                                     const int32_t *__restrict__ idx,
-                                                                     float *__restrict__ out) {
-    const long long total = (long long)B * N * k * 2 * F;
-    const int F2 = 2 * F;
-    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (long long)gridDim.x * kThreads) {
-        const long long row = e / F2;  // (b*N+i)*k + r
-        const int f = (int)(e - row * F2);
-        const long long bn = row / k;  // b*N + i
-        if (f < F) {
-            out[e] = x[(size_t)bn * F + f];
-        } else {
-            const int b = (int)(bn / N);
-            const int j = idx[row];
-            out[e] = x[((size_t)b * N + j) * F + (f - F)] - x[(size_t)bn * F + (f - F)];
-        }
-    }
-}
-
-// layout 1: out (K*N, 2F, B), what reaches the 1x1 conv after PermutedDimsArray + reshape (:48-51).
-// One thread per (r,i) position (the contiguous dimension of the output), looping over features, so every
-// feature row is written with unit stride; the two source rows are read as float4 when F % 4 == 0.
-template <bool VEC4>
-__global__ __launch_bounds__(kThreads) void edge_features_mlp_kernel(const float *__restrict__ x, int N, int B,
-                                                                     int F, int k,
-                                                                     const int32_t *__restrict__ idx,
-                                                                     float *__restrict__ out) {
-    const int b = blockIdx.y;
-    const long long KN = (long long)k * N;
-    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;  // i*k + r
-    if (e >= KN) return;
-    const int i = (int)(e / k);
-    const int j = idx[(size_t)b * KN + e];
-    const float *xi = x + ((size_t)b * N + i) * F;
-    const float *xj = x + ((size_t)b * N + j) * F;
-    float *o = out + (size_t)b * 2 * F * KN + e;
-    if (VEC4) {
-        for (int f = 0; f < F; f += 4) {
-            const float4 a = *reinterpret_cast<const float4 *>(xi + f);
-            const float4 c = *reinterpret_cast<const float4 *>(xj + f);
-            o[(size_t)(f + 0) * KN] = a.x;
-            o[(size_t)(f + 1) * KN] = a.y;
-            o[(size_t)(f + 2) * KN] = a.z;
-            o[(size_t)(f + 3) * KN] = a.w;
-            o[(size_t)(F + f + 0) * KN] = c.x - a.x;
-            o[(size_t)(F + f + 1) * KN] = c.y - a.y;
-            o[(size_t)(F + f + 2) * KN] = c.z - a.z;
-            o[(size_t)(F + f + 3) * KN] = c.w - a.w;
-        }
-    } else {
-        for (int f = 0; f < F; ++f) {
-            const float a = xi[f];
-            o[(size_t)f * KN] = a;
-            o[(size_t)(F + f) * KN] = xj[f] - a;
-        }
-    }
-}
-
-// Same, four consecutive (r,i) positions per thread: the 4 x 4 block (4 positions x 4 features) is read as
-// float4 along the features and written as float4 along the positions -- every store is 16 bytes, a wave writes
-// 1 KiB runs.  Needs F % 4 == 0, (k*N) % 4 == 0 and 16-byte aligned x / out.
-// Round 4: blockIdx.z splits the feature loop (fper features per block) -- F = 64 at C4' is 335 MB written by what used to be 640
-// blocks (2.5 per CU, ten waves per CU, each a serial loop of load -> 8 stores); the write stream wants many more waves in
-// flight (tools/ubench_hbm.hip: 4.7 TB/s from 2048 blocks, 6.1 from 32768) -- and NT selects streaming (non-temporal) stores:
-// the tensor is larger than the Infinity Cache and nobody reads it back inside the launch.
-template <bool NT>
-__global__ __launch_bounds__(kThreads) void edge_features_mlp4_kernel(const float *__restrict__ x, int N, int B,
-                                                                      int F, int k,
-                                                                      const int32_t *__restrict__ idx,
-                                                                      float *__restrict__ out, int fper) {
-    const int b = blockIdx.y;
-    const long long KN = (long long)k * N;
-    const long long e0 = ((long long)blockIdx.x * kThreads + threadIdx.x) * 4;  // i*k + r of the first position
-    if (e0 >= KN) return;
-    const int f_lo = blockIdx.z * fper, f_hi = f_lo + fper < F ? f_lo + fper : F;
-    const int4 jj = *reinterpret_cast<const int4 *>(idx + (size_t)b * KN + e0);
-    const float *xb = x + (size_t)b * N * F;
-    const float *xi0 = xb + (size_t)(e0 / k) * F, *xi1 = xb + (size_t)((e0 + 1) / k) * F;
-    const float *xi2 = xb + (size_t)((e0 + 2) / k) * F, *xi3 = xb + (size_t)((e0 + 3) / k) * F;
-    const float *xj0 = xb + (size_t)jj.x * F, *xj1 = xb + (size_t)jj.y * F, *xj2 = xb + (size_t)jj.z * F,
-                *xj3 = xb + (size_t)jj.w * F;
-    float *o = out + (size_t)b * 2 * F * KN + e0;
-    auto put = [](float *p, const f32x4v &v) {
-        if (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4v *>(p));
-        else *reinterpret_cast<f32x4v *>(p) = v;
-    };
-    for (int f = f_lo; f < f_hi; f += 4) {
-        const float4 a0 = *reinterpret_cast<const float4 *>(xi0 + f), a1 = *reinterpret_cast<const float4 *>(xi1 + f);
-        const float4 a2 = *reinterpret_cast<const float4 *>(xi2 + f), a3 = *reinterpret_cast<const float4 *>(xi3 + f);
-        const float4 c0 = *reinterpret_cast<const float4 *>(xj0 + f), c1 = *reinterpret_cast<const float4 *>(xj1 + f);
-        const float4 c2 = *reinterpret_cast<const float4 *>(xj2 + f), c3 = *reinterpret_cast<const float4 *>(xj3 + f);
-        put(o + (size_t)(f + 0) * KN, f32x4v{a0.x, a1.x, a2.x, a3.x});
-        put(o + (size_t)(f + 1) * KN, f32x4v{a0.y, a1.y, a2.y, a3.y});
-        put(o + (size_t)(f + 2) * KN, f32x4v{a0.z, a1.z, a2.z, a3.z});
-        put(o + (size_t)(f + 3) * KN, f32x4v{a0.w, a1.w, a2.w, a3.w});
-        put(o + (size_t)(F + f + 0) * KN, f32x4v{c0.x - a0.x, c1.x - a1.x, c2.x - a2.x, c3.x - a3.x});
-        put(o + (size_t)(F + f + 1) * KN, f32x4v{c0.y - a0.y, c1.y - a1.y, c2.y - a2.y, c3.y - a3.y});
-        put(o + (size_t)(F + f + 2) * KN, f32x4v{c0.z - a0.z, c1.z - a1.z, c2.z - a2.z, c3.z - a3.z});
-        put(o + (size_t)(F + f + 3) * KN, f32x4v{c0.w - a0.w, c1.w - a1.w, c2.w - a2.w, c3.w - a3.w});
-    }
-}
-
-// Adjoint w.r.t. X.  CreateSingleKNNGraph is @nograd (src/models/dgcnn.jl:9), so the gathered neighbours are
-// constants and dX[f,i,b] = sum_r (g[f,r,i,b] - g[F+f,r,i,b]), accumulated in rank order.
-__global__ __launch_bounds__(kThreads) void edge_features_bwd_kernel(const float *__restrict__ g, int N, int B, int F,
-                                                                     int k, int layout, float *__restrict__ gx) {
-    const long long total = (long long)B * N * F;
-    const long long KN = (long long)k * N;
-    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (long long)gridDim.x * kThreads) {
-        long long bn;
-        int f;
-        if (layout == 0) {  // consecutive threads -> consecutive f (reads stride 1 in f)
-            bn = e / F;
-            f = (int)(e - bn * F);
-        } else {            // consecutive threads -> consecutive i (reads k-float runs)
-            const long long bf = e / N;
-            const int i = (int)(e - bf * N);
-            const int b = (int)(bf / F);
-            f = (int)(bf - (long long)b * F);
-            bn = (long long)b * N + i;
-        }
-        const int b = (int)(bn / N);
-        const int i = (int)(bn - (long long)b * N);
-        float acc = 0.0f;
-        for (int r = 0; r < k; ++r) {
-            float a, c;
-            if (layout == 0) {
-                const size_t base = ((size_t)bn * k + r) * 2 * F;
-                a = g[base + f];
-                c = g[base + F + f];
-            } else {
-                const size_t base = (size_t)b * 2 * F * KN + (size_t)i * k + r;
-                a = g[base + (size_t)f * KN];
-                c = g[base + (size_t)(F + f) * KN];
-            }
-            acc = acc + (a - c);
-        }
-        gx[(size_t)bn * F + f] = acc;
-    }
-}
 
 size_t knn_wave_generic_lds(int D) {
     return (size_t)kGT * (D + 1) * 4 + (kWThreads / 64) * (kGQ * (64 * 16 + 8) + D * 16) + 16;
@@ -720,13 +526,24 @@ int knn_select_list(int M, int kk, int *nw) {
     *nw = w > 4 ? 4 : w;
     return lcap;
 }
-bool knn_needs_select(int M, int D, int kk) {
-    // (D = 3, 44 < kk <= 64: the wave kernel's candidate list holds 64 - kk entries between merges -- 546 us at kk = 64 and C4's
-    //  shape against 188 us here, 160 against ~185 at kk = 41)
-    if (D == 3 && knn_f16_d3_shape_ok(M, kk)) return false;  // (round 3: the matrix-core kernel up to kk = 64)
-    if (D == 3 && kk > 44 && kk <= 64 && knn_select_waves(M) >= 1) return true;
-    return kk > 64 || (D != 3 && !knn_mfma_eligible(M, D, kk) && knn_wave_generic_lds(D) > 64 * 1024);
+// Which kernel a shape takes: the ONE owner of that decision (launch_knn, the entry points' checks, knn_slices, the fused case of
+// fx3d_edgeconv_graph).  A pure function of the shape and of the option knn_no_mfma.
+enum class KnnRoute { Select, F16D3, WaveD3, Mfma, WaveGeneric };
+KnnRoute knn_route(int M, int D, int kk) {
+    if (D == 3) {
+        if (knn_f16_d3_shape_ok(M, kk)) return KnnRoute::F16D3;  // (round 3: the matrix-core kernel up to kk = 64)
+        // (44 < kk <= 64: the wave kernel's candidate list holds 64 - kk entries between merges -- 546 us at kk = 64 and C4's
+        //  shape against 188 us for the selection kernel, 160 against ~185 at kk = 41)
+        if (kk > 64 || (kk > 44 && knn_select_waves(M) >= 1)) return KnnRoute::Select;
+        return KnnRoute::WaveD3;
+    }
+    const bool mfma = !opt(OPT_KNN_NO_MFMA) && knn_mfma_eligible(M, D, kk);
+    if (kk > 64 || (!mfma && knn_wave_generic_lds(D) > 64 * 1024)) return KnnRoute::Select;  // (D >= 85: the wave kernel's tile does not fit)
+    return mfma ? KnnRoute::Mfma : KnnRoute::WaveGeneric;
 }
+// the kernels that index the batch by blockIdx.y (B <= 65535); the matrix-core kernels fold it into blockIdx.x
+bool knn_route_batch_in_grid_y(KnnRoute r) { return r == KnnRoute::Select || r == KnnRoute::WaveD3 || r == KnnRoute::WaveGeneric; }
+bool knn_route_matrix_core(KnnRoute r) { return r == KnnRoute::F16D3 || r == KnnRoute::Mfma; }  // ... which also take candidate slices (xdiv)
 
 // ---- candidate slices (few clouds with many rows; fx3d_knn_ws) -----------------------------------------------------------------
 // A block of the matrix-core kernels takes 128 (64) queries against ALL candidates of their cloud: B = 1, N = M = 8192 is 64
@@ -846,7 +663,7 @@ int knn_slices(int N, int M, int B, int D, int kk) {
     const int force = opt(OPT_KNN_SLICES);  // 0 = automatic, 1 = never, 2 / 4 / 8 = forced (when the shape allows it)
     if (force == 1) return 1;
     const bool d3 = D == 3;
-    if (d3 ? !knn_f16_d3_shape_ok(M, kk) : (opt(OPT_KNN_NO_MFMA) || !knn_mfma_eligible(M, D, kk))) return 1;
+    if (!knn_route_matrix_core(knn_route(M, D, kk))) return 1;
     const int qpb = d3 && kk > 32 ? 64 : 128;
     const long long blocks = (long long)B * ((N + qpb - 1) / qpb);
     const int ncu = device_cus();
@@ -890,6 +707,7 @@ struct KnnScratch {
     int kl;       // entries per slice list: k + drop, or 32 with `verify`
     bool verify;  // the slices' lists are shorter than k + drop: verified merge + fallback for the flagged queries
     size_t pre_bytes, list_bytes, flag_bytes, copy_bytes, total;
+    size_t list_off, flag_off, copy_off;  // the parts' offsets ([0, pre_bytes): the pre-pass slabs; distances: list_off + list_bytes)
     static KnnScratch plan(int N, int M, int B, int D, int kk) {
         KnnScratch p{};
         p.S = knn_slices(N, M, B, D, kk);
@@ -899,48 +717,65 @@ struct KnnScratch {
             if (W > 1 && (long long)B * W <= 65535) { p.S = W; p.kl = 32; p.verify = true; }
         }
         const int Ms = M / p.S;
-        p.pre_bytes = knn_pre_shape_ok(Ms, D, p.kl) ? (knn_pre_bytes(Ms, B * p.S, D) + 255) & ~(size_t)255 : 0;
+        p.pre_bytes = knn_mfma_pre_shape_ok(Ms, D, p.kl) ? (knn_mfma_pre_bytes(Ms, B * p.S, D) + 255) & ~(size_t)255 : 0;
         p.list_bytes = p.S > 1 ? (((size_t)p.kl * N * B * p.S * 4 + 255) & ~(size_t)255) : 0;
         p.flag_bytes = p.verify ? (((size_t)N * B + 255) & ~(size_t)255) : 0;
         p.copy_bytes = p.verify ? (((size_t)M * D * B * 4 + 255) & ~(size_t)255) : 0;  // the interleaved copy of the candidate clouds
-        p.total = p.pre_bytes + 2 * p.list_bytes + p.flag_bytes + p.copy_bytes;
+        p.list_off = p.pre_bytes;
+        p.flag_off = p.list_off + 2 * p.list_bytes;
+        p.copy_off = p.flag_off + p.flag_bytes;
+        p.total = p.copy_off + p.copy_bytes;
         return p;
     }
 };
 
+// knn_select_kernel's one launch.  flags == nullptr: every query, a wave per query, as many waves per block as their key arrays fit
+// in LDS; else (the verified slice merge) the flagged queries only: 256 threads per 32 consecutive queries, a key array per wave
+// when four fit (many flagged queries), else one for the block.
+fx3d_status launch_knn_select(const float *x, int N, const float *y, int M, int B, int D, int k, int drop, int32_t *idx, float *dist,
+                              const unsigned char *flags, hipStream_t st) {
+    int nw = knn_select_waves(M);
+    const int Mpad = (M + 255) / 256 * 256;
+    const int lcap = knn_select_list(M, k + drop, &nw);
+    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_select_kernel), kSelMaxLds, "knn_select_kernel");
+    if (arc != FX3D_OK) return arc;
+    const int regions = flags ? (nw >= 4 ? 4 : 1) : nw;  // key arrays in LDS
+    hipLaunchKernelGGL(knn_select_kernel, flags ? dim3((N + 31) / 32, B) : dim3((N + nw - 1) / nw, B), dim3(flags ? 256 : 64 * nw),
+                       (size_t)regions * (Mpad + 2 * lcap) * 4, st, x, N, y, M, B, D, k, drop, idx, dist, Mpad, lcap, flags, flags ? regions : 0);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
 fx3d_status launch_knn(const float *x, int N, const float *y, int M, int B, int D, int k, int drop,
                        int32_t *idx, float *dist, hipStream_t st, void *pre_ws = nullptr, int xdiv = 1) {
     ProfileScope prof("knn", st);
-    const int kk = k + drop;
-    const bool grid_y = knn_needs_select(M, D, kk) || (D == 3 ? !knn_f16_d3_shape_ok(M, kk) : !knn_mfma_eligible(M, D, kk));
-    FX3D_REQUIRE(!grid_y || B <= 65535, "fx3d_knn: B=%d exceeds the grid's y range for this shape", B);
-    if (knn_needs_select(M, D, kk)) {
-        int nw = knn_select_waves(M);
-        const int Mpad = (M + 255) / 256 * 256;
-        const int lcap = knn_select_list(M, kk, &nw);
-        const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_select_kernel), kSelMaxLds, "knn_select_kernel");
-        if (arc != FX3D_OK) return arc;
-        hipLaunchKernelGGL(knn_select_kernel, dim3((N + nw - 1) / nw, B), dim3(64 * nw), (size_t)nw * (Mpad + 2 * lcap) * 4, st, x, N, y, M,
-                           B, D, k, drop, idx, dist, Mpad, lcap, nullptr, 0);
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
-    }
-    if (D == 3 && knn_f16_d3_shape_ok(M, kk))
-        return launch_knn_f16_d3(x, N, y, M, B, k, drop, idx, dist, st, nullptr, 0, xdiv);
-    FX3D_REQUIRE(xdiv == 1 || (D != 3 && !opt(OPT_KNN_NO_MFMA) && knn_mfma_eligible(M, D, kk)),
-                 "fx3d_knn: internal: candidate slices on a kernel without them");
-    if (D == 3) {
-        const int qpb = (kWThreads / 64) * kWQ;
-        hipLaunchKernelGGL(knn_wave_d3_kernel, dim3((N + qpb - 1) / qpb, B), dim3(kWThreads), 0, st, x, N, y, M, B, k,
-                           drop, idx, dist);
-    } else if (!opt(OPT_KNN_NO_MFMA) && knn_mfma_eligible(M, D, kk)) {
-        return launch_knn_mfma(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-    } else {
-        const int qpb = (kWThreads / 64) * kGQ;
-        hipLaunchKernelGGL(knn_wave_generic_kernel, dim3((N + qpb - 1) / qpb, B), dim3(kWThreads), knn_wave_generic_lds(D),
-                           st, x, N, y, M, B, D, k, drop, idx, dist);
+    const KnnRoute route = knn_route(M, D, k + drop);
+    FX3D_REQUIRE(!knn_route_batch_in_grid_y(route) || B <= 65535, "fx3d_knn: B=%d exceeds the grid's y range for this shape", B);
+    FX3D_REQUIRE(xdiv == 1 || knn_route_matrix_core(route), "fx3d_knn: internal: candidate slices on a kernel without them");
+    auto wave_grid = [&](int qpw) { return dim3((N + (kWThreads / 64) * qpw - 1) / ((kWThreads / 64) * qpw), B); };  // qpw queries per wave
+    switch (route) {
+        case KnnRoute::Select: return launch_knn_select(x, N, y, M, B, D, k, drop, idx, dist, nullptr, st);
+        case KnnRoute::F16D3: return knn_d3_launch(x, N, y, M, B, k, drop, idx, dist, st, nullptr, 0, xdiv);
+        case KnnRoute::Mfma: return knn_mfma_launch(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
+        case KnnRoute::WaveD3:
+            hipLaunchKernelGGL(knn_wave_d3_kernel, wave_grid(kWQ), dim3(kWThreads), 0, st, x, N, y, M, B, k, drop, idx, dist);
+            break;
+        case KnnRoute::WaveGeneric:
+            hipLaunchKernelGGL(knn_wave_generic_kernel, wave_grid(kGQ), dim3(kWThreads), knn_wave_generic_lds(D), st, x, N, y, M, B, D, k, drop, idx, dist);
+            break;
     }
     FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+// The entry points' common argument check (fn: the entry point's name for the messages).  search: x, y, idx are given (ptrs_ok)
+// and k + drop_first <= M is required; else (fx3d_knn_workspace_bytes) ptrs_ok is the output pointer and the shape alone is checked.
+fx3d_status knn_check_args(const char *fn, bool search, bool ptrs_ok, int N, int M, int B, int D, int k, int kk) {
+    FX3D_REQUIRE(ptrs_ok, "%s: null %s", fn, search ? "pointer" : "output");
+    const bool sizes_ok = N > 0 && M > 0 && B > 0 && D > 0 && k > 0;
+    FX3D_REQUIRE(sizes_ok || search, "%s: bad sizes", fn);
+    FX3D_REQUIRE(sizes_ok, "%s: bad sizes (N=%d M=%d B=%d D=%d k=%d)", fn, N, M, B, D, k);
+    FX3D_REQUIRE(!search || kk <= M, "%s: k+drop_first=%d exceeds the number of candidates M=%d", fn, kk, M);
     return FX3D_OK;
 }
 
@@ -950,14 +785,11 @@ extern "C" {
 
 fx3d_status fx3d_knn(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D,
                      int32_t k, int32_t drop_first, int32_t *idx, float *dist, fx3d_stream_t s) {
-    FX3D_REQUIRE(x && y && idx, "fx3d_knn: null pointer");
-    FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0 && k > 0, "fx3d_knn: bad sizes (N=%d M=%d B=%d D=%d k=%d)",
-                 N, M, B, D, k);
     const int drop = drop_first ? 1 : 0;
-    const int kk = k + drop;
-    FX3D_REQUIRE(kk <= M, "fx3d_knn: k+drop_first=%d exceeds the number of candidates M=%d", kk, M);
-    if (knn_needs_select(M, D, kk) && knn_select_waves(M) < 1) {
-        set_error("fx3d_knn: k+drop_first=%d > 64 (or D=%d beyond the wave kernel) is supported for M <= %d candidates, got M=%d", kk, D,
+    const fx3d_status rc = knn_check_args("fx3d_knn", true, x && y && idx, N, M, B, D, k, k + drop);
+    if (rc != FX3D_OK) return rc;
+    if (knn_route(M, D, k + drop) == KnnRoute::Select && knn_select_waves(M) < 1) {
+        set_error("fx3d_knn: k+drop_first=%d > 64 (or D=%d beyond the wave kernel) is supported for M <= %d candidates, got M=%d", k + drop, D,
                   kSelMaxLds / 4, M);
         return FX3D_ERR_UNSUPPORTED;
     }
@@ -965,9 +797,9 @@ fx3d_status fx3d_knn(const float *x, int32_t N, const float *y, int32_t M, int32
 }
 
 fx3d_status fx3d_knn_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, int32_t k, int32_t drop_first, size_t *bytes) {
-    FX3D_REQUIRE(bytes, "fx3d_knn_workspace_bytes: null output");
-    FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0 && k > 0, "fx3d_knn_workspace_bytes: bad sizes");
     const int kk = k + (drop_first ? 1 : 0);
+    const fx3d_status rc = knn_check_args("fx3d_knn_workspace_bytes", false, bytes != nullptr, N, M, B, D, k, kk);
+    if (rc != FX3D_OK) return rc;
     // (alignment of x / y is checked at the call: an ineligible call simply does not use the workspace)
     *bytes = kk <= M ? KnnScratch::plan(N, M, B, D, kk).total : 0;
     return FX3D_OK;
@@ -975,133 +807,45 @@ fx3d_status fx3d_knn_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D,
 
 fx3d_status fx3d_knn_ws(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D, int32_t k,
                         int32_t drop_first, int32_t *idx, float *dist, void *ws, size_t ws_bytes, fx3d_stream_t s) {
-    FX3D_REQUIRE(x && y && idx, "fx3d_knn_ws: null pointer");
-    FX3D_REQUIRE(N > 0 && M > 0 && B > 0 && D > 0 && k > 0, "fx3d_knn_ws: bad sizes (N=%d M=%d B=%d D=%d k=%d)", N, M, B, D, k);
     const int drop = drop_first ? 1 : 0;
     const int kk = k + drop;
-    FX3D_REQUIRE(kk <= M, "fx3d_knn_ws: k+drop_first=%d exceeds the number of candidates M=%d", kk, M);
+    const fx3d_status crc = knn_check_args("fx3d_knn_ws", true, x && y && idx, N, M, B, D, k, kk);
+    if (crc != FX3D_OK) return crc;
+    const hipStream_t st = as_stream(s);
     const bool ws_ok = ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0;
     const KnnScratch p = KnnScratch::plan(N, M, B, D, kk);
     if (p.S > 1 && ws_ok && ws_bytes >= p.total) {
         // candidate slices: the search on B x S virtual clouds of M / S rows (no drop: the merge drops), then the merge
         const int Ms = M / p.S;
         unsigned char *w8 = static_cast<unsigned char *>(ws);
-        int32_t *widx = reinterpret_cast<int32_t *>(w8 + p.pre_bytes);
-        float *wdist = reinterpret_cast<float *>(w8 + p.pre_bytes + p.list_bytes);
-        unsigned char *flags = p.verify ? w8 + p.pre_bytes + 2 * p.list_bytes : nullptr;
+        int32_t *widx = reinterpret_cast<int32_t *>(w8 + p.list_off);
+        float *wdist = reinterpret_cast<float *>(w8 + p.list_off + p.list_bytes);
+        unsigned char *flags = p.verify ? w8 + p.flag_off : nullptr;
         const float *ys = y;  // the clouds the slices are cut from
         if (p.verify) {       // 32 per slice must hold the cloud's kk nearest: interleaved slices (samples of the whole cloud)
-            float *yc = reinterpret_cast<float *>(w8 + p.pre_bytes + 2 * p.list_bytes + p.flag_bytes);
+            float *yc = reinterpret_cast<float *>(w8 + p.copy_off);
             const int vec4 = D % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
             const long long items = (long long)B * M * (vec4 ? D / 4 : D);
             const long long nb = (items + 255) / 256;
-            hipLaunchKernelGGL(knn_interleave_kernel, dim3((unsigned int)(nb < 8192 ? nb : 8192)), dim3(256), 0, as_stream(s), y, M, D, B, p.S, yc, vec4);
+            hipLaunchKernelGGL(knn_interleave_kernel, dim3((unsigned int)(nb < 8192 ? nb : 8192)), dim3(256), 0, st, y, M, D, B, p.S, yc, vec4);
             FX3D_LAUNCH_CHECK();
             ys = yc;
         }
-        void *pre_ws = p.pre_bytes && knn_pre_eligible(x, ys, Ms, D, p.kl) ? ws : nullptr;
-        const fx3d_status rc = launch_knn(x, N, ys, Ms, B * p.S, D, p.kl, 0, widx, wdist, as_stream(s), pre_ws, p.S);
+        void *pre_ws = p.pre_bytes && knn_mfma_pre_eligible(x, ys, Ms, D, p.kl) ? ws : nullptr;
+        const fx3d_status rc = launch_knn(x, N, ys, Ms, B * p.S, D, p.kl, 0, widx, wdist, st, pre_ws, p.S);
         if (rc != FX3D_OK) return rc;
         const int nent = p.S * p.kl;                                     // entries per query (<= 512)
         const int wpq = nent <= 64 ? 1 : (nent <= 128 ? 2 : 4), qpb = 4 / wpq;
         FX3D_REQUIRE(B <= 65535, "fx3d_knn_ws: B=%d exceeds the grid's y range for this shape", B);
         hipLaunchKernelGGL(knn_merge_slices_kernel, dim3((unsigned int)((N + qpb - 1) / qpb), (unsigned int)B), dim3(256), (size_t)qpb * nent * 8,
-                           as_stream(s), widx, wdist, N, B, p.S, Ms, p.kl, kk, k, drop, idx, dist, flags, p.verify ? 1 : 0, wpq);
+                           st, widx, wdist, N, B, p.S, Ms, p.kl, kk, k, drop, idx, dist, flags, p.verify ? 1 : 0, wpq);
         FX3D_LAUNCH_CHECK();
-        if (p.verify) {  // the flagged queries (a slice held more than 32 of their kk nearest) again, on all M candidates
-            int nw = knn_select_waves(M);
-            const int Mpad = (M + 255) / 256 * 256;
-            const int lcap = knn_select_list(M, kk, &nw);
-            const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_select_kernel), kSelMaxLds, "knn_select_kernel");
-            if (arc != FX3D_OK) return arc;
-            FX3D_REQUIRE(B <= 65535, "fx3d_knn_ws: B=%d exceeds the grid's y range for this shape", B);
-            const int regions = nw >= 4 ? 4 : 1;  // key arrays in LDS: one per wave when they fit (many flagged queries), else one
-            hipLaunchKernelGGL(knn_select_kernel, dim3((N + 31) / 32, B), dim3(256), (size_t)regions * (Mpad + 2 * lcap) * 4, as_stream(s), x, N,
-                               y, M, B, D, k, drop, idx, dist, Mpad, lcap, flags, regions);
-            FX3D_LAUNCH_CHECK();
-        }
-        return FX3D_OK;
+        // the flagged queries (a slice held more than 32 of their kk nearest) again, on all M candidates
+        return p.verify ? launch_knn_select(x, N, y, M, B, D, k, drop, idx, dist, flags, st) : FX3D_OK;
     }
-    const bool pre = ws_ok && knn_pre_eligible(x, y, M, D, kk) && ws_bytes >= knn_pre_bytes(M, B, D);
+    const bool pre = ws_ok && knn_mfma_pre_eligible(x, y, M, D, kk) && ws_bytes >= knn_mfma_pre_bytes(M, B, D);
     if (!pre) return fx3d_knn(x, N, y, M, B, D, k, drop_first, idx, dist, s);
-    return launch_knn(x, N, y, M, B, D, k, drop, idx, dist, as_stream(s), ws);
-}
-
-fx3d_status fx3d_knn_gather(const float *x, int32_t N, int32_t B, int32_t F, int32_t k,
-                            const int32_t *idx, float *out, fx3d_stream_t s) {
-    FX3D_REQUIRE(x && idx && out, "fx3d_knn_gather: null pointer");
-    FX3D_REQUIRE(N > 0 && B > 0 && F > 0 && k > 0, "fx3d_knn_gather: bad sizes");
-    if (F % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0) {  // 16-byte copies
-        const long long total4 = (long long)B * N * k * (F / 4);
-        long long g4 = (total4 + kThreads - 1) / kThreads;
-        if (g4 > 16384) g4 = 16384;
-        ProfileScope prof4("knn_gather", as_stream(s));
-        if ((size_t)F * k * N * B * 4 > kStreamingStoreBytes)
-            hipLaunchKernelGGL(knn_gather4_kernel<true>, dim3((unsigned)g4), dim3(kThreads), 0, as_stream(s), x, N, B, F / 4, k, idx, out);
-        else
-            hipLaunchKernelGGL(knn_gather4_kernel<false>, dim3((unsigned)g4), dim3(kThreads), 0, as_stream(s), x, N, B, F / 4, k, idx, out);
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
-    }
-    const long long total = (long long)B * N * k * F;
-    long long g = (total + kThreads - 1) / kThreads;
-    if (g > 8192) g = 8192;
-    ProfileScope prof("knn_gather", as_stream(s));
-    hipLaunchKernelGGL(knn_gather_kernel, dim3((unsigned)g), dim3(kThreads), 0, as_stream(s), x, N, B, F, k, idx, out);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-
-fx3d_status fx3d_edge_features(const float *x, int32_t N, int32_t B, int32_t F, int32_t k, const int32_t *idx,
-                               int32_t layout, float *out, fx3d_stream_t s) {
-    FX3D_REQUIRE(x && idx && out, "fx3d_edge_features: null pointer");
-    FX3D_REQUIRE(N > 0 && B > 0 && F > 0 && k > 0, "fx3d_edge_features: bad sizes");
-    FX3D_REQUIRE(layout == 0 || layout == 1, "fx3d_edge_features: layout must be 0 (2F,K,N,B) or 1 (K*N,2F,B)");
-    ProfileScope prof("edge_features", as_stream(s));
-    if (layout == 0) {
-        const long long total = (long long)B * N * k * 2 * F;
-        long long g = (total + kThreads - 1) / kThreads;
-        if (g > 16384) g = 16384;
-        hipLaunchKernelGGL(edge_features_cat_kernel, dim3((unsigned)g), dim3(kThreads), 0, as_stream(s), x, N, B, F, k,
-                           idx, out);
-    } else {
-        const long long KN = (long long)k * N;
-        dim3 grid((unsigned)((KN + kThreads - 1) / kThreads), B);
-        const bool al16 = (((uintptr_t)x | (uintptr_t)out | (uintptr_t)idx) & 15) == 0;
-        if (F % 4 == 0 && KN % 4 == 0 && al16) {
-            // the feature loop split over blockIdx.z until the grid holds ~16 blocks per CU
-            const long long gx = (KN / 4 + kThreads - 1) / kThreads;
-            int fper = F;
-            while (fper > 4 && gx * B * ((F + fper - 1) / fper) < 16ll * device_cus()) fper = (fper / 2 + 3) / 4 * 4;
-            const unsigned gz = (unsigned)((F + fper - 1) / fper);
-            const bool nt = (size_t)2 * F * KN * B * 4 > kStreamingStoreBytes;  // (smaller tensors may be read back from the caches)
-            if (nt)
-                hipLaunchKernelGGL(edge_features_mlp4_kernel<true>, dim3((unsigned)gx, B, gz), dim3(kThreads), 0, as_stream(s), x, N, B, F, k, idx, out, fper);
-            else
-                hipLaunchKernelGGL(edge_features_mlp4_kernel<false>, dim3((unsigned)gx, B, gz), dim3(kThreads), 0, as_stream(s), x, N, B, F, k, idx, out, fper);
-        }
-        else if (F % 4 == 0 && ((uintptr_t)x & 15) == 0)
-            hipLaunchKernelGGL(edge_features_mlp_kernel<true>, grid, dim3(kThreads), 0, as_stream(s), x, N, B, F, k, idx, out);
-        else
-            hipLaunchKernelGGL(edge_features_mlp_kernel<false>, grid, dim3(kThreads), 0, as_stream(s), x, N, B, F, k, idx, out);
-    }
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-fx3d_status fx3d_edge_features_bwd(const float *gout, int32_t N, int32_t B, int32_t F, int32_t k, int32_t layout,
-                                   float *gx, fx3d_stream_t s) {
-    FX3D_REQUIRE(gout && gx, "fx3d_edge_features_bwd: null pointer");
-    FX3D_REQUIRE(N > 0 && B > 0 && F > 0 && k > 0, "fx3d_edge_features_bwd: bad sizes");
-    FX3D_REQUIRE(layout == 0 || layout == 1, "fx3d_edge_features_bwd: bad layout");
-    const long long total = (long long)B * N * F;
-    long long g = (total + kThreads - 1) / kThreads;
-    if (g > 16384) g = 16384;
-    hipLaunchKernelGGL(edge_features_bwd_kernel, dim3((unsigned)g), dim3(kThreads), 0, as_stream(s), gout, N, B, F, k,
-                       layout, gx);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
+    return launch_knn(x, N, y, M, B, D, k, drop, idx, dist, st, ws);
 }
 
 fx3d_status fx3d_edgeconv_graph(const float *x, int32_t N, int32_t B, int32_t F, int32_t k, int32_t layout,
@@ -1109,11 +853,10 @@ fx3d_status fx3d_edgeconv_graph(const float *x, int32_t N, int32_t B, int32_t F,
     FX3D_REQUIRE(idx, "fx3d_edgeconv_graph: idx (k,N,B) is required (it is also the adjoint's side input)");
     FX3D_REQUIRE(x && out && N > 0 && B > 0 && F > 0 && k > 0, "fx3d_edgeconv_graph: bad argument");
     FX3D_REQUIRE(layout == 0 || layout == 1, "fx3d_edgeconv_graph: layout must be 0 (2F,K,N,B) or 1 (K*N,2F,B)");
-    if (F == 3 && k + 1 <= N && knn_f16_d3_shape_ok(N, k + 1) &&
-        !opt(OPT_EDGECONV_UNFUSED)) {
+    if (F == 3 && k + 1 <= N && knn_route(N, 3, k + 1) == KnnRoute::F16D3 && !opt(OPT_EDGECONV_UNFUSED)) {
         // first EdgeConv (coordinates): neighbour search and features in ONE kernel
         ProfileScope prof("edgeconv_graph", as_stream(s));
-        return launch_knn_f16_d3(x, N, x, N, B, k, 1, idx, nullptr, as_stream(s), out, layout);
+        return knn_d3_launch(x, N, x, N, B, k, 1, idx, nullptr, as_stream(s), out, layout, 1);
     }
     fx3d_status rc = fx3d_knn(x, N, x, N, B, F, k, 1, idx, nullptr, s);
     if (rc != FX3D_OK) return rc;

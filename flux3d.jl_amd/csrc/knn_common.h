@@ -1,7 +1,8 @@
-// Shared by the translation units of the k-NN kernels (knn.hip: wave / selection / gather / EdgeConv-feature kernels, the
-// dispatch and the C entry points; knn_d3.hip: knn_f16_d3_kernel; knn_mfma.hip: the feature-space pre-pass + knn_mfma_kernel):
-// constants, the wave-level sorting / selection helpers, knn_exact_bruteforce, knn_rank_ties / knn_rank_ties4, knn_tau_8of16, and the
-// declarations of what the units call across.  (File-local helpers live in an anonymous namespace: every unit has its copy.)
+// Shared by the translation units of the k-NN kernels (knn.hip: wave / selection / slice kernels, the route, the scratch plan and
+// the C entry points; knn_d3.hip: knn_f16_d3_kernel and its launcher; knn_mfma.hip: the feature-space pre-pass, knn_mfma_kernel and
+// their launcher): what at least two of them use -- constants, the wave-level sorting / selection helpers, knn_exact_bruteforce,
+// knn_rank_ties / knn_rank_ties4, k3_sort_regs, knn_tau_8of16, the shape predicates -- and the declarations of what the units call
+// across.  A helper of one unit lives in that unit.  (File-local helpers live in an anonymous namespace: every unit has its copy.)
 #pragma once
 #include <cmath>
 #include <cstdlib>
@@ -31,7 +32,6 @@ __device__ unsigned long long g_kprobe[4096 * 32];
 
 namespace {
 
-constexpr int kThreads = 256;
 
 // ------------------------------------------------------------------------------------------------
 // knn_wave_d3_kernel: one WAVE per query (D = 3).  The 64 lanes split the candidates (16 per lane and
@@ -312,84 +312,6 @@ __device__ __forceinline__ void knn_exact_bruteforce(const float *__restrict__ q
     bd_out = key_dist(bd);
 }
 
-// LDS image of a chunk: rows of PPR = DP/4 16-byte pieces, no padding; piece c of row r sits at position
-// (c + r) mod PPR of its row.  The rotation makes the consumers' b128 operand fetches (32 consecutive rows, one
-// column) conflict-free, and it is applied on the SOURCE side of the direct-to-LDS loads
-// (global_load_lds_dwordx4 writes lane-linear: wave-uniform base + lane*16), so staging costs one
-// instruction per KiB and no VGPR round trip -- the producers share their SIMD's issue slots with the
-// consumers' MFMAs, every VALU instruction they do not execute is matrix-core time.
-// knn_gather_kernel with 16-byte elements (F4 = F/4 float4 per row)
-// NT: streaming (non-temporal) stores for tensors beyond the caches (round 4: the F = 64 feature build gained 28 % from them).
-// Only for outputs larger than 3/4 of the 256 MB Infinity Cache: a consumer kernel may still find a smaller tensor there (the
-// 168 MB gather of C4' gains 3 % from streaming stores -- not worth taking that away from its reader).
-template <int DK>
-__device__ __forceinline__ int knn_piece_off(int row, int c) {  // float offset of piece c of row `row`
-    constexpr int PPR = DK * 8;
-    return (row * PPR + ((c + row) & (PPR - 1))) * 4;
-}
-
-// producer wave pw stages rows [pw*RW, (pw+1)*RW) of the chunk [j0, j0+cn) and their norms
-template <int DK>
-__device__ __forceinline__ void knn_stage_chunk(const float *__restrict__ yb, int D, int j0, int cn, int CH, float *img,
-                                                float *cnorm, unsigned int *cmax, bool want_cmax, bool do_norms,
-                                                bool vec4, int pw, int lane) {
-    constexpr int PPR = DK * 8;
-    const int RW = CH / kMWaves;          // rows per producer wave (CH is a multiple of 64)
-    const int row_lo = pw * RW;
-    const int rq = D / 4;
-    if (vec4) {
-        const int ninstr = RW * PPR / 64;
-        for (int i = 0; i < ninstr; ++i) {
-            const int S0 = row_lo * PPR + i * 64;  // first 16-byte slot of this wave-instruction
-            const int S = S0 + lane;
-            const int row = S / PPR, pos = S & (PPR - 1);
-            const int c = (pos - row) & (PPR - 1);
-            if (row < cn && c < rq)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)(yb + (size_t)(j0 + row) * D + 4 * c),
-                    (__attribute__((address_space(3))) void *)(img + (size_t)S0 * 4), 16, 0, 0);
-        }
-        __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's pieces have landed
-    } else {
-        for (int e = lane; e < RW * D; e += 64) {
-            const int row = row_lo + e / D, d = e % D;
-            if (row < cn) img[knn_piece_off<DK>(row, d >> 2) + (d & 3)] = yb[(size_t)(j0 + row) * D + d];
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (!do_norms) return;  // phase B with the norms of phase A kept in LDS
-    // norms of this wave's rows (padding columns hold zeros); rows beyond the chunk get +inf: F = +inf
-    float wmax = 0.0f;
-    bool wnan = false;
-    for (int r0 = 0; r0 < RW; r0 += 64) {
-        const int row = row_lo + r0 + lane;
-        if (r0 + lane < RW) {
-            float t = INFINITY;
-            if (row < cn) {
-                t = 0.0f;
-#pragma unroll
-                for (int c = 0; c < PPR; ++c) {
-                    const float4 v = *reinterpret_cast<const float4 *>(img + knn_piece_off<DK>(row, c));
-                    t = __builtin_fmaf(v.x, v.x, t);
-                    t = __builtin_fmaf(v.y, v.y, t);
-                    t = __builtin_fmaf(v.z, v.z, t);
-                    t = __builtin_fmaf(v.w, v.w, t);
-                }
-                wnan |= (t != t);
-                wmax = fmaxf(wmax, t);
-            }
-            cnorm[row] = t;
-        }
-    }
-    if (want_cmax) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, m, 64));
-        const bool anynan = __ballot(wnan) != 0;
-        if (lane == 0) atomicMax(cmax, anynan ? 0x7fc00000u : __builtin_bit_cast(unsigned int, wmax));  // NaN > +inf
-    }
-}
-
 // Wave-cooperative ranking of ONE query's n survivors on the full (distance bits, index) keys: lane e ranks key e against all n (LDS
 // broadcast reads; qd / qj are padded with sentinels up to a multiple of four); keys are unique, so the ranks below kk are a
 // permutation and slots[0, kk) is the sorted answer.  The form for the rare tied query of ordinary data: well under a microsecond for
@@ -449,71 +371,12 @@ __device__ __forceinline__ void knn_rank_ties4(const unsigned int *qd, const int
 
 
 typedef _Float16 kh8 __attribute__((ext_vector_type(8)));
-// Geometry of one instantiation: G query groups (32 queries each) per block, two waves per group (each taking every other pair of
-// candidate tiles: two waves per SIMD overlap each other's LDS / shuffle latencies), CAP rows per lane list (CAP - 1 usable + the
-// scratch head; a lane sees half the tiles), KCAP keys per query (the four lanes' survivors; three sentinels follow them inside the
-// stride KS: 32 queries x b128 reads without bank conflicts), KKMAX = the largest k + drop (SS - 1 rank slots per query).
-template <int G_, int CAP_, int KCAP_, int KKMAX_>
-struct K3Geom {
-    static constexpr int G = G_, W = 2 * G_, T = W * 64, CAP = CAP_, KCAP = KCAP_, KS = KCAP_ + 4, KKMAX = KKMAX_, SS = KKMAX_ + 1;
-    static_assert((size_t)W * 32 * 33 * 4 <= (size_t)W * CAP * 64 * 4, "the tau exchange aliases the lists");
-    static_assert((size_t)G * 32 * SS * 8 + W * 128 * 4 <= (size_t)W * CAP * 64 * 4, "slots + scratch alias the lists");
-    static_assert(CAP <= 64 && KKMAX <= 64 && KKMAX % 16 == 0 && KCAP % 4 == 0, "one list word per lane in the medium path; 16-byte key rows");
-};
-using K3Base = K3Geom<4, 24, 64, 32>;    // k + drop <= 32: C4 gets 256 blocks of 128 queries, one per CU
-using K3Wide = K3Geom<2, 40, 128, 64>;   // 32 < k + drop <= 64: twice the keys and longer lists per query, half the queries per block
-// ... and a compact one (round 3) for 32 < k + drop <= 48: an allocation below half a CU's LDS, so that TWO blocks (eight waves) share a
-// CU as in the base geometry -- the wide geometry's four waves leave half of every CU's issue slots empty (C4's shape, k = 40:
-// 52.4 -> 34.8 us); the LDS image is held to the size of the key arrays (1472 candidates; larger clouds pass through it in
-// chunks), the raw coordinates stay in L2.  The same
-// form of the base geometry (K3Geom<2, 24, 64, 32>, two blocks per CU) measured equal to it (k = 20: 24.8 vs 25.0 us): not kept.
-using K3Mid = K3Geom<2, 28, 88, 48>;
-// (48 < k + drop <= 64 as K3Geom<1, 35, 120, 64>, 32 queries per block and three blocks per CU, measured equal to the wide geometry
-//  up to k = 56 -- four times the prologues -- and worse beyond, where 120 keys overflow: not kept)
-// dynamic LDS limit of a compact block: NB of them (+ ~0.7 KiB static each) fit in a CU's 160 KiB
-constexpr size_t k3_compact_lds(int nb) { return (size_t)160 * 1024 / nb - 1024; }
-constexpr int kTChunk = 3072;         // candidates per LDS image (32 B each): image + lists + counters <= 152 KiB
-constexpr int kTRawMax = 2048;        // clouds up to this size also keep their raw coordinates in LDS
-constexpr int kK3FarCap = 16;         // far candidates (robust range, as in nn1_f16_kernel) kept on the exact side list
 
 
 __device__ __forceinline__ float vmax_f32(float a, float b) {
     float r;
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-}
-__device__ __forceinline__ void k3_split2h(float v, _Float16 &h, _Float16 &l) {
-    h = (_Float16)v;
-    l = (_Float16)(v - (float)h);
-}
-// fp16 image pieces of one candidate c~ = s (c - mu): same K-slot table as nn1_f16_kernel
-constexpr float kK3BetaC = 0x1.2p-18f;  // candidate's share of the filter error, folded into its norm (chamfer.hip kBetaC, + the 17th term)
-__device__ __forceinline__ void k3_make_pieces(float cx, float cy, float cz, kh8 &p0, kh8 &p1) {
-    _Float16 hx, lx, hy, ly, hz, lz, n1, n2, n3;
-    k3_split2h(cx, hx, lx); k3_split2h(cy, hy, ly); k3_split2h(cz, hz, lz);
-    const float n0 = ((cx * cx) + (cy * cy)) + (cz * cz);
-    const float n = n0 + kK3BetaC * n0;
-    n1 = (_Float16)n;
-    const float r1 = n - (float)n1;
-    n2 = (_Float16)r1;
-    n3 = (_Float16)(r1 - (float)n2);
-    p0 = kh8{hx, hx, lx, hy, hy, ly, hz, hz};
-    p1 = kh8{lz, n1, n2, n3, lx, ly, lz, (_Float16)1.0f};  // slot 15: times the query's -threshold in phase B
-}
-// ... of a candidate that may lie beyond the robust range (|c~|_inf >= 2^7): zero pieces, norm +inf (its filter value is
-// +inf for every query), recorded once (first staging of its chunk) on the block's side list
-__device__ __forceinline__ void k3_pieces_far(float sx, float sy, float sz, bool has_far, bool record, int index, int *nfar, int *farlist,
-                                              kh8 &p0, kh8 &p1) {
-    if (!has_far) { k3_make_pieces(sx, sy, sz, p0, p1); return; }
-    const bool far = !(fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz)) < 128.0f);
-    k3_make_pieces(far ? 0.f : sx, far ? 0.f : sy, far ? 0.f : sz, p0, p1);
-    if (far) {
-        p1[1] = (_Float16)INFINITY;
-        if (record) {
-            const int f = atomicAdd(nfar, 1);
-            if (f < kK3FarCap) farlist[f] = index;
-        }
-    }
 }
 // ascending sort of NV registers (compile-time indices only): Batcher's odd-even merge sort, 191 compare-exchanges
 // for 32 values (the bitonic network needs 240)
@@ -652,10 +515,11 @@ inline bool knn_mfma_eligible(int M, int D, int kk) { return D >= 4 && D <= 128 
 }  // namespace
 
 namespace fx3d {
-// knn_d3.hip
+// knn_d3.hip: the D = 3 matrix-core kernel (geometry by k + drop; feat != nullptr: EdgeConv's features by the same kernel)
 fx3d_status knn_d3_launch(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx, float *dist, hipStream_t st,
                           float *feat, int layout, int xdiv);
-// knn_mfma.hip
+// knn_mfma.hip: the feature-space matrix-core kernel (pre_ws != nullptr: behind the per-cloud pre-pass, whose shapes, eligibility
+// and scratch bytes are the three functions below)
 fx3d_status knn_mfma_launch(const float *x, int N, const float *y, int M, int B, int D, int k, int drop, int32_t *idx, float *dist,
                             hipStream_t st, void *pre_ws, int xdiv);
 bool knn_mfma_pre_shape_ok(int M, int D, int kk);

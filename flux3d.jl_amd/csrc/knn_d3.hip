@@ -3,6 +3,70 @@
 
 namespace {
 
+// Geometry of one instantiation: G query groups (32 queries each) per block, two waves per group (each taking every other pair of
+// candidate tiles: two waves per SIMD overlap each other's LDS / shuffle latencies), CAP rows per lane list (CAP - 1 usable + the
+// scratch head; a lane sees half the tiles), KCAP keys per query (the four lanes' survivors; three sentinels follow them inside the
+// stride KS: 32 queries x b128 reads without bank conflicts), KKMAX = the largest k + drop (SS - 1 rank slots per query).
+template <int G_, int CAP_, int KCAP_, int KKMAX_>
+struct K3Geom {
+    static constexpr int G = G_, W = 2 * G_, T = W * 64, CAP = CAP_, KCAP = KCAP_, KS = KCAP_ + 4, KKMAX = KKMAX_, SS = KKMAX_ + 1;
+    // the fixed regions of the dynamic LDS behind the image (bytes): lane lists (also the tau exchange and, later, the slots) | per query: 4 part
+    // counts, overflow, n, fast, below
+    static constexpr int LIST_BYTES = W * CAP * 64 * 4, CTR_BYTES = G * 32 * 8 * 4;
+    static_assert((size_t)W * 32 * 33 * 4 <= (size_t)W * CAP * 64 * 4, "the tau exchange aliases the lists");
+    static_assert((size_t)G * 32 * SS * 8 + W * 128 * 4 <= (size_t)W * CAP * 64 * 4, "slots + scratch alias the lists");
+    static_assert(CAP <= 64 && KKMAX <= 64 && KKMAX % 16 == 0 && KCAP % 4 == 0, "one list word per lane in the medium path; 16-byte key rows");
+};
+using K3Base = K3Geom<4, 24, 64, 32>;    // k + drop <= 32: C4 gets 256 blocks of 128 queries, one per CU
+using K3Wide = K3Geom<2, 40, 128, 64>;   // 32 < k + drop <= 64: twice the keys and longer lists per query, half the queries per block
+// ... and a compact one (round 3) for 32 < k + drop <= 48: an allocation below half a CU's LDS, so that TWO blocks (eight waves) share a
+// CU as in the base geometry -- the wide geometry's four waves leave half of every CU's issue slots empty (C4's shape, k = 40:
+// 52.4 -> 34.8 us); the LDS image is held to the size of the key arrays (1472 candidates; larger clouds pass through it in
+// chunks), the raw coordinates stay in L2.  The same
+// form of the base geometry (K3Geom<2, 24, 64, 32>, two blocks per CU) measured equal to it (k = 20: 24.8 vs 25.0 us): not kept.
+using K3Mid = K3Geom<2, 28, 88, 48>;
+// (48 < k + drop <= 64 as K3Geom<1, 35, 120, 64>, 32 queries per block and three blocks per CU, measured equal to the wide geometry
+//  up to k = 56 -- four times the prologues -- and worse beyond, where 120 keys overflow: not kept)
+// dynamic LDS limit of a compact block: NB of them (+ ~0.7 KiB static each) fit in a CU's 160 KiB
+constexpr size_t k3_compact_lds(int nb) { return (size_t)160 * 1024 / nb - 1024; }
+constexpr int kTChunk = 3072;         // candidates per LDS image (32 B each): image + lists + counters <= 152 KiB
+constexpr int kTRawMax = 2048;        // clouds up to this size also keep their raw coordinates in LDS
+constexpr int kK3FarCap = 16;         // far candidates (robust range, as in nn1_f16_kernel) kept on the exact side list
+
+__device__ __forceinline__ void k3_split2h(float v, _Float16 &h, _Float16 &l) {
+    h = (_Float16)v;
+    l = (_Float16)(v - (float)h);
+}
+// fp16 image pieces of one candidate c~ = s (c - mu): same K-slot table as nn1_f16_kernel
+constexpr float kK3BetaC = 0x1.2p-18f;  // candidate's share of the filter error, folded into its norm (chamfer.hip kBetaC, + the 17th term)
+__device__ __forceinline__ void k3_make_pieces(float cx, float cy, float cz, kh8 &p0, kh8 &p1) {
+    _Float16 hx, lx, hy, ly, hz, lz, n1, n2, n3;
+    k3_split2h(cx, hx, lx); k3_split2h(cy, hy, ly); k3_split2h(cz, hz, lz);
+    const float n0 = ((cx * cx) + (cy * cy)) + (cz * cz);
+    const float n = n0 + kK3BetaC * n0;
+    n1 = (_Float16)n;
+    const float r1 = n - (float)n1;
+    n2 = (_Float16)r1;
+    n3 = (_Float16)(r1 - (float)n2);
+    p0 = kh8{hx, hx, lx, hy, hy, ly, hz, hz};
+    p1 = kh8{lz, n1, n2, n3, lx, ly, lz, (_Float16)1.0f};  // slot 15: times the query's -threshold in phase B
+}
+// ... of a candidate that may lie beyond the robust range (|c~|_inf >= 2^7): zero pieces, norm +inf (its filter value is
+// +inf for every query), recorded once (first staging of its chunk) on the block's side list
+__device__ __forceinline__ void k3_pieces_far(float sx, float sy, float sz, bool has_far, bool record, int index, int *nfar, int *farlist,
+                                              kh8 &p0, kh8 &p1) {
+    if (!has_far) { k3_make_pieces(sx, sy, sz, p0, p1); return; }
+    const bool far = !(fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz)) < 128.0f);
+    k3_make_pieces(far ? 0.f : sx, far ? 0.f : sy, far ? 0.f : sz, p0, p1);
+    if (far) {
+        p1[1] = (_Float16)INFINITY;
+        if (record) {
+            const int f = atomicAdd(nfar, 1);
+            if (f < kK3FarCap) farlist[f] = index;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // knn_f16_d3_kernel: kNN for D = 3 (DGCNN's first EdgeConv, BASELINE config 4) with the chamfer kernel's
 // fp16-split filter (chamfer.hip, nn1_f16_kernel: t = |c~|^2 + qm~ . c~ on ONE v_mfma_f32_32x32x16_f16 per
@@ -54,8 +118,8 @@ __global__ __launch_bounds__(C::T) void knn_f16_d3_kernel(const float *__restric
     __shared__ int nfar;                    // candidates of the cloud beyond the robust range ...
     __shared__ int farlist[kK3FarCap];      // ... their indices: outside the filter, every query evaluates them exactly
     kh8 *imgp = reinterpret_cast<kh8 *>(k3sm);  // piece (blk, half, row) at (blk*2 + half)*32 + row
-    constexpr int kListBytes = C::W * C::CAP * 64 * 4;      // lane lists; also the tau exchange and, later, the slots
-    constexpr int kCtrInts = C::G * 32 * 8;               // per query: 4 part counts, overflow, n, fast, below
+    constexpr int kListBytes = C::LIST_BYTES;
+    constexpr int kCtrInts = C::CTR_BYTES / 4;
     int *lists_all = reinterpret_cast<int *>(k3sm + img_bytes);                                  // [C::W][C::CAP][64]
     int *ctr = reinterpret_cast<int *>(k3sm + img_bytes + kListBytes);                           // [C::G*32][8]
     const float4 *rawc = reinterpret_cast<const float4 *>(k3sm + img_bytes + kListBytes + kCtrInts * 4);  // [M] when raw_ok
@@ -700,59 +764,70 @@ __global__ __launch_bounds__(C::T) void knn_f16_d3_kernel(const float *__restric
     KNN_PROBE_MARK(11);
 }
 
-template <class C, int COMPACT = 0>  // COMPACT = blocks per CU the allocation is held to (0: one block, the whole CU)
-fx3d_status launch_knn_f16_d3_geom(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx,
-                                   float *dist, hipStream_t st, float *feat, int layout, int xdiv) {
-    int CH = (M + 63) / 64 * 64;
-    if (CH > kTChunk) CH = kTChunk;
-    const size_t keys = (size_t)C::G * 32 * C::KS * 8;  // distance bits + indices
-    // (COMPACT: the LDS image no larger than the key arrays -- larger clouds go through it in several chunks)
-    if (COMPACT && (size_t)CH * 32 > keys) CH = (int)(keys / 32 / 64 * 64);
-    size_t img = (size_t)CH * 32;
-    if (img < keys) img = keys;
-    const size_t fixed = (size_t)C::W * C::CAP * 64 * 4 + (size_t)C::G * 32 * 8 * 4;  // lists (exchange, slots) + counters
-    // COMPACT: the whole allocation stays below half a CU's LDS (two blocks per CU); the optional parts only if they fit under that
-    const size_t raw_limit = COMPACT ? k3_compact_lds(COMPACT ? COMPACT : 1) : 152 * 1024, all_limit = COMPACT ? k3_compact_lds(COMPACT ? COMPACT : 1) : 156 * 1024;
-    const int raw_ok = M <= kTRawMax && img + fixed + (size_t)M * 16 <= raw_limit;
-    size_t lds = img + fixed + (raw_ok ? (size_t)M * 16 : 0);
-    // medium path scratch (id list + merge lists per wave), when it fits next to everything else
-    int med_cap = 0, med_off = 0;
-    for (int cap = 512; cap >= 128; cap >>= 1)
-        if (lds + (size_t)C::W * (cap + 128) * 4 <= all_limit) {
-            med_cap = cap; med_off = (int)lds; lds += (size_t)C::W * (cap + 128) * 4;
-            break;
-        }
-    const fx3d_status arc = feat ? ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_f16_d3_kernel<true, C>), 156 * 1024, "knn_f16_d3_kernel<feat>")
-                                 : ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_f16_d3_kernel<false, C>), 156 * 1024, "knn_f16_d3_kernel");
-    if (arc != FX3D_OK) return arc;
-    const int nbx = (N + C::G * 32 - 1) / (C::G * 32);
-    const int bpad = B >= 8 ? (B + 7) / 8 * 8 : B;
-    if (feat)
-        hipLaunchKernelGGL((knn_f16_d3_kernel<true, C>), dim3(nbx * bpad), dim3(C::T), lds, st, x, N, y, M, B, k, drop, idx, dist,
-                           CH, (int)img, raw_ok, feat, layout, med_cap, med_off, xdiv);
-    else
-        hipLaunchKernelGGL((knn_f16_d3_kernel<false, C>), dim3(nbx * bpad), dim3(C::T), lds, st, x, N, y, M, B, k, drop, idx, dist,
-                           CH, (int)img, raw_ok, feat, layout, med_cap, med_off, xdiv);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-fx3d_status launch_knn_f16_d3(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx,
-                              float *dist, hipStream_t st, float *feat = nullptr, int layout = 0, int xdiv = 1) {
-    const bool compact = true;
-    if (k + drop <= 32) return launch_knn_f16_d3_geom<K3Base>(x, N, y, M, B, k, drop, idx, dist, st, feat, layout, xdiv);
-    // (measured, tools/knn_compact_ab.py: 1.3-1.6 x over the wide geometry at M = 1600 ... 8192 too -- several image chunks --, except
-    //  where many queries overflow the 88 keys and fall to the exact merge over a large cloud: k + drop > 44 with M > 4096)
-    if (k + drop <= K3Mid::KKMAX && compact && (k + drop <= 44 || M <= 4096))
-        return launch_knn_f16_d3_geom<K3Mid, 2>(x, N, y, M, B, k, drop, idx, dist, st, feat, layout, xdiv);
-    return launch_knn_f16_d3_geom<K3Wide>(x, N, y, M, B, k, drop, idx, dist, st, feat, layout, xdiv);
+// ---- host: geometry choice, LDS plan, launch ---------------------------------------------------------------------------------
+// what the plan and the launch need of a K3Geom, as values (compact = blocks per CU the allocation is held to; 0: one block, the whole
+// CU; kernel[FEAT])
+using K3Kernel = void (*)(const float *, int, const float *, int, int, int, int, int32_t *, float *, int, int, int, float *, int, int, int, int);
+struct K3Launch {
+    int G, T, KS, compact;
+    size_t fixed;  // lists + counters
+    K3Kernel kernel[2];
+};
+template <class C>
+K3Launch k3_launch(int compact) {
+    return {C::G, C::T, C::KS, compact, (size_t)C::LIST_BYTES + C::CTR_BYTES, {knn_f16_d3_kernel<false, C>, knn_f16_d3_kernel<true, C>}};
 }
 
+// The dynamic LDS of a block, in the order of the kernel's carve-up (knn_f16_d3_kernel: k3sm):
+//   [0, img) image chunk, later the key arrays | lists (LIST_BYTES) | counters (CTR_BYTES) | raw coordinates [M] (raw_ok) | medium path (med_off)
+struct K3Plan {
+    int CH, img, raw_ok, med_cap, med_off;
+    size_t lds;
+};
+K3Plan knn_d3_plan(const K3Launch &g, int M) {
+    K3Plan p{};
+    p.CH = (M + 63) / 64 * 64;
+    if (p.CH > kTChunk) p.CH = kTChunk;
+    const size_t keys = (size_t)g.G * 32 * g.KS * 8;  // distance bits + indices
+    // (compact: the LDS image no larger than the key arrays -- larger clouds go through it in several chunks)
+    if (g.compact && (size_t)p.CH * 32 > keys) p.CH = (int)(keys / 32 / 64 * 64);
+    size_t img = (size_t)p.CH * 32;
+    if (img < keys) img = keys;
+    p.img = (int)img;
+    const size_t fixed = g.fixed;
+    // compact: the whole allocation stays below half a CU's LDS (two blocks per CU); the optional parts only if they fit under that
+    const size_t raw_limit = g.compact ? k3_compact_lds(g.compact) : 152 * 1024, all_limit = g.compact ? k3_compact_lds(g.compact) : 156 * 1024;
+    p.raw_ok = M <= kTRawMax && img + fixed + (size_t)M * 16 <= raw_limit;
+    p.lds = img + fixed + (p.raw_ok ? (size_t)M * 16 : 0);
+    // medium path scratch (id list + merge lists per wave), when it fits next to everything else
+    const size_t W = 2 * (size_t)g.G;
+    for (int cap = 512; cap >= 128; cap >>= 1)
+        if (p.lds + W * (cap + 128) * 4 <= all_limit) {
+            p.med_cap = cap; p.med_off = (int)p.lds; p.lds += W * (cap + 128) * 4;
+            break;
+        }
+    return p;
+}
 
 }  // namespace
 
-namespace fx3d {
-fx3d_status knn_d3_launch(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx, float *dist, hipStream_t st,
-                          float *feat, int layout, int xdiv) {
-    return launch_knn_f16_d3(x, N, y, M, B, k, drop, idx, dist, st, feat, layout, xdiv);
+fx3d_status fx3d::knn_d3_launch(const float *x, int N, const float *y, int M, int B, int k, int drop, int32_t *idx, float *dist, hipStream_t st,
+                                float *feat, int layout, int xdiv) {
+    // the geometry by k + drop.  (measured, tools/knn_compact_ab.py: the compact one is 1.3-1.6 x over the wide geometry at M = 1600 ... 8192
+    // too -- several image chunks --, except where many queries overflow the 88 keys and fall to the exact merge over a large cloud:
+    // k + drop > 44 with M > 4096)
+    const int kk = k + drop;
+    const int gi = kk <= 32 ? 0 : (kk <= K3Mid::KKMAX && (kk <= 44 || M <= 4096) ? 1 : 2);
+    static const K3Launch geoms[3] = {k3_launch<K3Base>(0), k3_launch<K3Mid>(2), k3_launch<K3Wide>(0)};
+    const K3Launch &g = geoms[gi];
+    const K3Kernel kernel = g.kernel[feat ? 1 : 0];
+    const K3Plan p = knn_d3_plan(g, M);
+    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), 156 * 1024, feat ? "knn_f16_d3_kernel<feat>" : "knn_f16_d3_kernel");
+    if (arc != FX3D_OK) return arc;
+    const int nbx = (N + g.G * 32 - 1) / (g.G * 32);
+    const int bpad = B >= 8 ? (B + 7) / 8 * 8 : B;
+    hipLaunchKernelGGL(kernel, dim3(nbx * bpad), dim3(g.T), p.lds, st, x, N, y, M, B, k, drop, idx, dist, p.CH, p.img, p.raw_ok, feat, layout,
+                       p.med_cap, p.med_off, xdiv);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
 }
-}  // namespace fx3d

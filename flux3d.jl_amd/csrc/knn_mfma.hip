@@ -177,6 +177,80 @@ __device__ __forceinline__ void knn_stage_fetch(const float *__restrict__ yb, in
     }
 }
 
+// LDS image of a chunk: rows of PPR = DP/4 16-byte pieces, no padding; piece c of row r sits at position
+// (c + r) mod PPR of its row.  The rotation makes the consumers' b128 operand fetches (32 consecutive rows, one
+// column) conflict-free, and it is applied on the SOURCE side of the direct-to-LDS loads
+// (global_load_lds_dwordx4 writes lane-linear: wave-uniform base + lane*16), so staging costs one
+// instruction per KiB and no VGPR round trip -- the producers share their SIMD's issue slots with the
+// consumers' MFMAs, every VALU instruction they do not execute is matrix-core time.
+template <int DK>
+__device__ __forceinline__ int knn_piece_off(int row, int c) {  // float offset of piece c of row `row`
+    constexpr int PPR = DK * 8;
+    return (row * PPR + ((c + row) & (PPR - 1))) * 4;
+}
+
+// producer wave pw stages rows [pw*RW, (pw+1)*RW) of the chunk [j0, j0+cn) and their norms
+template <int DK>
+__device__ __forceinline__ void knn_stage_chunk(const float *__restrict__ yb, int D, int j0, int cn, int CH, float *img,
+                                                float *cnorm, unsigned int *cmax, bool want_cmax, bool do_norms,
+                                                bool vec4, int pw, int lane) {
+    constexpr int PPR = DK * 8;
+    const int RW = CH / kMWaves;          // rows per producer wave (CH is a multiple of 64)
+    const int row_lo = pw * RW;
+    const int rq = D / 4;
+    if (vec4) {
+        const int ninstr = RW * PPR / 64;
+        for (int i = 0; i < ninstr; ++i) {
+            const int S0 = row_lo * PPR + i * 64;  // first 16-byte slot of this wave-instruction
+            const int S = S0 + lane;
+            const int row = S / PPR, pos = S & (PPR - 1);
+            const int c = (pos - row) & (PPR - 1);
+            if (row < cn && c < rq)
+                __builtin_amdgcn_global_load_lds(
+                    (const __attribute__((address_space(1))) void *)(yb + (size_t)(j0 + row) * D + 4 * c),
+                    (__attribute__((address_space(3))) void *)(img + (size_t)S0 * 4), 16, 0, 0);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's pieces have landed
+    } else {
+        for (int e = lane; e < RW * D; e += 64) {
+            const int row = row_lo + e / D, d = e % D;
+            if (row < cn) img[knn_piece_off<DK>(row, d >> 2) + (d & 3)] = yb[(size_t)(j0 + row) * D + d];
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (!do_norms) return;  // phase B with the norms of phase A kept in LDS
+    // norms of this wave's rows (padding columns hold zeros); rows beyond the chunk get +inf: F = +inf
+    float wmax = 0.0f;
+    bool wnan = false;
+    for (int r0 = 0; r0 < RW; r0 += 64) {
+        const int row = row_lo + r0 + lane;
+        if (r0 + lane < RW) {
+            float t = INFINITY;
+            if (row < cn) {
+                t = 0.0f;
+#pragma unroll
+                for (int c = 0; c < PPR; ++c) {
+                    const float4 v = *reinterpret_cast<const float4 *>(img + knn_piece_off<DK>(row, c));
+                    t = __builtin_fmaf(v.x, v.x, t);
+                    t = __builtin_fmaf(v.y, v.y, t);
+                    t = __builtin_fmaf(v.z, v.z, t);
+                    t = __builtin_fmaf(v.w, v.w, t);
+                }
+                wnan |= (t != t);
+                wmax = fmaxf(wmax, t);
+            }
+            cnorm[row] = t;
+        }
+    }
+    if (want_cmax) {
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, m, 64));
+        const bool anynan = __ballot(wnan) != 0;
+        if (lane == 0) atomicMax(cmax, anynan ? 0x7fc00000u : __builtin_bit_cast(unsigned int, wmax));  // NaN > +inf
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Pre-pass of the feature-space kNN (fx3d_knn_ws): the per-cloud statistics and the fp16 image are built ONCE per cloud
 // instead of by every block of the cloud (8 blocks per cloud at C4': the scale pass alone was 8 us of the 78, bound by the
@@ -1838,137 +1912,131 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
     KNN_PROBE_MARK(25);
 }
 
+// ---- host: pre-pass predicates, LDS plan, launch ------------------------------------------------------------------------------
+int knn_mfma_dp(int D) { return (D + 31) / 32 * 32 == 96 ? 128 : (D + 31) / 32 * 32; }  // padded feature dimension: DK = 1, 2, 4
 
-
-
-size_t knn_pre_bytes(int M, int B, int D) {
-    const int DP = (D + 31) / 32 * 32 == 96 ? 128 : (D + 31) / 32 * 32;
-    return KnnPre::make(nullptr, M, DP).stride * (size_t)B;
+// The fixed regions of knn_mfma_kernel's dynamic LDS, in bytes, in the order of the kernel's carve-up (`lcnt` ... `nall` behind
+// sm + img_floats): the plan below adds up what the kernel steps through in pointers.
+//   small: list lengths [kMWaves][64] | survivors, fast-path flag, entries below kk per query [3][kMWaves][32] | cmax (4 words used
+//          of 64 bytes) | per-dimension centre [DP] | per-stage survivor counts [kMWaves][32] x 8 bytes
+//   tail (dead after the decode): mask lists (later the rank slots) | medium path: ids + merge scratch per wave | candidate norms,
+//          one array (keep_norms) or two (two_norms)
+constexpr size_t knn_mfma_small_bytes(int DP) {
+    return (size_t)kMWaves * 64 * 4 + (size_t)3 * kMWaves * 32 * 4 + 64 + (size_t)DP * 4 + (size_t)kMWaves * 32 * 8;
 }
-bool knn_pre_shape_ok(int M, int D, int kk) {
-    return D >= 4 && D <= 128 && kk <= 32 && M >= 64 && M <= 4096 && D % 4 == 0 && kPreThreads % (D / 4) == 0 && D / 4 <= 32;
-}
-// the shapes fx3d_knn_ws serves with the pre-pass: the fp16 filter (the default of knn_mfma_kernel)
-bool knn_pre_eligible(const float *x, const float *y, int M, int D, int kk) {
-    if (!knn_pre_shape_ok(M, D, kk)) return false;
-    if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) != 0) return false;
-    return !(opt(OPT_KNN_NO_MFMA) || opt(OPT_KNN_NO_PREPASS));
-}
+constexpr size_t kMListBytes = (size_t)kMWaves * kMLCap * 64 * 4;
+constexpr size_t kMMedBytes = (size_t)2 * kMWaves * (kMMedCap + 128) * 4;
+constexpr size_t knn_mfma_norm_bytes(int M) { return (size_t)((M + 255) / 256 * 256 + 256) * 4; }
+static_assert(kMWaves * 32 * 33 * 8 + 2 * kMWaves * 128 * 4 <= kMListBytes, "rank slots + fallback scratch alias the mask lists");
+constexpr size_t kMLdsMax = 152 * 1024;  // the kernels' opt-in limit of dynamic LDS
 
-template <int DK, bool F16>
-fx3d_status launch_knn_mfma_dk(const float *x, int N, const float *y, int M, int B, int D, int k, int drop,
-                               int32_t *idx, float *dist, hipStream_t st, void *pre_ws = nullptr, int xdiv = 1) {
-    constexpr int DP = DK * 32, RS = DP + 4, RSI = F16 ? DP / 2 : DP;
-    // list lengths + per-query counters + cmax + per-dimension centre + per-stage survivor counts ...
-    const bool use_pre = pre_ws != nullptr && F16;
-    const size_t small = (size_t)kMWaves * 64 * 4 + (size_t)3 * kMWaves * 32 * 4 + 64 + (size_t)DP * 4 + (size_t)kMWaves * 32 * 8;
-    static_assert(kMWaves * 32 * 33 * 8 + 2 * kMWaves * 128 * 4 <= kMWaves * kMLCap * 64 * 4, "rank slots + fallback scratch alias the mask lists");
-    const int keep_norms = M <= 4096;  // all candidate norms stay in LDS: phase B does not recompute them
-    // ... then the tail that is dead after the decode: lists (later the slots), medium path (id lists + merge scratch, one
-    // per wave), candidate norms
-    size_t tail = (size_t)kMWaves * kMLCap * 64 * 4 + (size_t)2 * kMWaves * (kMMedCap + 128) * 4;
-    if (keep_norms) tail += (size_t)((M + 255) / 256 * 256 + 256) * 4;
+struct KnnMfmaPlan {
+    int CH, img, keep_norms, two_norms, srl, csl;  // the kernel's arguments of the same names (img: img_floats)
+    size_t lds;
+};
+// f16: the fp16 filter; use_pre: behind the pre-pass; aligned16: x and y are 16-byte aligned
+KnnMfmaPlan knn_mfma_plan(int DP, bool f16, bool use_pre, int M, int D, bool aligned16) {
+    KnnMfmaPlan p{};
+    const int RS = DP + 4, RSI = f16 ? DP / 2 : DP;
+    const size_t small = knn_mfma_small_bytes(DP);
+    p.keep_norms = M <= 4096;  // all candidate norms stay in LDS: phase B does not recompute them
     // fp16 filter, room permitting: a second norms array (the candidate's error share folded in, upwards / downwards)
-    const int two_norms = F16 && keep_norms && M <= 2048;
-    if (two_norms) tail += (size_t)((M + 255) / 256 * 256 + 256) * 4;
-    const size_t fixed = small + tail;
+    p.two_norms = f16 && p.keep_norms && M <= 2048;
+    const size_t fixed = small + kMListBytes + kMMedBytes + (p.keep_norms + p.two_norms) * knn_mfma_norm_bytes(M);
     const size_t budget = 150 * 1024 - fixed;                                  // floats*4 for the two chunk buffers
     int CH = (int)(budget / 2 / ((size_t)RSI * 4 + 4)) / 64 * 64;
     if (CH > 256) CH = 256;
-    if (F16 && !use_pre && CH > kMUnits * kMProd * 8 / DP / 64 * 64) CH = kMUnits * kMProd * 8 / DP / 64 * 64;  // producer register budget
+    if (f16 && !use_pre && CH > kMUnits * kMProd * 8 / DP / 64 * 64) CH = kMUnits * kMProd * 8 / DP / 64 * 64;  // producer register budget
     const int mpad = (M + 63) / 64 * 64;
     if (CH > mpad) CH = mpad;
     if (use_pre) CH = CH >= 256 ? 256 : (CH >= 128 ? 128 : 64);  // chunks tile the image's 256-row padding exactly
+    p.CH = CH;
     size_t img = 2 * ((size_t)CH * RSI + CH);                                  // floats
     const size_t qstage = (size_t)kMWaves * 32 * RS;                           // prologue: query rows
     const size_t exact = (size_t)2 * kMWaves * 32 * kMKeyStride;               // exact phase: distance bits + indices
     if (img < qstage) img = qstage;
     if (img < exact) img = exact;
     img = (img + 3) & ~(size_t)3;
-    size_t lds = img * 4 + fixed;
-    // staged exact phase: candidate rows pass through the tail in stages of 2^srl rows of 4D + 16 bytes (at most 8 stages,
-    // at most 8 sweeps of the block per stage; the allocation may grow up to the limit for it).  0 = gather from L2.
-    int srl = 0;
+    p.img = (int)img;
+    p.lds = img * 4 + fixed;
+    // the exact phase's candidates pass through the tail (everything behind `small`); the allocation may grow up to the limit for it
+    const size_t head = img * 4 + small, room = kMLdsMax - head;
+    // staged exact phase: stages of 2^srl rows of 4D + 16 bytes (at most 8 stages, at most 8 sweeps of the block per stage).
+    // 0 = gather from L2.
     const int DS = DP > 64 && D > 64 ? 64 : D;  // staged width of a row: D > 64 goes through in two column halves
     const int PR = DS / 4;
-    const bool stageable = D % 4 == 0 && (kMThreads % PR) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+    const bool stageable = D % 4 == 0 && (kMThreads % PR) == 0 && aligned16;
     if (stageable) {
-        const size_t room = 152 * 1024 - (img * 4 + small);
         for (int l = 8; l >= 5; --l) {
             const size_t need = ((size_t)1 << l) * ((size_t)DS * 4 + 16);
             if (need <= room && ((size_t)1 << l) * PR <= 8 * (size_t)kMThreads && ((M + (1 << l) - 1) >> l) <= 8) {
-                srl = l;
-                if (img * 4 + small + need > lds) lds = img * 4 + small + need;
+                p.srl = l;
+                if (head + need > p.lds) p.lds = head + need;
                 break;
             }
         }
     }
     // column slices (round 4) instead of row stages: every row of the cloud, 16 dimensions at a time, as four planes of 16-byte
     // pieces -- when the whole cloud's slice fits the same tail (M <= 1024 at the kernel's 512 threads x 8 pieces)
-    int csl = 0;
     if (stageable && D % 16 == 0 && D <= 64 && M <= 8 * (kMThreads / 4)) {
-        const size_t room = 152 * 1024 - (img * 4 + small);
         const size_t mpc = (size_t)(M + kMThreads / 4 - 1) / (kMThreads / 4) * (kMThreads / 4);
         const size_t need = 4 * (mpc * 16 + 32);
         if (need <= room) {
-            csl = D / 16;
-            srl = 0;  // (the decode does not group the ids by row stage)
-            if (img * 4 + small + need > lds) lds = img * 4 + small + need;
+            p.csl = D / 16;
+            p.srl = 0;  // (the decode does not group the ids by row stage)
+            if (head + need > p.lds) p.lds = head + need;
         }
     }
-    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_mfma_kernel<DK, F16>), 152 * 1024, "knn_mfma_kernel");
-    if (arc != FX3D_OK) return arc;
-    FX3D_REQUIRE(lds <= 152 * 1024, "fx3d_knn: internal LDS plan exceeds the CU (D=%d)", D);
-    const int qpb = kMWaves * 32;
-    const int nbx = (N + qpb - 1) / qpb;
-    const int bpad = B >= 8 ? (B + 7) / 8 * 8 : B;
-    KnnPre pre{};
-    if (use_pre) {
-        pre = KnnPre::make(pre_ws, M, DP);
-        hipLaunchKernelGGL(knn_pre_stats_kernel, dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, DP, pre);
-        hipLaunchKernelGGL((knn_pre_image_kernel<DK>), dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, two_norms, pre);
-    }
-    if (use_pre) {
-        const fx3d_status arc2 = ensure_dynamic_lds(reinterpret_cast<const void *>(&knn_mfma_kernel<DK, F16, F16>), 152 * 1024,
-                                                    "knn_mfma_kernel<pre>");
-        if (arc2 != FX3D_OK) return arc2;
-        hipLaunchKernelGGL((knn_mfma_kernel<DK, F16, F16>), dim3(nbx * bpad), dim3(kMThreads), lds, st, x, N, y, M, B, D,
-                           k, drop, idx, dist, CH, (int)img, keep_norms, two_norms, srl, pre_ws, xdiv, csl, 1);
-    } else
-        hipLaunchKernelGGL((knn_mfma_kernel<DK, F16>), dim3(nbx * bpad), dim3(kMThreads), lds, st, x, N, y, M, B, D,
-                           k, drop, idx, dist, CH, (int)img, keep_norms, two_norms, srl, nullptr, xdiv, csl, 0);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
+    return p;
 }
 
-fx3d_status launch_knn_mfma(const float *x, int N, const float *y, int M, int B, int D, int k, int drop, int32_t *idx,
-                            float *dist, hipStream_t st, void *pre_ws = nullptr, int xdiv = 1) {
-    const int dk = (D + 31) / 32;
-    // fp16 filter: needs 16-byte loads (D % 4 == 0, aligned clouds) and all norms in LDS up front
-    const bool f16 = D % 4 == 0 && M <= 4096 && ((reinterpret_cast<uintptr_t>(y) & 15) == 0) &&
-                     ((size_t)M * D * 4) % 16 == 0;
-    if (f16) {
-        switch (dk) {
-            case 1: return launch_knn_mfma_dk<1, true>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-            case 2: return launch_knn_mfma_dk<2, true>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-            default: return launch_knn_mfma_dk<4, true>(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
-        }
-    }
-    switch (dk) {
-        case 1: return launch_knn_mfma_dk<1, false>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
-        case 2: return launch_knn_mfma_dk<2, false>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
-        default: return launch_knn_mfma_dk<4, false>(x, N, y, M, B, D, k, drop, idx, dist, st, nullptr, xdiv);
-    }
-}
+using KnnMfmaKernel = void (*)(const float *, int, const float *, int, int, int, int, int, int32_t *, float *, int, int, int, int, int, void *, int,
+                               int, int);
+using KnnPreImageKernel = void (*)(const float *, int, int, int, KnnPre);
 
 }  // namespace
 
 namespace fx3d {
+
+size_t knn_mfma_pre_bytes(int M, int B, int D) { return KnnPre::make(nullptr, M, knn_mfma_dp(D)).stride * (size_t)B; }
+bool knn_mfma_pre_shape_ok(int M, int D, int kk) {
+    return D >= 4 && D <= 128 && kk <= 32 && M >= 64 && M <= 4096 && D % 4 == 0 && kPreThreads % (D / 4) == 0 && D / 4 <= 32;
+}
+// the shapes fx3d_knn_ws serves with the pre-pass: the fp16 filter (the default of knn_mfma_kernel)
+bool knn_mfma_pre_eligible(const float *x, const float *y, int M, int D, int kk) {
+    if (!knn_mfma_pre_shape_ok(M, D, kk)) return false;
+    if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) != 0) return false;
+    return !(opt(OPT_KNN_NO_MFMA) || opt(OPT_KNN_NO_PREPASS));
+}
+
 fx3d_status knn_mfma_launch(const float *x, int N, const float *y, int M, int B, int D, int k, int drop, int32_t *idx, float *dist,
                             hipStream_t st, void *pre_ws, int xdiv) {
-    return launch_knn_mfma(x, N, y, M, B, D, k, drop, idx, dist, st, pre_ws, xdiv);
+    // fp16 filter: needs 16-byte loads (D % 4 == 0, aligned clouds) and all norms in LDS up front
+    const bool f16 = D % 4 == 0 && M <= 4096 && ((reinterpret_cast<uintptr_t>(y) & 15) == 0) && ((size_t)M * D * 4) % 16 == 0;
+    const bool use_pre = pre_ws != nullptr && f16;
+    const int DP = knn_mfma_dp(D), di = DP / 64;  // DK = 1, 2, 4 -> 0, 1, 2
+    // [DK][0: Float32 GEMM  1: fp16 filter  2: fp16 filter behind the pre-pass]
+    static const KnnMfmaKernel kernels[3][3] = {{knn_mfma_kernel<1, false>, knn_mfma_kernel<1, true>, knn_mfma_kernel<1, true, true>},
+                                                {knn_mfma_kernel<2, false>, knn_mfma_kernel<2, true>, knn_mfma_kernel<2, true, true>},
+                                                {knn_mfma_kernel<4, false>, knn_mfma_kernel<4, true>, knn_mfma_kernel<4, true, true>}};
+    static const KnnPreImageKernel pre_image[3] = {knn_pre_image_kernel<1>, knn_pre_image_kernel<2>, knn_pre_image_kernel<4>};
+    const KnnMfmaKernel kernel = kernels[di][use_pre ? 2 : (f16 ? 1 : 0)];
+    const KnnMfmaPlan p = knn_mfma_plan(DP, f16, use_pre, M, D, ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+    const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)kMLdsMax, use_pre ? "knn_mfma_kernel<pre>" : "knn_mfma_kernel");
+    if (arc != FX3D_OK) return arc;
+    FX3D_REQUIRE(p.lds <= kMLdsMax, "fx3d_knn: internal LDS plan exceeds the CU (D=%d)", D);
+    const int qpb = kMWaves * 32;
+    const int nbx = (N + qpb - 1) / qpb;
+    const int bpad = B >= 8 ? (B + 7) / 8 * 8 : B;
+    if (use_pre) {
+        const KnnPre pre = KnnPre::make(pre_ws, M, DP);
+        hipLaunchKernelGGL(knn_pre_stats_kernel, dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, DP, pre);
+        hipLaunchKernelGGL(pre_image[di], dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, p.two_norms, pre);
+    }
+    hipLaunchKernelGGL(kernel, dim3(nbx * bpad), dim3(kMThreads), p.lds, st, x, N, y, M, B, D, k, drop, idx, dist, p.CH, p.img, p.keep_norms,
+                       p.two_norms, p.srl, use_pre ? pre_ws : nullptr, xdiv, p.csl, use_pre ? 1 : 0);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
 }
-bool knn_mfma_pre_shape_ok(int M, int D, int kk) { return knn_pre_shape_ok(M, D, kk); }
-bool knn_mfma_pre_eligible(const float *x, const float *y, int M, int D, int kk) { return knn_pre_eligible(x, y, M, D, kk); }
-size_t knn_mfma_pre_bytes(int M, int B, int D) { return knn_pre_bytes(M, B, D); }
+
 }  // namespace fx3d

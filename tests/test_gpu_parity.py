@@ -1326,6 +1326,18 @@ def test_knn_candidate_slices_plan_is_a_function_of_the_shape(gpu_fx):
     assert np.array_equal(idx.to_host(), ref)
 
 
+def test_knn_no_mfma_beyond_the_wave_kernels_tile(gpu_fx, oracle, fx_option):
+    """knn_no_mfma = 1 at D = 96, k = 20: without the matrix-core kernel the shape's route is the general selection kernel (the
+    wave-per-query kernel's tile of 128 rows x (D + 1) floats passes 64 KiB of LDS from D = 85 on): the oracle's lists bit for bit."""
+    rng = np.random.default_rng(96)
+    x = np.asfortranarray(rng.standard_normal((96, 200, 2)).astype(np.float32))
+    y = np.asfortranarray(rng.standard_normal((96, 700, 2)).astype(np.float32))
+    fx_option("knn_no_mfma", "1")
+    idx, dist = gpu_fx.knn(x, 20, y=y)
+    oi, od = oracle.knn(x, 20, y=y)
+    assert np.array_equal(idx.to_host(), oi) and np.array_equal(dist.to_host(), od)
+
+
 @pytest.mark.parametrize("D,N,M,B,k,drop,kind", [(64, 300, 1024, 2, 40, True, "normal"), (64, 257, 512, 1, 63, True, "normal"), (16, 200, 2048, 2, 33, False, "normal"),
                                                   (128, 130, 256, 1, 64, False, "normal"), (64, 200, 1024, 1, 40, False, "sorted"), (32, 150, 1024, 2, 50, True, "sorted"),
                                                   (8, 300, 768, 1, 36, True, "lattice"), (64, 100, 1024, 1, 48, True, "dupes"), (20, 90, 640, 1, 41, False, "normal"),

@@ -1,8 +1,8 @@
 // Phase-level timing of knn_mfma_kernel at the second EdgeConv's shape (B=32, N=M=1024, D=64, k=20+1):
 // includes knn.hip with FX3D_PROBE so that thread 0 of every block stores cycle-counter stamps.  Build:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DFX3D_PROBE -I include -I flux3d.jl_amd/csrc \
-//         tools/knn_probe.hip flux3d.jl_amd/csrc/runtime.hip -o tools/knn_probe
-#define FX3D_KNN_ONE_TU  // the three units of the k-NN family in one translation unit: one g_kprobe, no cross-unit shims
+//         tools/knn_probe.hip flux3d.jl_amd/csrc/edge_features.hip flux3d.jl_amd/csrc/runtime.hip -o tools/knn_probe
+// the three units of the k-NN family in one translation unit: one g_kprobe
 #include "../flux3d.jl_amd/csrc/knn_d3.hip"
 #include "../flux3d.jl_amd/csrc/knn_mfma.hip"
 #include "../flux3d.jl_amd/csrc/knn.hip"
