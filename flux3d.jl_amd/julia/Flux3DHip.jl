@@ -29,7 +29,7 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  compute_verts_normals_packed, compute_faces_normals_packed,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
                  _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel,
-                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!, PointNet
+                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!, PointNet, DGCNN
 using SparseArrays: SparseMatrixCSC, findnz
 import Zygote
 
@@ -1529,6 +1529,55 @@ function pointnet_forward(m::PointNet, X::HipArray{Float32,3}; intermediates::Bo
     return intermediates ? (probs = probs, logits = logits, stn = stn, fstn = fstn, pooled = pooled) : probs
 end
 (m::PointNet)(X::HipArray{Float32,3}) = pointnet_forward(m, X)
+
+# ---- DGCNN inference: (m::DGCNN)(X) (src/models/dgcnn.jl:113-147) in test mode --------------------------------------------
+# As for PointNet: the Flux layers' arrays flattened in forward order (include/flux3d_hip.h "DGCNN inference") on every call,
+# running statistics, Dropout as the identity.  An EdgeConv's mlp is a Chain of conv_bn_blocks, each a Chain(Conv, BatchNorm,
+# closure) (src/models/utils.jl:1-3); conv_3, fc_4 and fc_5 are one such block each.  The neighbour search, the edge rows and
+# the maximum over k run inside the library: the (K N, 2F, B) array of :51 is never built.
+_flat_block!(out, blk) = (blk[1] isa Flux3D.Flux.Conv ? _flat_conv!(out, blk[1]) : _flat_dense!(out, blk[1]); _flat_bn!(out, blk[2]))
+function dgcnn_params(m::DGCNN)
+    out = Float32[]
+    for ec in (m.EdgeConv1, m.EdgeConv2), blk in ec.mlp.layers
+        _flat_block!(out, blk)
+    end
+    _flat_block!(out, m.conv_3); _flat_block!(out, m.fc_4); _flat_block!(out, m.fc_5)
+    _flat_dense!(out, m.fc_6)
+    return out
+end
+function dgcnn_forward(m::DGCNN, X::HipArray{Float32,3}; intermediates::Bool = false)
+    size(X, 1) == 3 || error("DGCNN takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    K = m.EdgeConv1.K
+    m.EdgeConv2.K == K || error("DGCNN: both EdgeConvs must use the same K")
+    npoints = m.maxpool_3.k[1]
+    N == npoints || error("DGCNN(num_classes, K, npoints = $npoints) takes clouds of npoints points, got $N: MaxPool((npoints,)) is the maximum over a whole cloud only then")
+    (1 <= K && K + 1 <= N) || error("DGCNN needs 1 <= K <= N - 1, got K = $K, N = $N")
+    nc = size(_dense_wb(m.fc_6)[1], 1)
+    params = dgcnn_params(m)
+    cnt = Ref{Int64}(0)
+    check(@ccall LIB.fx3d_dgcnn_param_count(Int32(nc)::Int32, cnt::Ref{Int64})::Int32)
+    length(params) == cnt[] || error("DGCNN has $(length(params)) parameters, the library expects $(cnt[])")
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_dgcnn_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(K)::Int32, Int32(nc)::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    probs = HipArray{Float32}(undef, nc, B)
+    logits = intermediates ? HipArray{Float32}(undef, nc, B) : nothing
+    idx1 = intermediates ? HipArray{Int32}(undef, K, N, B) : nothing
+    x1 = intermediates ? HipArray{Float32}(undef, 64, N, B) : nothing
+    idx2 = intermediates ? HipArray{Int32}(undef, K, N, B) : nothing
+    x2 = intermediates ? HipArray{Float32}(undef, 256, N, B) : nothing
+    pooled = intermediates ? HipArray{Float32}(undef, 1024, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_dgcnn_forward(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, Int32(K)::Int32, X.ptr::Ptr{Cvoid}, Int32(N)::Int32,
+                                        Int32(B)::Int32, probs.ptr::Ptr{Cvoid}, opt(logits)::Ptr{Cvoid}, opt(idx1)::Ptr{Cvoid},
+                                        opt(x1)::Ptr{Cvoid}, opt(idx2)::Ptr{Cvoid}, opt(x2)::Ptr{Cvoid}, opt(pooled)::Ptr{Cvoid},
+                                        ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    # idx1 / idx2 are the library's 0-based Int32 indices
+    return intermediates ? (probs = probs, logits = logits, idx1 = idx1, x1 = x1, idx2 = idx2, x2 = x2, pooled = pooled) : probs
+end
+(m::DGCNN)(X::HipArray{Float32,3}) = dgcnn_forward(m, X)
 
 
 end # module

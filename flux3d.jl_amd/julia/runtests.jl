@@ -200,4 +200,21 @@ end
             @test unhip(Flux3DHip.pointnet_forward(model, hip(x_test))) == y              # the same bits on every run
         end
     end
+
+    @testset "DGCNN (test/models.jl:24-41) on a device batch" begin
+        x_test = rand(Float32, 3, 64, 2)
+        for num_classes in [10, 40]
+            model = Flux3D.DGCNN(num_classes, 10, 64)
+            y_test = model(hip(x_test))
+            @test y_test isa AbstractArray
+            @test size(y_test) == (num_classes, size(x_test, 3))
+            y = unhip(y_test)
+            @test all(isapprox.(sum(y, dims = 1), 1f0, atol = 1f-5))
+            @test isapprox(y, Flux3D.Flux.testmode!(model)(x_test), rtol = 1f-3)     # Flux's BLAS sums: close, not equal
+            r = Flux3DHip.dgcnn_forward(model, hip(x_test); intermediates = true)
+            @test size(r.idx1) == (10, 64, 2) && size(r.x1) == (64, 64, 2) && size(r.x2) == (256, 64, 2) && size(r.pooled) == (1024, 2)
+            @test all(0 .<= unhip(r.idx1) .< 64)                                          # the library's indices are 0-based
+            @test unhip(Flux3DHip.dgcnn_forward(model, hip(x_test))) == y                 # the same bits on every run
+        end
+    end
 end

@@ -1,8 +1,9 @@
-"""PointNet inference on the device (src/models/pointnet.jl): ``PointNet(num_classes, 64)(X)`` in test mode.
+"""PointNet and DGCNN inference on the device (src/models/pointnet.jl, src/models/dgcnn.jl): ``PointNet(num_classes, 64)(X)``
+and ``DGCNN(num_classes, K, npoints)(X)`` in test mode.
 
-include/flux3d_hip.h states the network and its arithmetic ("PointNet inference"); this module owns the parameters (a name ->
-numpy array mapping in Flux's shapes), flattens them into the one device buffer fx3d_pointnet_forward reads, and checks
-every argument on the host before any launch.  Forward only: no training, no gradients."""
+include/flux3d_hip.h states the networks and their arithmetic ("PointNet inference", "DGCNN inference"); this module owns the
+parameters (a name -> numpy array mapping in Flux's shapes), flattens them into the one device buffer fx3d_pointnet_forward /
+fx3d_dgcnn_forward reads, and checks every argument on the host before any launch.  Forward only: no training, no gradients."""
 import ctypes as C
 
 import numpy as np
@@ -29,12 +30,12 @@ def layer_spec(num_classes):
                ("feat.dense2", "dense", (512, 256)), ("feat.bn4", "bn", 256), ("cls", "dense", (256, int(num_classes)))])
 
 
-def param_shapes(num_classes):
-    """name -> shape of every parameter array, in the order of the flat buffer.  Flux's shapes: Conv((1,), Cin => Cout) has
-    weight (1, Cin, Cout) and bias (Cout,); BatchNorm(C) has gamma, beta, mu, sigma2 (C,); Dense(in, out) has weight
-    (out, in) and bias (out,)."""
+def _shapes(spec):
+    """name -> shape of every parameter array of a layer table, in the order of the flat buffer.  Flux's shapes:
+    Conv((1,), Cin => Cout) has weight (1, Cin, Cout) and bias (Cout,); BatchNorm(C) has gamma, beta, mu, sigma2 (C,);
+    Dense(in, out) has weight (out, in) and bias (out,)."""
     shapes = {}
-    for name, kind, ch in layer_spec(num_classes):
+    for name, kind, ch in spec:
         if kind == "conv":
             shapes[name + ".weight"], shapes[name + ".bias"] = (1, ch[0], ch[1]), (ch[1],)
         elif kind == "dense":
@@ -45,25 +46,37 @@ def param_shapes(num_classes):
     return shapes
 
 
-class PointNet:
-    """``PointNet(num_classes=10, K=64)`` (src/models/pointnet.jl:41-60).
+def param_shapes(num_classes):
+    """PointNet: name -> shape of every parameter array, in the order of the flat buffer (Flux's shapes, :func:`_shapes`)."""
+    return _shapes(layer_spec(num_classes))
 
-    ``params``: name -> Float32 numpy array in Flux's shapes (:func:`param_shapes`).  A new model is filled the way Flux
-    fills one -- Glorot-uniform weights, zero biases, BatchNorm gamma = 1, beta = 0, mu = 0, sigma2 = 1 -- from a numpy
-    generator seeded with ``seed``: the reference's draws come from Julia's global RNG and cannot be reproduced here.
-    ``load(params)`` replaces them (a trained model's arrays) after shape checks.  They are uploaded once, at the first
-    forward after construction or ``load``, and the device copy is kept."""
 
-    def __init__(self, num_classes=10, K=64, seed=0):
-        if int(K) != 64:
-            raise ValueError(f"PointNet(num_classes, K) needs K = 64, got {K}: the reference's conv_block1 has 64 output "
-                             "channels whatever K is, so its batched_mul with the (K, K) feature transform throws for any other K")
-        if int(num_classes) < 1:
-            raise ValueError(f"num_classes must be positive, got {num_classes}")
-        self.num_classes, self.K = int(num_classes), 64
+def dgcnn_layer_spec(num_classes):
+    """DGCNN's layers that carry parameters, in forward order (src/models/dgcnn.jl:18-30,99-111): EdgeConv([3, 32, 64, 64], K)
+    has conv_bn_blocks 6 => 32, 32 => 64, 64 => 64; EdgeConv([64, 128, 256], K) has 128 => 128, 128 => 256."""
+    return [("ec1.conv1", "conv", (6, 32)), ("ec1.bn1", "bn", 32), ("ec1.conv2", "conv", (32, 64)), ("ec1.bn2", "bn", 64),
+            ("ec1.conv3", "conv", (64, 64)), ("ec1.bn3", "bn", 64),
+            ("ec2.conv1", "conv", (128, 128)), ("ec2.bn1", "bn", 128), ("ec2.conv2", "conv", (128, 256)), ("ec2.bn2", "bn", 256),
+            ("conv3.conv", "conv", (256, 1024)), ("conv3.bn", "bn", 1024),
+            ("fc4.dense", "dense", (1024, 512)), ("fc4.bn", "bn", 512), ("fc5.dense", "dense", (512, 256)), ("fc5.bn", "bn", 256),
+            ("fc6", "dense", (256, int(num_classes)))]
+
+
+def dgcnn_param_shapes(num_classes):
+    """DGCNN: name -> shape of every parameter array, in the order of the flat buffer (Flux's shapes, :func:`_shapes`)."""
+    return _shapes(dgcnn_layer_spec(num_classes))
+
+
+class _Model:
+    """What the two classifiers share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy,
+    and the check of the input clouds.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``."""
+
+    def _init_params(self, seed):
+        """Filled the way Flux fills a new model -- Glorot-uniform weights, zero biases, BatchNorm gamma = 1, beta = 0, mu = 0,
+        sigma2 = 1 -- from a numpy generator seeded with ``seed``."""
         rng = np.random.default_rng(seed)
         self.params = {}
-        for name, shape in param_shapes(self.num_classes).items():
+        for name, shape in self._shapes().items():
             field = name.rsplit(".", 1)[1]
             if field == "weight":
                 fan_in, fan_out = (shape[1], shape[2]) if len(shape) == 3 else (shape[1], shape[0])
@@ -73,12 +86,12 @@ class PointNet:
                 self.params[name] = np.full(shape, 1.0 if field in ("gamma", "sigma2") else 0.0, np.float32)
         self._dev = None
         count = C.c_int64(0)
-        _lib.call("fx3d_pointnet_param_count", self.num_classes, C.byref(count))
+        _lib.call(self._COUNT_FN, self.num_classes, C.byref(count))
         self.param_count = count.value
 
     def load(self, params):
-        """Replace the parameters: a mapping with exactly the names and shapes of :func:`param_shapes`."""
-        shapes = param_shapes(self.num_classes)
+        """Replace the parameters: a mapping with exactly the names and shapes of the model's ``param_shapes``."""
+        shapes = self._shapes()
         missing, extra = sorted(set(shapes) - set(params)), sorted(set(params) - set(shapes))
         if missing or extra:
             raise ValueError(f"parameter names do not match: missing {missing[:4]}, unknown {extra[:4]}")
@@ -92,8 +105,8 @@ class PointNet:
         return self
 
     def flat_params(self):
-        """The flat Float32 buffer of fx3d_pointnet_forward: every array column-major, in forward order."""
-        flat = np.concatenate([self.params[n].ravel(order="F") for n in param_shapes(self.num_classes)]).astype(np.float32)
+        """The flat Float32 buffer the forward entry point reads: every array column-major, in forward order."""
+        flat = np.concatenate([self.params[n].ravel(order="F") for n in self._shapes()]).astype(np.float32)
         assert flat.size == self.param_count, (flat.size, self.param_count)
         return flat
 
@@ -102,10 +115,8 @@ class PointNet:
             self._dev = DeviceArray.from_host(self.flat_params())
         return self._dev
 
-    def forward(self, X, intermediates=False):
-        """Class probabilities ``(num_classes, B)`` of the clouds ``X``: a PointCloud, a device array or a numpy array,
-        ``(3, N, B)`` or ``(3, N)`` (one cloud).  The result lives where the input lives.  ``intermediates=True``: a dict
-        with ``probs``, ``logits`` (num_classes, B), ``stn`` (3, 3, B), ``fstn`` (64, 64, B) and ``pooled`` (1024, B)."""
+    def _clouds(self, X, why3):
+        """(the points, N, B, whether they are on the device) after the shape checks; nothing is uploaded yet."""
         pts = X.points if isinstance(X, PointCloud) else X
         on_dev = is_device(pts)
         if on_dev:
@@ -120,11 +131,46 @@ class PointNet:
         if len(shape) != 3:
             raise ValueError(f"points must be (3, N) or (3, N, B), got {tuple(shape)}")
         if shape[0] != 3:
-            raise ValueError(f"PointNet takes 3 channels per point (stnKD(3)), got {shape[0]}")
+            raise ValueError(f"{self._NAME} takes 3 channels per point ({why3}), got {shape[0]}")
         N, B = int(shape[1]), int(shape[2])
         if N < 1 or B < 1:
-            raise ValueError(f"PointNet needs at least one point and one cloud, got N={N}, B={B}")
-        x = pts.reshape(3, N, B) if on_dev else DeviceArray.from_host(np.asfortranarray(pts.reshape(3, N, B, order="F")))
+            raise ValueError(f"{self._NAME} needs at least one point and one cloud, got N={N}, B={B}")
+        return pts, N, B, on_dev
+
+    @staticmethod
+    def _on_device(pts, N, B, on_dev):
+        return pts.reshape(3, N, B) if on_dev else DeviceArray.from_host(np.asfortranarray(pts.reshape(3, N, B, order="F")))
+
+
+class PointNet(_Model):
+    """``PointNet(num_classes=10, K=64)`` (src/models/pointnet.jl:41-60).
+
+    ``params``: name -> Float32 numpy array in Flux's shapes (:func:`param_shapes`).  A new model is filled the way Flux
+    fills one -- Glorot-uniform weights, zero biases, BatchNorm gamma = 1, beta = 0, mu = 0, sigma2 = 1 -- from a numpy
+    generator seeded with ``seed``: the reference's draws come from Julia's global RNG and cannot be reproduced here.
+    ``load(params)`` replaces them (a trained model's arrays) after shape checks.  They are uploaded once, at the first
+    forward after construction or ``load``, and the device copy is kept."""
+
+    _NAME, _COUNT_FN = "PointNet", "fx3d_pointnet_param_count"
+
+    def __init__(self, num_classes=10, K=64, seed=0):
+        if int(K) != 64:
+            raise ValueError(f"PointNet(num_classes, K) needs K = 64, got {K}: the reference's conv_block1 has 64 output "
+                             "channels whatever K is, so its batched_mul with the (K, K) feature transform throws for any other K")
+        if int(num_classes) < 1:
+            raise ValueError(f"num_classes must be positive, got {num_classes}")
+        self.num_classes, self.K = int(num_classes), 64
+        self._init_params(seed)
+
+    def _shapes(self):
+        return param_shapes(self.num_classes)
+
+    def forward(self, X, intermediates=False):
+        """Class probabilities ``(num_classes, B)`` of the clouds ``X``: a PointCloud, a device array or a numpy array,
+        ``(3, N, B)`` or ``(3, N)`` (one cloud).  The result lives where the input lives.  ``intermediates=True``: a dict
+        with ``probs``, ``logits`` (num_classes, B), ``stn`` (3, 3, B), ``fstn`` (64, 64, B) and ``pooled`` (1024, B)."""
+        pts, N, B, on_dev = self._clouds(X, "stnKD(3)")
+        x = self._on_device(pts, N, B, on_dev)
         nc = self.num_classes
         out = {"probs": DeviceArray.empty((nc, B), np.float32)}
         if intermediates:
@@ -135,6 +181,58 @@ class PointNet:
         ws = workspace(nb.value, tag="pointnet")
         opt = [out[k].ptr if intermediates else None for k in ("logits", "stn", "fstn", "pooled")]
         _lib.call("fx3d_pointnet_forward", self._params_dev().ptr, nc, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        if not on_dev:
+            out = {k: v.to_host() for k, v in out.items()}
+        return out if intermediates else out["probs"]
+
+    __call__ = forward
+
+
+class DGCNN(_Model):
+    """``DGCNN(num_classes=10, K=10, npoints=1024)`` (src/models/dgcnn.jl:99-111) in test mode: include/flux3d_hip.h
+    "DGCNN inference" states the network and its arithmetic.
+
+    ``params`` (:func:`dgcnn_param_shapes`), ``load``, ``flat_params`` and the seeded initialisation are PointNet's.
+    ``npoints`` is the window of the reference's ``MaxPool((npoints,))`` over the (N, 1024, B) output of conv_3: only with
+    N == npoints is that the one maximum per cloud and channel whose reshape gives the (1024, B) the classifier takes -- a
+    multiple of npoints leaves several windows per cloud, which the reshape folds into the batch, anything else drops
+    points.  ``forward`` therefore raises ``ValueError`` for clouds of any other size."""
+
+    _NAME, _COUNT_FN = "DGCNN", "fx3d_dgcnn_param_count"
+
+    def __init__(self, num_classes=10, K=10, npoints=1024, seed=0):
+        if int(num_classes) < 1:
+            raise ValueError(f"num_classes must be positive, got {num_classes}")
+        if int(K) < 1 or int(K) + 1 > int(npoints):
+            raise ValueError(f"DGCNN needs 1 <= K <= npoints - 1 (K neighbours besides the point itself), got K={K}, npoints={npoints}")
+        self.num_classes, self.K, self.npoints = int(num_classes), int(K), int(npoints)
+        self._init_params(seed)
+
+    def _shapes(self):
+        return dgcnn_param_shapes(self.num_classes)
+
+    def forward(self, X, intermediates=False):
+        """Class probabilities ``(num_classes, B)`` of the clouds ``X``: a PointCloud, a device array or a numpy array,
+        ``(3, npoints, B)`` or ``(3, npoints)`` (one cloud).  The result lives where the input lives.
+        ``intermediates=True``: a dict with ``probs``, ``logits`` (num_classes, B), ``idx1`` and ``idx2`` (K, N, B) int32,
+        0-based, ``x1`` (64, N, B), ``x2`` (256, N, B) and ``pooled`` (1024, B)."""
+        pts, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
+        if N != self.npoints:
+            raise ValueError(f"DGCNN(num_classes, K, npoints={self.npoints}) takes clouds of npoints points, got N={N}: "
+                             "MaxPool((npoints,)) is the maximum over a whole cloud only then")
+        x = self._on_device(pts, N, B, on_dev)
+        nc, K = self.num_classes, self.K
+        out = {"probs": DeviceArray.empty((nc, B), np.float32)}
+        if intermediates:
+            out.update(logits=DeviceArray.empty((nc, B), np.float32), idx1=DeviceArray.empty((K, N, B), np.int32),
+                       x1=DeviceArray.empty((64, N, B), np.float32), idx2=DeviceArray.empty((K, N, B), np.int32),
+                       x2=DeviceArray.empty((256, N, B), np.float32), pooled=DeviceArray.empty((1024, B), np.float32))
+        nb = C.c_size_t(0)
+        _lib.call("fx3d_dgcnn_workspace_bytes", N, B, K, nc, C.byref(nb))
+        ws = workspace(nb.value, tag="dgcnn")
+        opt = [out[k].ptr if intermediates else None for k in ("logits", "idx1", "x1", "idx2", "x2", "pooled")]
+        _lib.call("fx3d_dgcnn_forward", self._params_dev().ptr, nc, K, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
                   current_stream().handle)
         if not on_dev:
             out = {k: v.to_host() for k, v in out.items()}

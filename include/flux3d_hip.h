@@ -801,6 +801,44 @@ FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_
                                            int32_t B, float *probs, float *logits, float *stn, float *fstn,
                                            float *pooled, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- DGCNN inference: (m::DGCNN)(X) (src/models/dgcnn.jl:113-147) in test mode ------------------------------------------
+ * Forward only, Float32: BatchNorm uses its running statistics, Dropout is the identity.  x (3,N,B) device.  DGCNN(num_classes,
+ * K, npoints) with N == npoints: MaxPool((npoints,)) is then the maximum over all points of a cloud, which is what this
+ * computes (for another N the reference's reshape to (1024,B) fails or mixes clouds; the host layers refuse it).
+ * conv_bn_block / fc_bn_block (src/models/utils.jl:1-7) are conv or dense, BN, relu -- in this order.  In the order they run:
+ *   EdgeConv1 = EdgeConv([3,32,64,64], K) (:32-71):  idx1 (K,N,B) = the K nearest neighbours of every point among its cloud's
+ *                      points in coordinate space, the point itself (rank 0 of K+1) dropped: fx3d_knn's order and 0-based
+ *                      indices; edge row (k,n) = [x_n (3), x_idx1(k,n) - x_n (3)]; conv 6->32, 32->64, 64->64, each BN, relu;
+ *                      x1[c,n,b] = max over k                                             -> x1 (64,N,B)
+ *   EdgeConv2 = EdgeConv([64,128,256], K):  the same on x1: idx2 from the 64-dimensional rows of x1; edge row of 128;
+ *                      conv 128->128, 128->256, each BN, relu; max over k                 -> x2 (256,N,B)
+ *   conv_3:            conv 256->1024, BN, relu; max over the N points                    -> pooled (1024,B)
+ *   fc_4, fc_5:        dense 1024->512, BN, relu . dense 512->256, BN, relu . (Dropout)
+ *   fc_6:              dense 256->num_classes = logits (no activation before the softmax, unlike PointNet) . softmax = probs
+ * The reference's reshape(K, an N, B) / MaxPool((K,)) / reshape / permute (:57-68) is the maximum over k per (channel, point).
+ * Arithmetic: the PointNet contract above, verbatim -- contraction as one fmaf chain from +0.0f over ALL 2F concatenated
+ * channels ascending (the x_n half first), one Float32 bias addition, BatchNorm with eps = 1f-5 and every operation rounded
+ * to Float32, relu and both maxima as Julia's max (NaN wins, max(-0.0, +0.0) = +0.0: order-free), the softmax as there.  The
+ * edge difference is one Float32 subtraction.  (Flux's MaxPool is NNlib's; its NaN behaviour is not pinned here: Julia's max
+ * is the definition.)  The (K N, 2F, B) edge array is never written to memory.
+ * idx1, x1, idx2, x2, pooled and logits are bit-identical to the restatement tests/dgcnn_ref.py and from run to run, whatever
+ * N, B, K and the launch shape: one accumulator per output element, no contraction split over waves or blocks, no float atomics.
+ * params_dev: ONE flat device Float32 buffer in forward order -- EdgeConv1's three (conv, BN), EdgeConv2's two, conv_3's one,
+ *   (fc_4 dense, BN), (fc_5 dense, BN), fc_6 -- each layer laid out as for PointNet (conv W (Cin,Cout) then b; BN gamma, beta,
+ *   mu, var; dense W (out,in) then b).  fx3d_dgcnn_param_count(num_classes) is its length in floats.
+ * 1 <= K <= N - 1, N <= 36864 (the neighbour search's general kernel), B <= 65535, N B K <= 2^31; anything else, a NULL
+ * required pointer, a short workspace or one not 256-byte aligned is FX3D_ERR_INVALID_ARG before any launch.
+ * probs (num_classes,B) is required; logits (num_classes,B), idx1 and idx2 (K,N,B) int32, x1 (64,N,B; 16-byte aligned),
+ * x2 (256,N,B) and pooled (1024,B) are optional (NULL: not written).  Launches on `s` only (two searches through fx3d_knn_ws,
+ * two EdgeConv kernels, conv_3, the head), no host synchronisation, no host memory read after the argument check
+ * (graph-capturable).  ws: fx3d_dgcnn_workspace_bytes(N, B, K, num_classes) -- x1, x2, the two index arrays, per-tile maxima
+ * and the search's scratch. */
+FX3D_API fx3d_status fx3d_dgcnn_param_count(int32_t num_classes, int64_t *count);
+FX3D_API fx3d_status fx3d_dgcnn_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N,
+                                        int32_t B, float *probs, float *logits, int32_t *idx1, float *x1, int32_t *idx2,
+                                        float *x2, float *pooled, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
