@@ -223,6 +223,13 @@ def call(name, *args):
     check(getattr(load(), name)(*args))
 
 
+def query_bytes(name, *args):
+    """A size query of the C ABI, ``fx3d_*_workspace_bytes(*args, size_t *bytes)``, as an int."""
+    n = sz(0)
+    call(name, *args, C.byref(n))
+    return n.value
+
+
 def set_option(name, value):
     """fx3d_set_option: choose one of the kernels' alternative code paths (include/flux3d_hip.h "variant switches")."""
     call("fx3d_set_option", name.encode(), int(value))

@@ -1,7 +1,5 @@
 """Representation conversions on the device: pointcloud_to_voxel and trimesh_to_voxel (src/conversions.jl:91-207), and
 voxel_to_trimesh with algo :Exact and the constructors built on it (src/conversions.jl:1-67, 209-349)."""
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -21,9 +19,8 @@ def pointcloud_to_voxel(pcloud, resolution=32):
     if D != 3:
         raise ValueError("pointcloud_to_voxel needs 3-D points")
     res = int(resolution)
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_voxel_workspace_bytes", B, C.byref(nb))
-    ws = workspace(nb.value, tag="voxel")
+    nb = _lib.query_bytes("fx3d_voxel_workspace_bytes", B)
+    ws = workspace(nb, tag="voxel")
     out = DeviceArray.empty((res, res, res, B), np.float32)
     _lib.call("fx3d_pointcloud_to_voxel", x.ptr, N, B, res, out.ptr, ws.ptr, ws.nbytes, current_stream().handle)
     return out
@@ -46,9 +43,8 @@ def trimesh_to_voxel(m, resolution=32, bad=None):
     verts = _verts_padded_dev(m)
     faces, flen = (m.dev("faces_padded").ptr, m.dev("faces_len").ptr) if m.F > 0 else (None, None)
     B = m.N
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_trimesh_voxel_workspace_bytes", m.V, m.F, B, res, C.byref(nb))
-    ws = workspace(nb.value, tag="trimesh_voxel")
+    nb = _lib.query_bytes("fx3d_trimesh_voxel_workspace_bytes", m.V, m.F, B, res)
+    ws = workspace(nb, tag="trimesh_voxel")
     out = DeviceArray.empty((res, res, res, B), np.float32)
     counter = DeviceArray.zeros((1,), np.uint32) if bad is None else bad
     _lib.call("fx3d_trimesh_to_voxel", verts.ptr, m.V, m.dev("nverts").ptr, faces, m.F, flen, B, res, out.ptr,
@@ -92,9 +88,8 @@ def _voxel_mesh(v, thresh, faces):
     res, B = vox.shape[0], vox.shape[3]
     if not 1 <= res <= 1024:
         raise ValueError("voxel_to_trimesh: resolution must lie in [1, 1024]")
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_voxel_mesh_workspace_bytes", res, B, C.byref(nb))
-    ws = workspace(nb.value, tag="voxel_mesh")
+    nb = _lib.query_bytes("fx3d_voxel_mesh_workspace_bytes", res, B)
+    ws = workspace(nb, tag="voxel_mesh")
     st = current_stream().handle
     counts = DeviceArray.empty((2 * B,), np.int64)  # K (B int64), then the invalid-element counts (B uint32)
     _lib.call("fx3d_voxel_mesh_count", vox.ptr, res, B, float(np.float32(thresh)), counts.ptr, counts.ptr + 8 * B,

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "fx3d_common.h"
+#include "mesh_host.h"
 #include "sample_gather.h"
 #include "mesh_reg.h"
 
@@ -536,6 +537,48 @@ int bg_nsplit(int B, int maxr, int sides = 2) {
     return nsplit;
 }
 
+// The weights of the two sums' gradient rows.  ONE expression, its order fixed: these are the bits every adjoint multiplies by.
+struct ChamferCoef { float ca, cb; };
+ChamferCoef chamfer_coef(float gout, float w1, float w2, int D, int N, int M, int64_t B_global) {
+    return ChamferCoef{gout * w1 * (float)(6.0 / ((double)D * N * (double)B_global)),
+                       gout * w2 * (float)(6.0 / ((double)D * M * (double)B_global))};
+}
+
+// The one launch site of chamfer_bwd_gather_kernel: `nsplit` row blocks per cloud and side with a gradient array.
+// pass == nullptr (fx3d_chamfer_bwd, any D): the row blocks alone.  Otherwise (fx3d_chamfer_sampled_bwd's first launch, D = 3): in
+// front of them the passengers -- ntab table jobs with `lds` bytes of dynamic LDS, then the regularisers' adjoint blocks.
+constexpr size_t kTabLds = 112 * 1024;  // what the table jobs may take beside the row blocks' 38 KB of static LDS
+struct BgPassengers {
+    SgTabJobs tj;
+    int ntab;
+    size_t lds;
+    const meshreg::Ride *ride;
+};
+fx3d_status launch_bwd_gather(const float *x, int N, const float *y, int M, int B, int D, const int32_t *idx_x, const int32_t *idx_y,
+                              ChamferCoef c, float *gx, float *gy, int nsplit, const BgPassengers *pass, hipStream_t st) {
+    const int sides = (gx ? 1 : 0) + (gy ? 1 : 0);
+    const dim3 block(kBgThreads);
+    if (!pass) {
+        ProfileScope prof("chamfer_bwd", st);
+        const dim3 grid(sides * B * nsplit);
+        if (D == 3)
+            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<true, false>), grid, block, 0, st, x, N, y, M, D, idx_x, idx_y, c.ca, c.cb, gx, gy,
+                               nsplit, 0, SgTabJobs{}, 0, meshreg::Ride{});
+        else
+            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<false, false>), grid, block, 0, st, x, N, y, M, D, idx_x, idx_y, c.ca, c.cb, gx, gy,
+                               nsplit, 0, SgTabJobs{}, 0, meshreg::Ride{});
+    } else {
+        if (pass->ntab)
+            FX3D_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&chamfer_bwd_gather_kernel<true, true>), (int)kTabLds, "chamfer_bwd_gather_kernel"));
+        ProfileScope prof("chamfer_sampled_bwd", st);
+        const int npass = pass->ntab + (pass->ride ? pass->ride->nadj : 0);
+        hipLaunchKernelGGL((chamfer_bwd_gather_kernel<true, true>), dim3(npass + sides * B * nsplit), block, pass->lds, st, x, N, y, M, D, idx_x,
+                           idx_y, c.ca, c.cb, gx, gy, nsplit, npass, pass->tj, pass->ntab, pass->ride ? *pass->ride : meshreg::Ride{});
+    }
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -549,29 +592,19 @@ fx3d_status fx3d_chamfer_bwd(const float *x, int32_t N, const float *y, int32_t 
     FX3D_REQUIRE(idx_x && idx_y && gx && gy, "fx3d_chamfer_bwd: null pointer");
     FX3D_REQUIRE(B_global >= B, "fx3d_chamfer_bwd: B_global < B");
     hipStream_t st = as_stream(s);
-    const float ca = gout * w1 * (float)(6.0 / ((double)D * N * (double)B_global));
-    const float cb = gout * w2 * (float)(6.0 / ((double)D * M * (double)B_global));
+    const ChamferCoef c = chamfer_coef(gout, w1, w2, D, N, M, B_global);
     const int nsplit = bg_nsplit(B, N > M ? N : M);
-    if ((long long)2 * B * nsplit < (1ll << 30) && !opt(OPT_BWD_GLOBAL_ATOMICS)) {
-        ProfileScope prof("chamfer_bwd", st);
-        if (D == 3)
-            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<true, false>), dim3(2 * B * nsplit), dim3(kBgThreads), 0, st, x, N, y, M, D, idx_x,
-                               idx_y, ca, cb, gx, gy, nsplit, 0, SgTabJobs{}, 0, meshreg::Ride{});
-        else
-            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<false, false>), dim3(2 * B * nsplit), dim3(kBgThreads), 0, st, x, N, y, M, D, idx_x,
-                               idx_y, ca, cb, gx, gy, nsplit, 0, SgTabJobs{}, 0, meshreg::Ride{});
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
-    }
+    if ((long long)2 * B * nsplit < (1ll << 30) && !opt(OPT_BWD_GLOBAL_ATOMICS))
+        return launch_bwd_gather(x, N, y, M, B, D, idx_x, idx_y, c, gx, gy, nsplit, nullptr, st);
     const long long total = (long long)B * (N + M);
     long long blocks = (total + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
     {
         ProfileScope prof("chamfer_bwd", st);
         hipLaunchKernelGGL(chamfer_bwd_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, N, y, M,
-                           B, D, idx_x, idx_y, ca, cb, gx, gy);
+                           B, D, idx_x, idx_y, c.ca, c.cb, gx, gy);
         hipLaunchKernelGGL(chamfer_bwd_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, N, y, M,
-                           B, D, idx_x, idx_y, ca, cb, gx, gy);
+                           B, D, idx_x, idx_y, c.ca, c.cb, gx, gy);
     }
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
@@ -591,12 +624,31 @@ struct SampledArgs {
     const int32_t *vf_rowptr, *vf_ent;
 };
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-// the ordered form's scratch: the adjoint's rows of both sides (published by a mesh's blocks, gathered by the last of them)
-size_t sampled_ws_bytes(int N, int M, int B) {
-    // (the tables' blobs are sized for the largest face count the ordered form takes at these draw counts: the caller need not name Fmax)
-    return al256(sizeof(float) * 3 * (size_t)N * B) + al256(sizeof(float) * 3 * (size_t)M * B) +
-           al256(sg::sg_blob_bytes(sg::kSgMaxF, N) * (size_t)B) + al256(sg::sg_blob_bytes(sg::kSgMaxF, M) * (size_t)B);
-}
+// The ordered form's scratch: the chamfer adjoint's rows of both sides, then the gather's tables of both sides (one blob per mesh), every
+// part 256-byte aligned.  ASYMMETRY, on purpose: `total` is sized for the largest face count the ordered form takes at these draw counts
+// (kSgMaxF -- the size query need not name Fmax), while the blobs are laid out with the stride of the ACTUAL Fmax, y's behind the blobs
+// x actually has.
+struct SampledWs {
+    size_t gsx, gsy, tbx, tby, total;  // byte offsets
+    static SampledWs plan(int N, int M, int B, int Fmax_x, int /*Fmax_y*/, bool want_x, bool /*want_y*/) {  // (nothing lies behind y's blobs)
+        SampledWs w{};
+        w.gsy = w.gsx + al256(sizeof(float) * 3 * (size_t)N * B);
+        w.tbx = w.gsy + al256(sizeof(float) * 3 * (size_t)M * B);
+        w.tby = w.tbx + al256(want_x ? sg::sg_blob_bytes(Fmax_x, N) * (size_t)B : 0);
+        w.total = w.tbx + al256(sg::sg_blob_bytes(sg::kSgMaxF, N) * (size_t)B) + al256(sg::sg_blob_bytes(sg::kSgMaxF, M) * (size_t)B);
+        return w;
+    }
+};
+// fx3d_chamfer_fwd_bwd's scratch: the forward's own (fx3d_chamfer_workspace_bytes, rounded up to 256), then the (N + M, B) neighbour indices
+struct FwdBwdWs {
+    size_t fwd, total;  // bytes of the forward's part = offset of the indices; bytes in all
+    static fx3d_status plan(int N, int M, int B, int D, FwdBwdWs *w) {
+        FX3D_TRY(fx3d_chamfer_workspace_bytes(N, M, B, D, &w->fwd));
+        w->fwd = al256(w->fwd);
+        w->total = w->fwd + al256(sizeof(int32_t) * (size_t)B * ((size_t)N + M));
+        return FX3D_OK;
+    }
+};
 fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, const float *y, int32_t M, int32_t B, const int32_t *idx_x,
                                      const int32_t *idx_y, float w1, float w2, float gout, int64_t B_global, const SampledArgs &ax,
                                      const SampledArgs &ay, int32_t accumulate, const sg::SgStep &step_x, void *ws, size_t ws_bytes,
@@ -611,8 +663,7 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
                  "%s: vf_rowptr and vf_ent go together", fn);
     FX3D_REQUIRE(B_global >= B, "%s: B_global < B", fn);
     hipStream_t st = as_stream(s);
-    const float ca = gout * w1 * (float)(6.0 / (3.0 * N * (double)B_global));
-    const float cb = gout * w2 * (float)(6.0 / (3.0 * M * (double)B_global));
+    const ChamferCoef c = chamfer_coef(gout, w1, w2, 3, N, M, B_global);
     const int nsplit = bg_nsplit(B, N > M ? N : M);
     FX3D_REQUIRE((long long)2 * B * nsplit < (1ll << 30), "%s: batch too large", fn);
     // Ordered form (no float atomics, bit-identical to the oracle): every requested side comes with its vertex -> face table and
@@ -641,51 +692,33 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
         // was built and measured equal inside the fit loop's graph, 104 against 105 us per iteration: the gather's tables, 7 us, do
         // overlap the rows there, but its tail -- acquire, staging, walk: ~9 us -- does not shrink; not kept: a bounded spin and a
         // dispatch-order argument for nothing.)
-        const size_t need = sampled_ws_bytes(N, M, B);
-        if (!ws || ws_bytes < need) {
-            set_error("%s: workspace too small (%zu < %zu bytes)", fn, ws ? ws_bytes : (size_t)0, need);
-            return FX3D_ERR_WORKSPACE;
-        }
-        char *w = static_cast<char *>(ws);
-        float *gsx = reinterpret_cast<float *>(w); w += al256(sizeof(float) * 3 * (size_t)N * B);
-        float *gsy = reinterpret_cast<float *>(w); w += al256(sizeof(float) * 3 * (size_t)M * B);
-        unsigned char *tbx = reinterpret_cast<unsigned char *>(w); w += al256(ax.gverts ? sg::sg_blob_bytes(ax.Fmax, N) * (size_t)B : 0);
-        unsigned char *tby = reinterpret_cast<unsigned char *>(w);
+        const SampledWs W = SampledWs::plan(N, M, B, ax.Fmax, ay.Fmax, ax.gverts != nullptr, ay.gverts != nullptr);
+        FX3D_TRY(ws_check(fn, "workspace", ws, ws_bytes, W.total));
+        unsigned char *w = static_cast<unsigned char *>(ws);
+        float *gsx = reinterpret_cast<float *>(w + W.gsx), *gsy = reinterpret_cast<float *>(w + W.gsy);
+        unsigned char *tbx = w + W.tbx, *tby = w + W.tby;
         {
-            // the rows of the requested sides + (behind them, one block per mesh and side) the gather's tables
-            SgTabJobs tj{};
-            tj.B = B;
-            size_t dyn = 0;
-            int ntab = 0;
-            if (ax.gverts) { tj.face_idx[0] = ax.face_idx; tj.blob[0] = tbx; tj.F[0] = ax.Fmax; tj.n[0] = N; dyn = std::max(dyn, sg::sg_tables_lds_bytes(ax.Fmax, N)); ntab += B; }
-            if (ay.gverts) { tj.face_idx[1] = ay.face_idx; tj.blob[1] = tby; tj.F[1] = ay.Fmax; tj.n[1] = M; dyn = std::max(dyn, sg::sg_tables_lds_bytes(ay.Fmax, M)); ntab += B; }
-            constexpr size_t kTabLds = 112 * 1024;  // beside the row blocks' 38 KB of static LDS
-            if (dyn > kTabLds) {  // (meshes of > ~20 000 faces: every gather block builds its own tables, as fx3d_sample_points_bwd's do)
-                tj = SgTabJobs{};
-                dyn = 0; ntab = 0;
+            // the rows of the requested sides + (in front of them, one block per mesh and side) the gather's tables
+            BgPassengers P{};
+            P.tj.B = B;
+            P.ride = ride;
+            if (ax.gverts) { P.tj.face_idx[0] = ax.face_idx; P.tj.blob[0] = tbx; P.tj.F[0] = ax.Fmax; P.tj.n[0] = N; P.lds = std::max(P.lds, sg::sg_tables_lds_bytes(ax.Fmax, N)); P.ntab += B; }
+            if (ay.gverts) { P.tj.face_idx[1] = ay.face_idx; P.tj.blob[1] = tby; P.tj.F[1] = ay.Fmax; P.tj.n[1] = M; P.lds = std::max(P.lds, sg::sg_tables_lds_bytes(ay.Fmax, M)); P.ntab += B; }
+            if (P.lds > kTabLds) {  // (meshes of > ~20 000 faces: every gather block builds its own tables, as fx3d_sample_points_bwd's do)
+                P.tj = SgTabJobs{};
+                P.lds = 0; P.ntab = 0;
                 tbx = tby = nullptr;
-            } else {
-                const fx3d_status arc = ensure_dynamic_lds(reinterpret_cast<const void *>(&chamfer_bwd_gather_kernel<true, true>), (int)kTabLds, "chamfer_bwd_gather_kernel");
-                if (arc != FX3D_OK) return arc;
             }
-            ProfileScope prof("chamfer_sampled_bwd", st);
-            const int sides = (ax.gverts ? 1 : 0) + (ay.gverts ? 1 : 0), npass = ntab + (ride ? ride->nadj : 0);
+            const int sides = (ax.gverts ? 1 : 0) + (ay.gverts ? 1 : 0);
             const int ns = bg_nsplit(B, sides == 2 ? (N > M ? N : M) : (ax.gverts ? N : M), sides);  // (row blocks of the requested sides only)
-            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<true, true>), dim3(npass + sides * B * ns), dim3(kBgThreads), dyn, st, x, N, y, M,
-                               3, idx_x, idx_y, ca, cb, ax.gverts ? gsx : nullptr, ay.gverts ? gsy : nullptr, ns, npass, tj, ntab,
-                               ride ? *ride : meshreg::Ride{});
-            FX3D_LAUNCH_CHECK();
+            FX3D_TRY(launch_bwd_gather(x, N, y, M, B, 3, idx_x, idx_y, c, ax.gverts ? gsx : nullptr, ay.gverts ? gsy : nullptr, ns, &P, st));
         }
-        if (ax.gverts) {
-            rc = sg::launch_sample_bwd_gather(ax.faces, ax.Vmax, ax.Fmax, B, N, ax.face_idx, ax.r1, ax.r2, gsx, ax.vf_rowptr, ax.vf_ent, ax.gverts,
-                                              accumulate, step_x, st, tbx);
-            if (rc) return rc;
-        }
-        if (ay.gverts) {
-            rc = sg::launch_sample_bwd_gather(ay.faces, ay.Vmax, ay.Fmax, B, M, ay.face_idx, ay.r1, ay.r2, gsy, ay.vf_rowptr, ay.vf_ent, ay.gverts,
-                                              accumulate, sg::SgStep{}, st, tby);
-            if (rc) return rc;
-        }
+        if (ax.gverts)
+            FX3D_TRY(sg::launch_sample_bwd_gather(ax.faces, ax.Vmax, ax.Fmax, B, N, ax.face_idx, ax.r1, ax.r2, gsx, ax.vf_rowptr, ax.vf_ent, ax.gverts,
+                                                  accumulate, step_x, st, tbx));
+        if (ay.gverts)
+            FX3D_TRY(sg::launch_sample_bwd_gather(ay.faces, ay.Vmax, ay.Fmax, B, M, ay.face_idx, ay.r1, ay.r2, gsy, ay.vf_rowptr, ay.vf_ent, ay.gverts,
+                                                  accumulate, sg::SgStep{}, st, tby));
         return FX3D_OK;
     }
     if (!accumulate) {
@@ -702,10 +735,24 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
         if (arc != FX3D_OK) return arc;
     }
     ProfileScope prof("chamfer_sampled_bwd", st);
-    hipLaunchKernelGGL(chamfer_sampled_bwd_kernel, dim3(2 * B * nsplit), dim3(kBgThreads), dyn, st, x, N, y, M, idx_x, idx_y, ca,
-                       cb, sx, sy, nsplit);
+    hipLaunchKernelGGL(chamfer_sampled_bwd_kernel, dim3(2 * B * nsplit), dim3(kBgThreads), dyn, st, x, N, y, M, idx_x, idx_y, c.ca,
+                       c.cb, sx, sy, nsplit);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
+}
+
+// fx3d_chamfer_sampled_bwd_step and _step_reg (reg: the regularisers that ride): the gradient w.r.t. mesh x alone + the optimiser step
+fx3d_status sampled_bwd_step(const char *fn, const float *x, int32_t N, const float *y, int32_t M, int32_t B, const int32_t *idx_x,
+                             const int32_t *idx_y, float w1, float w2, float gout, const int32_t *faces_x, int32_t V, int32_t F,
+                             const int32_t *face_idx_x, const float *r1_x, const float *r2_x, float *gverts_x, int32_t accumulate,
+                             const int32_t *vf_rowptr_x, const int32_t *vf_ent_x, float rho, float eta, float *vel, float *params,
+                             const float *base, float *out, uint64_t *ctr, uint64_t inc, void *ws, size_t ws_bytes,
+                             const fx3d_mesh_reg *reg, fx3d_stream_t s) {
+    FX3D_REQUIRE(vel && params && base && out && gverts_x, "%s: null pointer", fn);
+    const SampledArgs ax{faces_x, V, F, face_idx_x, r1_x, r2_x, gverts_x, vf_rowptr_x, vf_ent_x};
+    const SampledArgs ay{};
+    const sg::SgStep st{rho, eta, vel, params, base, out, reinterpret_cast<unsigned long long *>(ctr), (unsigned long long)inc};
+    return chamfer_sampled_bwd_impl(fn, x, N, y, M, B, idx_x, idx_y, w1, w2, gout, B, ax, ay, accumulate, st, ws, ws_bytes, s, reg);
 }
 }  // namespace
 
@@ -714,7 +761,7 @@ extern "C" {
 fx3d_status fx3d_chamfer_sampled_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, size_t *bytes) {
     FX3D_REQUIRE(bytes, "fx3d_chamfer_sampled_bwd_workspace_bytes: null output");
     FX3D_REQUIRE(N > 0 && M > 0 && B > 0, "fx3d_chamfer_sampled_bwd_workspace_bytes: bad sizes");
-    *bytes = sampled_ws_bytes(N, M, B);
+    *bytes = SampledWs::plan(N, M, B, sg::kSgMaxF, sg::kSgMaxF, true, true).total;
     return FX3D_OK;
 }
 
@@ -738,12 +785,8 @@ fx3d_status fx3d_chamfer_sampled_bwd_step(const float *x, int32_t N, const float
                                           float *gverts_x, int32_t accumulate, const int32_t *vf_rowptr_x, const int32_t *vf_ent_x,
                                           float rho, float eta, float *vel, float *params, const float *base, float *out,
                                           uint64_t *ctr, uint64_t inc, void *ws, size_t ws_bytes, fx3d_stream_t s) {
-    FX3D_REQUIRE(vel && params && base && out && gverts_x, "fx3d_chamfer_sampled_bwd_step: null pointer");
-    const SampledArgs ax{faces_x, V, F, face_idx_x, r1_x, r2_x, gverts_x, vf_rowptr_x, vf_ent_x};
-    const SampledArgs ay{};
-    const sg::SgStep st{rho, eta, vel, params, base, out, reinterpret_cast<unsigned long long *>(ctr), (unsigned long long)inc};
-    return chamfer_sampled_bwd_impl("fx3d_chamfer_sampled_bwd_step", x, N, y, M, B, idx_x, idx_y, w1, w2, gout, B, ax, ay, accumulate, st,
-                                    ws, ws_bytes, s);
+    return sampled_bwd_step("fx3d_chamfer_sampled_bwd_step", x, N, y, M, B, idx_x, idx_y, w1, w2, gout, faces_x, V, F, face_idx_x, r1_x, r2_x,
+                            gverts_x, accumulate, vf_rowptr_x, vf_ent_x, rho, eta, vel, params, base, out, ctr, inc, ws, ws_bytes, nullptr, s);
 }
 
 fx3d_status fx3d_chamfer_sampled_bwd_step_reg(const float *x, int32_t N, const float *y, int32_t M, int32_t B, const int32_t *idx_x,
@@ -753,17 +796,10 @@ fx3d_status fx3d_chamfer_sampled_bwd_step_reg(const float *x, int32_t N, const f
                                               float rho, float eta, float *vel, float *params, const float *base, float *out,
                                               uint64_t *ctr, uint64_t inc, void *ws, size_t ws_bytes, const fx3d_mesh_reg *reg,
                                               fx3d_stream_t s) {
-    FX3D_REQUIRE(vel && params && base && out && gverts_x && reg, "fx3d_chamfer_sampled_bwd_step_reg: null pointer");
-    const SampledArgs ax{faces_x, V, F, face_idx_x, r1_x, r2_x, gverts_x, vf_rowptr_x, vf_ent_x};
-    const SampledArgs ay{};
-    const sg::SgStep st{rho, eta, vel, params, base, out, reinterpret_cast<unsigned long long *>(ctr), (unsigned long long)inc};
-    return chamfer_sampled_bwd_impl("fx3d_chamfer_sampled_bwd_step_reg", x, N, y, M, B, idx_x, idx_y, w1, w2, gout, B, ax, ay, accumulate, st,
-                                    ws, ws_bytes, s, reg);
+    FX3D_REQUIRE(reg, "fx3d_chamfer_sampled_bwd_step_reg: null pointer");
+    return sampled_bwd_step("fx3d_chamfer_sampled_bwd_step_reg", x, N, y, M, B, idx_x, idx_y, w1, w2, gout, faces_x, V, F, face_idx_x, r1_x, r2_x,
+                            gverts_x, accumulate, vf_rowptr_x, vf_ent_x, rho, eta, vel, params, base, out, ctr, inc, ws, ws_bytes, reg, s);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 // Value AND gradient in one ABI call (the shape of `gradient(() -> chamfer_distance(A, B), ...)`, benchmarks/metrics.jl:24-38,
 // examples/fit_mesh.jl:106-110): the forward with indices and the adjoint are queued back to back on the stream, the
@@ -771,11 +807,9 @@ extern "C" {
 // leave the device idle between the launches for as long as the host needs for the second call.
 fx3d_status fx3d_chamfer_fwd_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, size_t *bytes) {
     FX3D_REQUIRE(bytes, "fx3d_chamfer_fwd_bwd_workspace_bytes: null output");
-    size_t fwd = 0;
-    const fx3d_status rc = fx3d_chamfer_workspace_bytes(N, M, B, D, &fwd);
-    if (rc) return rc;
-    fwd = (fwd + 255) & ~(size_t)255;
-    *bytes = fwd + ((sizeof(int32_t) * (size_t)B * ((size_t)N + M) + 255) & ~(size_t)255);
+    FwdBwdWs W;
+    FX3D_TRY(FwdBwdWs::plan(N, M, B, D, &W));
+    *bytes = W.total;
     return FX3D_OK;
 }
 
@@ -786,20 +820,14 @@ fx3d_status fx3d_chamfer_fwd_bwd(const float *x, int32_t N, const float *y, int3
     if (rc) return rc;
     FX3D_REQUIRE(loss_dev && gx && gy, "fx3d_chamfer_fwd_bwd: null output pointer");
     FX3D_REQUIRE(B_global >= B, "fx3d_chamfer_fwd_bwd: B_global < B");
-    size_t fwd = 0, need = 0;
-    rc = fx3d_chamfer_workspace_bytes(N, M, B, D, &fwd);
-    if (rc) return rc;
-    fx3d_chamfer_fwd_bwd_workspace_bytes(N, M, B, D, &need);
-    fwd = (fwd + 255) & ~(size_t)255;
-    if (!ws || ws_bytes < need) {
-        set_error("fx3d_chamfer_fwd_bwd: workspace too small (%zu < %zu bytes)", ws ? ws_bytes : (size_t)0, need);
-        return FX3D_ERR_WORKSPACE;
-    }
-    int32_t *ix = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + fwd);
+    FwdBwdWs W;
+    FX3D_TRY(FwdBwdWs::plan(N, M, B, D, &W));
+    FX3D_TRY(ws_check("fx3d_chamfer_fwd_bwd", "workspace", ws, ws_bytes, W.total));
+    int32_t *ix = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + W.fwd);
     int32_t *iy = ix + (size_t)B * N;
     if (idx_x) ix = idx_x;
     if (idx_y) iy = idx_y;
-    rc = chamfer_forward(x, N, y, M, B, D, nullptr, loss_dev, (long long)B_global, w1, w2, ix, iy, ws, fwd, as_stream(s),
+    rc = chamfer_forward(x, N, y, M, B, D, nullptr, loss_dev, (long long)B_global, w1, w2, ix, iy, ws, W.fwd, as_stream(s),
                          "fx3d_chamfer_fwd_bwd");
     if (rc) return rc;
     rc = fx3d_chamfer_bwd(x, N, y, M, B, D, ix, iy, w1, w2, gout, B_global, gx, gy, s);

@@ -41,7 +41,7 @@ inline hipStream_t as_stream(fx3d_stream_t s) { return reinterpret_cast<hipStrea
 // Opt a kernel in to more than 64 KiB of dynamic LDS, once per (kernel, device): the attribute is per device, and
 // a process may drive several (runtime.hip).
 // Library-owned arrival counter for a fused "last block finalises" reduction (runtime.hip): zero at hand-out, the kernel
-// returns it to zero (nn1_common.h: fused_finalize_wave0; mesh.hip).  A launch that `st` is capturing into a graph gets a
+// returns it to zero (nn1_common.h: fused_finalize_wave0; mesh_losses.hip).  A launch that `st` is capturing into a graph gets a
 // slot of its own, never reused.  nullptr + *rc on allocation failure.
 unsigned int *ticket_slot(fx3d_status *rc, hipStream_t st);
 // Words per ticket slot: the arrival counter at [0] + 16 first-level counters, one per 64-byte line (ticket_arrive_last).

@@ -1,5 +1,5 @@
 // mesh_reg.h -- device bodies of the two fit_mesh regularisers (0.1 laplacian_loss + edge_loss, /root/reference/examples/fit_mesh.jl:80-83,
-// src/metrics/mesh.jl:9-15,24-35) shared by their own launches (mesh.hip) and by the launches of the fit iteration they can ride in
+// src/metrics/mesh.jl:9-15,24-35) shared by their own launches (mesh_losses.hip) and by the launches of the fit iteration they can ride in
 // (round 6): the forward as extra blocks of the sampler's draw launch (sampler.hip), the adjoint as extra blocks of the launch that
 // forms the chamfer adjoint's rows (chamfer_bwd.hip) -- two graph nodes (~ 4.4 us each) and their kernels' time off the iteration's
 // critical path.  One source for the arithmetic: the riding blocks produce the bits of fx3d_mesh_losses / fx3d_mesh_losses_bwd.
@@ -247,7 +247,7 @@ __device__ __forceinline__ void adjoint_vertex(const float *__restrict__ verts, 
     gverts[3 * i] = o0; gverts[3 * i + 1] = o1; gverts[3 * i + 2] = o2;
 }
 
-// What rides (device view of include/flux3d_hip.h's fx3d_mesh_reg; filled by mesh.hip's mesh_reg_plan)
+// What rides (device view of include/flux3d_hip.h's fx3d_mesh_reg; filled by mesh_losses.hip's mesh_reg_plan)
 struct Ride {
     FwdArgs fwd;          // forward (draw launch); .total unused there
     float c_lap, c_edge;  // adjoint (rows launch): w_lap gout / V, w_edge gout / E
@@ -268,7 +268,7 @@ __device__ __forceinline__ void adj_block(const Ride &R, int j) {
 
 }  // namespace meshreg
 
-// host side (mesh.hip): checks an fx3d_mesh_reg and lays out its launches; fn: the caller's name for messages
+// host side (mesh_losses.hip): checks an fx3d_mesh_reg and lays out its launches; fn: the caller's name for messages
 fx3d_status mesh_reg_plan(const fx3d_mesh_reg *reg, float gout, float *gverts, int accumulate, hipStream_t st, const char *fn, meshreg::Ride *out);
 // the adjoint (+ the sum) of a planned Ride by launches of their own -- for callers whose launch cannot carry it
 fx3d_status mesh_reg_adjoint_standalone(const fx3d_mesh_reg *reg, float gout, float *gverts, int accumulate, hipStream_t st);

@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void normals_bwd_gather_kernel(const floa
 }
 
 // Grids: the vertex walks take a vertex per thread with no cap (the Laplacian adjoint's gather measured fastest that way,
-// mesh.hip: grid_for); the face kernels stop at 4096 blocks like faces_areas.  Option mesh_max_blocks != 0 caps both.
+// mesh_host.h: mesh_grid_for); the face kernels stop at 4096 blocks like faces_areas.  Option mesh_max_blocks != 0 caps both.
 int grid_vertices(long long n) {
     long long g = (n + kThreads - 1) / kThreads;
     const int cap = opt(OPT_MESH_MAX_BLOCKS);

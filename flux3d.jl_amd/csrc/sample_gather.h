@@ -410,7 +410,7 @@ __device__ __forceinline__ void sg_finish(unsigned char *lds, const SgMesh &m, c
             }
             if (ok) {
                 *reinterpret_cast<P3 *>(m.gverts + 3 * (size_t)v) = a;
-                if (st.vel) {  // fx3d_momentum_step_offset's arithmetic (mesh.hip: momentum_offset_kernel)
+                if (st.vel) {  // fx3d_momentum_step_offset's arithmetic (mesh_update.hip: momentum_offset_kernel)
                     const float g3[3] = {a.x, a.y, a.z}, v3[3] = {s_vel.x, s_vel.y, s_vel.z}, x3[3] = {s_x.x, s_x.y, s_x.z},
                                 b3[3] = {s_base.x, s_base.y, s_base.z};
                     float vn[3], xn[3], on[3];

@@ -4,7 +4,7 @@
 // (src/transforms/mesh_func.jl:21-82).  The reference loops over meshes on the host, copies each
 // probability vector D2H, builds a Distributions.Categorical alias table and draws with the
 // host RNG (:43-55).  Here the whole batch is three launches, nothing leaves the device:
-//   1. faces_areas_padded (mesh.hip)                         -- gather, HBM/L2 bound
+//   1. the face areas (in place, inside the CDF kernels)     -- gather, HBM/L2 bound
 //   2. face_cdf_kernel (one block per mesh up to 32 768 faces; five cdf_mb_* launches beyond): Float64 probabilities
 //      (:32-39, incl. the last-padded-column fix-up) and their CDF, summed in the order specified in
 //      oracle/flux3d_oracle.c (a radix-32 tree, every node left to right) so oracle and device agree bit-for-bit
@@ -13,14 +13,11 @@
 #include <cmath>
 
 #include "fx3d_common.h"
+#include "mesh_host.h"
 #include "sample_gather.h"
 #include "mesh_reg.h"
 
 using namespace fx3d;
-
-// defined in mesh.hip
-extern "C" fx3d_status fx3d_faces_areas_padded(const float *, int32_t, const int32_t *, int32_t,
-                                               const int32_t *, int32_t, float *, fx3d_stream_t);
 
 namespace {
 
@@ -539,7 +536,9 @@ __global__ __launch_bounds__(sg::kSgThreads) void sample_bwd_gather_kernel(
     sg::sg_finish(sg_lds, m, step, vb, ve);
 }
 
-int grid_for(long long n) {
+// grid of the one-sample-per-thread kernels (explicit, seeded, scatter adjoint): 256-thread blocks, at most 2048 of them.
+// (Not mesh_host.h's mesh_grid_for: no option, no reduction.)
+int sample_grid_for(long long n) {
     long long g = (n + kThreads - 1) / kThreads;
     if (g < 1) g = 1;
     if (g > 2048) g = 2048;
@@ -581,7 +580,7 @@ fx3d_status fx3d_sample_points_explicit(const float *verts_padded, int32_t Vmax,
     FX3D_REQUIRE(verts_padded && faces_padded && face_idx && r1 && r2 && out,
                  "fx3d_sample_points_explicit: null pointer");
     FX3D_REQUIRE(Vmax > 0 && Fmax > 0 && B > 0 && n > 0, "fx3d_sample_points_explicit: bad sizes");
-    hipLaunchKernelGGL(sample_explicit_kernel, dim3(grid_for((long long)B * n)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(sample_explicit_kernel, dim3(sample_grid_for((long long)B * n)), dim3(kThreads), 0,
                        as_stream(s), verts_padded, Vmax, faces_padded, Fmax, B, n, face_idx, r1, r2, out);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
@@ -621,11 +620,7 @@ int cdf_variant(int Vmax, int Fmax, size_t *lds) {
 fx3d_status cdf_check(const CdfArgs &a, const char *fn) {
     FX3D_REQUIRE(a.verts_padded && a.faces_padded && a.faces_len, "%s: null pointer", fn);
     FX3D_REQUIRE(a.Vmax > 0 && a.Fmax > 0 && a.B > 0, "%s: bad sizes", fn);
-    if (!a.ws || a.ws_bytes < ws_bytes_needed(a.Fmax, a.B)) {
-        set_error("%s: workspace too small (%zu < %zu)", fn, a.ws ? a.ws_bytes : (size_t)0, ws_bytes_needed(a.Fmax, a.B));
-        return FX3D_ERR_WORKSPACE;
-    }
-    return FX3D_OK;
+    return ws_check(fn, "workspace", a.ws, a.ws_bytes, ws_bytes_needed(a.Fmax, a.B), "");
 }
 
 // one batch, or two in ONE launch when both take the same one-block variant (`b` may be null)
@@ -685,11 +680,7 @@ struct DrawArgs {
 fx3d_status draw_check(const DrawArgs &a, const char *fn) {
     FX3D_REQUIRE(a.verts_padded && a.faces_padded && a.faces_len && a.out, "%s: null pointer", fn);
     FX3D_REQUIRE(a.Vmax > 0 && a.Fmax > 0 && a.B > 0 && a.n > 0, "%s: bad sizes", fn);
-    if (!a.cdf_ws || a.ws_bytes < ws_bytes_needed(a.Fmax, a.B)) {
-        set_error("%s: CDF workspace too small (%zu < %zu)", fn, a.cdf_ws ? a.ws_bytes : (size_t)0, ws_bytes_needed(a.Fmax, a.B));
-        return FX3D_ERR_WORKSPACE;
-    }
-    return FX3D_OK;
+    return ws_check(fn, "CDF workspace", a.cdf_ws, a.ws_bytes, ws_bytes_needed(a.Fmax, a.B), "");
 }
 DrawSide draw_side(const DrawArgs &a) {
     return DrawSide{a.verts_padded, a.faces_padded, a.faces_len, reinterpret_cast<const double *>(a.cdf_ws), a.out, a.r1_out, a.r2_out,
@@ -697,12 +688,24 @@ DrawSide draw_side(const DrawArgs &a) {
 }
 fx3d_status draw_launch(const DrawArgs &a, const DrawArgs *b, const uint64_t *seed_dev, hipStream_t st, const meshreg::FwdArgs *reg = nullptr) {
     ProfileScope prof("sample_draw", st);
-    const int g0 = grid_for((long long)a.B * a.n), g1 = b ? grid_for((long long)b->B * b->n) : 0;
+    const int g0 = sample_grid_for((long long)a.B * a.n), g1 = b ? sample_grid_for((long long)b->B * b->n) : 0;
     const int gr = reg ? reg->gV + reg->gE : 0;
     hipLaunchKernelGGL(sample_seeded_kernel, dim3(g0 + g1 + gr), dim3(kThreads), 0, st, draw_side(a), draw_side(b ? *b : a), g0, g0 + g1, seed_dev,
                        reg ? *reg : meshreg::FwdArgs{});
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
+}
+// fx3d_sample_points_draw_pair and _draw_pair_reg (with_reg: the forward of `reg`'s regularisers rides behind the draw blocks)
+fx3d_status draw_pair(const char *fn, const DrawArgs &a, const DrawArgs &b, const uint64_t *seed_dev, bool with_reg, const fx3d_mesh_reg *reg,
+                      hipStream_t st) {
+    FX3D_TRY(draw_check(a, fn));
+    FX3D_TRY(draw_check(b, fn));
+    if (!with_reg) return draw_launch(a, &b, seed_dev, st);
+    meshreg::Ride R;
+    FX3D_TRY(mesh_reg_plan(reg, 1.0f, nullptr, 0, st, fn, &R));
+    R.fwd.total = nullptr;  // (the sum needs the chamfer loss: fx3d_chamfer_sampled_bwd_step_reg writes it)
+    R.fwd.base = nullptr;
+    return draw_launch(a, &b, seed_dev, st, &R.fwd);
 }
 }  // namespace
 
@@ -741,11 +744,7 @@ fx3d_status fx3d_sample_points_draw_pair(const float *verts0, int32_t Vmax0, con
                                          const uint64_t *seed_dev, fx3d_stream_t s) {
     const DrawArgs a{verts0, faces0, faces_len0, cdf_ws0, ws_bytes0, out0, r1_out0, r2_out0, face_out0, seed0, Vmax0, Fmax0, B0, n0};
     const DrawArgs b{verts1, faces1, faces_len1, cdf_ws1, ws_bytes1, out1, r1_out1, r2_out1, face_out1, seed1, Vmax1, Fmax1, B1, n1};
-    fx3d_status rc = draw_check(a, "fx3d_sample_points_draw_pair");
-    if (rc) return rc;
-    rc = draw_check(b, "fx3d_sample_points_draw_pair");
-    if (rc) return rc;
-    return draw_launch(a, &b, seed_dev, as_stream(s));
+    return draw_pair("fx3d_sample_points_draw_pair", a, b, seed_dev, false, nullptr, as_stream(s));
 }
 
 fx3d_status fx3d_sample_points_draw_pair_reg(const float *verts0, int32_t Vmax0, const int32_t *faces0, int32_t Fmax0,
@@ -757,16 +756,7 @@ fx3d_status fx3d_sample_points_draw_pair_reg(const float *verts0, int32_t Vmax0,
                                              const uint64_t *seed_dev, const fx3d_mesh_reg *reg, fx3d_stream_t s) {
     const DrawArgs a{verts0, faces0, faces_len0, cdf_ws0, ws_bytes0, out0, r1_out0, r2_out0, face_out0, seed0, Vmax0, Fmax0, B0, n0};
     const DrawArgs b{verts1, faces1, faces_len1, cdf_ws1, ws_bytes1, out1, r1_out1, r2_out1, face_out1, seed1, Vmax1, Fmax1, B1, n1};
-    fx3d_status rc = draw_check(a, "fx3d_sample_points_draw_pair_reg");
-    if (rc) return rc;
-    rc = draw_check(b, "fx3d_sample_points_draw_pair_reg");
-    if (rc) return rc;
-    meshreg::Ride R;
-    rc = mesh_reg_plan(reg, 1.0f, nullptr, 0, as_stream(s), "fx3d_sample_points_draw_pair_reg", &R);
-    if (rc) return rc;
-    R.fwd.total = nullptr;  // (the sum needs the chamfer loss: fx3d_chamfer_sampled_bwd_step_reg writes it)
-    R.fwd.base = nullptr;
-    return draw_launch(a, &b, seed_dev, as_stream(s), &R.fwd);
+    return draw_pair("fx3d_sample_points_draw_pair_reg", a, b, seed_dev, true, reg, as_stream(s));
 }
 
 fx3d_status fx3d_sample_points_draw(const float *verts_padded, int32_t Vmax, const int32_t *faces_padded,
@@ -816,7 +806,7 @@ fx3d_status fx3d_sample_points_bwd(const int32_t *faces_padded, int32_t Vmax, in
         return sg::launch_sample_bwd_gather(faces_padded, Vmax, Fmax, B, n, face_idx, r1, r2, gout, vf_rowptr, vf_ent, gverts, accumulate,
                                             sg::SgStep{}, st);
     if (!accumulate) FX3D_HIP(hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)Vmax * B, st));
-    hipLaunchKernelGGL(sample_bwd_kernel, dim3(grid_for((long long)B * n)), dim3(kThreads), 0, st,
+    hipLaunchKernelGGL(sample_bwd_kernel, dim3(sample_grid_for((long long)B * n)), dim3(kThreads), 0, st,
                        faces_padded, Vmax, Fmax, B, n, face_idx, r1, r2, gout, gverts);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;

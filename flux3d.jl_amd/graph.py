@@ -1,8 +1,6 @@
 """k-NN graph construction for DGCNN's EdgeConv (src/models/dgcnn.jl:3-9,36)."""
 import numpy as np
 
-import ctypes as C
-
 from . import _lib
 from .device import DeviceArray, current_stream, workspace
 from .metrics import _as_dev_points
@@ -21,10 +19,9 @@ def knn(x, k, y=None, drop_first=False, return_dist=True):
         raise ValueError("DimensionMismatch between x and y")
     idx = DeviceArray.empty((k, N, B), np.int32)
     dist = DeviceArray.empty((k, N, B), np.float32) if return_dist else None
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_knn_workspace_bytes", N, M, B, D, int(k), int(bool(drop_first)), C.byref(nb))
-    if nb.value:  # feature space: statistics + fp16 image of the candidate clouds built once per cloud (pre-pass)
-        ws = workspace(nb.value, "knn")
+    nb = _lib.query_bytes("fx3d_knn_workspace_bytes", N, M, B, D, int(k), int(bool(drop_first)))
+    if nb:  # feature space: statistics + fp16 image of the candidate clouds built once per cloud (pre-pass)
+        ws = workspace(nb, "knn")
         _lib.call("fx3d_knn_ws", x.ptr, N, y.ptr, M, B, D, int(k), int(bool(drop_first)), idx.ptr,
                   dist.ptr if dist else None, ws.ptr, ws.nbytes, current_stream().handle)
     else:
@@ -81,9 +78,8 @@ def edgeconv_graph(X, K, layout="mlp", return_idx=False):
     X = _as_dev_points(X)
     F, N, B = X.shape
     lay = _LAYOUTS[layout]
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_knn_workspace_bytes", N, N, B, F, int(K), 1, C.byref(nb))
-    if nb.value:  # feature space: the search with its pre-pass (fx3d_knn_ws), then the features -- what fx3d_edgeconv_graph
+    nb = _lib.query_bytes("fx3d_knn_workspace_bytes", N, N, B, F, int(K), 1)
+    if nb:  # feature space: the search with its pre-pass (fx3d_knn_ws), then the features -- what fx3d_edgeconv_graph
         idx = knn(X, K, drop_first=True, return_dist=False)  # does in one call, minus the per-block image builds
         out = edge_features(X, idx, layout)
         return (out, idx) if return_idx else out

@@ -11,6 +11,7 @@ import numpy as np
 from . import _lib
 from .device import DeviceArray, current_stream, is_device, workspace
 from .rep import PointCloud, TriMesh
+from .sampling import sample_points_pair, sampling_adjoint_is_ordered
 
 
 def _as_dev_points(a):
@@ -28,6 +29,23 @@ def _as_dev_points(a):
     if a.ndim != 3:
         raise ValueError("points must be (D,N) or (D,N,B)")
     return DeviceArray.from_host(a)
+
+
+class _LossOut:
+    """Where a loss entry point leaves its value: the 1-element device array ``dev`` (``into``, or a fresh one) and, with ``sync``,
+    a host float the call waits for.  ``value`` is what the wrappers return: the host Float32, or ``dev`` when not synchronised."""
+
+    def __init__(self, sync, into=None):
+        self.dev = into if into is not None else DeviceArray.empty((1,), np.float32)
+        self._host = C.c_float(0) if sync else None
+
+    @property
+    def host_arg(self):
+        return C.byref(self._host) if self._host is not None else None
+
+    @property
+    def value(self):
+        return np.float32(self._host.value) if self._host is not None else self.dev
 
 
 def _check_pair(x, y):
@@ -56,24 +74,20 @@ def nearest_neighbors(x, y, return_dist=False):
 
 
 def chamfer_workspace(N, M, B, D):
-    n = C.c_size_t(0)
-    _lib.call("fx3d_chamfer_workspace_bytes", N, M, B, D, C.byref(n))
-    return workspace(n.value, "chamfer")
+    return workspace(_lib.query_bytes("fx3d_chamfer_workspace_bytes", N, M, B, D), "chamfer")
 
 
 def _chamfer_points(x, y, w1, w2, return_indices=False, loss_out=None, sync=True):
     x, y = _as_dev_points(x), _as_dev_points(y)
     D, N, M, B = _check_pair(x, y)
     ws = chamfer_workspace(N, M, B, D)
-    loss_dev = loss_out if loss_out is not None else DeviceArray.empty((1,), np.float32)
+    loss = _LossOut(sync, loss_out)
     ix = DeviceArray.empty((N, B), np.int32) if return_indices else None
     iy = DeviceArray.empty((M, B), np.int32) if return_indices else None
-    host = C.c_float(0)
-    _lib.call("fx3d_chamfer_fwd", x.ptr, N, y.ptr, M, B, D, float(w1), float(w2), loss_dev.ptr,
-              C.byref(host) if sync else None, ix.ptr if ix else None, iy.ptr if iy else None,
+    _lib.call("fx3d_chamfer_fwd", x.ptr, N, y.ptr, M, B, D, float(w1), float(w2), loss.dev.ptr,
+              loss.host_arg, ix.ptr if ix else None, iy.ptr if iy else None,
               ws.ptr, ws.nbytes, current_stream().handle)
-    loss = np.float32(host.value) if sync else loss_dev
-    return (loss, ix, iy) if return_indices else loss
+    return (loss.value, ix, iy) if return_indices else loss.value
 
 
 def chamfer_distance(A, B, num_samples=5000, w1=1.0, w2=1.0, return_indices=False, seed=None,
@@ -86,7 +100,6 @@ def chamfer_distance(A, B, num_samples=5000, w1=1.0, w2=1.0, return_indices=Fals
     if isinstance(A, TriMesh) or isinstance(B, TriMesh):
         if not (isinstance(A, TriMesh) and isinstance(B, TriMesh)):
             raise TypeError("chamfer_distance: both arguments must be TriMesh")
-        from .transforms import sample_points_pair
         s1 = None if seed is None else seed
         s2 = None if seed is None else seed + 1
         PA, PB = sample_points_pair(A, B, num_samples, seed_a=s1, seed_b=s2, reuse_cdf=reuse_cdf)  # one CDF launch, one draw launch
@@ -101,14 +114,11 @@ def chamfer_loss_pairwise_f32(A, B, idx_a, idx_b, w1=1.0, w2=1.0, sync=True):
     this); use this one where the reference's last bit matters."""
     x, y = _as_dev_points(A), _as_dev_points(B)
     D, N, M, Bn = _check_pair(x, y)
-    n = C.c_size_t(0)
-    _lib.call("fx3d_chamfer_pairwise_workspace_bytes", N, M, Bn, D, C.byref(n))
-    ws = workspace(n.value, "chamfer_pairwise")
-    loss_dev = DeviceArray.empty((1,), np.float32)
-    host = C.c_float(0)
+    ws = workspace(_lib.query_bytes("fx3d_chamfer_pairwise_workspace_bytes", N, M, Bn, D), "chamfer_pairwise")
+    loss = _LossOut(sync)
     _lib.call("fx3d_chamfer_loss_pairwise_f32", x.ptr, N, y.ptr, M, Bn, D, idx_a.ptr, idx_b.ptr, float(w1), float(w2),
-              loss_dev.ptr, C.byref(host) if sync else None, ws.ptr, ws.nbytes, current_stream().handle)
-    return np.float32(host.value) if sync else loss_dev
+              loss.dev.ptr, loss.host_arg, ws.ptr, ws.nbytes, current_stream().handle)
+    return loss.value
 
 
 def chamfer_distance_grad(A, B, idx_a, idx_b, w1=1.0, w2=1.0, gout=1.0, B_global=None):
@@ -132,27 +142,15 @@ def chamfer_value_and_grad(A, B, w1=1.0, w2=1.0, gout=1.0, B_global=None, return
     ``sync=False``."""
     x, y = _as_dev_points(A), _as_dev_points(B)
     D, N, M, Bn = _check_pair(x, y)
-    n = C.c_size_t(0)
-    _lib.call("fx3d_chamfer_fwd_bwd_workspace_bytes", N, M, Bn, D, C.byref(n))
-    ws = workspace(n.value, "chamfer_fwd_bwd")
-    loss_dev = loss_out if loss_out is not None else DeviceArray.empty((1,), np.float32)
+    ws = workspace(_lib.query_bytes("fx3d_chamfer_fwd_bwd_workspace_bytes", N, M, Bn, D), "chamfer_fwd_bwd")
+    loss = _LossOut(sync, loss_out)
     gx, gy = out if out is not None else (DeviceArray.empty(x.shape, np.float32), DeviceArray.empty(y.shape, np.float32))
     ix = DeviceArray.empty((N, Bn), np.int32) if return_indices else None
     iy = DeviceArray.empty((M, Bn), np.int32) if return_indices else None
-    host = C.c_float(0)
     _lib.call("fx3d_chamfer_fwd_bwd", x.ptr, N, y.ptr, M, Bn, D, float(w1), float(w2), float(gout), int(B_global or Bn),
-              loss_dev.ptr, C.byref(host) if sync else None, gx.ptr, gy.ptr, ix.ptr if ix else None, iy.ptr if iy else None,
+              loss.dev.ptr, loss.host_arg, gx.ptr, gy.ptr, ix.ptr if ix else None, iy.ptr if iy else None,
               ws.ptr, ws.nbytes, current_stream().handle)
-    loss = np.float32(host.value) if sync else loss_dev
-    return (loss, gx, gy, ix, iy) if return_indices else (loss, gx, gy)
-
-
-def sampling_adjoint_is_ordered(m, n):
-    """Whether the ordered (atomic-free, bit-reproducible) sampling adjoint takes meshes of this shape with ``n`` draws each
-    (fx3d_sample_points_bwd_ordered: the draws and their tables must fit one CU's LDS); otherwise the calls scatter with float atomics."""
-    f = C.c_int32(0)
-    _lib.call("fx3d_sample_points_bwd_ordered", int(m.F), int(n), C.byref(f))
-    return f.value != 0
+    return (loss.value, gx, gy, ix, iy) if return_indices else (loss.value, gx, gy)
 
 
 def chamfer_sampled_grad(A, B, idx_a, idx_b, mesh_a=None, draws_a=None, mesh_b=None, draws_b=None, w1=1.0, w2=1.0,
@@ -177,16 +175,8 @@ def chamfer_sampled_grad(A, B, idx_a, idx_b, mesh_a=None, draws_a=None, mesh_b=N
     accumulate = ((out_a is not None) or (out_b is not None)) and reg is None
     if reg is not None and step is None:
         raise ValueError("chamfer_sampled_grad(reg=...) rides with step=...")
-    def fits(m, n):
-        if m is None:
-            return True
-        f = C.c_int32(0)
-        _lib.call("fx3d_sample_points_bwd_ordered", m.F, n, C.byref(f))
-        return f.value != 0
-    ordered = bool(ordered) and fits(mesh_a, N) and fits(mesh_b, M)
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_chamfer_sampled_bwd_workspace_bytes", N, M, Bn, C.byref(nb))
-    ws = workspace(nb.value, "chamfer_sampled_bwd") if ordered else None
+    ordered = bool(ordered) and all(m is None or sampling_adjoint_is_ordered(m, n) for m, n in ((mesh_a, N), (mesh_b, M)))
+    ws = workspace(_lib.query_bytes("fx3d_chamfer_sampled_bwd_workspace_bytes", N, M, Bn), "chamfer_sampled_bwd") if ordered else None
 
     def side(m, draws, out):
         if m is None:
@@ -217,9 +207,7 @@ def chamfer_sampled_grad(A, B, idx_a, idx_b, mesh_a=None, draws_a=None, mesh_b=N
 
 
 def _mesh_ws(count):
-    n = C.c_size_t(0)
-    _lib.call("fx3d_mesh_loss_workspace_bytes", int(count), C.byref(n))
-    return workspace(n.value, "mesh")
+    return workspace(_lib.query_bytes("fx3d_mesh_loss_workspace_bytes", int(count)), "mesh")
 
 
 def laplacian_loss(m, sync=True):
@@ -227,12 +215,11 @@ def laplacian_loss(m, sync=True):
     verts = m.dev("verts_packed")
     V = verts.shape[1]
     ws = _mesh_ws(V)
-    loss_dev = DeviceArray.empty((1,), np.float32)
-    host = C.c_float(0)
+    loss = _LossOut(sync)
     _lib.call("fx3d_laplacian_loss", verts.ptr, V, m.dev("lap_rowptr").ptr, m.dev("lap_colind").ptr,
-              m.dev("lap_vals").ptr, loss_dev.ptr, C.byref(host) if sync else None, ws.ptr,
+              m.dev("lap_vals").ptr, loss.dev.ptr, loss.host_arg, ws.ptr,
               ws.nbytes, current_stream().handle)
-    return np.float32(host.value) if sync else loss_dev
+    return loss.value
 
 
 _LAP_BWD_TWO_PASS_FROM = 1 << 16
@@ -262,11 +249,10 @@ def edge_loss(m, target_length=0.0, sync=True):
     edges = m.dev("edges")
     E = edges.shape[0]
     ws = _mesh_ws(E)
-    loss_dev = DeviceArray.empty((1,), np.float32)
-    host = C.c_float(0)
-    _lib.call("fx3d_edge_loss", verts.ptr, V, edges.ptr, E, float(target_length), loss_dev.ptr,
-              C.byref(host) if sync else None, ws.ptr, ws.nbytes, current_stream().handle)
-    return np.float32(host.value) if sync else loss_dev
+    loss = _LossOut(sync)
+    _lib.call("fx3d_edge_loss", verts.ptr, V, edges.ptr, E, float(target_length), loss.dev.ptr,
+              loss.host_arg, ws.ptr, ws.nbytes, current_stream().handle)
+    return loss.value
 
 
 def edge_loss_grad(m, target_length=0.0, gout=1.0, out=None):
@@ -292,9 +278,7 @@ def _mesh_fused_ws(m, V, E, must_exist=False):
         if must_exist:
             raise ValueError("mesh_losses_grad(reuse_forward=True) needs the forward's scratch: call mesh_losses on this very "
                              "DEVICE mesh first (gpu(m)); a host mesh keeps nothing between calls")
-        n = C.c_size_t(0)
-        _lib.call("fx3d_mesh_losses_workspace_bytes", int(V), int(E), C.byref(n))
-        ws = DeviceArray.empty((n.value,), np.uint8)
+        ws = DeviceArray.empty((_lib.query_bytes("fx3d_mesh_losses_workspace_bytes", int(V), int(E)),), np.uint8)
         if m.on_device:
             m._dev["mesh_fused_ws"] = ws
     return ws

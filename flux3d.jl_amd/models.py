@@ -176,9 +176,8 @@ class PointNet(_Model):
         if intermediates:
             out.update(logits=DeviceArray.empty((nc, B), np.float32), stn=DeviceArray.empty((3, 3, B), np.float32),
                        fstn=DeviceArray.empty((64, 64, B), np.float32), pooled=DeviceArray.empty((1024, B), np.float32))
-        nb = C.c_size_t(0)
-        _lib.call("fx3d_pointnet_workspace_bytes", N, B, nc, C.byref(nb))
-        ws = workspace(nb.value, tag="pointnet")
+        nb = _lib.query_bytes("fx3d_pointnet_workspace_bytes", N, B, nc)
+        ws = workspace(nb, tag="pointnet")
         opt = [out[k].ptr if intermediates else None for k in ("logits", "stn", "fstn", "pooled")]
         _lib.call("fx3d_pointnet_forward", self._params_dev().ptr, nc, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
                   current_stream().handle)
@@ -228,9 +227,8 @@ class DGCNN(_Model):
             out.update(logits=DeviceArray.empty((nc, B), np.float32), idx1=DeviceArray.empty((K, N, B), np.int32),
                        x1=DeviceArray.empty((64, N, B), np.float32), idx2=DeviceArray.empty((K, N, B), np.int32),
                        x2=DeviceArray.empty((256, N, B), np.float32), pooled=DeviceArray.empty((1024, B), np.float32))
-        nb = C.c_size_t(0)
-        _lib.call("fx3d_dgcnn_workspace_bytes", N, B, K, nc, C.byref(nb))
-        ws = workspace(nb.value, tag="dgcnn")
+        nb = _lib.query_bytes("fx3d_dgcnn_workspace_bytes", N, B, K, nc)
+        ws = workspace(nb, tag="dgcnn")
         opt = [out[k].ptr if intermediates else None for k in ("logits", "idx1", "x1", "idx2", "x2", "pooled")]
         _lib.call("fx3d_dgcnn_forward", self._params_dev().ptr, nc, K, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
                   current_stream().handle)

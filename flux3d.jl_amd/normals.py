@@ -3,8 +3,6 @@
 The vertex normals are what the reference computes on the CPU, not what its docstring says: per corner row, the cross
 product of the LAST face that has the vertex in that row (include/flux3d_hip.h states the definition).  Every result is the
 same bits on every run: no float atomics."""
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -125,9 +123,8 @@ def compute_verts_normals_grad(m, gout, out=None, accumulate=False):
     verts, faces = m.dev("verts_packed"), m.dev("faces_packed")
     V, F = _sizes(m)
     mask = _winner_mask(m)
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_normals_workspace_bytes", V, F, C.byref(nb))
-    ws = workspace(nb.value, tag="normals")
+    nb = _lib.query_bytes("fx3d_normals_workspace_bytes", V, F)
+    ws = workspace(nb, tag="normals")
     _lib.call("fx3d_verts_normals_bwd", verts.ptr, V, faces.ptr, F, m.dev("vf_packed_rowptr").ptr, m.dev("vf_packed_ent").ptr,
               mask.ptr, gout.ptr, g.ptr, int(bool(accumulate)), ws.ptr, ws.nbytes, current_stream().handle)
     return g
@@ -139,9 +136,8 @@ def compute_faces_normals_grad(m, gout, out=None, accumulate=False):
     gout, g = _grad_args(m, gout, out, accumulate, True, "compute_faces_normals_grad")
     verts, faces = m.dev("verts_packed"), m.dev("faces_packed")
     V, F = _sizes(m)
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_normals_workspace_bytes", V, F, C.byref(nb))
-    ws = workspace(nb.value, tag="normals")
+    nb = _lib.query_bytes("fx3d_normals_workspace_bytes", V, F)
+    ws = workspace(nb, tag="normals")
     _lib.call("fx3d_faces_normals_bwd", verts.ptr, V, faces.ptr, F, m.dev("vf_packed_rowptr").ptr, m.dev("vf_packed_ent").ptr,
               gout.ptr, g.ptr, int(bool(accumulate)), ws.ptr, ws.nbytes, current_stream().handle)
     return g

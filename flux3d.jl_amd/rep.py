@@ -187,9 +187,8 @@ def index_upload(arr, index_base, clamp_pad=False, limit=0):
     out = DeviceArray.empty(a.shape, np.int32)
     if a.size == 0:
         return out
-    n = C.c_size_t(0)
-    _lib.call("fx3d_index_upload_workspace_bytes", t, int(a.size), C.byref(n))
-    ws = DeviceArray.empty((n.value,), np.uint8)
+    n = _lib.query_bytes("fx3d_index_upload_workspace_bytes", t, int(a.size))
+    ws = DeviceArray.empty((n,), np.uint8)
     bad = DeviceArray.zeros((1,), np.uint32)
     _lib.call("fx3d_index_upload", a.ctypes.data, t, int(index_base), int(a.size), int(bool(clamp_pad)), int(limit), out.ptr, bad.ptr,
               ws.ptr, ws.nbytes, current_stream().handle)

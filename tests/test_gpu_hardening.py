@@ -1385,6 +1385,36 @@ def test_chamfer_sampled_adjoint_ordered_form_is_the_oracles_chain_bit_for_bit(g
     assert np.allclose(gaa.to_host(), ea, rtol=2e-4, atol=1e-8) and np.allclose(gba.to_host(), eb, rtol=2e-4, atol=1e-8)
 
 
+@pytest.mark.parametrize("cells,faces", [(120, 28800), (118, 27848)])
+def test_chamfer_sampled_adjoint_ordered_form_when_the_tables_do_not_ride(gpu_fx, oracle, cells, faces):
+    """fx3d_chamfer_sampled_bwd, ordered form, on a mesh whose gather tables do not fit the row launch's spare blocks (more than
+    112 KiB of LDS: at 512 draws, face counts in (28108, 32460]): the table jobs are dropped and every gather block builds its own
+    tables.  28 800 faces take that route, the twin of 27 848 faces just below the limit still hands the tables over; both are
+    array_equal to the oracle's chain (oracle.chamfer_bwd, then oracle.sample_points_bwd), twice in a row and on top of a base."""
+    fx = gpu_fx
+    n = 512
+    v, f = _grid_mesh(cells, cells, 11)
+    ma = fx.gpu(fx.TriMesh([v], [f]))
+    mb = fx.gpu(fx.load_trimesh(os.path.join(GOLDEN, "sphere.obj")))
+    assert ma.F == faces and ma.V == (cells + 1) ** 2 and ma.N == 1
+    assert fx.sampling_adjoint_is_ordered(ma, n)
+    A, fa, ra1, ra2 = fx.sample_points(ma, n, seed=5, return_draws=True)
+    Bp = fx.sample_points(mb, n, seed=6)
+    _, ix, iy = fx.chamfer_distance(A, Bp, w1=0.9, w2=1.1, return_indices=True)
+    oga, _ = oracle.chamfer_bwd(A.to_host(), Bp.to_host(), ix.to_host(), iy.to_host(), 0.9, 1.1, 1.5)
+    fp0 = ma.get_faces_padded().astype(np.int64) - 1
+    ea = oracle.sample_points_bwd(fp0, ma._faces_len, ma.V, fa.to_host(), ra1.to_host(), ra2.to_host(), oga)
+    assert np.abs(ea).max() > 0
+    for _ in range(2):
+        ga, none = fx.chamfer_sampled_grad(A, Bp, ix, iy, mesh_a=ma, draws_a=(fa, ra1, ra2), w1=0.9, w2=1.1, gout=1.5)
+        assert none is None and np.array_equal(ga.to_host(), ea), np.argwhere(ga.to_host() != ea)[:5]
+    base = np.asfortranarray(np.random.default_rng(3).standard_normal(ea.shape).astype(np.float32))
+    out = fx.gpu(base.copy(order="F"))
+    fx.chamfer_sampled_grad(A, Bp, ix, iy, mesh_a=ma, draws_a=(fa, ra1, ra2), w1=0.9, w2=1.1, gout=1.5, out_a=out)
+    ea2 = oracle.sample_points_bwd(fp0, ma._faces_len, ma.V, fa.to_host(), ra1.to_host(), ra2.to_host(), oga, base=base)
+    assert np.array_equal(out.to_host(), ea2)
+
+
 @pytest.mark.parametrize("nb", [1, 3])
 def test_chamfer_sampled_adjoint_with_the_optimiser_step_in_its_launch(gpu_fx, oracle, nb):
     """fx3d_chamfer_sampled_bwd_step = fx3d_chamfer_sampled_bwd (ordered, on top of a base gradient) followed by

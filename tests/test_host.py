@@ -320,6 +320,36 @@ def test_knn_scratch_plan_without_a_gpu(fx):
         assert ws(1024, 1024, 32, 64, 20, 1) == c4p
 
 
+def test_fit_path_workspace_sizes_are_the_recorded_ones(fx):
+    """The size functions of the fit path (sampler, ordered sampling adjoint, mesh losses) are functions of the shape alone and part
+    of the ABI's behaviour: a caller that sized its scratch with an older build must not come up short.  The table
+    tests/golden/fit_path_workspace_sizes.json was recorded from the build BEFORE these layouts got one owner each (rows:
+    arguments..., status, value); it holds the boundaries: faces either side of the one-block CDF limit (32 768), draws either side
+    of 4096 and 16 384, and the ordered adjoint's limits ((5120, 5300) and (32400, 512) ordered, (5120, 9000) and (32768, 512) not;
+    28 000 and 28 800 faces at 512 draws, where the tables no longer fit the row launch's spare blocks, still ordered)."""
+    import ctypes as C
+    import json
+    from flux3d_jl_amd import _lib
+    lib = _lib.load()
+    with open(os.path.join(GOLDEN, "fit_path_workspace_sizes.json")) as f:
+        table = json.load(f)
+    assert set(table) == {"fx3d_sample_points_workspace_bytes", "fx3d_chamfer_sampled_bwd_workspace_bytes",
+                          "fx3d_mesh_loss_workspace_bytes", "fx3d_mesh_losses_workspace_bytes", "fx3d_sample_points_bwd_ordered"}
+    nrows = 0
+    for name, rows in table.items():
+        out_t = _lib.SIGNATURES[name][-1]._type_
+        for *args, status, value in rows:
+            out = out_t(0)
+            got = getattr(lib, name)(*args, C.byref(out))
+            assert (got, out.value) == (status, value), (name, args)
+            if status == 0 and out_t is C.c_size_t:
+                assert _lib.query_bytes(name, *args) == value
+            nrows += 1
+    assert 200 <= nrows <= 320
+    ordered = {(F, n): v for F, n, _, v in table["fx3d_sample_points_bwd_ordered"]}
+    assert [ordered[k] for k in ((5120, 5300), (5120, 9000), (32400, 512), (32768, 512), (28000, 512), (28800, 512))] == [1, 0, 1, 0, 1, 1]
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """VERDICT r3 #1b: `python bench.py --gpus N` with no launcher must run N ranks or FAIL -- never print a line whose n_gpus
     differs from --gpus.  On a box with fewer than N devices (this container has none) the launcher exits non-zero before any

@@ -2,7 +2,6 @@
 """Per-call device time of fx3d_sample_points_cdf (face_cdf_kernel) on the fit loop's source mesh (sphere, 5120 faces,
 B = 1) and on C3's batch (8 teapots).  With FX3D_CDF_PROBE_READ=1 and a library built with `make EXTRA=-DFX3D_CDF_PROBE`:
 block 0's phase stamps (areas | chunk totals | total | divisions | chunk prefixes | offsets + fix-up | output)."""
-import ctypes as C
 import os
 import sys
 
@@ -13,7 +12,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import flux3d_jl_amd as fx  # noqa: E402
 from flux3d_jl_amd import _lib  # noqa: E402
-from flux3d_jl_amd.transforms import _verts_padded_dev, EPS  # noqa: E402
+from flux3d_jl_amd.sampling import _verts_padded_dev, EPS  # noqa: E402
 from bench_ops import gpu_time  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -21,9 +20,8 @@ cases = {"sphere B=1": fx.gpu(fx.load_trimesh(os.path.join(GOLD, "sphere.obj")))
          "teapot B=8": fx.gpu(fx.load_trimesh(*[os.path.join(GOLD, "teapot.obj")] * 8))}
 for name, m in cases.items():
     verts, faces = _verts_padded_dev(m), m.dev("faces_padded")
-    nb = C.c_size_t(0)
-    _lib.call("fx3d_sample_points_workspace_bytes", m.F, m.N, C.byref(nb))
-    ws = fx.DeviceArray.empty((nb.value,), np.uint8)
+    nb = _lib.query_bytes("fx3d_sample_points_workspace_bytes", m.F, m.N)
+    ws = fx.DeviceArray.empty((nb,), np.uint8)
 
     def run():
         _lib.call("fx3d_sample_points_cdf", verts.ptr, m.V, faces.ptr, m.F, m.dev("faces_len").ptr, m.N, float(EPS),
