@@ -55,12 +55,7 @@ __device__ __forceinline__ void conv_mfma_fold(const float *in, int cout, const 
         const int o = sl * 32 + j;
         f32x16 acc0 = {0}, acc1 = {0};
         mfma_slab<CIN>(a0, a1, c.W + (size_t)CIN * o, h, acc0, acc1);
-        const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = sqrtf(c.bn.v[o] + kBnEps);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            rm0[s][r] = jmax(rm0[s][r], epilogue<kBnRelu>(acc0[r], bi, g, be, mu, sd));
-            rm1[s][r] = jmax(rm1[s][r], epilogue<kBnRelu>(acc1[r], bi, g, be, mu, sd));
-        }
+        fold_slab(acc0, acc1, c, o, rm0[s], rm1[s]);
     }
 }
 
@@ -76,36 +71,13 @@ __global__ __launch_bounds__(kPtThreads) void dgcnn_edgeconv_kernel(const EdgeAr
     const float *xb = a.x + (size_t)b * a.N * F;
     const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
     f32x16 rm0[NS], rm1[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rm0[s][r] = rm1[s][r] = __int_as_float(0xff800000);  // -Inf: neutral for Julia's max
-    // x_n, the first half of every edge row of point n, whatever k
-    if constexpr (F == 3) {
-        for (int i = tid; i < kTile * 3; i += kPtThreads) {
-            const int p = i / 3, c = i - 3 * p;
-            es[p * 6 + c] = p < nvalid ? xb[(size_t)(p0 + p) * 3 + c] : 0.0f;
-        }
-    } else {
-        for (int i = tid; i < kTile * F; i += kPtThreads) {
-            const int p = i / F, c = i - p * F;
-            bufA[p * kLd + c] = p < nvalid ? xb[(size_t)(p0 + p) * F + c] : 0.0f;
-        }
-    }
+    fold_init<NS>(rm0, rm1);
+    float *rows = F == 3 ? es : bufA;  // the edge rows: es[p][6] or image A's first 128 channels
+    constexpr int ldr = F == 3 ? 6 : kLd;
+    gather_centre<F>(rows, ldr, xb, F, p0, nvalid);  // x_n, the first half of every edge row of point n, whatever k
     __syncthreads();
     for (int k = 0; k < a.K; ++k) {
-        // x_idx(k, n) - x_n, the second half: one Float32 subtraction
-        for (int i = tid; i < kTile * F; i += kPtThreads) {
-            const int p = i / F, c = i - p * F;
-            float *row = F == 3 ? es + p * 6 : bufA + p * kLd;
-            float v = 0.0f;
-            if (p < nvalid) {
-                int jn = ib[(size_t)p * a.K + k];
-                jn = (unsigned int)jn < (unsigned int)a.N ? jn : p0 + p;  // (the search returns valid indices only)
-                v = xb[(size_t)jn * F + c] - row[c];
-            }
-            row[F + c] = v;
-        }
+        gather_diff<F>(rows, ldr, xb, ib, F, a.N, a.K, k, p0, nvalid);  // x_idx(k, n) - x_n, the second half
         __syncthreads();
         if constexpr (F == 3) {
             for (int i = tid; i < kTile * 32; i += kPtThreads) {
@@ -128,20 +100,7 @@ __global__ __launch_bounds__(kPtThreads) void dgcnn_edgeconv_kernel(const EdgeAr
         // the next k's writes: es / image A's second half were last read before the barrier above; image B is written again only
         // after the barrier that follows the next gather, which a wave reaches after its fold
     }
-    const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, j = lane & 31;
-    float *ob = a.out + ((size_t)b * a.N + p0) * COUT;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int sl = wave + s * (kPtThreads / 64);
-        if (sl >= COUT / 32) break;
-        const int o = sl * 32 + j;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int p = mfma_row(r, h);
-            if (p < nvalid) ob[(size_t)p * COUT + o] = rm0[s][r];
-            if (p + 32 < nvalid) ob[(size_t)(p + 32) * COUT + o] = rm1[s][r];
-        }
-    }
+    fold_store<NS>(a.out + ((size_t)b * a.N + p0) * COUT, COUT, nvalid, rm0, rm1);
 }
 
 __global__ __launch_bounds__(kPtThreads) void dgcnn_conv3_kernel(const float *__restrict__ x2, const Conv c, float *__restrict__ tmax_all,

@@ -1,0 +1,303 @@
+// EdgeConv(layers, K) as a layer in its own right (gfx950): (m::EdgeConv)(X) of src/models/dgcnn.jl:11-71 in test mode, Float32,
+// forward only, for layer widths chosen at run time.  include/flux3d_hip.h ("EdgeConv inference") states the layer, the
+// arithmetic and the parameter layout; this file is how they are computed.  The design is dgcnn.hip's EdgeConv kernel with the
+// widths as arguments: the arithmetic is the same contract (mlp_common.h), so EdgeConv([3, 32, 64, 64], K) and
+// EdgeConv([64, 128, 256], K) give DGCNN's x1 and x2 bit for bit.
+//
+// Per call: the neighbour search (fx3d_knn_ws on the cloud's own F-dimensional rows, rank 0 dropped) unless the caller gives
+// the lists, then edgeconv_kernel<NS, LD>: one block = 64 points of one cloud, 4 waves, looping over the neighbour rank k.
+//   LDS: up to three 64-row images of one row stride LD = 66 / 130 / 258 (the smallest that holds the widest layer INPUT;
+//     LD mod 64 = 2 is the bank pattern kLd documents; a template parameter, so that an LDS address is a register plus an
+//     immediate): `rows` holds the edge rows [x_n, x_idx(k,n) - x_n], img0 and img1 take the hidden layers in turn
+//     (rows -> img0 -> img1 -> img0).  L = 1 needs `rows` alone, L = 2 rows and img0.  Three images of stride 258 (198 KB)
+//     do not fit the CU's 160 KB (two are 132 KB): then img1 IS `rows`, and the x_n half, otherwise gathered once before the
+//     loop, is gathered again with every k (EdgeConvArgs::shared_rows).
+//   Per k: gather the second half of the rows; every hidden layer from image to image (conv_rt: the MFMA over the first
+//     4 floor(Cin / 4) input channels, v_fma_f32 on the accumulator for the rest, mfma_slab_rt); the LAST layer is never stored
+//     but folded into a running Julia max per (point, channel) in registers (fold_slab): a lane owns one channel and 16 points per
+//     32-point half, a wave the slabs wave, wave + 4 of 32 channels.  NS = 1 up to 128 output channels, NS = 2 (64 VGPRs
+//     of maxima) up to 256.  A layer of up to 64 channels has two slabs at most: there a wave takes one HALF of one slab, so
+//     that no wave idles (split_halves).
+//   An output width that is no multiple of 32 leaves the last slab partial: its lanes beyond the width read the parameters of
+//     the last channel (inside the buffer), run the wave's MFMAs with them and write nothing.
+//   Rows beyond the cloud's last point are zeros: computed, never written.  After the last k, plain stores (fold_store).
+#include "mlp_common.h"
+
+using namespace fx3d;
+using namespace fx3d::mlp;
+
+namespace {
+
+constexpr int kMaxLayers = 4;     // conv_bn_blocks of one EdgeConv
+constexpr int kMaxF = 128;        // input features: an edge row has 2 F channels, one image row of stride 258 at most
+constexpr int kMaxWidth = 256;    // 8 slabs of 32 channels = 2 per wave = 64 VGPRs of running maxima per lane
+constexpr int kMaxN = 36864;      // the neighbour search's general kernel holds a query's N distance keys in LDS
+constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // two images of the widest stride: 132 KB of the CU's 160 KB
+
+struct EdgeConvArgs {
+    const float *x;      // (F, N, B)
+    const int32_t *idx;  // (K, N, B), 0-based
+    float *out;          // (cL, N, B)
+    Conv c[kMaxLayers];
+    int w[kMaxLayers + 1];  // F, c1, ..., cL
+    int nl, cout;           // L, cL
+    int N, K;
+    int img0, img1;         // offsets of the two hidden images from `rows` (floats)
+    int shared_rows;        // img1 is `rows`: the x_n half is gathered with every k
+};
+
+// Who computes what of a layer of `cout` channels.  Beyond 64 channels a wave owns the slabs wave, wave + 4, ... of 32 channels
+// for both 32-point halves of the tile (one weight load feeds four MFMAs).  Up to 64 channels there are two slabs at most, and
+// two of the four waves would idle: there a wave owns ONE half of one slab -- slab wave / 2, half wave % 2.
+__device__ __forceinline__ bool split_halves(int cout) { return cout <= 64; }
+
+// one slab (NH = 2) or one half of it (NH = 1, half `half`) of a hidden layer:
+// out[p][o] = relu(BN(sum_c in[p][c] W[c + cin o] + b[o])) for o < cout
+template <int LD, int NH>
+__device__ __forceinline__ void conv_item(const float *in, float *out, int cin, int cout, const Conv &c, int sl, int half) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+    const int o = sl * 32 + j, oc = min(o, cout - 1);  // oc: what a lane beyond a partial slab reads
+    f32x16 acc[NH];
+#pragma unroll
+    for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
+    mfma_slab_rt<LD, NH>(in + half * 32 * LD, c.W + (size_t)cin * oc, cin, h, j, acc);
+    const float bi = c.b[oc], g = c.bn.g[oc], be = c.bn.b[oc], mu = c.bn.m[oc], sd = sqrtf(c.bn.v[oc] + kBnEps);
+    if (o < cout) {
+        float *ob = out + (half * 32) * LD + o;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int t = 0; t < NH; ++t) ob[(t * 32 + mfma_row(r, h)) * LD] = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd);
+    }
+}
+
+// one hidden layer, from image to image, for the tile's 64 points
+template <int LD>
+__device__ __forceinline__ void conv_rt(const float *in, float *out, int cin, int cout, const Conv &c) {
+    const int wave = threadIdx.x >> 6;
+    if (split_halves(cout)) {
+        if ((wave >> 1) * 32 < cout) conv_item<LD, 1>(in, out, cin, cout, c, wave >> 1, wave & 1);
+    } else {
+        for (int sl = wave; sl * 32 < cout; sl += kPtThreads / 64) conv_item<LD, 2>(in, out, cin, cout, c, sl, 0);
+    }
+}
+
+// the last layer for the current k, folded into the wave's running maxima (split_halves: into rm0[0] alone)
+template <int NS, int LD>
+__device__ __forceinline__ void conv_rt_fold(const float *in, int cin, int cout, const Conv &c, f32x16 (&rm0)[NS],
+                                             f32x16 (&rm1)[NS]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    if (NS == 1 && split_halves(cout)) {
+        if ((wave >> 1) * 32 >= cout) return;
+        const int oc = min((wave >> 1) * 32 + j, cout - 1);  // (a lane beyond a partial slab folds the last channel; never stored)
+        f32x16 acc[1] = {f32x16{0}};
+        mfma_slab_rt<LD, 1>(in + (wave & 1) * 32 * LD, c.W + (size_t)cin * oc, cin, h, j, acc);
+        fold_half(acc[0], c, oc, rm0[0]);
+        return;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int sl = wave + s * (kPtThreads / 64);
+        if (sl * 32 >= cout) break;  // wave-uniform
+        const int oc = min(sl * 32 + j, cout - 1);
+        f32x16 acc[2] = {f32x16{0}, f32x16{0}};
+        mfma_slab_rt<LD, 2>(in, c.W + (size_t)cin * oc, cin, h, j, acc);
+        fold_slab(acc[0], acc[1], c, oc, rm0[s], rm1[s]);
+    }
+}
+
+// fold_store for split_halves: the wave's half of its slab
+__device__ __forceinline__ void fold_store_half(float *ob, int cout, int nvalid, const f32x16 &rm) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const int o = (wave >> 1) * 32 + j;
+    if (o >= cout) return;  // a wave without a slab, the lanes beyond a partial slab
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int p = (wave & 1) * 32 + mfma_row(r, h);
+        if (p < nvalid) ob[(size_t)p * cout + o] = rm[r];
+    }
+}
+
+template <int NS, int LD>
+__global__ __launch_bounds__(kPtThreads) void edgeconv_kernel(const EdgeConvArgs a) {
+    extern __shared__ float lds[];
+    float *rows = lds, *img0 = lds + a.img0, *img1 = lds + a.img1;
+    const int tile = blockIdx.x, b = blockIdx.y;
+    const int p0 = tile * kTile;
+    const int nvalid = min(kTile, a.N - p0);
+    const int F = a.w[0], L = a.nl, cout = a.cout;
+    const float *xb = a.x + (size_t)b * a.N * F;
+    const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
+    f32x16 rm0[NS], rm1[NS];
+    fold_init<NS>(rm0, rm1);
+    if (!a.shared_rows) gather_centre<0>(rows, LD, xb, F, p0, nvalid);
+    __syncthreads();
+    for (int k = 0; k < a.K; ++k) {
+        if (a.shared_rows) gather_centre<0>(rows, LD, xb, F, p0, nvalid);  // (gather_diff reads what the same thread wrote)
+        gather_diff<0>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
+        __syncthreads();
+        // the layers: one copy of the code, its layer picked by wave-uniform selects among the kernel arguments (a constant
+        // index in every access, so that a.c[] and a.w[] stay in scalar registers)
+        const float *src = rows;
+        float *dst = img0;
+        int cin = 2 * F;
+        for (int i = 0; i + 1 < L; ++i) {
+            const Conv c = i == 0 ? a.c[0] : i == 1 ? a.c[1] : a.c[2];
+            const int co = i == 0 ? a.w[1] : i == 1 ? a.w[2] : a.w[3];
+            conv_rt<LD>(src, dst, cin, co, c);
+            __syncthreads();
+            src = dst;
+            dst = i == 0 ? img1 : img0;
+            cin = co;
+        }
+        conv_rt_fold<NS, LD>(src, cin, cout, L == 1 ? a.c[0] : L == 2 ? a.c[1] : L == 3 ? a.c[2] : a.c[3], rm0, rm1);
+        // The next k's writes.  `rows` was last read by the first layer, before a barrier above -- unless the fold itself read it
+        // (L = 1) or img1, which the fold of L = 3 read, is `rows`: then the waves meet here first.  img0 / img1 are written
+        // again only after the barrier that follows the next gather, which a wave reaches after its fold.
+        if (L == 1 || (L == 3 && a.shared_rows)) __syncthreads();
+    }
+    float *ob = a.out + ((size_t)b * a.N + p0) * cout;
+    if (NS == 1 && split_halves(cout)) fold_store_half(ob, cout, nvalid, rm0[0]);
+    else fold_store<NS>(ob, cout, nvalid, rm0, rm1);
+}
+
+// ---- the host side -------------------------------------------------------------------------------------------------
+fx3d_status check_layers(const char *fn, const int32_t *layers, int32_t nlayers) {
+    FX3D_REQUIRE(layers != nullptr, "%s: layers is NULL", fn);
+    if (nlayers < 2 || nlayers > kMaxLayers + 1) {
+        set_error("%s: layers must hold F and 1 to %d widths, got %d entries", fn, kMaxLayers, nlayers);
+        return FX3D_ERR_UNSUPPORTED;
+    }
+    if (layers[0] < 1 || layers[0] > kMaxF) {
+        set_error("%s: layers[0] = F must be in [1, %d] (an edge row has 2 F channels), got %d", fn, kMaxF, layers[0]);
+        return FX3D_ERR_UNSUPPORTED;
+    }
+    for (int i = 1; i < nlayers; ++i)
+        if (layers[i] < 1 || layers[i] > kMaxWidth) {
+            set_error("%s: layers[%d] must be in [1, %d], got %d", fn, i, kMaxWidth, layers[i]);
+            return FX3D_ERR_UNSUPPORTED;
+        }
+    return FX3D_OK;
+}
+
+fx3d_status check_sizes(const char *fn, int32_t N, int32_t B, int32_t K) {
+    FX3D_REQUIRE(N >= 1 && B >= 1, "%s: N and B must be positive, got N=%d B=%d", fn, N, B);
+    FX3D_REQUIRE(K >= 1, "%s: K must be positive, got %d", fn, K);
+    FX3D_REQUIRE((long long)K + 1 <= N, "%s: K + 1 = %lld neighbours (the point itself is dropped) of N = %d points", fn, (long long)K + 1, N);
+    FX3D_REQUIRE(N <= kMaxN, "%s: N must be at most %d (the neighbour search), got %d", fn, kMaxN, N);
+    FX3D_REQUIRE(B <= 65535, "%s: B must be at most 65535, got %d", fn, B);
+    FX3D_REQUIRE((long long)N * B * K <= (1ll << 31), "%s: N * B * K must be at most 2^31, got %lld", fn, (long long)N * B * K);
+    return FX3D_OK;
+}
+
+// the flat parameter buffer: per block conv W (Cin, Cout), b, then BatchNorm gamma, beta, mu, var
+long long layout(const float *params, const int32_t *layers, int nlayers, Conv *c) {
+    Cursor cur{params, 0};
+    for (int i = 1; i < nlayers; ++i) {
+        Conv v = cur.conv(i == 1 ? 2 * layers[0] : layers[i - 1], layers[i]);
+        v.bn = cur.bn(layers[i]);
+        if (c) c[i - 1] = v;
+    }
+    return cur.at;
+}
+
+// the LDS images: one stride for all, from the widest layer input
+void lds_plan(const int32_t *layers, int nlayers, EdgeConvArgs *a, int *ld, size_t *bytes) {
+    int widest = 2 * layers[0];
+    for (int i = 1; i + 1 < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
+    *ld = widest <= 64 ? 66 : widest <= 128 ? kLd : 258;
+    const int L = nlayers - 1, image = kTile * *ld;
+    int nimg = L >= 3 ? 3 : L;
+    a->shared_rows = (size_t)nimg * image * sizeof(float) > kMaxLds;
+    if (a->shared_rows) nimg = 2;
+    a->img0 = L >= 2 ? image : 0;
+    a->img1 = L >= 3 && !a->shared_rows ? 2 * image : 0;
+    *bytes = (size_t)nimg * image * sizeof(float);
+}
+
+// the workspace: the neighbour lists (K, N, B) | the neighbour search's scratch
+struct WsPlan { size_t idx, knn, knn_bytes, total; };
+fx3d_status ws_plan(int F, int N, int B, int K, WsPlan *w) {
+    size_t at = 0;
+    auto put = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+    w->idx = put((size_t)K * N * B * sizeof(int32_t));
+    const fx3d_status rc = fx3d_knn_workspace_bytes(N, N, B, F, K, 1, &w->knn_bytes);
+    if (rc != FX3D_OK) return rc;
+    w->knn = put(w->knn_bytes);
+    w->total = at;
+    return FX3D_OK;
+}
+
+template <int NS, int LD>
+fx3d_status launch(const EdgeConvArgs &a, size_t lds_bytes, int B, hipStream_t st) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&edgeconv_kernel<NS, LD>), (int)kMaxLds, "edgeconv_kernel");
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof("edgeconv", st);
+    hipLaunchKernelGGL((edgeconv_kernel<NS, LD>), dim3((a.N + kTile - 1) / kTile, B), dim3(kPtThreads), lds_bytes, st, a);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+fx3d_status fx3d_edgeconv_param_count(const int32_t *layers, int32_t nlayers, int64_t *count) {
+    const char *fn = "fx3d_edgeconv_param_count";
+    FX3D_REQUIRE(count != nullptr, "%s: count is NULL", fn);
+    const fx3d_status rc = check_layers(fn, layers, nlayers);
+    if (rc != FX3D_OK) return rc;
+    *count = layout(nullptr, layers, nlayers, nullptr);
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_edgeconv_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B, size_t *bytes) {
+    const char *fn = "fx3d_edgeconv_workspace_bytes";
+    FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
+    fx3d_status rc = check_layers(fn, layers, nlayers);
+    if (rc != FX3D_OK) return rc;
+    if ((rc = check_sizes(fn, N, B, K)) != FX3D_OK) return rc;
+    WsPlan w;
+    if ((rc = ws_plan(layers[0], N, B, K, &w)) != FX3D_OK) return rc;
+    *bytes = w.total;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
+                                  int32_t N, int32_t B, const int32_t *idx_in, float *out, int32_t *idx_out, void *ws,
+                                  size_t ws_bytes, fx3d_stream_t s) {
+    const char *fn = "fx3d_edgeconv_forward";
+    FX3D_REQUIRE(params_dev && x && out && ws, "%s: params_dev, x, out and ws must not be NULL", fn);
+    fx3d_status r = check_layers(fn, layers, nlayers);
+    if (r != FX3D_OK) return r;
+    if ((r = check_sizes(fn, N, B, K)) != FX3D_OK) return r;
+    WsPlan w;
+    if ((r = ws_plan(layers[0], N, B, K, &w)) != FX3D_OK) return r;
+    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_edgeconv_workspace_bytes says %zu", fn, ws_bytes, w.total);
+    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
+    EdgeConvArgs a{};
+    layout(params_dev, layers, nlayers, a.c);
+    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
+    a.nl = nlayers - 1; a.cout = layers[nlayers - 1];
+    a.N = N; a.K = K; a.x = x; a.out = out;
+    size_t lds_bytes = 0;
+    int ld = 0;
+    lds_plan(layers, nlayers, &a, &ld, &lds_bytes);
+    char *wsb = static_cast<char *>(ws);
+    if (idx_in) {
+        a.idx = idx_in;
+    } else {
+        int32_t *idx = idx_out ? idx_out : reinterpret_cast<int32_t *>(wsb + w.idx);
+        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, idx, nullptr, w.knn_bytes ? wsb + w.knn : nullptr, w.knn_bytes, s)) != FX3D_OK) return r;
+        a.idx = idx;
+    }
+    hipStream_t st = as_stream(s);
+    const bool wide = layers[nlayers - 1] > 128;  // two slabs of running maxima per wave
+    switch (ld) {
+        case 66: return wide ? launch<2, 66>(a, lds_bytes, B, st) : launch<1, 66>(a, lds_bytes, B, st);
+        case kLd: return wide ? launch<2, kLd>(a, lds_bytes, B, st) : launch<1, kLd>(a, lds_bytes, B, st);
+        default: return wide ? launch<2, 258>(a, lds_bytes, B, st) : launch<1, 258>(a, lds_bytes, B, st);
+    }
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// What the model units (pointnet.hip, dgcnn.hip) share: the exact-Float32 contraction on the f32 MFMA, the activation and
-// BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, and the walk over the flat parameter buffer.
+// What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip) share: the exact-Float32 contraction on the f32 MFMA, the
+// activation and BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, the EdgeConv kernels' gather of
+// the edge rows and fold of the last layer, and the walk over the flat parameter buffer.
 // include/flux3d_hip.h ("PointNet inference") states the arithmetic; pointnet.hip's header comment the tile and its LDS banks.
 #pragma once
 #include <cmath>
@@ -60,6 +61,36 @@ __device__ __forceinline__ void mfma_slab(const float *a0, const float *a1, cons
 // the accumulator's row r of a lane in half-wave h: the point within its 32-point half
 __device__ __forceinline__ int mfma_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// mfma_slab for a width known at run time only, on NH = 2 or 1 of the image's 32-point halves; `in`: row 0 of the first of
+// them, row stride LD (a constant: every LDS address of the lane is one register plus an immediate offset); j, h: the lane
+// within its half-wave and the half-wave.  The MFMA walks the first 4 floor(cin / 4) channels; the same chain then goes on,
+// channel by channel, as v_fma_f32 on the accumulator's elements (the rows of mfma_row): cin needs no padding, and a
+// contraction is never padded with zero channels (0 * Inf is NaN; pointnet.hip's header comment).  cin < 4 is v_fma_f32 alone.
+template <int LD, int NH>
+__device__ __forceinline__ void mfma_slab_rt(const float *in, const float *__restrict__ wrow, int cin, int h, int j,
+                                             f32x16 (&acc)[NH]) {
+    const float *a = in + j * LD + h;
+    const int c4 = cin & ~3;
+#pragma unroll 4
+    for (int c = 0; c < c4; c += 4) {
+        const W4 w = *reinterpret_cast<const W4 *>(wrow + c);
+        const float b0 = h ? w.y : w.x, b1 = h ? w.w : w.z;
+#pragma unroll
+        for (int t = 0; t < NH; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t * 32 * LD + c], b0, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NH; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t * 32 * LD + c + 2], b1, acc[t], 0, 0, 0);
+    }
+    const float *t0 = in + 4 * h * LD;  // row mfma_row(r, h) is 4 h + mfma_row(r, 0)
+#pragma unroll 1
+    for (int c = c4; c < cin; ++c) {
+        const float w = wrow[c];
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int t = 0; t < NH; ++t) acc[t][r] = fmaf(t0[(t * 32 + mfma_row(r, 0)) * LD + c], w, acc[t][r]);
+    }
+}
+
 // out[p][o] = epilogue(sum_c in[p][c] W[c + CIN o]) for the 64 points of the tile and o < cout (a multiple of 32), on the
 // f32 MFMA.  FINAL: nothing is stored; tmax[o] = max over the tile's first `nvalid` points.  All 4 waves call it.
 // LD: the row stride of both images (LD mod 64 = 2 keeps the bank pattern of kLd).
@@ -109,6 +140,84 @@ __device__ __forceinline__ void conv3(const float *xs, float *out, int ld, int c
         acc = fmaf(xs[p * 3 + 2], W[3 * o + 2], acc);
         if (EPI == kNone) out[p * ld + o] = acc;
         else out[p * ld + o] = epilogue<EPI>(acc, bias[o], bn.g[o], bn.b[o], bn.m[o], sqrtf(bn.v[o] + kBnEps));
+    }
+}
+
+// ---- what the EdgeConv kernels (dgcnn.hip, edgeconv.hip) share -----------------------------------------------------------
+// The edge rows [x_n (F), x_idx(k,n) - x_n (F)] of the tile's 64 points in `rows` (row stride ld).  xb: the cloud (F, N);
+// ib: the neighbour lists of the tile's points (K each); p0: the tile's first point.  gather_centre writes the x_n half, which
+// does not depend on k; gather_diff the other half for rank k, one Float32 subtraction from the x_n the row holds.  A thread
+// owns the same (point, channel) pairs in both: element i = p F + c for i = tid, tid + 256, ...  FC: F where it is a
+// constant (p = i / F is then a shift or a multiplication), 0 where it is the argument f: there p comes from one Float32
+// multiplication, exact for i < 2^13 and F <= 128 ((i + 1/2) / F is at least 1 / 256 away from every integer, the product's
+// error below 1e-5).  An index outside [0, N) reads the point itself; rows beyond the cloud's last point are zeros.
+template <int FC>
+__device__ __forceinline__ int edge_row_of(int i, float rf) { return FC ? i / (FC ? FC : 1) : (int)(((float)i + 0.5f) * rf); }
+template <int FC>
+__device__ __forceinline__ void gather_centre(float *rows, int ld, const float *xb, int f, int p0, int nvalid) {
+    const int F = FC ? FC : f;
+    const float rf = 1.0f / (float)F;
+    for (int i = threadIdx.x; i < kTile * F; i += kPtThreads) {
+        const int p = edge_row_of<FC>(i, rf), c = i - p * F;
+        rows[p * ld + c] = p < nvalid ? xb[(size_t)(p0 + p) * F + c] : 0.0f;
+    }
+}
+template <int FC>
+__device__ __forceinline__ void gather_diff(float *rows, int ld, const float *xb, const int32_t *ib, int f, int N, int K, int k,
+                                            int p0, int nvalid) {
+    const int F = FC ? FC : f;
+    const float rf = 1.0f / (float)F;
+    for (int i = threadIdx.x; i < kTile * F; i += kPtThreads) {
+        const int p = edge_row_of<FC>(i, rf), c = i - p * F;
+        float *row = rows + p * ld;
+        float v = 0.0f;
+        if (p < nvalid) {
+            int jn = ib[(size_t)p * K + k];
+            jn = (unsigned int)jn < (unsigned int)N ? jn : p0 + p;  // (the search returns valid indices only)
+            v = xb[(size_t)jn * F + c] - row[c];
+        }
+        row[F + c] = v;
+    }
+}
+
+// The last layer of an EdgeConv, never stored: its slab of channel o for the current k folded into the running Julia max per
+// (point, channel) that the lane keeps in registers: rm[r] = jmax(rm[r], relu(BN(acc[r] + b))).  fold_half: one 32-point half.
+__device__ __forceinline__ void fold_half(const f32x16 &acc, const Conv &c, int o, f32x16 &rm) {
+    const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = sqrtf(c.bn.v[o] + kBnEps);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rm[r] = jmax(rm[r], epilogue<kBnRelu>(acc[r], bi, g, be, mu, sd));
+}
+__device__ __forceinline__ void fold_slab(const f32x16 &acc0, const f32x16 &acc1, const Conv &c, int o, f32x16 &rm0, f32x16 &rm1) {
+    const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = sqrtf(c.bn.v[o] + kBnEps);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        rm0[r] = jmax(rm0[r], epilogue<kBnRelu>(acc0[r], bi, g, be, mu, sd));
+        rm1[r] = jmax(rm1[r], epilogue<kBnRelu>(acc1[r], bi, g, be, mu, sd));
+    }
+}
+template <int NS>
+__device__ __forceinline__ void fold_init(f32x16 (&rm0)[NS], f32x16 (&rm1)[NS]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rm0[s][r] = rm1[s][r] = __int_as_float(0xff800000);  // -Inf: neutral for Julia's max
+}
+// After the last k: the tile's (cout, 64) part of the (cout, N, B) output with plain stores.  A wave owns the slabs wave,
+// wave + 4, ... of 32 channels (NS of them at most); ob: the output row of the tile's first point.
+template <int NS>
+__device__ __forceinline__ void fold_store(float *ob, int cout, int nvalid, const f32x16 (&rm0)[NS], const f32x16 (&rm1)[NS]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int o = (wave + s * (kPtThreads / 64)) * 32 + j;
+        if (o - j >= cout) break;  // wave-uniform
+        if (o >= cout) continue;   // the lanes beyond a partial slab
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int p = mfma_row(r, h);
+            if (p < nvalid) ob[(size_t)p * cout + o] = rm0[s][r];
+            if (p + 32 < nvalid) ob[(size_t)(p + 32) * cout + o] = rm1[s][r];
+        }
     }
 }
 

@@ -29,7 +29,7 @@ import ..Flux3D: chamfer_distance, _chamfer_distance, _nearest_neighbors, sample
                  compute_verts_normals_packed, compute_faces_normals_packed,
                  _list_to_packed, _list_to_padded, _packed_to_padded, _packed_to_list,
                  _padded_to_list, _padded_to_packed, offset!, trimesh_to_voxel,
-                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!, PointNet, DGCNN
+                 voxel_to_trimesh, VoxelGrid, normalize!, scale!, rotate!, realign!, translate!, PointNet, DGCNN, EdgeConv
 using SparseArrays: SparseMatrixCSC, findnz
 import Zygote
 
@@ -1578,6 +1578,47 @@ function dgcnn_forward(m::DGCNN, X::HipArray{Float32,3}; intermediates::Bool = f
     return intermediates ? (probs = probs, logits = logits, idx1 = idx1, x1 = x1, idx2 = idx2, x2 = x2, pooled = pooled) : probs
 end
 (m::DGCNN)(X::HipArray{Float32,3}) = dgcnn_forward(m, X)
+
+# ---- EdgeConv inference: (m::EdgeConv)(X) (src/models/dgcnn.jl:11-71) in test mode, any layer widths -----------------------
+# EdgeConv(layers, K) as a layer in its own right (include/flux3d_hip.h "EdgeConv inference"): m.layers = [F, c1, ..., cL] goes
+# to the library as it is, the conv_bn_blocks of m.mlp are flattened as for DGCNN.  The search, the edge rows and the maximum
+# over k run inside the library.  idx: (K, N, B) Int32 0-based neighbour lists to use instead of the search (an index outside
+# [0, N) reads the point itself); return_idx: also return the lists that were used.
+function edgeconv_params(m::EdgeConv)
+    out = Float32[]
+    for blk in m.mlp.layers
+        _flat_block!(out, blk)
+    end
+    return out
+end
+function edgeconv_forward(m::EdgeConv, X::HipArray{Float32,3}; idx::Union{Nothing,HipArray{Int32,3}} = nothing, return_idx::Bool = false)
+    layers = Int32.(collect(m.layers))
+    nl = length(layers)
+    F, N, B = size(X)
+    K = m.K
+    F == layers[1] || error("EdgeConv($(m.layers), $K) takes $(layers[1]) channels per point, got $F")
+    (N >= 1 && B >= 1) || error("EdgeConv needs at least one point and one cloud")
+    (1 <= K && K + 1 <= N) || error("EdgeConv needs 1 <= K <= N - 1, got K = $K, N = $N")
+    idx === nothing || size(idx) == (K, N, B) || error("idx must be ($K, $N, $B), got $(size(idx))")
+    params = edgeconv_params(m)
+    cnt = Ref{Int64}(0)
+    check(@ccall LIB.fx3d_edgeconv_param_count(layers::Ptr{Int32}, Int32(nl)::Int32, cnt::Ref{Int64})::Int32)
+    length(params) == cnt[] || error("EdgeConv has $(length(params)) parameters, the library expects $(cnt[])")
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_edgeconv_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
+                                                   Int32(B)::Int32, nb::Ref{Csize_t})::Int32)
+    pd = hip(params)
+    ws = workspace(nb[])
+    out = HipArray{Float32}(undef, Int(layers[end]), N, B)
+    found = (return_idx && idx === nothing) ? HipArray{Int32}(undef, K, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_edgeconv_forward(pd.ptr::Ptr{Cvoid}, layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32,
+                                           X.ptr::Ptr{Cvoid}, Int32(N)::Int32, Int32(B)::Int32, opt(idx)::Ptr{Cvoid},
+                                           out.ptr::Ptr{Cvoid}, opt(found)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                           DEFAULT_STREAM::Stream)::Int32)
+    return return_idx ? (out, idx === nothing ? found : idx) : out
+end
+(m::EdgeConv)(X::HipArray{Float32,3}) = edgeconv_forward(m, X)
 
 
 end # module

@@ -217,4 +217,17 @@ end
             @test unhip(Flux3DHip.dgcnn_forward(model, hip(x_test))) == y                 # the same bits on every run
         end
     end
+
+    @testset "EdgeConv(layers, K) on its own (src/models/dgcnn.jl:11-71), widths of the caller's choice" begin
+        x_test = rand(Float32, 5, 65, 2)
+        layer = Flux3D.EdgeConv([5, 33, 70], 6)
+        y_test = layer(hip(x_test))
+        @test size(y_test) == (70, 65, 2)
+        y = unhip(y_test)
+        @test isapprox(y, Flux3D.Flux.testmode!(layer)(x_test), rtol = 1f-3)             # Flux's BLAS sums: close, not equal
+        out, idx = Flux3DHip.edgeconv_forward(layer, hip(x_test); return_idx = true)
+        @test size(idx) == (6, 65, 2) && all(0 .<= unhip(idx) .< 65)                      # 0-based
+        @test unhip(out) == y                                                             # the same bits on every run
+        @test unhip(Flux3DHip.edgeconv_forward(layer, hip(x_test); idx = idx)) == y       # the same lists, given
+    end
 end

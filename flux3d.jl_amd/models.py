@@ -1,9 +1,10 @@
-"""PointNet and DGCNN inference on the device (src/models/pointnet.jl, src/models/dgcnn.jl): ``PointNet(num_classes, 64)(X)``
-and ``DGCNN(num_classes, K, npoints)(X)`` in test mode.
+"""PointNet, DGCNN and EdgeConv inference on the device (src/models/pointnet.jl, src/models/dgcnn.jl):
+``PointNet(num_classes, 64)(X)``, ``DGCNN(num_classes, K, npoints)(X)`` and the layer ``EdgeConv(layers, K)(X)`` in test mode.
 
-include/flux3d_hip.h states the networks and their arithmetic ("PointNet inference", "DGCNN inference"); this module owns the
-parameters (a name -> numpy array mapping in Flux's shapes), flattens them into the one device buffer fx3d_pointnet_forward /
-fx3d_dgcnn_forward reads, and checks every argument on the host before any launch.  Forward only: no training, no gradients."""
+include/flux3d_hip.h states the networks and their arithmetic ("PointNet inference", "DGCNN inference", "EdgeConv inference");
+this module owns the parameters (a name -> numpy array mapping in Flux's shapes), flattens them into the one device buffer
+fx3d_pointnet_forward / fx3d_dgcnn_forward / fx3d_edgeconv_forward reads, and checks every argument on the host before any
+launch.  Forward only: no training, no gradients."""
 import ctypes as C
 
 import numpy as np
@@ -67,9 +68,27 @@ def dgcnn_param_shapes(num_classes):
     return _shapes(dgcnn_layer_spec(num_classes))
 
 
+def edgeconv_layer_spec(layers):
+    """EdgeConv(layers, K)'s layers that carry parameters, in forward order (src/models/dgcnn.jl:18-30): conv_bn_blocks
+    2 layers[0] => layers[1], layers[1] => layers[2], ..."""
+    spec = []
+    for i in range(1, len(layers)):
+        spec += [(f"conv{i}", "conv", (2 * layers[0] if i == 1 else layers[i - 1], layers[i])), (f"bn{i}", "bn", layers[i])]
+    return spec
+
+
+def edgeconv_param_shapes(layers):
+    """EdgeConv: name -> shape of every parameter array, in the order of the flat buffer (Flux's shapes, :func:`_shapes`)."""
+    return _shapes(edgeconv_layer_spec([int(c) for c in layers]))
+
+
 class _Model:
-    """What the two classifiers share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy,
-    and the check of the input clouds.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``."""
+    """What the models share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy, and
+    the check of the input clouds.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``, and ``_count_args()`` where
+    the count is not a function of ``num_classes``."""
+
+    def _count_args(self):
+        return (self.num_classes,)
 
     def _init_params(self, seed):
         """Filled the way Flux fills a new model -- Glorot-uniform weights, zero biases, BatchNorm gamma = 1, beta = 0, mu = 0,
@@ -86,7 +105,7 @@ class _Model:
                 self.params[name] = np.full(shape, 1.0 if field in ("gamma", "sigma2") else 0.0, np.float32)
         self._dev = None
         count = C.c_int64(0)
-        _lib.call(self._COUNT_FN, self.num_classes, C.byref(count))
+        _lib.call(self._COUNT_FN, *self._count_args(), C.byref(count))
         self.param_count = count.value
 
     def load(self, params):
@@ -115,8 +134,9 @@ class _Model:
             self._dev = DeviceArray.from_host(self.flat_params())
         return self._dev
 
-    def _clouds(self, X, why3):
-        """(the points, N, B, whether they are on the device) after the shape checks; nothing is uploaded yet."""
+    def _clouds(self, X, why, F=3):
+        """(the points, N, B, whether they are on the device) after the shape checks; nothing is uploaded yet.  F: the
+        channels per point the model takes, `why` the layer that fixes them."""
         pts = X.points if isinstance(X, PointCloud) else X
         on_dev = is_device(pts)
         if on_dev:
@@ -129,17 +149,17 @@ class _Model:
         if len(shape) == 2:
             shape = shape + (1,)
         if len(shape) != 3:
-            raise ValueError(f"points must be (3, N) or (3, N, B), got {tuple(shape)}")
-        if shape[0] != 3:
-            raise ValueError(f"{self._NAME} takes 3 channels per point ({why3}), got {shape[0]}")
+            raise ValueError(f"points must be ({F}, N) or ({F}, N, B), got {tuple(shape)}")
+        if shape[0] != F:
+            raise ValueError(f"{self._NAME} takes {F} channels per point ({why}), got {shape[0]}")
         N, B = int(shape[1]), int(shape[2])
         if N < 1 or B < 1:
             raise ValueError(f"{self._NAME} needs at least one point and one cloud, got N={N}, B={B}")
         return pts, N, B, on_dev
 
     @staticmethod
-    def _on_device(pts, N, B, on_dev):
-        return pts.reshape(3, N, B) if on_dev else DeviceArray.from_host(np.asfortranarray(pts.reshape(3, N, B, order="F")))
+    def _on_device(pts, N, B, on_dev, F=3):
+        return pts.reshape(F, N, B) if on_dev else DeviceArray.from_host(np.asfortranarray(pts.reshape(F, N, B, order="F")))
 
 
 class PointNet(_Model):
@@ -235,5 +255,94 @@ class DGCNN(_Model):
         if not on_dev:
             out = {k: v.to_host() for k, v in out.items()}
         return out if intermediates else out["probs"]
+
+    __call__ = forward
+
+
+class EdgeConv(_Model):
+    """``EdgeConv(layers, K)`` (src/models/dgcnn.jl:11-71) in test mode, as a layer in its own right: include/flux3d_hip.h
+    "EdgeConv inference" states the layer, its arithmetic and the envelope.  ``layers = [F, c1, ..., cL]`` is the reference
+    constructor's argument: L conv_bn_blocks 2F => c1, c1 => c2, ... on the edge rows [x_n, x_idx(k,n) - x_n] of the K nearest
+    neighbours of every point, then the maximum over k.  1 <= L <= 4, 1 <= F <= 128, every width in [1, 256].
+
+    ``params`` (:func:`edgeconv_param_shapes`: ``conv{i}.weight``, ``conv{i}.bias``, ``bn{i}.gamma`` / ``beta`` / ``mu`` /
+    ``sigma2``), ``load``, ``flat_params`` and the seeded initialisation are the classifiers'.  The ``ec1.`` / ``ec2.`` arrays
+    of a DGCNN, with that prefix dropped, are the parameters of ``EdgeConv([3, 32, 64, 64], K)`` / ``EdgeConv([64, 128, 256], K)``."""
+
+    _NAME, _COUNT_FN = "EdgeConv", "fx3d_edgeconv_param_count"
+    MAX_BLOCKS, MAX_F, MAX_WIDTH = 4, 128, 256
+
+    def __init__(self, layers, K, seed=0):
+        try:
+            widths = [int(c) for c in layers]
+            exact = all(c == w for c, w in zip(layers, widths))
+        except (TypeError, ValueError):
+            raise TypeError(f"layers must be a sequence of integers [F, c1, ..., cL], got {layers!r}") from None
+        if not exact:
+            raise TypeError(f"layers must be integers, got {list(layers)!r}")
+        if not 2 <= len(widths) <= self.MAX_BLOCKS + 1:
+            raise ValueError(f"EdgeConv takes F and 1 to {self.MAX_BLOCKS} widths, got {len(widths)} entries")
+        if not 1 <= widths[0] <= self.MAX_F:
+            raise ValueError(f"layers[0] = F must be in [1, {self.MAX_F}], got {widths[0]}")
+        for i, c in enumerate(widths[1:], 1):
+            if not 1 <= c <= self.MAX_WIDTH:
+                raise ValueError(f"layers[{i}] must be in [1, {self.MAX_WIDTH}], got {c}")
+        if int(K) < 1:
+            raise ValueError(f"EdgeConv needs K >= 1 neighbours besides the point itself, got K={K}")
+        self.layers, self.K = widths, int(K)
+        self._init_params(seed)
+
+    def _layers_c(self):
+        return (C.c_int32 * len(self.layers))(*self.layers), len(self.layers)
+
+    def _count_args(self):
+        return self._layers_c()
+
+    def _shapes(self):
+        return edgeconv_param_shapes(self.layers)
+
+    def _neighbours(self, idx, N, B):
+        """The caller's lists as a (K, N, B) int32 device array.  Host lists are range-checked here; lists that are on the
+        device already are used as they are (an index outside [0, N) reads the point itself, flux3d_hip.h)."""
+        K = self.K
+        if is_device(idx):
+            if idx.dtype != np.int32:
+                raise TypeError(f"device neighbour lists must be int32, got {idx.dtype}")
+            if tuple(idx.shape) not in ((K, N, B),) + (((K, N),) if B == 1 else ()):
+                raise ValueError(f"idx must be ({K}, {N}, {B}), got {tuple(idx.shape)}")
+            return idx.reshape(K, N, B)
+        a = np.asarray(idx)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"idx must hold integers, got {a.dtype}")
+        if a.shape not in ((K, N, B),) + (((K, N),) if B == 1 else ()):
+            raise ValueError(f"idx must be ({K}, {N}, {B}), got {a.shape}")
+        if a.size and (a.min() < 0 or a.max() >= N):
+            raise ValueError(f"idx must hold 0-based indices in [0, {N}), got values from {a.min()} to {a.max()}")
+        return DeviceArray.from_host(np.asfortranarray(a.reshape(K, N, B, order="F").astype(np.int32)))
+
+    def forward(self, X, idx=None, return_idx=False):
+        """``(cL, N, B)`` for the clouds ``X``: a device array or a numpy array, ``(F, N, B)`` or ``(F, N)`` (one cloud); a
+        PointCloud when F = 3.  The result lives where the input lives.  ``idx``: neighbour lists ``(K, N, B)``, 0-based,
+        to use instead of the search (numpy integers, checked against [0, N) here, or an int32 device array).
+        ``return_idx=True``: ``(out, idx)`` with the lists that were used, int32."""
+        F, K = self.layers[0], self.K
+        if isinstance(X, PointCloud) and F != 3:
+            raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
+        pts, N, B, on_dev = self._clouds(X, f"EdgeConv({self.layers}, {K})", F)
+        if K + 1 > N:
+            raise ValueError(f"EdgeConv needs 1 <= K <= N - 1 (K neighbours besides the point itself), got K={K}, N={N}")
+        layers, nl = self._layers_c()
+        nb = _lib.query_bytes("fx3d_edgeconv_workspace_bytes", layers, nl, K, N, B)  # (the library's own size limits)
+        given = None if idx is None else self._neighbours(idx, N, B)
+        x = self._on_device(pts, N, B, on_dev, F)
+        out = DeviceArray.empty((self.layers[-1], N, B), np.float32)
+        found = DeviceArray.empty((K, N, B), np.int32) if return_idx and given is None else None
+        ws = workspace(nb, tag="edgeconv")
+        _lib.call("fx3d_edgeconv_forward", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
+                  out.ptr, found.ptr if found else None, ws.ptr, ws.nbytes, current_stream().handle)
+        used = given if given is not None else found
+        if not on_dev:
+            out, used = out.to_host(), (used.to_host() if used is not None else None)
+        return (out, used) if return_idx else out
 
     __call__ = forward

@@ -839,6 +839,40 @@ FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_cla
                                         int32_t B, float *probs, float *logits, int32_t *idx1, float *x1, int32_t *idx2,
                                         float *x2, float *pooled, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- EdgeConv inference: (m::EdgeConv)(X) (src/models/dgcnn.jl:11-71) in test mode, for any layer widths -------------------
+ * EdgeConv(layers, K) as a layer in its own right, forward only, Float32.  layers: a HOST array [F, c1, ..., cL] of nlayers
+ * entries, the argument of the reference's constructor: L = nlayers - 1 conv_bn_blocks (src/models/utils.jl:1-3) 2F -> c1,
+ * c1 -> c2, ..., each conv, BatchNorm with its running statistics, relu -- in this order.  x (F,N,B) device, out (cL,N,B):
+ *   idx (K,N,B) = the K nearest neighbours of every point among its own cloud's F-dimensional rows, the point itself (rank 0 of
+ *     K+1) dropped: fx3d_knn_ws(x, N, x, N, B, F, K, 1, ...) with its order and its 0-based indices;
+ *   edge row (k,n) = [x_n (F), x_idx(k,n) - x_n (F)], the difference one Float32 subtraction; the L blocks on every row;
+ *   out[c,n,b] = max over k.  The (K N, 2F, B) edge array is never written to memory.
+ * idx_in == NULL: the search runs, and its lists are written to idx_out if that is given.  idx_in != NULL, (K,N,B) int32 on the
+ * device: the search is skipped and these lists are used (static graphs, tests); idx_out is then not touched.  Defined
+ * behaviour: an index outside [0, N) reads the point itself (an edge row [x_n, 0]).
+ * Arithmetic: the PointNet / DGCNN contract above, verbatim -- one accumulator per output element, acc = fmaf(x[c], W[c,o], acc)
+ * for c ascending from +0.0f over ALL 2F concatenated channels (the x_n half first), one Float32 bias addition, BatchNorm with
+ * eps = 1f-5 and every operation rounded to Float32, relu and the maximum as Julia's max.  No contraction is split over waves
+ * or blocks, no contraction is padded with zero channels, no float atomics: out and idx are bit-identical to the restatement
+ * tests/edgeconv_ref.py and from run to run, whatever N, B, K and the launch shape, and EdgeConv([3,32,64,64], K) /
+ * EdgeConv([64,128,256], K) on DGCNN's parameters give fx3d_dgcnn_forward's x1 / x2.
+ * params_dev: ONE flat device Float32 buffer in forward order, per block conv W (Cin,Cout) column-major then b (Cout), then
+ *   BatchNorm gamma, beta, mu, var (Cout each) -- the layout of the EdgeConv slices of the DGCNN buffer, so a slice of a DGCNN's
+ *   parameters is a valid EdgeConv buffer.  fx3d_edgeconv_param_count(layers, nlayers) is its length in floats.
+ * Envelope: 1 <= L <= 4, 1 <= F <= 128, every width in [1, 256] (no multiple of anything required) -- anything else is
+ * FX3D_ERR_UNSUPPORTED; 1 <= K <= N - 1, N <= 36864 (the neighbour search), B <= 65535, N B K <= 2^31 -- anything else, a NULL
+ * required pointer (params_dev, layers, x, out, ws), a short workspace or one not 256-byte aligned is FX3D_ERR_INVALID_ARG.
+ * Every refusal comes before any device work and names the offending value in fx3d_last_error.
+ * Launches on `s` only (the search through fx3d_knn_ws, one EdgeConv kernel), no host synchronisation, no host memory other
+ * than `layers` read, and none after the argument check (graph-capturable).  ws: fx3d_edgeconv_workspace_bytes(layers, nlayers,
+ * K, N, B) -- the neighbour lists and the search's scratch. */
+FX3D_API fx3d_status fx3d_edgeconv_param_count(const int32_t *layers, int32_t nlayers, int64_t *count);
+FX3D_API fx3d_status fx3d_edgeconv_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
+                                                   size_t *bytes);
+FX3D_API fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
+                                           const float *x, int32_t N, int32_t B, const int32_t *idx_in, float *out,
+                                           int32_t *idx_out, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
