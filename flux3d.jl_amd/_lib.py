@@ -186,6 +186,15 @@ SIGNATURES = {
     "fx3d_laplacian_loss_host": [vp, c_i64, vp, vp, vp, C.POINTER(c_f32)],
     "fx3d_build_edges_packed": [vp, c_i64, c_i64, c_i32, vp, vp, C.POINTER(c_i64)],
     "fx3d_build_laplacian_csr": [vp, c_i64, c_i64, c_i32, vp, vp, vp, C.POINTER(c_i64)],
+    "fx3d_edges_dev_workspace_bytes": [c_i64, c_i64, C.POINTER(sz)],
+    "fx3d_edges_dev_count": [vp, c_i64, c_i64, vp, vp, vp, sz, vp],
+    "fx3d_edges_dev_emit": [vp, c_i64, c_i64, c_i64, vp, vp, vp, sz, vp],
+    "fx3d_laplacian_dev_workspace_bytes": [c_i64, c_i64, C.POINTER(sz)],
+    "fx3d_laplacian_dev_csr": [vp, c_i64, c_i64, vp, vp, vp, vp, vp, vp, sz, vp],
+    "fx3d_vertex_faces_dev_workspace_bytes": [c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_vertex_faces_dev": [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, sz, vp],
+    "fx3d_faces_padded_to_packed_dev_workspace_bytes": [c_i32, C.POINTER(sz)],
+    "fx3d_faces_padded_to_packed_dev": [vp, vp, vp, c_i32, c_i32, c_i64, vp, vp, sz, vp],
 }
 _RESTYPES = {"fx3d_version": C.c_char_p, "fx3d_last_error": sz, "fx3d_option_count": c_i32, "fx3d_option_name": C.c_char_p}
 

@@ -712,6 +712,65 @@ function laplacian_csr_dev(m)
     end
 end
 
+# ---- topology of DEVICE-resident faces (csrc/topology_dev.hip): the tables above, bit for bit, built without the host.
+#      A TriMesh of this shim owns host faces and runs the reference's own topology code (INTEGRATION.md), so none of these
+#      is on its path; they serve a pipeline whose faces a kernel wrote.  All index arrays Int32, 0-based.
+function edges_packed_dev(faces::HipArray{Int32,2}, V::Integer; faces_to_edges::Bool = false)
+    F = size(faces, 2); nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_edges_dev_workspace_bytes(F::Int64, V::Int64, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[]); counts = HipArray{Int64}(undef, 2)   # E, then the bad-id count (UInt32)
+    check(@ccall LIB.fx3d_edges_dev_count(faces.ptr::Ptr{Cvoid}, F::Int64, V::Int64, counts.ptr::Ptr{Cvoid},
+                                          (counts.ptr + 8)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                          DEFAULT_STREAM::Stream)::Int32)
+    h = unhip(counts)   # the one synchronisation: E sizes the edge list
+    E = h[1]; nbad = reinterpret(UInt32, h[2:2])[1]
+    nbad == 0 || throw(ArgumentError("edges_packed_dev: $nbad vertex ids outside [0, $V)"))
+    edges = HipArray{Int32}(undef, E, 2)
+    f2e = faces_to_edges ? HipArray{Int32}(undef, F, 3) : nothing
+    f2e_ptr = f2e === nothing ? C_NULL : f2e.ptr
+    check(@ccall LIB.fx3d_edges_dev_emit(faces.ptr::Ptr{Cvoid}, F::Int64, V::Int64, E::Int64, edges.ptr::Ptr{Cvoid},
+                                         f2e_ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                         DEFAULT_STREAM::Stream)::Int32)
+    return edges, f2e
+end
+function laplacian_csr_dev(edges::HipArray{Int32,2}, V::Integer)
+    E = size(edges, 1); nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_laplacian_dev_workspace_bytes(E::Int64, V::Int64, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[]); counts = HipArray{Int64}(undef, 2)   # nnz, then the bad-id count (UInt32)
+    rowptr = HipArray{Int32}(undef, V + 1); colind = HipArray{Int32}(undef, 2E + V); vals = HipArray{Float32}(undef, 2E + V)
+    check(@ccall LIB.fx3d_laplacian_dev_csr(edges.ptr::Ptr{Cvoid}, E::Int64, V::Int64, rowptr.ptr::Ptr{Cvoid},
+                                            colind.ptr::Ptr{Cvoid}, vals.ptr::Ptr{Cvoid}, counts.ptr::Ptr{Cvoid},
+                                            (counts.ptr + 8)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                            DEFAULT_STREAM::Stream)::Int32)
+    h = unhip(counts)
+    nnz = h[1]; nbad = reinterpret(UInt32, h[2:2])[1]
+    nbad == 0 || throw(ArgumentError("laplacian_csr_dev: $nbad edge ends outside [0, $V)"))
+    return rowptr, colind, vals, nnz   # colind / vals hold nnz entries (capacity 2E + V)
+end
+function vertex_faces_dev(faces_padded::HipArray{Int32,3}, faces_len::HipArray{Int32,1}, Vmax::Integer)
+    Fmax, B = size(faces_padded, 2), size(faces_padded, 3); nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_vertex_faces_dev_workspace_bytes(Vmax::Int32, Fmax::Int32, B::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[]); bad = HipArray{UInt32}(undef, 1)
+    rowptr = HipArray{Int32}(undef, Vmax + 1, B); ent = HipArray{Int32}(undef, 3Fmax, B)
+    check(@ccall LIB.fx3d_vertex_faces_dev(faces_padded.ptr::Ptr{Cvoid}, faces_len.ptr::Ptr{Cvoid}, Vmax::Int32, Fmax::Int32,
+                                           B::Int32, rowptr.ptr::Ptr{Cvoid}, ent.ptr::Ptr{Cvoid}, bad.ptr::Ptr{Cvoid},
+                                           ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    nbad = unhip(bad)[1]
+    nbad == 0 || throw(ArgumentError("vertex_faces_dev: $nbad vertex ids or face counts out of range"))
+    return rowptr, ent
+end
+function faces_padded_to_packed_dev(faces_padded::HipArray{Int32,3}, faces_len::HipArray{Int32,1}, nverts::HipArray{Int32,1},
+                                    sumF::Integer)
+    Fmax, B = size(faces_padded, 2), size(faces_padded, 3); nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_faces_padded_to_packed_dev_workspace_bytes(B::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[]); out = HipArray{Int32}(undef, 3, sumF)
+    check(@ccall LIB.fx3d_faces_padded_to_packed_dev(faces_padded.ptr::Ptr{Cvoid}, faces_len.ptr::Ptr{Cvoid},
+                                                     nverts.ptr::Ptr{Cvoid}, Fmax::Int32, B::Int32, sumF::Int64,
+                                                     out.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                                     DEFAULT_STREAM::Stream)::Int32)
+    return out
+end
+
 # ---- sample_points: replaces src/transforms/mesh_func.jl:21-58 for HipArray-backed meshes -------
 function sample_points(m::TriMesh{Float32,R,HipArray}, num_samples::Int = 5000; eps::Number = Flux3D.EPS,
                        seed::UInt64 = rand(UInt64)) where {R}

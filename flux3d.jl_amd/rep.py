@@ -198,6 +198,13 @@ def index_upload(arr, index_base, clamp_pad=False, limit=0):
     return out
 
 
+class _Deferred:
+    """Host cache entry of a table that was built on the device: ``fetch()`` downloads it in the host form."""
+
+    def __init__(self, fetch):
+        self.fetch = fetch
+
+
 class TriMesh:
     """TriMesh(verts_list, faces_list; offset=-1) -- src/rep/mesh.jl:70-187.
 
@@ -291,7 +298,12 @@ class TriMesh:
         return m
 
     def _topo_prop(name):  # noqa: N805  (attribute backed by the shared topology dict)
-        return property(lambda self: self._topo.get(name), lambda self, v: self._topo.__setitem__(name, v))
+        def get(self):
+            v = self._topo.get(name)
+            if isinstance(v, _Deferred):  # built on the device: downloaded when the host first reads it
+                v = self._topo[name] = v.fetch()
+            return v
+        return property(get, lambda self, v: self._topo.__setitem__(name, v))
 
     _faces_packed = _topo_prop("faces_packed")
     _faces_padded = _topo_prop("faces_padded")
@@ -405,7 +417,19 @@ class TriMesh:
         return self._faces_padded
 
     # ---- topology (host builders of the C ABI; cached forever like the reference) ---------------
+    def _device_born(self):
+        """A device mesh without host face lists (:meth:`_from_device`, until something asks for them): its topology is
+        built on the device and the host getters download it."""
+        return self._device and self.__dict__.get("_faces_list_") is None
+
+    def _index_download(self, arr):
+        """Device int32 0-based index array -> the reference's type and numbering (the inverse of :func:`index_upload`)."""
+        return np.asfortranarray((arr.to_host().astype(np.int64) + self.index_base).astype(self.R))
+
     def _build_edges(self):
+        if self._device_born():  # (the device build leaves the host entries behind as deferred downloads)
+            self.dev("edges"), self.dev("faces_to_edges")
+            return
         faces = np.asfortranarray(self.get_faces_packed(), dtype=np.int64)
         F = faces.shape[1]
         V = int(self._verts_len.sum())
@@ -437,6 +461,8 @@ class TriMesh:
 
     def get_laplacian_packed(self):
         """get_laplacian_packed (src/rep/mesh.jl:559-565) as 0-based CSR (rowptr, colind, vals)."""
+        if self._laplacian_packed is None and self._device_born():
+            self.dev("lap_rowptr")
         if self._laplacian_packed is None:
             e = np.asfortranarray(self.get_edges_packed(), dtype=np.int64)
             E, V = e.shape[0], int(self._verts_len.sum())
@@ -461,7 +487,14 @@ class TriMesh:
     def dev(self, name):
         """Cached device copies: faces_packed / faces_padded / faces_len / nverts (int32 0-based), edges
         (E,2) int32 0-based, lap_rowptr / lap_colind / lap_vals, the vertex -> (face, corner) tables vf_rowptr / vf_ent
-        (padded batch) and vf_packed_rowptr / vf_packed_ent (packed faces), and verts_* float32."""
+        (padded batch) and vf_packed_rowptr / vf_packed_ent (packed faces), and verts_* float32.
+
+        One rule for edges, faces_to_edges, lap_*, vf_*, vf_packed_* and faces_packed: an item whose host form is already
+        cached is uploaded; otherwise a device mesh builds it on the device from its device faces (csrc/topology_dev.hip:
+        the same bits as the host builders), and a host mesh builds it on the host and uploads it.  A device build is
+        eager -- it reads one count back to size its output -- so, like the host build, it has to run before a graph
+        capture begins: touch the mesh's losses (or ``dev(name)``) once outside the capture.  The host form of a table
+        built on the device is downloaded when a host getter first reads it."""
         store = self._dev if name.startswith("verts") else self._topo_dev
         if name in store:
             return store[name]
@@ -470,6 +503,8 @@ class TriMesh:
             arr = DeviceArray.from_host(self.get_verts_packed_host())
         elif name == "verts_padded":
             arr = DeviceArray.from_host(self.get_verts_padded_host())
+        elif name == "faces_packed" and self._faces_packed is None and self._device_born() and "faces_padded" in store:
+            arr = self._pack_faces_dev()
         elif name == "faces_packed":   # the reference's own arrays (UInt32 / Int64, 1-based) cross the ABI untouched: the
             arr = index_upload(self.get_faces_packed(), b, limit=int(np.sum(self._verts_len)))   # library converts on the device
         elif name == "faces_padded":    # (pad entries -- value 0 in the reference -- become 0: never dereferenced)
@@ -478,8 +513,16 @@ class TriMesh:
             arr = DeviceArray.from_host(self._faces_len.astype(np.int32))
         elif name == "nverts":  # per-mesh vertex counts (B) int32 (not "verts_len": names starting with "verts" are vertex mirrors)
             arr = DeviceArray.from_host(self._verts_len.astype(np.int32))
+        elif name in ("edges", "faces_to_edges") and self._device and self._topo.get(name + "_packed") is None:
+            self._build_edges_dev(name)
+            return store[name]
         elif name == "edges":
             arr = index_upload(self.get_edges_packed(), b, limit=int(np.sum(self._verts_len)))
+        elif name == "faces_to_edges":
+            arr = index_upload(self.get_faces_to_edges_packed(), b)
+        elif name in ("vf_rowptr", "vf_ent", "vf_packed_rowptr", "vf_packed_ent") and self._device:
+            self._build_vertex_faces_dev(packed="packed" in name)
+            return store[name]
         elif name in ("vf_rowptr", "vf_ent"):  # vertex -> (face, corner) table of the ordered sampling adjoint (padded batch)
             fp = np.asfortranarray(self.get_faces_padded().astype(np.int64) - b).astype(np.int32)
             fp[fp < 0] = 0  # (padding faces: never read, faces_len bounds the walk)
@@ -502,6 +545,9 @@ class TriMesh:
             store["vf_packed_rowptr"] = DeviceArray.from_host(rowptr)
             store["vf_packed_ent"] = DeviceArray.from_host(ent)
             return store[name]
+        elif name in ("lap_rowptr", "lap_colind", "lap_vals") and self._device and self._laplacian_packed is None:
+            self._build_laplacian_dev()
+            return store[name]
         elif name in ("lap_rowptr", "lap_colind", "lap_vals"):
             rowptr, colind, vals = self.get_laplacian_packed()
             store["lap_rowptr"] = DeviceArray.from_host(rowptr)
@@ -514,6 +560,73 @@ class TriMesh:
             return arr  # host mesh: do not cache vertex uploads (verts may change)
         store[name] = arr
         return arr
+
+    # ---- topology built on the device (csrc/topology_dev.hip); each leaves its tables in the shared _topo_dev ----------
+    @staticmethod
+    def _check_ids(what, bad):
+        nbad = int(bad.to_host()[0])
+        if nbad:
+            raise ValueError(f"{what}: {nbad} vertex ids outside the mesh's vertex range")
+
+    def _pack_faces_dev(self):
+        fp = self.dev("faces_padded")
+        out = DeviceArray.empty((3, int(self._faces_len.sum())), np.int32)
+        ws = DeviceArray.empty((_lib.query_bytes("fx3d_faces_padded_to_packed_dev_workspace_bytes", self.N),), np.uint8)
+        _lib.call("fx3d_faces_padded_to_packed_dev", fp.ptr, self.dev("faces_len").ptr, self.dev("nverts").ptr, int(self.F),
+                  int(self.N), out.shape[1], out.ptr, ws.ptr, ws.nbytes, current_stream().handle)
+        return out
+
+    def _build_edges_dev(self, name):
+        faces, store, s = self.dev("faces_packed"), self._topo_dev, current_stream().handle
+        F, V = int(faces.shape[1]), int(np.sum(self._verts_len))
+        ws = DeviceArray.empty((_lib.query_bytes("fx3d_edges_dev_workspace_bytes", F, V),), np.uint8)
+        count, bad = DeviceArray.empty((1,), np.int64), DeviceArray.empty((1,), np.uint32)
+        _lib.call("fx3d_edges_dev_count", faces.ptr, F, V, count.ptr, bad.ptr, ws.ptr, ws.nbytes, s)
+        E = int(count.to_host()[0])  # the one synchronisation of the build: E sizes the edge list
+        self._check_ids("edges", bad)
+        edges = DeviceArray.empty((E, 2), np.int32)
+        f2e = DeviceArray.empty((F, 3), np.int32) if name == "faces_to_edges" else None  # no kernel reads it: on request only
+        _lib.call("fx3d_edges_dev_emit", faces.ptr, F, V, E, edges.ptr, f2e.ptr if f2e is not None else None, ws.ptr, ws.nbytes, s)
+        edges = store.setdefault("edges", edges)
+        self._topo.setdefault("edges_packed", _Deferred(lambda: self._index_download(edges)))
+        if f2e is not None:
+            store["faces_to_edges"] = f2e
+            self._topo["faces_to_edges_packed"] = _Deferred(lambda: self._index_download(f2e))
+
+    def _build_laplacian_dev(self):
+        edges, store = self.dev("edges"), self._topo_dev
+        E, V = int(edges.shape[0]), int(np.sum(self._verts_len))
+        ws = DeviceArray.empty((_lib.query_bytes("fx3d_laplacian_dev_workspace_bytes", E, V),), np.uint8)
+        rowptr, colind, vals = (DeviceArray.empty((n,), t) for n, t in ((V + 1, np.int32), (2 * E + V, np.int32), (2 * E + V, np.float32)))
+        count, bad = DeviceArray.empty((1,), np.int64), DeviceArray.empty((1,), np.uint32)
+        _lib.call("fx3d_laplacian_dev_csr", edges.ptr, E, V, rowptr.ptr, colind.ptr, vals.ptr, count.ptr, bad.ptr, ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        nnz = int(count.to_host()[0])  # 2E + V less two per self-edge: the arrays are handed out at that length
+        self._check_ids("laplacian", bad)
+        store["lap_rowptr"] = rowptr
+        store["lap_colind"] = DeviceArray(colind.ptr, (nnz,), np.int32, keep=colind)
+        store["lap_vals"] = DeviceArray(vals.ptr, (nnz,), np.float32, keep=vals)
+        self._topo["laplacian_packed"] = _Deferred(lambda: tuple(store[n].to_host() for n in ("lap_rowptr", "lap_colind", "lap_vals")))
+
+    def _build_vertex_faces_dev(self, packed):
+        """The padded batch's tables, or (``packed``) the B = 1 table over the packed faces."""
+        store = self._topo_dev
+        if packed:
+            faces = self.dev("faces_packed")
+            V, F, B, pre = int(np.sum(self._verts_len)), int(faces.shape[1]), 1, "vf_packed_"
+            flen = None  # (every face is live)
+            shapes = ((V + 1,), (3 * F,))
+        else:
+            faces, flen = self.dev("faces_padded"), self.dev("faces_len")
+            V, F, B, pre = int(self.V), int(self.F), int(self.N), "vf_"
+            shapes = ((V + 1, B), (3 * F, B))
+        ws = DeviceArray.empty((_lib.query_bytes("fx3d_vertex_faces_dev_workspace_bytes", V, F, B),), np.uint8)
+        rowptr, ent = DeviceArray.empty(shapes[0], np.int32), DeviceArray.empty(shapes[1], np.int32)
+        bad = DeviceArray.empty((1,), np.uint32)
+        _lib.call("fx3d_vertex_faces_dev", faces.ptr, flen.ptr if flen is not None else None, V, F, B, rowptr.ptr, ent.ptr, bad.ptr, ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        self._check_ids("vertex tables", bad)
+        store[pre + "rowptr"], store[pre + "ent"] = rowptr, ent
 
     # ---- gpu / cpu (functor(::TriMesh) moves only the verts, src/rep/mesh.jl:189-190) ---------------
     @property

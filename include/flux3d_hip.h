@@ -762,6 +762,54 @@ FX3D_API fx3d_status fx3d_build_laplacian_csr(const int64_t *edges, int64_t E, i
                                               int32_t index_base, int32_t *rowptr,
                                               int32_t *colind, float *vals, int64_t *nnz_out);
 
+/* ---- topology on the device: the same tables from device faces, for meshes that are born there -------------------
+ * Every output is bit for bit what the host builders above (and fx3d_build_vertex_faces) write from the same faces.  All
+ * arrays are device memory, int32 0-based.  Ordering is a stable radix sort: integer atomics only count bad ids, no output
+ * bit depends on the order in which anything lands, no float atomics.  Ids outside their range are COUNTED in *bad_dev
+ * (overwritten, one uint32) and stand in as vertex 0: a kernel never dereferences them; what such a call writes is defined
+ * but meaningless.  No entry point synchronises the host.
+ * Limits (an error status, like F = 0 or V = 0): 3F < 2^31; 2E + V < 2^31; Fmax < 2^29, 3 Fmax B < 2^31 and Vmax B < 2^31 - 1.
+ *
+ * _compute_edges_packed (src/rep/mesh.jl:907-955) in two phases, because E depends on the data.
+ * fx3d_edges_dev_count: faces_packed (3,F), V = sum V_i.  *E_dev (int64): the number of distinct undirected edges -- the
+ *   caller reads it back (the one synchronisation of a build) to size `edges`.  *bad_dev: corner ids outside [0, V)
+ *   (REQUIRED).  The workspace keeps what fx3d_edges_dev_emit needs.
+ * fx3d_edges_dev_emit: consumes the workspace of the last fx3d_edges_dev_count with the same F and V (same stream).
+ *   edges (E,2) column-major: every (lo, hi), lo <= hi, ascending by (lo, hi); rows beyond the counted E are not written.
+ *   faces_to_edges (F,3) column-major, optional (NULL: none; faces_packed is read only for it): edge ids in the reference's
+ *   column order (e23, e31, e12) (:946).  ws: fx3d_edges_dev_workspace_bytes(F, V). */
+FX3D_API fx3d_status fx3d_edges_dev_workspace_bytes(int64_t F, int64_t V, size_t *bytes);
+FX3D_API fx3d_status fx3d_edges_dev_count(const int32_t *faces_packed, int64_t F, int64_t V, int64_t *E_dev,
+                                          uint32_t *bad_dev, void *ws, size_t ws_bytes, fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_edges_dev_emit(const int32_t *faces_packed, int64_t F, int64_t V, int64_t E, int32_t *edges,
+                                         int32_t *faces_to_edges, void *ws, size_t ws_bytes, fx3d_stream_t s);
+/* _compute_laplacian_packed (src/rep/mesh.jl:957-1002) with the semantics of fx3d_build_laplacian_csr: edges (E,2)
+ * column-major (any order), rowptr (V+1), colind / vals of capacity 2E + V (entries behind nnz are not written), *nnz_dev
+ * (int64).  Columns ascend within a row, the diagonal is -1, off-diagonal values are deg > 0 ? (float)(1.0 / (double)deg) :
+ * (float)deg where deg counts both ends of every edge (a self-edge adds 2); the copies of a repeated coordinate are summed in
+ * the host's order, a self-edge's as (inv + inv) + (-1.0f): nnz = 2E + V - 2 (self-edges) for distinct edges.
+ * bad_dev optional: edge ends outside [0, V).  ws: fx3d_laplacian_dev_workspace_bytes(E, V). */
+FX3D_API fx3d_status fx3d_laplacian_dev_workspace_bytes(int64_t E, int64_t V, size_t *bytes);
+FX3D_API fx3d_status fx3d_laplacian_dev_csr(const int32_t *edges, int64_t E, int64_t V, int32_t *rowptr, int32_t *colind,
+                                            float *vals, int64_t *nnz_dev, uint32_t *bad_dev, void *ws, size_t ws_bytes,
+                                            fx3d_stream_t s);
+/* fx3d_build_vertex_faces for a padded batch on the device (the reference has no such table: it serves the ordered adjoint of
+ * sample_points, src/rep/mesh.jl:67-71, and the vertex normals, :589-621): faces_padded (3,Fmax,B) mesh-local, faces_len (B; NULL: every
+ * mesh has Fmax faces); vf_rowptr (Vmax+1,B), vf_ent (3 Fmax,B): the entries of a vertex are face * 4 + corner ascending, padding faces are ignored,
+ * the slots of a column behind vf_rowptr[Vmax,b] are 0.  The packed table is the B = 1 call over faces_packed.  bad_dev
+ * optional: ids outside [0, Vmax) in live faces and lengths outside [0, Fmax].  ws: fx3d_vertex_faces_dev_workspace_bytes. */
+FX3D_API fx3d_status fx3d_vertex_faces_dev_workspace_bytes(int32_t Vmax, int32_t Fmax, int32_t B, size_t *bytes);
+FX3D_API fx3d_status fx3d_vertex_faces_dev(const int32_t *faces_padded, const int32_t *faces_len, int32_t Vmax, int32_t Fmax,
+                                           int32_t B, int32_t *vf_rowptr, int32_t *vf_ent, uint32_t *bad_dev, void *ws,
+                                           size_t ws_bytes, fx3d_stream_t s);
+/* _compute_faces_packed (src/rep/mesh.jl:884-896) from the padded device faces: faces_packed (3,sumF), mesh after mesh, each
+ * id plus the vertex count of the meshes before it (nverts (B) int32).  sumF: capacity of faces_packed in faces (the sum of
+ * faces_len); a mesh that would end behind it is not written.  ws: fx3d_faces_padded_to_packed_dev_workspace_bytes(B). */
+FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev_workspace_bytes(int32_t B, size_t *bytes);
+FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev(const int32_t *faces_padded, const int32_t *faces_len,
+                                                     const int32_t *nverts, int32_t Fmax, int32_t B, int64_t sumF,
+                                                     int32_t *faces_packed, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 /* ---- PointNet inference: (m::PointNet)(X) (src/models/pointnet.jl:62-85) in test mode -----------------------------
  * Forward only, Float32: BatchNorm uses its running statistics, Dropout is the identity.  x (3,N,B) device; point n of
  * cloud b has channels x[:,n,b].  PointNet(num_classes, 64): the reference's conv_block1 is fixed at 64 channels, so no
