@@ -1,8 +1,8 @@
 // EdgeConv(layers, K) as a layer in its own right (gfx950): (m::EdgeConv)(X) of src/models/dgcnn.jl:11-71 in test mode, Float32,
 // forward only, for layer widths chosen at run time.  include/flux3d_hip.h ("EdgeConv inference") states the layer, the
-// arithmetic and the parameter layout; this file is how they are computed.  The design is dgcnn.hip's EdgeConv kernel with the
-// widths as arguments: the arithmetic is the same contract (mlp_common.h), so EdgeConv([3, 32, 64, 64], K) and
-// EdgeConv([64, 128, 256], K) give DGCNN's x1 and x2 bit for bit.
+// arithmetic and the parameter layout; this file is how they are computed.  It is the library's one EdgeConv: fx3d_edgeconv_forward
+// and both stages of fx3d_dgcnn_forward (dgcnn.hip) go through edgeconv_run below, so EdgeConv([3, 32, 64, 64], K) and
+// EdgeConv([64, 128, 256], K) are DGCNN's x1 and x2.  The arithmetic is the contract of mlp_common.h.
 //
 // Per call: the neighbour search (fx3d_knn_ws on the cloud's own F-dimensional rows, rank 0 dropped) unless the caller gives
 // the lists, then edgeconv_kernel<NS, LD>: one block = 64 points of one cloud, 4 waves, looping over the neighbour rank k.
@@ -31,7 +31,6 @@ namespace {
 constexpr int kMaxLayers = 4;     // conv_bn_blocks of one EdgeConv
 constexpr int kMaxF = 128;        // input features: an edge row has 2 F channels, one image row of stride 258 at most
 constexpr int kMaxWidth = 256;    // 8 slabs of 32 channels = 2 per wave = 64 VGPRs of running maxima per lane
-constexpr int kMaxN = 36864;      // the neighbour search's general kernel holds a query's N distance keys in LDS
 constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // two images of the widest stride: 132 KB of the CU's 160 KB
 
 struct EdgeConvArgs {
@@ -130,11 +129,11 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_kernel(const EdgeConvArgs
     const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
     f32x16 rm0[NS], rm1[NS];
     fold_init<NS>(rm0, rm1);
-    if (!a.shared_rows) gather_centre<0>(rows, LD, xb, F, p0, nvalid);
+    if (!a.shared_rows) gather_centre(rows, LD, xb, F, p0, nvalid);
     __syncthreads();
     for (int k = 0; k < a.K; ++k) {
-        if (a.shared_rows) gather_centre<0>(rows, LD, xb, F, p0, nvalid);  // (gather_diff reads what the same thread wrote)
-        gather_diff<0>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
+        if (a.shared_rows) gather_centre(rows, LD, xb, F, p0, nvalid);  // (gather_diff reads what the same thread wrote)
+        gather_diff(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
         __syncthreads();
         // the layers: one copy of the code, its layer picked by wave-uniform selects among the kernel arguments (a constant
         // index in every access, so that a.c[] and a.w[] stay in scalar registers)
@@ -180,27 +179,6 @@ fx3d_status check_layers(const char *fn, const int32_t *layers, int32_t nlayers)
     return FX3D_OK;
 }
 
-fx3d_status check_sizes(const char *fn, int32_t N, int32_t B, int32_t K) {
-    FX3D_REQUIRE(N >= 1 && B >= 1, "%s: N and B must be positive, got N=%d B=%d", fn, N, B);
-    FX3D_REQUIRE(K >= 1, "%s: K must be positive, got %d", fn, K);
-    FX3D_REQUIRE((long long)K + 1 <= N, "%s: K + 1 = %lld neighbours (the point itself is dropped) of N = %d points", fn, (long long)K + 1, N);
-    FX3D_REQUIRE(N <= kMaxN, "%s: N must be at most %d (the neighbour search), got %d", fn, kMaxN, N);
-    FX3D_REQUIRE(B <= 65535, "%s: B must be at most 65535, got %d", fn, B);
-    FX3D_REQUIRE((long long)N * B * K <= (1ll << 31), "%s: N * B * K must be at most 2^31, got %lld", fn, (long long)N * B * K);
-    return FX3D_OK;
-}
-
-// the flat parameter buffer: per block conv W (Cin, Cout), b, then BatchNorm gamma, beta, mu, var
-long long layout(const float *params, const int32_t *layers, int nlayers, Conv *c) {
-    Cursor cur{params, 0};
-    for (int i = 1; i < nlayers; ++i) {
-        Conv v = cur.conv(i == 1 ? 2 * layers[0] : layers[i - 1], layers[i]);
-        v.bn = cur.bn(layers[i]);
-        if (c) c[i - 1] = v;
-    }
-    return cur.at;
-}
-
 // the LDS images: one stride for all, from the widest layer input
 void lds_plan(const int32_t *layers, int nlayers, EdgeConvArgs *a, int *ld, size_t *bytes) {
     int widest = 2 * layers[0];
@@ -218,27 +196,82 @@ void lds_plan(const int32_t *layers, int nlayers, EdgeConvArgs *a, int *ld, size
 // the workspace: the neighbour lists (K, N, B) | the neighbour search's scratch
 struct WsPlan { size_t idx, knn, knn_bytes, total; };
 fx3d_status ws_plan(int F, int N, int B, int K, WsPlan *w) {
-    size_t at = 0;
-    auto put = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
-    w->idx = put((size_t)K * N * B * sizeof(int32_t));
+    WsBump ws;
+    w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
     const fx3d_status rc = fx3d_knn_workspace_bytes(N, N, B, F, K, 1, &w->knn_bytes);
     if (rc != FX3D_OK) return rc;
-    w->knn = put(w->knn_bytes);
-    w->total = at;
+    w->knn = ws.put(w->knn_bytes);
+    w->total = ws.at;
     return FX3D_OK;
 }
 
 template <int NS, int LD>
-fx3d_status launch(const EdgeConvArgs &a, size_t lds_bytes, int B, hipStream_t st) {
+fx3d_status launch(const EdgeConvArgs &a, size_t lds_bytes, int B, hipStream_t st, const char *label) {
     const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&edgeconv_kernel<NS, LD>), (int)kMaxLds, "edgeconv_kernel");
     if (rc != FX3D_OK) return rc;
-    ProfileScope prof("edgeconv", st);
+    ProfileScope prof(label, st);
     hipLaunchKernelGGL((edgeconv_kernel<NS, LD>), dim3((a.N + kTile - 1) / kTile, B), dim3(kPtThreads), lds_bytes, st, a);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
 
 }  // namespace
+
+// ---- the entry the model units share (mlp_common.h) -----------------------------------------------------------------------
+namespace fx3d {
+namespace mlp {
+
+// the flat parameter buffer: per block conv W (Cin, Cout), b, then BatchNorm gamma, beta, mu, var
+long long edgeconv_layout(const float *params, const int32_t *layers, int nlayers, Conv *c) {
+    Cursor cur{params, 0};
+    for (int i = 1; i < nlayers; ++i) {
+        Conv v = cur.conv(i == 1 ? 2 * layers[0] : layers[i - 1], layers[i]);
+        v.bn = cur.bn(layers[i]);
+        if (c) c[i - 1] = v;
+    }
+    return cur.at;
+}
+
+fx3d_status edgeconv_workspace_bytes(int F, int N, int B, int K, size_t *bytes) {
+    WsPlan w;
+    const fx3d_status rc = ws_plan(F, N, B, K, &w);
+    if (rc != FX3D_OK) return rc;
+    *bytes = w.total;
+    return FX3D_OK;
+}
+
+fx3d_status edgeconv_run(const float *params_dev, const int32_t *layers, int nlayers, int K, const float *x, int N, int B,
+                         const int32_t *idx_in, float *out, int32_t *idx_out, void *ws, fx3d_stream_t s, const char *label) {
+    EdgeConvArgs a{};
+    edgeconv_layout(params_dev, layers, nlayers, a.c);
+    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
+    a.nl = nlayers - 1; a.cout = layers[nlayers - 1];
+    a.N = N; a.K = K; a.x = x; a.out = out;
+    size_t lds_bytes = 0;
+    int ld = 0;
+    lds_plan(layers, nlayers, &a, &ld, &lds_bytes);
+    if (idx_in) {
+        a.idx = idx_in;
+    } else {
+        WsPlan w;
+        fx3d_status r = ws_plan(layers[0], N, B, K, &w);
+        if (r != FX3D_OK) return r;
+        char *wsb = static_cast<char *>(ws);
+        int32_t *idx = idx_out ? idx_out : reinterpret_cast<int32_t *>(wsb + w.idx);
+        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, idx, nullptr, w.knn_bytes ? wsb + w.knn : nullptr, w.knn_bytes, s)) != FX3D_OK) return r;
+        a.idx = idx;
+    }
+    hipStream_t st = as_stream(s);
+    const bool wide = a.cout > 128;  // two slabs of running maxima per wave
+    switch (ld) {
+        case 66: return wide ? launch<2, 66>(a, lds_bytes, B, st, label) : launch<1, 66>(a, lds_bytes, B, st, label);
+        case kLd: return wide ? launch<2, kLd>(a, lds_bytes, B, st, label) : launch<1, kLd>(a, lds_bytes, B, st, label);
+        default: return wide ? launch<2, 258>(a, lds_bytes, B, st, label) : launch<1, 258>(a, lds_bytes, B, st, label);
+    }
+}
+
+}  // namespace mlp
+}  // namespace fx3d
 
 extern "C" {
 
@@ -247,7 +280,7 @@ fx3d_status fx3d_edgeconv_param_count(const int32_t *layers, int32_t nlayers, in
     FX3D_REQUIRE(count != nullptr, "%s: count is NULL", fn);
     const fx3d_status rc = check_layers(fn, layers, nlayers);
     if (rc != FX3D_OK) return rc;
-    *count = layout(nullptr, layers, nlayers, nullptr);
+    *count = edgeconv_layout(nullptr, layers, nlayers, nullptr);
     return FX3D_OK;
 }
 
@@ -256,11 +289,8 @@ fx3d_status fx3d_edgeconv_workspace_bytes(const int32_t *layers, int32_t nlayers
     FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
     fx3d_status rc = check_layers(fn, layers, nlayers);
     if (rc != FX3D_OK) return rc;
-    if ((rc = check_sizes(fn, N, B, K)) != FX3D_OK) return rc;
-    WsPlan w;
-    if ((rc = ws_plan(layers[0], N, B, K, &w)) != FX3D_OK) return rc;
-    *bytes = w.total;
-    return FX3D_OK;
+    if ((rc = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return rc;
+    return edgeconv_workspace_bytes(layers[0], N, B, K, bytes);
 }
 
 fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
@@ -270,34 +300,12 @@ fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_t *layers
     FX3D_REQUIRE(params_dev && x && out && ws, "%s: params_dev, x, out and ws must not be NULL", fn);
     fx3d_status r = check_layers(fn, layers, nlayers);
     if (r != FX3D_OK) return r;
-    if ((r = check_sizes(fn, N, B, K)) != FX3D_OK) return r;
-    WsPlan w;
-    if ((r = ws_plan(layers[0], N, B, K, &w)) != FX3D_OK) return r;
-    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_edgeconv_workspace_bytes says %zu", fn, ws_bytes, w.total);
+    if ((r = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return r;
+    size_t need = 0;
+    if ((r = edgeconv_workspace_bytes(layers[0], N, B, K, &need)) != FX3D_OK) return r;
+    FX3D_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, fx3d_edgeconv_workspace_bytes says %zu", fn, ws_bytes, need);
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
-    EdgeConvArgs a{};
-    layout(params_dev, layers, nlayers, a.c);
-    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
-    a.nl = nlayers - 1; a.cout = layers[nlayers - 1];
-    a.N = N; a.K = K; a.x = x; a.out = out;
-    size_t lds_bytes = 0;
-    int ld = 0;
-    lds_plan(layers, nlayers, &a, &ld, &lds_bytes);
-    char *wsb = static_cast<char *>(ws);
-    if (idx_in) {
-        a.idx = idx_in;
-    } else {
-        int32_t *idx = idx_out ? idx_out : reinterpret_cast<int32_t *>(wsb + w.idx);
-        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, idx, nullptr, w.knn_bytes ? wsb + w.knn : nullptr, w.knn_bytes, s)) != FX3D_OK) return r;
-        a.idx = idx;
-    }
-    hipStream_t st = as_stream(s);
-    const bool wide = layers[nlayers - 1] > 128;  // two slabs of running maxima per wave
-    switch (ld) {
-        case 66: return wide ? launch<2, 66>(a, lds_bytes, B, st) : launch<1, 66>(a, lds_bytes, B, st);
-        case kLd: return wide ? launch<2, kLd>(a, lds_bytes, B, st) : launch<1, kLd>(a, lds_bytes, B, st);
-        default: return wide ? launch<2, 258>(a, lds_bytes, B, st) : launch<1, 258>(a, lds_bytes, B, st);
-    }
+    return edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx_in, out, idx_out, ws, s, "edgeconv");
 }
 
 }  // extern "C"

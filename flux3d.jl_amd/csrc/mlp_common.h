@@ -1,6 +1,7 @@
 // What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip) share: the exact-Float32 contraction on the f32 MFMA, the
-// activation and BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, the EdgeConv kernels' gather of
-// the edge rows and fold of the last layer, and the walk over the flat parameter buffer.
+// activation and BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, the EdgeConv kernel's gather of
+// the edge rows and fold of the last layer, the two ends of a classifier head, and on the host the walk over the flat
+// parameter buffer, the workspace allocator, the size limits of the neighbour search and the EdgeConv entry DGCNN runs on.
 // include/flux3d_hip.h ("PointNet inference") states the arithmetic; pointnet.hip's header comment the tile and its LDS banks.
 #pragma once
 #include <cmath>
@@ -15,6 +16,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kTile = 64;          // points per block
 constexpr int kLd = 130;           // LDS row stride of an activation image of up to 128 channels (floats)
 constexpr int kPtThreads = 256;    // 4 waves
+constexpr int kFeat = 1024;        // channels of the pooled feature
+constexpr int kHeadThreads = 1024; // a head block: one thread per pooled channel
 constexpr float kBnEps = 1e-5f;    // BatchNorm's default epsilon, 1f-5
 
 struct __attribute__((packed, aligned(4))) W4 { float x, y, z, w; };  // four consecutive weights, 4-byte aligned
@@ -143,32 +146,27 @@ __device__ __forceinline__ void conv3(const float *xs, float *out, int ld, int c
     }
 }
 
-// ---- what the EdgeConv kernels (dgcnn.hip, edgeconv.hip) share -----------------------------------------------------------
+// ---- the EdgeConv kernel's (edgeconv.hip) gather and fold ---------------------------------------------------------------
 // The edge rows [x_n (F), x_idx(k,n) - x_n (F)] of the tile's 64 points in `rows` (row stride ld).  xb: the cloud (F, N);
 // ib: the neighbour lists of the tile's points (K each); p0: the tile's first point.  gather_centre writes the x_n half, which
 // does not depend on k; gather_diff the other half for rank k, one Float32 subtraction from the x_n the row holds.  A thread
-// owns the same (point, channel) pairs in both: element i = p F + c for i = tid, tid + 256, ...  FC: F where it is a
-// constant (p = i / F is then a shift or a multiplication), 0 where it is the argument f: there p comes from one Float32
-// multiplication, exact for i < 2^13 and F <= 128 ((i + 1/2) / F is at least 1 / 256 away from every integer, the product's
-// error below 1e-5).  An index outside [0, N) reads the point itself; rows beyond the cloud's last point are zeros.
-template <int FC>
-__device__ __forceinline__ int edge_row_of(int i, float rf) { return FC ? i / (FC ? FC : 1) : (int)(((float)i + 0.5f) * rf); }
-template <int FC>
-__device__ __forceinline__ void gather_centre(float *rows, int ld, const float *xb, int f, int p0, int nvalid) {
-    const int F = FC ? FC : f;
+// owns the same (point, channel) pairs in both: element i = p F + c for i = tid, tid + 256, ...  F is known at run time only:
+// p comes from one Float32 multiplication, exact for i < 2^13 and F <= 128 ((i + 1/2) / F is at least 1 / 256 away from every
+// integer, the product's error below 1e-5).  An index outside [0, N) reads the point itself; rows beyond the cloud's last
+// point are zeros.
+__device__ __forceinline__ int edge_row_of(int i, float rf) { return (int)(((float)i + 0.5f) * rf); }
+__device__ __forceinline__ void gather_centre(float *rows, int ld, const float *xb, int F, int p0, int nvalid) {
     const float rf = 1.0f / (float)F;
     for (int i = threadIdx.x; i < kTile * F; i += kPtThreads) {
-        const int p = edge_row_of<FC>(i, rf), c = i - p * F;
+        const int p = edge_row_of(i, rf), c = i - p * F;
         rows[p * ld + c] = p < nvalid ? xb[(size_t)(p0 + p) * F + c] : 0.0f;
     }
 }
-template <int FC>
-__device__ __forceinline__ void gather_diff(float *rows, int ld, const float *xb, const int32_t *ib, int f, int N, int K, int k,
+__device__ __forceinline__ void gather_diff(float *rows, int ld, const float *xb, const int32_t *ib, int F, int N, int K, int k,
                                             int p0, int nvalid) {
-    const int F = FC ? FC : f;
     const float rf = 1.0f / (float)F;
     for (int i = threadIdx.x; i < kTile * F; i += kPtThreads) {
-        const int p = edge_row_of<FC>(i, rf), c = i - p * F;
+        const int p = edge_row_of(i, rf), c = i - p * F;
         float *row = rows + p * ld;
         float v = 0.0f;
         if (p < nvalid) {
@@ -230,6 +228,37 @@ __device__ __forceinline__ float dense_chain(const float *x, int n, const float 
     return acc;
 }
 
+// ---- the two ends of a head kernel (one block of kHeadThreads per cloud b) -------------------------------------------------
+// MaxPool over the cloud's points: thread tid folds channel tid of the per-tile maxima tmax (kFeat, ntiles, B)
+__device__ __forceinline__ float fold_tile_maxima(const float *tmax, int ntiles, int b) {
+    const float *t = tmax + (size_t)b * ntiles * kFeat + threadIdx.x;
+    float m = t[0];
+    for (int k = 1; k < ntiles; ++k) m = jmax(m, t[(size_t)k * kFeat]);
+    return m;
+}
+// pr = softmax(z) over the n logits the block has just written to z (both in memory): the maximum and the sum in class
+// order, each in thread 0
+__device__ __forceinline__ void softmax_of_logits(const float *z, float *pr, int n) {
+    __shared__ float zmax, esum;
+    const int tid = threadIdx.x;
+    __syncthreads();  // the block's logits are in memory
+    if (tid == 0) {
+        float m = z[0];
+        for (int i = 1; i < n; ++i) m = jmax(m, z[i]);
+        zmax = m;
+    }
+    __syncthreads();
+    for (int o = tid; o < n; o += kHeadThreads) pr[o] = expf(z[o] - zmax);
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.0f;
+        for (int i = 0; i < n; ++i) s = s + pr[i];  // in class order
+        esum = s;
+    }
+    __syncthreads();
+    for (int o = tid; o < n; o += kHeadThreads) pr[o] = pr[o] / esum;
+}
+
 // ---- the flat parameter buffer, layer by layer in forward order (flux3d_hip.h) ------------------------------------------
 struct Cursor {
     const float *base;
@@ -257,6 +286,38 @@ struct Cursor {
         return d;
     }
 };
+
+// ---- the workspace of an entry point: slots of whole 256-byte lines, in the order they are asked for ------------------------
+struct WsBump {
+    size_t at = 0;
+    size_t put(size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
+// ---- the sizes an EdgeConv takes (dgcnn.hip, edgeconv.hip), for the entry point `fn` ----------------------------------------
+constexpr int kMaxN = 36864;  // the neighbour search's general kernel holds a query's N distance keys in LDS
+inline fx3d_status check_edgeconv_sizes(const char *fn, int32_t N, int32_t B, int32_t K) {
+    FX3D_REQUIRE(N >= 1 && B >= 1, "%s: N and B must be positive, got N=%d B=%d", fn, N, B);
+    FX3D_REQUIRE(K >= 1, "%s: K must be positive, got %d", fn, K);
+    FX3D_REQUIRE((long long)K + 1 <= N, "%s: K + 1 = %lld neighbours (the point itself is dropped) of N = %d points", fn, (long long)K + 1, N);
+    FX3D_REQUIRE(N <= kMaxN, "%s: N must be at most %d (the neighbour search), got %d", fn, kMaxN, N);
+    FX3D_REQUIRE(B <= 65535, "%s: B must be at most 65535, got %d", fn, B);
+    FX3D_REQUIRE((long long)N * B * K <= (1ll << 31), "%s: N * B * K must be at most 2^31, got %lld", fn, (long long)N * B * K);
+    return FX3D_OK;
+}
+
+// ---- edgeconv.hip: EdgeConv(layers, K) on x (F, N, B) -> out (cL, N, B), for fx3d_edgeconv_forward and fx3d_dgcnn_forward -----
+// The arguments are fx3d_edgeconv_forward's (flux3d_hip.h), already checked: layers by the envelope, N, B, K by
+// check_edgeconv_sizes, ws 256-byte aligned and of edgeconv_workspace_bytes(F = layers[0], ...) at least.  `label`: the name
+// of the kernel's launches in the library's profile.  edgeconv_layout: the length of the parameter buffer in floats (and, with
+// c, its layers).
+long long edgeconv_layout(const float *params, const int32_t *layers, int nlayers, Conv *c);
+fx3d_status edgeconv_workspace_bytes(int F, int N, int B, int K, size_t *bytes);
+fx3d_status edgeconv_run(const float *params_dev, const int32_t *layers, int nlayers, int K, const float *x, int N, int B,
+                         const int32_t *idx_in, float *out, int32_t *idx_out, void *ws, fx3d_stream_t s, const char *label);
 
 }  // namespace mlp
 }  // namespace fx3d

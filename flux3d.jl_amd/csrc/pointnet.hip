@@ -29,8 +29,6 @@ using namespace fx3d::mlp;
 
 namespace {
 
-constexpr int kHeadThreads = 1024;
-constexpr int kFeat = 1024;        // channels of the pooled feature
 constexpr size_t kPtLds = (size_t)(2 * kTile * kLd + 2 * kTile * 3) * sizeof(float);
 
 struct PointArgs {
@@ -101,13 +99,9 @@ template <bool FEAT>
 __global__ __launch_bounds__(kHeadThreads) void pointnet_head_kernel(const HeadArgs a) {
     __shared__ float v0[kFeat], v1[512], v2[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    {
-        const float *t = a.tmax + (size_t)b * a.ntiles * kFeat + tid;
-        float m = t[0];
-        for (int k = 1; k < a.ntiles; ++k) m = jmax(m, t[(size_t)k * kFeat]);
-        v0[tid] = m;
-        if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + tid] = m;
-    }
+    const float m = fold_tile_maxima(a.tmax, a.ntiles, b);
+    v0[tid] = m;
+    if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + tid] = m;
     __syncthreads();
     if (tid < 512) {
         float v = relu(dense_chain(v0, kFeat, a.d1.W, 512, tid) + a.d1.b[tid]);
@@ -130,26 +124,7 @@ __global__ __launch_bounds__(kHeadThreads) void pointnet_head_kernel(const HeadA
             if (a.mat_user) a.mat_user[at] = v;
         }
     }
-    if (FEAT) {
-        __syncthreads();  // the block's logits are in memory
-        float *z = a.logits + (size_t)b * a.n3, *pr = a.probs + (size_t)b * a.n3;
-        __shared__ float zmax, esum;
-        if (tid == 0) {
-            float m = z[0];
-            for (int i = 1; i < a.n3; ++i) m = jmax(m, z[i]);
-            zmax = m;
-        }
-        __syncthreads();
-        for (int o = tid; o < a.n3; o += kHeadThreads) pr[o] = expf(z[o] - zmax);
-        __syncthreads();
-        if (tid == 0) {
-            float s = 0.0f;
-            for (int i = 0; i < a.n3; ++i) s = s + pr[i];  // in class order
-            esum = s;
-        }
-        __syncthreads();
-        for (int o = tid; o < a.n3; o += kHeadThreads) pr[o] = pr[o] / esum;
-    }
+    if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
 }
 
 struct Stn { Conv c1, c2, c3; Dense d1, d2, d3; Bn bn; };
@@ -193,14 +168,13 @@ struct WsPlan { size_t h, tmax, T, F, logits, total; int ntiles; };
 WsPlan ws_plan(int N, int B, int nc) {
     WsPlan w;
     w.ntiles = (N + kTile - 1) / kTile;
-    size_t at = 0;
-    auto put = [&](size_t floats) { const size_t o = at; at += (floats * sizeof(float) + 255) & ~(size_t)255; return o; };
-    w.h = put((size_t)64 * N * B);
-    w.tmax = put((size_t)kFeat * w.ntiles * B);
-    w.T = put((size_t)9 * B);
-    w.F = put((size_t)4096 * B);
-    w.logits = put((size_t)nc * B);
-    w.total = at;
+    WsBump ws;
+    w.h = ws.put((size_t)64 * N * B * sizeof(float));
+    w.tmax = ws.put((size_t)kFeat * w.ntiles * B * sizeof(float));
+    w.T = ws.put((size_t)9 * B * sizeof(float));
+    w.F = ws.put((size_t)4096 * B * sizeof(float));
+    w.logits = ws.put((size_t)nc * B * sizeof(float));
+    w.total = ws.at;
     return w;
 }
 

@@ -83,8 +83,8 @@ def edgeconv_param_shapes(layers):
 
 
 class _Model:
-    """What the models share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy, and
-    the check of the input clouds.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``, and ``_count_args()`` where
+    """What the models share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy, the
+    check of the input clouds and the classifiers' forward.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``, and ``_count_args()`` where
     the count is not a function of ``num_classes``."""
 
     def _count_args(self):
@@ -161,6 +161,24 @@ class _Model:
     def _on_device(pts, N, B, on_dev, F=3):
         return pts.reshape(F, N, B) if on_dev else DeviceArray.from_host(np.asfortranarray(pts.reshape(F, N, B, order="F")))
 
+    def _classify(self, clouds, entry, lead, size_args, optional, intermediates):
+        """The forward of a classifier on the checked ``clouds`` (:meth:`_clouds`) through ``fx3d_{entry}_forward``, whose
+        arguments are the parameters, ``lead``, x, N, B, probs, the optional outputs in the order of the table ``optional``
+        (name -> (shape, dtype); allocated and passed with ``intermediates`` only) and the workspace of
+        ``fx3d_{entry}_workspace_bytes(*size_args)``.  Probabilities, or the dict of all outputs, where the input lives."""
+        pts, N, B, on_dev = clouds
+        x = self._on_device(pts, N, B, on_dev)
+        out = {"probs": DeviceArray.empty((self.num_classes, B), np.float32)}
+        if intermediates:
+            out.update({k: DeviceArray.empty(shape, dtype) for k, (shape, dtype) in optional.items()})
+        ws = workspace(_lib.query_bytes(f"fx3d_{entry}_workspace_bytes", *size_args), tag=entry)
+        opt = [out[k].ptr if intermediates else None for k in optional]
+        _lib.call(f"fx3d_{entry}_forward", self._params_dev().ptr, *lead, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        if not on_dev:
+            out = {k: v.to_host() for k, v in out.items()}
+        return out if intermediates else out["probs"]
+
 
 class PointNet(_Model):
     """``PointNet(num_classes=10, K=64)`` (src/models/pointnet.jl:41-60).
@@ -189,21 +207,10 @@ class PointNet(_Model):
         """Class probabilities ``(num_classes, B)`` of the clouds ``X``: a PointCloud, a device array or a numpy array,
         ``(3, N, B)`` or ``(3, N)`` (one cloud).  The result lives where the input lives.  ``intermediates=True``: a dict
         with ``probs``, ``logits`` (num_classes, B), ``stn`` (3, 3, B), ``fstn`` (64, 64, B) and ``pooled`` (1024, B)."""
-        pts, N, B, on_dev = self._clouds(X, "stnKD(3)")
-        x = self._on_device(pts, N, B, on_dev)
-        nc = self.num_classes
-        out = {"probs": DeviceArray.empty((nc, B), np.float32)}
-        if intermediates:
-            out.update(logits=DeviceArray.empty((nc, B), np.float32), stn=DeviceArray.empty((3, 3, B), np.float32),
-                       fstn=DeviceArray.empty((64, 64, B), np.float32), pooled=DeviceArray.empty((1024, B), np.float32))
-        nb = _lib.query_bytes("fx3d_pointnet_workspace_bytes", N, B, nc)
-        ws = workspace(nb, tag="pointnet")
-        opt = [out[k].ptr if intermediates else None for k in ("logits", "stn", "fstn", "pooled")]
-        _lib.call("fx3d_pointnet_forward", self._params_dev().ptr, nc, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
-                  current_stream().handle)
-        if not on_dev:
-            out = {k: v.to_host() for k, v in out.items()}
-        return out if intermediates else out["probs"]
+        _, N, B, _ = clouds = self._clouds(X, "stnKD(3)")
+        nc, f32 = self.num_classes, np.float32
+        optional = {"logits": ((nc, B), f32), "stn": ((3, 3, B), f32), "fstn": ((64, 64, B), f32), "pooled": ((1024, B), f32)}
+        return self._classify(clouds, "pointnet", (nc,), (N, B, nc), optional, intermediates)
 
     __call__ = forward
 
@@ -236,25 +243,14 @@ class DGCNN(_Model):
         ``(3, npoints, B)`` or ``(3, npoints)`` (one cloud).  The result lives where the input lives.
         ``intermediates=True``: a dict with ``probs``, ``logits`` (num_classes, B), ``idx1`` and ``idx2`` (K, N, B) int32,
         0-based, ``x1`` (64, N, B), ``x2`` (256, N, B) and ``pooled`` (1024, B)."""
-        pts, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
+        _, N, B, _ = clouds = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
         if N != self.npoints:
             raise ValueError(f"DGCNN(num_classes, K, npoints={self.npoints}) takes clouds of npoints points, got N={N}: "
                              "MaxPool((npoints,)) is the maximum over a whole cloud only then")
-        x = self._on_device(pts, N, B, on_dev)
-        nc, K = self.num_classes, self.K
-        out = {"probs": DeviceArray.empty((nc, B), np.float32)}
-        if intermediates:
-            out.update(logits=DeviceArray.empty((nc, B), np.float32), idx1=DeviceArray.empty((K, N, B), np.int32),
-                       x1=DeviceArray.empty((64, N, B), np.float32), idx2=DeviceArray.empty((K, N, B), np.int32),
-                       x2=DeviceArray.empty((256, N, B), np.float32), pooled=DeviceArray.empty((1024, B), np.float32))
-        nb = _lib.query_bytes("fx3d_dgcnn_workspace_bytes", N, B, K, nc)
-        ws = workspace(nb, tag="dgcnn")
-        opt = [out[k].ptr if intermediates else None for k in ("logits", "idx1", "x1", "idx2", "x2", "pooled")]
-        _lib.call("fx3d_dgcnn_forward", self._params_dev().ptr, nc, K, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
-                  current_stream().handle)
-        if not on_dev:
-            out = {k: v.to_host() for k, v in out.items()}
-        return out if intermediates else out["probs"]
+        nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
+        optional = {"logits": ((nc, B), f32), "idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32),
+                    "x2": ((256, N, B), f32), "pooled": ((1024, B), f32)}
+        return self._classify(clouds, "dgcnn", (nc, K), (N, B, K, nc), optional, intermediates)
 
     __call__ = forward
 

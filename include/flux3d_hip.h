@@ -877,10 +877,11 @@ FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_
  * 1 <= K <= N - 1, N <= 36864 (the neighbour search's general kernel), B <= 65535, N B K <= 2^31; anything else, a NULL
  * required pointer, a short workspace or one not 256-byte aligned is FX3D_ERR_INVALID_ARG before any launch.
  * probs (num_classes,B) is required; logits (num_classes,B), idx1 and idx2 (K,N,B) int32, x1 (64,N,B; 16-byte aligned),
- * x2 (256,N,B) and pooled (1024,B) are optional (NULL: not written).  Launches on `s` only (two searches through fx3d_knn_ws,
- * two EdgeConv kernels, conv_3, the head), no host synchronisation, no host memory read after the argument check
- * (graph-capturable).  ws: fx3d_dgcnn_workspace_bytes(N, B, K, num_classes) -- x1, x2, the two index arrays, per-tile maxima
- * and the search's scratch. */
+ * x2 (256,N,B) and pooled (1024,B) are optional (NULL: not written).  Launches on `s` only (per EdgeConv what
+ * fx3d_edgeconv_forward below launches -- the search through fx3d_knn_ws and the EdgeConv kernel --, then conv_3 and the
+ * head), no host synchronisation, no host memory read after the argument check (graph-capturable).
+ * ws: fx3d_dgcnn_workspace_bytes(N, B, K, num_classes) -- x1, x2, per-tile maxima, the logits and one EdgeConv workspace (the
+ * neighbour lists and the search's scratch), the larger of the two stages', which they use in turn. */
 FX3D_API fx3d_status fx3d_dgcnn_param_count(int32_t num_classes, int64_t *count);
 FX3D_API fx3d_status fx3d_dgcnn_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N,

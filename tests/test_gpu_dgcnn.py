@@ -2,7 +2,8 @@
 neighbour lists, both EdgeConv outputs, the pooled feature and the logits bit for bit (uint32 views, no element left out), the
 probabilities within 1e-5 relative of the Float64 softmax of the device's own logits -- for the reference's test shape,
 partial tiles and small clouds, K up to N - 1 and beyond the matrix-core search's 32, ModelNet size, NaN input, all-negative
-channels, a captured graph and host arrays; the C entry points' status codes and the workspace bound.
+channels, a captured graph and host arrays; every way of giving or leaving out the optional outputs; the C entry points'
+status codes and the workspace bound.
 
 Every draw of parameters is first held to dgcnn_ref.check_draw on the restatement's own arrays (the relu leaves at least half
 of x1 and x2 alive, every probability lies in [1e-4, 1 - 1e-4]), so that what is compared has something in it."""
@@ -227,6 +228,47 @@ def test_status_codes(gpu_fx):
     for args in ((0, B, K, nc), (N, 0, K, nc), (N, B, 0, nc), (N, B, N, nc), (N, B, K, 0), (36865, 1, K, nc)):
         assert lib.fx3d_dgcnn_workspace_bytes(*args, ctypes.byref(nb)) == INVALID, args
     assert lib.fx3d_dgcnn_workspace_bytes(N, B, K, nc, None) == INVALID
+
+
+@pytest.mark.parametrize("N,B,K", [(65, 2, 3), (2, 1, 1)])
+def test_every_subset_of_optional_outputs(gpu_fx, N, B, K):
+    """fx3d_dgcnn_forward with no optional output, with each of logits, idx1, x1, idx2, x2, pooled given alone, and with all of
+    them: whatever is not given lives in the workspace (or, the neighbour lists, in the EdgeConv stage's own), and nothing of the
+    result may depend on which it is.  probs is the same uint32 array in all eight calls, and each output given alone is the one
+    of the all-given call bit for bit.  A partial second tile (65 points) and the smallest legal cloud (2 points, K = 1).  Every
+    output array starts as all-ones bits (a NaN, index -1), so that an array the call left alone cannot pass."""
+    fx = gpu_fx
+    from flux3d_jl_amd import _lib
+    from flux3d_jl_amd.device import DeviceArray
+    nc = 5
+    m, _ = _model(fx, nc, K, N, seed=7)
+    x = fx.gpu(_cloud(N + K, N, B))
+    shapes = {"logits": ((nc, B), F32), "idx1": ((K, N, B), np.int32), "x1": ((64, N, B), F32), "idx2": ((K, N, B), np.int32),
+              "x2": ((256, N, B), F32), "pooled": ((1024, B), F32)}
+    ws = DeviceArray.empty((_lib.query_bytes("fx3d_dgcnn_workspace_bytes", N, B, K, nc),), np.uint8)
+    assert ws.ptr % 256 == 0
+
+    def run(given):
+        blank = lambda shape, dtype: DeviceArray.from_host(np.full(shape, -1, np.int32).view(dtype))  # noqa: E731
+        out = {k: blank(*shapes[k]) for k in given}
+        probs = blank((nc, B), F32)
+        _lib.call("fx3d_dgcnn_forward", m._params_dev().ptr, nc, K, x.ptr, N, B, probs.ptr,
+                  *[out[k].ptr if k in out else None for k in shapes], ws.ptr, ws.nbytes, None)
+        fx.synchronize()
+        return _bits(probs.to_host()), {k: _bits(v.to_host()) for k, v in out.items()}
+
+    probs_none, _ = run(())
+    assert not np.any(probs_none == 0xFFFFFFFF)
+    alone = {}
+    for k in shapes:
+        probs, out = run((k,))
+        assert np.array_equal(probs, probs_none), f"probs with {k} given differ from probs with nothing given"
+        alone[k] = out[k]
+    probs, every = run(tuple(shapes))
+    assert np.array_equal(probs, probs_none), "probs with every output given differ from probs with nothing given"
+    for k in shapes:
+        assert alone[k].shape == every[k].shape and np.array_equal(alone[k], every[k]), f"{k} given alone differs from the all-given call"
+        assert not np.any(every[k] == 0xFFFFFFFF), f"{k}: elements the call did not write"
 
 
 def test_workspace_is_smaller_than_the_edge_tensor(gpu_fx):

@@ -1,18 +1,15 @@
 #!/usr/bin/env python3
 """EdgeConv(layers, K) on the device (fx.EdgeConv, fx3d_edgeconv_forward) at 32 x 1024 with K = 20: time per call (search +
-kernel) and per kernel of the run-time-width kernel for DGCNN's two instances, [3, 32, 64, 64] and [64, 128, 256], beside
-fx3d_dgcnn_forward's own specialised EdgeConv kernels on the same inputs and parameters, and for one shape DGCNN never ran,
-[64, 64, 128, 256].
+kernel) and per kernel for DGCNN's two stages, [3, 32, 64, 64] and [64, 128, 256], on DGCNN's inputs and parameters, and for
+one shape DGCNN never runs, [64, 64, 128, 256].  (fx3d_dgcnn_forward runs the same kernel; tools/dgcnn_time.py times it there.)
 
-One process; --rounds rounds, each visiting every configuration in turn (generic EdgeConv1, generic EdgeConv2, the DGCNN
-forward, the third shape), so that the two kernels of a pair are measured alternately and share whatever else the host and the
+One process; --rounds rounds, each visiting every configuration in turn, so that they share whatever else the host and the
 device are doing.  Per visit: device events around --reps unprofiled calls (time per call), then the library's own events
 around each kernel's launch over --kreps calls (fx3d_profile_enable; time per kernel).  After a warm-up of every
-configuration.  Reported per configuration: the median over the rounds and their spread (min, max); per pair the ratio
-generic / specialised of the kernel medians, with the larger of the two relative spreads beside it -- a ratio within that
-spread of 1 says nothing.  The generic outputs are first compared with DGCNN's x1 / x2 bit for bit.  One JSON line per
-configuration and per pair.  For what the run-time widths cost instruction by instruction run it under
-`rocprofv3 --kernel-trace --stats -- python tools/edgeconv_time.py` in a run of its own (tracing adds to the event times).
+configuration.  Reported per configuration: the median over the rounds and their spread (min, max).  The outputs of the two
+DGCNN shapes are first compared with DGCNN's x1 / x2 bit for bit.  One JSON line per configuration.  For a per-kernel table
+run it under `rocprofv3 --kernel-trace --stats -- python tools/edgeconv_time.py` in a run of its own (tracing adds to the
+event times).
 
   python tools/edgeconv_time.py [--rounds 5] [--reps 20] [--kreps 10] [--warmup 3] [--no-third]
 """
@@ -49,8 +46,8 @@ def flop(layers):
     return 2 * sum(ci * co for ci, co in zip(cins, layers[1:])) * K * N * B
 
 
-def visit(run, kernels, reps, kreps):
-    """(ms per call, {kernel: ms per launch}) of one visit of a configuration."""
+def visit(run, reps, kreps):
+    """(ms per call, ms per kernel launch) of one visit of a configuration."""
     e0, e1 = fx.Event(), fx.Event()
     e0.record()
     for _ in range(reps):
@@ -62,9 +59,9 @@ def visit(run, kernels, reps, kreps):
     for _ in range(kreps):
         run()
     fx.synchronize()
-    per_kernel = {k: kernel_ms(k) for k in kernels}
+    ms = kernel_ms("edgeconv")
     _lib.call("fx3d_profile_enable", 0)
-    return call_ms, per_kernel
+    return call_ms, ms
 
 
 def summary(values):
@@ -95,42 +92,26 @@ def main():
     e3 = fx.EdgeConv(L3, K).load(edgeconv_ref.random_params(L3, seed=1))
     same = (np.array_equal(e1(xd).to_host().view(np.uint32), x1.to_host().view(np.uint32))
             and np.array_equal(e2(x1).to_host().view(np.uint32), inter["x2"].to_host().view(np.uint32)))
-    print(json.dumps({"shape": f"{B} x {N}", "K": K, "generic_outputs_equal_dgcnn_x1_x2_bit_for_bit": bool(same)}), flush=True)
+    print(json.dumps({"shape": f"{B} x {N}", "K": K, "outputs_equal_dgcnn_x1_x2_bit_for_bit": bool(same)}), flush=True)
     assert same
-    configs = [("edgeconv [3,32,64,64]", lambda: e1(xd), ("edgeconv",)),
-               ("edgeconv [64,128,256]", lambda: e2(x1), ("edgeconv",)),
-               ("dgcnn forward", lambda: dg(xd), ("dgcnn_edgeconv1", "dgcnn_edgeconv2")),
-               ("edgeconv [64,64,128,256]", lambda: e3(x1), ("edgeconv",))][:3 if a.no_third else 4]
-    for _, run, _ in configs:
+    configs = [(L1, lambda: e1(xd)), (L2, lambda: e2(x1)), (L3, lambda: e3(x1))][:2 if a.no_third else 3]
+    for _, run in configs:
         for _ in range(a.warmup):
             run()
     fx.synchronize()
-    calls = {name: [] for name, _, _ in configs}
-    kern = {}
+    calls, kern = {}, {}
     for _ in range(a.rounds):
-        for name, run, kernels in configs:
-            call_ms, per_kernel = visit(run, kernels, a.reps, a.kreps)
-            calls[name].append(call_ms)
-            for k, ms in per_kernel.items():
-                kern.setdefault((name, k), []).append(ms)
-    rows = {}
-    for (name, k), values in kern.items():
-        label = name if k == "edgeconv" else k
-        rows[label] = summary(values)
-        row = {"config": label, "kernel_ms": rows[label]}
-        if k == "edgeconv":
-            layers = json.loads(name.split(" ", 1)[1])
-            row["call_ms_search_and_kernel"] = summary(calls[name])
-            row["GFLOP"] = round(flop(layers) / 1e9, 3)
-            row["kernel_TFLOPs"] = round(flop(layers) / (rows[label]["median"] * 1e-3) / 1e12, 2)
-            row["kernel_share_of_f32_matrix_peak"] = round(flop(layers) / (rows[label]["median"] * 1e-3) / PEAK_F32_MATRIX, 4)
-        else:
-            row["dgcnn_forward_call_ms"] = summary(calls[name])
-        print(json.dumps(row), flush=True)
-    for generic, special in (("edgeconv [3,32,64,64]", "dgcnn_edgeconv1"), ("edgeconv [64,128,256]", "dgcnn_edgeconv2")):
-        g, s = rows[generic], rows[special]
-        print(json.dumps({"pair": f"{generic} / {special}", "ratio_generic_over_specialised": round(g["median"] / s["median"], 4),
-                          "largest_relative_spread_of_the_two": max(g["spread"], s["spread"])}), flush=True)
+        for layers, run in configs:
+            call_ms, ms = visit(run, a.reps, a.kreps)
+            calls.setdefault(str(layers), []).append(call_ms)
+            kern.setdefault(str(layers), []).append(ms)
+    for layers, _ in configs:
+        k = summary(kern[str(layers)])
+        print(json.dumps({"config": "edgeconv " + json.dumps(layers, separators=(",", ":")), "kernel_ms": k,
+                          "call_ms_search_and_kernel": summary(calls[str(layers)]), "GFLOP": round(flop(layers) / 1e9, 3),
+                          "kernel_TFLOPs": round(flop(layers) / (k["median"] * 1e-3) / 1e12, 2),
+                          "kernel_share_of_f32_matrix_peak": round(flop(layers) / (k["median"] * 1e-3) / PEAK_F32_MATRIX, 4)}),
+              flush=True)
 
 
 if __name__ == "__main__":
