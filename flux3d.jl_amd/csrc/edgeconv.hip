@@ -28,9 +28,6 @@ using namespace fx3d::mlp;
 
 namespace {
 
-constexpr int kMaxLayers = 4;     // conv_bn_blocks of one EdgeConv
-constexpr int kMaxF = 128;        // input features: an edge row has 2 F channels, one image row of stride 258 at most
-constexpr int kMaxWidth = 256;    // 8 slabs of 32 channels = 2 per wave = 64 VGPRs of running maxima per lane
 constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // two images of the widest stride: 132 KB of the CU's 160 KB
 
 struct EdgeConvArgs {
@@ -161,24 +158,6 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_kernel(const EdgeConvArgs
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------
-fx3d_status check_layers(const char *fn, const int32_t *layers, int32_t nlayers) {
-    FX3D_REQUIRE(layers != nullptr, "%s: layers is NULL", fn);
-    if (nlayers < 2 || nlayers > kMaxLayers + 1) {
-        set_error("%s: layers must hold F and 1 to %d widths, got %d entries", fn, kMaxLayers, nlayers);
-        return FX3D_ERR_UNSUPPORTED;
-    }
-    if (layers[0] < 1 || layers[0] > kMaxF) {
-        set_error("%s: layers[0] = F must be in [1, %d] (an edge row has 2 F channels), got %d", fn, kMaxF, layers[0]);
-        return FX3D_ERR_UNSUPPORTED;
-    }
-    for (int i = 1; i < nlayers; ++i)
-        if (layers[i] < 1 || layers[i] > kMaxWidth) {
-            set_error("%s: layers[%d] must be in [1, %d], got %d", fn, i, kMaxWidth, layers[i]);
-            return FX3D_ERR_UNSUPPORTED;
-        }
-    return FX3D_OK;
-}
-
 // the LDS images: one stride for all, from the widest layer input
 void lds_plan(const int32_t *layers, int nlayers, EdgeConvArgs *a, int *ld, size_t *bytes) {
     int widest = 2 * layers[0];

@@ -1,0 +1,371 @@
+// EdgeConv(layers, K): the gradient with respect to the input x, test-mode BatchNorm, in one fused kernel (gfx950).
+// include/flux3d_hip.h ("EdgeConv input adjoint") states the definition; tests/edgeconv_bwd_ref.py restates it on the host.
+// The neighbours are constants (CreateSingleKNNGraph is @nograd), so the gradient of point n depends on the K edge rows of
+// point n alone: no scatter, no inverse lists, no atomics.  The arithmetic is the forward's contract (mlp_common.h), transposed.
+//
+// Per call: the search and / or the forward if the caller does not give idx / out (edgeconv_run and fx3d_knn_ws, as
+// fx3d_edgeconv_forward runs them), transpose_weights (Wt_l[o + cout c] = W_l[c + cin o] for every layer into the workspace, so
+// that the backward contraction over o reads a lane's weights as one row, which is what mfma_slab_rt takes), then
+// edgeconv_bwd_kernel<LD, NH, NS>: one block = 32 NH points of one cloud, 4 waves, looping over the neighbour rank k.
+//   LDS: max(L, 2) images of 32 NH rows and one row stride LD = 66 / 130 / 258, the smallest that holds the widest of 2F, c1 .. cL.
+//     img[0] = `rows`: the edge rows, then dz_L (L >= 2), after the last k the sums S.  img[l], 1 <= l < L: a_l, overwritten in
+//     place by dz_l on the way back (the lane that produces an element is the only one that reads its a_l).  L = 1: dz_1 in img[1].
+//     64 points (NH = 2) where that fits 132 KB, else 32 (NH = 1): four images of stride 258 are 132 KB at 32 points.
+//   Registers, per lane (one channel, 16 points per 32-point half, NS slabs per wave as in the forward's fold: the strides 66
+//   and 130 hold 128 channels = one slab per wave at most, the stride 258 two):
+//     tgt  the forward's out where it is positive, else NaN -- and NaN from the k on that reproduced it: the first k that equals
+//          the maximum takes the gradient, no later one does ("already chosen" is the NaN; NaN == anything is false);
+//     dzg  (gout gamma_L) / sd_L, what dz_L is where k is chosen;  dz0 = (+0 gamma_L) / sd_L, what it is elsewhere;
+//     S    the running sums over k of d_0, for the lane's channel of the 2F.
+//   Per k: gather the edge rows; the hidden layers image to image and the last layer slab by slab exactly as edgeconv_kernel
+//     computes them (mfma_slab_rt, epilogue<kBnRelu>: the forward's bits); compare with tgt and write dz_L; walk back: for
+//     l = L .. 2 d_{l-1} = the chain over ALL o of dz_l with Wt_l, masked by a_{l-1} > 0, times gamma_{l-1}, divided by sd_{l-1}
+//     into a_{l-1}'s place; d_0 from dz_1 and Wt_1, added to S.  After the last k: S to `rows`, gx[f] = S[f] - S[F + f].
+//   A slab beyond a width's last channel: its lanes read the last channel's parameters, run the wave's MFMAs and write nothing.
+//   Rows beyond the cloud's last point are zeros with tgt = NaN: computed, never written.
+#include "mlp_common.h"
+
+using namespace fx3d;
+using namespace fx3d::mlp;
+
+namespace {
+
+constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // as edgeconv.hip: 132 KB of the CU's 160 KB
+constexpr int kWaves = kPtThreads / 64;
+
+struct EdgeConvBwdArgs {
+    const float *x;      // (F, N, B)
+    const int32_t *idx;  // (K, N, B), 0-based
+    const float *out;    // (cL, N, B): the forward's
+    const float *gout;   // (cL, N, B)
+    float *gx;           // (F, N, B)
+    Conv c[kMaxLayers];
+    const float *wt[kMaxLayers];  // Wt_l[o + cout c]
+    int w[kMaxLayers + 1];        // F, c1, ..., cL
+    int nl, cout;                 // L, cL
+    int N, K;
+};
+
+struct TransposeArgs {
+    const float *W[kMaxLayers];
+    float *wt[kMaxLayers];
+    int cin[kMaxLayers], cout[kMaxLayers];
+};
+
+// Wt_l[o + cout c] = W_l[c + cin o]; blockIdx.y: the layer
+__global__ __launch_bounds__(256) void transpose_weights(const TransposeArgs t) {
+    const int l = blockIdx.y;
+    const float *W = l == 0 ? t.W[0] : l == 1 ? t.W[1] : l == 2 ? t.W[2] : t.W[3];
+    float *wt = l == 0 ? t.wt[0] : l == 1 ? t.wt[1] : l == 2 ? t.wt[2] : t.wt[3];
+    const int cin = l == 0 ? t.cin[0] : l == 1 ? t.cin[1] : l == 2 ? t.cin[2] : t.cin[3];
+    const int cout = l == 0 ? t.cout[0] : l == 1 ? t.cout[1] : l == 2 ? t.cout[2] : t.cout[3];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cin * cout; i += gridDim.x * blockDim.x) {
+        const int c = i / cout, o = i - c * cout;
+        wt[i] = W[c + cin * o];
+    }
+}
+
+// gather_centre and gather_diff (mlp_common.h) in one pass, for a tile of T points: both halves are written with every k
+template <int T>
+__device__ __forceinline__ void gather_rows(float *rows, int ld, const float *xb, const int32_t *ib, int F, int N, int K, int k,
+                                            int p0, int nvalid) {
+    const float rf = 1.0f / (float)F;
+    for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
+        const int p = edge_row_of(i, rf), c = i - p * F;
+        float xc = 0.0f, v = 0.0f;
+        if (p < nvalid) {
+            xc = xb[(size_t)(p0 + p) * F + c];
+            int jn = ib[(size_t)p * K + k];
+            jn = (unsigned int)jn < (unsigned int)N ? jn : p0 + p;
+            v = xb[(size_t)jn * F + c] - xc;
+        }
+        rows[p * ld + c] = xc;
+        rows[p * ld + F + c] = v;
+    }
+}
+
+// one hidden layer forward, image to image: conv_item of edgeconv.hip on the wave's slabs
+template <int LD, int NH>
+__device__ __forceinline__ void hidden_fwd(const float *in, float *out, int cin, int cout, const Conv &c) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    for (int sl = wave; sl * 32 < cout; sl += kWaves) {
+        const int o = sl * 32 + j, oc = min(o, cout - 1);
+        f32x16 acc[NH];
+#pragma unroll
+        for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
+        mfma_slab_rt<LD, NH>(in, c.W + (size_t)cin * oc, cin, h, j, acc);
+        const float bi = c.b[oc], g = c.bn.g[oc], be = c.bn.b[oc], mu = c.bn.m[oc], sd = sqrtf(c.bn.v[oc] + kBnEps);
+        if (o < cout) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) out[(t * 32 + mfma_row(r, h)) * LD + o] = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd);
+        }
+    }
+}
+
+// one hidden layer backward: d[p][c] = the chain over o < cout of dz[p][o] Wt[o + cout c] for c < cin, then in a's place
+// dz'[p][c] = ((a[p][c] > 0 ? d : +0) gamma[c]) / sd[c] with the BatchNorm of the layer that made a
+template <int LD, int NH>
+__device__ __forceinline__ void hidden_bwd(const float *dz, float *a, int cout, int cin, const float *__restrict__ wt, const Bn &bn) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    for (int sl = wave; sl * 32 < cin; sl += kWaves) {
+        const int c = sl * 32 + j, cc = min(c, cin - 1);
+        f32x16 acc[NH];
+#pragma unroll
+        for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
+        mfma_slab_rt<LD, NH>(dz, wt + (size_t)cout * cc, cout, h, j, acc);
+        const float g = bn.g[cc], sd = sqrtf(bn.v[cc] + kBnEps);
+        if (c < cin) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    float *e = a + (t * 32 + mfma_row(r, h)) * LD + c;
+                    const float d = *e > 0.0f ? acc[t][r] : 0.0f;
+                    *e = (d * g) / sd;
+                }
+        }
+    }
+}
+
+template <int LD, int NH, int NS>
+__global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const EdgeConvBwdArgs a) {
+    extern __shared__ float lds[];
+    constexpr int T = 32 * NH, IMG = T * LD;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const int b = blockIdx.y, p0 = blockIdx.x * T;
+    const int nvalid = min(T, a.N - p0);
+    const int F = a.w[0], L = a.nl, cout = a.cout;
+    const float *xb = a.x + (size_t)b * a.N * F;
+    const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
+    float *rows = lds;
+    float *dzl = L == 1 ? lds + IMG : lds;  // where dz_L goes
+    const float nan = __int_as_float(0x7fc00000);
+    // the layers by wave-uniform selects among the kernel arguments (a constant index in every access, as edgeconv_kernel)
+    const Conv cl = L == 1 ? a.c[0] : L == 2 ? a.c[1] : L == 3 ? a.c[2] : a.c[3];
+    const int cinl = L == 1 ? 2 * F : L == 2 ? a.w[1] : L == 3 ? a.w[2] : a.w[3];  // the last layer's input width
+
+    f32x16 tgt[NS][NH], dzg[NS][NH], S[NS][NH];
+    float dz0[NS];
+    {
+        const size_t base = ((size_t)b * a.N + p0) * cout;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int sl = wave + s * kWaves;
+            dz0[s] = 0.0f;
+#pragma unroll
+            for (int t = 0; t < NH; ++t) S[s][t] = tgt[s][t] = dzg[s][t] = f32x16{0};
+            if (sl * 32 >= cout) continue;  // wave-uniform
+            const int oc = min(sl * 32 + j, cout - 1);
+            const float g = cl.bn.g[oc], sd = sqrtf(cl.bn.v[oc] + kBnEps);
+            dz0[s] = (0.0f * g) / sd;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    const int p = t * 32 + mfma_row(r, h);
+                    float ov = nan, gv = 0.0f;
+                    if (p < nvalid) {
+                        ov = a.out[base + (size_t)p * cout + oc];
+                        gv = a.gout[base + (size_t)p * cout + oc];
+                    }
+                    tgt[s][t][r] = ov > 0.0f ? ov : nan;
+                    dzg[s][t][r] = (gv * g) / sd;
+                }
+        }
+    }
+    for (int k = 0; k < a.K; ++k) {
+        // (`rows` was last read before a barrier of the previous k: by its first layer, or by hidden_bwd of layer L as dz_L)
+        gather_rows<T>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
+        __syncthreads();
+        const float *src = rows;
+        int cin = 2 * F;
+        for (int i = 0; i + 1 < L; ++i) {
+            const Conv c = i == 0 ? a.c[0] : i == 1 ? a.c[1] : a.c[2];
+            const int co = i == 0 ? a.w[1] : i == 1 ? a.w[2] : a.w[3];
+            float *dst = lds + (i + 1) * IMG;
+            hidden_fwd<LD, NH>(src, dst, cin, co, c);
+            __syncthreads();
+            src = dst;
+            cin = co;
+        }
+        // the last layer, compared with the forward's maxima: dz_L
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int sl = wave + s * kWaves;
+            if (sl * 32 >= cout) continue;  // wave-uniform
+            const int o = sl * 32 + j, oc = min(o, cout - 1);
+            f32x16 acc[NH];
+#pragma unroll
+            for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
+            mfma_slab_rt<LD, NH>(src, cl.W + (size_t)cinl * oc, cinl, h, j, acc);
+            const float bi = cl.b[oc], g = cl.bn.g[oc], be = cl.bn.b[oc], mu = cl.bn.m[oc], sd = sqrtf(cl.bn.v[oc] + kBnEps);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    const bool first = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd) == tgt[s][t][r];
+                    if (o < cout) dzl[(t * 32 + mfma_row(r, h)) * LD + o] = first ? dzg[s][t][r] : dz0[s];
+                    tgt[s][t][r] = first ? nan : tgt[s][t][r];
+                }
+        }
+        __syncthreads();
+        // the way back: dz_l in img[l] (dz_L in dzl), d_{l-1} into a_{l-1}'s place
+        for (int l = L; l >= 2; --l) {
+            const float *dz = l == L ? dzl : lds + l * IMG;
+            const int co = l == 2 ? a.w[2] : l == 3 ? a.w[3] : a.w[4];
+            const int ci = l == 2 ? a.w[1] : l == 3 ? a.w[2] : a.w[3];
+            const float *wt = l == 2 ? a.wt[1] : l == 3 ? a.wt[2] : a.wt[3];
+            const Bn bn = l == 2 ? a.c[0].bn : l == 3 ? a.c[1].bn : a.c[2].bn;
+            hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn);
+            __syncthreads();
+        }
+        // d_0 from dz_1 (img[1] for every L), added to the sums over k
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int sl = wave + s * kWaves;
+            if (sl * 32 >= 2 * F) continue;  // wave-uniform
+            const int cc = min(sl * 32 + j, 2 * F - 1);
+            f32x16 acc[NH];
+#pragma unroll
+            for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
+            mfma_slab_rt<LD, NH>(lds + IMG, a.wt[0] + (size_t)a.w[1] * cc, a.w[1], h, j, acc);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) S[s][t][r] = S[s][t][r] + acc[t][r];
+        }
+        // (img[1] is written again after the barrier that follows the next gather, which a wave reaches after these reads)
+    }
+    // S to `rows` (last read before a barrier above), then gx[f] = S[f] - S[F + f]
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int c = (wave + s * kWaves) * 32 + j;
+        if (c >= 2 * F) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int t = 0; t < NH; ++t) rows[(t * 32 + mfma_row(r, h)) * LD + c] = S[s][t][r];
+    }
+    __syncthreads();
+    float *gb = a.gx + ((size_t)b * a.N + p0) * F;
+    const float rf = 1.0f / (float)F;
+    for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
+        const int p = edge_row_of(i, rf), c = i - p * F;
+        if (p < nvalid) gb[(size_t)p * F + c] = rows[p * LD + c] - rows[p * LD + F + c];
+    }
+}
+
+// ---- the host side -------------------------------------------------------------------------------------------------
+// the LDS images: one stride for all, from the widest of 2F, c1 .. cL; 64 points per block where they fit, else 32
+void lds_plan(const int32_t *layers, int nlayers, int *ld, int *nh, size_t *bytes) {
+    int widest = 2 * layers[0];
+    for (int i = 1; i < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
+    *ld = widest <= 64 ? 66 : widest <= 128 ? kLd : 258;
+    const int L = nlayers - 1, nimg = L >= 2 ? L : 2;
+    const size_t half = (size_t)nimg * 32 * *ld * sizeof(float);
+    *nh = 2 * half <= kMaxLds ? 2 : 1;
+    *bytes = *nh * half;
+}
+
+// the workspace: the forward's own (the search's scratch) | the neighbour lists (K, N, B) | out (cL, N, B) | the transposed weights
+struct WsPlan { size_t fwd, fwd_bytes, idx, out, wt, total; };
+fx3d_status ws_plan(const int32_t *layers, int nlayers, int N, int B, int K, WsPlan *w) {
+    WsBump ws;
+    const fx3d_status rc = edgeconv_workspace_bytes(layers[0], N, B, K, &w->fwd_bytes);
+    if (rc != FX3D_OK) return rc;
+    w->fwd = ws.put(w->fwd_bytes);
+    w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
+    w->out = ws.put((size_t)layers[nlayers - 1] * N * B * sizeof(float));
+    size_t nw = 0;
+    for (int i = 1; i < nlayers; ++i) nw += (size_t)(i == 1 ? 2 * layers[0] : layers[i - 1]) * layers[i];
+    w->wt = ws.put(nw * sizeof(float));
+    w->total = ws.at;
+    return FX3D_OK;
+}
+
+template <int LD, int NH, int NS>
+fx3d_status launch(const EdgeConvBwdArgs &a, size_t lds_bytes, int B, hipStream_t st) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&edgeconv_bwd_kernel<LD, NH, NS>), (int)kMaxLds, "edgeconv_bwd_kernel");
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof("edgeconv_bwd", st);
+    const int T = 32 * NH;
+    hipLaunchKernelGGL((edgeconv_bwd_kernel<LD, NH, NS>), dim3((a.N + T - 1) / T, B), dim3(kPtThreads), lds_bytes, st, a);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+fx3d_status fx3d_edgeconv_bwd_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B, size_t *bytes) {
+    const char *fn = "fx3d_edgeconv_bwd_workspace_bytes";
+    FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
+    fx3d_status rc = check_layers(fn, layers, nlayers);
+    if (rc != FX3D_OK) return rc;
+    if ((rc = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return rc;
+    WsPlan w;
+    if ((rc = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return rc;
+    *bytes = w.total;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x, int32_t N,
+                              int32_t B, const int32_t *idx, const float *out, const float *gout, float *gx, void *ws,
+                              size_t ws_bytes, fx3d_stream_t s) {
+    const char *fn = "fx3d_edgeconv_bwd";
+    FX3D_REQUIRE(params_dev && x && gout && gx && ws, "%s: params_dev, x, gout, gx and ws must not be NULL", fn);
+    fx3d_status r = check_layers(fn, layers, nlayers);
+    if (r != FX3D_OK) return r;
+    if ((r = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return r;
+    WsPlan w;
+    if ((r = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return r;
+    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_edgeconv_bwd_workspace_bytes says %zu", fn, ws_bytes, w.total);
+    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
+
+    char *wsb = static_cast<char *>(ws);
+    hipStream_t st = as_stream(s);
+    EdgeConvBwdArgs a{};
+    edgeconv_layout(params_dev, layers, nlayers, a.c);
+    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
+    a.nl = nlayers - 1; a.cout = layers[nlayers - 1];
+    a.N = N; a.K = K; a.x = x; a.gout = gout; a.gx = gx;
+    // the forward's part: the lists and / or out where the caller has none (the search is deterministic: the forward's lists)
+    int32_t *ws_idx = reinterpret_cast<int32_t *>(wsb + w.idx);
+    float *ws_out = reinterpret_cast<float *>(wsb + w.out);
+    if (!out) {
+        if ((r = edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx, ws_out, idx ? nullptr : ws_idx, wsb + w.fwd, s, "edgeconv")) != FX3D_OK) return r;
+    } else if (!idx) {
+        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, ws_idx, nullptr, wsb + w.fwd, w.fwd_bytes, s)) != FX3D_OK) return r;
+    }
+    a.idx = idx ? idx : ws_idx;
+    a.out = out ? out : ws_out;
+    // the transposed weights
+    TransposeArgs t{};
+    float *wt = reinterpret_cast<float *>(wsb + w.wt);
+    int most = 1;
+    for (int l = 0; l < a.nl; ++l) {
+        t.W[l] = a.c[l].W;
+        t.cin[l] = l == 0 ? 2 * layers[0] : layers[l];
+        t.cout[l] = layers[l + 1];
+        t.wt[l] = wt;
+        a.wt[l] = wt;
+        wt += (size_t)t.cin[l] * t.cout[l];
+        most = t.cin[l] * t.cout[l] > most ? t.cin[l] * t.cout[l] : most;
+    }
+    hipLaunchKernelGGL(transpose_weights, dim3((most + 255) / 256, a.nl), dim3(256), 0, st, t);
+    FX3D_LAUNCH_CHECK();
+    size_t lds_bytes = 0;
+    int ld = 0, nh = 0;
+    lds_plan(layers, nlayers, &ld, &nh, &lds_bytes);
+    // the stride 66 holds 64 channels at most: one slab per wave there
+    switch (ld) {
+        case 66: return launch<66, 2, 1>(a, lds_bytes, B, st);  // (four images are 68 KB: always 64 points)
+        case kLd: return nh == 2 ? launch<kLd, 2, 1>(a, lds_bytes, B, st) : launch<kLd, 1, 1>(a, lds_bytes, B, st);
+        default: return nh == 2 ? launch<258, 2, 2>(a, lds_bytes, B, st) : launch<258, 1, 2>(a, lds_bytes, B, st);
+    }
+}
+
+}  // extern "C"

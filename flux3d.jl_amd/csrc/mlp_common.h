@@ -1,7 +1,7 @@
-// What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip) share: the exact-Float32 contraction on the f32 MFMA, the
+// What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip, edgeconv_bwd.hip) share: the exact-Float32 contraction on the f32 MFMA, the
 // activation and BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, the EdgeConv kernel's gather of
 // the edge rows and fold of the last layer, the two ends of a classifier head, and on the host the walk over the flat
-// parameter buffer, the workspace allocator, the size limits of the neighbour search and the EdgeConv entry DGCNN runs on.
+// parameter buffer, the workspace allocator, the size limits of the neighbour search, the EdgeConv envelope and the EdgeConv entry DGCNN and the adjoint run on.
 // include/flux3d_hip.h ("PointNet inference") states the arithmetic; pointnet.hip's header comment the tile and its LDS banks.
 #pragma once
 #include <cmath>
@@ -306,6 +306,28 @@ inline fx3d_status check_edgeconv_sizes(const char *fn, int32_t N, int32_t B, in
     FX3D_REQUIRE(N <= kMaxN, "%s: N must be at most %d (the neighbour search), got %d", fn, kMaxN, N);
     FX3D_REQUIRE(B <= 65535, "%s: B must be at most 65535, got %d", fn, B);
     FX3D_REQUIRE((long long)N * B * K <= (1ll << 31), "%s: N * B * K must be at most 2^31, got %lld", fn, (long long)N * B * K);
+    return FX3D_OK;
+}
+
+// the envelope of an EdgeConv (edgeconv.hip, edgeconv_bwd.hip), for the entry point `fn`
+constexpr int kMaxLayers = 4;     // conv_bn_blocks of one EdgeConv
+constexpr int kMaxF = 128;        // input features: an edge row has 2 F channels, one image row of stride 258 at most
+constexpr int kMaxWidth = 256;    // 8 slabs of 32 channels = 2 per wave = 64 VGPRs of running maxima per lane
+inline fx3d_status check_layers(const char *fn, const int32_t *layers, int32_t nlayers) {
+    FX3D_REQUIRE(layers != nullptr, "%s: layers is NULL", fn);
+    if (nlayers < 2 || nlayers > kMaxLayers + 1) {
+        set_error("%s: layers must hold F and 1 to %d widths, got %d entries", fn, kMaxLayers, nlayers);
+        return FX3D_ERR_UNSUPPORTED;
+    }
+    if (layers[0] < 1 || layers[0] > kMaxF) {
+        set_error("%s: layers[0] = F must be in [1, %d] (an edge row has 2 F channels), got %d", fn, kMaxF, layers[0]);
+        return FX3D_ERR_UNSUPPORTED;
+    }
+    for (int i = 1; i < nlayers; ++i)
+        if (layers[i] < 1 || layers[i] > kMaxWidth) {
+            set_error("%s: layers[%d] must be in [1, %d], got %d", fn, i, kMaxWidth, layers[i]);
+            return FX3D_ERR_UNSUPPORTED;
+        }
     return FX3D_OK;
 }
 

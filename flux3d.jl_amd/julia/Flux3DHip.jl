@@ -1679,5 +1679,36 @@ function edgeconv_forward(m::EdgeConv, X::HipArray{Float32,3}; idx::Union{Nothin
 end
 (m::EdgeConv)(X::HipArray{Float32,3}) = edgeconv_forward(m, X)
 
+# The gradient of sum(gout .* m(X)) with respect to X (include/flux3d_hip.h "EdgeConv input adjoint"): test-mode BatchNorm, the
+# neighbours constants as CreateSingleKNNGraph is @nograd.  idx, out: the forward's lists and result (edgeconv_forward with
+# return_idx = true); either may be left out and is then computed again.
+# There is deliberately NO Zygote.@adjoint on (m::EdgeConv)(X): it would have to return `nothing` for the parameters, and a user
+# who trains through it would get silently zero weight gradients.  It waits for the parameter gradients.
+function edgeconv_input_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{Float32,3};
+                                 idx::Union{Nothing,HipArray{Int32,3}} = nothing, out::Union{Nothing,HipArray{Float32,3}} = nothing)
+    layers = Int32.(collect(m.layers))
+    nl = length(layers)
+    F, N, B = size(X)
+    K = m.K
+    cL = Int(layers[end])
+    F == layers[1] || error("EdgeConv($(m.layers), $K) takes $(layers[1]) channels per point, got $F")
+    (1 <= K && K + 1 <= N) || error("EdgeConv needs 1 <= K <= N - 1, got K = $K, N = $N")
+    size(gout) == (cL, N, B) || error("gout must be ($cL, $N, $B), got $(size(gout))")
+    out === nothing || size(out) == (cL, N, B) || error("out must be ($cL, $N, $B), got $(size(out))")
+    idx === nothing || size(idx) == (K, N, B) || error("idx must be ($K, $N, $B), got $(size(idx))")
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_edgeconv_bwd_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
+                                                       Int32(B)::Int32, nb::Ref{Csize_t})::Int32)
+    pd = hip(edgeconv_params(m))
+    ws = workspace(nb[])
+    gx = HipArray{Float32}(undef, F, N, B)
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_edgeconv_bwd(pd.ptr::Ptr{Cvoid}, layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, X.ptr::Ptr{Cvoid},
+                                       Int32(N)::Int32, Int32(B)::Int32, opt(idx)::Ptr{Cvoid}, opt(out)::Ptr{Cvoid},
+                                       gout.ptr::Ptr{Cvoid}, gx.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                       DEFAULT_STREAM::Stream)::Int32)
+    return gx
+end
+
 
 end # module

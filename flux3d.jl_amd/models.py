@@ -223,7 +223,12 @@ class DGCNN(_Model):
     ``npoints`` is the window of the reference's ``MaxPool((npoints,))`` over the (N, 1024, B) output of conv_3: only with
     N == npoints is that the one maximum per cloud and channel whose reshape gives the (1024, B) the classifier takes -- a
     multiple of npoints leaves several windows per cloud, which the reshape folds into the batch, anything else drops
-    points.  ``forward`` therefore raises ``ValueError`` for clouds of any other size."""
+    points.  ``forward`` therefore raises ``ValueError`` for clouds of any other size.
+
+    Forward only.  The gradient of the two EdgeConv stages with respect to the input is a composition of
+    :meth:`EdgeConv.input_grad`: with ``ec1 = EdgeConv([3, 32, 64, 64], K)`` and ``ec2 = EdgeConv([64, 128, 256], K)`` loaded
+    with the ``ec1.`` / ``ec2.`` arrays, and ``idx1, x1, idx2, x2`` of ``forward(X, intermediates=True)``,
+    ``ec1.input_grad(X, ec2.input_grad(x1, g, idx2, x2), idx1, x1)`` is the gradient of ``sum(g * x2)`` with respect to ``X``."""
 
     _NAME, _COUNT_FN = "DGCNN", "fx3d_dgcnn_param_count"
 
@@ -342,3 +347,50 @@ class EdgeConv(_Model):
         return (out, used) if return_idx else out
 
     __call__ = forward
+
+    def _like_out(self, a, name, N, B, on_dev):
+        """``gout`` / ``out`` after its checks, as (cL, N, B): a device array, or a Float32 host array still to be uploaded.
+        It must live where ``X`` lives."""
+        cL = self.layers[-1]
+        ok = ((cL, N, B),) + (((cL, N),) if B == 1 else ())
+        if is_device(a) != on_dev:
+            raise TypeError(f"{name} must live where X lives ({'the device' if on_dev else 'the host'})")
+        if on_dev:
+            if a.dtype != np.float32:
+                raise TypeError(f"device {name} must be Float32, got {a.dtype}")
+            if tuple(a.shape) not in ok:
+                raise ValueError(f"{name} must be ({cL}, {N}, {B}), got {tuple(a.shape)}")
+            return a.reshape(cL, N, B)
+        a = np.asarray(a)
+        if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise TypeError(f"{name} must hold real numbers, got {a.dtype}")
+        if a.shape not in ok:
+            raise ValueError(f"{name} must be ({cL}, {N}, {B}), got {a.shape}")
+        return np.asfortranarray(a.reshape(cL, N, B, order="F").astype(np.float32))
+
+    def input_grad(self, X, gout, idx=None, out=None):
+        """The gradient ``(F, N, B)`` of ``sum(gout * forward(X))`` with respect to ``X``, with the neighbours held constant
+        as the reference holds them (CreateSingleKNNGraph is @nograd) and BatchNorm in test mode: include/flux3d_hip.h
+        "EdgeConv input adjoint".  ``X`` as in :meth:`forward`; ``gout`` ``(cL, N, B)`` lives where ``X`` lives, and so does
+        the result.  ``idx``: the forward's neighbour lists (``return_idx=True``), ``out``: the forward's result; either may
+        be left out, and is then computed again (the search is deterministic).  An ``out`` that is not this forward's passes
+        gradient only where some k reproduces it.  No parameter gradients: the weights are constants here."""
+        F, K = self.layers[0], self.K
+        if isinstance(X, PointCloud) and F != 3:
+            raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
+        pts, N, B, on_dev = self._clouds(X, f"EdgeConv({self.layers}, {K})", F)
+        if K + 1 > N:
+            raise ValueError(f"EdgeConv needs 1 <= K <= N - 1 (K neighbours besides the point itself), got K={K}, N={N}")
+        layers, nl = self._layers_c()
+        nb = _lib.query_bytes("fx3d_edgeconv_bwd_workspace_bytes", layers, nl, K, N, B)
+        g = self._like_out(gout, "gout", N, B, on_dev)
+        o = None if out is None else self._like_out(out, "out", N, B, on_dev)
+        given = None if idx is None else self._neighbours(idx, N, B)
+        if not on_dev:
+            g, o = DeviceArray.from_host(g), (None if o is None else DeviceArray.from_host(o))
+        x = self._on_device(pts, N, B, on_dev, F)
+        gx = DeviceArray.empty((F, N, B), np.float32)
+        ws = workspace(nb, tag="edgeconv_bwd")
+        _lib.call("fx3d_edgeconv_bwd", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
+                  o.ptr if o is not None else None, g.ptr, gx.ptr, ws.ptr, ws.nbytes, current_stream().handle)
+        return gx if on_dev else gx.to_host()

@@ -889,7 +889,7 @@ FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_cla
                                         float *x2, float *pooled, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 /* ---- EdgeConv inference: (m::EdgeConv)(X) (src/models/dgcnn.jl:11-71) in test mode, for any layer widths -------------------
- * EdgeConv(layers, K) as a layer in its own right, forward only, Float32.  layers: a HOST array [F, c1, ..., cL] of nlayers
+ * EdgeConv(layers, K) as a layer in its own right, Float32 (the gradient with respect to x: "EdgeConv input adjoint" below).  layers: a HOST array [F, c1, ..., cL] of nlayers
  * entries, the argument of the reference's constructor: L = nlayers - 1 conv_bn_blocks (src/models/utils.jl:1-3) 2F -> c1,
  * c1 -> c2, ..., each conv, BatchNorm with its running statistics, relu -- in this order.  x (F,N,B) device, out (cL,N,B):
  *   idx (K,N,B) = the K nearest neighbours of every point among its own cloud's F-dimensional rows, the point itself (rank 0 of
@@ -921,6 +921,43 @@ FX3D_API fx3d_status fx3d_edgeconv_workspace_bytes(const int32_t *layers, int32_
 FX3D_API fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
                                            const float *x, int32_t N, int32_t B, const int32_t *idx_in, float *out,
                                            int32_t *idx_out, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
+/* ---- EdgeConv input adjoint: the gradient of (m::EdgeConv)(X) with respect to X, test mode -----------------------------------
+ * gx (F,N,B) = d sum(gout . out) / d x for out = fx3d_edgeconv_forward(x), in one fused kernel; the arguments up to B are the
+ * forward's.  BatchNorm uses its running statistics.  The neighbours are constants: CreateSingleKNNGraph is @nograd
+ * (src/models/dgcnn.jl:9), so gradient reaches x only through the repeated x_n of cat(X, KNNGraph - X), as fx3d_edge_features_bwd
+ * states, and gx[:,n] depends on the K edge rows of point n alone.  No parameter gradients: the weights are constants here.
+ * idx (K,N,B) and out (cL,N,B): the forward's lists and result.  idx == NULL: the search runs as in the forward (it is
+ * deterministic: the lists are the forward's).  out == NULL: the forward runs first, into the workspace.  gout (cL,N,B).
+ * With a_0[k,n,:] = [x_n, x_idx(k,n) - x_n] and a_l = relu(BN(conv_l(a_{l-1}))), the forward's bits, per cloud:
+ *   maximum over k:  d_L[k,n,o] = gout[o,n] if out[o,n] > 0 and k is the smallest k with a_L[k,n,o] == out[o,n] (Float32
+ *     comparison), else +0.  A NaN or non-positive out element passes nothing, and so does one that no k reproduces (defined
+ *     behaviour for an out that did not come from this forward).
+ *   per layer, l = L .. 1:  for l < L first d_l = (a_l > 0) ? d_l : +0;  dz_l = (d_l gamma_l) / sd_l, sd_l = sqrtf(var_l + 1f-5),
+ *     both operations rounded to Float32;  d_{l-1}[k,n,c] = one fmaf chain from +0.0f over ALL o ascending,
+ *     acc = fmaf(dz_l[k,n,o], W_l[c,o], acc).  The forward's contract, transposed: one accumulator per element, no contraction
+ *     split over waves or blocks, none padded with zero channels, no term skipped because it is zero (0 * Inf is NaN).
+ *   sum over k:  S[n,c] = sum_k d_0[k,n,c], Float32 additions from +0, k ascending, for the 2F channels;
+ *   gx[f,n] = S[n,f] - S[n,F+f], one Float32 subtraction.
+ * gx is bit-identical to the restatement tests/edgeconv_bwd_ref.py and from run to run, whatever N, B, K and the launch shape;
+ * no float atomics, and no (K N, ., B) array in memory.
+ * Deviation from the reference: NNlib's CPU max-pool adjoint is said to give the gradient to the first element that is
+ * approximately the maximum, cuDNN gives it to an argmax; neither can be run here to settle it.  Here it goes to the first k
+ * that EQUALS the maximum.  (Ties among positive maxima need two edge rows with the same last-layer value: repeated
+ * neighbours, or hidden layers the relu has zeroed.)
+ * Envelope, refusals, status codes and messages are fx3d_edgeconv_forward's: 1 <= L <= 4, 1 <= F <= 128, widths in [1, 256],
+ * else FX3D_ERR_UNSUPPORTED; a bad K, N or B, a NULL required pointer (params_dev, layers, x, gout, gx, ws), a short workspace
+ * or one not 256-byte aligned is FX3D_ERR_INVALID_ARG; each names the offending value and comes before any device work.  An
+ * index outside [0, N) reads the point itself, as in the forward.
+ * Launches on `s` only (the search and / or the forward where idx / out are NULL, one small kernel that lays the weights out
+ * transposed in the workspace, the adjoint kernel), no host synchronisation, no host memory other than `layers` read, and none
+ * after the argument check (graph-capturable).  ws: fx3d_edgeconv_bwd_workspace_bytes(layers, nlayers, K, N, B) -- the forward's
+ * workspace, the lists, out and the transposed weights. */
+FX3D_API fx3d_status fx3d_edgeconv_bwd_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
+                                                       size_t *bytes);
+FX3D_API fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
+                                       int32_t N, int32_t B, const int32_t *idx, const float *out, const float *gout, float *gx,
+                                       void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 #ifdef __cplusplus
 }
