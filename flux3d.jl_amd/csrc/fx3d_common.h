@@ -36,7 +36,26 @@ inline fx3d_status hip_fail(hipError_t e, const char *what, const char *file, in
 // checks the launch itself (configuration errors); execution errors surface at the next sync
 #define FX3D_LAUNCH_CHECK() FX3D_HIP(hipGetLastError())
 
+// Before the first launch of an entry point whose other HIP calls are all kernel launches, AFTER its argument and workspace
+// checks (a bad argument stays FX3D_ERR_INVALID_ARG with or without a device): without a device the entry point returns an
+// error status (FX3D_ERR_NO_DEVICE) instead of launching into nothing.  Not dead code: the device id itself is not used.
+#define FX3D_REQUIRE_DEVICE()            \
+    do {                                 \
+        int dev;                         \
+        FX3D_HIP(hipGetDevice(&dev));    \
+    } while (0)
+
 inline hipStream_t as_stream(fx3d_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- the workspace of an entry point: slots of whole 256-byte lines, in the order they are asked for ------------------------
+struct WsBump {
+    size_t at = 0;
+    size_t put(size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
 
 // Opt a kernel in to more than 64 KiB of dynamic LDS, once per (kernel, device): the attribute is per device, and
 // a process may drive several (runtime.hip).

@@ -287,16 +287,6 @@ struct Cursor {
     }
 };
 
-// ---- the workspace of an entry point: slots of whole 256-byte lines, in the order they are asked for ------------------------
-struct WsBump {
-    size_t at = 0;
-    size_t put(size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 // ---- the sizes an EdgeConv takes (dgcnn.hip, edgeconv.hip), for the entry point `fn` ----------------------------------------
 constexpr int kMaxN = 36864;  // the neighbour search's general kernel holds a query's N distance keys in LDS
 inline fx3d_status check_edgeconv_sizes(const char *fn, int32_t N, int32_t B, int32_t K) {

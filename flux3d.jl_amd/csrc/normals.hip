@@ -246,7 +246,9 @@ int grid_faces(long long n) {
 
 size_t ws_need(int64_t V, int64_t F) {
     const int64_t n = V > F ? V : F;
-    return ((size_t)n * 12 + 255) & ~(size_t)255;
+    WsBump ws;
+    ws.put((size_t)n * 12);  // the raw gradients of the vertices or the faces
+    return ws.at;
 }
 
 fx3d_status check_sizes(const char *fn, int64_t V, int64_t F) {

@@ -24,6 +24,7 @@
 //              key behind every mesh; sorted on the key windows only, so the stable sort leaves each vertex's entries
 //              ascending.  Row starts by binary search.
 #include "fx3d_common.h"
+#include "scan_common.h"
 
 namespace fx3d {
 namespace {
@@ -40,28 +41,6 @@ constexpr int kScanItems = 16;                      // values per thread of a sc
 constexpr int kScanChunk = kThreads * kScanItems;
 constexpr int kScanThreads = 1024;
 constexpr long long kMaxElems = (1ll << 31) - 1;    // positions and counts are uint32 / int32
-
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T *sw, T *total) {  // sw: blockDim.x / kWave values
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave, nw = blockDim.x / kWave;
-    T inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const T u = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += u;
-    }
-    if (lane == kWave - 1) sw[w] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int i = 0; i < nw; ++i) {
-        const T x = sw[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();  // sw is reused by the next call
-    *total = tot;
-    return base + inc - v;
-}
 
 // ---- exclusive scan of n uint32 in place: chunk sums, one block over the sums, chunks again -----------------------
 __global__ __launch_bounds__(kThreads) void td_scan_sums_kernel(const uint32_t *__restrict__ data, long long n,
@@ -89,17 +68,10 @@ __global__ __launch_bounds__(kScanThreads) void td_scan_top_kernel(uint32_t *__r
                                                                    int64_t *__restrict__ total_a,
                                                                    int64_t *__restrict__ total_b) {
     __shared__ uint32_t sw[kScanThreads / kWave];
-    uint32_t carry = 0;
-    for (long long base = 0; base < nb; base += kScanThreads) {
-        const long long e = base + threadIdx.x;
-        uint32_t tot;
-        const uint32_t ex = block_exclusive_scan<uint32_t>(e < nb ? sums[e] : 0u, sw, &tot);
-        if (e < nb) sums[e] = carry + ex;
-        carry += tot;
-    }
+    const uint32_t total = scan_entries<uint32_t, kScanThreads>(nb, [&](long long e) { return sums[e]; }, sums, sw);
     if (threadIdx.x == 0) {
-        if (total_a) *total_a = (int64_t)carry;
-        if (total_b) *total_b = (int64_t)carry;
+        if (total_a) *total_a = (int64_t)total;
+        if (total_b) *total_b = (int64_t)total;
     }
 }
 
@@ -301,23 +273,22 @@ __global__ __launch_bounds__(kThreads) void td_f2e_kernel(const int32_t *__restr
     }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the buffers of one sort of n elements plus the flags of its runs
 struct SortLayout {
     size_t a, b, hist, sums, flag, fsums, count, total;
 };
 SortLayout sort_layout(long long n) {
     const long long nh = (long long)kRadix * sort_tiles(n);
+    WsBump ws;
     SortLayout l;
-    l.a = 0;
-    l.b = l.a + up256(8 * (size_t)n);
-    l.hist = l.b + up256(8 * (size_t)n);
-    l.sums = l.hist + up256(4 * (size_t)nh);
-    l.flag = l.sums + up256(4 * (size_t)scan_chunks(nh));
-    l.fsums = l.flag + up256(4 * (size_t)n);
-    l.count = l.fsums + up256(4 * (size_t)scan_chunks(n));
-    l.total = l.count + 256;
+    l.a = ws.put(8 * (size_t)n);
+    l.b = ws.put(8 * (size_t)n);
+    l.hist = ws.put(4 * (size_t)nh);
+    l.sums = ws.put(4 * (size_t)scan_chunks(nh));
+    l.flag = ws.put(4 * (size_t)n);
+    l.fsums = ws.put(4 * (size_t)scan_chunks(n));
+    l.count = ws.put(8);
+    l.total = ws.at;
     return l;
 }
 
@@ -396,8 +367,9 @@ struct LapLayout {
 LapLayout lap_layout(int64_t E, int64_t V) {
     LapLayout l;
     l.s = sort_layout(2 * E + V);
-    l.raw = l.s.total;
-    l.total = l.raw + up256(4 * (size_t)(V + 1));
+    WsBump ws{l.s.total};  // behind the sort's buffers
+    l.raw = ws.put(4 * (size_t)(V + 1));
+    l.total = ws.at;
     return l;
 }
 
@@ -466,8 +438,9 @@ struct VfLayout {
 VfLayout vf_layout(int32_t Fmax, int32_t B) {
     VfLayout l;
     l.s = sort_layout(3ll * Fmax * B);
-    l.mstart = l.s.total;
-    l.total = l.mstart + up256(4 * ((size_t)B + 1));
+    WsBump ws{l.s.total};  // behind the sort's buffers
+    l.mstart = ws.put(4 * ((size_t)B + 1));
+    l.total = ws.at;
     return l;
 }
 
@@ -477,22 +450,13 @@ __global__ __launch_bounds__(kScanThreads) void td_pack_offsets_kernel(const int
                                                                        const int32_t *__restrict__ nverts, int Fmax, int B,
                                                                        long long *__restrict__ foff, long long *__restrict__ voff) {
     __shared__ long long sw[kScanThreads / kWave];
-    long long cf = 0, cv = 0;
-    for (int base = 0; base < B; base += kScanThreads) {
-        const int b = base + threadIdx.x;
-        long long tf, tv;
-        const long long ef = block_exclusive_scan<long long>(b < B ? clamp_len(faces_len[b], Fmax) : 0, sw, &tf);
-        const long long ev = block_exclusive_scan<long long>(b < B ? (nverts[b] > 0 ? nverts[b] : 0) : 0, sw, &tv);
-        if (b < B) {
-            foff[b] = cf + ef;
-            voff[b] = cv + ev;
-        }
-        cf += tf;
-        cv += tv;
-    }
+    const long long sumf = scan_entries<long long, kScanThreads>(
+        B, [&](long long b) -> long long { return clamp_len(faces_len[b], Fmax); }, foff, sw);
+    const long long sumv = scan_entries<long long, kScanThreads>(
+        B, [&](long long b) -> long long { return nverts[b] > 0 ? nverts[b] : 0; }, voff, sw);
     if (threadIdx.x == 0) {
-        foff[B] = cf;
-        voff[B] = cv;
+        foff[B] = sumf;
+        voff[B] = sumv;
     }
 }
 
@@ -505,6 +469,18 @@ __global__ __launch_bounds__(kThreads) void td_pack_faces_kernel(const int32_t *
         const long long f0 = foff[b], f1 = foff[b + 1];
         if (e < 3 * (f1 - f0) && f1 <= sumF) out[3 * f0 + e] = (int32_t)((long long)faces[g] + voff[b]);
     }
+}
+
+struct PackLayout {
+    size_t foff, voff, total;
+};
+PackLayout pack_layout(int32_t B) {
+    WsBump ws;
+    PackLayout l;
+    l.foff = ws.put(8 * ((size_t)B + 1));
+    l.voff = ws.put(8 * ((size_t)B + 1));
+    l.total = ws.at;
+    return l;
 }
 
 }  // namespace
@@ -527,8 +503,7 @@ fx3d_status fx3d_edges_dev_count(const int32_t *faces_packed, int64_t F, int64_t
     const long long n = 3 * F;
     const SortLayout l = sort_layout(n);
     FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_edges_dev_count: workspace too small");
-    int dev;
-    FX3D_HIP(hipGetDevice(&dev));
+    FX3D_REQUIRE_DEVICE();
     hipStream_t st = as_stream(s);
     char *w = static_cast<char *>(ws);
     auto *a = reinterpret_cast<u64 *>(w + l.a), *b = reinterpret_cast<u64 *>(w + l.b);
@@ -553,8 +528,7 @@ fx3d_status fx3d_edges_dev_emit(const int32_t *faces_packed, int64_t F, int64_t 
     FX3D_REQUIRE(edges && ws && (faces_packed || !faces_to_edges), "fx3d_edges_dev_emit: null pointer");
     const SortLayout l = sort_layout(3 * F);
     FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_edges_dev_emit: workspace too small");
-    int dev;
-    FX3D_HIP(hipGetDevice(&dev));
+    FX3D_REQUIRE_DEVICE();
     hipStream_t st = as_stream(s);
     char *w = static_cast<char *>(ws);
     const int vb = bits_for((u64)V - 1);
@@ -583,8 +557,7 @@ fx3d_status fx3d_laplacian_dev_csr(const int32_t *edges, int64_t E, int64_t V, i
     const long long n = 2 * E + V;
     const LapLayout l = lap_layout(E, V);
     FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_laplacian_dev_csr: workspace too small");
-    int dev;
-    FX3D_HIP(hipGetDevice(&dev));
+    FX3D_REQUIRE_DEVICE();
     hipStream_t st = as_stream(s);
     char *w = static_cast<char *>(ws);
     auto *a = reinterpret_cast<u64 *>(w + l.s.a), *b = reinterpret_cast<u64 *>(w + l.s.b);
@@ -618,8 +591,7 @@ fx3d_status fx3d_vertex_faces_dev(const int32_t *faces_padded, const int32_t *fa
     const long long n = 3ll * Fmax * B;
     const VfLayout l = vf_layout(Fmax, B);
     FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_vertex_faces_dev: workspace too small");
-    int dev;
-    FX3D_HIP(hipGetDevice(&dev));
+    FX3D_REQUIRE_DEVICE();
     hipStream_t st = as_stream(s);
     char *w = static_cast<char *>(ws);
     auto *a = reinterpret_cast<u64 *>(w + l.s.a), *b = reinterpret_cast<u64 *>(w + l.s.b);
@@ -638,7 +610,7 @@ fx3d_status fx3d_vertex_faces_dev(const int32_t *faces_padded, const int32_t *fa
 
 fx3d_status fx3d_faces_padded_to_packed_dev_workspace_bytes(int32_t B, size_t *bytes) {
     FX3D_REQUIRE(bytes && B > 0, "fx3d_faces_padded_to_packed_dev_workspace_bytes: bad arguments B=%d", B);
-    *bytes = 2 * up256(8 * ((size_t)B + 1));
+    *bytes = pack_layout(B).total;
     return FX3D_OK;
 }
 
@@ -648,12 +620,12 @@ fx3d_status fx3d_faces_padded_to_packed_dev(const int32_t *faces_padded, const i
     FX3D_REQUIRE(Fmax > 0 && B > 0 && Fmax < (1 << 29) && sumF > 0 && sumF <= (int64_t)Fmax * B,
                  "fx3d_faces_padded_to_packed_dev: bad sizes Fmax=%d B=%d sumF=%lld", Fmax, B, (long long)sumF);
     FX3D_REQUIRE(faces_padded && faces_len && nverts && faces_packed && ws, "fx3d_faces_padded_to_packed_dev: null pointer");
-    const size_t half = up256(8 * ((size_t)B + 1));
-    FX3D_REQUIRE(ws_bytes >= 2 * half, "fx3d_faces_padded_to_packed_dev: workspace too small");
-    int dev;
-    FX3D_HIP(hipGetDevice(&dev));
+    const PackLayout l = pack_layout(B);
+    FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_faces_padded_to_packed_dev: workspace too small");
+    FX3D_REQUIRE_DEVICE();
     hipStream_t st = as_stream(s);
-    auto *foff = reinterpret_cast<long long *>(ws), *voff = reinterpret_cast<long long *>(static_cast<char *>(ws) + half);
+    char *w = static_cast<char *>(ws);
+    auto *foff = reinterpret_cast<long long *>(w + l.foff), *voff = reinterpret_cast<long long *>(w + l.voff);
     hipLaunchKernelGGL(td_pack_offsets_kernel, dim3(1), dim3(kScanThreads), 0, st, faces_len, nverts, Fmax, B, foff, voff);
     hipLaunchKernelGGL(td_pack_faces_kernel, dim3(grid_for(3ll * Fmax * B)), dim3(kThreads), 0, st, faces_padded, Fmax, B, foff, voff,
                        (long long)sumF, faces_packed);

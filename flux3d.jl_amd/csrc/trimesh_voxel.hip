@@ -35,6 +35,7 @@
 //             node that still tests "kept" explores its subtree depth first -- no work is ever dropped.
 // Every write is a plain store of 1.0f into a grid zeroed by hipMemsetAsync: no atomics, no float sums, deterministic.
 #include "fx3d_common.h"
+#include "scan_common.h"
 
 namespace fx3d {
 namespace {
@@ -90,66 +91,21 @@ __device__ __forceinline__ int depth_bound(const Tri &t, double thr) {
     return K;  // 0 .. kMaxSlotDigits + 1; slots = K ? 4^(K-1) : 0
 }
 
-__device__ __forceinline__ long long block_exclusive_scan(long long v, long long *sw, long long *total) {
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-    long long inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const long long u = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += u;
-    }
-    if (lane == kWave - 1) sw[w] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long run = 0;
-        for (int i = 0; i < (int)blockDim.x / kWave; ++i) {
-            const long long x = sw[i];
-            sw[i] = run;
-            run += x;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    const long long r = sw[w] + inc - v;
-    __syncthreads();  // sw / total are reused by the next call
-    return r;
-}
-
 // launch 1: block b = mesh b.  The scalar range and the mesh's validity.
 __global__ __launch_bounds__(kPlanThreads) void tv_range_kernel(const float *__restrict__ verts, int Vmax,
                                                                 const int32_t *__restrict__ verts_len,
                                                                 MeshInfo *__restrict__ info, uint32_t *bad_dev) {
     const int b = blockIdx.x;
     const int Vb = min(max(verts_len[b], 0), Vmax);
-    const float *vb = verts + (size_t)b * Vmax * 3;
-    float lo = __builtin_inff(), hi = -__builtin_inff();
-    int nan = 0;
-    for (int e = threadIdx.x; e < 3 * Vb; e += kPlanThreads) {
-        const float v = vb[e];
-        nan |= (v != v);
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-    }
-    __shared__ float slo[kPlanThreads / kWave], shi[kPlanThreads / kWave];
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o, kWave));
-        hi = fmaxf(hi, __shfl_xor(hi, o, kWave));
-    }
-    const int anynan = __syncthreads_or(nan);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        slo[threadIdx.x / kWave] = lo;
-        shi[threadIdx.x / kWave] = hi;
-    }
-    __syncthreads();
+    __shared__ float sw[2 * kPlanThreads / kWave];
+    const Range r = block_range<kPlanThreads>(verts + (size_t)b * Vmax * 3, 3 * Vb, sw);
     if (threadIdx.x == 0) {
-        for (int i = 1; i < kPlanThreads / kWave; ++i) {
-            lo = fminf(lo, slo[i]);
-            hi = fmaxf(hi, shi[i]);
-        }
-        const float span = hi - lo;
+        // (a zero lo or hi may carry either sign: span is the same, and a vertex that normalises to -0.0 instead of +0.0
+        //  gives the same sides (dx * dx), the same truncated index 0 and midpoints of the same value)
+        const float span = r.hi - r.lo;
         // finite inputs with 0 < span < inf normalise into [0, 1]; anything else yields a NaN vertex (the reference throws)
-        const bool bad = anynan || Vb == 0 || !(span > 0.0f) || !(span <= 3.402823466e38f);
-        info[b] = MeshInfo{lo, span, bad ? 1 : 0, 0};
+        const bool bad = r.nan || Vb == 0 || !(span > 0.0f) || !(span <= 3.402823466e38f);
+        info[b] = MeshInfo{r.lo, span, bad ? 1 : 0, 0};
         if (bad && bad_dev) atomicAdd(bad_dev, 1u);
     }
 }
@@ -183,7 +139,7 @@ __global__ __launch_bounds__(kPlanThreads) void tv_count_kernel(const float *__r
             badface = 1;
         }
     }
-    const long long ex = block_exclusive_scan(cnt, sw, &stot);
+    const long long ex = block_exclusive_scan_serial(cnt, sw, &stot);
     if (f < Fb) face_off[(size_t)b * Fmax + f] = ex;
     if (__syncthreads_or(badface) && threadIdx.x == 0) {
         if (atomicExch(&info[b].bad, 1) == 0 && bad_dev) atomicAdd(bad_dev, 1u);  // the first to flag the mesh counts it
@@ -207,7 +163,7 @@ __global__ __launch_bounds__(kPlanThreads) void tv_scan_kernel(const int32_t *__
             const int b = (int)(e / (nch + 1)), j = (int)(e % (nch + 1));
             if (!info[b].bad) items = j == 0 ? (long long)min(max(verts_len[b], 0), Vmax) : chunk_tot[(size_t)b * nch + j - 1];
         }
-        const long long ex = block_exclusive_scan(items, sw, &stot);
+        const long long ex = block_exclusive_scan_serial(items, sw, &stot);
         if (e < n) start[e] = carry + ex;
         carry += stot;
     }
@@ -312,17 +268,19 @@ __global__ __launch_bounds__(kSlotThreads) void tv_slots_kernel(const float *__r
 int chunks(int Fmax) { return (Fmax + kPlanThreads - 1) / kPlanThreads; }
 
 // info (B) | face_off (B * Fmax) | chunk_tot (B * nch) | start (B * (nch + 1) + 1)
-size_t ws_layout(int Fmax, int B, size_t *o_face, size_t *o_tot, size_t *o_start) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+struct Layout {
+    size_t info, face, tot, start, total;
+};
+Layout ws_layout(int Fmax, int B) {
     const size_t nch = (size_t)chunks(Fmax);
-    const size_t info = up(sizeof(MeshInfo) * (size_t)B);
-    const size_t face = up(sizeof(long long) * (size_t)B * (size_t)Fmax);
-    const size_t tot = up(sizeof(long long) * (size_t)B * nch);
-    const size_t start = up(sizeof(long long) * ((size_t)B * (nch + 1) + 1));
-    *o_face = info;
-    *o_tot = info + face;
-    *o_start = info + face + tot;
-    return info + face + tot + start;
+    WsBump ws;
+    Layout l;
+    l.info = ws.put(sizeof(MeshInfo) * (size_t)B);
+    l.face = ws.put(sizeof(long long) * (size_t)B * (size_t)Fmax);
+    l.tot = ws.put(sizeof(long long) * (size_t)B * nch);
+    l.start = ws.put(sizeof(long long) * ((size_t)B * (nch + 1) + 1));
+    l.total = ws.at;
+    return l;
 }
 
 }  // namespace
@@ -335,8 +293,7 @@ extern "C" {
 fx3d_status fx3d_trimesh_voxel_workspace_bytes(int32_t Vmax, int32_t Fmax, int32_t B, int32_t res, size_t *bytes) {
     FX3D_REQUIRE(bytes && Vmax > 0 && Fmax >= 0 && B > 0 && res > 0 && res <= 1024,
                  "fx3d_trimesh_voxel_workspace_bytes: bad arguments");
-    size_t a, c, d;
-    *bytes = ws_layout(Fmax, B, &a, &c, &d);
+    *bytes = ws_layout(Fmax, B).total;
     return FX3D_OK;
 }
 
@@ -349,14 +306,14 @@ fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vmax, const
     FX3D_REQUIRE(Vmax > 0 && Vmax <= INT32_MAX / 3 && Fmax >= 0 && B > 0 && res > 0 && res <= 1024 &&
                      (long long)B * (chunks(Fmax) + 1) < INT32_MAX,
                  "fx3d_trimesh_to_voxel: bad sizes");
-    size_t o_face, o_tot, o_start;
-    FX3D_REQUIRE(ws_bytes >= ws_layout(Fmax, B, &o_face, &o_tot, &o_start), "fx3d_trimesh_to_voxel: workspace too small");
+    const Layout l = ws_layout(Fmax, B);
+    FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_trimesh_to_voxel: workspace too small");
     hipStream_t st = as_stream(s);
     char *w = static_cast<char *>(ws);
-    MeshInfo *info = reinterpret_cast<MeshInfo *>(w);
-    long long *face_off = reinterpret_cast<long long *>(w + o_face);
-    long long *chunk_tot = reinterpret_cast<long long *>(w + o_tot);
-    long long *start = reinterpret_cast<long long *>(w + o_start);
+    MeshInfo *info = reinterpret_cast<MeshInfo *>(w + l.info);
+    long long *face_off = reinterpret_cast<long long *>(w + l.face);
+    long long *chunk_tot = reinterpret_cast<long long *>(w + l.tot);
+    long long *start = reinterpret_cast<long long *>(w + l.start);
     const int nch = chunks(Fmax);
     const double r = 1.0 / (double)res;
     const double thr = r * r;  // smallest_side = (1.0 / resolution)^2 (:153)

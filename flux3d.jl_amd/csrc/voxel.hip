@@ -11,6 +11,7 @@
 // centres are tested with the reference's own Float64 arithmetic (unfused, dimension order), so occupancy
 // is bit-identical; the work is O(N), the traffic is the cloud read + the res^3*B grid write.
 #include "fx3d_common.h"
+#include "scan_common.h"
 
 namespace fx3d {
 namespace {
@@ -20,36 +21,14 @@ constexpr int kVoxThreads = 256;
 // one block per cloud: scalar min / max over all 3N coordinates (src/conversions.jl:94-95)
 __global__ __launch_bounds__(kVoxThreads) void cloud_range_kernel(const float *__restrict__ p, int N,
                                                                   float *__restrict__ range) {
+    __shared__ float sw[2 * kVoxThreads / kWave];
     const int b = blockIdx.x;
-    const float *pb = p + (size_t)b * N * 3;
-    float lo = __builtin_inff(), hi = -__builtin_inff();
-    bool nan = false;
-    for (int e = threadIdx.x; e < 3 * N; e += kVoxThreads) {
-        const float v = pb[e];
-        nan |= (v != v);
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-    }
-    __shared__ float slo[kVoxThreads], shi[kVoxThreads];
-    __shared__ int snan;
-    if (threadIdx.x == 0) snan = 0;
-    __syncthreads();
-    slo[threadIdx.x] = lo;
-    shi[threadIdx.x] = hi;
-    if (nan) snan = 1;
-    __syncthreads();
-    for (int s = kVoxThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            slo[threadIdx.x] = fminf(slo[threadIdx.x], slo[threadIdx.x + s]);
-            shi[threadIdx.x] = fmaxf(shi[threadIdx.x], shi[threadIdx.x + s]);
-        }
-        __syncthreads();
-    }
+    const Range r = block_range<kVoxThreads>(p + (size_t)b * N * 3, 3 * N, sw);
     if (threadIdx.x == 0) {
         // Julia's maximum/minimum propagate NaN; a NaN range yields an all-NaN cloud and an empty grid
         const float q = __builtin_nanf("");
-        range[2 * b] = snan ? q : slo[0];
-        range[2 * b + 1] = snan ? q : shi[0];
+        range[2 * b] = r.nan ? q : r.lo;
+        range[2 * b + 1] = r.nan ? q : r.hi;
     }
 }
 
@@ -61,6 +40,7 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_scatter_kernel(const float 
     if (i >= N) return;
     const float lo = range[2 * b], hi = range[2 * b + 1];
     const float span = hi - lo;
+    // (a zero lo or hi may carry either sign: span is the same, and c = -0.0 picks the k and gives the d of c = +0.0)
     const float *q = p + ((size_t)b * N + i) * 3;
     // cloud = (p .- verts_min) ./ (verts_max - verts_min), Float32 (:96)
     const double c0 = (double)((q[0] - lo) / span);

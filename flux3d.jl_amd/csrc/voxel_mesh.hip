@@ -25,6 +25,7 @@
 //          launch 5 (optional)  zero the padding of faces_padded behind each grid's 12 K faces.
 // Cube placement is a prefix sum: no atomics place anything, no float atomics anywhere, bit-identical run to run.
 #include "fx3d_common.h"
+#include "scan_common.h"
 
 namespace fx3d {
 namespace {
@@ -144,31 +145,6 @@ __global__ __launch_bounds__(kThreads) void vm_erode_kernel(const unsigned long 
     }
 }
 
-__device__ __forceinline__ long long block_exclusive_scan(long long v, long long *sw, long long *total) {
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-    long long inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const long long u = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += u;
-    }
-    if (lane == kWave - 1) sw[w] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long run = 0;
-        for (int i = 0; i < (int)blockDim.x / kWave; ++i) {
-            const long long x = sw[i];
-            sw[i] = run;
-            run += x;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    const long long r = sw[w] + inc - v;
-    __syncthreads();  // sw / total are reused by the next call
-    return r;
-}
-
 // launch 3 (one block): start[i] = survivors in tiles [0, i) of the batch, start[n] = the total; cubes[b] = K of grid b.
 __global__ __launch_bounds__(kScanThreads) void vm_scan_kernel(const int32_t *__restrict__ tile_cnt, Dims d,
                                                                long long *__restrict__ start, int64_t *__restrict__ cubes) {
@@ -177,7 +153,7 @@ __global__ __launch_bounds__(kScanThreads) void vm_scan_kernel(const int32_t *__
     long long carry = 0;
     for (long long base = 0; base < n; base += kScanThreads) {
         const long long e = base + threadIdx.x;
-        const long long ex = block_exclusive_scan(e < n ? tile_cnt[e] : 0, sw, &stot);
+        const long long ex = block_exclusive_scan_serial(e < n ? tile_cnt[e] : 0, sw, &stot);
         if (e < n) start[e] = carry + ex;
         carry += stot;
     }
@@ -270,15 +246,15 @@ struct Layout {
     size_t occ, surv, cnt, start, gmax, total;
 };
 Layout layout(const Dims &d) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t words = (size_t)d.wpg * d.B, tiles = (size_t)d.tpg * d.B;
+    WsBump ws;
     Layout l;
-    l.occ = 0;
-    l.surv = up(8 * words);
-    l.cnt = l.surv + up(8 * words);
-    l.start = l.cnt + up(4 * tiles);
-    l.gmax = l.start + up(8 * (tiles + 1));
-    l.total = l.gmax + up(4 * (size_t)d.B);
+    l.occ = ws.put(8 * words);
+    l.surv = ws.put(8 * words);
+    l.cnt = ws.put(4 * tiles);
+    l.start = ws.put(8 * (tiles + 1));
+    l.gmax = ws.put(4 * (size_t)d.B);
+    l.total = ws.at;
     return l;
 }
 

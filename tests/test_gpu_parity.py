@@ -994,6 +994,24 @@ def test_pointcloud_to_voxel_sphere_and_degenerate(gpu_fx, oracle):
     assert oracle.pointcloud_to_voxel(flat, 8).sum() == 0
 
 
+@pytest.mark.parametrize("N", [2, 85, 86, 257])
+def test_pointcloud_to_voxel_range_with_signed_zeros(gpu_fx, oracle, N):
+    """The minimum of each cloud is -0.0 and +0.0 occurs too (point 0 is (-0, +0, -0) in one cloud and (+0, -0, +0) in the other;
+    the last coordinate of a longer cloud is a zero as well), with 3N either side of the range block's 256 threads and of 768:
+    whichever zero the reduction returns, the grid is the oracle's.  (A point with a zero coordinate marks no voxel: the lattice
+    starts at 1.5 / res.)"""
+    rng = np.random.default_rng(8000 + N)
+    p = np.asfortranarray(rng.random((3, N, 2), dtype=np.float32) * 3)
+    p[:, 0, 0] = np.array([-0.0, 0.0, -0.0], np.float32)
+    p[:, 0, 1] = np.array([0.0, -0.0, 0.0], np.float32)
+    if N > 2:
+        p[2, N - 1, :] = np.array([0.0, -0.0], np.float32)
+    assert p.min() == 0 and np.signbit(p).sum() == (3 if N == 2 else 4)
+    vox = gpu_fx.pointcloud_to_voxel(gpu_fx.PointCloud(p), 8).to_host()
+    exp = oracle.pointcloud_to_voxel(p, 8)
+    assert np.array_equal(vox, exp) and 0 < exp.sum() < exp.size
+
+
 # ------------------------------------------------------------------------------ randomised shape sweeps
 def _sweep_cases(seed, count, lo, hi):
     rng = np.random.default_rng(seed)

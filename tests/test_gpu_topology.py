@@ -249,6 +249,16 @@ def test_sheet_padded_batch(dev):
     check_raw(dev, [a, b, a], [61 * 51, 7 * 6, 61 * 51])
 
 
+def test_more_meshes_than_one_round_of_the_offset_scan(dev):
+    """B = 1025 ragged meshes of one to three faces over three to five vertices: the face and vertex offsets of faces_packed take
+    two rounds of the one-block scan's 1024 (td_pack_offsets_kernel), so mesh 1024 is placed by the first round's totals."""
+    rng = np.random.default_rng(1025)
+    vlen = rng.integers(3, 6, 1025)
+    faces = [np.asfortranarray(rng.integers(0, v, (3, int(rng.integers(1, 4)))).astype(np.int64)) for v in vlen]
+    assert {f.shape[1] for f in faces} == {1, 2, 3}
+    check_raw(dev, faces, vlen)
+
+
 # ---- 6. device-born meshes -------------------------------------------------------------------------------------------
 def test_device_born_mesh_never_builds_host_faces(dev):
     fx = dev.fx

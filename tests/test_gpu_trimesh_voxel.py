@@ -145,3 +145,27 @@ def test_non_finite_mesh_raises_and_the_rest_of_the_batch_is_right(gpu_fx, ref_m
     assert int(cnt.to_host()[0]) == 1
     assert g[..., 1].sum() == 0
     assert np.array_equal(g[..., 0], ref.voxelize(sv, sf, 28)) and np.array_equal(g[..., 2], ref.voxelize(tv, tf, 28))
+
+
+def test_more_scan_entries_than_one_round_of_the_scan_block(gpu_fx):
+    """600 one-triangle meshes at res 4: B * (chunks + 1) = 1200 entries, two rounds of the one-block scan's 1024 (launch 3),
+    so the second round's starts carry the first round's total."""
+    rng = np.random.default_rng(4242)
+    verts = [np.asfortranarray(rng.random((3, 3), dtype=np.float32)) for _ in range(600)]
+    faces = [np.asfortranarray(np.array([[1], [2], [3]], np.uint32)) for _ in range(600)]
+    g = _check(gpu_fx, verts, faces, 4)
+    assert all(g[..., i].sum() >= 3 for i in (0, 511, 512, 599))  # three distinct corners at least, before and behind the carry
+
+
+def test_range_with_signed_zeros(gpu_fx):
+    """The minimum of the mesh is -0.0 and +0.0 occurs too, in several waves of the range block (1025 vertices: 3075 coordinates
+    over 1024 threads): whichever zero the reduction returns, the grid is the restatement's."""
+    rng = np.random.default_rng(77)
+    v = np.asfortranarray(rng.random((3, 1025), dtype=np.float32))
+    flat = v.reshape(-1, order="F")  # a view: element e = coordinate e of the device array
+    flat[[0, 70, 1023, 2000, 3074]] = np.float32(-0.0)
+    flat[[1, 64, 1024, 2049, 3073]] = np.float32(0.0)
+    assert v.min() == 0 and np.signbit(v).sum() == 5 and np.shares_memory(flat, v)
+    f = rng.integers(1, 1026, (3, 40)).astype(np.uint32)
+    for res in (5, 16):
+        _check(gpu_fx, [v], [np.asfortranarray(f)], res)

@@ -80,6 +80,12 @@ def test_random_grids(gpu_fx, res):
         _check(gpu_fx, _random_batch(rng, res, B))
 
 
+def test_more_tiles_than_one_round_of_the_scan_block(gpu_fx):
+    """res 32, B = 65: 16 tiles per grid, 1040 in the batch -- the smallest batch whose tile counts take two rounds of the
+    one-block scan's 1024 (launch 3), so the last grid's cubes start at the first round's total."""
+    _check(gpu_fx, _random_batch(np.random.default_rng(7065), 32, 65))
+
+
 @pytest.mark.parametrize("thresh", [0.05, 0.9, 1.0])
 def test_random_values_other_thresholds(gpu_fx, thresh):
     rng = np.random.default_rng(int(thresh * 100))

@@ -350,6 +350,37 @@ def test_fit_path_workspace_sizes_are_the_recorded_ones(fx):
     assert [ordered[k] for k in ((5120, 5300), (5120, 9000), (32400, 512), (32768, 512), (28000, 512), (28800, 512))] == [1, 0, 1, 0, 1, 1]
 
 
+def test_conversion_workspace_sizes_are_the_recorded_ones(fx):
+    """The size functions of the conversions (pointcloud_to_voxel, trimesh_to_voxel, voxel_to_trimesh), of the device topology
+    builders and of the normals, like the fit path's above: tests/golden/conversion_workspace_sizes.json was recorded from the
+    build BEFORE these layouts moved onto WsBump (rows: arguments..., status, value; a refused query leaves 0).  It holds the
+    boundaries the layouts turn on: Fmax either side of the chunks of 1024 faces (0, 1, 1024, 1025, 2049); res 1, 63, 64, 65, 1024
+    (the words per row) and 1025 (refused); sorts of 1023 .. 1026 elements (one tile of 1024) and of 4095 .. 4097 and 16 383 ..
+    16 386 (a scan chunk of 4096 flags / of 256 x 16 tiles' counters); 12 n bytes either side of a 256-byte line (n = 21, 22); and
+    the refused limits: 3F >= 2^31, 2E + V >= 2^31, Fmax >= 2^29, 3 Fmax B >= 2^31, tiles >= 2^31, B <= 0."""
+    import ctypes as C
+    import json
+    from flux3d_jl_amd import _lib
+    lib = _lib.load()
+    with open(os.path.join(GOLDEN, "conversion_workspace_sizes.json")) as f:
+        table = json.load(f)
+    assert set(table) == {"fx3d_voxel_workspace_bytes", "fx3d_trimesh_voxel_workspace_bytes", "fx3d_voxel_mesh_workspace_bytes",
+                          "fx3d_edges_dev_workspace_bytes", "fx3d_laplacian_dev_workspace_bytes",
+                          "fx3d_vertex_faces_dev_workspace_bytes", "fx3d_faces_padded_to_packed_dev_workspace_bytes",
+                          "fx3d_normals_workspace_bytes"}
+    nrows = 0
+    for name, rows in table.items():
+        assert any(status != 0 for *_, status, _ in rows) and any(status == 0 for *_, status, _ in rows), name
+        for *args, status, value in rows:
+            out = C.c_size_t(0)
+            got = getattr(lib, name)(*args, C.byref(out))
+            assert (got, out.value) == (status, value), (name, args)
+            if status == 0:
+                assert _lib.query_bytes(name, *args) == value
+            nrows += 1
+    assert 150 <= nrows <= 400
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """VERDICT r3 #1b: `python bench.py --gpus N` with no launcher must run N ranks or FAIL -- never print a line whose n_gpus
     differs from --gpus.  On a box with fewer than N devices (this container has none) the launcher exits non-zero before any
