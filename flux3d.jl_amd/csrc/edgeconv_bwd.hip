@@ -31,7 +31,6 @@ using namespace fx3d::mlp;
 namespace {
 
 constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // as edgeconv.hip: 132 KB of the CU's 160 KB
-constexpr int kWaves = kPtThreads / 64;
 
 struct EdgeConvBwdArgs {
     const float *x;      // (F, N, B)
@@ -62,70 +61,6 @@ __global__ __launch_bounds__(256) void transpose_weights(const TransposeArgs t) 
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cin * cout; i += gridDim.x * blockDim.x) {
         const int c = i / cout, o = i - c * cout;
         wt[i] = W[c + cin * o];
-    }
-}
-
-// gather_centre and gather_diff (mlp_common.h) in one pass, for a tile of T points: both halves are written with every k
-template <int T>
-__device__ __forceinline__ void gather_rows(float *rows, int ld, const float *xb, const int32_t *ib, int F, int N, int K, int k,
-                                            int p0, int nvalid) {
-    const float rf = 1.0f / (float)F;
-    for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
-        const int p = edge_row_of(i, rf), c = i - p * F;
-        float xc = 0.0f, v = 0.0f;
-        if (p < nvalid) {
-            xc = xb[(size_t)(p0 + p) * F + c];
-            int jn = ib[(size_t)p * K + k];
-            jn = (unsigned int)jn < (unsigned int)N ? jn : p0 + p;
-            v = xb[(size_t)jn * F + c] - xc;
-        }
-        rows[p * ld + c] = xc;
-        rows[p * ld + F + c] = v;
-    }
-}
-
-// one hidden layer forward, image to image: conv_item of edgeconv.hip on the wave's slabs
-template <int LD, int NH>
-__device__ __forceinline__ void hidden_fwd(const float *in, float *out, int cin, int cout, const Conv &c) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    for (int sl = wave; sl * 32 < cout; sl += kWaves) {
-        const int o = sl * 32 + j, oc = min(o, cout - 1);
-        f32x16 acc[NH];
-#pragma unroll
-        for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-        mfma_slab_rt<LD, NH>(in, c.W + (size_t)cin * oc, cin, h, j, acc);
-        const float bi = c.b[oc], g = c.bn.g[oc], be = c.bn.b[oc], mu = c.bn.m[oc], sd = sqrtf(c.bn.v[oc] + kBnEps);
-        if (o < cout) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int t = 0; t < NH; ++t) out[(t * 32 + mfma_row(r, h)) * LD + o] = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd);
-        }
-    }
-}
-
-// one hidden layer backward: d[p][c] = the chain over o < cout of dz[p][o] Wt[o + cout c] for c < cin, then in a's place
-// dz'[p][c] = ((a[p][c] > 0 ? d : +0) gamma[c]) / sd[c] with the BatchNorm of the layer that made a
-template <int LD, int NH>
-__device__ __forceinline__ void hidden_bwd(const float *dz, float *a, int cout, int cin, const float *__restrict__ wt, const Bn &bn) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    for (int sl = wave; sl * 32 < cin; sl += kWaves) {
-        const int c = sl * 32 + j, cc = min(c, cin - 1);
-        f32x16 acc[NH];
-#pragma unroll
-        for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-        mfma_slab_rt<LD, NH>(dz, wt + (size_t)cout * cc, cout, h, j, acc);
-        const float g = bn.g[cc], sd = sqrtf(bn.v[cc] + kBnEps);
-        if (c < cin) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int t = 0; t < NH; ++t) {
-                    float *e = a + (t * 32 + mfma_row(r, h)) * LD + c;
-                    const float d = *e > 0.0f ? acc[t][r] : 0.0f;
-                    *e = (d * g) / sd;
-                }
-        }
     }
 }
 
@@ -218,7 +153,7 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const EdgeConv
             const int ci = l == 2 ? a.w[1] : l == 3 ? a.w[2] : a.w[3];
             const float *wt = l == 2 ? a.wt[1] : l == 3 ? a.wt[2] : a.wt[3];
             const Bn bn = l == 2 ? a.c[0].bn : l == 3 ? a.c[1].bn : a.c[2].bn;
-            hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn);
+            hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn, NoSink{});
             __syncthreads();
         }
         // d_0 from dz_1 (img[1] for every L), added to the sums over k
@@ -257,6 +192,37 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const EdgeConv
     }
 }
 
+}  // namespace
+
+// Wt_l of every layer into `wt` (edgeconv_transposed_floats(layers, nlayers) floats), wt_of[l]: where layer l + 1's begins
+namespace fx3d {
+namespace mlp {
+size_t edgeconv_transposed_floats(const int32_t *layers, int nlayers) {
+    size_t nw = 0;
+    for (int i = 1; i < nlayers; ++i) nw += (size_t)(i == 1 ? 2 * layers[0] : layers[i - 1]) * layers[i];
+    return nw;
+}
+fx3d_status edgeconv_transpose_weights(const Conv *c, const int32_t *layers, int nlayers, float *wt, const float **wt_of, hipStream_t st) {
+    TransposeArgs t{};
+    int most = 1;
+    for (int l = 0; l + 1 < nlayers; ++l) {
+        t.W[l] = c[l].W;
+        t.cin[l] = l == 0 ? 2 * layers[0] : layers[l];
+        t.cout[l] = layers[l + 1];
+        t.wt[l] = wt;
+        wt_of[l] = wt;
+        wt += (size_t)t.cin[l] * t.cout[l];
+        most = t.cin[l] * t.cout[l] > most ? t.cin[l] * t.cout[l] : most;
+    }
+    hipLaunchKernelGGL(transpose_weights, dim3((most + 255) / 256, nlayers - 1), dim3(256), 0, st, t);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+}  // namespace mlp
+}  // namespace fx3d
+
+namespace {
+
 // ---- the host side -------------------------------------------------------------------------------------------------
 // the LDS images: one stride for all, from the widest of 2F, c1 .. cL; 64 points per block where they fit, else 32
 void lds_plan(const int32_t *layers, int nlayers, int *ld, int *nh, size_t *bytes) {
@@ -278,9 +244,7 @@ fx3d_status ws_plan(const int32_t *layers, int nlayers, int N, int B, int K, WsP
     w->fwd = ws.put(w->fwd_bytes);
     w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
     w->out = ws.put((size_t)layers[nlayers - 1] * N * B * sizeof(float));
-    size_t nw = 0;
-    for (int i = 1; i < nlayers; ++i) nw += (size_t)(i == 1 ? 2 * layers[0] : layers[i - 1]) * layers[i];
-    w->wt = ws.put(nw * sizeof(float));
+    w->wt = ws.put(edgeconv_transposed_floats(layers, nlayers) * sizeof(float));
     w->total = ws.at;
     return FX3D_OK;
 }
@@ -342,21 +306,7 @@ fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *layers, in
     }
     a.idx = idx ? idx : ws_idx;
     a.out = out ? out : ws_out;
-    // the transposed weights
-    TransposeArgs t{};
-    float *wt = reinterpret_cast<float *>(wsb + w.wt);
-    int most = 1;
-    for (int l = 0; l < a.nl; ++l) {
-        t.W[l] = a.c[l].W;
-        t.cin[l] = l == 0 ? 2 * layers[0] : layers[l];
-        t.cout[l] = layers[l + 1];
-        t.wt[l] = wt;
-        a.wt[l] = wt;
-        wt += (size_t)t.cin[l] * t.cout[l];
-        most = t.cin[l] * t.cout[l] > most ? t.cin[l] * t.cout[l] : most;
-    }
-    hipLaunchKernelGGL(transpose_weights, dim3((most + 255) / 256, a.nl), dim3(256), 0, st, t);
-    FX3D_LAUNCH_CHECK();
+    if ((r = edgeconv_transpose_weights(a.c, layers, nlayers, reinterpret_cast<float *>(wsb + w.wt), a.wt, st)) != FX3D_OK) return r;
     size_t lds_bytes = 0;
     int ld = 0, nh = 0;
     lds_plan(layers, nlayers, &ld, &nh, &lds_bytes);

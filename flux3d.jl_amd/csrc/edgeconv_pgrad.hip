@@ -1,0 +1,498 @@
+// EdgeConv(layers, K): the gradients with respect to the parameters (conv W and b, BatchNorm gamma and beta; test-mode
+// BatchNorm) and, when asked, with respect to the input, from one fused kernel (gfx950).  include/flux3d_hip.h ("EdgeConv
+// parameter adjoint") states the definition and the order of every sum; tests/edgeconv_pgrad_ref.py restates it on the host.
+//
+// The chain is the input adjoint's (edgeconv_bwd.hip; gather_rows, hidden_fwd, hidden_bwd of mlp_common.h): per neighbour rank k
+// the forward tile is recomputed, the k that took the maximum found, and the layers walked back.  Where that kernel drops a
+// layer's upstream gradient d_l, this one contracts it with the layer's input, which is still in its LDS image:
+//   H_l[c,o] += sum over the tile's rows of a_{l-1}[row][c] d_l[row][o],   h_l[o] += sum of d_l[row][o].
+// edgeconv_pgrad_kernel<LD, NS, NT>: one block = one chunk of kGradChunk = 128 consecutive points of one cloud = up to four
+//   32-point tiles, one after the other, 4 waves, looping over k inside a tile.  gridDim = (chunks, B, passes).
+//   The contraction: the lane that produces d_l[row][o] for its channel o holds its 16 rows mfma_row(r, h) in registers (the
+//     compare step for layer L, hidden_bwd's accumulators for the others).  They are the B operand of v_mfma_f32_32x32x2f32 as
+//     they stand: MFMA r contracts the two rows mfma_row(r, 0) (lanes 0-31) and mfma_row(r, 1) (lanes 32-63), in this order.
+//     The A operand is a_{l-1}[mfma_row(r, h)][c0 + lane % 32] from LDS: consecutive words per half-wave.  The result tile is
+//     H_l[c0 + mfma_row(r', h)][o0 + lane % 32]: 16 registers per lane per (32 input channels) x (32 output channels).
+//     Rows beyond the cloud's last point have d = +0 in the registers: every product is a zero and the chain, which began at
+//     +0 and therefore never holds -0, does not change.  Channel tails: the index is clamped, the tile computed, not written.
+//   The accumulators: wave w owns the output slabs w, w + 4, ... of every layer (the forward's ownership), times all of the
+//     layer's ceil(cin / 32) input tiles -- its tile list, layer by layer.  NT of them live in registers across the tiles and k
+//     of a chunk; pass z (blockIdx.z) of a block takes tiles z NT .. z NT + NT - 1 of every wave's list and recomputes the chain.
+//     An element of H has one owner in one pass: the passes change no bit.  A later pass holds later layers only and ends its
+//     walk back at the lowest of them (PgradArgs::lmin); pass 0 walks all the way and owns gx.
+//     After the chunk: one plain store per element into the chunk's partial slab (the parameter buffer's layout: H_l in W_l's
+//     place, h_l in b_l's).  No atomics.
+//   h_l[o]: two chains per chunk, one per half-wave (rows mfma_row(r, 0) and mfma_row(r, 1)), added once at the flush; pass 0.
+//   LDS: images of 32 rows, stride LD as the adjoint.  L = 1: rows, dz_1.  L = 2: rows, a_1 / dz_1, dz_2 (d_1 is contracted with
+//     the edge rows, which must outlive dz_2).  L >= 3: L images, dz_L in `rows`' place as in the adjoint, and the edge rows
+//     gathered again for the same k once hidden_bwd(L) has consumed dz_L.  Four images of stride 258 are 132 KB.
+//   gx (pass 0, when asked): the adjoint's sums S and subtraction, per tile.
+// Then pgrad_reduce (the chunk partials of every H and h element as one chain, b ascending, chunk ascending) and pgrad_finish
+// (the four families from H and h).
+#include "mlp_common.h"
+
+using namespace fx3d;
+using namespace fx3d::mlp;
+
+namespace {
+
+constexpr int kGradChunk = FX3D_EDGECONV_GRAD_CHUNK;
+constexpr int kGradTiles = kGradChunk / 32;
+constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // as edgeconv.hip: 132 KB of the CU's 160 KB
+
+struct PgradArgs {
+    const float *x;      // (F, N, B)
+    const int32_t *idx;  // (K, N, B), 0-based
+    const float *out;    // (cL, N, B): the forward's
+    const float *gout;   // (cL, N, B)
+    float *gx;           // (F, N, B) or NULL
+    float *part;         // (psize, chunks, B): the chunk partials
+    Conv c[kMaxLayers];
+    const float *wt[kMaxLayers];  // Wt_l[o + cout c]
+    int woff[kMaxLayers], boff[kMaxLayers];  // W_l and b_l in the parameter buffer (floats)
+    int w[kMaxLayers + 1];        // F, c1, ..., cL
+    int nl, cout;                 // L, cL
+    int N, K, psize;
+    unsigned int lmin;            // 4 bits per pass: the lowest layer that has a tile in it
+};
+
+// the tiles of one layer in a wave's list: its slabs (wave, wave + 4, ... below cout) times the layer's input tiles
+__device__ __forceinline__ int wave_slabs(int cout, int wave) { return max(0, ((cout + 31) / 32 - wave + kWaves - 1) / kWaves); }
+
+// The wave's slab sl of d_l (this lane: channel sl 32 + j, rows mfma_row(r, h)) against a_{l-1} in `ain` (cin channels): the h
+// chain of the slab (hs: one per slab of the wave) and the slab's input tiles.  first: the layer's first tile in the wave's list,
+// less the pass's first.
+template <int LD, int NT, int NS>
+__device__ __forceinline__ void take(f32x16 (&H)[NT], float (&hs)[NS], f32x16 d, int sl, int wave, int nvalid, int first,
+                                     const float *ain, int cin, int h, int j) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d[r] = mfma_row(r, h) < nvalid ? d[r] : 0.0f;
+    const int s = __builtin_amdgcn_readfirstlane((sl - wave) / kWaves);  // (hidden_bwd's slab index is no scalar to the compiler)
+#pragma unroll
+    for (int q = 0; q < NS; ++q)
+        if (s == q) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) hs[q] = hs[q] + d[r];
+        }
+    // the slab's input tiles are the register tiles t0 .. t0 + nci - 1 where they are this pass's: one static tile after the other
+    const int nci = (cin + 31) / 32, t0 = first + s * nci;
+    const float *a0 = ain + 4 * h * LD;  // row mfma_row(r, h) is 4 h + mfma_row(r, 0)
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        const int ci = i - t0;
+        if (ci < 0 || ci >= nci) continue;  // wave-uniform
+        const float *ap = a0 + min(ci * 32 + j, cin - 1);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) H[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[mfma_row(r, 0) * LD], d[r], H[i], 0, 0, 0);
+    }
+}
+
+template <int LD, int NS, int NT>
+__global__ __launch_bounds__(kPtThreads) void edgeconv_pgrad_kernel(const PgradArgs a) {
+    extern __shared__ float lds[];
+    constexpr int T = 32, IMG = T * LD;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, j = lane & 31;
+    const int b = blockIdx.y, chunk = blockIdx.x, t0 = blockIdx.z * NT;
+    const int F = a.w[0], L = a.nl, cout = a.cout;
+    const bool sums = a.gx != nullptr && blockIdx.z == 0;  // the input gradient: pass 0
+    const int lmin = (a.lmin >> (4 * blockIdx.z)) & 15;    // this pass needs d_l for l >= lmin only: the walk back ends there
+    const float *xb = a.x + (size_t)b * a.N * F;
+    float *rows = lds;
+    float *dzl = L == 1 ? lds + IMG : L == 2 ? lds + 2 * IMG : lds;  // where dz_L goes
+    const float nan = __int_as_float(0x7fc00000);
+    const Conv cl = L == 1 ? a.c[0] : L == 2 ? a.c[1] : L == 3 ? a.c[2] : a.c[3];
+    const int cinl = L == 1 ? 2 * F : L == 2 ? a.w[1] : L == 3 ? a.w[2] : a.w[3];  // the last layer's input width
+    // the wave's tile list: base[i] = the first tile of layer i + 1
+    int base[kMaxLayers];
+    {
+        int at = 0;
+#pragma unroll
+        for (int i = 0; i < kMaxLayers; ++i) {
+            base[i] = at;
+            if (i < L) at += wave_slabs(a.w[i + 1], wave) * (((i == 0 ? 2 * F : a.w[i]) + 31) / 32);
+        }
+    }
+    const int basel = (L == 1 ? base[0] : L == 2 ? base[1] : L == 3 ? base[2] : base[3]) - t0;
+
+    f32x16 H[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) H[i] = f32x16{0};
+    float hl[NS], hh[kMaxLayers - 1][NS];  // the h chains of this half-wave: layer L, and layers 1 .. 3 where they are hidden
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        hl[s] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < kMaxLayers - 1; ++i) hh[i][s] = 0.0f;
+    }
+
+    for (int tile = 0; tile < kGradTiles; ++tile) {
+        const int p0 = chunk * kGradChunk + tile * T;
+        if (p0 >= a.N) break;  // block-uniform
+        const int nvalid = min(T, a.N - p0);
+        const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
+        f32x16 tgt[NS], gv[NS], S[NS];
+        float dz0[NS];
+        {
+            const size_t ob = ((size_t)b * a.N + p0) * cout;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int sl = wave + s * kWaves;
+                dz0[s] = 0.0f;
+                S[s] = tgt[s] = gv[s] = f32x16{0};
+                if (sl * 32 >= cout) continue;  // wave-uniform
+                const int oc = min(sl * 32 + j, cout - 1);
+                dz0[s] = (0.0f * cl.bn.g[oc]) / sqrtf(cl.bn.v[oc] + kBnEps);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int p = mfma_row(r, h);
+                    float ov = nan, g = 0.0f;
+                    if (p < nvalid) {
+                        ov = a.out[ob + (size_t)p * cout + oc];
+                        g = a.gout[ob + (size_t)p * cout + oc];
+                    }
+                    tgt[s][r] = ov > 0.0f ? ov : nan;
+                    gv[s][r] = g;
+                }
+            }
+        }
+        for (int k = 0; k < a.K; ++k) {
+            gather_rows<T>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
+            __syncthreads();
+            const float *src = rows;
+            int cin = 2 * F;
+            for (int i = 0; i + 1 < L; ++i) {
+                const Conv c = i == 0 ? a.c[0] : i == 1 ? a.c[1] : a.c[2];
+                const int co = i == 0 ? a.w[1] : i == 1 ? a.w[2] : a.w[3];
+                float *dst = lds + (i + 1) * IMG;
+                hidden_fwd<LD, 1>(src, dst, cin, co, c);
+                __syncthreads();
+                src = dst;
+                cin = co;
+            }
+            // the last layer, compared with the forward's maxima: dz_L to its image, d_L against a_{L-1}
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int sl = wave + s * kWaves;
+                if (sl * 32 >= cout) continue;  // wave-uniform
+                const int o = sl * 32 + j, oc = min(o, cout - 1);
+                f32x16 acc[1] = {f32x16{0}};
+                mfma_slab_rt<LD, 1>(src, cl.W + (size_t)cinl * oc, cinl, h, j, acc);
+                const float bi = cl.b[oc], g = cl.bn.g[oc], be = cl.bn.b[oc], mu = cl.bn.m[oc], sd = sqrtf(cl.bn.v[oc] + kBnEps);
+                f32x16 d;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool first = epilogue<kBnRelu>(acc[0][r], bi, g, be, mu, sd) == tgt[s][r];
+                    if (o < cout) dzl[mfma_row(r, h) * LD + o] = first ? (gv[s][r] * g) / sd : dz0[s];
+                    d[r] = first ? gv[s][r] : 0.0f;
+                    tgt[s][r] = first ? nan : tgt[s][r];
+                }
+                take<LD, NT, NS>(H, hl, d, sl, wave, nvalid, basel, src, cinl, h, j);
+            }
+            __syncthreads();
+            // the way back: dz_l in img[l] (dz_L in dzl), d_{l-1} into a_{l-1}'s place and against a_{l-2}
+#pragma unroll
+            for (int l = kMaxLayers; l >= 2; --l) {
+                if (l > L || l <= lmin) continue;  // block-uniform
+                const float *dz = l == L ? dzl : lds + l * IMG;
+                const float *ain = l == 2 ? rows : lds + (l - 2) * IMG;
+                const int cprev = l == 2 ? 2 * F : a.w[l - 2];
+                hidden_bwd<LD, 1>(dz, lds + (l - 1) * IMG, a.w[l], a.w[l - 1], a.wt[l - 1], a.c[l - 2].bn,
+                                  [&](int sl, const f32x16(&d)[1]) {
+                                      take<LD, NT, NS>(H, hh[l - 2], d[0], sl, wave, nvalid, base[l - 2] - t0, ain, cprev, h, j);
+                                  });
+                __syncthreads();
+                if (l == L && L >= 3) {  // dz_L is consumed: the edge rows of this k again, for d_1
+                    gather_rows<T>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
+                    __syncthreads();
+                }
+            }
+            // d_0 from dz_1 (img[1] for every L), added to the sums over k
+            if (sums) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int sl = wave + s * kWaves;
+                    if (sl * 32 >= 2 * F) continue;  // wave-uniform
+                    const int cc = min(sl * 32 + j, 2 * F - 1);
+                    f32x16 acc[1] = {f32x16{0}};
+                    mfma_slab_rt<LD, 1>(lds + IMG, a.wt[0] + (size_t)a.w[1] * cc, a.w[1], h, j, acc);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) S[s][r] = S[s][r] + acc[0][r];
+                }
+            }
+            // (img[1] and `rows` are written again after barriers that a wave reaches after these reads)
+        }
+        if (sums) {
+            // S to `rows` (last read before a barrier above), then gx[f] = S[f] - S[F + f]
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int c = (wave + s * kWaves) * 32 + j;
+                if (c >= 2 * F) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) rows[mfma_row(r, h) * LD + c] = S[s][r];
+            }
+            __syncthreads();
+            float *gb = a.gx + ((size_t)b * a.N + p0) * F;
+            const float rf = 1.0f / (float)F;
+            for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
+                const int p = edge_row_of(i, rf), c = i - p * F;
+                if (p < nvalid) gb[(size_t)p * F + c] = rows[p * LD + c] - rows[p * LD + F + c];
+            }
+            __syncthreads();  // before the next tile's gather
+        }
+    }
+
+    // the flush: this pass's tiles of the wave's list, and in pass 0 the h chains (half-wave 0's plus half-wave 1's)
+    float *part = a.part + ((size_t)b * gridDim.x + chunk) * a.psize;
+#pragma unroll
+    for (int i = 0; i < kMaxLayers; ++i) {
+        if (i >= L) continue;
+        const int ci_w = i == 0 ? 2 * F : a.w[i], co_w = a.w[i + 1];
+        const int nci = (ci_w + 31) / 32;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int sl = wave + s * kWaves;
+            if (sl * 32 >= co_w) continue;  // wave-uniform
+            const int o = sl * 32 + j;
+            if (blockIdx.z == 0) {
+                float own = hl[s];
+                if (i < kMaxLayers - 1 && i + 1 < L) own = hh[i < kMaxLayers - 1 ? i : 0][s];
+                const float other = __shfl_xor(own, 32, 64);
+                if (h == 0 && o < co_w) part[a.boff[i] + o] = own + other;
+            }
+            const int tf = base[i] - t0 + s * nci;  // the slab's first tile among this pass's
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+                const int ci = q - tf;
+                if (ci < 0 || ci >= nci) continue;  // wave-uniform
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = ci * 32 + mfma_row(r, h);
+                    if (c < ci_w && o < co_w) part[a.woff[i] + c + (size_t)ci_w * o] = H[q][r];
+                }
+            }
+        }
+    }
+}
+
+// ---- the finishing kernels -----------------------------------------------------------------------------------------------------
+struct FinishArgs {
+    const float *part;  // (psize, nparts)
+    float *sums;        // psize: H_l in W_l's place, h_l in b_l's
+    float *g;           // psize: the result
+    Conv c[kMaxLayers];
+    int woff[kMaxLayers], cin[kMaxLayers], cout[kMaxLayers];
+    int nl, psize, nparts;
+};
+
+// which layer element e of the parameter buffer belongs to, and its place in the layer's block W | b | gamma | beta | mu | var
+__device__ __forceinline__ bool locate(const FinishArgs &f, int e, int *layer, int *at) {
+#pragma unroll
+    for (int l = 0; l < kMaxLayers; ++l) {
+        if (l >= f.nl) break;
+        const int n = f.cin[l] * f.cout[l] + 5 * f.cout[l];
+        if (e >= f.woff[l] && e < f.woff[l] + n) {
+            *layer = l;
+            *at = e - f.woff[l];
+            return true;
+        }
+    }
+    return false;
+}
+
+// sums[e] = the chain from +0 over the chunk partials, b ascending, chunk ascending, for the elements of every H_l and h_l
+__global__ __launch_bounds__(256) void pgrad_reduce(const FinishArgs f) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    int l, at;
+    if (e >= f.psize || !locate(f, e, &l, &at)) return;
+    const int cin = l == 0 ? f.cin[0] : l == 1 ? f.cin[1] : l == 2 ? f.cin[2] : f.cin[3];
+    const int cout = l == 0 ? f.cout[0] : l == 1 ? f.cout[1] : l == 2 ? f.cout[2] : f.cout[3];
+    if (at >= (cin + 1) * cout) return;  // gamma, beta, mu, var: no sums
+    float acc = 0.0f;
+    for (int p = 0; p < f.nparts; ++p) acc = acc + f.part[(size_t)p * f.psize + e];
+    f.sums[e] = acc;
+}
+
+// the four families from H and h (flux3d_hip.h); mu and var: +0
+__global__ __launch_bounds__(256) void pgrad_finish(const FinishArgs f) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    int l, at;
+    if (e >= f.psize || !locate(f, e, &l, &at)) return;
+    const Conv c = l == 0 ? f.c[0] : l == 1 ? f.c[1] : l == 2 ? f.c[2] : f.c[3];
+    const int cin = l == 0 ? f.cin[0] : l == 1 ? f.cin[1] : l == 2 ? f.cin[2] : f.cin[3];
+    const int cout = l == 0 ? f.cout[0] : l == 1 ? f.cout[1] : l == 2 ? f.cout[2] : f.cout[3];
+    const int woff = l == 0 ? f.woff[0] : l == 1 ? f.woff[1] : l == 2 ? f.woff[2] : f.woff[3];
+    const float *Hs = f.sums + woff, *hs = Hs + cin * cout;
+    const int nw = cin * cout;
+    float v = 0.0f;
+    if (at < nw) {  // dW[c,o] = (H[c,o] gamma[o]) / sd[o]
+        const int o = at / cin;
+        v = (Hs[at] * c.bn.g[o]) / sqrtf(c.bn.v[o] + kBnEps);
+    } else {
+        const int fam = (at - nw) / cout, o = at - nw - fam * cout;
+        const float sd = sqrtf(c.bn.v[o] + kBnEps);
+        if (fam == 0) {  // db
+            v = (hs[o] * c.bn.g[o]) / sd;
+        } else if (fam == 1) {  // dgamma
+            float acc = 0.0f;
+            for (int i = 0; i < cin; ++i) acc = fmaf(c.W[i + cin * o], Hs[i + cin * o], acc);
+            v = (acc + (c.b[o] - c.bn.m[o]) * hs[o]) / sd;
+        } else if (fam == 2) {  // dbeta
+            v = hs[o];
+        }
+    }
+    f.g[e] = v;
+}
+
+// ---- the host side -------------------------------------------------------------------------------------------------
+struct Plan {
+    int ld, nt_w0, passes;  // the row stride; the tiles of wave 0's list (the longest); the passes over it
+    unsigned int lmin;      // PgradArgs::lmin
+    size_t lds_bytes;
+};
+// the H tiles a wave keeps in registers: what leaves the kernel without scratch at one wave per SIMD
+constexpr int kTilesNarrow = 14, kTilesWide = 12;  // strides 66 and 130 (one slab per wave); stride 258 (two)
+Plan plan(const int32_t *layers, int nlayers) {
+    Plan p{};
+    int widest = 2 * layers[0];
+    for (int i = 1; i < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
+    p.ld = widest <= 64 ? 66 : widest <= 128 ? kLd : 258;
+    const int L = nlayers - 1, nimg = L == 1 ? 2 : L == 2 ? 3 : L;
+    p.lds_bytes = (size_t)nimg * 32 * p.ld * sizeof(float);
+    for (int i = 1; i < nlayers; ++i) {
+        const int cin = i == 1 ? 2 * layers[0] : layers[i - 1];
+        p.nt_w0 += (((layers[i] + 31) / 32 + kWaves - 1) / kWaves) * ((cin + 31) / 32);
+    }
+    const int nt = p.ld == 258 ? kTilesWide : kTilesNarrow;
+    p.passes = (p.nt_w0 + nt - 1) / nt;
+    // the lowest layer of each pass: that of tile z nt of a wave's list (layer by layer, ascending), over the waves that have one
+    for (int z = 0; z < p.passes; ++z) {
+        int lmin = nlayers - 1;
+        for (int w = 0; w < kWaves; ++w) {
+            int at = 0;
+            for (int i = 1; i < nlayers; ++i) {
+                const int cin = i == 1 ? 2 * layers[0] : layers[i - 1];
+                const int slabs = (layers[i] + 31) / 32 - w;
+                at += (slabs > 0 ? (slabs + kWaves - 1) / kWaves : 0) * ((cin + 31) / 32);
+                if (at > z * nt) {
+                    lmin = i < lmin ? i : lmin;
+                    break;
+                }
+            }
+        }
+        p.lmin |= (unsigned int)lmin << (4 * z);
+    }
+    return p;
+}
+
+// the workspace: the forward's own | the lists | out | the transposed weights | the chunk partials | the sums
+struct WsPlan { size_t fwd, fwd_bytes, idx, out, wt, part, sums, total; long long psize; int chunks; };
+fx3d_status ws_plan(const int32_t *layers, int nlayers, int N, int B, int K, WsPlan *w) {
+    WsBump ws;
+    const fx3d_status rc = edgeconv_workspace_bytes(layers[0], N, B, K, &w->fwd_bytes);
+    if (rc != FX3D_OK) return rc;
+    w->psize = edgeconv_layout(nullptr, layers, nlayers, nullptr);
+    w->chunks = (N + kGradChunk - 1) / kGradChunk;
+    w->fwd = ws.put(w->fwd_bytes);
+    w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
+    w->out = ws.put((size_t)layers[nlayers - 1] * N * B * sizeof(float));
+    w->wt = ws.put(edgeconv_transposed_floats(layers, nlayers) * sizeof(float));
+    w->part = ws.put((size_t)w->psize * w->chunks * B * sizeof(float));
+    w->sums = ws.put((size_t)w->psize * sizeof(float));
+    w->total = ws.at;
+    return FX3D_OK;
+}
+
+template <int LD, int NS, int NT>
+fx3d_status launch(const PgradArgs &a, const Plan &p, int chunks, int B, hipStream_t st) {
+    const void *fn = reinterpret_cast<const void *>(&edgeconv_pgrad_kernel<LD, NS, NT>);
+    const fx3d_status rc = ensure_dynamic_lds(fn, (int)kMaxLds, "edgeconv_pgrad_kernel");
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof("edgeconv_pgrad", st);
+    hipLaunchKernelGGL((edgeconv_pgrad_kernel<LD, NS, NT>), dim3(chunks, B, p.passes), dim3(kPtThreads), p.lds_bytes, st, a);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+fx3d_status fx3d_edgeconv_grad_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B, size_t *bytes) {
+    const char *fn = "fx3d_edgeconv_grad_workspace_bytes";
+    FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
+    fx3d_status rc = check_layers(fn, layers, nlayers);
+    if (rc != FX3D_OK) return rc;
+    if ((rc = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return rc;
+    WsPlan w;
+    if ((rc = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return rc;
+    *bytes = w.total;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x, int32_t N,
+                               int32_t B, const int32_t *idx, const float *out, const float *gout, float *gparams, float *gx,
+                               void *ws, size_t ws_bytes, fx3d_stream_t s) {
+    const char *fn = "fx3d_edgeconv_grad";
+    FX3D_REQUIRE(params_dev && x && gout && gparams && ws, "%s: params_dev, x, gout, gparams and ws must not be NULL", fn);
+    fx3d_status r = check_layers(fn, layers, nlayers);
+    if (r != FX3D_OK) return r;
+    if ((r = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return r;
+    WsPlan w;
+    if ((r = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return r;
+    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_edgeconv_grad_workspace_bytes says %zu", fn, ws_bytes, w.total);
+    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
+
+    char *wsb = static_cast<char *>(ws);
+    hipStream_t st = as_stream(s);
+    PgradArgs a{};
+    FinishArgs f{};
+    edgeconv_layout(params_dev, layers, nlayers, a.c);
+    const int L = nlayers - 1;
+    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
+    for (int l = 0; l < L; ++l) {
+        a.woff[l] = (int)(a.c[l].W - params_dev);
+        a.boff[l] = (int)(a.c[l].b - params_dev);
+        f.c[l] = a.c[l];
+        f.woff[l] = a.woff[l];
+        f.cin[l] = l == 0 ? 2 * layers[0] : layers[l];
+        f.cout[l] = layers[l + 1];
+    }
+    a.nl = L; a.cout = layers[L];
+    a.N = N; a.K = K; a.x = x; a.gout = gout; a.gx = gx;
+    a.psize = (int)w.psize;
+    a.part = reinterpret_cast<float *>(wsb + w.part);
+    // the forward's part: the lists and / or out where the caller has none (the search is deterministic: the forward's lists)
+    int32_t *ws_idx = reinterpret_cast<int32_t *>(wsb + w.idx);
+    float *ws_out = reinterpret_cast<float *>(wsb + w.out);
+    if (!out) {
+        if ((r = edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx, ws_out, idx ? nullptr : ws_idx, wsb + w.fwd, s, "edgeconv")) != FX3D_OK) return r;
+    } else if (!idx) {
+        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, ws_idx, nullptr, wsb + w.fwd, w.fwd_bytes, s)) != FX3D_OK) return r;
+    }
+    a.idx = idx ? idx : ws_idx;
+    a.out = out ? out : ws_out;
+    if ((r = edgeconv_transpose_weights(a.c, layers, nlayers, reinterpret_cast<float *>(wsb + w.wt), a.wt, st)) != FX3D_OK) return r;
+    const Plan p = plan(layers, nlayers);
+    a.lmin = p.lmin;
+    switch (p.ld) {
+        case 66: r = launch<66, 1, kTilesNarrow>(a, p, w.chunks, B, st); break;
+        case kLd: r = launch<kLd, 1, kTilesNarrow>(a, p, w.chunks, B, st); break;
+        default: r = launch<258, 2, kTilesWide>(a, p, w.chunks, B, st); break;
+    }
+    if (r != FX3D_OK) return r;
+    f.part = a.part;
+    f.sums = reinterpret_cast<float *>(wsb + w.sums);
+    f.g = gparams;
+    f.nl = L; f.psize = a.psize; f.nparts = w.chunks * B;
+    const int blocks = (f.psize + 255) / 256;
+    {
+        ProfileScope prof("edgeconv_pgrad_finish", st);
+        hipLaunchKernelGGL(pgrad_reduce, dim3(blocks), dim3(256), 0, st, f);
+        FX3D_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pgrad_finish, dim3(blocks), dim3(256), 0, st, f);
+        FX3D_LAUNCH_CHECK();
+    }
+    return FX3D_OK;
+}
+
+}  // extern "C"

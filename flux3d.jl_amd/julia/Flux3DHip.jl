@@ -1683,7 +1683,7 @@ end
 # neighbours constants as CreateSingleKNNGraph is @nograd.  idx, out: the forward's lists and result (edgeconv_forward with
 # return_idx = true); either may be left out and is then computed again.
 # There is deliberately NO Zygote.@adjoint on (m::EdgeConv)(X): it would have to return `nothing` for the parameters, and a user
-# who trains through it would get silently zero weight gradients.  It waits for the parameter gradients.
+# who trains through it would get silently zero weight gradients.  edgeconv_gradient below has the parameter gradients.
 function edgeconv_input_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{Float32,3};
                                  idx::Union{Nothing,HipArray{Int32,3}} = nothing, out::Union{Nothing,HipArray{Float32,3}} = nothing)
     layers = Int32.(collect(m.layers))
@@ -1708,6 +1708,41 @@ function edgeconv_input_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipA
                                        gout.ptr::Ptr{Cvoid}, gx.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
                                        DEFAULT_STREAM::Stream)::Int32)
     return gx
+end
+
+
+# The gradients of sum(gout .* m(X)) with respect to m's parameters and to X (include/flux3d_hip.h "EdgeConv parameter adjoint"):
+# test-mode BatchNorm (gamma and beta are parameters, the running statistics constants), the neighbours constants.  Returns
+# (gflat, gx): gflat in the layout of edgeconv_params(m) with zeros in the mu / sigma2 slots, gx as edgeconv_input_gradient gives
+# it (nothing with input_grad = false).  Still no Zygote.@adjoint on (m::EdgeConv)(X): the reference trains with train-mode
+# BatchNorm, whose batch statistics this test-mode gradient does not differentiate.
+function edgeconv_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{Float32,3};
+                           idx::Union{Nothing,HipArray{Int32,3}} = nothing, out::Union{Nothing,HipArray{Float32,3}} = nothing,
+                           input_grad::Bool = true)
+    layers = Int32.(collect(m.layers))
+    nl = length(layers)
+    F, N, B = size(X)
+    K = m.K
+    cL = Int(layers[end])
+    F == layers[1] || error("EdgeConv($(m.layers), $K) takes $(layers[1]) channels per point, got $F")
+    (1 <= K && K + 1 <= N) || error("EdgeConv needs 1 <= K <= N - 1, got K = $K, N = $N")
+    size(gout) == (cL, N, B) || error("gout must be ($cL, $N, $B), got $(size(gout))")
+    out === nothing || size(out) == (cL, N, B) || error("out must be ($cL, $N, $B), got $(size(out))")
+    idx === nothing || size(idx) == (K, N, B) || error("idx must be ($K, $N, $B), got $(size(idx))")
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_edgeconv_grad_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
+                                                        Int32(B)::Int32, nb::Ref{Csize_t})::Int32)
+    params = edgeconv_params(m)
+    pd = hip(params)
+    ws = workspace(nb[])
+    gflat = HipArray{Float32}(undef, length(params))
+    gx = input_grad ? HipArray{Float32}(undef, F, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_edgeconv_grad(pd.ptr::Ptr{Cvoid}, layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, X.ptr::Ptr{Cvoid},
+                                        Int32(N)::Int32, Int32(B)::Int32, opt(idx)::Ptr{Cvoid}, opt(out)::Ptr{Cvoid},
+                                        gout.ptr::Ptr{Cvoid}, gflat.ptr::Ptr{Cvoid}, opt(gx)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid},
+                                        length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    return gflat, gx
 end
 
 

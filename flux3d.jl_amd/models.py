@@ -4,7 +4,7 @@
 include/flux3d_hip.h states the networks and their arithmetic ("PointNet inference", "DGCNN inference", "EdgeConv inference");
 this module owns the parameters (a name -> numpy array mapping in Flux's shapes), flattens them into the one device buffer
 fx3d_pointnet_forward / fx3d_dgcnn_forward / fx3d_edgeconv_forward reads, and checks every argument on the host before any
-launch.  Forward only: no training, no gradients."""
+launch.  The classifiers are forward only; EdgeConv also has its input gradient and its parameter gradients (test-mode BatchNorm)."""
 import ctypes as C
 
 import numpy as np
@@ -225,7 +225,8 @@ class DGCNN(_Model):
     multiple of npoints leaves several windows per cloud, which the reshape folds into the batch, anything else drops
     points.  ``forward`` therefore raises ``ValueError`` for clouds of any other size.
 
-    Forward only.  The gradient of the two EdgeConv stages with respect to the input is a composition of
+    Forward only.  The two EdgeConv stages have their gradients: :meth:`EdgeConv.grad` gives a stage's parameter gradients
+    (test-mode BatchNorm) together with its input gradient, and the gradient with respect to the input is a composition of
     :meth:`EdgeConv.input_grad`: with ``ec1 = EdgeConv([3, 32, 64, 64], K)`` and ``ec2 = EdgeConv([64, 128, 256], K)`` loaded
     with the ``ec1.`` / ``ec2.`` arrays, and ``idx1, x1, idx2, x2`` of ``forward(X, intermediates=True)``,
     ``ec1.input_grad(X, ec2.input_grad(x1, g, idx2, x2), idx1, x1)`` is the gradient of ``sum(g * x2)`` with respect to ``X``."""
@@ -374,7 +375,7 @@ class EdgeConv(_Model):
         "EdgeConv input adjoint".  ``X`` as in :meth:`forward`; ``gout`` ``(cL, N, B)`` lives where ``X`` lives, and so does
         the result.  ``idx``: the forward's neighbour lists (``return_idx=True``), ``out``: the forward's result; either may
         be left out, and is then computed again (the search is deterministic).  An ``out`` that is not this forward's passes
-        gradient only where some k reproduces it.  No parameter gradients: the weights are constants here."""
+        gradient only where some k reproduces it.  The weights are constants here; :meth:`grad` gives their gradients too."""
         F, K = self.layers[0], self.K
         if isinstance(X, PointCloud) and F != 3:
             raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
@@ -394,3 +395,57 @@ class EdgeConv(_Model):
         _lib.call("fx3d_edgeconv_bwd", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
                   o.ptr if o is not None else None, g.ptr, gx.ptr, ws.ptr, ws.nbytes, current_stream().handle)
         return gx if on_dev else gx.to_host()
+
+    def _grad_call(self, X, gout, idx, out, input_grad):
+        """fx3d_edgeconv_grad after :meth:`input_grad`'s checks: (the flat gradient, gx or None) on the device, and whether
+        ``X`` lives there."""
+        F, K = self.layers[0], self.K
+        if isinstance(X, PointCloud) and F != 3:
+            raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
+        pts, N, B, on_dev = self._clouds(X, f"EdgeConv({self.layers}, {K})", F)
+        if K + 1 > N:
+            raise ValueError(f"EdgeConv needs 1 <= K <= N - 1 (K neighbours besides the point itself), got K={K}, N={N}")
+        layers, nl = self._layers_c()
+        nb = _lib.query_bytes("fx3d_edgeconv_grad_workspace_bytes", layers, nl, K, N, B)
+        g = self._like_out(gout, "gout", N, B, on_dev)
+        o = None if out is None else self._like_out(out, "out", N, B, on_dev)
+        given = None if idx is None else self._neighbours(idx, N, B)
+        if not on_dev:
+            g, o = DeviceArray.from_host(g), (None if o is None else DeviceArray.from_host(o))
+        x = self._on_device(pts, N, B, on_dev, F)
+        gp = DeviceArray.empty((self.param_count,), np.float32)
+        gx = DeviceArray.empty((F, N, B), np.float32) if input_grad else None
+        ws = workspace(nb, tag="edgeconv_grad")
+        _lib.call("fx3d_edgeconv_grad", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
+                  o.ptr if o is not None else None, g.ptr, gp.ptr, gx.ptr if gx is not None else None, ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        return gp, gx, on_dev
+
+    def flat_grad(self, X, gout, idx=None, out=None, input_grad=True):
+        """``(gflat, gx)``: the gradient of ``sum(gout * forward(X))`` with respect to the parameters as ONE flat Float32
+        buffer with the layout of :meth:`flat_params` (the ``mu`` / ``sigma2`` slots are zero), for callers that step the
+        flat parameter buffer, and the gradient with respect to ``X`` (``None`` with ``input_grad=False``).  Arguments and
+        placement as :meth:`grad`."""
+        gp, gx, on_dev = self._grad_call(X, gout, idx, out, input_grad)
+        if not on_dev:
+            gp, gx = gp.to_host(), (None if gx is None else gx.to_host())
+        return gp, gx
+
+    def grad(self, X, gout, idx=None, out=None, input_grad=True):
+        """``(grads, gx)``: the gradients of ``sum(gout * forward(X))`` with respect to the parameters and to ``X``, from one
+        fused kernel: include/flux3d_hip.h "EdgeConv parameter adjoint".  BatchNorm in test mode: ``gamma`` and ``beta``
+        are parameters, the running statistics constants.  ``grads`` has the names and Flux shapes of
+        :func:`edgeconv_param_shapes`; its ``mu`` / ``sigma2`` entries are zero.  ``gx`` is :meth:`input_grad`'s result,
+        bit for bit, or ``None`` with ``input_grad=False``.  ``X``, ``gout``, ``idx`` and ``out`` as in :meth:`input_grad`;
+        everything lives where ``X`` lives."""
+        gp, gx, on_dev = self._grad_call(X, gout, idx, out, input_grad)
+        flat = None if on_dev else gp.to_host()
+        grads, at = {}, 0
+        for name, shape in self._shapes().items():
+            n = int(np.prod(shape))
+            if on_dev:  # a view of the flat buffer, which it keeps alive
+                grads[name] = DeviceArray(gp.ptr + 4 * at, shape, np.float32, owned=False, keep=gp)
+            else:
+                grads[name] = flat[at:at + n].reshape(shape, order="F")
+            at += n
+        return grads, (gx if on_dev or gx is None else gx.to_host())

@@ -959,6 +959,47 @@ FX3D_API fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *l
                                        int32_t N, int32_t B, const int32_t *idx, const float *out, const float *gout, float *gx,
                                        void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- EdgeConv parameter adjoint: the gradients of (m::EdgeConv)(X) with respect to its parameters, and to X, test mode --------
+ * gparams = d sum(gout . out) / d params for out = fx3d_edgeconv_forward(x), a flat Float32 buffer with the layout of params_dev
+ * (fx3d_edgeconv_param_count floats), and, if gx != NULL, gx (F,N,B) exactly as fx3d_edgeconv_bwd gives it, from one fused kernel
+ * and two small finishing kernels.  BatchNorm in test mode: mu and var are constants (their slots are written as +0), gamma and
+ * beta are parameters.  The neighbours are constants.  Arguments, idx == NULL and out == NULL as in "EdgeConv input adjoint".
+ * Notation of "EdgeConv input adjoint"; for layer l = 1 .. L and every edge row (b, n, k):
+ *   z_l = the forward's chain over c of a_{l-1}[c] W_l[c,o];  t_l = ((z_l + b_l) - mu_l) / sd_l;  a_l = relu(gamma_l t_l + beta_l).
+ *   d_l, the gradient at the relu's argument, is what the input adjoint forms, bit for bit: d_L = gout at the first k that
+ *   reproduces a positive out, else +0;  d_{l-1} = (a_{l-1} > 0) ? the chain over all o of dz_l Wt_l : +0;  dz_l = (d_l gamma_l) / sd_l.
+ * Two sums over all edge rows per layer:
+ *   H_l[c,o] = sum a_{l-1}[c] d_l[o]   (cin_l x cout_l)          h_l[o] = sum d_l[o]
+ * and from them, every operation rounded to Float32, none dividing by gamma:
+ *   dbeta_l[o]  = h_l[o]
+ *   db_l[o]     = (h_l[o] gamma_l[o]) / sd_l[o]
+ *   dW_l[c,o]   = (H_l[c,o] gamma_l[o]) / sd_l[o]
+ *   dgamma_l[o] = (acc + (b_l[o] - mu_l[o]) h_l[o]) / sd_l[o],  acc = fmaf(W_l[c,o], H_l[c,o], acc) for c ascending from +0.0f
+ *   (sum d z = sum_c W[c,o] H[c,o]: t_l is never kept).
+ * The order of the sums is part of the contract.  It depends on (layers, K, N, B) alone -- not on the device, the launch shape,
+ * how the kernel splits its work, the workspace or the run:
+ *   a chunk is FX3D_EDGECONV_GRAD_CHUNK = 128 consecutive points of one cloud (the last chunk of a cloud may be shorter), made
+ *   of tiles of 32 consecutive points.  Within a tile the points are visited in the order
+ *     perm = 0,4, 1,5, 2,6, 3,7, 8,12, 9,13, 10,14, 11,15, 16,20, 17,21, 18,22, 19,23, 24,28, 25,29, 26,30, 27,31
+ *   (pair r = 0 .. 15 is (q, q + 4) with q = (r mod 4) + 8 (r div 4)), points beyond the cloud's last one left out.
+ *   H_l[c,o] of a chunk: ONE chain from +0.0f, acc = fmaf(a_{l-1}[row][c], d_l[row][o], acc), over the chunk's tiles ascending,
+ *     within a tile k ascending, within a k the tile's points in the order perm.
+ *   h_l[o] of a chunk: two chains of Float32 additions from +0 in the same order, one over the first points of the pairs
+ *     (q), one over the second (q + 4), then first + second.
+ *   H_l and h_l: one chain of Float32 additions from +0 over the chunk values, b ascending, within b the chunks ascending.
+ *   (So a batch is not the sum of its clouds' separate results, and N > 128 is not one chain.)
+ * gparams and gx are bit-identical to the restatement tests/edgeconv_pgrad_ref.py and from run to run; no float atomics, no
+ * (K N, ., B) array in memory.  gx is fx3d_edgeconv_bwd's, bit for bit.
+ * Envelope, refusals, their order, status codes and messages are fx3d_edgeconv_bwd's (required pointers: params_dev, layers, x,
+ * gout, gparams, ws); every refusal comes before any device work.  Launches on `s` only (the search and / or the forward where
+ * idx / out are NULL, the weight transpose, the kernel, two finishing kernels), no host synchronisation (graph-capturable).
+ * ws: fx3d_edgeconv_grad_workspace_bytes -- the input adjoint's, one partial of param_count floats per chunk and cloud, and the sums. */#define FX3D_EDGECONV_GRAD_CHUNK 128 /* points of one cloud whose rows are summed as one chain ("EdgeConv parameter adjoint") */
+FX3D_API fx3d_status fx3d_edgeconv_grad_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
+                                                        size_t *bytes);
+FX3D_API fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
+                                        int32_t N, int32_t B, const int32_t *idx, const float *out, const float *gout,
+                                        float *gparams, float *gx, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
