@@ -10,7 +10,7 @@
 //     LD mod 64 = 2 is the bank pattern kLd documents; a template parameter, so that an LDS address is a register plus an
 //     immediate): `rows` holds the edge rows [x_n, x_idx(k,n) - x_n], img0 and img1 take the hidden layers in turn
 //     (rows -> img0 -> img1 -> img0).  L = 1 needs `rows` alone, L = 2 rows and img0.  Three images of stride 258 (198 KB)
-//     do not fit the CU's 160 KB (two are 132 KB): then img1 IS `rows`, and the x_n half, otherwise gathered once before the
+//     do not fit the CU's 160 KB (two are 132 KB, kMaxLds): then img1 IS `rows`, and the x_n half, otherwise gathered once before the
 //     loop, is gathered again with every k (EdgeConvArgs::shared_rows).
 //   Per k: gather the second half of the rows; every hidden layer from image to image (conv_rt: the MFMA over the first
 //     4 floor(Cin / 4) input channels, v_fma_f32 on the accumulator for the rest, mfma_slab_rt); the LAST layer is never stored
@@ -27,8 +27,6 @@ using namespace fx3d;
 using namespace fx3d::mlp;
 
 namespace {
-
-constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // two images of the widest stride: 132 KB of the CU's 160 KB
 
 struct EdgeConvArgs {
     const float *x;      // (F, N, B)
@@ -162,7 +160,7 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_kernel(const EdgeConvArgs
 void lds_plan(const int32_t *layers, int nlayers, EdgeConvArgs *a, int *ld, size_t *bytes) {
     int widest = 2 * layers[0];
     for (int i = 1; i + 1 < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
-    *ld = widest <= 64 ? 66 : widest <= 128 ? kLd : 258;
+    *ld = edge_stride(widest);
     const int L = nlayers - 1, image = kTile * *ld;
     int nimg = L >= 3 ? 3 : L;
     a->shared_rows = (size_t)nimg * image * sizeof(float) > kMaxLds;

@@ -2,6 +2,8 @@
 // include/flux3d_hip.h ("EdgeConv input adjoint") states the definition; tests/edgeconv_bwd_ref.py restates it on the host.
 // The neighbours are constants (CreateSingleKNNGraph is @nograd), so the gradient of point n depends on the K edge rows of
 // point n alone: no scatter, no inverse lists, no atomics.  The arithmetic is the forward's contract (mlp_common.h), transposed.
+// The chain's steps are edgeconv_adjoint.h's, which the parameter adjoint (edgeconv_pgrad.hip) calls too; this file owns the
+// transpose and the host preamble of both (edgeconv_adjoint_plan, edgeconv_adjoint_prepare).
 //
 // Per call: the search and / or the forward if the caller does not give idx / out (edgeconv_run and fx3d_knn_ws, as
 // fx3d_edgeconv_forward runs them), transpose_weights (Wt_l[o + cout c] = W_l[c + cin o] for every layer into the workspace, so
@@ -17,33 +19,19 @@
 //          the maximum takes the gradient, no later one does ("already chosen" is the NaN; NaN == anything is false);
 //     dzg  (gout gamma_L) / sd_L, what dz_L is where k is chosen;  dz0 = (+0 gamma_L) / sd_L, what it is elsewhere;
 //     S    the running sums over k of d_0, for the lane's channel of the 2F.
-//   Per k: gather the edge rows; the hidden layers image to image and the last layer slab by slab exactly as edgeconv_kernel
-//     computes them (mfma_slab_rt, epilogue<kBnRelu>: the forward's bits); compare with tgt and write dz_L; walk back: for
-//     l = L .. 2 d_{l-1} = the chain over ALL o of dz_l with Wt_l, masked by a_{l-1} > 0, times gamma_{l-1}, divided by sd_{l-1}
-//     into a_{l-1}'s place; d_0 from dz_1 and Wt_1, added to S.  After the last k: S to `rows`, gx[f] = S[f] - S[F + f].
+//   Per k (the steps of edgeconv_adjoint.h): gather_rows; hidden_fwd_chain, the hidden layers image to image, and last_compare,
+//     the last layer slab by slab, exactly as edgeconv_kernel computes them (mfma_slab_rt, epilogue<kBnRelu>: the forward's bits),
+//     compared with tgt, dz_L written; back_layer for l = L .. 2: d_{l-1} = the chain over ALL o of dz_l with Wt_l, masked by
+//     a_{l-1} > 0, times gamma_{l-1}, divided by sd_{l-1} into a_{l-1}'s place; add_d0: d_0 from dz_1 and Wt_1, added to S.
+//     After the last k, store_gx: S to `rows`, gx[f] = S[f] - S[F + f].
 //   A slab beyond a width's last channel: its lanes read the last channel's parameters, run the wave's MFMAs and write nothing.
 //   Rows beyond the cloud's last point are zeros with tgt = NaN: computed, never written.
-#include "mlp_common.h"
+#include "edgeconv_adjoint.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
 
 namespace {
-
-constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // as edgeconv.hip: 132 KB of the CU's 160 KB
-
-struct EdgeConvBwdArgs {
-    const float *x;      // (F, N, B)
-    const int32_t *idx;  // (K, N, B), 0-based
-    const float *out;    // (cL, N, B): the forward's
-    const float *gout;   // (cL, N, B)
-    float *gx;           // (F, N, B)
-    Conv c[kMaxLayers];
-    const float *wt[kMaxLayers];  // Wt_l[o + cout c]
-    int w[kMaxLayers + 1];        // F, c1, ..., cL
-    int nl, cout;                 // L, cL
-    int N, K;
-};
 
 struct TransposeArgs {
     const float *W[kMaxLayers];
@@ -65,7 +53,7 @@ __global__ __launch_bounds__(256) void transpose_weights(const TransposeArgs t) 
 }
 
 template <int LD, int NH, int NS>
-__global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const EdgeConvBwdArgs a) {
+__global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const AdjointArgs a) {
     extern __shared__ float lds[];
     constexpr int T = 32 * NH, IMG = T * LD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
@@ -76,13 +64,14 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const EdgeConv
     const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
     float *rows = lds;
     float *dzl = L == 1 ? lds + IMG : lds;  // where dz_L goes
-    const float nan = __int_as_float(0x7fc00000);
-    // the layers by wave-uniform selects among the kernel arguments (a constant index in every access, as edgeconv_kernel)
+    // the last layer by wave-uniform selects among the kernel arguments (a constant index in every access, as edgeconv_kernel)
     const Conv cl = L == 1 ? a.c[0] : L == 2 ? a.c[1] : L == 3 ? a.c[2] : a.c[3];
-    const int cinl = L == 1 ? 2 * F : L == 2 ? a.w[1] : L == 3 ? a.w[2] : a.w[3];  // the last layer's input width
+    const int cinl = L == 1 ? 2 * F : L == 2 ? a.w[1] : L == 3 ? a.w[2] : a.w[3];  // its input width
 
+    const float nan = quiet_nan();
     f32x16 tgt[NS][NH], dzg[NS][NH], S[NS][NH];
     float dz0[NS];
+    // the target load (each adjoint's own, edgeconv_adjoint.h says why)
     {
         const size_t base = ((size_t)b * a.N + p0) * cout;
 #pragma unroll
@@ -114,89 +103,43 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_bwd_kernel(const EdgeConv
         // (`rows` was last read before a barrier of the previous k: by its first layer, or by hidden_bwd of layer L as dz_L)
         gather_rows<T>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
         __syncthreads();
-        const float *src = rows;
-        int cin = 2 * F;
-        for (int i = 0; i + 1 < L; ++i) {
-            const Conv c = i == 0 ? a.c[0] : i == 1 ? a.c[1] : a.c[2];
-            const int co = i == 0 ? a.w[1] : i == 1 ? a.w[2] : a.w[3];
-            float *dst = lds + (i + 1) * IMG;
-            hidden_fwd<LD, NH>(src, dst, cin, co, c);
-            __syncthreads();
-            src = dst;
-            cin = co;
-        }
-        // the last layer, compared with the forward's maxima: dz_L
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int sl = wave + s * kWaves;
-            if (sl * 32 >= cout) continue;  // wave-uniform
-            const int o = sl * 32 + j, oc = min(o, cout - 1);
-            f32x16 acc[NH];
-#pragma unroll
-            for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-            mfma_slab_rt<LD, NH>(src, cl.W + (size_t)cinl * oc, cinl, h, j, acc);
-            const float bi = cl.b[oc], g = cl.bn.g[oc], be = cl.bn.b[oc], mu = cl.bn.m[oc], sd = sqrtf(cl.bn.v[oc] + kBnEps);
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int t = 0; t < NH; ++t) {
-                    const bool first = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd) == tgt[s][t][r];
-                    if (o < cout) dzl[(t * 32 + mfma_row(r, h)) * LD + o] = first ? dzg[s][t][r] : dz0[s];
-                    tgt[s][t][r] = first ? nan : tgt[s][t][r];
-                }
-        }
+        const float *src = hidden_fwd_chain<LD, NH>(a, lds, F, L);
+        last_compare<LD, NH, NS, true>(src, dzl, cl, cinl, cout, wave, h, j, tgt, dzg, dz0, NoSink{});
         __syncthreads();
-        // the way back: dz_l in img[l] (dz_L in dzl), d_{l-1} into a_{l-1}'s place
-        for (int l = L; l >= 2; --l) {
-            const float *dz = l == L ? dzl : lds + l * IMG;
-            const int co = l == 2 ? a.w[2] : l == 3 ? a.w[3] : a.w[4];
-            const int ci = l == 2 ? a.w[1] : l == 3 ? a.w[2] : a.w[3];
-            const float *wt = l == 2 ? a.wt[1] : l == 3 ? a.wt[2] : a.wt[3];
-            const Bn bn = l == 2 ? a.c[0].bn : l == 3 ? a.c[1].bn : a.c[2].bn;
-            hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn, NoSink{});
-            __syncthreads();
-        }
-        // d_0 from dz_1 (img[1] for every L), added to the sums over k
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int sl = wave + s * kWaves;
-            if (sl * 32 >= 2 * F) continue;  // wave-uniform
-            const int cc = min(sl * 32 + j, 2 * F - 1);
-            f32x16 acc[NH];
-#pragma unroll
-            for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-            mfma_slab_rt<LD, NH>(lds + IMG, a.wt[0] + (size_t)a.w[1] * cc, a.w[1], h, j, acc);
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int t = 0; t < NH; ++t) S[s][t][r] = S[s][t][r] + acc[t][r];
-        }
+        for (int l = L; l >= 2; --l) back_layer<LD, NH>(a, lds, dzl, L, l, NoSink{});
+        add_d0<LD, NH, NS>(a, lds, F, wave, h, j, S);
         // (img[1] is written again after the barrier that follows the next gather, which a wave reaches after these reads)
     }
-    // S to `rows` (last read before a barrier above), then gx[f] = S[f] - S[F + f]
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int c = (wave + s * kWaves) * 32 + j;
-        if (c >= 2 * F) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int t = 0; t < NH; ++t) rows[(t * 32 + mfma_row(r, h)) * LD + c] = S[s][t][r];
-    }
-    __syncthreads();
-    float *gb = a.gx + ((size_t)b * a.N + p0) * F;
-    const float rf = 1.0f / (float)F;
-    for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
-        const int p = edge_row_of(i, rf), c = i - p * F;
-        if (p < nvalid) gb[(size_t)p * F + c] = rows[p * LD + c] - rows[p * LD + F + c];
-    }
+    store_gx<LD, NH, NS>(a, rows, b, p0, nvalid, wave, h, j, S);
+}
+
+// ---- the host side -------------------------------------------------------------------------------------------------
+// the LDS images: 64 points per block where max(L, 2) of them fit, else 32
+void lds_plan(const int32_t *layers, int nlayers, int *ld, int *nh, size_t *bytes) {
+    *ld = adjoint_stride(layers, nlayers);
+    const int L = nlayers - 1, nimg = L >= 2 ? L : 2;
+    const size_t half = (size_t)nimg * 32 * *ld * sizeof(float);
+    *nh = 2 * half <= kMaxLds ? 2 : 1;
+    *bytes = *nh * half;
+}
+
+template <int LD, int NH, int NS>
+fx3d_status launch(const AdjointArgs &a, size_t lds_bytes, int B, hipStream_t st) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&edgeconv_bwd_kernel<LD, NH, NS>), (int)kMaxLds, "edgeconv_bwd_kernel");
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof("edgeconv_bwd", st);
+    const int T = 32 * NH;
+    hipLaunchKernelGGL((edgeconv_bwd_kernel<LD, NH, NS>), dim3((a.N + T - 1) / T, B), dim3(kPtThreads), lds_bytes, st, a);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
 }
 
 }  // namespace
 
-// Wt_l of every layer into `wt` (edgeconv_transposed_floats(layers, nlayers) floats), wt_of[l]: where layer l + 1's begins
 namespace fx3d {
 namespace mlp {
+
+// Wt_l of every layer into `wt` (edgeconv_transposed_floats(layers, nlayers) floats), wt_of[l]: where layer l + 1's begins
 size_t edgeconv_transposed_floats(const int32_t *layers, int nlayers) {
     size_t nw = 0;
     for (int i = 1; i < nlayers; ++i) nw += (size_t)(i == 1 ? 2 * layers[0] : layers[i - 1]) * layers[i];
@@ -218,61 +161,58 @@ fx3d_status edgeconv_transpose_weights(const Conv *c, const int32_t *layers, int
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
-}  // namespace mlp
-}  // namespace fx3d
 
-namespace {
-
-// ---- the host side -------------------------------------------------------------------------------------------------
-// the LDS images: one stride for all, from the widest of 2F, c1 .. cL; 64 points per block where they fit, else 32
-void lds_plan(const int32_t *layers, int nlayers, int *ld, int *nh, size_t *bytes) {
-    int widest = 2 * layers[0];
-    for (int i = 1; i < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
-    *ld = widest <= 64 ? 66 : widest <= 128 ? kLd : 258;
-    const int L = nlayers - 1, nimg = L >= 2 ? L : 2;
-    const size_t half = (size_t)nimg * 32 * *ld * sizeof(float);
-    *nh = 2 * half <= kMaxLds ? 2 : 1;
-    *bytes = *nh * half;
-}
-
-// the workspace: the forward's own (the search's scratch) | the neighbour lists (K, N, B) | out (cL, N, B) | the transposed weights
-struct WsPlan { size_t fwd, fwd_bytes, idx, out, wt, total; };
-fx3d_status ws_plan(const int32_t *layers, int nlayers, int N, int B, int K, WsPlan *w) {
-    WsBump ws;
-    const fx3d_status rc = edgeconv_workspace_bytes(layers[0], N, B, K, &w->fwd_bytes);
+// ---- the host preamble of both adjoints (edgeconv_adjoint.h) -----------------------------------------------------------------
+fx3d_status edgeconv_adjoint_plan(const char *fn, const int32_t *layers, int nlayers, int N, int B, int K, WsBump &ws, AdjointWs *w) {
+    fx3d_status rc = check_layers(fn, layers, nlayers);
     if (rc != FX3D_OK) return rc;
+    if ((rc = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return rc;
+    if ((rc = edgeconv_workspace_bytes(layers[0], N, B, K, &w->fwd_bytes)) != FX3D_OK) return rc;
     w->fwd = ws.put(w->fwd_bytes);
     w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
     w->out = ws.put((size_t)layers[nlayers - 1] * N * B * sizeof(float));
     w->wt = ws.put(edgeconv_transposed_floats(layers, nlayers) * sizeof(float));
-    w->total = ws.at;
     return FX3D_OK;
 }
 
-template <int LD, int NH, int NS>
-fx3d_status launch(const EdgeConvBwdArgs &a, size_t lds_bytes, int B, hipStream_t st) {
-    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&edgeconv_bwd_kernel<LD, NH, NS>), (int)kMaxLds, "edgeconv_bwd_kernel");
-    if (rc != FX3D_OK) return rc;
-    ProfileScope prof("edgeconv_bwd", st);
-    const int T = 32 * NH;
-    hipLaunchKernelGGL((edgeconv_bwd_kernel<LD, NH, NS>), dim3((a.N + T - 1) / T, B), dim3(kPtThreads), lds_bytes, st, a);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
+fx3d_status edgeconv_adjoint_prepare(const char *fn, const char *size_fn, const AdjointWs &w, size_t need, const float *params_dev,
+                                     const int32_t *layers, int nlayers, int K, const float *x, int N, int B, const int32_t *idx,
+                                     const float *out, const float *gout, float *gx, void *ws, size_t ws_bytes, fx3d_stream_t s,
+                                     AdjointArgs *a) {
+    FX3D_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, %s says %zu", fn, ws_bytes, size_fn, need);
+    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
+    char *wsb = static_cast<char *>(ws);
+    edgeconv_layout(params_dev, layers, nlayers, a->c);
+    for (int i = 0; i < nlayers; ++i) a->w[i] = layers[i];
+    a->nl = nlayers - 1; a->cout = layers[nlayers - 1];
+    a->N = N; a->K = K; a->x = x; a->gout = gout; a->gx = gx;
+    // the forward's part: the lists and / or out where the caller has none (the search is deterministic: the forward's lists)
+    int32_t *ws_idx = reinterpret_cast<int32_t *>(wsb + w.idx);
+    float *ws_out = reinterpret_cast<float *>(wsb + w.out);
+    fx3d_status r = FX3D_OK;
+    if (!out) {
+        if ((r = edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx, ws_out, idx ? nullptr : ws_idx, wsb + w.fwd, s, "edgeconv")) != FX3D_OK) return r;
+    } else if (!idx) {
+        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, ws_idx, nullptr, wsb + w.fwd, w.fwd_bytes, s)) != FX3D_OK) return r;
+    }
+    a->idx = idx ? idx : ws_idx;
+    a->out = out ? out : ws_out;
+    return edgeconv_transpose_weights(a->c, layers, nlayers, reinterpret_cast<float *>(wsb + w.wt), a->wt, as_stream(s));
 }
 
-}  // namespace
+}  // namespace mlp
+}  // namespace fx3d
 
 extern "C" {
 
 fx3d_status fx3d_edgeconv_bwd_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B, size_t *bytes) {
     const char *fn = "fx3d_edgeconv_bwd_workspace_bytes";
     FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
-    fx3d_status rc = check_layers(fn, layers, nlayers);
+    WsBump ws;
+    AdjointWs w;
+    const fx3d_status rc = edgeconv_adjoint_plan(fn, layers, nlayers, N, B, K, ws, &w);
     if (rc != FX3D_OK) return rc;
-    if ((rc = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return rc;
-    WsPlan w;
-    if ((rc = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return rc;
-    *bytes = w.total;
+    *bytes = ws.at;
     return FX3D_OK;
 }
 
@@ -281,35 +221,17 @@ fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *layers, in
                               size_t ws_bytes, fx3d_stream_t s) {
     const char *fn = "fx3d_edgeconv_bwd";
     FX3D_REQUIRE(params_dev && x && gout && gx && ws, "%s: params_dev, x, gout, gx and ws must not be NULL", fn);
-    fx3d_status r = check_layers(fn, layers, nlayers);
+    WsBump bump;
+    AdjointWs w;
+    AdjointArgs a{};
+    fx3d_status r = edgeconv_adjoint_plan(fn, layers, nlayers, N, B, K, bump, &w);
     if (r != FX3D_OK) return r;
-    if ((r = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return r;
-    WsPlan w;
-    if ((r = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return r;
-    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_edgeconv_bwd_workspace_bytes says %zu", fn, ws_bytes, w.total);
-    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
-
-    char *wsb = static_cast<char *>(ws);
-    hipStream_t st = as_stream(s);
-    EdgeConvBwdArgs a{};
-    edgeconv_layout(params_dev, layers, nlayers, a.c);
-    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
-    a.nl = nlayers - 1; a.cout = layers[nlayers - 1];
-    a.N = N; a.K = K; a.x = x; a.gout = gout; a.gx = gx;
-    // the forward's part: the lists and / or out where the caller has none (the search is deterministic: the forward's lists)
-    int32_t *ws_idx = reinterpret_cast<int32_t *>(wsb + w.idx);
-    float *ws_out = reinterpret_cast<float *>(wsb + w.out);
-    if (!out) {
-        if ((r = edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx, ws_out, idx ? nullptr : ws_idx, wsb + w.fwd, s, "edgeconv")) != FX3D_OK) return r;
-    } else if (!idx) {
-        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, ws_idx, nullptr, wsb + w.fwd, w.fwd_bytes, s)) != FX3D_OK) return r;
-    }
-    a.idx = idx ? idx : ws_idx;
-    a.out = out ? out : ws_out;
-    if ((r = edgeconv_transpose_weights(a.c, layers, nlayers, reinterpret_cast<float *>(wsb + w.wt), a.wt, st)) != FX3D_OK) return r;
+    if ((r = edgeconv_adjoint_prepare(fn, "fx3d_edgeconv_bwd_workspace_bytes", w, bump.at, params_dev, layers, nlayers, K, x, N, B,
+                                      idx, out, gout, gx, ws, ws_bytes, s, &a)) != FX3D_OK) return r;
     size_t lds_bytes = 0;
     int ld = 0, nh = 0;
     lds_plan(layers, nlayers, &ld, &nh, &lds_bytes);
+    hipStream_t st = as_stream(s);
     // the stride 66 holds 64 channels at most: one slab per wave there
     switch (ld) {
         case 66: return launch<66, 2, 1>(a, lds_bytes, B, st);  // (four images are 68 KB: always 64 points)

@@ -2,9 +2,10 @@
 // BatchNorm) and, when asked, with respect to the input, from one fused kernel (gfx950).  include/flux3d_hip.h ("EdgeConv
 // parameter adjoint") states the definition and the order of every sum; tests/edgeconv_pgrad_ref.py restates it on the host.
 //
-// The chain is the input adjoint's (edgeconv_bwd.hip; gather_rows, hidden_fwd, hidden_bwd of mlp_common.h): per neighbour rank k
-// the forward tile is recomputed, the k that took the maximum found, and the layers walked back.  Where that kernel drops a
-// layer's upstream gradient d_l, this one contracts it with the layer's input, which is still in its LDS image:
+// The chain is the input adjoint's (edgeconv_bwd.hip), step by step the functions of edgeconv_adjoint.h that it calls: per
+// neighbour rank k the forward tile is recomputed (gather_rows, hidden_fwd_chain), the k that took the maximum found
+// (last_compare), and the layers walked back (back_layer, add_d0; store_gx per tile).  Where that kernel gives the steps empty
+// sinks, this one contracts a layer's upstream gradient d_l with the layer's input, which is still in its LDS image (take):
 //   H_l[c,o] += sum over the tile's rows of a_{l-1}[row][c] d_l[row][o],   h_l[o] += sum of d_l[row][o].
 // edgeconv_pgrad_kernel<LD, NS, NT>: one block = one chunk of kGradChunk = 128 consecutive points of one cloud = up to four
 //   32-point tiles, one after the other, 4 waves, looping over k inside a tile.  gridDim = (chunks, B, passes).
@@ -26,10 +27,11 @@
 //   LDS: images of 32 rows, stride LD as the adjoint.  L = 1: rows, dz_1.  L = 2: rows, a_1 / dz_1, dz_2 (d_1 is contracted with
 //     the edge rows, which must outlive dz_2).  L >= 3: L images, dz_L in `rows`' place as in the adjoint, and the edge rows
 //     gathered again for the same k once hidden_bwd(L) has consumed dz_L.  Four images of stride 258 are 132 KB.
-//   gx (pass 0, when asked): the adjoint's sums S and subtraction, per tile.
+//   gx (pass 0, when asked): the adjoint's sums S and subtraction, per tile.  Unlike the input adjoint this kernel keeps gout as
+//     it is (gv) and scales at the compare (last_compare with SCALED = false): d_L is what it contracts.
 // Then pgrad_reduce (the chunk partials of every H and h element as one chain, b ascending, chunk ascending) and pgrad_finish
 // (the four families from H and h).
-#include "mlp_common.h"
+#include "edgeconv_adjoint.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
@@ -38,22 +40,12 @@ namespace {
 
 constexpr int kGradChunk = FX3D_EDGECONV_GRAD_CHUNK;
 constexpr int kGradTiles = kGradChunk / 32;
-constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);  // as edgeconv.hip: 132 KB of the CU's 160 KB
 
-struct PgradArgs {
-    const float *x;      // (F, N, B)
-    const int32_t *idx;  // (K, N, B), 0-based
-    const float *out;    // (cL, N, B): the forward's
-    const float *gout;   // (cL, N, B)
-    float *gx;           // (F, N, B) or NULL
-    float *part;         // (psize, chunks, B): the chunk partials
-    Conv c[kMaxLayers];
-    const float *wt[kMaxLayers];  // Wt_l[o + cout c]
+struct PgradArgs : AdjointArgs {
+    float *part;                             // (psize, chunks, B): the chunk partials
     int woff[kMaxLayers], boff[kMaxLayers];  // W_l and b_l in the parameter buffer (floats)
-    int w[kMaxLayers + 1];        // F, c1, ..., cL
-    int nl, cout;                 // L, cL
-    int N, K, psize;
-    unsigned int lmin;            // 4 bits per pass: the lowest layer that has a tile in it
+    int psize;
+    unsigned int lmin;                       // 4 bits per pass: the lowest layer that has a tile in it
 };
 
 // the tiles of one layer in a wave's list: its slabs (wave, wave + 4, ... below cout) times the layer's input tiles
@@ -99,9 +91,9 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_pgrad_kernel(const PgradA
     const float *xb = a.x + (size_t)b * a.N * F;
     float *rows = lds;
     float *dzl = L == 1 ? lds + IMG : L == 2 ? lds + 2 * IMG : lds;  // where dz_L goes
-    const float nan = __int_as_float(0x7fc00000);
+    // the last layer by wave-uniform selects among the kernel arguments (a constant index in every access, as edgeconv_kernel)
     const Conv cl = L == 1 ? a.c[0] : L == 2 ? a.c[1] : L == 3 ? a.c[2] : a.c[3];
-    const int cinl = L == 1 ? 2 * F : L == 2 ? a.w[1] : L == 3 ? a.w[2] : a.w[3];  // the last layer's input width
+    const int cinl = L == 1 ? 2 * F : L == 2 ? a.w[1] : L == 3 ? a.w[2] : a.w[3];  // its input width
     // the wave's tile list: base[i] = the first tile of layer i + 1
     int base[kMaxLayers];
     {
@@ -130,15 +122,18 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_pgrad_kernel(const PgradA
         if (p0 >= a.N) break;  // block-uniform
         const int nvalid = min(T, a.N - p0);
         const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
-        f32x16 tgt[NS], gv[NS], S[NS];
+        f32x16 tgt[NS][1], gv[NS][1], S[NS][1];
         float dz0[NS];
+        const float nan = quiet_nan();
+        // the target load (kept here, not a step of edgeconv_adjoint.h: as one, this kernel spilled to scratch at stride 258):
+        // tgt = out where positive, else NaN; gv = gout; dz0 = (+0 gamma_L) / sd_L; rows beyond the cloud: NaN and +0
         {
             const size_t ob = ((size_t)b * a.N + p0) * cout;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int sl = wave + s * kWaves;
                 dz0[s] = 0.0f;
-                S[s] = tgt[s] = gv[s] = f32x16{0};
+                S[s][0] = tgt[s][0] = gv[s][0] = f32x16{0};
                 if (sl * 32 >= cout) continue;  // wave-uniform
                 const int oc = min(sl * 32 + j, cout - 1);
                 dz0[s] = (0.0f * cl.bn.g[oc]) / sqrtf(cl.bn.v[oc] + kBnEps);
@@ -150,93 +145,39 @@ __global__ __launch_bounds__(kPtThreads) void edgeconv_pgrad_kernel(const PgradA
                         ov = a.out[ob + (size_t)p * cout + oc];
                         g = a.gout[ob + (size_t)p * cout + oc];
                     }
-                    tgt[s][r] = ov > 0.0f ? ov : nan;
-                    gv[s][r] = g;
+                    tgt[s][0][r] = ov > 0.0f ? ov : nan;
+                    gv[s][0][r] = g;
                 }
             }
         }
         for (int k = 0; k < a.K; ++k) {
             gather_rows<T>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
             __syncthreads();
-            const float *src = rows;
-            int cin = 2 * F;
-            for (int i = 0; i + 1 < L; ++i) {
-                const Conv c = i == 0 ? a.c[0] : i == 1 ? a.c[1] : a.c[2];
-                const int co = i == 0 ? a.w[1] : i == 1 ? a.w[2] : a.w[3];
-                float *dst = lds + (i + 1) * IMG;
-                hidden_fwd<LD, 1>(src, dst, cin, co, c);
-                __syncthreads();
-                src = dst;
-                cin = co;
-            }
-            // the last layer, compared with the forward's maxima: dz_L to its image, d_L against a_{L-1}
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int sl = wave + s * kWaves;
-                if (sl * 32 >= cout) continue;  // wave-uniform
-                const int o = sl * 32 + j, oc = min(o, cout - 1);
-                f32x16 acc[1] = {f32x16{0}};
-                mfma_slab_rt<LD, 1>(src, cl.W + (size_t)cinl * oc, cinl, h, j, acc);
-                const float bi = cl.b[oc], g = cl.bn.g[oc], be = cl.bn.b[oc], mu = cl.bn.m[oc], sd = sqrtf(cl.bn.v[oc] + kBnEps);
-                f32x16 d;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const bool first = epilogue<kBnRelu>(acc[0][r], bi, g, be, mu, sd) == tgt[s][r];
-                    if (o < cout) dzl[mfma_row(r, h) * LD + o] = first ? (gv[s][r] * g) / sd : dz0[s];
-                    d[r] = first ? gv[s][r] : 0.0f;
-                    tgt[s][r] = first ? nan : tgt[s][r];
-                }
-                take<LD, NT, NS>(H, hl, d, sl, wave, nvalid, basel, src, cinl, h, j);
-            }
+            const float *src = hidden_fwd_chain<LD, 1>(a, lds, F, L);
+            // dz_L to its image, d_L against a_{L-1}
+            last_compare<LD, 1, NS, false>(src, dzl, cl, cinl, cout, wave, h, j, tgt, gv, dz0, [&](int sl, const f32x16(&d)[1]) {
+                take<LD, NT, NS>(H, hl, d[0], sl, wave, nvalid, basel, src, cinl, h, j);
+            });
             __syncthreads();
-            // the way back: dz_l in img[l] (dz_L in dzl), d_{l-1} into a_{l-1}'s place and against a_{l-2}
+            // the way back: d_{l-1} into a_{l-1}'s place and against a_{l-2}
 #pragma unroll
             for (int l = kMaxLayers; l >= 2; --l) {
                 if (l > L || l <= lmin) continue;  // block-uniform
-                const float *dz = l == L ? dzl : lds + l * IMG;
                 const float *ain = l == 2 ? rows : lds + (l - 2) * IMG;
                 const int cprev = l == 2 ? 2 * F : a.w[l - 2];
-                hidden_bwd<LD, 1>(dz, lds + (l - 1) * IMG, a.w[l], a.w[l - 1], a.wt[l - 1], a.c[l - 2].bn,
-                                  [&](int sl, const f32x16(&d)[1]) {
-                                      take<LD, NT, NS>(H, hh[l - 2], d[0], sl, wave, nvalid, base[l - 2] - t0, ain, cprev, h, j);
-                                  });
-                __syncthreads();
+                back_layer<LD, 1>(a, lds, dzl, L, l, [&](int, int sl, const f32x16(&d)[1]) {
+                    take<LD, NT, NS>(H, hh[l - 2], d[0], sl, wave, nvalid, base[l - 2] - t0, ain, cprev, h, j);
+                });
                 if (l == L && L >= 3) {  // dz_L is consumed: the edge rows of this k again, for d_1
                     gather_rows<T>(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
                     __syncthreads();
                 }
             }
-            // d_0 from dz_1 (img[1] for every L), added to the sums over k
-            if (sums) {
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const int sl = wave + s * kWaves;
-                    if (sl * 32 >= 2 * F) continue;  // wave-uniform
-                    const int cc = min(sl * 32 + j, 2 * F - 1);
-                    f32x16 acc[1] = {f32x16{0}};
-                    mfma_slab_rt<LD, 1>(lds + IMG, a.wt[0] + (size_t)a.w[1] * cc, a.w[1], h, j, acc);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) S[s][r] = S[s][r] + acc[0][r];
-                }
-            }
+            if (sums) add_d0<LD, 1, NS>(a, lds, F, wave, h, j, S);
             // (img[1] and `rows` are written again after barriers that a wave reaches after these reads)
         }
         if (sums) {
-            // S to `rows` (last read before a barrier above), then gx[f] = S[f] - S[F + f]
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int c = (wave + s * kWaves) * 32 + j;
-                if (c >= 2 * F) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) rows[mfma_row(r, h) * LD + c] = S[s][r];
-            }
-            __syncthreads();
-            float *gb = a.gx + ((size_t)b * a.N + p0) * F;
-            const float rf = 1.0f / (float)F;
-            for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
-                const int p = edge_row_of(i, rf), c = i - p * F;
-                if (p < nvalid) gb[(size_t)p * F + c] = rows[p * LD + c] - rows[p * LD + F + c];
-            }
+            store_gx<LD, 1, NS>(a, rows, b, p0, nvalid, wave, h, j, S);
             __syncthreads();  // before the next tile's gather
         }
     }
@@ -353,9 +294,7 @@ struct Plan {
 constexpr int kTilesNarrow = 14, kTilesWide = 12;  // strides 66 and 130 (one slab per wave); stride 258 (two)
 Plan plan(const int32_t *layers, int nlayers) {
     Plan p{};
-    int widest = 2 * layers[0];
-    for (int i = 1; i < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
-    p.ld = widest <= 64 ? 66 : widest <= 128 ? kLd : 258;
+    p.ld = adjoint_stride(layers, nlayers);
     const int L = nlayers - 1, nimg = L == 1 ? 2 : L == 2 ? 3 : L;
     p.lds_bytes = (size_t)nimg * 32 * p.ld * sizeof(float);
     for (int i = 1; i < nlayers; ++i) {
@@ -384,18 +323,14 @@ Plan plan(const int32_t *layers, int nlayers) {
     return p;
 }
 
-// the workspace: the forward's own | the lists | out | the transposed weights | the chunk partials | the sums
-struct WsPlan { size_t fwd, fwd_bytes, idx, out, wt, part, sums, total; long long psize; int chunks; };
-fx3d_status ws_plan(const int32_t *layers, int nlayers, int N, int B, int K, WsPlan *w) {
+// the workspace: the adjoints' prefix (edgeconv_adjoint_plan, with the checks of the entry `fn`) | the chunk partials | the sums
+struct WsPlan { AdjointWs adj; size_t part, sums, total; long long psize; int chunks; };
+fx3d_status ws_plan(const char *fn, const int32_t *layers, int nlayers, int N, int B, int K, WsPlan *w) {
     WsBump ws;
-    const fx3d_status rc = edgeconv_workspace_bytes(layers[0], N, B, K, &w->fwd_bytes);
+    const fx3d_status rc = edgeconv_adjoint_plan(fn, layers, nlayers, N, B, K, ws, &w->adj);
     if (rc != FX3D_OK) return rc;
     w->psize = edgeconv_layout(nullptr, layers, nlayers, nullptr);
     w->chunks = (N + kGradChunk - 1) / kGradChunk;
-    w->fwd = ws.put(w->fwd_bytes);
-    w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
-    w->out = ws.put((size_t)layers[nlayers - 1] * N * B * sizeof(float));
-    w->wt = ws.put(edgeconv_transposed_floats(layers, nlayers) * sizeof(float));
     w->part = ws.put((size_t)w->psize * w->chunks * B * sizeof(float));
     w->sums = ws.put((size_t)w->psize * sizeof(float));
     w->total = ws.at;
@@ -420,11 +355,9 @@ extern "C" {
 fx3d_status fx3d_edgeconv_grad_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B, size_t *bytes) {
     const char *fn = "fx3d_edgeconv_grad_workspace_bytes";
     FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
-    fx3d_status rc = check_layers(fn, layers, nlayers);
-    if (rc != FX3D_OK) return rc;
-    if ((rc = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return rc;
     WsPlan w;
-    if ((rc = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return rc;
+    const fx3d_status rc = ws_plan(fn, layers, nlayers, N, B, K, &w);
+    if (rc != FX3D_OK) return rc;
     *bytes = w.total;
     return FX3D_OK;
 }
@@ -434,21 +367,16 @@ fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *layers, i
                                void *ws, size_t ws_bytes, fx3d_stream_t s) {
     const char *fn = "fx3d_edgeconv_grad";
     FX3D_REQUIRE(params_dev && x && gout && gparams && ws, "%s: params_dev, x, gout, gparams and ws must not be NULL", fn);
-    fx3d_status r = check_layers(fn, layers, nlayers);
-    if (r != FX3D_OK) return r;
-    if ((r = check_edgeconv_sizes(fn, N, B, K)) != FX3D_OK) return r;
     WsPlan w;
-    if ((r = ws_plan(layers, nlayers, N, B, K, &w)) != FX3D_OK) return r;
-    FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_edgeconv_grad_workspace_bytes says %zu", fn, ws_bytes, w.total);
-    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
-
-    char *wsb = static_cast<char *>(ws);
-    hipStream_t st = as_stream(s);
     PgradArgs a{};
     FinishArgs f{};
-    edgeconv_layout(params_dev, layers, nlayers, a.c);
+    fx3d_status r = ws_plan(fn, layers, nlayers, N, B, K, &w);
+    if (r != FX3D_OK) return r;
+    if ((r = edgeconv_adjoint_prepare(fn, "fx3d_edgeconv_grad_workspace_bytes", w.adj, w.total, params_dev, layers, nlayers, K, x, N, B,
+                                      idx, out, gout, gx, ws, ws_bytes, s, &a)) != FX3D_OK) return r;
+    char *wsb = static_cast<char *>(ws);
+    hipStream_t st = as_stream(s);
     const int L = nlayers - 1;
-    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
     for (int l = 0; l < L; ++l) {
         a.woff[l] = (int)(a.c[l].W - params_dev);
         a.boff[l] = (int)(a.c[l].b - params_dev);
@@ -457,21 +385,8 @@ fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *layers, i
         f.cin[l] = l == 0 ? 2 * layers[0] : layers[l];
         f.cout[l] = layers[l + 1];
     }
-    a.nl = L; a.cout = layers[L];
-    a.N = N; a.K = K; a.x = x; a.gout = gout; a.gx = gx;
     a.psize = (int)w.psize;
     a.part = reinterpret_cast<float *>(wsb + w.part);
-    // the forward's part: the lists and / or out where the caller has none (the search is deterministic: the forward's lists)
-    int32_t *ws_idx = reinterpret_cast<int32_t *>(wsb + w.idx);
-    float *ws_out = reinterpret_cast<float *>(wsb + w.out);
-    if (!out) {
-        if ((r = edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx, ws_out, idx ? nullptr : ws_idx, wsb + w.fwd, s, "edgeconv")) != FX3D_OK) return r;
-    } else if (!idx) {
-        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, ws_idx, nullptr, wsb + w.fwd, w.fwd_bytes, s)) != FX3D_OK) return r;
-    }
-    a.idx = idx ? idx : ws_idx;
-    a.out = out ? out : ws_out;
-    if ((r = edgeconv_transpose_weights(a.c, layers, nlayers, reinterpret_cast<float *>(wsb + w.wt), a.wt, st)) != FX3D_OK) return r;
     const Plan p = plan(layers, nlayers);
     a.lmin = p.lmin;
     switch (p.ld) {

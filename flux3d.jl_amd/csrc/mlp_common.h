@@ -1,7 +1,9 @@
-// What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip, edgeconv_bwd.hip, edgeconv_pgrad.hip) share: the exact-Float32 contraction on the f32 MFMA, the
+// What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip, and through edgeconv_adjoint.h edgeconv_bwd.hip and
+// edgeconv_pgrad.hip) share: the exact-Float32 contraction on the f32 MFMA, the
 // activation and BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, the EdgeConv kernel's gather of
 // the edge rows and fold of the last layer, the two ends of a classifier head, and on the host the walk over the flat
-// parameter buffer, the workspace allocator, the size limits of the neighbour search, the EdgeConv envelope and the EdgeConv entry DGCNN and the adjoint run on.
+// parameter buffer, the workspace allocator, the size limits of the neighbour search, the EdgeConv envelope, LDS budget and row stride, and the EdgeConv entry DGCNN and the adjoints run on.
+// What only the adjoints share is in edgeconv_adjoint.h.
 // include/flux3d_hip.h ("PointNet inference") states the arithmetic; pointnet.hip's header comment the tile and its LDS banks.
 #pragma once
 #include <cmath>
@@ -19,6 +21,11 @@ constexpr int kPtThreads = 256;    // 4 waves
 constexpr int kFeat = 1024;        // channels of the pooled feature
 constexpr int kHeadThreads = 1024; // a head block: one thread per pooled channel
 constexpr float kBnEps = 1e-5f;    // BatchNorm's default epsilon, 1f-5
+
+// The EdgeConv kernels' (edgeconv.hip and the adjoints) dynamic LDS, at most two 64-row images of the widest stride: 132 KB of the
+// CU's 160 KB.  Their images share one row stride, the smallest of 66 / kLd / 258 that holds the widest row they keep.
+constexpr size_t kMaxLds = (size_t)2 * kTile * 258 * sizeof(float);
+inline int edge_stride(int widest) { return widest <= 64 ? 66 : widest <= 128 ? kLd : 258; }
 
 struct __attribute__((packed, aligned(4))) W4 { float x, y, z, w; };  // four consecutive weights, 4-byte aligned
 
@@ -219,82 +226,6 @@ __device__ __forceinline__ void fold_store(float *ob, int cout, int nvalid, cons
     }
 }
 
-// ---- the adjoints' (edgeconv_bwd.hip, edgeconv_pgrad.hip) pieces of the chain: 32 NH points per image --------------------------
-constexpr int kWaves = kPtThreads / 64;
-
-// gather_centre and gather_diff in one pass, for a tile of T points: both halves are written with every k
-template <int T>
-__device__ __forceinline__ void gather_rows(float *rows, int ld, const float *xb, const int32_t *ib, int F, int N, int K, int k,
-                                            int p0, int nvalid) {
-    const float rf = 1.0f / (float)F;
-    for (int i = threadIdx.x; i < T * F; i += kPtThreads) {
-        const int p = edge_row_of(i, rf), c = i - p * F;
-        float xc = 0.0f, v = 0.0f;
-        if (p < nvalid) {
-            xc = xb[(size_t)(p0 + p) * F + c];
-            int jn = ib[(size_t)p * K + k];
-            jn = (unsigned int)jn < (unsigned int)N ? jn : p0 + p;
-            v = xb[(size_t)jn * F + c] - xc;
-        }
-        rows[p * ld + c] = xc;
-        rows[p * ld + F + c] = v;
-    }
-}
-
-// one hidden layer forward, image to image: conv_item of edgeconv.hip on the wave's slabs
-template <int LD, int NH>
-__device__ __forceinline__ void hidden_fwd(const float *in, float *out, int cin, int cout, const Conv &c) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    for (int sl = wave; sl * 32 < cout; sl += kWaves) {
-        const int o = sl * 32 + j, oc = min(o, cout - 1);
-        f32x16 acc[NH];
-#pragma unroll
-        for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-        mfma_slab_rt<LD, NH>(in, c.W + (size_t)cin * oc, cin, h, j, acc);
-        const float bi = c.b[oc], g = c.bn.g[oc], be = c.bn.b[oc], mu = c.bn.m[oc], sd = sqrtf(c.bn.v[oc] + kBnEps);
-        if (o < cout) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int t = 0; t < NH; ++t) out[(t * 32 + mfma_row(r, h)) * LD + o] = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd);
-        }
-    }
-}
-
-// one hidden layer backward: d[p][c] = the chain over o < cout of dz[p][o] Wt[o + cout c] for c < cin, then in a's place
-// dz'[p][c] = ((a[p][c] > 0 ? d : +0) gamma[c]) / sd[c] with the BatchNorm of the layer that made a
-// sink(sl, d): the wave's slab sl of d as it stands in the accumulators' rows (mfma_row), before gamma and sd; what the lanes
-// beyond cin hold there is not d.  The input adjoint has no use for it (NoSink); the parameter adjoint contracts it.
-template <int LD, int NH, class Sink>
-__device__ __forceinline__ void hidden_bwd(const float *dz, float *a, int cout, int cin, const float *__restrict__ wt, const Bn &bn,
-                                           Sink &&sink) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    for (int sl = wave; sl * 32 < cin; sl += kWaves) {
-        const int c = sl * 32 + j, cc = min(c, cin - 1);
-        f32x16 acc[NH];
-#pragma unroll
-        for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-        mfma_slab_rt<LD, NH>(dz, wt + (size_t)cout * cc, cout, h, j, acc);
-        const float g = bn.g[cc], sd = sqrtf(bn.v[cc] + kBnEps);
-        if (c < cin) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int t = 0; t < NH; ++t) {
-                    float *e = a + (t * 32 + mfma_row(r, h)) * LD + c;
-                    const float d = *e > 0.0f ? acc[t][r] : 0.0f;
-                    acc[t][r] = d;
-                    *e = (d * g) / sd;
-                }
-        }
-        sink(sl, acc);
-    }
-}
-struct NoSink {
-    template <int NH>
-    __device__ __forceinline__ void operator()(int, const f32x16 (&)[NH]) const {}
-};
-
 // x[0 .. n) in LDS, W (nout, n) column-major: acc = fmaf(x[i], W[o, i], acc) upwards from +0.0f
 __device__ __forceinline__ float dense_chain(const float *x, int n, const float *__restrict__ W, int nout, int o) {
     float acc = 0.0f;
@@ -407,12 +338,6 @@ fx3d_status edgeconv_workspace_bytes(int F, int N, int B, int K, size_t *bytes);
 fx3d_status edgeconv_run(const float *params_dev, const int32_t *layers, int nlayers, int K, const float *x, int N, int B,
                          const int32_t *idx_in, float *out, int32_t *idx_out, void *ws, fx3d_stream_t s, const char *label);
 
-
-// ---- edgeconv_bwd.hip: the weights as the adjoints read them, Wt_l[o + cout c] = W_l[c + cin o] -------------------------------
-// c: edgeconv_layout's layers.  One launch on st writes every layer's Wt into wt (edgeconv_transposed_floats floats), wt_of[l] is
-// where layer l + 1's begins.
-size_t edgeconv_transposed_floats(const int32_t *layers, int nlayers);
-fx3d_status edgeconv_transpose_weights(const Conv *c, const int32_t *layers, int nlayers, float *wt, const float **wt_of, hipStream_t st);
 
 }  // namespace mlp
 }  // namespace fx3d

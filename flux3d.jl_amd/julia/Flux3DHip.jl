@@ -1650,15 +1650,23 @@ function edgeconv_params(m::EdgeConv)
     end
     return out
 end
-function edgeconv_forward(m::EdgeConv, X::HipArray{Float32,3}; idx::Union{Nothing,HipArray{Int32,3}} = nothing, return_idx::Bool = false)
+# The checks and set-up every EdgeConv call begins with: m.layers as the library takes them, the sizes of X, K against N and the
+# shape of the lists.  The adjoints give gout (and out): both (cL, N, B).
+function _edgeconv_setup(m::EdgeConv, X::HipArray{Float32,3}, idx; gout = nothing, out = nothing)
     layers = Int32.(collect(m.layers))
-    nl = length(layers)
     F, N, B = size(X)
     K = m.K
+    cL = Int(layers[end])
     F == layers[1] || error("EdgeConv($(m.layers), $K) takes $(layers[1]) channels per point, got $F")
-    (N >= 1 && B >= 1) || error("EdgeConv needs at least one point and one cloud")
+    gout !== nothing || (N >= 1 && B >= 1) || error("EdgeConv needs at least one point and one cloud")  # (the forward's)
     (1 <= K && K + 1 <= N) || error("EdgeConv needs 1 <= K <= N - 1, got K = $K, N = $N")
+    gout === nothing || size(gout) == (cL, N, B) || error("gout must be ($cL, $N, $B), got $(size(gout))")
+    out === nothing || size(out) == (cL, N, B) || error("out must be ($cL, $N, $B), got $(size(out))")
     idx === nothing || size(idx) == (K, N, B) || error("idx must be ($K, $N, $B), got $(size(idx))")
+    return layers, length(layers), F, N, B, K
+end
+function edgeconv_forward(m::EdgeConv, X::HipArray{Float32,3}; idx::Union{Nothing,HipArray{Int32,3}} = nothing, return_idx::Bool = false)
+    layers, nl, F, N, B, K = _edgeconv_setup(m, X, idx)
     params = edgeconv_params(m)
     cnt = Ref{Int64}(0)
     check(@ccall LIB.fx3d_edgeconv_param_count(layers::Ptr{Int32}, Int32(nl)::Int32, cnt::Ref{Int64})::Int32)
@@ -1686,16 +1694,7 @@ end
 # who trains through it would get silently zero weight gradients.  edgeconv_gradient below has the parameter gradients.
 function edgeconv_input_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{Float32,3};
                                  idx::Union{Nothing,HipArray{Int32,3}} = nothing, out::Union{Nothing,HipArray{Float32,3}} = nothing)
-    layers = Int32.(collect(m.layers))
-    nl = length(layers)
-    F, N, B = size(X)
-    K = m.K
-    cL = Int(layers[end])
-    F == layers[1] || error("EdgeConv($(m.layers), $K) takes $(layers[1]) channels per point, got $F")
-    (1 <= K && K + 1 <= N) || error("EdgeConv needs 1 <= K <= N - 1, got K = $K, N = $N")
-    size(gout) == (cL, N, B) || error("gout must be ($cL, $N, $B), got $(size(gout))")
-    out === nothing || size(out) == (cL, N, B) || error("out must be ($cL, $N, $B), got $(size(out))")
-    idx === nothing || size(idx) == (K, N, B) || error("idx must be ($K, $N, $B), got $(size(idx))")
+    layers, nl, F, N, B, K = _edgeconv_setup(m, X, idx; gout = gout, out = out)
     nb = Ref{Csize_t}(0)
     check(@ccall LIB.fx3d_edgeconv_bwd_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
                                                        Int32(B)::Int32, nb::Ref{Csize_t})::Int32)
@@ -1719,16 +1718,7 @@ end
 function edgeconv_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{Float32,3};
                            idx::Union{Nothing,HipArray{Int32,3}} = nothing, out::Union{Nothing,HipArray{Float32,3}} = nothing,
                            input_grad::Bool = true)
-    layers = Int32.(collect(m.layers))
-    nl = length(layers)
-    F, N, B = size(X)
-    K = m.K
-    cL = Int(layers[end])
-    F == layers[1] || error("EdgeConv($(m.layers), $K) takes $(layers[1]) channels per point, got $F")
-    (1 <= K && K + 1 <= N) || error("EdgeConv needs 1 <= K <= N - 1, got K = $K, N = $N")
-    size(gout) == (cL, N, B) || error("gout must be ($cL, $N, $B), got $(size(gout))")
-    out === nothing || size(out) == (cL, N, B) || error("out must be ($cL, $N, $B), got $(size(out))")
-    idx === nothing || size(idx) == (K, N, B) || error("idx must be ($K, $N, $B), got $(size(idx))")
+    layers, nl, F, N, B, K = _edgeconv_setup(m, X, idx; gout = gout, out = out)
     nb = Ref{Csize_t}(0)
     check(@ccall LIB.fx3d_edgeconv_grad_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
                                                         Int32(B)::Int32, nb::Ref{Csize_t})::Int32)

@@ -322,18 +322,24 @@ class EdgeConv(_Model):
             raise ValueError(f"idx must hold 0-based indices in [0, {N}), got values from {a.min()} to {a.max()}")
         return DeviceArray.from_host(np.asfortranarray(a.reshape(K, N, B, order="F").astype(np.int32)))
 
-    def forward(self, X, idx=None, return_idx=False):
-        """``(cL, N, B)`` for the clouds ``X``: a device array or a numpy array, ``(F, N, B)`` or ``(F, N)`` (one cloud); a
-        PointCloud when F = 3.  The result lives where the input lives.  ``idx``: neighbour lists ``(K, N, B)``, 0-based,
-        to use instead of the search (numpy integers, checked against [0, N) here, or an int32 device array).
-        ``return_idx=True``: ``(out, idx)`` with the lists that were used, int32."""
+    def _head(self, X):
+        """The checks every call begins with, in their order: a PointCloud only for F = 3, the clouds (:meth:`_clouds`), K against
+        N.  ``(pts, N, B, on_dev, layers, nl)`` with the widths as the C array the library takes."""
         F, K = self.layers[0], self.K
         if isinstance(X, PointCloud) and F != 3:
             raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
         pts, N, B, on_dev = self._clouds(X, f"EdgeConv({self.layers}, {K})", F)
         if K + 1 > N:
             raise ValueError(f"EdgeConv needs 1 <= K <= N - 1 (K neighbours besides the point itself), got K={K}, N={N}")
-        layers, nl = self._layers_c()
+        return (pts, N, B, on_dev) + self._layers_c()
+
+    def forward(self, X, idx=None, return_idx=False):
+        """``(cL, N, B)`` for the clouds ``X``: a device array or a numpy array, ``(F, N, B)`` or ``(F, N)`` (one cloud); a
+        PointCloud when F = 3.  The result lives where the input lives.  ``idx``: neighbour lists ``(K, N, B)``, 0-based,
+        to use instead of the search (numpy integers, checked against [0, N) here, or an int32 device array).
+        ``return_idx=True``: ``(out, idx)`` with the lists that were used, int32."""
+        F, K = self.layers[0], self.K
+        pts, N, B, on_dev, layers, nl = self._head(X)
         nb = _lib.query_bytes("fx3d_edgeconv_workspace_bytes", layers, nl, K, N, B)  # (the library's own size limits)
         given = None if idx is None else self._neighbours(idx, N, B)
         x = self._on_device(pts, N, B, on_dev, F)
@@ -369,6 +375,26 @@ class EdgeConv(_Model):
             raise ValueError(f"{name} must be ({cL}, {N}, {B}), got {a.shape}")
         return np.asfortranarray(a.reshape(cL, N, B, order="F").astype(np.float32))
 
+    def _adjoint_call(self, entry, X, gout, idx, out, results):
+        """``fx3d_{entry}`` on the checked ``(X, gout, idx, out)`` of :meth:`input_grad`, everything on the device, with the
+        workspace of ``fx3d_{entry}_workspace_bytes``.  ``results(N, B)``: the entry's result arrays in its argument order (one
+        may be None).  They come back on the device, with whether ``X`` lives there."""
+        F, K = self.layers[0], self.K
+        pts, N, B, on_dev, layers, nl = self._head(X)
+        nb = _lib.query_bytes(f"fx3d_{entry}_workspace_bytes", layers, nl, K, N, B)
+        g = self._like_out(gout, "gout", N, B, on_dev)
+        o = None if out is None else self._like_out(out, "out", N, B, on_dev)
+        given = None if idx is None else self._neighbours(idx, N, B)
+        if not on_dev:
+            g, o = DeviceArray.from_host(g), (None if o is None else DeviceArray.from_host(o))
+        x = self._on_device(pts, N, B, on_dev, F)
+        res = results(N, B)
+        ws = workspace(nb, tag=entry)
+        _lib.call(f"fx3d_{entry}", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
+                  o.ptr if o is not None else None, g.ptr, *(r.ptr if r is not None else None for r in res), ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        return res, on_dev
+
     def input_grad(self, X, gout, idx=None, out=None):
         """The gradient ``(F, N, B)`` of ``sum(gout * forward(X))`` with respect to ``X``, with the neighbours held constant
         as the reference holds them (CreateSingleKNNGraph is @nograd) and BatchNorm in test mode: include/flux3d_hip.h
@@ -376,49 +402,17 @@ class EdgeConv(_Model):
         the result.  ``idx``: the forward's neighbour lists (``return_idx=True``), ``out``: the forward's result; either may
         be left out, and is then computed again (the search is deterministic).  An ``out`` that is not this forward's passes
         gradient only where some k reproduces it.  The weights are constants here; :meth:`grad` gives their gradients too."""
-        F, K = self.layers[0], self.K
-        if isinstance(X, PointCloud) and F != 3:
-            raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
-        pts, N, B, on_dev = self._clouds(X, f"EdgeConv({self.layers}, {K})", F)
-        if K + 1 > N:
-            raise ValueError(f"EdgeConv needs 1 <= K <= N - 1 (K neighbours besides the point itself), got K={K}, N={N}")
-        layers, nl = self._layers_c()
-        nb = _lib.query_bytes("fx3d_edgeconv_bwd_workspace_bytes", layers, nl, K, N, B)
-        g = self._like_out(gout, "gout", N, B, on_dev)
-        o = None if out is None else self._like_out(out, "out", N, B, on_dev)
-        given = None if idx is None else self._neighbours(idx, N, B)
-        if not on_dev:
-            g, o = DeviceArray.from_host(g), (None if o is None else DeviceArray.from_host(o))
-        x = self._on_device(pts, N, B, on_dev, F)
-        gx = DeviceArray.empty((F, N, B), np.float32)
-        ws = workspace(nb, tag="edgeconv_bwd")
-        _lib.call("fx3d_edgeconv_bwd", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
-                  o.ptr if o is not None else None, g.ptr, gx.ptr, ws.ptr, ws.nbytes, current_stream().handle)
+        (gx,), on_dev = self._adjoint_call("edgeconv_bwd", X, gout, idx, out,
+                                           lambda N, B: (DeviceArray.empty((self.layers[0], N, B), np.float32),))
         return gx if on_dev else gx.to_host()
 
     def _grad_call(self, X, gout, idx, out, input_grad):
         """fx3d_edgeconv_grad after :meth:`input_grad`'s checks: (the flat gradient, gx or None) on the device, and whether
         ``X`` lives there."""
-        F, K = self.layers[0], self.K
-        if isinstance(X, PointCloud) and F != 3:
-            raise ValueError(f"a PointCloud has 3 channels per point, EdgeConv({self.layers}, {K}) takes {F}")
-        pts, N, B, on_dev = self._clouds(X, f"EdgeConv({self.layers}, {K})", F)
-        if K + 1 > N:
-            raise ValueError(f"EdgeConv needs 1 <= K <= N - 1 (K neighbours besides the point itself), got K={K}, N={N}")
-        layers, nl = self._layers_c()
-        nb = _lib.query_bytes("fx3d_edgeconv_grad_workspace_bytes", layers, nl, K, N, B)
-        g = self._like_out(gout, "gout", N, B, on_dev)
-        o = None if out is None else self._like_out(out, "out", N, B, on_dev)
-        given = None if idx is None else self._neighbours(idx, N, B)
-        if not on_dev:
-            g, o = DeviceArray.from_host(g), (None if o is None else DeviceArray.from_host(o))
-        x = self._on_device(pts, N, B, on_dev, F)
-        gp = DeviceArray.empty((self.param_count,), np.float32)
-        gx = DeviceArray.empty((F, N, B), np.float32) if input_grad else None
-        ws = workspace(nb, tag="edgeconv_grad")
-        _lib.call("fx3d_edgeconv_grad", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
-                  o.ptr if o is not None else None, g.ptr, gp.ptr, gx.ptr if gx is not None else None, ws.ptr, ws.nbytes,
-                  current_stream().handle)
+        (gp, gx), on_dev = self._adjoint_call(
+            "edgeconv_grad", X, gout, idx, out,
+            lambda N, B: (DeviceArray.empty((self.param_count,), np.float32),
+                          DeviceArray.empty((self.layers[0], N, B), np.float32) if input_grad else None))
         return gp, gx, on_dev
 
     def flat_grad(self, X, gout, idx=None, out=None, input_grad=True):

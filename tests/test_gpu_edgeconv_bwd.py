@@ -62,6 +62,7 @@ CASES = [([3, 16], 7, 1, 6),
          ([64, 64, 128, 256], 70, 1, 5),             # 32-point tiles
          ([65, 8, 8, 8], 66, 1, 3),
          ([65, 8, 8, 8, 8], 66, 2, 3),
+         ([40, 8, 8, 8, 72], 34, 2, 3),              # stride 130 at L = 4: 32-point tiles, a second tile of two points, tails of 8
          ([128, 256, 256, 256, 256], 33, 1, 2),      # the LDS corner: four images of stride 258 at 32 points
          ([3, 32, 64, 64], 64, 2, 10),               # DGCNN's two stages
          ([64, 128, 256], 64, 2, 10)]

@@ -72,6 +72,7 @@ CASES = [([3, 16], 7, 1, 6),
          ([64, 128, 256], 64, 2, 10),                # DGCNN's second stage
          ([3, 32, 64, 64], 64, 2, 10),               # DGCNN's first stage
          ([64, 64, 128, 256], 70, 1, 5),
+         ([40, 8, 8, 8, 72], 34, 2, 3),              # stride 130 at L = 4, a second tile of two points, tails of 8 channels
          ([128, 256, 256, 256, 256], 33, 1, 2),      # the LDS corner, several passes over the tile list
          ([5, 33, 70], 130, 2, 3),                   # two chunks: a full one and a tail of two points
          ([3, 16, 16], 257, 1, 2)]                   # three chunks, L = 2's extra image

@@ -381,6 +381,34 @@ def test_conversion_workspace_sizes_are_the_recorded_ones(fx):
     assert 150 <= nrows <= 400
 
 
+def test_edgeconv_adjoint_workspace_sizes_are_the_recorded_ones(fx):
+    """The size functions of the EdgeConv forward and of its two adjoints, like the conversions' above:
+    tests/golden/edgeconv_adjoint_workspace_sizes.json was recorded from the build BEFORE the adjoints' workspace prefix
+    (the forward's | idx | out | Wt) and their checks got one owner (rows: layers, nlayers, K, N, B, status, value; a refused query
+    leaves 0).  It holds the shapes the layouts turn on: L = 1 .. 4; F of 1, 64, 65, 128 and 0 and 129 (refused); widths either
+    side of 64, 128 and 256 (257 refused); 1 and 6 entries (refused); N of 1 and 2 with K + 1 > N (refused), 127, 128 and 129 (the
+    parameter adjoint's chunks of 128), 36 864 and 36 865 (refused); B of 1, 65 535 and 65 536 (refused); N B K either side of
+    2^31; K = 0 and B = 0 (refused)."""
+    import ctypes as C
+    import json
+    from flux3d_jl_amd import _lib
+    lib = _lib.load()
+    with open(os.path.join(GOLDEN, "edgeconv_adjoint_workspace_sizes.json")) as f:
+        table = json.load(f)
+    assert set(table) == {"fx3d_edgeconv_workspace_bytes", "fx3d_edgeconv_bwd_workspace_bytes", "fx3d_edgeconv_grad_workspace_bytes"}
+    nrows = 0
+    for name, rows in table.items():
+        assert any(status != 0 for *_, status, _ in rows) and any(status == 0 for *_, status, _ in rows), name
+        for layers, *args, status, value in rows:
+            out = C.c_size_t(0)
+            got = getattr(lib, name)((C.c_int32 * len(layers))(*layers), *args, C.byref(out))
+            assert (got, out.value) == (status, value), (name, layers, args)
+            if status == 0:
+                assert _lib.query_bytes(name, (C.c_int32 * len(layers))(*layers), *args) == value
+            nrows += 1
+    assert 90 <= nrows <= 150
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """VERDICT r3 #1b: `python bench.py --gpus N` with no launcher must run N ranks or FAIL -- never print a line whose n_gpus
     differs from --gpus.  On a box with fewer than N devices (this container has none) the launcher exits non-zero before any
