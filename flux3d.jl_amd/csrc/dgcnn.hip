@@ -1,4 +1,5 @@
-// DGCNN inference (gfx950): (m::DGCNN)(X) of src/models/dgcnn.jl:113-147 in test mode, Float32, forward only.
+// DGCNN inference (gfx950): (m::DGCNN)(X) of src/models/dgcnn.jl:113-147 in test mode, Float32: the forward (its adjoint:
+// dgcnn_grad.hip; dgcnn_net.h holds what the two share).
 // include/flux3d_hip.h ("DGCNN inference") states the network, the arithmetic and the parameter layout; this file is how they are
 // computed.  The arithmetic is PointNet's (mlp_common.h): one accumulator per output element, walking the input channels
 // upwards on v_mfma_f32_32x32x2_f32 (or v_fma_f32 for the dense head); no contraction split over waves or blocks, no float
@@ -12,25 +13,20 @@
 //     pattern of kLd), conv 256 -> 1024 + BN + relu reduced to the tile's maximum per channel (conv_mfma<.., FINAL>).
 //   dgcnn_head_kernel: one block per cloud folds the tile maxima (= MaxPool((npoints,))), then fc_4, fc_5 (dense, BN, relu),
 //     fc_6 (dense, no activation) with one thread per output element, and the softmax.
-#include "mlp_common.h"
+#include "dgcnn_net.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
 
 namespace {
 
-constexpr int kLd3 = 258;         // LDS row stride of conv_3's 256-channel input image
-constexpr size_t kConv3Lds = (size_t)kTile * kLd3 * sizeof(float);
-constexpr int32_t kEc1[] = {3, 32, 64, 64}, kEc2[] = {64, 128, 256};  // the layers of the two EdgeConv stages
-
 __global__ __launch_bounds__(kPtThreads) void dgcnn_conv3_kernel(const float *__restrict__ x2, const Conv c, float *__restrict__ tmax_all,
                                                                  int N, int ntiles) {
     extern __shared__ float lds[];
-    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int tile = blockIdx.x, b = blockIdx.y;
     const int p0 = tile * kTile;
     const int nvalid = min(kTile, N - p0);
-    const float *xb = x2 + ((size_t)b * N + p0) * 256;
-    for (int i = tid; i < kTile * 256; i += kPtThreads) lds[(i >> 8) * kLd3 + (i & 255)] = i < nvalid * 256 ? xb[i] : 0.0f;
+    load_x2_tile(lds, x2, b, N, p0, nvalid);
     __syncthreads();
     conv_mfma<256, kBnRelu, true, kLd3>(lds, nullptr, kFeat, c.W, c.b, c.bn, nvalid, tmax_all + ((size_t)b * ntiles + tile) * kFeat);
 }
@@ -67,33 +63,6 @@ __global__ __launch_bounds__(kHeadThreads) void dgcnn_head_kernel(const HeadArgs
     softmax_of_logits(z, pr, a.nc);
 }
 
-// ---- the flat parameter buffer in forward order (flux3d_hip.h) ----------------------------------------------------------
-struct Net {
-    const float *ec1, *ec2;  // the parameters of the two EdgeConv stages, in the EdgeConv layout
-    Conv c3;
-    Dense d4, d5, d6;
-    Bn bn4, bn5;
-    long long count;
-};
-
-Net layout(const float *params, int num_classes) {
-    Cursor c{params, 0};
-    Net n;
-    n.ec1 = c.take(edgeconv_layout(nullptr, kEc1, 4, nullptr));
-    n.ec2 = c.take(edgeconv_layout(nullptr, kEc2, 3, nullptr));
-    n.c3 = c.conv(256, kFeat);  n.c3.bn = c.bn(kFeat);
-    n.d4 = c.dense(kFeat, 512); n.bn4 = c.bn(512);
-    n.d5 = c.dense(512, 256);   n.bn5 = c.bn(256);
-    n.d6 = c.dense(256, num_classes);
-    n.count = c.at;
-    return n;
-}
-
-fx3d_status check_sizes(const char *fn, int32_t N, int32_t B, int32_t K, int32_t nc) {
-    FX3D_REQUIRE(nc >= 1 && nc <= (1 << 20), "%s: num_classes must be in [1, 2^20], got %d", fn, nc);
-    return check_edgeconv_sizes(fn, N, B, K);
-}
-
 // the workspace: x1 (64, N, B) | x2 (256, N, B) | per-tile maxima (1024, ntiles, B) | logits (num_classes, B) | one EdgeConv
 // workspace, the larger of the two stages'
 struct WsPlan { size_t x1, x2, tmax, logits, ec, total; int ntiles; };
@@ -120,13 +89,13 @@ extern "C" {
 fx3d_status fx3d_dgcnn_param_count(int32_t num_classes, int64_t *count) {
     FX3D_REQUIRE(count != nullptr, "fx3d_dgcnn_param_count: count is NULL");
     FX3D_REQUIRE(num_classes >= 1 && num_classes <= (1 << 20), "fx3d_dgcnn_param_count: num_classes must be in [1, 2^20], got %d", num_classes);
-    *count = layout(nullptr, num_classes).count;
+    *count = dgcnn_layout(nullptr, num_classes).count;
     return FX3D_OK;
 }
 
 fx3d_status fx3d_dgcnn_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes) {
     FX3D_REQUIRE(bytes != nullptr, "fx3d_dgcnn_workspace_bytes: bytes is NULL");
-    fx3d_status rc = check_sizes("fx3d_dgcnn_workspace_bytes", N, B, K, num_classes);
+    fx3d_status rc = dgcnn_check_sizes("fx3d_dgcnn_workspace_bytes", N, B, K, num_classes);
     if (rc != FX3D_OK) return rc;
     WsPlan w;
     if ((rc = ws_plan(N, B, K, num_classes, &w)) != FX3D_OK) return rc;
@@ -139,14 +108,14 @@ fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_classes, int
                                void *ws, size_t ws_bytes, fx3d_stream_t s) {
     const char *fn = "fx3d_dgcnn_forward";
     FX3D_REQUIRE(params_dev && x && probs && ws, "%s: params_dev, x, probs and ws must not be NULL", fn);
-    fx3d_status r = check_sizes(fn, N, B, K, num_classes);
+    fx3d_status r = dgcnn_check_sizes(fn, N, B, K, num_classes);
     if (r != FX3D_OK) return r;
     WsPlan w;
     if ((r = ws_plan(N, B, K, num_classes, &w)) != FX3D_OK) return r;
     FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_dgcnn_workspace_bytes says %zu", fn, ws_bytes, w.total);
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
     FX3D_REQUIRE(!x1 || (reinterpret_cast<uintptr_t>(x1) & 15) == 0, "%s: x1 must be 16-byte aligned", fn);
-    const Net n = layout(params_dev, num_classes);
+    const Net n = dgcnn_layout(params_dev, num_classes);
     hipStream_t st = as_stream(s);
     char *wsb = static_cast<char *>(ws);
     float *f1 = x1 ? x1 : reinterpret_cast<float *>(wsb + w.x1), *f2 = x2 ? x2 : reinterpret_cast<float *>(wsb + w.x2);

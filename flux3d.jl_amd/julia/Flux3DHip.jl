@@ -1638,6 +1638,40 @@ function dgcnn_forward(m::DGCNN, X::HipArray{Float32,3}; intermediates::Bool = f
 end
 (m::DGCNN)(X::HipArray{Float32,3}) = dgcnn_forward(m, X)
 
+# The gradients of sum(glogits .* logits) with respect to every parameter of m and to X (include/flux3d_hip.h "DGCNN adjoint"):
+# test mode as dgcnn_forward (running statistics, Dropout the identity), the neighbours constants.  glogits (num_classes, B) is
+# the gradient with respect to the LOGITS: the softmax stays with the caller.  fwd: dgcnn_forward(m, X; intermediates = true),
+# whose idx1, x1, idx2, x2 and pooled are used; without it the library runs the forward again.  Returns (gflat, gx): gflat in the
+# layout of dgcnn_params(m) with zeros in the mu / sigma2 slots, gx (3, N, B) or nothing with input_grad = false.
+function dgcnn_gradient(m::DGCNN, X::HipArray{Float32,3}, glogits::HipArray{Float32,2}; fwd = nothing, input_grad::Bool = true)
+    size(X, 1) == 3 || error("DGCNN takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    K = m.EdgeConv1.K
+    m.EdgeConv2.K == K || error("DGCNN: both EdgeConvs must use the same K")
+    npoints = m.maxpool_3.k[1]
+    N == npoints || error("DGCNN(num_classes, K, npoints = $npoints) takes clouds of npoints points, got $N: MaxPool((npoints,)) is the maximum over a whole cloud only then")
+    (1 <= K && K + 1 <= N) || error("DGCNN needs 1 <= K <= N - 1, got K = $K, N = $N")
+    nc = size(_dense_wb(m.fc_6)[1], 1)
+    size(glogits) == (nc, B) || error("glogits must be ($nc, $B), got $(size(glogits))")
+    params = dgcnn_params(m)
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_dgcnn_grad_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(K)::Int32, Int32(nc)::Int32,
+                                                     nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    gflat = HipArray{Float32}(undef, length(params))
+    gx = input_grad ? HipArray{Float32}(undef, 3, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    part(k) = fwd === nothing ? C_NULL : getproperty(fwd, k).ptr
+    check(@ccall LIB.fx3d_dgcnn_grad(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, Int32(K)::Int32, X.ptr::Ptr{Cvoid}, Int32(N)::Int32,
+                                     Int32(B)::Int32, part(:idx1)::Ptr{Cvoid}, part(:x1)::Ptr{Cvoid}, part(:idx2)::Ptr{Cvoid},
+                                     part(:x2)::Ptr{Cvoid}, part(:pooled)::Ptr{Cvoid}, glogits.ptr::Ptr{Cvoid},
+                                     gflat.ptr::Ptr{Cvoid}, opt(gx)::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Cvoid},
+                                     ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    return gflat, gx
+end
+
+
 # ---- EdgeConv inference: (m::EdgeConv)(X) (src/models/dgcnn.jl:11-71) in test mode, any layer widths -----------------------
 # EdgeConv(layers, K) as a layer in its own right (include/flux3d_hip.h "EdgeConv inference"): m.layers = [F, c1, ..., cL] goes
 # to the library as it is, the conv_bn_blocks of m.mlp are flattened as for DGCNN.  The search, the edge rows and the maximum

@@ -4,7 +4,9 @@
 include/flux3d_hip.h states the networks and their arithmetic ("PointNet inference", "DGCNN inference", "EdgeConv inference");
 this module owns the parameters (a name -> numpy array mapping in Flux's shapes), flattens them into the one device buffer
 fx3d_pointnet_forward / fx3d_dgcnn_forward / fx3d_edgeconv_forward reads, and checks every argument on the host before any
-launch.  The classifiers are forward only; EdgeConv also has its input gradient and its parameter gradients (test-mode BatchNorm)."""
+launch.  PointNet is forward only.  EdgeConv has its input gradient and its parameter gradients, and DGCNN the gradients of the
+whole network with respect to every parameter and to the input points (``DGCNN.grad`` over fx3d_dgcnn_grad, "DGCNN adjoint"),
+all with BatchNorm in test mode."""
 import ctypes as C
 
 import numpy as np
@@ -225,11 +227,12 @@ class DGCNN(_Model):
     multiple of npoints leaves several windows per cloud, which the reshape folds into the batch, anything else drops
     points.  ``forward`` therefore raises ``ValueError`` for clouds of any other size.
 
-    Forward only.  The two EdgeConv stages have their gradients: :meth:`EdgeConv.grad` gives a stage's parameter gradients
-    (test-mode BatchNorm) together with its input gradient, and the gradient with respect to the input is a composition of
-    :meth:`EdgeConv.input_grad`: with ``ec1 = EdgeConv([3, 32, 64, 64], K)`` and ``ec2 = EdgeConv([64, 128, 256], K)`` loaded
-    with the ``ec1.`` / ``ec2.`` arrays, and ``idx1, x1, idx2, x2`` of ``forward(X, intermediates=True)``,
-    ``ec1.input_grad(X, ec2.input_grad(x1, g, idx2, x2), idx1, x1)`` is the gradient of ``sum(g * x2)`` with respect to ``X``."""
+    The network has its gradients, in test mode (BatchNorm's running statistics are constants, Dropout is the identity, the
+    neighbour lists are constants): :meth:`grad` gives the gradient of ``sum(glogits * logits)`` with respect to every parameter
+    and to the input points from one library call (include/flux3d_hip.h "DGCNN adjoint"), :meth:`flat_grad` the same as one
+    flat buffer, :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  The two
+    EdgeConv stages inside are :meth:`EdgeConv.grad`'s kernel on the ``ec2.`` and ``ec1.`` parameters, bit for bit.  Training-mode
+    BatchNorm (batch statistics) and Dropout in training mode are not differentiated."""
 
     _NAME, _COUNT_FN = "DGCNN", "fx3d_dgcnn_param_count"
 
@@ -259,6 +262,125 @@ class DGCNN(_Model):
         return self._classify(clouds, "dgcnn", (nc, K), (N, B, K, nc), optional, intermediates)
 
     __call__ = forward
+
+    _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
+
+    @staticmethod
+    def _like(a, name, shape, dtype, on_dev):
+        """An argument of :meth:`grad` after its checks, with exactly ``shape`` (a trailing batch axis of 1 may be left out): a
+        device array, or a host array of ``dtype`` still to be uploaded.  It must live where ``X`` lives."""
+        ok = (shape,) + ((shape[:-1],) if shape[-1] == 1 else ())
+        what = "Float32" if dtype == np.float32 else "int32"
+        if is_device(a) != on_dev:
+            raise TypeError(f"{name} must live where X lives ({'the device' if on_dev else 'the host'})")
+        if on_dev:
+            if a.dtype != dtype:
+                raise TypeError(f"device {name} must be {what}, got {a.dtype}")
+            if tuple(a.shape) not in ok:
+                raise ValueError(f"{name} must be {shape}, got {tuple(a.shape)}")
+            return a.reshape(*shape)
+        a = np.asarray(a)
+        if dtype == np.int32:
+            if not np.issubdtype(a.dtype, np.integer):
+                raise TypeError(f"{name} must hold integers, got {a.dtype}")
+        elif not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise TypeError(f"{name} must hold real numbers, got {a.dtype}")
+        if a.shape not in ok:
+            raise ValueError(f"{name} must be {shape}, got {a.shape}")
+        return np.asfortranarray(a.reshape(shape, order="F").astype(dtype))
+
+    def _grad_call(self, X, glogits, fwd, input_grad, intermediates):
+        """fx3d_dgcnn_grad after the argument checks: (the flat gradient, gx or None, gx2 and gx1 or None) on the device, and
+        whether ``X`` lives there."""
+        pts, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
+        if N != self.npoints:
+            raise ValueError(f"DGCNN(num_classes, K, npoints={self.npoints}) takes clouds of npoints points, got N={N}: "
+                             "MaxPool((npoints,)) is the maximum over a whole cloud only then")
+        nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
+        nb = _lib.query_bytes("fx3d_dgcnn_grad_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
+        g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
+        given = [None] * len(self._FWD_KEYS)
+        if fwd is not None:
+            missing = [k for k in self._FWD_KEYS if k not in fwd]
+            if missing:
+                raise ValueError(f"fwd must be the dict of forward(X, intermediates=True): it has no {missing}")
+            shapes = {"idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32), "x2": ((256, N, B), f32),
+                      "pooled": ((1024, B), f32)}
+            given = [self._like(fwd[k], f"fwd['{k}']", *shapes[k], on_dev) for k in self._FWD_KEYS]
+            for k, a in zip(self._FWD_KEYS, given):
+                if not on_dev and a.dtype == i32 and a.size and (a.min() < 0 or a.max() >= N):
+                    raise ValueError(f"fwd['{k}'] must hold 0-based indices in [0, {N}), got values from {a.min()} to {a.max()}")
+        if not on_dev:
+            g = DeviceArray.from_host(g)
+            given = [None if a is None else DeviceArray.from_host(a) for a in given]
+        x = self._on_device(pts, N, B, on_dev)
+        gp = DeviceArray.empty((self.param_count,), f32)
+        gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
+        mid = {"gx2": DeviceArray.empty((256, N, B), f32), "gx1": DeviceArray.empty((64, N, B), f32)} if intermediates else None
+        ws = workspace(nb, tag="dgcnn_grad")
+        _lib.call("fx3d_dgcnn_grad", self._params_dev().ptr, nc, K, x.ptr, N, B, *(None if a is None else a.ptr for a in given),
+                  g.ptr, gp.ptr, gx.ptr if gx is not None else None, mid["gx2"].ptr if mid else None,
+                  mid["gx1"].ptr if mid else None, ws.ptr, ws.nbytes, current_stream().handle)
+        return gp, gx, mid, on_dev
+
+    def flat_grad(self, X, glogits, fwd=None, input_grad=True, intermediates=False):
+        """``(gflat, gx)``: the gradient of ``sum(glogits * logits)`` with respect to the parameters as ONE flat Float32 buffer
+        with the layout of :meth:`flat_params` (the ``mu`` / ``sigma2`` slots are zero), and the gradient with respect to ``X``
+        (``None`` with ``input_grad=False``).  Arguments, ``intermediates`` and placement as :meth:`grad`."""
+        gp, gx, mid, on_dev = self._grad_call(X, glogits, fwd, input_grad, intermediates)
+        if not on_dev:
+            gp, gx = gp.to_host(), (None if gx is None else gx.to_host())
+            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
+        return (gp, gx, mid) if intermediates else (gp, gx)
+
+    def grad(self, X, glogits, fwd=None, input_grad=True, intermediates=False):
+        """``(grads, gx)``: the gradients of ``sum(glogits * logits)`` with respect to every parameter of the network and to
+        the points ``X``, test mode: include/flux3d_hip.h "DGCNN adjoint".  ``X`` as in :meth:`forward`; ``glogits``
+        ``(num_classes, B)`` is the gradient with respect to the logits (the softmax stays with the caller, see
+        :meth:`crossentropy_grad`).  ``fwd``: the dict of ``forward(X, intermediates=True)``, whose ``idx1``, ``x1``, ``idx2``,
+        ``x2`` and ``pooled`` are used; without it the forward runs again inside the call.  ``grads`` has the names and Flux
+        shapes of :func:`dgcnn_param_shapes` (on the device: views of one flat buffer); its ``mu`` / ``sigma2`` entries are zero.
+        ``gx`` is ``(3, N, B)``, or ``None`` with ``input_grad=False``.  ``intermediates=True``: ``(grads, gx, mid)`` with
+        ``mid`` a dict of ``gx2`` (256, N, B) and ``gx1`` (64, N, B), the gradients at ``x2`` and ``x1``.  Everything lives where
+        ``X`` lives."""
+        gp, gx, mid, on_dev = self._grad_call(X, glogits, fwd, input_grad, intermediates)
+        flat = None if on_dev else gp.to_host()
+        grads, at = {}, 0
+        for name, shape in self._shapes().items():
+            n = int(np.prod(shape))
+            if on_dev:  # a view of the flat buffer, which it keeps alive
+                grads[name] = DeviceArray(gp.ptr + 4 * at, shape, np.float32, owned=False, keep=gp)
+            else:
+                grads[name] = flat[at:at + n].reshape(shape, order="F")
+            at += n
+        if not on_dev:
+            gx = None if gx is None else gx.to_host()
+            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
+        return (grads, gx, mid) if intermediates else (grads, gx)
+
+    def crossentropy_grad(self, X, labels):
+        """``(loss, grads, gx)`` for ``Flux.crossentropy(m(X), onehot(labels))``, the mean over the batch: ``labels`` are B
+        integers in [0, num_classes), 0-based.  One ``forward(X, intermediates=True)``; its ``probs`` are read back to the host,
+        ``loss = -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) /
+        Float32(B)`` with one Float32 subtraction and one Float32 division, then :meth:`grad` with that forward."""
+        _, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
+        y = np.asarray(labels)
+        if not np.issubdtype(y.dtype, np.integer):
+            raise TypeError(f"labels must hold integers, got {y.dtype}")
+        if y.shape != (B,):
+            raise ValueError(f"labels must be ({B},), got {y.shape}")
+        if y.size and (y.min() < 0 or y.max() >= self.num_classes):
+            raise ValueError(f"labels must be in [0, {self.num_classes}), got values from {y.min()} to {y.max()}")
+        fwd = self.forward(X, intermediates=True)
+        probs = fwd["probs"].to_host() if on_dev else fwd["probs"]
+        cols = np.arange(B)
+        with np.errstate(divide="ignore"):
+            loss = float(-np.mean(np.log(probs[y, cols].astype(np.float64))))
+        onehot = np.zeros((self.num_classes, B), np.float32)
+        onehot[y, cols] = 1
+        glogits = np.asfortranarray(((probs - onehot).astype(np.float32) / np.float32(B)).astype(np.float32))
+        grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits, fwd=fwd)
+        return loss, grads, gx
 
 
 class EdgeConv(_Model):

@@ -850,7 +850,7 @@ FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_
                                            float *pooled, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 /* ---- DGCNN inference: (m::DGCNN)(X) (src/models/dgcnn.jl:113-147) in test mode ------------------------------------------
- * Forward only, Float32: BatchNorm uses its running statistics, Dropout is the identity.  x (3,N,B) device.  DGCNN(num_classes,
+ * The forward (its gradients: "DGCNN adjoint" below), Float32: BatchNorm uses its running statistics, Dropout is the identity.  x (3,N,B) device.  DGCNN(num_classes,
  * K, npoints) with N == npoints: MaxPool((npoints,)) is then the maximum over all points of a cloud, which is what this
  * computes (for another N the reference's reshape to (1024,B) fails or mixes clouds; the host layers refuse it).
  * conv_bn_block / fc_bn_block (src/models/utils.jl:1-7) are conv or dense, BN, relu -- in this order.  In the order they run:
@@ -999,6 +999,57 @@ FX3D_API fx3d_status fx3d_edgeconv_grad_workspace_bytes(const int32_t *layers, i
 FX3D_API fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
                                         int32_t N, int32_t B, const int32_t *idx, const float *out, const float *gout,
                                         float *gparams, float *gx, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
+/* ---- DGCNN adjoint: the gradients of (m::DGCNN)(X) with respect to its parameters and to X, test mode --------------------------
+ * gparams = d sum(glogits . logits) / d params for logits = fx3d_dgcnn_forward(x), a flat Float32 buffer with the layout of
+ * params_dev (fx3d_dgcnn_param_count floats), and, if gx != NULL, gx (3,N,B) = d sum(glogits . logits) / d x.  The arguments up
+ * to B are the forward's.  glogits (num_classes,B) is the upstream gradient with respect to the LOGITS: the softmax uses expf,
+ * is not part of the bit-exact contract and stays with the caller.  Test mode throughout: BatchNorm's mu and var are constants
+ * (their slots are written as +0), gamma and beta are parameters, Dropout is the identity, the neighbour lists are constants.
+ * idx1, x1, idx2, x2, pooled: the forward's intermediates, ALL FIVE or NONE; with none, fx3d_dgcnn_forward runs first, into the
+ * workspace.  gx2 (256,N,B) and gx1 (64,N,B), the gradients at x2 and x1, are optional outputs (NULL: kept in the workspace).
+ * Per cloud b, all of it the forward's own bits:  p = pooled[:,b];  a4 = relu(BN4(W4 p + b4)) (512);  a5 = relu(BN5(W5 a4 + b5))
+ * (256);  a3[c,n] = relu(BN3(conv_3(x2)[c,n]));  sd_l = sqrtf(var_l + 1f-5).  Every operation is rounded to Float32; every chain
+ * is one fmaf accumulator from +0.0f over ALL terms in the stated order, no term skipped because it is zero except in the gather.
+ *   head:  d6[o] = glogits[o,b];  g5[i] = chain over o ascending, acc = fmaf(d6[o], W6[o,i], acc);  d5[i] = a5[i] > 0 ? g5[i] : +0;
+ *     dz5 = (d5 gamma5) / sd5;  g4[i] = chain over o, fmaf(dz5[o], W5[o,i], acc);  d4[i] = a4[i] > 0 ? g4[i] : +0;
+ *     dz4 = (d4 gamma4) / sd4;  gp[c] = chain over o, fmaf(dz4[o], W4[o,c], acc).
+ *   maximum over the points:  n*(c,b) = the smallest n with a3[c,n,b] == pooled[c,b] (Float32 comparison), defined only where
+ *     pooled[c,b] > 0.  A NaN or non-positive pooled value, or one that no point reproduces (a pooled that did not come from this
+ *     forward), has no winner and passes nothing.  d3[c,b] = gp[c] where a winner exists, else +0;  dz3 = (d3 gamma3) / sd3.
+ *     Deviation from the reference, as for the EdgeConv adjoints' maximum over k: NNlib's CPU max-pool adjoint is said to give the
+ *     gradient to the first element that is approximately the maximum, cuDNN gives it to an argmax; neither can be run here to
+ *     settle it.  Here it goes to the first point that EQUALS the maximum.
+ *   conv_3's input gradient, a gather:  gx2[i,n,b] = the chain over the channels c with n*(c,b) == n, c ascending, of
+ *     fmaf(dz3[c,b], W3[i,c], acc);  +0 for a point that wins no channel.  The terms of channels won elsewhere are not formed:
+ *     in the dense product they are dz3 = +-0 times W3, which changes a chain that began at +0 only where W3 is not finite (0 * Inf
+ *     is NaN) -- the gather differs from the dense product for non-finite weights only.
+ *   parameter sums over the clouds, each element ONE chain over b ascending from +0:
+ *     H6[o,i] = fmaf(d6[o,b], a5[i,b], acc), h6[o] = sum_b d6[o,b] (Float32 additions from +0);  H5 with d5, a4;  H4 with d4, p;
+ *     H3[i,c] = fmaf(x2[i, n*(c,b), b], d3[c,b], acc) and h3[c] = sum d3[c,b], both over the clouds that have a winner for c.
+ *   the families are "EdgeConv parameter adjoint"'s, verbatim:  dbeta = h;  db = (h gamma) / sd;  dW = (H gamma) / sd;
+ *     dgamma = (acc + (b - mu) h) / sd with acc the chain over the input index ascending of fmaf(W, H, acc).  fc_6 has no
+ *     BatchNorm: dW6 = H6, db6 = h6.
+ *   the two stages:  fx3d_edgeconv_grad itself on the ec2 slice with x = x1, idx = idx2, out = x2, gout = gx2 gives the ec2 slice of
+ *     gparams and gx1; again on the ec1 slice with x, idx1, x1, gout = gx1 it gives the ec1 slice and, if asked for, gx.  Their
+ *     sums have the order "EdgeConv parameter adjoint" states.
+ * gparams, gx, gx2 and gx1 are bit-identical to the restatement tests/dgcnn_grad_ref.py and from run to run, whatever the launch
+ * shape: no float atomics, no scatter.
+ * Envelope, refusals, their order, status codes and messages are fx3d_dgcnn_forward's: a NULL required pointer (params_dev, x,
+ * glogits, gparams, ws), some but not all of the five intermediates, num_classes outside [1, 2^20], a bad K, N or B, a short
+ * workspace or one not 256-byte aligned is FX3D_ERR_INVALID_ARG; each comes before any device work.
+ * Launches on `s` only (the forward where no intermediates are given, the argmax recomputation of conv_3, the head's adjoint, the
+ * two gathers, the sums over the clouds and their finishing, the two fx3d_edgeconv_grad calls), no host synchronisation, no host
+ * memory read after the argument check (graph-capturable).
+ * ws: fx3d_dgcnn_grad_workspace_bytes(N, B, K, num_classes) -- the forward's intermediates and probabilities; per (tile of 64
+ * points, channel) the first point that reproduces pooled; n*, a4, a5, d5, d4, d3, dz3; H and h of fc_4 and fc_5; gx2 and gx1; and
+ * one scratch region, the largest of fx3d_dgcnn_workspace_bytes and the two stages' fx3d_edgeconv_grad_workspace_bytes, which
+ * use it in turn. */
+FX3D_API fx3d_status fx3d_dgcnn_grad_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N, int32_t B,
+                                     const int32_t *idx1, const float *x1, const int32_t *idx2, const float *x2,
+                                     const float *pooled, const float *glogits, float *gparams, float *gx, float *gx2, float *gx1,
+                                     void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 #ifdef __cplusplus
 }
