@@ -271,6 +271,12 @@ __device__ __forceinline__ double wave_sum_l63_f64(double v) {  // fixed order: 
 // and they stop after the first one unless the range it finds is kRobustHarm times below cinf: the folded norms keep the
 // filter sharp with a point up to ~10^3 x the extent away, only beyond that does the bulk sink below fp16's resolution.
 constexpr float kRobustGate = 64.0f;
+// A cloud no wider than this gets no scale (sc = 1): its fp16 image is all zeros, every candidate passes the filter and the
+// exact merge orders them.  Below it the oracle's own Float32 squared distances, (2 x 1e-12)^2 and smaller, have terms that are
+// subnormal or underflow to zero: they carry an ABSOLUTE error (2^-150 per term) that the filter's bands, relative to the scaled
+// norms, do not cover -- a cloud of extent 1e-29 came back with the neighbours of its scaled image where the oracle sees one
+// tie.  (The bound was 1e-30, which only kept frexpf away from subnormals.)
+constexpr float kTinyExtent = 1.0e-12f;
 constexpr float kRobustHarm = 8.0f;  // (round 0 measures about a mean the outliers pulled: one extreme point among N gives cinf / rng ~ N / 32)
 
 // The robust range of a D = 3 cloud with outliers (nn1_f16_kernel, knn_f16_d3_kernel): clean clouds never call it.

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(C::T) void knn_f16_d3_kernel(const float *__restric
     }
     const bool has_far = sane && rng < cinf;
     float sc = 1.0f;
-    if (sane && rng > 1.0e-30f) {
+    if (sane && rng > kTinyExtent) {
         int e;
         (void)frexpf(rng, &e);
         sc = ldexpf(1.0f, 7 - e);  // |c~| < 2^7: a bulk far smaller than the farthest point stays out of fp16's subnormals

@@ -456,7 +456,7 @@ __device__ __forceinline__ void knn_pre_image_body(const float *__restrict__ y, 
     }
     const float cinf = __builtin_bit_cast(float, sh[0]);
     float sc = 1.0f;
-    if (cinf > 1.0e-30f && cinf < 1.0e30f) {
+    if (cinf > kTinyExtent && cinf < 1.0e30f) {
         int e;
         (void)frexpf(cinf * 1.000001f, &e);
         sc = ldexpf(1.0f, 10 - e);
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(kMThreads) void knn_mfma_kernel(const float *__rest
             __syncthreads();
         }
         const float cinf = __builtin_bit_cast(float, *cmax);
-        if (cinf > 1.0e-30f && cinf < 1.0e30f) {
+        if (cinf > kTinyExtent && cinf < 1.0e30f) {
             int e;
             (void)frexpf(cinf * 1.000001f, &e);  // = m 2^e, m in [0.5, 1)
             // |sc (c - mu)| < 2^10: ten binades above 1 so that a bulk far smaller than the largest |c - mu| (a few far

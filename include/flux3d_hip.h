@@ -325,7 +325,9 @@ FX3D_API fx3d_status fx3d_chamfer_sampled_bwd_step_reg(const float *x, int32_t N
  * a general selection kernel everything else
  * (k+drop_first up to M, any D) for M <= 36864 candidates; beyond that FX3D_ERR_UNSUPPORTED.
  * Order = Julia's isless on the Float32 squared distance, then the lower index: NaN distances (non-finite coordinates)
- * sort after +Inf, so every returned index is valid; fx3d_nn1 / the chamfer entry points use the same order. */
+ * sort after +Inf, so every returned index is valid; fx3d_nn1 / the chamfer entry points use the same order.  The distance is
+ * the Float32 one AS ROUNDED: where the squares underflow (a cloud of extent 1e-20: subnormal distances of a few bits; 1e-29:
+ * every distance +0) the ties this makes are ordered by index, like those of +Inf distances at the other end. */
 FX3D_API fx3d_status fx3d_knn(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
                               int32_t D, int32_t k, int32_t drop_first, int32_t *idx,
                               float *dist, fx3d_stream_t s);
