@@ -23,7 +23,7 @@
 //   knn_d3.hip         knn_f16_d3_kernel<FEAT, K3Geom>: D = 3, fp16-split matrix-core filter + exact re-scan in three geometries --
 //                      base (k+drop <= 32, M >= 64), compact (<= 48, two blocks per CU), wide (<= 64); FEAT: EdgeConv's
 //                      cat(X, KNN - X) written by the same kernel
-//   knn_mfma.hip       knn_pre_*_kernel (fx3d_knn_ws: per-cloud statistics + fp16 image built once) and knn_mfma_kernel<DK, F16, PRE>:
+//   knn_mfma.hip       knn_pre_*_kernel (fx3d_knn_ws: per-cloud statistics + fp16 image built once) and knn_mfma_kernel<DK, KnnFilter>:
 //                      4 <= D <= 128, k+drop <= 32, M >= 64: GEMM filter (fp16 rounded halves or Float32) + exact re-scan
 //   edge_features.hip  knn_gather[4]_kernel, edge_features_*_kernel: X[:, idx], cat(X, KNN - X) + permute for any F, the adjoint
 #include "knn_common.h"

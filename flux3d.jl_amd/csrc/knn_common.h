@@ -403,7 +403,7 @@ __device__ __forceinline__ void k3_sort_regs(float (&v)[NV]) {
 }
 
 // tau = an upper bound of the kk-th smallest filter value of every query (kk <= 24) from its 128 group minima -- 32 in this lane (mn), 32
-// in its partner half-lane, 64 in the other wave of the pair (wave index +- GW) -- shared by knn_f16_d3_kernel and knn_mfma_kernel<PRE>:
+// in its partner half-lane, 64 in the other wave of the pair (wave index +- GW) -- shared by knn_f16_d3_kernel and knn_mfma_kernel<F16Pre>:
 // the EIGHT smallest of each HALF of a lane's group minima (16 of its 32) instead of a sort of all 32.  The kk-th smallest of any
 // subset of the 128 group minima bounds the kk-th smallest filter value (every group minimum is some candidate's value); the subset
 // {8 smallest of each of the query's eight half-lane sets of 16} holds the kk <= 24 smallest of all 128 unless one set holds more

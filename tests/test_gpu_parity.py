@@ -419,6 +419,8 @@ def test_knn_feature_space(gpu_fx, oracle, D):
     (16, 256, 256, 1, 12, True, "lattice"),      # integer features: masses of exact ties
     (8, 128, 160, 1, 20, False, "same"),         # all candidates identical: list overflow -> brute-force merge
     (64, 96, 1500, 1, 20, False, "offset"),      # far-from-origin cloud (cancellation in the expanded form)
+    (128, 64, 160, 1, 20, False, "same"),        # DK = 4: every list overflows -> brute-force merge
+    (6, 64, 160, 1, 20, False, "same"),          # the same under the Float32 GEMM (D % 4 != 0)
 ])
 def test_knn_matrix_core_path(gpu_fx, oracle, D, N, M, B, k, drop, kind):
     """knn_mfma_kernel: Float32 GEMM filter + exact re-scan must reproduce the oracle's (distance, index)
@@ -446,7 +448,8 @@ def test_knn_float32_filter_variant(gpu_fx, oracle):
     """The Float32 GEMM filter is what feature-space clouds get that the fp16 filter does not take (D % 4 != 0, or more than 4096
     candidates): shapes on both sides of either rule must give the oracle's lists."""
     rng = np.random.default_rng(77)
-    for (D, N, M, k) in ((62, 300, 1024, 20), (30, 100, 200, 9), (127, 64, 96, 5), (64, 96, 4160, 20), (6, 200, 333, 7)):
+    for (D, N, M, k) in ((62, 300, 1024, 20), (30, 100, 200, 9), (127, 64, 96, 5), (64, 96, 4160, 20), (6, 200, 333, 7),
+                         (128, 64, 4161, 5), (64, 64, 4161, 5)):  # an odd M > 4096 is not sliced: the Float32 GEMM with the vectorised gather
         x = np.asfortranarray(rng.standard_normal((D, N, 2)).astype(np.float32))
         y = np.asfortranarray(rng.standard_normal((D, M, 2)).astype(np.float32))
         idx, dist = gpu_fx.knn(x, k, y=y)
@@ -479,8 +482,11 @@ def test_knn_fp16_filter(gpu_fx, oracle):
     (32, 200, 2000, 2, 31, False),
     (16, 100, 700, 1, 7, False),
     (4, 333, 2048, 1, 32, False),    # smallest row (one 16-byte piece)
-    (64, 100, 4096, 1, 20, False),   # more than 8 stages: the gather from L2 stays
+    (64, 100, 4096, 1, 20, False),   # one long cloud on an empty grid: 8 candidate slices of 512 rows
     (62, 150, 700, 2, 12, False),    # D % 4 != 0: no staging, every survivor's row gathered from L2
+    (128, 100, 2305, 1, 12, False),  # more than 8 stages and an odd M (no candidate slices): the vectorised gather, query pieces re-read
+    (64, 100, 2305, 1, 20, False),   # the same at D = 64 and
+    (32, 100, 2305, 1, 9, False),    # at D = 32 (query row in registers)
 ])
 def test_knn_staged_exact_phase(gpu_fx, oracle, fx_option, D, N, M, B, k, drop):
     """knn_mfma_kernel's exact phase with the candidate rows staged through LDS (default when D/4 divides the block and
@@ -500,10 +506,11 @@ def test_knn_staged_exact_phase(gpu_fx, oracle, fx_option, D, N, M, B, k, drop):
         assert np.array_equal(dist.to_host(), od), f"nopre={nopre}"
 
 
-@pytest.mark.parametrize("D,csize,spread", [(64, 80, 1e-3), (32, 200, 1e-4), (64, 700, 1e-3)])
+@pytest.mark.parametrize("D,csize,spread", [(64, 80, 1e-3), (32, 200, 1e-4), (64, 700, 1e-3), (128, 200, 1e-3), (30, 200, 1e-3)])
 def test_knn_feature_space_clustered_data(gpu_fx, oracle, D, csize, spread):
     """Tight clusters put more candidates inside a query's band than the fast path's key arrays hold (60): the medium
-    path selects exactly among the query's own survivors (up to 512), larger clusters take the full exact merge."""
+    path selects exactly among the query's own survivors (up to 512), larger clusters take the full exact merge.  D = 128: the
+    widest instantiation; D = 30: the Float32 GEMM's two lane lists per query instead of the pre-pass mode's four."""
     rng = np.random.default_rng(D + csize)
     N = 1024
     centres = rng.standard_normal((D, N // csize + 1, 2)) * 3
