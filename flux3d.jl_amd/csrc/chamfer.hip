@@ -25,6 +25,7 @@
 //     reference; any other D): nn1_exact.hip.
 // nn1_split_finalize_kernel (below the fp16 kernel) unpacks the rows of a candidate-split run that did not merge them itself.
 #include <cmath>
+#include <type_traits>
 
 #include "nn1_common.h"
 
@@ -153,6 +154,13 @@ __device__ __forceinline__ float vmin(float a, float b) {
     return r;
 }
 
+// plain v_max_f32, the twin of vmin (like v_min_f32 it returns the other operand when one is a quiet NaN)
+__device__ __forceinline__ float vmax(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 __device__ __forceinline__ void split2h(float v, _Float16 &h, _Float16 &l) {
     h = (_Float16)v;
     l = (_Float16)(v - (float)h);
@@ -198,14 +206,18 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     constexpr int QB = (kHThreads / 64) * 32;  // queries per tile pass
 
     const int L = blockIdx.x;
-    const int per_cloud = p.tiles * p.nsplit;
+    // (PRUNE) what the host guarantees of a pruned launch (chamfer_host.hip: run_nn1 refuses any other plan), as compile-time facts: ONE chunk
+    // holds the whole candidate cloud -- no candidate split, no tail, one trip of the chunk loop -- so the chunk's counters, the far
+    // list's slot and the "last chunk" tests below are constants instead of scalar state carried (and spilled) across the passes
+    const int nsplit = PRUNE ? 1 : p.nsplit;
+    const int per_cloud = p.tiles * nsplit;
     // >= 8 clouds: all blocks of a cloud get ids with equal L%8, i.e. one XCD and one L2 (block L runs on
     // XCD L%8).  Fewer clouds than XCDs: plain order, so that a cloud's blocks spread over every XCD.
     const bool by_xcd = 2 * p.B >= 8;
     const int slot = by_xcd ? L >> 3 : L;
     const int c = by_xcd ? (slot / per_cloud) * 8 + (L & 7) : slot / per_cloud;
-    const int tile = (slot % per_cloud) / p.nsplit;
-    const int split = (slot % per_cloud) % p.nsplit;
+    const int tile = (slot % per_cloud) / nsplit;
+    const int split = (slot % per_cloud) % nsplit;
     if (c >= 2 * p.B) return;
     const int dir = c >= p.B ? 1 : 0;
     const int b = dir ? c - p.B : c;
@@ -213,7 +225,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     const int NC = dir ? p.N : p.M;
     if (tile >= (dir ? p.tiles_y : p.tiles_x)) return;
     if ((long long)split * p.chunk >= NC) return;  // this direction has fewer chunks than splits
-    const int ctail = (p.tail > 0 && p.nsplit == 1 && NC > p.chunk && NC - p.chunk <= p.tail) ? NC - p.chunk : 0;
+    const int ctail = (!PRUNE && p.tail > 0 && nsplit == 1 && NC > p.chunk && NC - p.chunk <= p.tail) ? NC - p.chunk : 0;
     const int NCm = NC - ctail;                    // candidates that go through the filter (the chunk loop)
     const float *__restrict__ qb = (dir ? p.y : p.x) + (size_t)b * NQ * 3;
     const float *__restrict__ cb = (dir ? p.x : p.y) + (size_t)b * NC * 3;
@@ -234,7 +246,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     unsigned short *items = witems + wv * kHItemCap;
     float *qtab = wq + wv * 96;
     const bool vec = (reinterpret_cast<uintptr_t>(cb) & 15) == 0;
-    const bool one_shot = NCm <= CH;
+    const bool one_shot = PRUNE || NCm <= CH;
     if (tid == 0) { nfar[0] = 0; nfar[1] = 0; }  // (ordered before their first use by the barrier of the bounding-box pass)
     float qpre[3];  // this lane's query of the coming tile pass (the load's latency hides behind the prologue)
     {
@@ -258,7 +270,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     // candidate-split run whose block takes ONE chunk, that chunk alone (round 5: any centre is correct and the scale only has to
     // cover the candidates of THIS block's image; C3's blocks walked all 5000 points for an image of 1728, and read their chunk
     // a second time for the image: it is parked in LDS during the pass now, as in one-chunk runs)
-    const bool own_chunk_only = p.nsplit > 1 && (long long)split * CH + (long long)p.nsplit * CH >= NCm;
+    const bool own_chunk_only = nsplit > 1 && (long long)split * CH + (long long)nsplit * CH >= NCm;
     const int s_lo = own_chunk_only ? split * CH : 0;
     const int SN = own_chunk_only ? (NCm - s_lo < CH ? NCm - s_lo : CH) : NC;
     const float *__restrict__ sb = cb + (size_t)s_lo * 3;
@@ -679,9 +691,10 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     h8 bq;
     double acc = 0.0;
 
-    const int jfirst = split * CH, jstep = p.nsplit * CH;
+    const int jfirst = split * CH, jstep = nsplit * CH;
     for (int j0 = jfirst; j0 < NCm; j0 += jstep) {
-        const int cnt = (NCm - j0) < CH ? (NCm - j0) : CH;
+        const int cnt = PRUNE || (NCm - j0) < CH ? (NCm - j0) : CH;
+        const bool last_chunk = PRUNE || j0 + jstep >= NCm;
         const int cnt_pad = (cnt + 32 * kHLT - 1) / (32 * kHLT) * (32 * kHLT);
         if (j0 > jfirst) __syncthreads();
         // ---- stage the fp16 split image ------------------------------------------------------------------
@@ -689,26 +702,30 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
 // (PRUNE) the 16 threads of a DPP row convert the 64 image rows of ONE lane tile where the sort laid them (or where the cloud
             // pass parked them): row k 16 + (lane of the row) in step k -- 256 contiguous bytes per row and LDS access --, write them to
             // the block's scratch, and reduce the tile's box (image frame) with four row steps
-            for (int tl = tid >> 4; tl * 64 < cnt_pad + 64; tl += kHThreads / 16) {
+            // A wave takes four consecutive lane tiles per step.  All four full (wave-uniform; every tile of a step but a cloud's last): no
+            // per-row test.  All four behind the cloud (the padding blocks): their constant pieces and an empty box.  Else -- the
+            // ragged last tile, or padding beside real rows -- every row is tested.
+            auto stage_tile = [&](int tl, auto full_c) {
+                constexpr bool kFull = decltype(full_c)::value;
                 float4 r4[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int pt = tl * 64 + k * 16 + (tid & 15);
-                    r4[k] = float4{0.f, 0.f, 0.f, 0.f};
-                    if (pt < cnt) r4[k] = imgf[((pt >> 5) * 2) * 32 + (pt & 31)];
+                    if (!kFull) r4[k] = float4{0.f, 0.f, 0.f, 0.f};
+                    if (kFull || pt < cnt) r4[k] = imgf[((pt >> 5) * 2) * 32 + (pt & 31)];
                 }
                 float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int pt = tl * 64 + k * 16 + (tid & 15), i0 = ((pt >> 5) * 2) * 32 + (pt & 31);
                     h8 p0, p1;
-                    if (pt < cnt) {
+                    if (kFull || pt < cnt) {
                         pieces(r4[k].x, r4[k].y, r4[k].z, pt, p0, p1);
                         const int id = sorted_c ? __builtin_bit_cast(int, r4[k].w) : j0 + pt;
                         cs[pt] = float4{r4[k].x, r4[k].y, r4[k].z, __builtin_bit_cast(float, id)};
                         const float b3[3] = {(r4[k].x - mu[0]) * sc, (r4[k].y - mu[1]) * sc, (r4[k].z - mu[2]) * sc};
 #pragma unroll
-                        for (int d = 0; d < 3; ++d) { lo3[d] = vmin(lo3[d], b3[d]); hi3[d] = -vmin(-hi3[d], -b3[d]); }
+                        for (int d = 0; d < 3; ++d) { lo3[d] = vmin(lo3[d], b3[d]); hi3[d] = vmax(hi3[d], b3[d]); }
                     } else {
                         make_pieces(0.f, 0.f, 0.f, p0, p1);
                         p1[7] = (_Float16)kPadF16;
@@ -722,6 +739,28 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 if ((tid & 15) == 0 && tl < 64) {
                     boxes[tl * 2] = float4{bl[0], bl[1], bl[2], 0.0f};
                     boxes[tl * 2 + 1] = float4{bh[0], bh[1], bh[2], 0.0f};
+                }
+            };
+            for (int tw = 4 * wv; tw * 64 < cnt_pad + 64; tw += kHThreads / 16) {
+                const int tl = tw + (lane >> 4);
+                if (64 * (tw + 4) <= cnt) {
+                    stage_tile(tl, std::true_type{});
+                } else if (64 * tw < cnt) {
+                    if (tl * 64 < cnt_pad + 64) stage_tile(tl, std::false_type{});
+                } else if (tl * 64 < cnt_pad + 64) {
+                    h8 p0, p1;
+                    make_pieces(0.f, 0.f, 0.f, p0, p1);
+                    p1[7] = (_Float16)kPadF16;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int pt = tl * 64 + k * 16 + (tid & 15), i0 = ((pt >> 5) * 2) * 32 + (pt & 31);
+                        imgp[i0] = p0;
+                        imgp[i0 + 32] = p1;
+                    }
+                    if ((tid & 15) == 0 && tl < 64) {
+                        boxes[tl * 2] = float4{INFINITY, INFINITY, INFINITY, 0.0f};
+                        boxes[tl * 2 + 1] = float4{-INFINITY, -INFINITY, -INFINITY, 0.0f};
+                    }
                 }
             }
         } else
@@ -748,8 +787,10 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
         FX3D_PROBE_MARKW(0);
 
         const int nf = nfar[fslot];          // far candidates of this chunk (valid after the barrier above)
-        if (tid == 0) nfar[fslot ^ 1] = 0;   // the next chunk's counter (its staging starts behind the barrier at the loop top)
-        fslot ^= 1;
+        if constexpr (!PRUNE) {
+            if (tid == 0) nfar[fslot ^ 1] = 0;   // the next chunk's counter (its staging starts behind the barrier at the loop top)
+            fslot ^= 1;
+        }
         const bool far_ok = nf <= kHFarCap;  // more than the side list holds: this chunk's filter is not used
         // (the last tile of a direction goes on past tpb passes while queries are left: the planner folds a remainder of <= 64
         //  queries into it instead of giving them a block of their own)
@@ -1306,7 +1347,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                     }
                 }
                 // the cloud's tail beyond the LDS image (<= kHTail candidates): every query of the wave against each, exactly
-                if (ctail && j0 + jstep >= NCm) {
+                if (ctail && last_chunk) {
                     for (int t = lane; t < 32 * ctail; t += 64) {
                         const int qs = t & 31, jc = NCm + (t >> 5);
                         const float qq[3] = {qtab[qs * 3], qtab[qs * 3 + 1], qtab[qs * 3 + 2]};
@@ -1319,14 +1360,14 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
             FX3D_PROBE_MARK(tp == 0 ? 4 : 8);
             FX3D_PROBE_MARKW(tp == 0 ? 2 : 4);
 
-            if (j0 + jstep >= NCm) {  // last chunk of this block: results of this tile pass
+            if (last_chunk) {  // last chunk of this block: results of this tile pass
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 __builtin_amdgcn_wave_barrier();
                 if (hh == 0) {
                     const unsigned long long r = qres[jq];
                     const float dd = __builtin_bit_cast(float, (unsigned int)(r >> 32));
                     const int ii = (int)(unsigned int)r;
-                    if (p.nsplit > 1) {  // this chunk subset's row; the finalize kernel (or, fused, the tile's last subset) takes the
+                    if (nsplit > 1) {  // this chunk subset's row; the finalize kernel (or, fused, the tile's last subset) takes the
                                          // minimum over the subsets.  Fused: a write-through (agent-scope) store -- the reader may sit
                                          // on another XCD, behind another L2; a device-wide fence instead costs a whole L2 write-back
                                          // per block (measured: 32 -> 94 us)
@@ -1344,9 +1385,10 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 __builtin_amdgcn_wave_barrier();
             }
         }
+        if constexpr (PRUNE) break;  // (the one chunk)
     }
     FX3D_PROBE_MARK(11);
-    if (SPLITFUSE && p.nsplit > 1) {
+    if (SPLITFUSE && nsplit > 1) {
         // ---- candidate-split run, merge fused (round 5): the chunk subsets of one query tile arrive at a counter of their own
         //      (a spare word of the launch's ticket slot: zero between launches, the last arriver returns it to zero); the last one
         //      takes the 64-bit minimum over the subsets' rows -- (distance bits, index): `isless`, then the lowest index --, writes
@@ -1361,7 +1403,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
         //  counter 1.2 k, merge 4.6 k, finalisation 4.9 k cycles)
         __syncthreads();
         FX3D_PROBE_MARK2(12);
-        const int ns = (NC + CH - 1) / CH < p.nsplit ? (NC + CH - 1) / CH : p.nsplit;  // subsets that exist for this direction
+        const int ns = (NC + CH - 1) / CH < nsplit ? (NC + CH - 1) / CH : nsplit;  // subsets that exist for this direction
         if (tid == 0) {
             const unsigned int t = (unsigned int)c * (unsigned int)p.tiles + (unsigned int)tile;
             unsigned int *ctr = p.ticket + (t / 15u) * 16u + 1u + t % 15u;

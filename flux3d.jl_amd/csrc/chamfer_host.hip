@@ -276,6 +276,12 @@ fx3d_status run_nn1(Nn1Params p, int D, const Plan &pl, hipStream_t st) {
     p.fuse_split = p.gres && p.ticket ? 1 : 0;  // (the caller checked that the tile counters fit the ticket slot)
     p.pscr_stride = p.pscr ? prune_rows_per_block(pl, p.N, p.M, D) : 0;
     if (!p.pscr_stride) p.pscr = nullptr;
+    // The pruned instantiation has these as compile-time facts (chamfer.hip: one chunk holds each candidate cloud, no candidate split, no
+    // tail, no split rows): a plan that breaks one must not reach it.
+    if (p.pscr)
+        FX3D_REQUIRE(p.nsplit == 1 && p.tail == 0 && !p.gres && (p.N > p.M ? p.N : p.M) <= p.chunk && p.chunk <= kHChunkMax,
+                     "nn1: pruning scratch with a plan the pruned kernel does not take (nsplit=%d tail=%d chunk=%d N=%d M=%d)", p.nsplit, p.tail,
+                     p.chunk, p.N, p.M);
     const Nn1Kernel k = plan_kernel(pl, D);
     ProfileScope prof("nn1", st);
     if (k == NN1_F16) return nn1_f16_launch(p, pl.grid, pl.lds_bytes, st);
