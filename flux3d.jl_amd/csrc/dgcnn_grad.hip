@@ -65,21 +65,6 @@ __global__ __launch_bounds__(kPtThreads) void dgcnn_argmax_kernel(const float *_
     }
 }
 
-// dz[0 .. nout) in LDS, W (nout, nin) column-major, nout a multiple of 4: acc = fmaf(dz[o], W[o, i], acc) upwards from +0.0f
-__device__ __forceinline__ float transposed_chain(const float *dz, int nout, const float *__restrict__ W, int i) {
-    float acc = 0.0f;
-    const float *w = W + (size_t)nout * i;
-#pragma unroll 4
-    for (int o = 0; o < nout; o += 4) {
-        const W4 q = *reinterpret_cast<const W4 *>(w + o);
-        acc = fmaf(dz[o], q.x, acc);
-        acc = fmaf(dz[o + 1], q.y, acc);
-        acc = fmaf(dz[o + 2], q.z, acc);
-        acc = fmaf(dz[o + 3], q.w, acc);
-    }
-    return acc;
-}
-
 struct HeadBwdArgs {
     const int32_t *tfirst;  // (1024, ntiles, B)
     int ntiles, nc;
@@ -202,22 +187,9 @@ __global__ __launch_bounds__(256) void dgcnn_conv3_pgrad_kernel(const float *__r
     }
 }
 
-// H[o, i] = the chain over b of d[o, b] a[i, b], h[o] = the sum over b of d[o, b]: one thread per element
-struct DenseSums { const float *d, *a; int nin, nout, B; float *H, *h; };
+// H[o, i] = the chain over b of d[o, b] a[i, b], h[o] = the sum over b of d[o, b]: one thread per element (dense_sums)
 __global__ __launch_bounds__(256) void dense_sums_kernel(const DenseSums s) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x, nw = (long long)s.nin * s.nout;
-    if (e < nw) {
-        const int i = (int)(e / s.nout), o = (int)(e - (long long)i * s.nout);
-        float acc = 0.0f;
-#pragma unroll 8
-        for (int b = 0; b < s.B; ++b) acc = fmaf(s.d[o + (size_t)s.nout * b], s.a[i + (size_t)s.nin * b], acc);
-        s.H[e] = acc;
-    } else if (e < nw + s.nout) {
-        const int o = (int)(e - nw);
-        float acc = 0.0f;
-        for (int b = 0; b < s.B; ++b) acc = acc + s.d[o + (size_t)s.nout * b];
-        s.h[o] = acc;
-    }
+    dense_sums(s, (long long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // the four families of a dense layer with BatchNorm from H and h (flux3d_hip.h); mu and var: +0

@@ -1,4 +1,4 @@
-// What the model units (pointnet.hip, dgcnn.hip, edgeconv.hip, and through edgeconv_adjoint.h edgeconv_bwd.hip and
+// What the model units (pointnet.hip and pointnet_grad.hip through pointnet_net.h, dgcnn.hip, edgeconv.hip, and through edgeconv_adjoint.h edgeconv_bwd.hip and
 // edgeconv_pgrad.hip) share: the exact-Float32 contraction on the f32 MFMA, the
 // activation and BatchNorm epilogue, the v_fma_f32 chains of the narrow and the dense layers, the EdgeConv kernel's gather of
 // the edge rows and fold of the last layer, the two ends of a classifier head, and on the host the walk over the flat
@@ -33,7 +33,7 @@ struct Bn { const float *g, *b, *m, *v; };
 struct Conv { const float *W, *b; Bn bn; };
 struct Dense { const float *W, *b; };
 
-enum Epi { kNone, kReluBn, kBnRelu, kBnOnly };
+enum Epi { kNone, kReluBn, kBnRelu, kBnOnly, kRelu };  // kRelu: relu(acc + bias), what kReluBn hands its BatchNorm (the adjoints)
 
 // Julia's max on IEEE floats: NaN propagates, -0.0 < +0.0 (as transforms.hip)
 __device__ __forceinline__ float jmax(float x, float y) {
@@ -46,6 +46,7 @@ template <int EPI>
 __device__ __forceinline__ float epilogue(float acc, float bias, float g, float be, float mu, float sd) {
     if (EPI == kNone) return acc;
     float v = acc + bias;
+    if (EPI == kRelu) return relu(v);
     if (EPI == kReluBn) v = relu(v);
     v = batchnorm(v, g, be, mu, sd);
     if (EPI == kBnRelu) v = relu(v);
@@ -233,6 +234,40 @@ __device__ __forceinline__ float dense_chain(const float *x, int n, const float 
 #pragma unroll 8
     for (int i = 0; i < n; ++i) acc = fmaf(x[i], w[(size_t)nout * i], acc);
     return acc;
+}
+
+// dz[0 .. nout) in LDS, W (nout, nin) column-major, nout a multiple of 4: acc = fmaf(dz[o], W[o, i], acc) upwards from +0.0f
+__device__ __forceinline__ float transposed_chain(const float *dz, int nout, const float *__restrict__ W, int i) {
+    float acc = 0.0f;
+    const float *w = W + (size_t)nout * i;
+#pragma unroll 4
+    for (int o = 0; o < nout; o += 4) {
+        const W4 q = *reinterpret_cast<const W4 *>(w + o);
+        acc = fmaf(dz[o], q.x, acc);
+        acc = fmaf(dz[o + 1], q.y, acc);
+        acc = fmaf(dz[o + 2], q.z, acc);
+        acc = fmaf(dz[o + 3], q.w, acc);
+    }
+    return acc;
+}
+
+// The parameter sums of a dense layer over the clouds (the adjoints' dense_sums_kernel): H[o, i] = the chain over b of
+// d[o, b] a[i, b], h[o] = the sum over b of d[o, b]; element e of nin nout + nout, one thread each
+struct DenseSums { const float *d, *a; int nin, nout, B; float *H, *h; };
+__device__ __forceinline__ void dense_sums(const DenseSums &s, long long e) {
+    const long long nw = (long long)s.nin * s.nout;
+    if (e < nw) {
+        const int i = (int)(e / s.nout), o = (int)(e - (long long)i * s.nout);
+        float acc = 0.0f;
+#pragma unroll 8
+        for (int b = 0; b < s.B; ++b) acc = fmaf(s.d[o + (size_t)s.nout * b], s.a[i + (size_t)s.nin * b], acc);
+        s.H[e] = acc;
+    } else if (e < nw + s.nout) {
+        const int o = (int)(e - nw);
+        float acc = 0.0f;
+        for (int b = 0; b < s.B; ++b) acc = acc + s.d[o + (size_t)s.nout * b];
+        s.h[o] = acc;
+    }
 }
 
 // ---- the two ends of a head kernel (one block of kHeadThreads per cloud b) -------------------------------------------------

@@ -1,4 +1,4 @@
-// PointNet inference (gfx950): (m::PointNet)(X) of src/models/pointnet.jl:62-85 in test mode, Float32, forward only.
+// PointNet inference (gfx950): (m::PointNet)(X) of src/models/pointnet.jl:62-85 in test mode, Float32: the forward (pointnet_grad.hip: its adjoint).
 // include/flux3d_hip.h states the network, the arithmetic and the parameter layout; this file is how they are computed.
 //
 // Every contraction is one accumulator per output element that walks the input channels upwards with one rounding per
@@ -22,26 +22,27 @@
 //     output element (W (out, in) column-major: consecutive threads read consecutive weights), BatchNorm, and for the
 //     classifier relu + softmax.  stn / fstn write their (K, K) matrix already transposed (T[i,j] = d[j + K i] at i + K j),
 //     which is the (Cin, Cout) layout of a convolution: the per-cloud transform is one more bias-free layer of the point kernel.
-#include "mlp_common.h"
+#include "pointnet_net.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
+using namespace fx3d::mlp::pointnet;
 
 namespace {
 
-constexpr size_t kPtLds = (size_t)(2 * kTile * kLd + 2 * kTile * 3) * sizeof(float);
+// the round's last layer (128 -> 1024), reduced to the tile's maxima
+template <int EPI, bool WIN>
+__device__ __forceinline__ void last_layer(const PointArgs &a, const float *in, int nvalid, int p0, float *tmax) {
+    if (WIN) {
+        const size_t at = tmax - a.tmax;
+        conv_final_win<EPI>(in, a.c3.W, a.c3.b, a.c3.bn, nvalid, p0, tmax, a.tfirst + at, a.tpre + at);
+    } else {
+        conv_mfma<128, EPI, true>(in, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+    }
+}
 
-struct PointArgs {
-    const float *x;   // (3, N, B): MODE 0, 1
-    float *h;         // workspace (64, N, B): written by MODE 1, read by MODE 2
-    const float *tf;  // the cloud's transform, (3, 3, B) for MODE 1, (64, 64, B) for MODE 2
-    Conv c0;          // MODE 1: conv_block1
-    Conv c1, c2, c3;  // the round's convolutions (MODE 2: c2, c3)
-    float *tmax;      // (1024, ntiles, B)
-    int N, ntiles;
-};
-
-template <int MODE>
+// WIN: the adjoint's instantiation (pointnet_grad.hip), whose last layer also writes the tile's winners (conv_final_win)
+template <int MODE, bool WIN>
 __global__ __launch_bounds__(kPtThreads) void pointnet_points_kernel(const PointArgs a) {
     extern __shared__ float lds[];
     float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_points_kernel(const Point
         __syncthreads();
         conv_mfma<64, kReluBn, false>(bufA, bufB, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
         __syncthreads();
-        conv_mfma<128, kReluBn, true>(bufB, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+        last_layer<kReluBn, WIN>(a, bufB, nvalid, p0, tmax);
     } else if (MODE == 1) {
         conv3<kNone>(xs, xt, 3, 3, a.tf + (size_t)b * 9, nullptr, Bn{});
         __syncthreads();
@@ -75,26 +76,16 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_points_kernel(const Point
         __syncthreads();
         conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
         __syncthreads();
-        conv_mfma<128, kReluBn, true>(bufA, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+        last_layer<kReluBn, WIN>(a, bufA, nvalid, p0, tmax);
     } else {
         conv_mfma<64, kNone, false>(bufA, bufB, 64, a.tf + (size_t)b * 4096, nullptr, Bn{}, nvalid, nullptr);
         __syncthreads();
         conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
         __syncthreads();
-        conv_mfma<128, kBnOnly, true>(bufA, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
+        last_layer<kBnOnly, WIN>(a, bufA, nvalid, p0, tmax);
     }
 }
 
-struct HeadArgs {
-    const float *tmax;  // (1024, ntiles, B)
-    int ntiles;
-    Dense d1, d2, d3;   // 1024 -> 512, 512 -> 256, 256 -> n3
-    Bn bn1, bn2;        // FEAT: BatchNorm(512) after d1; both: BatchNorm(256) after d2
-    int n3, K;          // outputs of d3; stn / fstn: n3 = K K
-    float *mat, *mat_user;  // stn / fstn: (K, K, B) in the workspace and, optionally, the caller's copy
-    float *pooled;          // FEAT, optional: (1024, B)
-    float *logits, *probs;  // FEAT: (n3, B) each; logits is the caller's array or the workspace
-};
 template <bool FEAT>
 __global__ __launch_bounds__(kHeadThreads) void pointnet_head_kernel(const HeadArgs a) {
     __shared__ float v0[kFeat], v1[512], v2[256];
@@ -127,93 +118,43 @@ __global__ __launch_bounds__(kHeadThreads) void pointnet_head_kernel(const HeadA
     if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
 }
 
-struct Stn { Conv c1, c2, c3; Dense d1, d2, d3; Bn bn; };
-struct Net {
-    Stn stn, fstn;
-    Conv block1, f1, f2;
-    Dense fd1, fd2, cls;
-    Bn fbn1, fbn2;
-    long long count;
-};
-
-Stn layout_stn(Cursor &c, int K) {
-    Stn s;
-    s.c1 = c.conv(K, 64);     s.c1.bn = c.bn(64);
-    s.c2 = c.conv(64, 128);   s.c2.bn = c.bn(128);
-    s.c3 = c.conv(128, 1024); s.c3.bn = c.bn(1024);
-    s.d1 = c.dense(1024, 512);
-    s.d2 = c.dense(512, 256);
-    s.bn = c.bn(256);
-    s.d3 = c.dense(256, K * K);
-    return s;
-}
-
-Net layout(const float *params, int num_classes) {
-    Cursor c{params, 0};
-    Net n;
-    n.stn = layout_stn(c, 3);
-    n.block1 = c.conv(3, 64);   n.block1.bn = c.bn(64);
-    n.fstn = layout_stn(c, 64);
-    n.f1 = c.conv(64, 128);     n.f1.bn = c.bn(128);
-    n.f2 = c.conv(128, 1024);   n.f2.bn = c.bn(1024);
-    n.fd1 = c.dense(1024, 512); n.fbn1 = c.bn(512);
-    n.fd2 = c.dense(512, 256);  n.fbn2 = c.bn(256);
-    n.cls = c.dense(256, num_classes);
-    n.count = c.at;
-    return n;
-}
-
-// the workspace: h (64, N, B) | per-tile maxima (1024, ntiles, B) | T (3, 3, B) | F (64, 64, B) | logits (num_classes, B)
-struct WsPlan { size_t h, tmax, T, F, logits, total; int ntiles; };
-WsPlan ws_plan(int N, int B, int nc) {
-    WsPlan w;
-    w.ntiles = (N + kTile - 1) / kTile;
-    WsBump ws;
-    w.h = ws.put((size_t)64 * N * B * sizeof(float));
-    w.tmax = ws.put((size_t)kFeat * w.ntiles * B * sizeof(float));
-    w.T = ws.put((size_t)9 * B * sizeof(float));
-    w.F = ws.put((size_t)4096 * B * sizeof(float));
-    w.logits = ws.put((size_t)nc * B * sizeof(float));
-    w.total = ws.at;
-    return w;
-}
-
-fx3d_status check_sizes(const char *fn, int32_t N, int32_t B, int32_t nc) {
-    FX3D_REQUIRE(nc >= 1 && nc <= (1 << 20), "%s: num_classes must be in [1, 2^20], got %d", fn, nc);
-    FX3D_REQUIRE(N >= 1 && B >= 1, "%s: N and B must be positive, got N=%d B=%d", fn, N, B);
-    FX3D_REQUIRE(B <= 65535, "%s: B must be at most 65535, got %d", fn, B);
-    FX3D_REQUIRE((long long)N * B <= (1ll << 31), "%s: N * B must be at most 2^31, got %lld", fn, (long long)N * B);
-    return FX3D_OK;
-}
-
-template <int MODE>
-fx3d_status launch_points(const PointArgs &a, int B, hipStream_t st) {
-    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&pointnet_points_kernel<MODE>), (int)kPtLds,
+template <int MODE, bool WIN>
+fx3d_status launch_points_of(const PointArgs &a, int B, hipStream_t st) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&pointnet_points_kernel<MODE, WIN>), (int)kPtLds,
                                               "pointnet_points_kernel");
     if (rc != FX3D_OK) return rc;
-    ProfileScope prof("pointnet_points", st);
-    hipLaunchKernelGGL(pointnet_points_kernel<MODE>, dim3(a.ntiles, B), dim3(kPtThreads), kPtLds, st, a);
+    ProfileScope prof(WIN ? "pointnet_points_win" : "pointnet_points", st);
+    hipLaunchKernelGGL((pointnet_points_kernel<MODE, WIN>), dim3(a.ntiles, B), dim3(kPtThreads), kPtLds, st, a);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
 
 template <bool FEAT>
-fx3d_status launch_head(const HeadArgs &a, int B, hipStream_t st) {
+fx3d_status launch_head_of(const HeadArgs &a, int B, hipStream_t st) {
     ProfileScope prof("pointnet_head", st);
     hipLaunchKernelGGL(pointnet_head_kernel<FEAT>, dim3(B), dim3(kHeadThreads), 0, st, a);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
 
-HeadArgs stn_head(const Stn &s, int K, const float *tmax, int ntiles, float *mat, float *mat_user) {
-    HeadArgs h{};
-    h.tmax = tmax; h.ntiles = ntiles;
-    h.d1 = s.d1; h.d2 = s.d2; h.d3 = s.d3; h.bn2 = s.bn;
-    h.n3 = K * K; h.K = K; h.mat = mat; h.mat_user = mat_user;
-    return h;
+}  // namespace
+
+namespace fx3d {
+namespace mlp {
+namespace pointnet {
+
+fx3d_status launch_points(int mode, bool win, const PointArgs &a, int B, hipStream_t st) {
+    if (win) return mode == 0 ? launch_points_of<0, true>(a, B, st) : mode == 1 ? launch_points_of<1, true>(a, B, st) : launch_points_of<2, true>(a, B, st);
+    return mode == 0 ? launch_points_of<0, false>(a, B, st) : mode == 1 ? launch_points_of<1, false>(a, B, st) : launch_points_of<2, false>(a, B, st);
 }
 
-}  // namespace
+fx3d_status launch_head(bool feat, const HeadArgs &a, int B, hipStream_t st) {
+    return feat ? launch_head_of<true>(a, B, st) : launch_head_of<false>(a, B, st);
+}
+
+}  // namespace pointnet
+}  // namespace mlp
+}  // namespace fx3d
 
 extern "C" {
 
@@ -255,20 +196,20 @@ fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_classes, 
     fx3d_status r;
     // stn: the (3, 3) input transform of every cloud
     p.c1 = n.stn.c1; p.c2 = n.stn.c2; p.c3 = n.stn.c3;
-    if ((r = launch_points<0>(p, B, st)) != FX3D_OK) return r;
-    if ((r = launch_head<false>(stn_head(n.stn, 3, tmax, w.ntiles, T, stn), B, st)) != FX3D_OK) return r;
+    if ((r = launch_points(0, false, p, B, st)) != FX3D_OK) return r;
+    if ((r = launch_head(false, stn_head(n.stn, 3, tmax, w.ntiles, T, stn), B, st)) != FX3D_OK) return r;
     // input transform, conv_block1 (kept as h), fstn: the (64, 64) feature transform
     p.tf = T; p.c0 = n.block1; p.c1 = n.fstn.c1; p.c2 = n.fstn.c2; p.c3 = n.fstn.c3;
-    if ((r = launch_points<1>(p, B, st)) != FX3D_OK) return r;
-    if ((r = launch_head<false>(stn_head(n.fstn, 64, tmax, w.ntiles, F, fstn), B, st)) != FX3D_OK) return r;
+    if ((r = launch_points(1, false, p, B, st)) != FX3D_OK) return r;
+    if ((r = launch_head(false, stn_head(n.fstn, 64, tmax, w.ntiles, F, fstn), B, st)) != FX3D_OK) return r;
     // feature transform, feat, cls, softmax
     p.tf = F; p.c2 = n.f1; p.c3 = n.f2;
-    if ((r = launch_points<2>(p, B, st)) != FX3D_OK) return r;
+    if ((r = launch_points(2, false, p, B, st)) != FX3D_OK) return r;
     HeadArgs hd{};
     hd.tmax = tmax; hd.ntiles = w.ntiles;
     hd.d1 = n.fd1; hd.bn1 = n.fbn1; hd.d2 = n.fd2; hd.bn2 = n.fbn2; hd.d3 = n.cls;
     hd.n3 = num_classes; hd.K = 1; hd.pooled = pooled; hd.logits = lg; hd.probs = probs;
-    return launch_head<true>(hd, B, st);
+    return launch_head(true, hd, B, st);
 }
 
 }  // extern "C"

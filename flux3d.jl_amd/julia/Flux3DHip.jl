@@ -1589,6 +1589,34 @@ function pointnet_forward(m::PointNet, X::HipArray{Float32,3}; intermediates::Bo
 end
 (m::PointNet)(X::HipArray{Float32,3}) = pointnet_forward(m, X)
 
+# The gradients of sum(glogits .* logits) with respect to every parameter of m and to X (include/flux3d_hip.h "PointNet adjoint"):
+# test mode as pointnet_forward (running statistics, Dropout the identity).  glogits (num_classes, B) is the gradient with respect
+# to the LOGITS as pointnet_forward returns them, after cls's relu: the softmax stays with the caller.  The library runs the
+# forward again inside the call.  Returns (gflat, gx): gflat in the layout of pointnet_params(m) with zeros in the mu / sigma2
+# slots, gx (3, N, B) or nothing with input_grad = false.
+function pointnet_gradient(m::PointNet, X::HipArray{Float32,3}, glogits::HipArray{Float32,2}; input_grad::Bool = true)
+    size(X, 1) == 3 || error("PointNet takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    (N >= 1 && B >= 1) || error("PointNet needs at least one point and one cloud")
+    nc = size(_dense_wb(m.cls)[1], 1)
+    size(_dense_wb(m.fstn[12])[1], 1) == 64 * 64 ||
+        error("PointNet(num_classes, K) needs K = 64: conv_block1 has 64 output channels whatever K is (src/models/pointnet.jl:41-60)")
+    size(glogits) == (nc, B) || error("glogits must be ($nc, $B), got $(size(glogits))")
+    params = pointnet_params(m)
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_pointnet_grad_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(nc)::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    gflat = HipArray{Float32}(undef, length(params))
+    gx = input_grad ? HipArray{Float32}(undef, 3, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_pointnet_grad(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, X.ptr::Ptr{Cvoid}, Int32(N)::Int32, Int32(B)::Int32,
+                                        glogits.ptr::Ptr{Cvoid}, gflat.ptr::Ptr{Cvoid}, opt(gx)::Ptr{Cvoid}, C_NULL::Ptr{Cvoid},
+                                        C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid},
+                                        length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    return gflat, gx
+end
+
 # ---- DGCNN inference: (m::DGCNN)(X) (src/models/dgcnn.jl:113-147) in test mode --------------------------------------------
 # As for PointNet: the Flux layers' arrays flattened in forward order (include/flux3d_hip.h "DGCNN inference") on every call,
 # running statistics, Dropout as the identity.  An EdgeConv's mlp is a Chain of conv_bn_blocks, each a Chain(Conv, BatchNorm,

@@ -4,9 +4,9 @@
 include/flux3d_hip.h states the networks and their arithmetic ("PointNet inference", "DGCNN inference", "EdgeConv inference");
 this module owns the parameters (a name -> numpy array mapping in Flux's shapes), flattens them into the one device buffer
 fx3d_pointnet_forward / fx3d_dgcnn_forward / fx3d_edgeconv_forward reads, and checks every argument on the host before any
-launch.  PointNet is forward only.  EdgeConv has its input gradient and its parameter gradients, and DGCNN the gradients of the
-whole network with respect to every parameter and to the input points (``DGCNN.grad`` over fx3d_dgcnn_grad, "DGCNN adjoint"),
-all with BatchNorm in test mode."""
+launch.  EdgeConv has its input gradient and its parameter gradients, and DGCNN and PointNet the gradients of the
+whole network with respect to every parameter and to the input points (``DGCNN.grad`` over fx3d_dgcnn_grad, "DGCNN adjoint";
+``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode."""
 import ctypes as C
 
 import numpy as np
@@ -182,6 +182,67 @@ class _Model:
         return out if intermediates else out["probs"]
 
 
+    @staticmethod
+    def _like(a, name, shape, dtype, on_dev):
+        """An argument of a model's ``grad`` after its checks, with exactly ``shape`` (a trailing batch axis of 1 may be left out): a
+        device array, or a host array of ``dtype`` still to be uploaded.  It must live where ``X`` lives."""
+        ok = (shape,) + ((shape[:-1],) if shape[-1] == 1 else ())
+        what = "Float32" if dtype == np.float32 else "int32"
+        if is_device(a) != on_dev:
+            raise TypeError(f"{name} must live where X lives ({'the device' if on_dev else 'the host'})")
+        if on_dev:
+            if a.dtype != dtype:
+                raise TypeError(f"device {name} must be {what}, got {a.dtype}")
+            if tuple(a.shape) not in ok:
+                raise ValueError(f"{name} must be {shape}, got {tuple(a.shape)}")
+            return a.reshape(*shape)
+        a = np.asarray(a)
+        if dtype == np.int32:
+            if not np.issubdtype(a.dtype, np.integer):
+                raise TypeError(f"{name} must hold integers, got {a.dtype}")
+        elif not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise TypeError(f"{name} must hold real numbers, got {a.dtype}")
+        if a.shape not in ok:
+            raise ValueError(f"{name} must be {shape}, got {a.shape}")
+        return np.asfortranarray(a.reshape(shape, order="F").astype(dtype))
+
+    def _grad_views(self, gp, on_dev):
+        """The flat gradient ``gp`` (on the device) as a dict with the names and Flux shapes of the model's parameters, where
+        ``X`` lives: views of the flat buffer on the device, of its host copy otherwise."""
+        flat = None if on_dev else gp.to_host()
+        grads, at = {}, 0
+        for name, shape in self._shapes().items():
+            n = int(np.prod(shape))
+            if on_dev:  # a view of the flat buffer, which it keeps alive
+                grads[name] = DeviceArray(gp.ptr + 4 * at, shape, np.float32, owned=False, keep=gp)
+            else:
+                grads[name] = flat[at:at + n].reshape(shape, order="F")
+            at += n
+        return grads
+
+    def _labels(self, labels, B):
+        """``labels`` of ``crossentropy_grad`` after their checks: B integers in [0, num_classes)."""
+        y = np.asarray(labels)
+        if not np.issubdtype(y.dtype, np.integer):
+            raise TypeError(f"labels must hold integers, got {y.dtype}")
+        if y.shape != (B,):
+            raise ValueError(f"labels must be ({B},), got {y.shape}")
+        if y.size and (y.min() < 0 or y.max() >= self.num_classes):
+            raise ValueError(f"labels must be in [0, {self.num_classes}), got values from {y.min()} to {y.max()}")
+        return y
+
+    def _crossentropy(self, probs, y, B):
+        """``(loss, glogits)`` of ``Flux.crossentropy(probs, onehot(y))`` from the host copy of ``probs``: the loss
+        ``-mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) / Float32(B)``
+        with one Float32 subtraction and one Float32 division."""
+        cols = np.arange(B)
+        with np.errstate(divide="ignore"):
+            loss = float(-np.mean(np.log(probs[y, cols].astype(np.float64))))
+        onehot = np.zeros((self.num_classes, B), np.float32)
+        onehot[y, cols] = 1
+        return loss, np.asfortranarray(((probs - onehot).astype(np.float32) / np.float32(B)).astype(np.float32))
+
+
 class PointNet(_Model):
     """``PointNet(num_classes=10, K=64)`` (src/models/pointnet.jl:41-60).
 
@@ -189,7 +250,13 @@ class PointNet(_Model):
     fills one -- Glorot-uniform weights, zero biases, BatchNorm gamma = 1, beta = 0, mu = 0, sigma2 = 1 -- from a numpy
     generator seeded with ``seed``: the reference's draws come from Julia's global RNG and cannot be reproduced here.
     ``load(params)`` replaces them (a trained model's arrays) after shape checks.  They are uploaded once, at the first
-    forward after construction or ``load``, and the device copy is kept."""
+    forward after construction or ``load``, and the device copy is kept.
+
+    The network has its gradients, in test mode (BatchNorm's running statistics are constants, Dropout is the identity):
+    :meth:`grad` gives the gradient of ``sum(glogits * logits)`` with respect to every parameter and to the input points from
+    one library call (include/flux3d_hip.h "PointNet adjoint"), :meth:`flat_grad` the same as one flat buffer,
+    :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  Training-mode
+    BatchNorm (batch statistics) and Dropout in training mode are not differentiated."""
 
     _NAME, _COUNT_FN = "PointNet", "fx3d_pointnet_param_count"
 
@@ -215,6 +282,65 @@ class PointNet(_Model):
         return self._classify(clouds, "pointnet", (nc,), (N, B, nc), optional, intermediates)
 
     __call__ = forward
+
+    _MID = {"gstn": (3, 3), "gfstn": (64, 64), "gh": (64, None), "gxt": (3, None)}  # fx3d_pointnet_grad's optional outputs, in order
+
+    def _grad_call(self, X, glogits, input_grad, intermediates):
+        """fx3d_pointnet_grad after the argument checks: (the flat gradient, gx or None, the intermediates or None) on the
+        device, and whether ``X`` lives there."""
+        pts, N, B, on_dev = self._clouds(X, "stnKD(3)")
+        nc, f32 = self.num_classes, np.float32
+        nb = _lib.query_bytes("fx3d_pointnet_grad_workspace_bytes", N, B, nc)  # (the library's own size limits)
+        g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
+        if not on_dev:
+            g = DeviceArray.from_host(g)
+        x = self._on_device(pts, N, B, on_dev)
+        gp = DeviceArray.empty((self.param_count,), f32)
+        gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
+        mid = {k: DeviceArray.empty((r, N if c is None else c, B), f32) for k, (r, c) in self._MID.items()} if intermediates else None
+        ws = workspace(nb, tag="pointnet_grad")
+        _lib.call("fx3d_pointnet_grad", self._params_dev().ptr, nc, x.ptr, N, B, g.ptr, gp.ptr, gx.ptr if gx is not None else None,
+                  *(mid[k].ptr if mid else None for k in self._MID), ws.ptr, ws.nbytes, current_stream().handle)
+        return gp, gx, mid, on_dev
+
+    def flat_grad(self, X, glogits, input_grad=True, intermediates=False):
+        """``(gflat, gx)``: the gradient of ``sum(glogits * logits)`` with respect to the parameters as ONE flat Float32 buffer
+        with the layout of :meth:`flat_params` (the ``mu`` / ``sigma2`` slots are zero), and the gradient with respect to ``X``
+        (``None`` with ``input_grad=False``).  Arguments, ``intermediates`` and placement as :meth:`grad`."""
+        gp, gx, mid, on_dev = self._grad_call(X, glogits, input_grad, intermediates)
+        if not on_dev:
+            gp, gx = gp.to_host(), (None if gx is None else gx.to_host())
+            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
+        return (gp, gx, mid) if intermediates else (gp, gx)
+
+    def grad(self, X, glogits, input_grad=True, intermediates=False):
+        """``(grads, gx)``: the gradients of ``sum(glogits * logits)`` with respect to every parameter of the network and to
+        the points ``X``, test mode: include/flux3d_hip.h "PointNet adjoint".  ``X`` as in :meth:`forward`; ``glogits``
+        ``(num_classes, B)`` is the gradient with respect to the logits as :meth:`forward` returns them, after ``cls``'s relu
+        (the softmax stays with the caller, see :meth:`crossentropy_grad`).  The forward runs again inside the call.  ``grads``
+        has the names and Flux shapes of :func:`param_shapes` (on the device: views of one flat buffer); its ``mu`` /
+        ``sigma2`` entries are zero.  ``gx`` is ``(3, N, B)``, or ``None`` with ``input_grad=False``.  ``intermediates=True``:
+        ``(grads, gx, mid)`` with ``mid`` a dict of ``gstn`` (3, 3, B) and ``gfstn`` (64, 64, B), the gradients at the two
+        transforms, ``gh`` (64, N, B), the gradient at conv_block1's output, and ``gxt`` (3, N, B), the gradient at the
+        transformed points.  Everything lives where ``X`` lives."""
+        gp, gx, mid, on_dev = self._grad_call(X, glogits, input_grad, intermediates)
+        grads = self._grad_views(gp, on_dev)
+        if not on_dev:
+            gx = None if gx is None else gx.to_host()
+            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
+        return (grads, gx, mid) if intermediates else (grads, gx)
+
+    def crossentropy_grad(self, X, labels):
+        """``(loss, grads, gx)`` for ``Flux.crossentropy(m(X), onehot(labels))``, the mean over the batch: ``labels`` are B
+        integers in [0, num_classes), 0-based.  One :meth:`forward` for ``probs``, which are read back to the host; ``loss =
+        -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) / Float32(B)``
+        with one Float32 subtraction and one Float32 division, then :meth:`grad`, inside which the forward runs again."""
+        _, N, B, on_dev = self._clouds(X, "stnKD(3)")
+        y = self._labels(labels, B)
+        probs = self.forward(X)
+        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
+        grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits)
+        return loss, grads, gx
 
 
 class DGCNN(_Model):
@@ -264,30 +390,6 @@ class DGCNN(_Model):
     __call__ = forward
 
     _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
-
-    @staticmethod
-    def _like(a, name, shape, dtype, on_dev):
-        """An argument of :meth:`grad` after its checks, with exactly ``shape`` (a trailing batch axis of 1 may be left out): a
-        device array, or a host array of ``dtype`` still to be uploaded.  It must live where ``X`` lives."""
-        ok = (shape,) + ((shape[:-1],) if shape[-1] == 1 else ())
-        what = "Float32" if dtype == np.float32 else "int32"
-        if is_device(a) != on_dev:
-            raise TypeError(f"{name} must live where X lives ({'the device' if on_dev else 'the host'})")
-        if on_dev:
-            if a.dtype != dtype:
-                raise TypeError(f"device {name} must be {what}, got {a.dtype}")
-            if tuple(a.shape) not in ok:
-                raise ValueError(f"{name} must be {shape}, got {tuple(a.shape)}")
-            return a.reshape(*shape)
-        a = np.asarray(a)
-        if dtype == np.int32:
-            if not np.issubdtype(a.dtype, np.integer):
-                raise TypeError(f"{name} must hold integers, got {a.dtype}")
-        elif not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
-            raise TypeError(f"{name} must hold real numbers, got {a.dtype}")
-        if a.shape not in ok:
-            raise ValueError(f"{name} must be {shape}, got {a.shape}")
-        return np.asfortranarray(a.reshape(shape, order="F").astype(dtype))
 
     def _grad_call(self, X, glogits, fwd, input_grad, intermediates):
         """fx3d_dgcnn_grad after the argument checks: (the flat gradient, gx or None, gx2 and gx1 or None) on the device, and
@@ -344,15 +446,7 @@ class DGCNN(_Model):
         ``mid`` a dict of ``gx2`` (256, N, B) and ``gx1`` (64, N, B), the gradients at ``x2`` and ``x1``.  Everything lives where
         ``X`` lives."""
         gp, gx, mid, on_dev = self._grad_call(X, glogits, fwd, input_grad, intermediates)
-        flat = None if on_dev else gp.to_host()
-        grads, at = {}, 0
-        for name, shape in self._shapes().items():
-            n = int(np.prod(shape))
-            if on_dev:  # a view of the flat buffer, which it keeps alive
-                grads[name] = DeviceArray(gp.ptr + 4 * at, shape, np.float32, owned=False, keep=gp)
-            else:
-                grads[name] = flat[at:at + n].reshape(shape, order="F")
-            at += n
+        grads = self._grad_views(gp, on_dev)
         if not on_dev:
             gx = None if gx is None else gx.to_host()
             mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
@@ -364,21 +458,9 @@ class DGCNN(_Model):
         ``loss = -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) /
         Float32(B)`` with one Float32 subtraction and one Float32 division, then :meth:`grad` with that forward."""
         _, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
-        y = np.asarray(labels)
-        if not np.issubdtype(y.dtype, np.integer):
-            raise TypeError(f"labels must hold integers, got {y.dtype}")
-        if y.shape != (B,):
-            raise ValueError(f"labels must be ({B},), got {y.shape}")
-        if y.size and (y.min() < 0 or y.max() >= self.num_classes):
-            raise ValueError(f"labels must be in [0, {self.num_classes}), got values from {y.min()} to {y.max()}")
+        y = self._labels(labels, B)
         fwd = self.forward(X, intermediates=True)
-        probs = fwd["probs"].to_host() if on_dev else fwd["probs"]
-        cols = np.arange(B)
-        with np.errstate(divide="ignore"):
-            loss = float(-np.mean(np.log(probs[y, cols].astype(np.float64))))
-        onehot = np.zeros((self.num_classes, B), np.float32)
-        onehot[y, cols] = 1
-        glogits = np.asfortranarray(((probs - onehot).astype(np.float32) / np.float32(B)).astype(np.float32))
+        loss, glogits = self._crossentropy(fwd["probs"].to_host() if on_dev else fwd["probs"], y, B)
         grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits, fwd=fwd)
         return loss, grads, gx
 
@@ -555,13 +637,4 @@ class EdgeConv(_Model):
         bit for bit, or ``None`` with ``input_grad=False``.  ``X``, ``gout``, ``idx`` and ``out`` as in :meth:`input_grad`;
         everything lives where ``X`` lives."""
         gp, gx, on_dev = self._grad_call(X, gout, idx, out, input_grad)
-        flat = None if on_dev else gp.to_host()
-        grads, at = {}, 0
-        for name, shape in self._shapes().items():
-            n = int(np.prod(shape))
-            if on_dev:  # a view of the flat buffer, which it keeps alive
-                grads[name] = DeviceArray(gp.ptr + 4 * at, shape, np.float32, owned=False, keep=gp)
-            else:
-                grads[name] = flat[at:at + n].reshape(shape, order="F")
-            at += n
-        return grads, (gx if on_dev or gx is None else gx.to_host())
+        return self._grad_views(gp, on_dev), (gx if on_dev or gx is None else gx.to_host())

@@ -813,7 +813,8 @@ FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev(const int32_t *faces_padded
                                                      int32_t *faces_packed, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 /* ---- PointNet inference: (m::PointNet)(X) (src/models/pointnet.jl:62-85) in test mode -----------------------------
- * Forward only, Float32: BatchNorm uses its running statistics, Dropout is the identity.  x (3,N,B) device; point n of
+ * The forward (its gradients: "PointNet adjoint" below), Float32: BatchNorm uses its running statistics, Dropout is the identity.
+ * x (3,N,B) device; point n of
  * cloud b has channels x[:,n,b].  PointNet(num_classes, 64): the reference's conv_block1 is fixed at 64 channels, so no
  * other K works there (src/models/pointnet.jl:41-60).  In the order the layers run (stnKD: :3-20, conv_bn_block:
  * src/models/utils.jl:1-3):
@@ -1052,6 +1053,66 @@ FX3D_API fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classe
                                      const int32_t *idx1, const float *x1, const int32_t *idx2, const float *x2,
                                      const float *pooled, const float *glogits, float *gparams, float *gx, float *gx2, float *gx1,
                                      void *ws, size_t ws_bytes, fx3d_stream_t s);
+
+/* ---- PointNet adjoint: the gradients of (m::PointNet)(X) with respect to its parameters and to X, test mode -----------------------
+ * gparams = d sum(glogits . logits) / d params for logits = fx3d_pointnet_forward(x), a flat Float32 buffer with the layout of
+ * params_dev (fx3d_pointnet_param_count floats), and, if gx != NULL, gx (3,N,B) = the same derivative with respect to x.  The
+ * arguments up to B are the forward's.  glogits (num_classes,B) is the gradient at the LOGITS as the forward returns them, that is
+ * after cls's relu: the softmax stays with the caller, as for DGCNN.  Test mode throughout: BatchNorm's mu and var are constants
+ * (their slots are written as +0), gamma and beta are parameters, Dropout is the identity.  The call runs the forward's three
+ * rounds itself, into its workspace (the forward does not expose the transform nets' pooled vectors).  Optional outputs (NULL: kept
+ * in the workspace): gstn (3,3,B) and gfstn (64,64,B), the gradients at the two transforms; gh (64,N,B), the gradient at
+ * conv_block1's output h, both paths summed; gxt (3,N,B), the gradient at x T.
+ * Names are tests/pointnet_ref.py's (forward / stn_stage); sd = sqrtf(var + 1f-5); every operation is rounded to Float32; a chain
+ * is one fmaf accumulator from +0.0f over all terms in the stated order, a sum one accumulator of Float32 additions from +0.
+ *   relu:  passes the gradient where its OUTPUT is > 0 (Float32 compare; NaN passes nothing), else +0.
+ *   BatchNorm:  passes (g gamma) / sd.
+ *   conv or dense with relu, then BatchNorm (stn / fstn conv1..3 and dense2, feat.conv1, feat.dense1, feat.dense2):  forward
+ *     r = relu(z + b), y = gamma ((r - mu) / sd) + beta, upstream gy.   dbeta = sum gy;   dgamma = the chain of
+ *     fmaf(gy, (r - mu) / sd, acc);   d = r > 0 ? (gy gamma) / sd : +0;   db = sum d;   dW[c,o] = the chain of fmaf(a_in[c], d[o], acc)
+ *     (dense layers: fmaf(d[o], a_in[i], acc)).  Nothing divides by gamma.  feat.conv2 (BatchNorm only): the same with r = z + b
+ *     and no mask.  stn / fstn.dense1 (relu only): d = r > 0 ? g : +0.  dense3: d = g.  cls: d = logits > 0 ? glogits : +0.
+ *     conv_block1 (BatchNorm, then relu): "EdgeConv parameter adjoint"'s formulas verbatim from H[c,o] = the chain of
+ *     fmaf(x_t[c], d[o], acc) and h[o] = sum d[o], d = h > 0 ? gh : +0.
+ *   the way back through a layer:  the gradient at its input i = the chain over ALL its outputs o ascending of fmaf(d[o], W[i,o], acc)
+ *     (conv W[i,o] is W (Cin,Cout); dense W[o,i]).
+ *   maximum over the points, in each of the three rounds:  n*(c,b) = the smallest n whose activation EQUALS the round's pooled
+ *     value (Float32 ==, so -0 equals +0).  A NaN pooled value has no winner and passes nothing.  There is no "pooled > 0"
+ *     condition: in stn / fstn a channel whose relu is zero at every point still has a winner, the first point; its dbeta and dgamma
+ *     are then generally non-zero, its db and dW +0.  gy of conv3 is the head's gradient at the winner, and r the winner's.
+ *     Deviation from the reference: the note of "DGCNN adjoint" (NNlib and cuDNN cannot be consulted here) applies verbatim.
+ *   conv3's input gradient (feat: conv2's), the gather of "DGCNN adjoint":  per point the chain over the channels c it wins, c
+ *     ascending, of fmaf(d[c,b], W[i,c], acc); +0 for a point that wins nothing.
+ *   conv3's parameter sums run over the clouds that have a winner only, at the winner: one chain (sum) over b ascending.
+ *   transforms:  x_t[j,n] = sum_i x[i,n] T[i,j,b].   gT[i,j,b] = the chain over n of fmaf(x[i,n,b], gxt[j,n,b], acc);  the path into
+ *     x is the chain over j ascending of fmaf(gxt[j,n], T[i,j,b], acc).  The same for F with h and 64.  T[i,j,b] = d3[K i + j]: the
+ *     gradient at dense3's output is gT re-indexed.
+ *   sums of paths, one Float32 addition per element in this order:  gh = (the feat path through F) + (the fstn path);
+ *     gx = (gxt through T) + (the stn path).
+ * The order of every sum over points and clouds is part of the contract and depends on (N, B, num_classes) alone -- not on the
+ * device, the launch shape, the workspace or the run.  A tile is FX3D_POINTNET_GRAD_TILE = 64 consecutive points of one cloud (the
+ * last tile of a cloud may be shorter).
+ *   the convolutions below a round's last (stn / fstn conv1 and conv2, feat.conv1, conv_block1) and gT, gF:  per tile ONE chain
+ *     (sum) from +0 over the tile's points ascending; then one sum of Float32 additions from +0 over the tile values, b ascending,
+ *     within b the tiles ascending (gT and gF: over the tiles of cloud b).  The families are formed after the sums (conv_block1).
+ *   the dense layers and their BatchNorms, and the rounds' last convolutions:  one chain (sum) over b ascending.
+ *   (So a batch is not the sum of its clouds' separate results, and N > 64 is not one chain.)
+ * gparams, gx and the four optional outputs are bit-identical to the restatement tests/pointnet_grad_ref.py and from run to run:
+ * no float atomics, no scatter with more than one writer.
+ * Envelope, refusals, their order, status codes and messages are fx3d_pointnet_forward's: a NULL required pointer (params_dev, x,
+ * glogits, gparams, ws), num_classes outside [1, 2^20], N or B below 1, B above 65535, N B above 2^31, a short workspace or one not
+ * 256-byte aligned (fx3d_dgcnn_grad's alignment) is FX3D_ERR_INVALID_ARG; each comes before any device work.
+ * Launches on `s` only (the forward's five launches below the classifier's head; per round the head's adjoint, the trunk's
+ * adjoint, the last convolution's sums, the head's sums over the clouds, the chains over the tile partials), no host
+ * synchronisation, no host memory read after the argument check (graph-capturable).
+ * ws: fx3d_pointnet_grad_workspace_bytes(N, B, num_classes) -- h, T, F; per round and (tile, channel) the maximum, its first point
+ * and the BatchNorm's input there; the head's vectors; the last convolution's input rows at the winners (128,1024,B); one partial
+ * per tile and cloud; the feat path's gradient at h; gxt, gT and gF. */
+#define FX3D_POINTNET_GRAD_TILE 64 /* points of one cloud whose rows are summed as one chain ("PointNet adjoint") */
+FX3D_API fx3d_status fx3d_pointnet_grad_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, const float *x, int32_t N, int32_t B,
+                                        const float *glogits, float *gparams, float *gx, float *gstn, float *gfstn, float *gh,
+                                        float *gxt, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 #ifdef __cplusplus
 }
