@@ -72,6 +72,31 @@ inline Net layout(const float *params, int num_classes) {
     return n;
 }
 
+// ---- training mode (pointnet_train.hip): the 13 BatchNorms in forward order -- stn.bn1 .. bn4, conv_block1.bn, fstn.bn1 .. bn4,
+// feat.bn1 .. bn4 -- which is the order of their mu / sigma2 slots in the flat parameter buffer and of the statistics buffer
+// (flux3d_hip.h "PointNet training-mode forward": per BatchNorm mean (C) then variance (C)).  f(bn, C) for each of them.
+constexpr int kNumBn = 13;
+constexpr int kStatChannels = 2 * (64 + 128 + kFeat + 256) + 64 + 128 + kFeat + 512 + 256;  // 4928
+template <class NetT, class F>
+inline void for_each_bn(NetT &n, F f) {
+    auto stn = [&](auto &s) { f(s.c1.bn, 64); f(s.c2.bn, 128); f(s.c3.bn, kFeat); f(s.bn, 256); };
+    stn(n.stn);
+    f(n.block1.bn, 64);
+    stn(n.fstn);
+    f(n.f1.bn, 128); f(n.f2.bn, kFeat); f(n.fbn1, 512); f(n.fbn2, 256);
+}
+// the network whose BatchNorms read their mean and variance from a statistics buffer instead of the running values: the
+// test-mode kernels then evaluate every layer whose statistics are there in training mode
+inline Net with_batch_stats(Net n, const float *stats) {
+    size_t at = 0;
+    for_each_bn(n, [&](Bn &bn, int C) {
+        bn.m = stats + at;
+        bn.v = stats + at + C;
+        at += 2 * (size_t)C;
+    });
+    return n;
+}
+
 // the workspace: h (64, N, B) | per-tile maxima (1024, ntiles, B) | T (3, 3, B) | F (64, 64, B) | logits (num_classes, B)
 struct WsPlan { size_t h, tmax, T, F, logits, total; int ntiles; };
 inline WsPlan ws_plan(int N, int B, int nc) {

@@ -1,0 +1,463 @@
+// PointNet in training mode (gfx950), the forward: every BatchNorm normalises by the statistics of the current batch, Dropout
+// multiplies by a given mask, and the running statistics Flux would leave behind are returned.  include/flux3d_hip.h
+// ("PointNet training-mode forward") states the statistics, their orders and the running update; this file is how they are computed.
+//
+// A Bn holds four pointers and the test-mode kernels read the mean and the variance through bn.m / bn.v, so a layer whose batch
+// statistics exist IS the test-mode layer with m / v pointed at the statistics buffer (pointnet_net.h: with_batch_stats).  What is
+// new is producing the statistics in dependency order.  Per round (stn, fstn, feat) and BatchNorm L of the round:
+//   pointnet_stats_kernel<MODE, L>: the forward's tile (one block = 64 points of one cloud, the same LDS images, conv3 /
+//     conv_mfma for the layers below L with the statistics already known), then layer L's contraction; while its slab is in
+//     the accumulators, what the BatchNorm is given (before_bn) is summed per channel over the tile's valid rows in Float64,
+//     S1 = sum v and S2 = sum v v, and both are stored with plain stores to sums (2, C, ntiles, B).  Layer L itself goes nowhere else.
+//   pointnet_stat_finish_kernel: folds the tile sums of a layer over (tile, cloud) and writes the mean, the variance and the
+//     updated running statistics.
+//   then the forward's own pointnet_points_kernel<MODE> (launch_points) gives the per-tile maxima (and h in the fstn round).
+// The heads split at their BatchNorms, which need all B clouds: head_a (maxima, dense1, relu; stn / fstn: dense2, relu too),
+// feat only head_b (BatchNorm, dense2, relu, the dropout multiplier), head_c (BatchNorm, dense3 / cls, relu + softmax), with
+// pointnet_dense_stats_kernel in between: one thread per channel sums the (C, B) activations in ascending b.
+// No atomics anywhere: every sum has one owner and one order, which depends on (N, B) alone.
+#include <initializer_list>
+
+#include "pointnet_net.h"
+
+using namespace fx3d;
+using namespace fx3d::mlp;
+using namespace fx3d::mlp::pointnet;
+
+namespace {
+
+constexpr int kFinishGroups = FX3D_POINTNET_STAT_GROUPS;  // interleaved partial sums over (tile, cloud), the header's order
+constexpr int kFinishChannels = 16;                       // channels of one finishing block: 256 contiguous bytes per read
+constexpr int kFinishThreads = kFinishGroups * kFinishChannels;
+constexpr int kDenseStatThreads = 256;
+
+// one BatchNorm's statistics: where they go, and the running values they update
+struct StatOut {
+    const float *run_m, *run_v;  // the running mean and variance in the parameter buffer
+    float *mu, *var;             // the batch statistics buffer
+    float *new_m, *new_v;        // the updated running statistics, or NULL
+    float mtm;
+    long long m;                 // values per channel: N B after a convolution, B after a dense layer
+};
+
+// the header's "mean and variance" and "running statistics", for channel c with the sums S1, S2 over its m values
+__device__ __forceinline__ void finish_channel(const StatOut &o, int c, double S1, double S2) {
+    const double dm = (double)o.m;
+    const double mu64 = S1 / dm;
+    double v64 = S2 / dm - mu64 * mu64;
+    v64 = v64 < 0.0 ? 0.0 : v64;  // (a NaN stays)
+    const float mu = (float)mu64, var = (float)v64;
+    o.mu[c] = mu;
+    o.var[c] = var;
+    if (o.new_m) {
+        const float keep = 1.0f - o.mtm;
+        o.new_m[c] = (keep * o.run_m[c]) + (o.mtm * mu);
+        o.new_v[c] = (keep * o.run_v[c]) + (((o.mtm * (float)o.m) / (float)(o.m - 1)) * var);
+    }
+}
+
+// a tile's sums of one channel: the rows p of the tile with bit 2 of p equal to h are one chain in ascending p (what a lane
+// of half-wave h holds of a slab, mfma_row), and the tile's sum is chain(0) + chain(1)
+struct TileSum {
+    double s1 = 0.0, s2 = 0.0;
+    __device__ __forceinline__ void add(float v) {
+        const double d = (double)v;
+        s1 = s1 + d;
+        s2 = s2 + d * d;  // the product of two Float32 is exact in Float64
+    }
+};
+__device__ __forceinline__ void store_tile_sum(double *sums, int o, double s1, double s2) {
+    sums[2 * o] = s1;
+    sums[2 * o + 1] = s2;
+}
+
+// layer L = a convolution on the MFMA: conv_mfma's slabs with the statistics epilogue.  sums: the tile's (2, cout).
+template <int CIN, int EPI>
+__device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const float *__restrict__ W, const float *__restrict__ bias,
+                                               int nvalid, double *__restrict__ sums) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const float *a0 = in + j * kLd + h, *a1 = a0 + 32 * kLd;
+    for (int sl = wave; sl < cout / 32; sl += kPtThreads / 64) {
+        const int o = sl * 32 + j;
+        f32x16 acc0 = {0}, acc1 = {0};
+        mfma_slab<CIN>(a0, a1, W + (size_t)CIN * o, h, acc0, acc1);
+        const float bi = bias[o];
+        TileSum t;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (mfma_row(r, h) < nvalid) t.add(before_bn<EPI>(acc0[r], bi));
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (mfma_row(r, h) + 32 < nvalid) t.add(before_bn<EPI>(acc1[r], bi));
+        const double o1 = __shfl_xor(t.s1, 32, 64), o2 = __shfl_xor(t.s2, 32, 64);
+        if (h == 0) store_tile_sum(sums, o, t.s1 + o1, t.s2 + o2);
+    }
+}
+
+// layer L = a convolution of 3 input channels (conv3's chain) to 64: waves 0 and 1 are the two chains of a channel
+template <int EPI>
+__device__ __forceinline__ void conv_stat3(const float *xs, const float *__restrict__ W, const float *__restrict__ bias, int nvalid,
+                                           double *__restrict__ sums) {
+    __shared__ double other[2][64];
+    const int o = threadIdx.x & 63, h = threadIdx.x >> 6;
+    TileSum t;
+    if (h < 2) {
+        const float w0 = W[3 * o], w1 = W[3 * o + 1], w2 = W[3 * o + 2], bi = bias[o];
+        for (int q = 0; q < 8; ++q)
+            for (int i = 0; i < 4; ++i) {
+                const int p = 8 * q + 4 * h + i;
+                if (p >= nvalid) continue;
+                float acc = 0.0f;
+                acc = fmaf(xs[p * 3 + 0], w0, acc);
+                acc = fmaf(xs[p * 3 + 1], w1, acc);
+                acc = fmaf(xs[p * 3 + 2], w2, acc);
+                t.add(before_bn<EPI>(acc, bi));
+            }
+    }
+    if (h == 1) { other[0][o] = t.s1; other[1][o] = t.s2; }
+    __syncthreads();
+    if (h == 0) store_tile_sum(sums, o, t.s1 + other[0][o], t.s2 + other[1][o]);
+}
+
+struct StatArgs {
+    PointArgs p;
+    double *sums;  // (2, C, ntiles, B) for the C channels of the layer
+};
+
+// the round's BatchNorms in the order they run: MODE 0 (stn) bn1, bn2, bn3; MODE 1 (fstn) conv_block1.bn, bn1, bn2, bn3;
+// MODE 2 (feat) bn1, bn2.  The layers below L are pointnet_points_kernel<MODE>'s, call for call (h is not written here).
+template <int MODE, int L>
+__global__ __launch_bounds__(kPtThreads) void pointnet_stats_kernel(const StatArgs s) {
+    const PointArgs &a = s.p;
+    extern __shared__ float lds[];
+    float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
+    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int p0 = tile * kTile;
+    const int nvalid = min(kTile, a.N - p0);
+    constexpr int C = (MODE == 0 ? (L == 0 ? 64 : L == 1 ? 128 : kFeat)
+                       : MODE == 1 ? (L <= 1 ? 64 : L == 2 ? 128 : kFeat) : (L == 0 ? 128 : kFeat));
+    double *sums = s.sums + 2 * ((size_t)b * a.ntiles + tile) * C;
+    if (MODE != 2) {
+        const float *xb = a.x + ((size_t)b * a.N + p0) * 3;
+        for (int i = tid; i < kTile * 3; i += kPtThreads) xs[i] = i < nvalid * 3 ? xb[i] : 0.0f;
+    } else {
+        const float *hb = a.h + ((size_t)b * a.N + p0) * 64;
+        for (int i = tid; i < kTile * 64; i += kPtThreads) bufA[(i >> 6) * kLd + (i & 63)] = i < nvalid * 64 ? hb[i] : 0.0f;
+    }
+    __syncthreads();
+    if (MODE == 0) {
+        if (L == 0) { conv_stat3<kReluBn>(xs, a.c1.W, a.c1.b, nvalid, sums); return; }
+        conv3<kReluBn>(xs, bufA, kLd, 64, a.c1.W, a.c1.b, a.c1.bn);
+        __syncthreads();
+        if (L == 1) { conv_stat_mfma<64, kReluBn>(bufA, 128, a.c2.W, a.c2.b, nvalid, sums); return; }
+        conv_mfma<64, kReluBn, false>(bufA, bufB, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_stat_mfma<128, kReluBn>(bufB, kFeat, a.c3.W, a.c3.b, nvalid, sums);
+    } else if (MODE == 1) {
+        conv3<kNone>(xs, xt, 3, 3, a.tf + (size_t)b * 9, nullptr, Bn{});
+        __syncthreads();
+        if (L == 0) { conv_stat3<kBnRelu>(xt, a.c0.W, a.c0.b, nvalid, sums); return; }
+        conv3<kBnRelu>(xt, bufA, kLd, 64, a.c0.W, a.c0.b, a.c0.bn);
+        __syncthreads();
+        if (L == 1) { conv_stat_mfma<64, kReluBn>(bufA, 64, a.c1.W, a.c1.b, nvalid, sums); return; }
+        conv_mfma<64, kReluBn, false>(bufA, bufB, 64, a.c1.W, a.c1.b, a.c1.bn, nvalid, nullptr);
+        __syncthreads();
+        if (L == 2) { conv_stat_mfma<64, kReluBn>(bufB, 128, a.c2.W, a.c2.b, nvalid, sums); return; }
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_stat_mfma<128, kReluBn>(bufA, kFeat, a.c3.W, a.c3.b, nvalid, sums);
+    } else {
+        conv_mfma<64, kNone, false>(bufA, bufB, 64, a.tf + (size_t)b * 4096, nullptr, Bn{}, nvalid, nullptr);
+        __syncthreads();
+        if (L == 0) { conv_stat_mfma<64, kReluBn>(bufB, 128, a.c2.W, a.c2.b, nvalid, sums); return; }
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        conv_stat_mfma<128, kBnOnly>(bufA, kFeat, a.c3.W, a.c3.b, nvalid, sums);
+    }
+}
+
+// Folds sums (2, C, T) over the T = ntiles B tile sums t = tile + ntiles b of a layer: kFinishGroups chains, chain g over
+// t = g, g + kFinishGroups, ... ascending from +0.0, then the chains in ascending g from +0.0.  One block = 16 channels.
+__global__ __launch_bounds__(kFinishThreads) void pointnet_stat_finish_kernel(const double *__restrict__ sums, int C, long long T,
+                                                                            const StatOut o) {
+    __shared__ double p1[kFinishGroups][kFinishChannels], p2[kFinishGroups][kFinishChannels];
+    const int cl = threadIdx.x % kFinishChannels, g = threadIdx.x / kFinishChannels;
+    const int c = blockIdx.x * kFinishChannels + cl;  // C is a multiple of 16
+    double s1 = 0.0, s2 = 0.0;
+    for (long long t = g; t < T; t += kFinishGroups) {
+        const double *at = sums + 2 * ((size_t)t * C + c);
+        s1 = s1 + at[0];
+        s2 = s2 + at[1];
+    }
+    p1[g][cl] = s1;
+    p2[g][cl] = s2;
+    __syncthreads();
+    if (g != 0) return;
+    s1 = 0.0; s2 = 0.0;
+    for (int k = 0; k < kFinishGroups; ++k) {
+        s1 = s1 + p1[k][cl];
+        s2 = s2 + p2[k][cl];
+    }
+    finish_channel(o, c, s1, s2);
+}
+
+// a dense BatchNorm: thread c sums channel c of act (C, B) over the clouds in ascending b from +0.0, and finishes it
+__global__ __launch_bounds__(kDenseStatThreads) void pointnet_dense_stats_kernel(const float *__restrict__ act, int C, int B,
+                                                                               const StatOut o) {
+    const int c = blockIdx.x * kDenseStatThreads + threadIdx.x;  // C is a multiple of 256
+    TileSum t;
+#pragma unroll 8
+    for (int b = 0; b < B; ++b) t.add(act[(size_t)b * C + c]);
+    finish_channel(o, c, t.s1, t.s2);
+}
+
+struct TrainHeadArgs {
+    HeadArgs h;            // the test-mode head's arguments, bn1 / bn2 at the batch statistics
+    float *a1, *a2;        // workspace: relu(dense1) (512, B), FEAT only; relu(dense2) [times the dropout multiplier] (256, B)
+    const float *dropout;  // FEAT: (256, B) multipliers or NULL
+};
+
+// up to the head's first BatchNorm: MaxPool, relu(dense1); stn / fstn have no BatchNorm there and go on through relu(dense2)
+template <bool FEAT>
+__global__ __launch_bounds__(kHeadThreads) void pointnet_train_head_a_kernel(const TrainHeadArgs t) {
+    const HeadArgs &a = t.h;
+    __shared__ float v0[kFeat], v1[512];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float m = fold_tile_maxima(a.tmax, a.ntiles, b);
+    v0[tid] = m;
+    if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + tid] = m;
+    __syncthreads();
+    if (tid < 512) {
+        const float v = relu(dense_chain(v0, kFeat, a.d1.W, 512, tid) + a.d1.b[tid]);
+        if (FEAT) t.a1[(size_t)b * 512 + tid] = v;
+        else v1[tid] = v;
+    }
+    if (FEAT) return;
+    __syncthreads();
+    if (tid < 256) t.a2[(size_t)b * 256 + tid] = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
+}
+
+// feat: BatchNorm(512) at the batch statistics, relu(dense2), the dropout multiplier
+__global__ __launch_bounds__(512) void pointnet_train_head_b_kernel(const TrainHeadArgs t) {
+    const HeadArgs &a = t.h;
+    __shared__ float v1[512];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    v1[tid] = batchnorm(t.a1[(size_t)b * 512 + tid], a.bn1.g[tid], a.bn1.b[tid], a.bn1.m[tid], sqrtf(a.bn1.v[tid] + kBnEps));
+    __syncthreads();
+    if (tid < 256) {
+        float v = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
+        if (t.dropout) v = v * t.dropout[(size_t)b * 256 + tid];
+        t.a2[(size_t)b * 256 + tid] = v;
+    }
+}
+
+// BatchNorm(256) at the batch statistics, then the test-mode head's end: dense3 as the transposed (K, K) matrix, or cls,
+// relu and the softmax
+template <bool FEAT>
+__global__ __launch_bounds__(kHeadThreads) void pointnet_train_head_c_kernel(const TrainHeadArgs t) {
+    const HeadArgs &a = t.h;
+    __shared__ float v2[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid < 256)
+        v2[tid] = batchnorm(t.a2[(size_t)b * 256 + tid], a.bn2.g[tid], a.bn2.b[tid], a.bn2.m[tid], sqrtf(a.bn2.v[tid] + kBnEps));
+    __syncthreads();
+    for (int o = tid; o < a.n3; o += kHeadThreads) {
+        const float v = dense_chain(v2, 256, a.d3.W, a.n3, o) + a.d3.b[o];
+        if (FEAT) {
+            a.logits[(size_t)b * a.n3 + o] = relu(v);
+        } else {
+            const size_t at = (size_t)b * a.n3 + (o / a.K) + (size_t)a.K * (o % a.K);
+            a.mat[at] = v;
+            if (a.mat_user) a.mat_user[at] = v;
+        }
+    }
+    if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
+}
+
+template <int MODE, int L>
+fx3d_status launch_stats_of(const StatArgs &s, int B, bool last, hipStream_t st) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&pointnet_stats_kernel<MODE, L>), (int)kPtLds,
+                                              "pointnet_stats_kernel");
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof(last ? "pointnet_train_stats_last" : "pointnet_train_stats", st);
+    hipLaunchKernelGGL((pointnet_stats_kernel<MODE, L>), dim3(s.p.ntiles, B), dim3(kPtThreads), kPtLds, st, s);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+// BatchNorm L of round `mode`; `last`: the round's 1024-channel layer (a label of its own in the library's profile)
+fx3d_status launch_stats(int mode, int L, const StatArgs &s, int B, hipStream_t st) {
+    switch (mode * 4 + L) {
+        case 0: return launch_stats_of<0, 0>(s, B, false, st);
+        case 1: return launch_stats_of<0, 1>(s, B, false, st);
+        case 2: return launch_stats_of<0, 2>(s, B, true, st);
+        case 4: return launch_stats_of<1, 0>(s, B, false, st);
+        case 5: return launch_stats_of<1, 1>(s, B, false, st);
+        case 6: return launch_stats_of<1, 2>(s, B, false, st);
+        case 7: return launch_stats_of<1, 3>(s, B, true, st);
+        case 8: return launch_stats_of<2, 0>(s, B, false, st);
+        default: return launch_stats_of<2, 1>(s, B, true, st);
+    }
+}
+
+fx3d_status launch_finish(const double *sums, int C, long long T, const StatOut &o, hipStream_t st) {
+    ProfileScope prof("pointnet_train_finish", st);
+    hipLaunchKernelGGL(pointnet_stat_finish_kernel, dim3(C / kFinishChannels), dim3(kFinishThreads), 0, st, sums, C, T, o);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+fx3d_status launch_dense_stats(const float *act, int C, int B, const StatOut &o, hipStream_t st) {
+    ProfileScope prof("pointnet_train_dense_stats", st);
+    hipLaunchKernelGGL(pointnet_dense_stats_kernel, dim3(C / kDenseStatThreads), dim3(kDenseStatThreads), 0, st, act, C, B, o);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+// part 0 = head_a, 1 = head_b (feat), 2 = head_c
+fx3d_status launch_train_head(int part, bool feat, const TrainHeadArgs &t, int B, hipStream_t st) {
+    ProfileScope prof("pointnet_train_head", st);
+    if (part == 0) {
+        if (feat) hipLaunchKernelGGL(pointnet_train_head_a_kernel<true>, dim3(B), dim3(kHeadThreads), 0, st, t);
+        else hipLaunchKernelGGL(pointnet_train_head_a_kernel<false>, dim3(B), dim3(kHeadThreads), 0, st, t);
+    } else if (part == 1) {
+        hipLaunchKernelGGL(pointnet_train_head_b_kernel, dim3(B), dim3(512), 0, st, t);
+    } else {
+        if (feat) hipLaunchKernelGGL(pointnet_train_head_c_kernel<true>, dim3(B), dim3(kHeadThreads), 0, st, t);
+        else hipLaunchKernelGGL(pointnet_train_head_c_kernel<false>, dim3(B), dim3(kHeadThreads), 0, st, t);
+    }
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+// the forward's workspace, then the tile sums of the widest layer, relu(dense1) of feat and relu(dense2) of every head
+struct TrainPlan { WsPlan fwd; size_t sums, a1, a2, total; };
+TrainPlan train_plan(int N, int B, int nc) {
+    TrainPlan t;
+    t.fwd = ws_plan(N, B, nc);
+    WsBump ws;
+    ws.at = t.fwd.total;
+    t.sums = ws.put((size_t)2 * kFeat * t.fwd.ntiles * B * sizeof(double));
+    t.a1 = ws.put((size_t)512 * B * sizeof(float));
+    t.a2 = ws.put((size_t)256 * B * sizeof(float));
+    t.total = ws.at;
+    return t;
+}
+
+fx3d_status check_train_sizes(const char *fn, int32_t N, int32_t B, int32_t nc) {
+    const fx3d_status rc = check_sizes(fn, N, B, nc);
+    if (rc != FX3D_OK) return rc;
+    FX3D_REQUIRE(B >= 2, "%s: training-mode BatchNorm needs B >= 2 clouds (a Dense BatchNorm's running variance divides by B - 1), got %d",
+                 fn, B);
+    return FX3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+fx3d_status fx3d_pointnet_stat_count(int64_t *count) {
+    FX3D_REQUIRE(count != nullptr, "fx3d_pointnet_stat_count: count is NULL");
+    *count = 2 * kStatChannels;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_pointnet_train_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes) {
+    FX3D_REQUIRE(bytes != nullptr, "fx3d_pointnet_train_workspace_bytes: bytes is NULL");
+    const fx3d_status rc = check_train_sizes("fx3d_pointnet_train_workspace_bytes", N, B, num_classes);
+    if (rc != FX3D_OK) return rc;
+    *bytes = train_plan(N, B, num_classes).total;
+    return FX3D_OK;
+}
+
+fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_classes, const float *x, int32_t N, int32_t B,
+                                        const float *dropout, float momentum, float *probs, float *logits, float *stn, float *fstn,
+                                        float *pooled, float *batch_stats, float *running, void *ws, size_t ws_bytes,
+                                        fx3d_stream_t s) {
+    const char *fn = "fx3d_pointnet_forward_train";
+    FX3D_REQUIRE(params_dev && x && probs && batch_stats && ws, "%s: params_dev, x, probs, batch_stats and ws must not be NULL", fn);
+    const fx3d_status rc = check_train_sizes(fn, N, B, num_classes);
+    if (rc != FX3D_OK) return rc;
+    FX3D_REQUIRE(std::isfinite(momentum) && momentum >= 0.0f && momentum <= 1.0f, "%s: momentum must be finite and in [0, 1], got %g",
+                 fn, (double)momentum);
+    const TrainPlan tp = train_plan(N, B, num_classes);
+    const WsPlan &w = tp.fwd;
+    FX3D_REQUIRE(ws_bytes >= tp.total, "%s: workspace of %zu bytes, fx3d_pointnet_train_workspace_bytes says %zu", fn, ws_bytes,
+                 tp.total);
+    FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", fn);
+    const Net run = layout(params_dev, num_classes);  // the running statistics, read for `running` alone
+    const Net n = with_batch_stats(run, batch_stats);
+    // the 13 BatchNorms in forward order: their slots of the statistics buffers and their running values
+    StatOut so[kNumBn];
+    {
+        int i = 0;
+        size_t at = 0;
+        for_each_bn(run, [&](const Bn &bn, int C) {
+            so[i].run_m = bn.m; so[i].run_v = bn.v;
+            so[i].mu = batch_stats + at; so[i].var = batch_stats + at + C;
+            so[i].new_m = running ? running + at : nullptr; so[i].new_v = running ? running + at + C : nullptr;
+            so[i].mtm = momentum;
+            so[i].m = (long long)N * B;
+            at += 2 * (size_t)C;
+            ++i;
+        });
+        for (int k : {3, 8, 11, 12}) so[k].m = B;  // the BatchNorms after a dense layer
+    }
+    hipStream_t st = as_stream(s);
+    char *wsb = static_cast<char *>(ws);
+    float *h = reinterpret_cast<float *>(wsb + w.h), *tmax = reinterpret_cast<float *>(wsb + w.tmax);
+    float *T = reinterpret_cast<float *>(wsb + w.T), *F = reinterpret_cast<float *>(wsb + w.F);
+    float *lg = logits ? logits : reinterpret_cast<float *>(wsb + w.logits);
+    double *sums = reinterpret_cast<double *>(wsb + tp.sums);
+    float *a1 = reinterpret_cast<float *>(wsb + tp.a1), *a2 = reinterpret_cast<float *>(wsb + tp.a2);
+    const long long ntl = (long long)w.ntiles * B;
+
+    StatArgs sa{};
+    PointArgs &p = sa.p;
+    sa.sums = sums;
+    p.x = x; p.h = h; p.tmax = tmax; p.N = N; p.ntiles = w.ntiles;
+    fx3d_status r;
+    // the round's point BatchNorms in order (slot `first` on, widths C[]), then the round's closing full pass
+    auto run_round = [&](int mode, int first, std::initializer_list<int> widths) -> fx3d_status {
+        int L = 0;
+        for (int C : widths) {
+            if ((r = launch_stats(mode, L, sa, B, st)) != FX3D_OK) return r;
+            if ((r = launch_finish(sums, C, ntl, so[first + L], st)) != FX3D_OK) return r;
+            ++L;
+        }
+        return launch_points(mode, false, p, B, st);
+    };
+    // a stn / fstn head: relu(dense2), its BatchNorm's statistics, the (K, K) matrix
+    auto stn_heads = [&](const Stn &sn, int K, int slot, float *mat, float *mat_user) -> fx3d_status {
+        TrainHeadArgs t{};
+        t.h = stn_head(sn, K, tmax, w.ntiles, mat, mat_user);
+        t.a2 = a2;
+        if ((r = launch_train_head(0, false, t, B, st)) != FX3D_OK) return r;
+        if ((r = launch_dense_stats(a2, 256, B, so[slot], st)) != FX3D_OK) return r;
+        return launch_train_head(2, false, t, B, st);
+    };
+    // stn: the (3, 3) input transform of every cloud
+    p.c1 = n.stn.c1; p.c2 = n.stn.c2; p.c3 = n.stn.c3;
+    if ((r = run_round(0, 0, {64, 128, kFeat})) != FX3D_OK) return r;
+    if ((r = stn_heads(n.stn, 3, 3, T, stn)) != FX3D_OK) return r;
+    // input transform, conv_block1 (kept as h by the closing pass), fstn: the (64, 64) feature transform
+    p.tf = T; p.c0 = n.block1; p.c1 = n.fstn.c1; p.c2 = n.fstn.c2; p.c3 = n.fstn.c3;
+    if ((r = run_round(1, 4, {64, 64, 128, kFeat})) != FX3D_OK) return r;
+    if ((r = stn_heads(n.fstn, 64, 8, F, fstn)) != FX3D_OK) return r;
+    // feature transform, feat, cls, softmax
+    p.tf = F; p.c2 = n.f1; p.c3 = n.f2;
+    if ((r = run_round(2, 9, {128, kFeat})) != FX3D_OK) return r;
+    TrainHeadArgs t{};
+    HeadArgs &hd = t.h;
+    hd.tmax = tmax; hd.ntiles = w.ntiles;
+    hd.d1 = n.fd1; hd.bn1 = n.fbn1; hd.d2 = n.fd2; hd.bn2 = n.fbn2; hd.d3 = n.cls;
+    hd.n3 = num_classes; hd.K = 1; hd.pooled = pooled; hd.logits = lg; hd.probs = probs;
+    t.a1 = a1; t.a2 = a2; t.dropout = dropout;
+    if ((r = launch_train_head(0, true, t, B, st)) != FX3D_OK) return r;
+    if ((r = launch_dense_stats(a1, 512, B, so[11], st)) != FX3D_OK) return r;
+    if ((r = launch_train_head(1, true, t, B, st)) != FX3D_OK) return r;
+    if ((r = launch_dense_stats(a2, 256, B, so[12], st)) != FX3D_OK) return r;
+    return launch_train_head(2, true, t, B, st);
+}
+
+}  // extern "C"

@@ -1589,6 +1589,49 @@ function pointnet_forward(m::PointNet, X::HipArray{Float32,3}; intermediates::Bo
 end
 (m::PointNet)(X::HipArray{Float32,3}) = pointnet_forward(m, X)
 
+# The same network in TRAINING mode (include/flux3d_hip.h "PointNet training-mode forward"): every BatchNorm normalises by the
+# statistics of the current batch, `dropout` is nothing (the identity) or the (256, B) multipliers of feat's Dropout(0.4), and
+# the running statistics Flux's BatchNorm would hold after the step come back as one flat buffer.  The parameters are flattened as
+# for pointnet_forward; their μ / σ² are the running statistics and are not written.  batch_stats and running have
+# pointnet_stat_count() floats: per BatchNorm in forward order μ (C), then σ² (C).  B >= 2.
+function pointnet_stat_count()
+    cnt = Ref{Int64}(0)
+    check(@ccall LIB.fx3d_pointnet_stat_count(cnt::Ref{Int64})::Int32)
+    return Int(cnt[])
+end
+function pointnet_forward_train(m::PointNet, X::HipArray{Float32,3}; dropout::Union{Nothing,HipArray{Float32,2}} = nothing,
+                                momentum::Real = 0.1f0, intermediates::Bool = false)
+    size(X, 1) == 3 || error("PointNet takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    (N >= 1 && B >= 2) || error("PointNet in training mode needs at least one point and two clouds")
+    nc = size(_dense_wb(m.cls)[1], 1)
+    size(_dense_wb(m.fstn[12])[1], 1) == 64 * 64 ||
+        error("PointNet(num_classes, K) needs K = 64: conv_block1 has 64 output channels whatever K is (src/models/pointnet.jl:41-60)")
+    (dropout === nothing || size(dropout) == (256, B)) || error("dropout must be (256, $B), got $(size(dropout))")
+    params = pointnet_params(m)
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_pointnet_train_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(nc)::Int32, nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    nstat = pointnet_stat_count()
+    probs = HipArray{Float32}(undef, nc, B)
+    batch_stats = HipArray{Float32}(undef, nstat)
+    running = HipArray{Float32}(undef, nstat)
+    logits = intermediates ? HipArray{Float32}(undef, nc, B) : nothing
+    stn = intermediates ? HipArray{Float32}(undef, 3, 3, B) : nothing
+    fstn = intermediates ? HipArray{Float32}(undef, 64, 64, B) : nothing
+    pooled = intermediates ? HipArray{Float32}(undef, 1024, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_pointnet_forward_train(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, X.ptr::Ptr{Cvoid}, Int32(N)::Int32,
+                                                 Int32(B)::Int32, opt(dropout)::Ptr{Cvoid}, Float32(momentum)::Float32,
+                                                 probs.ptr::Ptr{Cvoid}, opt(logits)::Ptr{Cvoid}, opt(stn)::Ptr{Cvoid},
+                                                 opt(fstn)::Ptr{Cvoid}, opt(pooled)::Ptr{Cvoid}, batch_stats.ptr::Ptr{Cvoid},
+                                                 running.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                                 DEFAULT_STREAM::Stream)::Int32)
+    return intermediates ? (probs = probs, logits = logits, stn = stn, fstn = fstn, pooled = pooled, batch_stats = batch_stats,
+                            running = running) : (probs = probs, batch_stats = batch_stats, running = running)
+end
+
 # The gradients of sum(glogits .* logits) with respect to every parameter of m and to X (include/flux3d_hip.h "PointNet adjoint"):
 # test mode as pointnet_forward (running statistics, Dropout the identity).  glogits (num_classes, B) is the gradient with respect
 # to the LOGITS as pointnet_forward returns them, after cls's relu: the softmax stays with the caller.  The library runs the

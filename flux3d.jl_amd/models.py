@@ -6,7 +6,8 @@ this module owns the parameters (a name -> numpy array mapping in Flux's shapes)
 fx3d_pointnet_forward / fx3d_dgcnn_forward / fx3d_edgeconv_forward reads, and checks every argument on the host before any
 launch.  EdgeConv has its input gradient and its parameter gradients, and DGCNN and PointNet the gradients of the
 whole network with respect to every parameter and to the input points (``DGCNN.grad`` over fx3d_dgcnn_grad, "DGCNN adjoint";
-``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode."""
+``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode.  PointNet also has its
+training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_train, "PointNet training-mode forward")."""
 import ctypes as C
 
 import numpy as np
@@ -255,8 +256,9 @@ class PointNet(_Model):
     The network has its gradients, in test mode (BatchNorm's running statistics are constants, Dropout is the identity):
     :meth:`grad` gives the gradient of ``sum(glogits * logits)`` with respect to every parameter and to the input points from
     one library call (include/flux3d_hip.h "PointNet adjoint"), :meth:`flat_grad` the same as one flat buffer,
-    :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  Training-mode
-    BatchNorm (batch statistics) and Dropout in training mode are not differentiated."""
+    :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  The training-mode
+    forward -- BatchNorm at the batch statistics, Dropout as a given mask, the updated running statistics -- is
+    :meth:`forward_train` (include/flux3d_hip.h "PointNet training-mode forward"); it is not differentiated yet."""
 
     _NAME, _COUNT_FN = "PointNet", "fx3d_pointnet_param_count"
 
@@ -282,6 +284,94 @@ class PointNet(_Model):
         return self._classify(clouds, "pointnet", (nc,), (N, B, nc), optional, intermediates)
 
     __call__ = forward
+
+    @staticmethod
+    def dropout_mask(B, seed, p=0.4):
+        """The multipliers ``(256, B)`` Float32 of ``Dropout(p)`` in training mode for :meth:`forward_train`, from a numpy
+        generator seeded with ``seed``: Flux's ``rand > p ? T(1 / (1 - p)) : 0`` per entry, so every entry is 0 or
+        ``np.float32(1.0 / (1.0 - p))`` (bits 0x3FD55555 for p = 0.4).  The draws are numpy's, not Julia's."""
+        if not 0.0 <= float(p) < 1.0:
+            raise ValueError(f"p must be in [0, 1), got {p}")
+        if int(B) < 1:
+            raise ValueError(f"B must be positive, got {B}")
+        u = np.random.default_rng(seed).random((256, int(B)))
+        return np.asfortranarray(np.where(u > p, np.float32(1.0 / (1.0 - float(p))), np.float32(0.0)).astype(np.float32))
+
+    def _stat_slots(self):
+        """(BatchNorm name, C, offset in the statistics layout, offset of its ``mu`` in the flat parameter buffer) for the 13
+        BatchNorms in forward order; in both buffers ``sigma2`` (C) follows ``mu`` (C) directly."""
+        slots, at, flat = [], 0, 0
+        for name, shape in self._shapes().items():
+            if name.endswith(".mu"):
+                slots.append((name[:-3], shape[0], at, flat))
+                at += 2 * shape[0]
+            flat += int(np.prod(shape))
+        return slots
+
+    def forward_train(self, X, dropout=None, momentum=0.1, update=False, intermediates=False):
+        """Class probabilities ``(num_classes, B)`` of the clouds ``X`` (as in :meth:`forward`, at least two clouds) with the
+        network in TRAINING mode: include/flux3d_hip.h "PointNet training-mode forward".  Every BatchNorm normalises by the
+        mean and uncorrected variance of the current batch; ``dropout`` is ``None`` (the identity), a ``(256, B)`` array of
+        multipliers for the output of ``feat``'s ``Dense(512, 256, relu)`` (numpy, or a device array beside a device ``X``), or an ``int`` seed for
+        :meth:`dropout_mask`.  ``intermediates=True``: a dict with ``probs``, ``logits``, ``stn``, ``fstn``, ``pooled`` as
+        :meth:`forward` gives them, ``batch_stats`` and ``running``: dicts name -> array with the ``...bnK.mu`` / ``.sigma2``
+        names of :func:`param_shapes`, the batch statistics and the running statistics Flux's BatchNorm would hold after this
+        step (``momentum``; computed from the model's ``mu`` / ``sigma2``).  Everything lives where ``X`` lives.
+        ``update=True`` writes ``running`` into the model's parameters, on the host (which reads them back: not inside a graph
+        capture) and in the kept device copy: the next :meth:`forward` is the test-mode network after one training step's worth
+        of statistics.  The gradient of this forward is not built."""
+        pts, N, B, on_dev = self._clouds(X, "stnKD(3)")
+        nc, f32 = self.num_classes, np.float32
+        if B < 2:
+            raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
+                             f"B - 1), got B={B}")
+        momentum = float(momentum)
+        if not (np.isfinite(momentum) and 0.0 <= momentum <= 1.0):
+            raise ValueError(f"momentum must be finite and in [0, 1], got {momentum}")
+        mask = None
+        if dropout is not None:
+            if isinstance(dropout, (int, np.integer)):
+                mask = self.dropout_mask(B, int(dropout))
+            else:
+                if is_device(dropout) and not on_dev:
+                    raise TypeError("a device dropout mask needs X on the device")
+                mask = self._like(dropout, "dropout", (256, B), f32, is_device(dropout))
+        nb = _lib.query_bytes("fx3d_pointnet_train_workspace_bytes", N, B, nc)  # (the library's own size limits)
+        if mask is not None and not is_device(mask):
+            mask = DeviceArray.from_host(mask)
+        x = self._on_device(pts, N, B, on_dev)
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        out = {"probs": DeviceArray.empty((nc, B), f32)}
+        if intermediates:
+            out.update({"logits": DeviceArray.empty((nc, B), f32), "stn": DeviceArray.empty((3, 3, B), f32),
+                        "fstn": DeviceArray.empty((64, 64, B), f32), "pooled": DeviceArray.empty((1024, B), f32)})
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if intermediates or update:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        params = self._params_dev()
+        ws = workspace(nb, tag="pointnet_train")
+        stream = current_stream().handle
+        _lib.call("fx3d_pointnet_forward_train", params.ptr, nc, x.ptr, N, B, mask.ptr if mask is not None else None, momentum,
+                  out["probs"].ptr, *(out[k].ptr if intermediates else None for k in ("logits", "stn", "fstn", "pooled")),
+                  stats["batch_stats"].ptr, stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
+        if update:
+            run = stats["running"]
+            host = run.to_host()
+            for name, C, at, flat in slots:  # mu then sigma2, adjacent in both layouts
+                self.params[name + ".mu"], self.params[name + ".sigma2"] = host[at:at + C].copy(), host[at + C:at + 2 * C].copy()
+                _lib.call("fx3d_memcpy_d2d", params.ptr + 4 * flat, run.ptr + 4 * at, 8 * C, stream)
+        if not intermediates:
+            return out["probs"] if on_dev else out["probs"].to_host()
+        for key, buf in stats.items():
+            named, host = {}, (None if on_dev else buf.to_host())
+            for name, C, at, _ in slots:
+                for f, o in ((".mu", at), (".sigma2", at + C)):
+                    named[name + f] = (DeviceArray(buf.ptr + 4 * o, (C,), f32, owned=False, keep=buf) if on_dev else host[o:o + C])
+            out[key] = named
+        if not on_dev:
+            out = {k: (v if isinstance(v, dict) else v.to_host()) for k, v in out.items()}
+        return out
 
     _MID = {"gstn": (3, 3), "gfstn": (64, 64), "gh": (64, None), "gxt": (3, None)}  # fx3d_pointnet_grad's optional outputs, in order
 

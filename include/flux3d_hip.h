@@ -1114,6 +1114,47 @@ FX3D_API fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_cla
                                         const float *glogits, float *gparams, float *gx, float *gstn, float *gfstn, float *gh,
                                         float *gxt, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- PointNet training-mode forward: (m::PointNet)(X) with Flux's BatchNorm and Dropout(0.4) in training mode ----------------
+ * The network, the layouts and all arithmetic but BatchNorm's statistics are "PointNet inference" above.  Every one of the 13
+ * BatchNorms normalises by the mean and the uncorrected variance of what it is given over the current batch -- m = N B values per
+ * channel for the nine after a 1x1 convolution, m = B for the four after a dense layer -- and the running statistics Flux
+ * would then hold are returned.  What a BatchNorm is given: relu(conv + bias) in stn, fstn and feat.bn1; conv + bias in
+ * conv_block1.bn and feat.bn2; relu(dense + bias) in stn.bn4, fstn.bn4 and feat.bn3; relu(dense + bias) times the dropout
+ * multiplier in feat.bn4 (Dropout sits before that BatchNorm, src/models/pointnet.jl:45-57).
+ * Julia's Float32 mean and sum have no order that could be reproduced; the statistics are defined here instead.
+ * Sums, in Float64 (v is the Float32 value the BatchNorm is given; v v is exact in Float64, so fused or not is the same):
+ *   S1 = sum (double)v, S2 = sum (double)v (double)v, every chain from +0.0 with one rounding per addition.
+ *   A convolution's BatchNorm, per channel: the points of a cloud in tiles of 64 (tile k: points 64 k .. 64 k + 63; rows beyond
+ *     the cloud's last point take no part).  Within a tile the rows p = 0 .. 63 whose bit 2 is h form chain h, h = 0, 1, in
+ *     ascending p; the tile's sum is chain(0) + chain(1).  The tile sums t = tile + ntiles b (ntiles = ceil(N / 64)) are then
+ *     folded as FX3D_POINTNET_STAT_GROUPS chains, chain g over t = g, g + 32, g + 64, ... ascending, and the chains are added
+ *     in ascending g (a chain without a tile is +0.0).
+ *   A dense layer's BatchNorm, per channel: one chain over the clouds in ascending b.
+ *   The orders depend on (N, B) alone, never on the launch shape; no atomics.
+ * Mean and variance, in Float64:  mu64 = S1 / m;  var64 = S2 / m - mu64 mu64, and 0 where that is below 0 (a NaN stays);
+ *   mu = Float32(mu64), var = Float32(var64).  The normalisation is "PointNet inference"'s BatchNorm at (mu, var).
+ * Running statistics, in Float32, one rounding per operation, nothing fused, with mtm = momentum:
+ *   mu'  = ((1 - mtm) mu_run) + (mtm mu);   var' = ((1 - mtm) var_run) + (((mtm Float32(m)) / Float32(m - 1)) var).
+ * Statistics layout (batch_stats and running, fx3d_pointnet_stat_count floats = 2 x 4928): per BatchNorm in forward order --
+ *   stn.bn1 .. bn4, conv_block1.bn, fstn.bn1 .. bn4, feat.bn1 .. bn4, the order of the mu / var slots of params_dev -- mu (C), then var (C).
+ * dropout: (256,B) Float32 multipliers applied with one Float32 multiplication to relu(feat.dense2); NULL: the identity.
+ * batch_stats is required; running is optional and is computed from the mu / var slots of params_dev, which is not written.
+ * probs (required), logits, stn, fstn, pooled (optional) as in fx3d_pointnet_forward.  logits, stn, fstn, pooled, batch_stats
+ * and running are bit-identical to the restatement tests/pointnet_train_ref.py and from run to run.  fx3d_pointnet_forward on
+ * parameters whose mu / var slots hold batch_stats gives, with dropout NULL, the same logits, stn, fstn and pooled bit for bit.
+ * Refusals, FX3D_ERR_INVALID_ARG, before any device work: a NULL required pointer; fx3d_pointnet_forward's size limits;
+ * B < 2 (a dense BatchNorm's running variance divides by B - 1); momentum not finite or outside [0, 1]; a short workspace or
+ * one not 16-byte aligned.  32 launches on `s`, no host synchronisation, no host memory read after the argument check
+ * (graph-capturable).  ws: fx3d_pointnet_train_workspace_bytes(N, B, num_classes) -- the forward's workspace, the tile sums
+ * (2,1024,ntiles,B) Float64, and the heads' (512,B) and (256,B) activations. */
+#define FX3D_POINTNET_STAT_GROUPS 32 /* chains the tile sums of a layer are folded in ("PointNet training-mode forward") */
+FX3D_API fx3d_status fx3d_pointnet_stat_count(int64_t *count);
+FX3D_API fx3d_status fx3d_pointnet_train_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_classes, const float *x, int32_t N,
+                                                 int32_t B, const float *dropout, float momentum, float *probs, float *logits,
+                                                 float *stn, float *fstn, float *pooled, float *batch_stats, float *running,
+                                                 void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
