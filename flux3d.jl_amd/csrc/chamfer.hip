@@ -248,12 +248,27 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     const bool vec = (reinterpret_cast<uintptr_t>(cb) & 15) == 0;
     const bool one_shot = PRUNE || NCm <= CH;
     if (tid == 0) { nfar[0] = 0; nfar[1] = 0; }  // (ordered before their first use by the barrier of the bounding-box pass)
-    float qpre[3];  // this lane's query of the coming tile pass (the load's latency hides behind the prologue)
-    {
+    [[maybe_unused]] float qpre[3];  // this lane's query of the coming tile pass (the load's latency hides behind the prologue)
+    if constexpr (!PRUNE) {
         const int q0i = (tile * tpb) * QB + wv * 32 + jq;
         const int qc0 = q0i < NQ ? q0i : NQ - 1;
 #pragma unroll
         for (int d = 0; d < 3; ++d) qpre[d] = qb[(size_t)qc0 * 3 + d];
+    }
+    // (PRUNE) a pruned block sorts the WHOLE query cloud (up to 4 * kHThreads points, four per thread: the sort below), its passes
+    // read their queries from the sorted window: the cloud is requested here, beside the candidates' first loads, so that its trip
+    // to memory runs under the cloud pass instead of behind its two barriers.  Whether the sort takes place (`sorted_q`) is known
+    // only after the pass; if it does not, the four rows go unused.  (A pruned launch holds either cloud in one chunk: NQ <= 4 * kHThreads
+    // always; the test stands for the sort's own condition.)
+    [[maybe_unused]] P3 qv[4];
+    if constexpr (PRUNE) {
+        if (NQ <= 4 * kHThreads) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int qp = 256 * wv + 64 * e + lane;
+                qv[e] = *reinterpret_cast<const P3 *>(qb + (size_t)(qp < NQ ? qp : NQ - 1) * 3);
+            }
+        }
     }
     if constexpr (PRUNE) {  // the sort's counters (in the waves' scratch, idle until the passes) and the query groups' boxes: the cloud pass's barrier orders this
         unsigned int *zc = reinterpret_cast<unsigned int *>(wres);
@@ -390,8 +405,13 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     // tile exactly, in the isless order (a finite cloud with cinf < 1e16 never produces an infinite or NaN distance
     // to a query inside the fp16 range)
     const bool sane = allfin && cinf < 1.0e16f;  // usable queries lie within 234 cinf of the centre: 3 (235 cinf)^2 stays finite
+    // A cloud narrower than 2^-50 stays unscaled (its image is all zeros: every candidate lies within every band and is compared
+    // exactly).  The bands charge the oracle's own rounding as RELATIVE to its distances; a product (dx dx) that underflows is
+    // rounded to a multiple of 2^-149 instead, 3 x 2^-150 absolute per distance or 6 x 2^-150 sc^2 between two of them in the
+    // image's unit: 2^-36 at sc = 2^56, far inside the bands' floor of 2^-22 -- but larger than the distances themselves for a
+    // cloud of extent 1e-20, where sc = 2^74 picked neighbours the oracle's subnormal distances do not (the gate stood at 1e-30).
     float sc = 1.0f;
-    if (sane && rng > 1.0e-30f) {
+    if (sane && rng > 0x1p-50f) {
         int e;
         (void)frexpf(rng, &e);  // rng = m 2^e, m in [0.5,1)
         sc = ldexpf(1.0f, 7 - e);
@@ -454,14 +474,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
         // candidates' frame a chair's points fell outside an aeroplane's flat box and crowded into its border cells), found by the
         // block while the candidates are counted: integer-key min / max over the wave (DPP), 6 LDS atomics per wave.
         const bool sorted_q = do_sort && NQ <= 4 * kHThreads;
-        P3 qv[4];
-        if (sorted_q) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int qp = 256 * wv + 64 * e + lane;
-                qv[e] = *reinterpret_cast<const P3 *>(qb + (size_t)(qp < NQ ? qp : NQ - 1) * 3);
-            }
-        }
+        // (its rows qv[e] -- point 256 wave + 64 e + lane -- were requested at the kernel's entry)
         FX3D_PROBE_MARK2(0);
         int *gbox = reinterpret_cast<int *>(boxes + 64 * 2);  // [groups of 32 window rows] x (lo keys, -, hi keys, -)
         auto group_box = [&](int wrow, float x, float y, float z) {  // a query of the window: into the box of its group (image frame)
@@ -824,16 +837,23 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 // fp16 values with a power of two are exact).  Without it such queries scanned the whole chunk exactly:
                 // 690 us instead of ~100 for C2's shape with an extent ratio of 250.  (The padding slot stays unscaled: 4.3e9.)
                 float sq = 1.0f, fl_s = 0.0f;
+                float rsq = 1.0f;  // 1 / sq, exactly
                 if (S >= 3.0e4f && S < 0x1p28f) {
                     int e;
                     (void)frexpf(S, &e);          // S = f 2^e, f in [0.5, 1)
                     sq = ldexpf(1.0f, 14 - e);    // sq S in [2^13, 2^14); sq >= 2^-14: a normal fp16
+                    rsq = ldexpf(1.0f, e - 14);   // (e = 15 ... 28: 2 ... 2^14)
                     m0 *= sq; m1 *= sq; m2 *= sq; S *= sq;
                     fl_s = 0x1p-15f;              // fp16 subnormal quantum of a scaled-down small component x |c~_d| <= 2^-25 x 3 x 128
                 }
                 qok = S < 3.0e4f;  // inside the fp16 range (also false for NaN)
                 qfin = fabsf(qr[0]) + fabsf(qr[1]) + fabsf(qr[2]) < INFINITY;
-                const float qn = 0.25f * ((m0 * m0 + m1 * m1) + m2 * m2) / sq;  // sq |q~|^2: the band in the query's unit
+                // sq |q~|^2: the band in the query's unit.  The division by sq is a multiplication by rsq, bit for bit (an IEEE division
+                // expands to about ten VALU): with a scale of its own the dividend lies in [2^24 / 3, 2^26) and the quotient below 2^40 is that
+                // value times a power of two, exact either way; without one sq = rsq = 1, and x / 1 and x * 1 both return x for
+                // every x -- zeros, infinities and subnormals included (the kernel keeps Float32 subnormals: no flush mode) --
+                // and a quiet NaN for a NaN.
+                const float qn = 0.25f * ((m0 * m0 + m1 * m1) + m2 * m2) * rsq;
                 da = kBandA * qn + 0x1p-24f * (S + 4.0f) + fl_s;
                 // Round 4, queries OUTSIDE the candidate cloud (|q~| >~ Cmax: clouds of different extent -- a unit teapot against a
                 // table in millimetres).  The filter's error is really beta (|c~|^2 + |q~||c~|) + floor (tools/test_f16_filter.hip:
@@ -846,7 +866,17 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 // left is the reference's own Float32 rounding of distances that large.  Both are valid; the lower one is used.
                 {
                     const float c2 = sq * cm2;                     // in the query's unit, like qn = sq |q~|^2
-                    da_far = 2.1f * kBetaC * c2 + 2.0f * kBetaC * sqrtf(qn * c2) + 0x1p-19f * qn + 0x1p-24f * (S + 4.0f) + fl_s;
+                    // (PRUNE) the cross term's root |q~| Cmax by the hardware's v_sqrt_f32 instead of the correctly rounded sqrtf (an
+                    // expansion of some twenty VALU): the term only has to be an UPPER bound.  The instruction is documented to 1 ulp on normal inputs -- 2 ulp
+                    // (2^-22 relative) are budgeted -- and may take a subnormal input x < 2^-126 for zero, where sqrt(x) < 2^-63.  So
+                    //   r = fma(v_sqrt(x), 1 + 2^-20, 2^-62) >= sqrt(x) (1 - 2^-22) (1 + 2^-20) (1 - 2^-24) > sqrt(x) (1 + 2^-22) >= sqrtf(x),
+                    //   r >= 2^-62 > sqrt(x) for a subnormal x,   r <= sqrt(x) (1 + 6 2^-22) + 2^-62:
+                    // never below the root it replaces, and this one term of the band at most 6 2^-22 wider (+Inf and NaN pass
+                    // through as before: such a query is not `qok`).
+                    float root;
+                    if constexpr (PRUNE) root = __builtin_fmaf(__builtin_amdgcn_sqrtf(qn * c2), 1.0f + 0x1p-20f, 0x1p-62f);
+                    else root = sqrtf(qn * c2);
+                    da_far = 2.1f * kBetaC * c2 + 2.0f * kBetaC * root + 0x1p-19f * qn + 0x1p-24f * (S + 4.0f) + fl_s;
                 }
                 if constexpr (PRUNE) {
                     // |q~ - c~|^2 = |q~|^2 + t(c) and t(c) <= (its filter value) + beta (|c~|^2 + |q~|^2) + floor (the filter's error
@@ -984,8 +1014,14 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                     // largest upper bound of a nearest squared distance among the wave's queries (+Inf / NaN: every tile)
                     const float kb = fk[0];
                     const float bb = __builtin_fmaf(fabsf(kb), kKeyUp, kb);
-                    const float dj = fminf(bb, __shfl_xor(bb, 32, 64)) + dpr;
-                    const float ucut = wave_max_f(__builtin_fmaf(dj, 1.0f + 0x1p-9f, 0x1p-8f));
+                    const float dj = vmin(bb, __shfl_xor(bb, 32, 64)) + dpr;  // (bb: the result of an fma, a quiet NaN if any)
+                    // the wave's maximum on integer keys: a Float32 maximum canonicalises the operands of every DPP step (wave_max_f:
+                    // three instructions per step), an integer one takes the DPP operand directly and the four rows meet in scalar
+                    // registers.  Same `todo`: without a NaN the key order is the float order, and a NaN among the dj sends the wave
+                    // to every tile below whatever ucut is (as a key it lies beyond the infinities; fmaxf would skip it).
+                    const int kr = row_mm_key<true>(fkey(__builtin_fmaf(dj, 1.0f + 0x1p-9f, 0x1p-8f)));
+                    const float ucut = fkey_inv(imm<true>(imm<true>(__builtin_amdgcn_readlane(kr, 0), __builtin_amdgcn_readlane(kr, 16)),
+                                                          imm<true>(__builtin_amdgcn_readlane(kr, 32), __builtin_amdgcn_readlane(kr, 48))));
                     const bool keep = !(bd > ucut) || !(dj == dj);
                     todo = (__ballot(!(dj == dj)) ? all_lt : __ballot(keep)) & all_lt & ~done;
                     if (!todo) break;
@@ -1216,6 +1252,9 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                             }
                         }
                     }
+#ifdef FX3D_PROBE_COUNT
+                    if ((threadIdx.x & 63) == 0) atomicAdd(&g_probe[4095 * 16 + 8], (unsigned long long)nitems);  // items handed to the exact tasks
+#endif
                     // all 64 lanes share the (item, run-of-4-candidates) tasks
                     __builtin_amdgcn_s_waitcnt(0xc07f);
                     __builtin_amdgcn_wave_barrier();

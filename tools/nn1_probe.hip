@@ -98,6 +98,8 @@ int main(int argc, char **argv) {
     printf("kernel span (first block start -> last block end): %llu ticks\n", tmax - t0min);
     for (int k = 1; k <= 12; ++k) printf("  %-20s avg %10.1f ticks\n", names[k], d[k] / nb);
     printf("accumulated over all launches: wave-passes %llu, with slow queries %llu, retried %llu, with run items %llu; slow queries %llu, lanes with an unusable filter %llu\n", pr[4095 * 16], pr[4095 * 16 + 1], pr[4095 * 16 + 2], pr[4095 * 16 + 3], pr[4095 * 16 + 4], pr[4095 * 16 + 5]);
+    printf("items handed to the exact tasks (a lane's 16 rows of one block each; run items: four rows): %llu -- per wave-pass %.1f\n", pr[4095 * 16 + 8],
+           pr[4095 * 16] ? (double)pr[4095 * 16 + 8] / pr[4095 * 16] : 0.0);
     printf("(pruned launches) lane tiles run in phase 0: %llu, in phase 1: %llu -- per wave-pass of %d: %.1f + %.1f\n", pr[4095 * 16 + 6], pr[4095 * 16 + 7],
            (M + 63) / 64, pr[4095 * 16] ? (double)pr[4095 * 16 + 6] / pr[4095 * 16] : 0.0, pr[4095 * 16] ? (double)pr[4095 * 16 + 7] / pr[4095 * 16] : 0.0);
     if (getenv("RAW")) {
