@@ -744,6 +744,10 @@ def test_loss_dolphin_gradient(gpu_fx, oracle):
                        + oracle.edge_loss(v, e0))
     assert np.isclose(loss, l_ref, rtol=1e-5)
     assert np.allclose(g.to_host(), ref, rtol=1e-3, atol=1e-7)
+    # ... and bit for bit the ordered chain: both mesh-loss adjoints added in Float32, the sampling adjoint gathered on top of them
+    g0 = np.asfortranarray((g2 + g3).astype(np.float32)).reshape((3, 2562, 1), order="F")
+    ordered = oracle.sample_points_bwd(fp, m._faces_len, m.V, fa, r1, r2, gA, base=g0)
+    assert np.array_equal(g.to_host(), ordered.reshape((3, 2562), order="F"))
 
 
 def test_loss_dolphin_async_matches_sync(gpu_fx):
@@ -781,8 +785,10 @@ def test_fit_mesh_loop_decreases_loss(gpu_fx):
 
 def test_fit_step_graph_matches_eager_loop(gpu_fx):
     """The hipGraph recording of one fit_mesh iteration replays to the same trajectory as the eager loop: same
-    samples (seed + 2 per iteration through the device counter), same losses, same offsets up to the float
-    atomics of the adjoints; the cached target CDF and the single-mesh packed/padded alias are on this path."""
+    samples (seed + 2 per iteration through the device counter), same losses, same offsets; the cached target CDF and the
+    single-mesh packed/padded alias are on this path.  (The default path is the ordered one and has no float atomics:
+    tests/test_gpu_fit_chain.py holds both loops to the host chain bit for bit; the tolerances here are those of the atomic form,
+    FitStepGraph(ordered=False).)"""
     fx = gpu_fx
     tv, tf = fx.load_obj(os.path.join(GOLDEN, "teapot.obj"))
     tv = (tv - tv.mean(1, keepdims=True)) / tv.std()
