@@ -13,6 +13,7 @@
 // and walks it with lane-parallel gathers and an ordered readlane chain), and the owner of a row subtracts its entries in
 // order.  D = 3: accumulators in registers, 12-byte row loads; other D: the row of g itself is the accumulator.
 #include <algorithm>
+#include <type_traits>
 
 #include "fx3d_common.h"
 #include "mesh_host.h"
@@ -59,24 +60,18 @@ __global__ __launch_bounds__(kThreads) void chamfer_bwd_kernel(
 }
 
 // ---- the gather form ---------------------------------------------------------------------------------------------------------
-#ifndef FX3D_BG_THREADS
-#define FX3D_BG_THREADS 1024
-#endif
-constexpr int kBgThreads = FX3D_BG_THREADS;
+constexpr int kBgThreads = 1024;
 constexpr int kBgRows = 4096;    // rows of g one block owns at most
 constexpr int kBgPer = kBgRows / kBgThreads;  // rows / scan slots / other-side rows per thread and round
 constexpr int kBgChunk = 4096;   // rows of the other side bucketed per round (their round-local ids fit 16 bits)
 constexpr int kBgSmall = 8;      // lists up to this length are ordered in the owner's registers (one in 10^6 of uniform data's is longer)
 constexpr int kBgSortWaves = kBgThreads / 64;  // every wave takes rows with longer lists (one 4096-bit bitmap each)
 constexpr int kBgBigW = 256;     // long rows whose own point and index travel through LDS (the others re-read them from memory)
-#ifndef FX3D_BG_OCC
-#define FX3D_BG_OCC 4   // waves per SIMD the kernels are compiled for.  4 = one 1024-thread block per CU with up to 128 registers; 8 (two
-#endif                  // blocks per CU, 64 registers) spills and measured 41 - 51 us against 37 at B = 256 x 4096 in every form tried
+constexpr int kBgOcc = 4;  // waves per SIMD the kernels are compiled for.  4 = one 1024-thread block per CU with up to 128 registers; 8 (two
+                           // blocks per CU, 64 registers) spills and measured 41 - 51 us against 37 at B = 256 x 4096 in every form tried
+static_assert(kBgPer == 4, "the pins in bg_load_rows and bg_read_indices name four values each");
+static_assert(kBgThreads == sg::kSgThreads, "row blocks and table blocks share a launch");
 
-#ifndef FX3D_BG_STOP
-#define FX3D_BG_STOP 0   // timing experiments only: leave after phase n
-#endif
-#define BG_STOP(n) do { if (FX3D_BG_STOP == (n)) return; } while (0)
 #ifdef FX3D_BG_PROBE   // phase stamps of every block (s_memtime, 100 MHz) for tools/chamfer_bwd_probe.py; never in the shipped build
 __device__ unsigned long long g_bg_probe[1024 * 8];
 #define BG_STAMP(n) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_bg_probe[blockIdx.x * 8 + (n)] = __builtin_readcyclecounter(); } while (0)
@@ -123,13 +118,17 @@ __device__ __forceinline__ unsigned int wave_scan_incl(unsigned int v) {
 __device__ __forceinline__ float lane_val(float v, int l) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
+__device__ __forceinline__ P3 lane_val(P3 v, int l) { return P3{lane_val(v.x, l), lane_val(v.y, l), lane_val(v.z, l)}; }
 
+// One side of a sampled adjoint: its mesh, the draws of its samples, where the gradient w.r.t. its vertices goes
 struct SampledSide {
     const int32_t *faces;     // (3, Fmax, B) mesh-local
     const int32_t *face_idx;  // (n, B) the draws
     const float *r1, *r2;
-    float *gverts;            // (3, Vmax, B), added to
+    float *gverts;            // (3, Vmax, B), added to; nullptr: no gradient w.r.t. this side's mesh
     int Vmax, Fmax;
+    const int32_t *vf_rowptr, *vf_ent;  // the vertex -> face table of the ordered form (the host picks the form by it; no kernel here reads it)
+    bool complete() const { return faces && face_idx && r1 && r2 && Vmax > 0 && Fmax > 0; }  // (host: what a side with gverts must bring)
 };
 
 struct BgJob {
@@ -160,280 +159,323 @@ __device__ __forceinline__ void bg_scatter_sample(const BgJob &J, int i, P3 a) {
         for (int d = 0; d < 3; ++d) atomicAdd(&gb[3ll * f3[t] + d], wt[t] * gr[d]);
 }
 
+// ---- a block's rows: bg_rows<MODE> and its phases -------------------------------------------------------------------------------------
 // MODE 0: D = 3, rows stored to g;  1: any D, rows accumulated in g (no LDS image: gathers from L2);  2: D = 3, rows scattered
-// onto the sampled faces' vertices
+// onto the sampled faces' vertices.
+
+// What a thread carries from phase to phase.  (Plain scalar arrays: an array of the packed 12-byte P3 is not promoted to registers -- it
+// lived in scratch.)
+struct BgThread {
+    int tid, lane, wv, nrows, rpt;
+    int jown[kBgPer];                              // my rows (tid + u * kBgThreads): the other side's row of their own term,
+    float wx[kBgPer], wy[kBgPer], wz[kBgPer];      // D = 3: the rows themselves
+    float ojx[kBgPer], ojy[kBgPer], ojz[kBgPer];   // D = 3: and the rows jown names
+    int il[kBgPer];                                // this round: which of the block's rows the other side's row tid + v * kBgThreads points at (or none)
+};
+// One round: rows [c0, c0 + cn) of the other side.  WHEN A ROW'S OWN TERM IS ADDED is decided here and nowhere else -- side x: it
+// opens the row (the oracle's first loop), side y: it closes it.
+struct BgRound {
+    int c0, cn;
+    bool first, last, own_first;
+    __device__ __forceinline__ bool own_opens() const { return first && own_first; }
+    __device__ __forceinline__ bool own_closes() const { return last && !own_first; }
+};
+__device__ __forceinline__ BgRound bg_round(const BgJob &J, int c0) {
+    return BgRound{c0, J.S - c0 < kBgChunk ? J.S - c0 : kBgChunk, c0 == 0, c0 + kBgChunk >= J.S, J.side == 0};
+}
+
+// ---- one row's sum: the one statement of it, for the long rows of phase (4) and the owners of phase (5) ---------------------------------
+// V is what one sum runs over: the whole row (D = 3: three registers) or one coordinate of it (other D: the caller loops over d).
+// The arithmetic reads the same in both forms (never contracted: -ffp-contract=off).
+__device__ __forceinline__ P3 operator+(P3 a, P3 b) { return P3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ P3 operator-(P3 a, P3 b) { return P3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ P3 operator*(float c, P3 a) { return P3{c * a.x, c * a.y, c * a.z}; }
+
 template <int MODE>
-__device__ __forceinline__ void bg_rows(BgLds &L, const BgJob &J) {
+struct BgAcc {
+    using V = std::conditional_t<MODE == 1, float, P3>;
+    V a;
+    V *home;  // WHERE THE SUM LIVES BETWEEN ROUNDS, decided here and nowhere else: the row of g itself, or (MODE 2, which has no g) J.part in LDS
+    __device__ __forceinline__ BgAcc(const BgJob &J, int lr, int d) {
+        const size_t i = (size_t)(J.r0 + lr);
+        if constexpr (MODE == 2) home = J.part + lr;  // (one round: J.part has no bytes behind it -- and open / finish never follow it)
+        else if constexpr (MODE == 0) home = reinterpret_cast<P3 *>(J.g + i * 3);
+        else home = J.g + i * J.D + d;
+    }
+    // row r of p (D = 3), coordinate d of it (other D)
+    static __device__ __forceinline__ V row(const float *p, size_t r, int D, int d) {
+        if constexpr (MODE == 1) return p[r * D + d];
+        else return *reinterpret_cast<const P3 *>(p + r * 3);
+    }
+    // ot: the own term, c_own * (w - o)
+    __device__ __forceinline__ void open(const BgRound &R, V ot) {
+        if (!R.first) a = *home;
+        else if (R.own_opens()) a = V{} + ot;  // (0 + ot, as the oracle has it: an own term of -0 gives +0)
+        else a = V{};
+    }
+    __device__ __forceinline__ void sub(V t) { a = a - t; }  // t: c_oth * (o - w), one call per entry, entries ascending
+    __device__ __forceinline__ void close(const BgRound &R, V ot) { if (R.own_closes()) a = a + ot; }
+    __device__ __forceinline__ void finish(const BgJob &J, const BgRound &R, int lr) {
+        if constexpr (MODE == 2) if (R.last) return bg_scatter_sample(J, J.r0 + lr, a);
+        *home = a;
+    }
+};
+
+// ---- the phases ---------------------------------------------------------------------------------------------------------------------------
+// requested before anything else: this thread's rows and their indices, then the own term's rows of the other side
+template <int MODE>
+__device__ __forceinline__ void bg_load_rows(const BgJob &J, BgThread &T) {
     constexpr bool D3 = MODE != 1;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the long-row loop and its readlane chain must not be "divergent")
-    const int nrows = J.r1 - J.r0, D = J.D;
-    const int rpt = (nrows + kBgThreads - 1) / kBgThreads;  // 1 .. 4 rows per thread, kBgThreads apart: a wave's rows are contiguous
-                                                            // (12-byte loads / stores of consecutive lanes coalesce; 48 bytes apart they are 64 transactions)
-    const float *__restrict__ own = J.own;
-    const float *__restrict__ oth = J.oth;
-    const float c_own = J.c_own, c_oth = J.c_oth;
-    const bool own_first = J.side == 0;  // side x: the own term opens the row (the oracle's first loop), side y: it closes it
-    // requested before anything else: this thread's rows and their indices
-    int jown[kBgPer];
-    float wx[kBgPer], wy[kBgPer], wz[kBgPer];  // (plain scalar arrays: an array of the packed 12-byte P3 is not promoted to registers -- it lived in scratch)
+    T.tid = threadIdx.x; T.lane = T.tid & 63;
+    T.wv = __builtin_amdgcn_readfirstlane(T.tid >> 6);  // (scalar: the long-row loop and its readlane chain must not be "divergent")
+    T.nrows = J.r1 - J.r0;
+    T.rpt = (T.nrows + kBgThreads - 1) / kBgThreads;  // 1 .. 4 rows per thread, kBgThreads apart: a wave's rows are contiguous
+                                                      // (12-byte loads / stores of consecutive lanes coalesce; 48 bytes apart they are 64 transactions)
 #pragma unroll
     for (int u = 0; u < kBgPer; ++u) {
-        const bool mine = u < rpt && tid + u * kBgThreads < nrows;
-        jown[u] = mine ? J.idx_own[J.r0 + tid + u * kBgThreads] : 0;
-        wx[u] = 0.0f; wy[u] = 0.0f; wz[u] = 0.0f;
+        const bool mine = u < T.rpt && T.tid + u * kBgThreads < T.nrows;
+        T.jown[u] = mine ? J.idx_own[J.r0 + T.tid + u * kBgThreads] : 0;
+        T.wx[u] = 0.0f; T.wy[u] = 0.0f; T.wz[u] = 0.0f;
         if (D3 && mine) {
-            const P3 t = *reinterpret_cast<const P3 *>(own + (size_t)(J.r0 + tid + u * kBgThreads) * 3);
-            wx[u] = t.x; wy[u] = t.y; wz[u] = t.z;
+            const P3 t = *reinterpret_cast<const P3 *>(J.own + (size_t)(J.r0 + T.tid + u * kBgThreads) * 3);
+            T.wx[u] = t.x; T.wy[u] = t.y; T.wz[u] = t.z;
         }
     }
     // (round 6) the own term's rows of the other side, requested as soon as the indices are here and consumed in phase (5): the request
     // used to sit inside phase (5)'s per-row branch with a full wait behind it -- one more dependent trip to the L2 per row.
-    // UNCONDITIONAL loads throughout this function (a thread without a row reads row 0): `cond ? load : 0` compiles to a branch
+    // UNCONDITIONAL loads throughout these phases (a thread without a row reads row 0): `cond ? load : 0` compiles to a branch
     // around the load and `s_waitcnt vmcnt(0)` behind it, i.e. the loads of a group leave one after the other.
-    float ojx[kBgPer], ojy[kBgPer], ojz[kBgPer];
+    // (The pin, as in bg_read_indices: without it the optimiser moves each index's `* 12` into the branch of its `mine` select, with a
+    //  wait for that index behind it -- four dependent trips instead of one; seen in the ISA, +0.3 us at B = 32 x 4096.)
+    asm volatile("" : "+v"(T.jown[0]), "+v"(T.jown[1]), "+v"(T.jown[2]), "+v"(T.jown[3]));
 #pragma unroll
     for (int u = 0; u < kBgPer; ++u) {
-        ojx[u] = 0.0f; ojy[u] = 0.0f; ojz[u] = 0.0f;
+        T.ojx[u] = 0.0f; T.ojy[u] = 0.0f; T.ojz[u] = 0.0f;
         if (D3) {
-            const P3 t = *reinterpret_cast<const P3 *>(oth + (size_t)jown[u] * 3);
-            ojx[u] = t.x; ojy[u] = t.y; ojz[u] = t.z;
+            const P3 t = *reinterpret_cast<const P3 *>(J.oth + (size_t)T.jown[u] * 3);
+            T.ojx[u] = t.x; T.ojy[u] = t.y; T.ojz[u] = t.z;
         }
     }
+}
+
+// (1) this round's indices of the other side: which of my block's rows does other row c0 + jl point at
+__device__ __forceinline__ void bg_read_indices(BgLds &L, const BgJob &J, const BgRound &R, BgThread &T) {
+    if (T.tid == 0) L.nbig = 0u;
+#pragma unroll
+    for (int v = 0; v < kBgPer; ++v) {
+        const int jl = T.tid + v * kBgThreads;
+        T.il[v] = J.idx_oth[R.c0 + (jl < R.cn ? jl : 0)];
+    }
+    // (an empty asm that names all four: the optimiser otherwise sinks every load back into the branch of its `jl < cn` select,
+    //  with a full wait behind it -- four dependent trips to memory instead of one)
+    asm volatile("" : "+v"(T.il[0]), "+v"(T.il[1]), "+v"(T.il[2]), "+v"(T.il[3]));
+#pragma unroll
+    for (int v = 0; v < kBgPer; ++v) T.il[v] = T.tid + v * kBgThreads < R.cn ? T.il[v] - J.r0 : -1;
+}
+
+__device__ __forceinline__ void bg_count(BgLds &L, const BgThread &T) {
+#pragma unroll
+    for (int v = 0; v < kBgPer; ++v)
+        if ((unsigned int)T.il[v] < (unsigned int)T.nrows) atomicAdd(&L.cnt2[T.il[v] >> 1], (T.il[v] & 1) ? 0x10000u : 1u);
+}
+
+// (2) exclusive scan of the counts over the rows (thread t: slots 4t .. 4t+3) -> start[]; one barrier inside, behind the waves' sums
+__device__ __forceinline__ void bg_scan(BgLds &L, const BgThread &T) {
+    unsigned int cc[kBgPer], s4 = 0u;
+#pragma unroll
+    for (int q = 0; q < kBgPer / 2; ++q) {
+        const unsigned int cw = L.cnt2[kBgPer / 2 * T.tid + q];
+        cc[2 * q] = cw & 0xFFFFu; cc[2 * q + 1] = cw >> 16;
+        s4 += cc[2 * q] + cc[2 * q + 1];
+    }
+    const unsigned int inc = wave_scan_incl(s4);
+    if (T.lane == 63) L.wsum[T.wv] = inc;
+    __syncthreads();
+    unsigned int base = 0u;
+#pragma unroll
+    for (int q = 0; q < kBgThreads / 64; q += 4) {
+        const uint4 t = *reinterpret_cast<const uint4 *>(&L.wsum[q]);
+        base += (q < T.wv ? t.x : 0u) + (q + 1 < T.wv ? t.y : 0u) + (q + 2 < T.wv ? t.z : 0u) + (q + 3 < T.wv ? t.w : 0u);
+    }
+    unsigned int ex = base + inc - s4;
+#pragma unroll
+    for (int q = 0; q < kBgPer / 2; ++q) {
+        const unsigned int lo = ex, hi = ex + cc[2 * q];
+        *reinterpret_cast<unsigned int *>(&L.start[kBgPer * T.tid + 2 * q]) = lo | (hi << 16);
+        ex = hi + cc[2 * q + 1];
+    }
+    if (T.tid == kBgThreads - 1) L.start[kBgRows] = (unsigned short)ex;
+}
+
+// (3) placement, from the back of every list (arrival order inside a list: whatever the atomics give; put right in (4) and (5));
+//     the owners register their rows with long lists and hand the waves what they hold of them
+template <int MODE>
+__device__ __forceinline__ void bg_place(BgLds &L, const BgThread &T) {
+    constexpr bool D3 = MODE != 1;
+#pragma unroll
+    for (int v = 0; v < kBgPer; ++v)
+        if ((unsigned int)T.il[v] < (unsigned int)T.nrows) {
+            const int sh = (T.il[v] & 1) * 16;
+            const unsigned int old = atomicSub(&L.cnt2[T.il[v] >> 1], 1u << sh);
+            L.list[L.start[T.il[v]] + ((old >> sh) & 0xFFFFu) - 1u] = (unsigned short)(T.tid + v * kBgThreads);
+        }
+#pragma unroll
+    for (int u = 0; u < kBgPer; ++u) {
+        const int lr = T.tid + u * kBgThreads;
+        if (u < T.rpt && lr < T.nrows && (int)L.start[lr + 1] - (int)L.start[lr] > kBgSmall) {
+            const unsigned int k = atomicAdd(&L.nbig, 1u);
+            L.big[k] = (unsigned short)lr;
+            if (D3 && k < (unsigned int)kBgBigW) L.bigw[k] = float4{T.wx[u], T.wy[u], T.wz[u], __builtin_bit_cast(float, T.jown[u])};
+        }
+    }
+}
+
+// (4) rows with long lists: one wave each -- bitmap sort in place, lane-parallel gathers, an ordered readlane chain
+template <int MODE>
+__device__ __forceinline__ void bg_long_rows(BgLds &L, const BgJob &J, const BgRound &R, const BgThread &T) {
+    constexpr bool D3 = MODE != 1;
+    using V = typename BgAcc<MODE>::V;
+    const unsigned int nb = (unsigned int)__builtin_amdgcn_readfirstlane((int)L.nbig);
+    for (unsigned int k = (unsigned int)T.wv; k < nb; k += kBgSortWaves) {
+        const int lr = __builtin_amdgcn_readfirstlane((int)L.big[k]);
+        const int start = __builtin_amdgcn_readfirstlane((int)L.start[lr]);
+        const int c = __builtin_amdgcn_readfirstlane((int)L.start[lr + 1]) - start;
+        unsigned int *bm = L.bitmap[T.wv];
+        bm[T.lane] = 0u;
+        bm[T.lane + 64] = 0u;
+        wave_lds_sync();
+        for (int e = T.lane; e < c; e += 64) {
+            const unsigned int j = L.list[start + e];
+            atomicOr(&bm[j >> 5], 1u << (j & 31u));
+        }
+        wave_lds_sync();
+        unsigned int w0 = bm[2 * T.lane], w1 = bm[2 * T.lane + 1];
+        const unsigned int p = __popc(w0) + __popc(w1);
+        const unsigned int pin = wave_scan_incl(p);
+        int pos = start + (int)(pin - p);
+        while (w0) { L.list[pos++] = (unsigned short)(64 * T.lane + __ffs(w0) - 1); w0 &= w0 - 1u; }
+        while (w1) { L.list[pos++] = (unsigned short)(64 * T.lane + 32 + __ffs(w1) - 1); w1 &= w1 - 1u; }
+        wave_lds_sync();
+        const size_t i = (size_t)(J.r0 + lr);
+        V w;
+        int jo;
+        if (D3 && k < (unsigned int)kBgBigW) {  // the row's point and index came through LDS
+            const float4 t = L.bigw[k];
+            if constexpr (D3) w = P3{t.x, t.y, t.z};
+            jo = __builtin_bit_cast(int, t.w);
+        } else {
+            if constexpr (D3) w = BgAcc<MODE>::row(J.own, i, 3, 0);
+            jo = J.idx_own[i];
+        }
+        for (int d = 0; d < (D3 ? 1 : J.D); ++d) {  // (D = 3: the whole row at once)
+            if constexpr (!D3) w = J.own[i * J.D + d];
+            V ot{};  // the own term
+            if (!D3 || R.own_opens() || R.own_closes()) ot = J.c_own * (w - BgAcc<MODE>::row(J.oth, (size_t)jo, J.D, d));
+            BgAcc<MODE> acc(J, lr, d);
+            acc.open(R, ot);
+            for (int e0 = 0; e0 < c; e0 += 64) {
+                V t{};
+                if (e0 + T.lane < c) t = J.c_oth * (BgAcc<MODE>::row(J.oth, (size_t)(R.c0 + L.list[start + e0 + T.lane]), J.D, d) - w);
+                const int n = c - e0 < 64 ? c - e0 : 64;
+                for (int l = 0; l < n; ++l) acc.sub(lane_val(t, l));
+            }
+            acc.close(R, ot);
+            if (T.lane == 0) acc.finish(J, R, lr);
+        }
+    }
+}
+
+// (5) the owners: short lists ordered in registers, subtracted in order (no barrier between (4) and (5): the waves
+//     touch only the lists / rows of the long rows, which the owners skip).  Row by row: two rows at a time with every
+//     stage's LDS reads issued together was measured slower at every list cap (4 / 6 / 8: the arrays of both rows spill)
+template <int MODE>
+__device__ __forceinline__ void bg_owners(const BgLds &L, const BgJob &J, const BgRound &R, const BgThread &T) {
+    constexpr bool D3 = MODE != 1;
+    using V = typename BgAcc<MODE>::V;
+#pragma unroll
+    for (int u = 0; u < kBgPer; ++u) {
+        const int lr = T.tid + u * kBgThreads;
+        if (!(u < T.rpt && lr < T.nrows)) continue;
+        const int start = L.start[lr], c = (int)L.start[lr + 1] - start;
+        if (c > kBgSmall || (c == 0 && !R.first && !R.last)) continue;
+        unsigned int e[kBgSmall];
+#pragma unroll
+        for (int k = 0; k < kBgSmall; ++k) e[k] = k < c ? (unsigned int)L.list[start + k] : 0xFFFFu;
+        if (c > 4) {
+            ce(e[0], e[1]); ce(e[2], e[3]); ce(e[4], e[5]); ce(e[6], e[7]);
+            ce(e[0], e[2]); ce(e[1], e[3]); ce(e[4], e[6]); ce(e[5], e[7]);
+            ce(e[1], e[2]); ce(e[5], e[6]); ce(e[0], e[4]); ce(e[3], e[7]);
+            ce(e[1], e[5]); ce(e[2], e[6]);
+            ce(e[1], e[4]); ce(e[3], e[6]);
+            ce(e[2], e[4]); ce(e[3], e[5]);
+            ce(e[3], e[4]);
+        } else if (c > 2) {
+            ce(e[0], e[1]); ce(e[2], e[3]); ce(e[0], e[2]); ce(e[1], e[3]); ce(e[1], e[2]);
+        } else if (c == 2) {
+            ce(e[0], e[1]);
+        }
+        for (int d = 0; d < (D3 ? 1 : J.D); ++d) {  // (D = 3: the whole row at once)
+            V w, o;
+            if constexpr (D3) { w = P3{T.wx[u], T.wy[u], T.wz[u]}; o = P3{T.ojx[u], T.ojy[u], T.ojz[u]}; }
+            else { w = J.own[(size_t)(J.r0 + lr) * J.D + d]; o = J.oth[(size_t)T.jown[u] * J.D + d]; }
+            V ot{};  // the own term
+            if (!D3 || R.own_opens() || R.own_closes()) ot = J.c_own * (w - o);
+            BgAcc<MODE> acc(J, lr, d);
+            acc.open(R, ot);
+            if constexpr (D3) {
+#pragma unroll
+                for (int h = 0; h < kBgSmall; h += 4) {  // four gathers in flight
+                    if (h >= c) break;
+                    float ox[4], oy[4], oz[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {  // (unconditional: a slot beyond the list re-reads the round's first row)
+                        const P3 t = *reinterpret_cast<const P3 *>(J.oth + (size_t)(R.c0 + (h + k < c ? e[h + k] : 0u)) * 3);
+                        ox[k] = t.x; oy[k] = t.y; oz[k] = t.z;
+                    }
+                    asm volatile("" : "+v"(ox[0]), "+v"(oy[0]), "+v"(oz[0]), "+v"(ox[1]), "+v"(oy[1]), "+v"(oz[1]), "+v"(ox[2]), "+v"(oy[2]),
+                                      "+v"(oz[2]), "+v"(ox[3]), "+v"(oy[3]), "+v"(oz[3]));  // (all four requested before the first is used)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (h + k < c) acc.sub(J.c_oth * (P3{ox[k], oy[k], oz[k]} - w));
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < kBgSmall; ++k)
+                    if (k < c) acc.sub(J.c_oth * (J.oth[(size_t)(R.c0 + e[k]) * J.D + d] - w));
+            }
+            acc.close(R, ot);
+            acc.finish(J, R, lr);
+        }
+    }
+}
+
+// The rows [J.r0, J.r1) of the block's (cloud, side).  Every barrier of a round but the scan's own is here.
+template <int MODE>
+__device__ __forceinline__ void bg_rows(BgLds &L, const BgJob &J) {
+    BgThread T;
+    bg_load_rows<MODE>(J, T);
     BG_STAMP(0);
 #pragma unroll
-    for (int q = 0; q < kBgPer / 2; ++q) L.cnt2[kBgPer / 2 * tid + q] = 0u;  // (the placement of every round leaves the counters at zero)
-
+    for (int q = 0; q < kBgPer / 2; ++q) L.cnt2[kBgPer / 2 * T.tid + q] = 0u;  // (the placement of every round leaves the counters at zero)
     for (int c0 = 0; c0 < J.S; c0 += kBgChunk) {
-        const int cn = J.S - c0 < kBgChunk ? J.S - c0 : kBgChunk;
-        const bool first = c0 == 0, last = c0 + kBgChunk >= J.S;
-        // (1) this round's rows of the other side -> LDS image; counts: which of my rows does other row c0 + jl point at
-        if (tid == 0) L.nbig = 0u;
-        int il[kBgPer];
-#pragma unroll
-        for (int v = 0; v < kBgPer; ++v) {
-            const int jl = tid + v * kBgThreads;
-            il[v] = J.idx_oth[c0 + (jl < cn ? jl : 0)];
-        }
-        static_assert(kBgPer == 4, "the pin below names four values");
-        // (an empty asm that names all four: the optimiser otherwise sinks every load back into the branch of its `jl < cn` select,
-        //  with a full wait behind it -- four dependent trips to memory instead of one)
-        asm volatile("" : "+v"(il[0]), "+v"(il[1]), "+v"(il[2]), "+v"(il[3]));
-#pragma unroll
-        for (int v = 0; v < kBgPer; ++v) il[v] = tid + v * kBgThreads < cn ? il[v] - J.r0 : -1;
+        const BgRound R = bg_round(J, c0);
+        bg_read_indices(L, J, R, T);     // (1)
         __syncthreads();
         BG_STAMP(1);
-        BG_STOP(1);
-#pragma unroll
-        for (int v = 0; v < kBgPer; ++v)
-            if ((unsigned int)il[v] < (unsigned int)nrows) atomicAdd(&L.cnt2[il[v] >> 1], (il[v] & 1) ? 0x10000u : 1u);
+        bg_count(L, T);
         __syncthreads();
         BG_STAMP(2);
-        BG_STOP(2);
-        // (2) exclusive scan over the rows (thread t: slots 4t .. 4t+3), long lists registered
-        unsigned int cc[kBgPer], s4 = 0u;
-#pragma unroll
-        for (int q = 0; q < kBgPer / 2; ++q) {
-            const unsigned int cw = L.cnt2[kBgPer / 2 * tid + q];
-            cc[2 * q] = cw & 0xFFFFu; cc[2 * q + 1] = cw >> 16;
-            s4 += cc[2 * q] + cc[2 * q + 1];
-        }
-        const unsigned int inc = wave_scan_incl(s4);
-        if (lane == 63) L.wsum[wv] = inc;
-        __syncthreads();
-        {
-            unsigned int base = 0u;
-            {
-#pragma unroll
-                for (int q = 0; q < kBgThreads / 64; q += 4) {
-                    const uint4 t = *reinterpret_cast<const uint4 *>(&L.wsum[q]);
-                    base += (q < wv ? t.x : 0u) + (q + 1 < wv ? t.y : 0u) + (q + 2 < wv ? t.z : 0u) + (q + 3 < wv ? t.w : 0u);
-                }
-            }
-            unsigned int ex = base + inc - s4;
-#pragma unroll
-            for (int q = 0; q < kBgPer / 2; ++q) {
-                const unsigned int lo = ex, hi = ex + cc[2 * q];
-                *reinterpret_cast<unsigned int *>(&L.start[kBgPer * tid + 2 * q]) = lo | (hi << 16);
-                ex = hi + cc[2 * q + 1];
-            }
-            if (tid == kBgThreads - 1) L.start[kBgRows] = (unsigned short)ex;
-        }
+        bg_scan(L, T);                   // (2)
         __syncthreads();
         BG_STAMP(3);
-        BG_STOP(3);
-        // (3) placement, from the back of every list (arrival order inside a list: whatever the atomics give; put right below);
-        //     the owners register their rows with long lists and hand the waves what they hold of them
-#pragma unroll
-        for (int v = 0; v < kBgPer; ++v)
-            if ((unsigned int)il[v] < (unsigned int)nrows) {
-                const int sh = (il[v] & 1) * 16;
-                const unsigned int old = atomicSub(&L.cnt2[il[v] >> 1], 1u << sh);
-                L.list[L.start[il[v]] + ((old >> sh) & 0xFFFFu) - 1u] = (unsigned short)(tid + v * kBgThreads);
-            }
-#pragma unroll
-        for (int u = 0; u < kBgPer; ++u) {
-            const int lr = tid + u * kBgThreads;
-            if (u < rpt && lr < nrows && (int)L.start[lr + 1] - (int)L.start[lr] > kBgSmall) {
-                const unsigned int k = atomicAdd(&L.nbig, 1u);
-                L.big[k] = (unsigned short)lr;
-                if (D3 && k < (unsigned int)kBgBigW) L.bigw[k] = float4{wx[u], wy[u], wz[u], __builtin_bit_cast(float, jown[u])};
-            }
-        }
+        bg_place<MODE>(L, T);            // (3)
         __syncthreads();
         BG_STAMP(4);
-        BG_STOP(4);
-        // (4) rows with long lists: one wave each -- bitmap sort in place, lane-parallel gathers, an ordered readlane chain
-        const unsigned int nb = (unsigned int)__builtin_amdgcn_readfirstlane((int)L.nbig);
-        for (unsigned int k = (unsigned int)wv; k < nb; k += kBgSortWaves) {
-            const int lr = __builtin_amdgcn_readfirstlane((int)L.big[k]);
-            const int start = __builtin_amdgcn_readfirstlane((int)L.start[lr]);
-            const int c = __builtin_amdgcn_readfirstlane((int)L.start[lr + 1]) - start;
-            unsigned int *bm = L.bitmap[wv];
-            bm[lane] = 0u;
-            bm[lane + 64] = 0u;
-            wave_lds_sync();
-            for (int e = lane; e < c; e += 64) {
-                const unsigned int j = L.list[start + e];
-                atomicOr(&bm[j >> 5], 1u << (j & 31u));
-            }
-            wave_lds_sync();
-            unsigned int w0 = bm[2 * lane], w1 = bm[2 * lane + 1];
-            const unsigned int p = __popc(w0) + __popc(w1);
-            const unsigned int pin = wave_scan_incl(p);
-            int pos = start + (int)(pin - p);
-            while (w0) { L.list[pos++] = (unsigned short)(64 * lane + __ffs(w0) - 1); w0 &= w0 - 1u; }
-            while (w1) { L.list[pos++] = (unsigned short)(64 * lane + 32 + __ffs(w1) - 1); w1 &= w1 - 1u; }
-            wave_lds_sync();
-            const size_t i = (size_t)(J.r0 + lr);
-            if (D3) {
-                P3 w;
-                int jo;
-                if (k < (unsigned int)kBgBigW) {
-                    const float4 t = L.bigw[k];
-                    w = P3{t.x, t.y, t.z}; jo = __builtin_bit_cast(int, t.w);
-                } else {
-                    w = *reinterpret_cast<const P3 *>(own + i * 3); jo = J.idx_own[i];
-                }
-                P3 ot{0.0f, 0.0f, 0.0f};  // the own term
-                if ((first && own_first) || (last && !own_first)) {
-                    const P3 o = *reinterpret_cast<const P3 *>(oth + (size_t)jo * 3);
-                    ot = P3{c_own * (w.x - o.x), c_own * (w.y - o.y), c_own * (w.z - o.z)};
-                }
-                P3 a{0.0f, 0.0f, 0.0f};
-                if (!first) a = MODE == 2 ? J.part[lr] : *reinterpret_cast<const P3 *>(J.g + i * 3);
-                else if (own_first) a = P3{0.0f + ot.x, 0.0f + ot.y, 0.0f + ot.z};
-                for (int e0 = 0; e0 < c; e0 += 64) {
-                    float tx = 0.0f, ty = 0.0f, tz = 0.0f;
-                    if (e0 + lane < c) {
-                        const P3 o = *reinterpret_cast<const P3 *>(oth + (size_t)(c0 + L.list[start + e0 + lane]) * 3);
-                        tx = c_oth * (o.x - w.x); ty = c_oth * (o.y - w.y); tz = c_oth * (o.z - w.z);
-                    }
-                    const int n = c - e0 < 64 ? c - e0 : 64;
-                    for (int l = 0; l < n; ++l) {
-                        a.x = a.x - lane_val(tx, l); a.y = a.y - lane_val(ty, l); a.z = a.z - lane_val(tz, l);
-                    }
-                }
-                if (last && !own_first) a = P3{a.x + ot.x, a.y + ot.y, a.z + ot.z};
-                if (lane == 0) {
-                    if (MODE == 2) { if (last) bg_scatter_sample(J, (int)i, a); else J.part[lr] = a; }
-                    else *reinterpret_cast<P3 *>(J.g + i * 3) = a;
-                }
-            } else {
-                const int jo = J.idx_own[i];
-                for (int d = 0; d < D; ++d) {
-                    const float wd = own[i * D + d];
-                    const float ot = c_own * (wd - oth[(size_t)jo * D + d]);
-                    float a = first ? (own_first ? 0.0f + ot : 0.0f) : J.g[i * D + d];
-                    for (int e0 = 0; e0 < c; e0 += 64) {
-                        float t = 0.0f;
-                        if (e0 + lane < c) t = c_oth * (oth[(size_t)(c0 + L.list[start + e0 + lane]) * D + d] - wd);
-                        const int n = c - e0 < 64 ? c - e0 : 64;
-                        for (int l = 0; l < n; ++l) a = a - lane_val(t, l);
-                    }
-                    if (last && !own_first) a = a + ot;
-                    if (lane == 0) J.g[i * D + d] = a;
-                }
-            }
-        }
+        bg_long_rows<MODE>(L, J, R, T);  // (4)
         BG_STAMP(5);
-        BG_STOP(5);
-        // (5) the owners: short lists ordered in registers, subtracted in order (no barrier between (4) and (5): the waves
-        //     touch only the lists / rows of the long rows, which the owners skip).  Row by row: two rows at a time with every
-        //     stage's LDS reads issued together was measured slower at every list cap (4 / 6 / 8: the arrays of both rows spill)
-#pragma unroll
-        for (int u = 0; u < kBgPer; ++u) {
-            const int lr = tid + u * kBgThreads;
-            if (!(u < rpt && lr < nrows)) continue;
-            const int start = L.start[lr], c = (int)L.start[lr + 1] - start;
-            if (c > kBgSmall || (c == 0 && !first && !last)) continue;
-            unsigned int e[kBgSmall];
-#pragma unroll
-            for (int k = 0; k < kBgSmall; ++k) e[k] = k < c ? (unsigned int)L.list[start + k] : 0xFFFFu;
-            if (c > 4) {
-                ce(e[0], e[1]); ce(e[2], e[3]); ce(e[4], e[5]); ce(e[6], e[7]);
-                ce(e[0], e[2]); ce(e[1], e[3]); ce(e[4], e[6]); ce(e[5], e[7]);
-                ce(e[1], e[2]); ce(e[5], e[6]); ce(e[0], e[4]); ce(e[3], e[7]);
-                ce(e[1], e[5]); ce(e[2], e[6]);
-                ce(e[1], e[4]); ce(e[3], e[6]);
-                ce(e[2], e[4]); ce(e[3], e[5]);
-                ce(e[3], e[4]);
-            } else if (c > 2) {
-                ce(e[0], e[1]); ce(e[2], e[3]); ce(e[0], e[2]); ce(e[1], e[3]); ce(e[1], e[2]);
-            } else if (c == 2) {
-                ce(e[0], e[1]);
-            }
-            const size_t i = (size_t)(J.r0 + lr);
-            const int jo = jown[u];
-            if (D3) {
-                const P3 w{wx[u], wy[u], wz[u]};
-                P3 ot{0.0f, 0.0f, 0.0f};
-                if ((first && own_first) || (last && !own_first)) {
-                    const P3 o{ojx[u], ojy[u], ojz[u]};
-                    ot = P3{c_own * (w.x - o.x), c_own * (w.y - o.y), c_own * (w.z - o.z)};
-                }
-                P3 a{0.0f, 0.0f, 0.0f};
-                if (!first) a = MODE == 2 ? J.part[lr] : *reinterpret_cast<const P3 *>(J.g + i * 3);
-                else if (own_first) a = P3{0.0f + ot.x, 0.0f + ot.y, 0.0f + ot.z};
-                {
-#pragma unroll
-                    for (int h = 0; h < kBgSmall; h += 4) {  // four gathers in flight
-                        if (h >= c) break;
-                        float ox[4], oy[4], oz[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {  // (unconditional: a slot beyond the list re-reads the round's first row)
-                            const P3 t = *reinterpret_cast<const P3 *>(oth + (size_t)(c0 + (h + k < c ? e[h + k] : 0u)) * 3);
-                            ox[k] = t.x; oy[k] = t.y; oz[k] = t.z;
-                        }
-                        asm volatile("" : "+v"(ox[0]), "+v"(oy[0]), "+v"(oz[0]), "+v"(ox[1]), "+v"(oy[1]), "+v"(oz[1]), "+v"(ox[2]), "+v"(oy[2]),
-                                          "+v"(oz[2]), "+v"(ox[3]), "+v"(oy[3]), "+v"(oz[3]));  // (all four requested before the first is used)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (h + k < c) {
-                                a.x = a.x - c_oth * (ox[k] - w.x);
-                                a.y = a.y - c_oth * (oy[k] - w.y);
-                                a.z = a.z - c_oth * (oz[k] - w.z);
-                            }
-                    }
-                }
-                if (last && !own_first) a = P3{a.x + ot.x, a.y + ot.y, a.z + ot.z};
-                if (MODE == 2) { if (last) bg_scatter_sample(J, (int)i, a); else J.part[lr] = a; }
-                else *reinterpret_cast<P3 *>(J.g + i * 3) = a;
-            } else {
-                for (int d = 0; d < D; ++d) {
-                    const float wd = own[i * D + d];
-                    const float ot = c_own * (wd - oth[(size_t)jo * D + d]);
-                    float a = first ? (own_first ? 0.0f + ot : 0.0f) : J.g[i * D + d];
-#pragma unroll
-                    for (int k = 0; k < kBgSmall; ++k)
-                        if (k < c) a = a - c_oth * (oth[(size_t)(c0 + e[k]) * D + d] - wd);
-                    if (last && !own_first) a = a + ot;
-                    J.g[i * D + d] = a;
-                }
-            }
-        }
+        bg_owners<MODE>(L, J, R, T);     // (5)
         BG_STAMP(6);
-        if (!last) __syncthreads();  // the next round reuses the image / start / list (and reads the accumulators back)
+        if (!R.last) __syncthreads();  // the next round reuses the image / start / list (and reads the accumulators back)
     }
 }
 
@@ -464,13 +506,7 @@ struct SgTabJobs {
     unsigned char *blob[2];
     int F[2], n[2], B;
 };
-static_assert(kBgThreads == sg::kSgThreads, "row blocks and table blocks share a launch");
-#ifdef FX3D_RIDE_NOINLINE  // (A/B: the passengers as calls, the row blocks' register allocation as without them)
-#define FX3D_RIDE_FN __attribute__((noinline))
-#else
-#define FX3D_RIDE_FN __forceinline__
-#endif
-__device__ FX3D_RIDE_FN void bg_passenger_block(int e, const SgTabJobs &tj, int ntab, const meshreg::Ride &ride, unsigned char *tab_lds) {
+__device__ __forceinline__ void bg_passenger_block(int e, const SgTabJobs &tj, int ntab, const meshreg::Ride &ride, unsigned char *tab_lds) {
     if (e >= ntab) {  // the regularisers' adjoint (mesh_reg.h): reads the vertices and the forward's unit rows, writes gverts
         meshreg::adj_block(ride, e - ntab);
         return;
@@ -486,7 +522,7 @@ __device__ FX3D_RIDE_FN void bg_passenger_block(int e, const SgTabJobs &tj, int 
 // RIDE: the launch carries passengers behind its nrow row blocks (fx3d_chamfer_sampled_bwd's first launch); fx3d_chamfer_bwd's own
 // launches are compiled without them
 template <bool D3, bool RIDE>
-__global__ __launch_bounds__(kBgThreads, FX3D_BG_OCC) void chamfer_bwd_gather_kernel(
+__global__ __launch_bounds__(kBgThreads, kBgOcc) void chamfer_bwd_gather_kernel(
     const float *__restrict__ x, int N, const float *__restrict__ y, int M, int D, const int32_t *__restrict__ idx_x,
     const int32_t *__restrict__ idx_y, float ca, float cb, float *__restrict__ gx, float *__restrict__ gy, int nsplit, int npass,
     SgTabJobs tj, int ntab, meshreg::Ride ride) {
@@ -514,7 +550,7 @@ __global__ __launch_bounds__(kBgThreads, FX3D_BG_OCC) void chamfer_bwd_gather_ke
 // the three vertices of its sampled face with global float atomics (sums in arrival order) instead of being written out.  A side
 // without a mesh gradient (gverts == nullptr) is skipped.  (The ORDERED form -- fx3d_chamfer_sampled_bwd with the vertex -> face
 // tables -- is two launches: chamfer_bwd_gather_kernel writes the rows, sample_bwd_gather_kernel gathers them, sample_gather.h.)
-__global__ __launch_bounds__(kBgThreads, FX3D_BG_OCC) void chamfer_sampled_bwd_kernel(
+__global__ __launch_bounds__(kBgThreads, kBgOcc) void chamfer_sampled_bwd_kernel(
     const float *__restrict__ x, int N, const float *__restrict__ y, int M, const int32_t *__restrict__ idx_x,
     const int32_t *__restrict__ idx_y, float ca, float cb, SampledSide sx, SampledSide sy, int nsplit) {
     __shared__ BgLds L;
@@ -556,25 +592,14 @@ struct BgPassengers {
 };
 fx3d_status launch_bwd_gather(const float *x, int N, const float *y, int M, int B, int D, const int32_t *idx_x, const int32_t *idx_y,
                               ChamferCoef c, float *gx, float *gy, int nsplit, const BgPassengers *pass, hipStream_t st) {
-    const int sides = (gx ? 1 : 0) + (gy ? 1 : 0);
-    const dim3 block(kBgThreads);
-    if (!pass) {
-        ProfileScope prof("chamfer_bwd", st);
-        const dim3 grid(sides * B * nsplit);
-        if (D == 3)
-            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<true, false>), grid, block, 0, st, x, N, y, M, D, idx_x, idx_y, c.ca, c.cb, gx, gy,
-                               nsplit, 0, SgTabJobs{}, 0, meshreg::Ride{});
-        else
-            hipLaunchKernelGGL((chamfer_bwd_gather_kernel<false, false>), grid, block, 0, st, x, N, y, M, D, idx_x, idx_y, c.ca, c.cb, gx, gy,
-                               nsplit, 0, SgTabJobs{}, 0, meshreg::Ride{});
-    } else {
-        if (pass->ntab)
-            FX3D_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&chamfer_bwd_gather_kernel<true, true>), (int)kTabLds, "chamfer_bwd_gather_kernel"));
-        ProfileScope prof("chamfer_sampled_bwd", st);
-        const int npass = pass->ntab + (pass->ride ? pass->ride->nadj : 0);
-        hipLaunchKernelGGL((chamfer_bwd_gather_kernel<true, true>), dim3(npass + sides * B * nsplit), block, pass->lds, st, x, N, y, M, D, idx_x,
-                           idx_y, c.ca, c.cb, gx, gy, nsplit, npass, pass->tj, pass->ntab, pass->ride ? *pass->ride : meshreg::Ride{});
-    }
+    const BgPassengers P = pass ? *pass : BgPassengers{};
+    const auto kernel = pass ? chamfer_bwd_gather_kernel<true, true>
+                             : (D == 3 ? chamfer_bwd_gather_kernel<true, false> : chamfer_bwd_gather_kernel<false, false>);
+    if (P.ntab) FX3D_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)kTabLds, "chamfer_bwd_gather_kernel"));
+    const int sides = (gx ? 1 : 0) + (gy ? 1 : 0), npass = P.ntab + (P.ride ? P.ride->nadj : 0);
+    ProfileScope prof(pass ? "chamfer_sampled_bwd" : "chamfer_bwd", st);
+    hipLaunchKernelGGL(kernel, dim3(npass + sides * B * nsplit), dim3(kBgThreads), P.lds, st, x, N, y, M, D, idx_x, idx_y, c.ca, c.cb, gx, gy,
+                       nsplit, npass, P.tj, P.ntab, P.ride ? *P.ride : meshreg::Ride{});
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
@@ -619,18 +644,14 @@ __attribute__((visibility("default"))) int fx3d_debug_bg_probe(unsigned long lon
 }  // extern "C"
 
 namespace {
-struct SampledArgs {
-    const int32_t *faces; int32_t Vmax, Fmax; const int32_t *face_idx; const float *r1, *r2; float *gverts;
-    const int32_t *vf_rowptr, *vf_ent;
-};
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // The ordered form's scratch: the chamfer adjoint's rows of both sides, then the gather's tables of both sides (one blob per mesh), every
 // part 256-byte aligned.  ASYMMETRY, on purpose: `total` is sized for the largest face count the ordered form takes at these draw counts
 // (kSgMaxF -- the size query need not name Fmax), while the blobs are laid out with the stride of the ACTUAL Fmax, y's behind the blobs
-// x actually has.
+// x actually has (nothing lies behind y's, so y's mesh does not enter).
 struct SampledWs {
     size_t gsx, gsy, tbx, tby, total;  // byte offsets
-    static SampledWs plan(int N, int M, int B, int Fmax_x, int /*Fmax_y*/, bool want_x, bool /*want_y*/) {  // (nothing lies behind y's blobs)
+    static SampledWs plan(int N, int M, int B, int Fmax_x, bool want_x) {
         SampledWs w{};
         w.gsy = w.gsx + al256(sizeof(float) * 3 * (size_t)N * B);
         w.tbx = w.gsy + al256(sizeof(float) * 3 * (size_t)M * B);
@@ -649,16 +670,19 @@ struct FwdBwdWs {
         return FX3D_OK;
     }
 };
+// ax / ay: the two sides, x's first; a side without gverts gets no gradient
 fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, const float *y, int32_t M, int32_t B, const int32_t *idx_x,
-                                     const int32_t *idx_y, float w1, float w2, float gout, int64_t B_global, const SampledArgs &ax,
-                                     const SampledArgs &ay, int32_t accumulate, const sg::SgStep &step_x, void *ws, size_t ws_bytes,
+                                     const int32_t *idx_y, float w1, float w2, float gout, int64_t B_global, const SampledSide &ax,
+                                     const SampledSide &ay, int32_t accumulate, const sg::SgStep &step_x, void *ws, size_t ws_bytes,
                                      fx3d_stream_t s, const fx3d_mesh_reg *reg = nullptr) {
+    const SampledSide *const side[2] = {&ax, &ay};
+    const int cnt[2] = {N, M};  // a side's samples
     fx3d_status rc = chamfer_check_shapes(fn, x, N, y, M, B, 3);
     if (rc) return rc;
     FX3D_REQUIRE(idx_x && idx_y, "%s: null index array", fn);
     FX3D_REQUIRE(ax.gverts || ay.gverts, "%s: no gradient requested", fn);
-    FX3D_REQUIRE(!ax.gverts || (ax.faces && ax.face_idx && ax.r1 && ax.r2 && ax.Vmax > 0 && ax.Fmax > 0), "%s: incomplete mesh of x", fn);
-    FX3D_REQUIRE(!ay.gverts || (ay.faces && ay.face_idx && ay.r1 && ay.r2 && ay.Vmax > 0 && ay.Fmax > 0), "%s: incomplete mesh of y", fn);
+    for (int k = 0; k < 2; ++k)
+        FX3D_REQUIRE(!side[k]->gverts || side[k]->complete(), "%s: incomplete mesh of %s", fn, k ? "y" : "x");
     FX3D_REQUIRE((ax.vf_rowptr == nullptr) == (ax.vf_ent == nullptr) && (ay.vf_rowptr == nullptr) == (ay.vf_ent == nullptr),
                  "%s: vf_rowptr and vf_ent go together", fn);
     FX3D_REQUIRE(B_global >= B, "%s: B_global < B", fn);
@@ -668,7 +692,8 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
     FX3D_REQUIRE((long long)2 * B * nsplit < (1ll << 30), "%s: batch too large", fn);
     // Ordered form (no float atomics, bit-identical to the oracle): every requested side comes with its vertex -> face table and
     // fits the gather's LDS tables.  Otherwise: the float-atomic scatter.
-    const bool ordered = (!ax.gverts || (ax.vf_rowptr && sg::sg_fits(ax.Fmax, N))) && (!ay.gverts || (ay.vf_rowptr && sg::sg_fits(ay.Fmax, M)));
+    bool ordered = true;
+    for (int k = 0; k < 2; ++k) ordered = ordered && (!side[k]->gverts || (side[k]->vf_rowptr && sg::sg_fits(side[k]->Fmax, cnt[k])));
     FX3D_REQUIRE(!step_x.vel || (ordered && ax.gverts), "%s: the optimiser step needs the ordered form (vertex -> face table, draws that fit "
                  "fx3d_sample_points_bwd_ordered)", fn);
     // the fit iteration's regularisers (fx3d_mesh_reg): their adjoint writes gverts_x, the sampling adjoint then accumulates on top
@@ -692,40 +717,41 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
         // was built and measured equal inside the fit loop's graph, 104 against 105 us per iteration: the gather's tables, 7 us, do
         // overlap the rows there, but its tail -- acquire, staging, walk: ~9 us -- does not shrink; not kept: a bounded spin and a
         // dispatch-order argument for nothing.)
-        const SampledWs W = SampledWs::plan(N, M, B, ax.Fmax, ay.Fmax, ax.gverts != nullptr, ay.gverts != nullptr);
+        const SampledWs W = SampledWs::plan(N, M, B, ax.Fmax, ax.gverts != nullptr);
         FX3D_TRY(ws_check(fn, "workspace", ws, ws_bytes, W.total));
         unsigned char *w = static_cast<unsigned char *>(ws);
-        float *gsx = reinterpret_cast<float *>(w + W.gsx), *gsy = reinterpret_cast<float *>(w + W.gsy);
-        unsigned char *tbx = w + W.tbx, *tby = w + W.tby;
-        {
-            // the rows of the requested sides + (in front of them, one block per mesh and side) the gather's tables
-            BgPassengers P{};
-            P.tj.B = B;
-            P.ride = ride;
-            if (ax.gverts) { P.tj.face_idx[0] = ax.face_idx; P.tj.blob[0] = tbx; P.tj.F[0] = ax.Fmax; P.tj.n[0] = N; P.lds = std::max(P.lds, sg::sg_tables_lds_bytes(ax.Fmax, N)); P.ntab += B; }
-            if (ay.gverts) { P.tj.face_idx[1] = ay.face_idx; P.tj.blob[1] = tby; P.tj.F[1] = ay.Fmax; P.tj.n[1] = M; P.lds = std::max(P.lds, sg::sg_tables_lds_bytes(ay.Fmax, M)); P.ntab += B; }
-            if (P.lds > kTabLds) {  // (meshes of > ~20 000 faces: every gather block builds its own tables, as fx3d_sample_points_bwd's do)
-                P.tj = SgTabJobs{};
-                P.lds = 0; P.ntab = 0;
-                tbx = tby = nullptr;
-            }
-            const int sides = (ax.gverts ? 1 : 0) + (ay.gverts ? 1 : 0);
-            const int ns = bg_nsplit(B, sides == 2 ? (N > M ? N : M) : (ax.gverts ? N : M), sides);  // (row blocks of the requested sides only)
-            FX3D_TRY(launch_bwd_gather(x, N, y, M, B, 3, idx_x, idx_y, c, ax.gverts ? gsx : nullptr, ay.gverts ? gsy : nullptr, ns, &P, st));
+        float *const gs[2] = {reinterpret_cast<float *>(w + W.gsx), reinterpret_cast<float *>(w + W.gsy)};
+        unsigned char *tb[2] = {w + W.tbx, w + W.tby};
+        // the rows of the requested sides + (in front of them, one block per mesh and side) the gather's tables
+        BgPassengers P{};
+        P.tj.B = B;
+        P.ride = ride;
+        for (int k = 0; k < 2; ++k) {
+            const SampledSide &a = *side[k];
+            if (!a.gverts) continue;
+            P.tj.face_idx[k] = a.face_idx; P.tj.blob[k] = tb[k]; P.tj.F[k] = a.Fmax; P.tj.n[k] = cnt[k];
+            P.lds = std::max(P.lds, sg::sg_tables_lds_bytes(a.Fmax, cnt[k]));
+            P.ntab += B;
         }
-        if (ax.gverts)
-            FX3D_TRY(sg::launch_sample_bwd_gather(ax.faces, ax.Vmax, ax.Fmax, B, N, ax.face_idx, ax.r1, ax.r2, gsx, ax.vf_rowptr, ax.vf_ent, ax.gverts,
-                                                  accumulate, step_x, st, tbx));
-        if (ay.gverts)
-            FX3D_TRY(sg::launch_sample_bwd_gather(ay.faces, ay.Vmax, ay.Fmax, B, M, ay.face_idx, ay.r1, ay.r2, gsy, ay.vf_rowptr, ay.vf_ent, ay.gverts,
-                                                  accumulate, sg::SgStep{}, st, tby));
+        if (P.lds > kTabLds) {  // (meshes of > ~20 000 faces: every gather block builds its own tables, as fx3d_sample_points_bwd's do)
+            P.tj = SgTabJobs{};
+            P.lds = 0; P.ntab = 0;
+            tb[0] = tb[1] = nullptr;
+        }
+        const int sides = (ax.gverts ? 1 : 0) + (ay.gverts ? 1 : 0);
+        const int ns = bg_nsplit(B, sides == 2 ? (N > M ? N : M) : (ax.gverts ? N : M), sides);  // (row blocks of the requested sides only)
+        FX3D_TRY(launch_bwd_gather(x, N, y, M, B, 3, idx_x, idx_y, c, ax.gverts ? gs[0] : nullptr, ay.gverts ? gs[1] : nullptr, ns, &P, st));
+        for (int k = 0; k < 2; ++k) {
+            const SampledSide &a = *side[k];
+            if (a.gverts)
+                FX3D_TRY(sg::launch_sample_bwd_gather(a.faces, a.Vmax, a.Fmax, B, cnt[k], a.face_idx, a.r1, a.r2, gs[k], a.vf_rowptr, a.vf_ent,
+                                                      a.gverts, accumulate, k == 0 ? step_x : sg::SgStep{}, st, tb[k]));
+        }
         return FX3D_OK;
     }
-    if (!accumulate) {
-        if (ax.gverts) FX3D_HIP(hipMemsetAsync(ax.gverts, 0, sizeof(float) * 3 * (size_t)ax.Vmax * B, st));
-        if (ay.gverts) FX3D_HIP(hipMemsetAsync(ay.gverts, 0, sizeof(float) * 3 * (size_t)ay.Vmax * B, st));
-    }
-    const SampledSide sx{ax.faces, ax.face_idx, ax.r1, ax.r2, ax.gverts, ax.Vmax, ax.Fmax}, sy{ay.faces, ay.face_idx, ay.r1, ay.r2, ay.gverts, ay.Vmax, ay.Fmax};
+    if (!accumulate)
+        for (int k = 0; k < 2; ++k)
+            if (side[k]->gverts) FX3D_HIP(hipMemsetAsync(side[k]->gverts, 0, sizeof(float) * 3 * (size_t)side[k]->Vmax * B, st));
     // sides beyond kBgChunk samples (the reference's default is 5000): the accumulators between the rounds live in LDS
     const int maxr = N > M ? N : M;
     const size_t dyn = maxr > kBgChunk ? sizeof(P3) * (size_t)((maxr + nsplit - 1) / nsplit) : 0;
@@ -736,7 +762,7 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
     }
     ProfileScope prof("chamfer_sampled_bwd", st);
     hipLaunchKernelGGL(chamfer_sampled_bwd_kernel, dim3(2 * B * nsplit), dim3(kBgThreads), dyn, st, x, N, y, M, idx_x, idx_y, c.ca,
-                       c.cb, sx, sy, nsplit);
+                       c.cb, ax, ay, nsplit);
     FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
@@ -749,8 +775,8 @@ fx3d_status sampled_bwd_step(const char *fn, const float *x, int32_t N, const fl
                              const float *base, float *out, uint64_t *ctr, uint64_t inc, void *ws, size_t ws_bytes,
                              const fx3d_mesh_reg *reg, fx3d_stream_t s) {
     FX3D_REQUIRE(vel && params && base && out && gverts_x, "%s: null pointer", fn);
-    const SampledArgs ax{faces_x, V, F, face_idx_x, r1_x, r2_x, gverts_x, vf_rowptr_x, vf_ent_x};
-    const SampledArgs ay{};
+    const SampledSide ax{faces_x, face_idx_x, r1_x, r2_x, gverts_x, V, F, vf_rowptr_x, vf_ent_x};
+    const SampledSide ay{};
     const sg::SgStep st{rho, eta, vel, params, base, out, reinterpret_cast<unsigned long long *>(ctr), (unsigned long long)inc};
     return chamfer_sampled_bwd_impl(fn, x, N, y, M, B, idx_x, idx_y, w1, w2, gout, B, ax, ay, accumulate, st, ws, ws_bytes, s, reg);
 }
@@ -761,7 +787,7 @@ extern "C" {
 fx3d_status fx3d_chamfer_sampled_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, size_t *bytes) {
     FX3D_REQUIRE(bytes, "fx3d_chamfer_sampled_bwd_workspace_bytes: null output");
     FX3D_REQUIRE(N > 0 && M > 0 && B > 0, "fx3d_chamfer_sampled_bwd_workspace_bytes: bad sizes");
-    *bytes = SampledWs::plan(N, M, B, sg::kSgMaxF, sg::kSgMaxF, true, true).total;
+    *bytes = SampledWs::plan(N, M, B, sg::kSgMaxF, true).total;
     return FX3D_OK;
 }
 
@@ -773,8 +799,8 @@ fx3d_status fx3d_chamfer_sampled_bwd(const float *x, int32_t N, const float *y, 
                                      const float *r2_y, float *gverts_y, int32_t accumulate, const int32_t *vf_rowptr_x,
                                      const int32_t *vf_ent_x, const int32_t *vf_rowptr_y, const int32_t *vf_ent_y, void *ws,
                                      size_t ws_bytes, fx3d_stream_t s) {
-    const SampledArgs ax{faces_x, Vmax_x, Fmax_x, face_idx_x, r1_x, r2_x, gverts_x, vf_rowptr_x, vf_ent_x};
-    const SampledArgs ay{faces_y, Vmax_y, Fmax_y, face_idx_y, r1_y, r2_y, gverts_y, vf_rowptr_y, vf_ent_y};
+    const SampledSide ax{faces_x, face_idx_x, r1_x, r2_x, gverts_x, Vmax_x, Fmax_x, vf_rowptr_x, vf_ent_x};
+    const SampledSide ay{faces_y, face_idx_y, r1_y, r2_y, gverts_y, Vmax_y, Fmax_y, vf_rowptr_y, vf_ent_y};
     return chamfer_sampled_bwd_impl("fx3d_chamfer_sampled_bwd", x, N, y, M, B, idx_x, idx_y, w1, w2, gout, B_global, ax, ay, accumulate,
                                     sg::SgStep{}, ws, ws_bytes, s);
 }

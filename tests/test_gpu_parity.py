@@ -281,6 +281,64 @@ def test_chamfer_backward_long_inverse_lists(gpu_fx, oracle, kind, D):
     assert np.array_equal(hy.view(np.uint32), ogy.view(np.uint32)), np.abs(hy - ogy).max()
 
 
+@pytest.mark.parametrize("N,M", [(300, 3600), (300, 7700), (600, 7700)])
+def test_chamfer_backward_more_long_rows_than_the_lds_table(gpu_fx, oracle, N, M):
+    """More rows with long lists in ONE block than the 256 whose point and index travel through LDS: the wave that takes such a
+    row re-reads both from memory.  D = 3, B = 160, iy[j] = j % 300: rows 0 .. 299 of side x each get 12 entries of every
+    4096-row round (13 or 14 of a full one) -- all long (> 8); a round has at most 4096 entries in all, and 300 <= the 456 rows
+    the list of long rows holds.  They belong to one block: blocks per (cloud, side) = max(1, CUs / (2 B)), = 1 for B = 160 on any device
+    below 320 CUs, raised until a block's share of max(N, M) rows is at most 4096 -- so 1 at M = 3600 (one round), and 2 at
+    M = 7700 (two rounds: rows past the table also reload their accumulator), where N = 300 leaves a block 150 rows, all in the
+    table, and N = 600 gives the first block rows 0 .. 299.  Bit-identical to the oracle."""
+    fx = gpu_fx
+    B = 160
+    rng = np.random.default_rng(7 * N + M)
+    x = np.asfortranarray(rng.standard_normal((3, N, B)).astype(np.float32))
+    y = np.asfortranarray(rng.standard_normal((3, M, B)).astype(np.float32))
+    ix = np.asfortranarray(rng.integers(0, M, (N, B)).astype(np.int32))
+    iy = np.asfortranarray(np.repeat((np.arange(M, dtype=np.int32) % 300)[:, None], B, axis=1))
+    ogx, ogy = oracle.chamfer_bwd(x, y, ix, iy, 0.9, 1.1, 1.0)
+    gx, gy = fx.chamfer_distance_grad(x, y, fx.gpu(ix), fx.gpu(iy), w1=0.9, w2=1.1, gout=1.0)
+    hx, hy = gx.to_host(), gy.to_host()
+    assert np.array_equal(hx.view(np.uint32), ogx.view(np.uint32)), np.abs(hx - ogx).max()
+    assert np.array_equal(hy.view(np.uint32), ogy.view(np.uint32)), np.abs(hy - ogy).max()
+
+
+@pytest.mark.parametrize("ordered", [True, False])
+@pytest.mark.parametrize("kind", ["all_to_one", "clusters"])
+def test_chamfer_sampled_adjoint_long_inverse_lists(gpu_fx, kind, ordered):
+    """The sampled entry points with index maps GIVEN, so that their lists are long (real nearest-neighbour maps have short
+    ones): one row the neighbour of thousands, tight clusters -- the kinds of test_chamfer_backward_long_inverse_lists at
+    n = 4200 samples, two rounds.  Against fx3d_chamfer_bwd followed by fx3d_sample_points_bwd on the same draws: the ordered
+    form bit for bit; the scatter form (long rows through the accumulators in LDS) up to the order of its float atomics."""
+    fx = gpu_fx
+    paths = [os.path.join(GOLDEN, "teapot.obj"), os.path.join(GOLDEN, "sphere.obj")]
+    ma, mb = fx.gpu(fx.load_trimesh(paths[0], paths[1])), fx.gpu(fx.load_trimesh(paths[1], paths[0]))
+    n, nb = 4200, 2
+    assert fx.sampling_adjoint_is_ordered(ma, n) and fx.sampling_adjoint_is_ordered(mb, n)
+    A, fa, ra1, ra2 = fx.sample_points(ma, n, seed=5, return_draws=True)
+    Bp, fb, rb1, rb2 = fx.sample_points(mb, n, seed=6, return_draws=True)
+    rng = np.random.default_rng(sum(map(ord, kind)))
+    if kind == "all_to_one":
+        ix = np.full((n, nb), 7, np.int32); iy = np.full((n, nb), n - 1, np.int32)
+        ix[::3, 1] = n - 2
+    else:
+        ix = rng.integers(0, 40, (n, nb)).astype(np.int32) * (n // 40)
+        iy = rng.integers(0, 30, (n, nb)).astype(np.int32) * (n // 30)
+    ix, iy = fx.gpu(np.asfortranarray(ix)), fx.gpu(np.asfortranarray(iy))
+    gA, gB = fx.chamfer_distance_grad(A, Bp, ix, iy, w1=0.9, w2=1.1, gout=1.5)
+    ref_a = fx.sample_points_grad(ma, fa, ra1, ra2, gA).to_host()
+    ref_b = fx.sample_points_grad(mb, fb, rb1, rb2, gB).to_host()
+    assert np.isfinite(ref_a).all() and np.abs(ref_a).max() > 0
+    ga, gb = fx.chamfer_sampled_grad(A, Bp, ix, iy, ma, (fa, ra1, ra2), mb, (fb, rb1, rb2), w1=0.9, w2=1.1, gout=1.5, ordered=ordered)
+    ha, hb = ga.to_host(), gb.to_host()
+    if ordered:
+        assert np.array_equal(ha.view(np.uint32), ref_a.view(np.uint32)), np.abs(ha - ref_a).max()
+        assert np.array_equal(hb.view(np.uint32), ref_b.view(np.uint32)), np.abs(hb - ref_b).max()
+    else:
+        assert np.allclose(ha, ref_a, rtol=2e-4, atol=1e-8) and np.allclose(hb, ref_b, rtol=2e-4, atol=1e-8)
+
+
 def test_invalid_arguments_raise(gpu_fx):
     fx = gpu_fx
     x = _rand((3, 10, 2), 0)
