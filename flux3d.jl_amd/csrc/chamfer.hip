@@ -276,6 +276,37 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
         int *gb = reinterpret_cast<int *>(wq + (kHThreads / 64) * 96) + 64 * 8;
         for (int i = tid; i < kHGroupsMax * 8; i += kHThreads) gb[i] = (i & 4) ? (int)0x80000000 : 0x7fffffff;  // lo keys: +max, hi keys: -max
     }
+    // (PRUNE) The query cloud's bounding box as integer keys, into the spare group slot (`qbb`; initialised with the groups' above): the
+    // frame of the grid the queries are sorted in.  It needs the four rows requested above and nothing of the cloud pass, so it
+    // runs between that pass's two barriers, where fifteen waves would otherwise only wait for the first wave's cross-wave
+    // reduction -- not in the counting phase behind them, which is bound by the VALU (it stood there: 0.3 us of 34.8 at B = 32,
+    // N = M = 4096; the first wave taking its own box to the counting phase, or weaving it into its reduction, measured no
+    // better and spilt two more scalars).  Like the rows it is guarded by the entry loads' condition, not by `sorted_q`, which is
+    // not known yet: without a sort the box goes unused.  Rows past the cloud (clamped loads) stay out; NaN keys enter as before.
+    [[maybe_unused]] auto query_key_box = [&]() {
+        int *qbb = reinterpret_cast<int *>(wq + (kHThreads / 64) * 96) + (64 * 2 + kHGroupsMax * 2 - 2) * 4;
+        int kl[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, kh[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int qp = 256 * wv + 64 * e + lane;
+            if (qp < NQ) {
+                const int k3[3] = {fkey(qv[e].x), fkey(qv[e].y), fkey(qv[e].z)};
+#pragma unroll
+                for (int d = 0; d < 3; ++d) { kl[d] = kl[d] < k3[d] ? kl[d] : k3[d]; kh[d] = kh[d] > k3[d] ? kh[d] : k3[d]; }
+            }
+        }
+        int a[3], b2[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            a[d] = row_mm_key<false>(kl[d]); b2[d] = row_mm_key<true>(kh[d]);
+            a[d] = imm<false>(a[d], dpp_keepi<0x142, 0xA>(a[d])); a[d] = imm<false>(a[d], dpp_keepi<0x143, 0xC>(a[d]));
+            b2[d] = imm<true>(b2[d], dpp_keepi<0x142, 0xA>(b2[d])); b2[d] = imm<true>(b2[d], dpp_keepi<0x143, 0xC>(b2[d]));
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { atomicMin(qbb + d, a[d]); atomicMax(qbb + 4 + d, b2[d]); }
+        }
+    };
     FX3D_PROBE_MARK(0);
 
     // ---- bounding box and mean -> centre mu = the MEAN (a stray far point moves the box centre, hardly the mean), largest
@@ -376,6 +407,9 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 o4[1] = float4{vm, fin ? 1.0f : 0.0f, 0.0f, 0.0f};
                 if (PRUNE) { o4[2] = float4{lo3[0], lo3[1], lo3[2], 0.0f}; o4[3] = float4{hi3[0], hi3[1], hi3[2], 0.0f}; }
             }
+        }
+        if constexpr (PRUNE) {  // (the first wave after its reduction, the others at once)
+            if (NQ <= 4 * kHThreads) query_key_box();
         }
         __syncthreads();
         {
@@ -541,32 +575,41 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 if (mine) rank = add(t, 1u);
                 return rank;
             };
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int pt = e * kHThreads + tid;
-                const unsigned int t = pt < cnt ? cell(cv[e].x, cv[e].y, cv[e].z) : 0u;
-                ccr[e] = (t << 16) | count_cells(pt < cnt, t, [&](unsigned int c, unsigned int n) { return atomicAdd(&ccnt[c], n); });
-            }
-            int *qbb = reinterpret_cast<int *>(boxes + 64 * 2 + kHGroupsMax * 2 - 2);  // the query cloud's box as keys: the spare group slot (initialised with the groups')
-            if (sorted_q) {
-                int kl[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, kh[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+            // A thread's four points of a cloud: ONE test for a crowded instruction among the four -- lanes whose neighbour sits in the
+            // same cell, in any of them: at least as many as in each -- and a plain atomic per point where it does not fire (clean
+            // clouds: never); where it does, every instruction is taken as above.  Either way the atomics of a wave are issued in
+            // the order of e, so a query's rank within (wave, cell) is e ascending, then lane ascending.
+            auto count_cells4 = [&](const bool (&valid)[4], const unsigned int (&t)[4], unsigned int (&cr)[4], auto &&add) {
+                unsigned long long nb = 0ull;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int qp = 256 * wv + 64 * e + lane;
-                    if (qp < NQ) {
-                        const int k3[3] = {fkey(qv[e].x), fkey(qv[e].y), fkey(qv[e].z)};
+                    // (lanes past the cloud and a row's first lane, which reads 0, may count as well: the test only has to fire wherever one of the four would)
+                    nb |= __builtin_amdgcn_ballot_w64(t[e] == (unsigned int)dpp_movi<0x111>((int)t[e]));  // row_shr:1
+                }
+                if ((int)__builtin_popcountll(nb) < 8) {
 #pragma unroll
-                        for (int d = 0; d < 3; ++d) { kl[d] = kl[d] < k3[d] ? kl[d] : k3[d]; kh[d] = kh[d] > k3[d] ? kh[d] : k3[d]; }
+                    for (int e = 0; e < 4; ++e) {
+                        unsigned int rank = 0u;
+                        if (valid[e]) rank = add(t[e], 1u);
+                        cr[e] = (t[e] << 16) | rank;
                     }
+                    return;
                 }
 #pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    int a = row_mm_key<false>(kl[d]), b2 = row_mm_key<true>(kh[d]);
-                    a = imm<false>(a, dpp_keepi<0x142, 0xA>(a)); a = imm<false>(a, dpp_keepi<0x143, 0xC>(a));
-                    b2 = imm<true>(b2, dpp_keepi<0x142, 0xA>(b2)); b2 = imm<true>(b2, dpp_keepi<0x143, 0xC>(b2));
-                    if (lane == 63) { atomicMin(qbb + d, a); atomicMax(qbb + 4 + d, b2); }
+                for (int e = 0; e < 4; ++e) cr[e] = (t[e] << 16) | count_cells(valid[e], t[e], add);
+            };
+            {
+                bool cval[4];
+                unsigned int ct[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int pt = e * kHThreads + tid;
+                    cval[e] = pt < cnt;
+                    ct[e] = cval[e] ? cell(cv[e].x, cv[e].y, cv[e].z) : 0u;
                 }
+                count_cells4(cval, ct, ccr, [&](unsigned int c, unsigned int n) { return atomicAdd(&ccnt[c], n); });
             }
+            const int *qbb = reinterpret_cast<const int *>(boxes + 64 * 2 + kHGroupsMax * 2 - 2);  // the query cloud's box as keys (query_key_box, in the cloud pass)
             FX3D_PROBE_MARK2(2);
             __syncthreads();
             FX3D_PROBE_MARK2(3);
@@ -615,17 +658,20 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
             };
             if (wv == 0) curve_scan(ccnt);  // the candidates' cells -> first image rows
             if (sorted_q) {                  // the queries' cells, counted per wave
+                bool qval[4];
+                unsigned int qt[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int qp = 256 * wv + 64 * e + lane;
-                    const unsigned int t = qp < NQ ? qcell(qv[e].x, qv[e].y, qv[e].z) : 0u;
-                    qcr[e] = (t << 16) | count_cells(qp < NQ, t, [&](unsigned int c, unsigned int n) {
-                                 const unsigned int sh = 16u * (c & 1u);
-                                 const unsigned int old = atomicAdd(&qwh[wv * 256 + (c >> 1)], n << sh);
-                                 atomicAdd(&qtot[c], n);
-                                 return (old >> sh) & 0xffffu;
-                             });
+                    qval[e] = qp < NQ;
+                    qt[e] = qval[e] ? qcell(qv[e].x, qv[e].y, qv[e].z) : 0u;
                 }
+                count_cells4(qval, qt, qcr, [&](unsigned int c, unsigned int n) {
+                    const unsigned int sh = 16u * (c & 1u);
+                    const unsigned int old = atomicAdd(&qwh[wv * 256 + (c >> 1)], n << sh);
+                    atomicAdd(&qtot[c], n);
+                    return (old >> sh) & 0xffffu;
+                });
             }
             FX3D_PROBE_MARK2(4);
             __syncthreads();
@@ -838,13 +884,22 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 // 690 us instead of ~100 for C2's shape with an extent ratio of 250.  (The padding slot stays unscaled: 4.3e9.)
                 float sq = 1.0f, fl_s = 0.0f;
                 float rsq = 1.0f;  // 1 / sq, exactly
-                if (S >= 3.0e4f && S < 0x1p28f) {
-                    int e;
-                    (void)frexpf(S, &e);          // S = f 2^e, f in [0.5, 1)
-                    sq = ldexpf(1.0f, 14 - e);    // sq S in [2^13, 2^14); sq >= 2^-14: a normal fp16
-                    rsq = ldexpf(1.0f, e - 14);   // (e = 15 ... 28: 2 ... 2^14)
-                    m0 *= sq; m1 *= sq; m2 *= sq; S *= sq;
-                    fl_s = 0x1p-15f;              // fp16 subnormal quantum of a scaled-down small component x |c~_d| <= 2^-25 x 3 x 128
+                // (PRUNE: behind a wave-uniform branch -- a wave without such a query, the usual one, skips the instructions: 0.14 us)
+                const bool own_scale = S >= 3.0e4f && S < 0x1p28f;
+                bool any_own = true;
+                if constexpr (PRUNE) any_own = __builtin_amdgcn_ballot_w64(own_scale) != 0ull;
+                if (any_own) {
+                    // (an empty statement the compiler may not drop keeps the branch: it otherwise folds the test into the lanes' mask
+                    //  and every wave issues the eight instructions below with no lane active)
+                    if constexpr (PRUNE) asm volatile("; a query with a scale of its own in this wave" ::);
+                    if (own_scale) {
+                        int e;
+                        (void)frexpf(S, &e);          // S = f 2^e, f in [0.5, 1)
+                        sq = ldexpf(1.0f, 14 - e);    // sq S in [2^13, 2^14); sq >= 2^-14: a normal fp16
+                        rsq = ldexpf(1.0f, e - 14);   // (e = 15 ... 28: 2 ... 2^14)
+                        m0 *= sq; m1 *= sq; m2 *= sq; S *= sq;
+                        fl_s = 0x1p-15f;              // fp16 subnormal quantum of a scaled-down small component x |c~_d| <= 2^-25 x 3 x 128
+                    }
                 }
                 qok = S < 3.0e4f;  // inside the fp16 range (also false for NaN)
                 qfin = fabsf(qr[0]) + fabsf(qr[1]) + fabsf(qr[2]) < INFINITY;
