@@ -7,7 +7,8 @@
 // instruction's k: padding with zeros would turn an Inf weight into NaN) and the dense heads run the same chain as v_fma_f32.
 // No split of a contraction over waves or blocks, no float atomics: the bits do not depend on the launch shape.
 //
-// Two kernels, three rounds (stn, fstn, feat):
+// Two kernels, three rounds (stn, fstn, feat).  pointnet_net.h states a round's layer chain (round_trunk) and the head's phases
+// (head_pool .. head_finish) for them, for the training-mode forward and for the adjoint; the kernels here are:
 //   pointnet_points_kernel<MODE>: one block = 64 points of one cloud, 4 waves.  The tile's activations live in two
 //     (64 x 128) LDS images (row stride 130 floats: the A-operand reads of a 32-point tile fall on 64 distinct banks; the
 //     epilogue's stores, 32 consecutive channels per lane half with the halves 4 rows = 8 banks apart, overlap on 24 banks).  A wave owns slabs of 32 output channels and computes them for both 32-point halves of the tile from
@@ -30,92 +31,36 @@ using namespace fx3d::mlp::pointnet;
 
 namespace {
 
-// the round's last layer (128 -> 1024), reduced to the tile's maxima
-template <int EPI, bool WIN>
-__device__ __forceinline__ void last_layer(const PointArgs &a, const float *in, int nvalid, int p0, float *tmax) {
-    if (WIN) {
-        const size_t at = tmax - a.tmax;
-        conv_final_win<EPI>(in, a.c3.W, a.c3.b, a.c3.bn, nvalid, p0, tmax, a.tfirst + at, a.tpre + at);
-    } else {
-        conv_mfma<128, EPI, true>(in, nullptr, kFeat, a.c3.W, a.c3.b, a.c3.bn, nvalid, tmax);
-    }
-}
-
-// WIN: the adjoint's instantiation (pointnet_grad.hip), whose last layer also writes the tile's winners (conv_final_win)
+// The round's layers (round_trunk) with the last one (128 -> 1024) reduced to the tile's maxima.  WIN: the adjoint's
+// instantiation (pointnet_grad.hip), whose last layer also writes the tile's winners (conv_final_win).
 template <int MODE, bool WIN>
 __global__ __launch_bounds__(kPtThreads) void pointnet_points_kernel(const PointArgs a) {
     extern __shared__ float lds[];
-    float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
-    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int tile = blockIdx.x, b = blockIdx.y;
     const int p0 = tile * kTile;
     const int nvalid = min(kTile, a.N - p0);
-    float *tmax = a.tmax + ((size_t)b * a.ntiles + tile) * kFeat;
-    // rows beyond the cloud's last point are zeros: they are computed and take part in nothing
-    if (MODE != 2) {
-        const float *xb = a.x + ((size_t)b * a.N + p0) * 3;
-        for (int i = tid; i < kTile * 3; i += kPtThreads) xs[i] = i < nvalid * 3 ? xb[i] : 0.0f;
-    } else {
-        const float *hb = a.h + ((size_t)b * a.N + p0) * 64;
-        for (int i = tid; i < kTile * 64; i += kPtThreads) bufA[(i >> 6) * kLd + (i & 63)] = i < nvalid * 64 ? hb[i] : 0.0f;
-    }
-    __syncthreads();
-    if (MODE == 0) {
-        conv3<kReluBn>(xs, bufA, kLd, 64, a.c1.W, a.c1.b, a.c1.bn);
-        __syncthreads();
-        conv_mfma<64, kReluBn, false>(bufA, bufB, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
-        __syncthreads();
-        last_layer<kReluBn, WIN>(a, bufB, nvalid, p0, tmax);
-    } else if (MODE == 1) {
-        conv3<kNone>(xs, xt, 3, 3, a.tf + (size_t)b * 9, nullptr, Bn{});
-        __syncthreads();
-        conv3<kBnRelu>(xt, bufA, kLd, 64, a.c0.W, a.c0.b, a.c0.bn);
-        __syncthreads();
-        float *hb = a.h + ((size_t)b * a.N + p0) * 64;
-        for (int i = tid; i < nvalid * 64; i += kPtThreads) hb[i] = bufA[(i >> 6) * kLd + (i & 63)];
-        conv_mfma<64, kReluBn, false>(bufA, bufB, 64, a.c1.W, a.c1.b, a.c1.bn, nvalid, nullptr);
-        __syncthreads();
-        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
-        __syncthreads();
-        last_layer<kReluBn, WIN>(a, bufA, nvalid, p0, tmax);
-    } else {
-        conv_mfma<64, kNone, false>(bufA, bufB, 64, a.tf + (size_t)b * 4096, nullptr, Bn{}, nvalid, nullptr);
-        __syncthreads();
-        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
-        __syncthreads();
-        last_layer<kBnOnly, WIN>(a, bufA, nvalid, p0, tmax);
-    }
+    const size_t at = ((size_t)b * a.ntiles + tile) * kFeat;
+    round_trunk<MODE, kLastLayer[MODE], true>(a, lds, b, p0, nvalid, [&](const float *in, const Conv &c, auto layer) {
+        constexpr int EPI = decltype(layer)::EPI;
+        if (WIN) conv_final_win<EPI>(in, c, nvalid, p0, a.tmax + at, a.tfirst + at, a.tpre + at);
+        else conv_mfma<128, EPI, true>(in, nullptr, kFeat, c.W, c.b, c.bn, nvalid, a.tmax + at);
+    });
 }
 
 template <bool FEAT>
 __global__ __launch_bounds__(kHeadThreads) void pointnet_head_kernel(const HeadArgs a) {
     __shared__ float v0[kFeat], v1[512], v2[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float m = fold_tile_maxima(a.tmax, a.ntiles, b);
-    v0[tid] = m;
-    if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + tid] = m;
+    head_pool<FEAT>(a, b, v0);
     __syncthreads();
     if (tid < 512) {
-        float v = relu(dense_chain(v0, kFeat, a.d1.W, 512, tid) + a.d1.b[tid]);
-        if (FEAT) v = batchnorm(v, a.bn1.g[tid], a.bn1.b[tid], a.bn1.m[tid], sqrtf(a.bn1.v[tid] + kBnEps));
-        v1[tid] = v;
+        const float v = head_relu_dense<512>(a.d1, v0);
+        v1[tid] = FEAT ? head_bn(a.bn1, v) : v;
     }
     __syncthreads();
-    if (tid < 256) {
-        const float v = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
-        v2[tid] = batchnorm(v, a.bn2.g[tid], a.bn2.b[tid], a.bn2.m[tid], sqrtf(a.bn2.v[tid] + kBnEps));
-    }
+    if (tid < 256) v2[tid] = head_bn(a.bn2, head_relu_dense<256>(a.d2, v1));
     __syncthreads();
-    for (int o = tid; o < a.n3; o += kHeadThreads) {
-        const float v = dense_chain(v2, 256, a.d3.W, a.n3, o) + a.d3.b[o];
-        if (FEAT) {
-            a.logits[(size_t)b * a.n3 + o] = relu(v);
-        } else {
-            const size_t at = (size_t)b * a.n3 + (o / a.K) + (size_t)a.K * (o % a.K);
-            a.mat[at] = v;
-            if (a.mat_user) a.mat_user[at] = v;
-        }
-    }
-    if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
+    head_finish<FEAT>(a, b, v2);
 }
 
 template <int MODE, bool WIN>
@@ -186,30 +131,20 @@ fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_classes, 
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", fn);
     const Net n = layout(params_dev, num_classes);
     hipStream_t st = as_stream(s);
-    char *wsb = static_cast<char *>(ws);
-    float *h = reinterpret_cast<float *>(wsb + w.h), *tmax = reinterpret_cast<float *>(wsb + w.tmax);
-    float *T = reinterpret_cast<float *>(wsb + w.T), *F = reinterpret_cast<float *>(wsb + w.F);
-    float *lg = logits ? logits : reinterpret_cast<float *>(wsb + w.logits);
-
+    const WsView v{static_cast<char *>(ws)};
+    float *tmax = v.f32(w.tmax), *T = v.f32(w.T), *F = v.f32(w.F);
     PointArgs p{};
-    p.x = x; p.h = h; p.tmax = tmax; p.N = N; p.ntiles = w.ntiles;
+    p.x = x; p.h = v.f32(w.h); p.tmax = tmax; p.N = N; p.ntiles = w.ntiles;
     fx3d_status r;
-    // stn: the (3, 3) input transform of every cloud
-    p.c1 = n.stn.c1; p.c2 = n.stn.c2; p.c3 = n.stn.c3;
-    if ((r = launch_points(0, false, p, B, st)) != FX3D_OK) return r;
-    if ((r = launch_head(false, stn_head(n.stn, 3, tmax, w.ntiles, T, stn), B, st)) != FX3D_OK) return r;
-    // input transform, conv_block1 (kept as h), fstn: the (64, 64) feature transform
-    p.tf = T; p.c0 = n.block1; p.c1 = n.fstn.c1; p.c2 = n.fstn.c2; p.c3 = n.fstn.c3;
-    if ((r = launch_points(1, false, p, B, st)) != FX3D_OK) return r;
-    if ((r = launch_head(false, stn_head(n.fstn, 64, tmax, w.ntiles, F, fstn), B, st)) != FX3D_OK) return r;
-    // feature transform, feat, cls, softmax
-    p.tf = F; p.c2 = n.f1; p.c3 = n.f2;
-    if ((r = launch_points(2, false, p, B, st)) != FX3D_OK) return r;
-    HeadArgs hd{};
-    hd.tmax = tmax; hd.ntiles = w.ntiles;
-    hd.d1 = n.fd1; hd.bn1 = n.fbn1; hd.d2 = n.fd2; hd.bn2 = n.fbn2; hd.d3 = n.cls;
-    hd.n3 = num_classes; hd.K = 1; hd.pooled = pooled; hd.logits = lg; hd.probs = probs;
-    return launch_head(true, hd, B, st);
+    // stn: T (3, 3) of every cloud; x T, conv_block1 (kept as h), fstn: F (64, 64); h F, feat, cls, softmax
+    for (int mode = 0; mode < 3; ++mode) {
+        set_round(p, n, mode, T, F);
+        if ((r = launch_points(mode, false, p, B, st)) != FX3D_OK) return r;
+        const HeadArgs hd = mode < 2 ? stn_head(n, mode, tmax, w.ntiles, T, F, mode == 0 ? stn : fstn)
+                                     : feat_head(n, num_classes, tmax, w.ntiles, pooled, logits ? logits : v.f32(w.logits), probs);
+        if ((r = launch_head(mode == 2, hd, B, st)) != FX3D_OK) return r;
+    }
+    return FX3D_OK;
 }
 
 }  // extern "C"

@@ -8,12 +8,12 @@
 // a second time to find its winners).  Each round keeps its own per-tile maxima.  Then, round by round from the last to the first
 // (feat, fstn, stn):
 //   pointnet_head_bwd_kernel<FEAT>: one block per cloud.  Thread c folds the tile maxima of channel c, takes the first tile whose
-//     maximum equals the cloud's -- its first point is n*(c) -- and the head's dense layers are computed again as the forward
-//     computes them (dense_chain), then walked back (transposed_chain), one thread per element.  What the sums over the clouds
+//     maximum equals the cloud's -- its first point is n*(c) -- and the head's dense layers are computed again by the forward's
+//     own phases (pointnet_net.h), then walked back (transposed_chain), one thread per element.  What the sums over the clouds
 //     need goes to the workspace: every layer's input, the gradient at its contraction, and for a BatchNorm the gradient at its
 //     output with the normalised value it was given.
 //   pointnet_trunk_bwd_kernel<MODE>: one block = 64 points of one cloud, 4 waves, three (64 x 128) LDS images of the forward's row
-//     stride.  The tile's layers below the last are computed again with the forward's own functions, the relu's output kept beside
+//     stride.  The tile's layers below the last are computed again with the forward's own functions and tile loads, the relu's output kept beside
 //     the BatchNorm's (the mask and dgamma need the former, the next contraction the latter).  The last layer's input gradient
 //     is the gather (a wave owns a point, lists its channels with ballots, ascending, and walks the list eight at a time); the rows
 //     the winners of this tile gave the last layer go to the workspace for its parameter sums.  The way back through the 64- and 128-channel layers is
@@ -40,20 +40,14 @@ constexpr size_t kTrunkLds = (size_t)(3 * kImg + 2 * kTile * 3 + 2 * kFeat + (kP
 static_assert(kTrunkLds <= kMaxLds, "the trunk adjoint's LDS");
 static_assert(kTile == FX3D_POINTNET_GRAD_TILE, "the tile of the stated sums");
 
-__device__ __forceinline__ float bn_sd(const Bn &bn, int o) { return sqrtf(bn.v[o] + kBnEps); }
-
 // ---- the head ------------------------------------------------------------------------------------------------------------------
-struct HeadBwdArgs {
-    const float *tmax;      // (1024, ntiles, B): the round's
+struct HeadBwdArgs : HeadArgs {  // the forward's head of the round: its layers, the round's tmax; pooled (1024, B), d1's input
     const int32_t *tfirst;  // (1024, ntiles, B)
     const float *tpre;      // (1024, ntiles, B)
-    int ntiles;
-    Dense d1, d2, d3;
-    Bn bn1, bn2, bn3;       // bn1: FEAT; bn3: the BatchNorm of the round's last convolution
-    int n3, K;
+    Bn bn3;                 // the BatchNorm of the round's last convolution
     const float *gup;       // FEAT: glogits (n3, B); else the gradient at the transform (K, K, B)
     int32_t *nstar;         // (1024, B): the winning point, -1 where there is none
-    float *pooled, *a1, *a2;  // the inputs of d1, d2, d3: (1024, B), (512, B), (256, B)
+    float *a1, *a2;           // the inputs of d2, d3: (512, B), (256, B)
     float *dd1, *dd2, *dd3;   // the gradients at the contractions of d1, d2, d3: (512, B), (256, B), (n3, B)
     float *gy1, *xh1;         // FEAT: the gradient at bn1's output and the normalised value it was given, (512, B)
     float *gy2, *xh2;         // the same for bn2, (256, B)
@@ -79,17 +73,17 @@ __global__ __launch_bounds__(kHeadThreads) void pointnet_head_bwd_kernel(const H
     v0[tid] = m;
     a.pooled[(size_t)b * kFeat + tid] = m;
     __syncthreads();
-    // the forward's head again; r1, r2: the relus' outputs of this thread's elements
+    // the forward's head again, phase by phase (pointnet_net.h); r1, r2: the relus' outputs of this thread's elements
     float r1 = 0.0f, r2 = 0.0f;
     if (tid < 512) {
-        r1 = relu(dense_chain(v0, kFeat, a.d1.W, 512, tid) + a.d1.b[tid]);
-        v1[tid] = FEAT ? batchnorm(r1, a.bn1.g[tid], a.bn1.b[tid], a.bn1.m[tid], bn_sd(a.bn1, tid)) : r1;
+        r1 = head_relu_dense<512>(a.d1, v0);
+        v1[tid] = FEAT ? head_bn(a.bn1, r1) : r1;
         a.a1[(size_t)b * 512 + tid] = v1[tid];
     }
     __syncthreads();
     if (tid < 256) {
-        r2 = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
-        v2[tid] = batchnorm(r2, a.bn2.g[tid], a.bn2.b[tid], a.bn2.m[tid], bn_sd(a.bn2, tid));
+        r2 = head_relu_dense<256>(a.d2, v1);
+        v2[tid] = head_bn(a.bn2, r2);
         a.a2[(size_t)b * 256 + tid] = v2[tid];
     }
     __syncthreads();
@@ -98,7 +92,7 @@ __global__ __launch_bounds__(kHeadThreads) void pointnet_head_bwd_kernel(const H
     for (int o = tid; o < a.n3; o += kHeadThreads) {
         float d;
         if (FEAT) {
-            const float l = relu(dense_chain(v2, 256, a.d3.W, a.n3, o) + a.d3.b[o]);
+            const float l = relu(head_dense3(a.d3, v2, a.n3, o));
             d = l > 0.0f ? a.gup[(size_t)b * a.n3 + o] : 0.0f;
         } else {
             d = a.gup[(size_t)b * a.n3 + (o / a.K) + (size_t)a.K * (o % a.K)];
@@ -188,12 +182,6 @@ __device__ __forceinline__ void bn_image(const float *r, float *out, int C, cons
         const int p = i / C, c = i - p * C;
         out[p * kLd + c] = batchnorm(r[p * kLd + c], bn.g[c], bn.b[c], bn.m[c], bn_sd(bn, c));
     }
-}
-
-// the tile of a (64, N, B) array into columns 0 .. 63 of an image, rows beyond the cloud's last point zeros
-__device__ __forceinline__ void load_tile64(float *img, const float *src, int b, int N, int p0, int nvalid) {
-    const float *sb = src + ((size_t)b * N + p0) * 64;
-    for (int i = threadIdx.x; i < kTile * 64; i += kPtThreads) img[(i >> 6) * kLd + (i & 63)] = i < nvalid * 64 ? sb[i] : 0.0f;
 }
 
 // The last convolution's input gradient, the gather: g[p][i], i < 128, = the chain over the channels c the point wins, c
@@ -330,10 +318,7 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_trunk_bwd_kernel(const Tr
         ns[c] = a.nstar[(size_t)b * kFeat + c];
         dzs[c] = a.dc3[(size_t)b * kFeat + c];
     }
-    if (MODE != 2) {
-        const float *xb = a.x + ((size_t)b * a.N + p0) * 3;
-        for (int i = tid; i < kTile * 3; i += kPtThreads) xs[i] = i < nvalid * 3 ? xb[i] : 0.0f;
-    }
+    if (MODE != 2) load_xs(xs, a.x, b, a.N, p0, nvalid);
     if (MODE == 1) load_tile64(I2, a.h, b, a.N, p0, nvalid);
     if (MODE == 2) load_tile64(I0, a.h, b, a.N, p0, nvalid);
     __syncthreads();
@@ -380,10 +365,7 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_trunk_bwd_kernel(const Tr
     back_mfma<128>(I2, I1, 64, a.c2.W);  // the gradient at a1, in r2's place
     __syncthreads();
     column_pass(I1, I0, a.c1.bn, 64, nvalid, part + c1at + c1in * 64);
-    if (MODE == 1) {
-        const float *hb = a.h + ((size_t)b * a.N + p0) * 64;  // h again, beside dz1
-        for (int i = tid; i < kTile * 64; i += kPtThreads) I1[(i >> 6) * kLd + 64 + (i & 63)] = i < nvalid * 64 ? hb[i] : 0.0f;
-    }
+    if (MODE == 1) load_tile64(I1 + 64, a.h, b, a.N, p0, nvalid);  // h again, beside dz1
     __syncthreads();
 
     if (MODE == 0) {
@@ -643,39 +625,42 @@ fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, con
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
     const Net n = layout(params_dev, num_classes), gn = layout(gparams, num_classes);
     hipStream_t st = as_stream(s);
-    char *wsb = static_cast<char *>(ws);
-    auto f32 = [&](size_t at) { return reinterpret_cast<float *>(wsb + at); };
-    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(wsb + at); };
-    float *T = f32(w.T), *F = f32(w.F), *gT = gstn ? gstn : f32(w.gT), *gF = gfstn ? gfstn : f32(w.gF);
-    float *gxt_ = gxt ? gxt : f32(w.gxt);
+    const WsView v{static_cast<char *>(ws)};
+    float *T = v.f32(w.T), *F = v.f32(w.F), *gT = gstn ? gstn : v.f32(w.gT), *gF = gfstn ? gfstn : v.f32(w.gF);
+    float *gxt_ = gxt ? gxt : v.f32(w.gxt);
     const int nt = w.ntiles;
 
     // the forward's three rounds, each with its winners per tile; the classifier's head is computed in the head adjoint
     {
         PointArgs p{};
-        p.x = x; p.h = f32(w.h); p.N = N; p.ntiles = nt;
-        auto round = [&](int k) { p.tmax = f32(w.tmax[k]); p.tfirst = i32(w.tfirst[k]); p.tpre = f32(w.tpre[k]); };
-        round(0); p.c1 = n.stn.c1; p.c2 = n.stn.c2; p.c3 = n.stn.c3;
-        if ((r = launch_points(0, true, p, B, st)) != FX3D_OK) return r;
-        if ((r = launch_head(false, stn_head(n.stn, 3, p.tmax, nt, T, nullptr), B, st)) != FX3D_OK) return r;
-        round(1); p.tf = T; p.c0 = n.block1; p.c1 = n.fstn.c1; p.c2 = n.fstn.c2; p.c3 = n.fstn.c3;
-        if ((r = launch_points(1, true, p, B, st)) != FX3D_OK) return r;
-        if ((r = launch_head(false, stn_head(n.fstn, 64, p.tmax, nt, F, nullptr), B, st)) != FX3D_OK) return r;
-        round(2); p.tf = F; p.c2 = n.f1; p.c3 = n.f2;
-        if ((r = launch_points(2, true, p, B, st)) != FX3D_OK) return r;
+        p.x = x; p.h = v.f32(w.h); p.N = N; p.ntiles = nt;
+        for (int mode = 0; mode < 3; ++mode) {
+            set_round(p, n, mode, T, F);
+            p.tmax = v.f32(w.tmax[mode]); p.tfirst = v.i32(w.tfirst[mode]); p.tpre = v.f32(w.tpre[mode]);
+            if ((r = launch_points(mode, true, p, B, st)) != FX3D_OK) return r;
+            if (mode < 2 && (r = launch_head(false, stn_head(n, mode, p.tmax, nt, T, F, nullptr), B, st)) != FX3D_OK) return r;
+        }
     }
 
     HeadBwdArgs hb{};
-    hb.ntiles = nt;
-    hb.nstar = i32(w.nstar); hb.pooled = f32(w.pooled); hb.a1 = f32(w.a1); hb.a2 = f32(w.a2);
-    hb.dd1 = f32(w.dd1); hb.dd2 = f32(w.dd2); hb.dd3 = f32(w.dd3);
-    hb.gy1 = f32(w.gy1); hb.xh1 = f32(w.xh1); hb.gy2 = f32(w.gy2); hb.xh2 = f32(w.xh2);
-    hb.gy3 = f32(w.gy3); hb.xh3 = f32(w.xh3); hb.dc3 = f32(w.dc3);
-    auto head_round = [&](int k) { hb.tmax = f32(w.tmax[k]); hb.tfirst = i32(w.tfirst[k]); hb.tpre = f32(w.tpre[k]); };
+    hb.nstar = v.i32(w.nstar); hb.a1 = v.f32(w.a1); hb.a2 = v.f32(w.a2);
+    hb.dd1 = v.f32(w.dd1); hb.dd2 = v.f32(w.dd2); hb.dd3 = v.f32(w.dd3);
+    hb.gy1 = v.f32(w.gy1); hb.xh1 = v.f32(w.xh1); hb.gy2 = v.f32(w.gy2); hb.xh2 = v.f32(w.xh2);
+    hb.gy3 = v.f32(w.gy3); hb.xh3 = v.f32(w.xh3); hb.dc3 = v.f32(w.dc3);
+    // round k's head as the forward has it, over the layers of net (the parameters, or their gradients); for the adjoint also
+    // the round's winners, the BatchNorm of its last convolution and the gradient that arrives
+    auto head_of = [&](const Net &net, int k) {
+        const float *tmax = v.f32(w.tmax[k]);
+        return k == 2 ? feat_head(net, num_classes, tmax, nt, nullptr, nullptr, nullptr) : stn_head(net, k, tmax, nt, T, F, nullptr);
+    };
+    auto head_round = [&](int k, const Bn &bn3, const float *gup) {
+        static_cast<HeadArgs &>(hb) = head_of(n, k);
+        hb.pooled = v.f32(w.pooled); hb.tfirst = v.i32(w.tfirst[k]); hb.tpre = v.f32(w.tpre[k]); hb.bn3 = bn3; hb.gup = gup;
+    };
 
     TrunkArgs t{};
-    t.x = x; t.h = f32(w.h); t.nstar = hb.nstar; t.dc3 = hb.dc3; t.awin = f32(w.awin); t.part = f32(w.part);
-    t.ghf = f32(w.ghf); t.gh = gh; t.gxt = gxt_; t.gx = gx; t.N = N; t.ntiles = nt;
+    t.x = x; t.h = v.f32(w.h); t.nstar = hb.nstar; t.dc3 = hb.dc3; t.awin = v.f32(w.awin); t.part = v.f32(w.part);
+    t.ghf = v.f32(w.ghf); t.gh = gh; t.gxt = gxt_; t.gx = gx; t.N = N; t.ntiles = nt;
 
     // the last convolution's sums, the head's sums over the clouds, and the chains over the tile partials of one round
     auto conv3_sums = [&](const Conv &g3) -> fx3d_status {
@@ -685,19 +670,20 @@ fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, con
         FX3D_LAUNCH_CHECK();
         return FX3D_OK;
     };
-    auto head_sums = [&](const Dense &g1, const Dense &g2, const Dense &g3, int n3, const Bn *gbn1, const Bn &gbn2) -> fx3d_status {
+    auto head_sums = [&](int k) -> fx3d_status {
         ProfileScope prof("pointnet_head_pgrad", st);
-        const DenseSums s1{hb.dd1, hb.pooled, kFeat, 512, B, mut(g1.W), mut(g1.b)}, s2{hb.dd2, hb.a1, 512, 256, B, mut(g2.W), mut(g2.b)},
-            s3{hb.dd3, hb.a2, 256, n3, B, mut(g3.W), mut(g3.b)};
+        const HeadArgs g = head_of(gn, k);
+        const DenseSums s1{hb.dd1, hb.pooled, kFeat, 512, B, mut(g.d1.W), mut(g.d1.b)}, s2{hb.dd2, hb.a1, 512, 256, B, mut(g.d2.W), mut(g.d2.b)},
+            s3{hb.dd3, hb.a2, 256, g.n3, B, mut(g.d3.W), mut(g.d3.b)};
         for (const DenseSums &q : {s1, s2, s3}) {
             hipLaunchKernelGGL(dense_sums_kernel, blocks((long long)(q.nin + 1) * q.nout), dim3(256), 0, st, q);
             FX3D_LAUNCH_CHECK();
         }
-        if (gbn1) {
-            hipLaunchKernelGGL(bn_sums_kernel, blocks(512), dim3(256), 0, st, hb.gy1, hb.xh1, 512, B, grad_block(*gbn1));
+        if (k == 2) {
+            hipLaunchKernelGGL(bn_sums_kernel, blocks(512), dim3(256), 0, st, hb.gy1, hb.xh1, 512, B, grad_block(g.bn1));
             FX3D_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(bn_sums_kernel, blocks(256), dim3(256), 0, st, hb.gy2, hb.xh2, 256, B, grad_block(gbn2));
+        hipLaunchKernelGGL(bn_sums_kernel, blocks(256), dim3(256), 0, st, hb.gy2, hb.xh2, 256, B, grad_block(g.bn2));
         FX3D_LAUNCH_CHECK();
         return FX3D_OK;
     };
@@ -720,14 +706,12 @@ fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, con
     };
 
     // feat and cls
-    head_round(2);
-    hb.d1 = n.fd1; hb.d2 = n.fd2; hb.d3 = n.cls; hb.bn1 = n.fbn1; hb.bn2 = n.fbn2; hb.bn3 = n.f2.bn;
-    hb.n3 = num_classes; hb.K = 1; hb.gup = glogits;
+    head_round(2, n.f2.bn, glogits);
     if ((r = launch_head_bwd<true>(hb, B, st)) != FX3D_OK) return r;
     t.tf = F; t.c1 = n.f1; t.W3 = n.f2.W; t.psize = kPsize2;
     if ((r = launch_trunk<2>(t, B, st)) != FX3D_OK) return r;
     if ((r = conv3_sums(gn.f2)) != FX3D_OK) return r;
-    if ((r = head_sums(gn.fd1, gn.fd2, gn.cls, num_classes, &gn.fbn1, gn.fbn2)) != FX3D_OK) return r;
+    if ((r = head_sums(2)) != FX3D_OK) return r;
     {
         ProfileScope prof("pointnet_grad_reduce", st);
         if ((r = reduce({layer_seg(kP2c1, gn.f1, 64, 128)}, kPsize2)) != FX3D_OK) return r;
@@ -735,32 +719,28 @@ fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, con
     }
 
     // fstn, conv_block1 and the input transform
-    head_round(1);
-    hb.d1 = n.fstn.d1; hb.d2 = n.fstn.d2; hb.d3 = n.fstn.d3; hb.bn2 = n.fstn.bn; hb.bn3 = n.fstn.c3.bn;
-    hb.n3 = 4096; hb.K = 64; hb.gup = gF;
+    head_round(1, n.fstn.c3.bn, gF);
     if ((r = launch_head_bwd<false>(hb, B, st)) != FX3D_OK) return r;
     t.tf = T; t.c0 = n.block1; t.c1 = n.fstn.c1; t.c2 = n.fstn.c2; t.W3 = n.fstn.c3.W; t.psize = kPsize1;
     if ((r = launch_trunk<1>(t, B, st)) != FX3D_OK) return r;
     if ((r = conv3_sums(gn.fstn.c3)) != FX3D_OK) return r;
-    if ((r = head_sums(gn.fstn.d1, gn.fstn.d2, gn.fstn.d3, 4096, nullptr, gn.fstn.bn)) != FX3D_OK) return r;
+    if ((r = head_sums(1)) != FX3D_OK) return r;
     {
         ProfileScope prof("pointnet_grad_reduce", st);
-        if ((r = reduce({layer_seg(kP1c1, gn.fstn.c1, 64, 64), layer_seg(kP1c2, gn.fstn.c2, 64, 128), Seg{kP1b1, f32(w.sums), 256, 0}},
+        if ((r = reduce({layer_seg(kP1c1, gn.fstn.c1, 64, 64), layer_seg(kP1c2, gn.fstn.c2, 64, 128), Seg{kP1b1, v.f32(w.sums), 256, 0}},
                         kPsize1)) != FX3D_OK) return r;
-        hipLaunchKernelGGL(block1_finish_kernel, dim3(1), dim3(256), 0, st, f32(w.sums), n.block1, grad_block(gn.block1));
+        hipLaunchKernelGGL(block1_finish_kernel, dim3(1), dim3(256), 0, st, v.f32(w.sums), n.block1, grad_block(gn.block1));
         FX3D_LAUNCH_CHECK();
         if ((r = cloud_reduce(kPsize1, kP1gT, 9, gT)) != FX3D_OK) return r;
     }
 
     // stn, and the two paths into x
-    head_round(0);
-    hb.d1 = n.stn.d1; hb.d2 = n.stn.d2; hb.d3 = n.stn.d3; hb.bn2 = n.stn.bn; hb.bn3 = n.stn.c3.bn;
-    hb.n3 = 9; hb.K = 3; hb.gup = gT;
+    head_round(0, n.stn.c3.bn, gT);
     if ((r = launch_head_bwd<false>(hb, B, st)) != FX3D_OK) return r;
     t.c1 = n.stn.c1; t.c2 = n.stn.c2; t.W3 = n.stn.c3.W; t.psize = kPsize0;
     if ((r = launch_trunk<0>(t, B, st)) != FX3D_OK) return r;
     if ((r = conv3_sums(gn.stn.c3)) != FX3D_OK) return r;
-    if ((r = head_sums(gn.stn.d1, gn.stn.d2, gn.stn.d3, 9, nullptr, gn.stn.bn)) != FX3D_OK) return r;
+    if ((r = head_sums(0)) != FX3D_OK) return r;
     ProfileScope prof("pointnet_grad_reduce", st);
     return reduce({layer_seg(kP0c1, gn.stn.c1, 3, 64), layer_seg(kP0c2, gn.stn.c2, 64, 128)}, kPsize0);
 }

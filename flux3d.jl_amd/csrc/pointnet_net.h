@@ -1,6 +1,9 @@
-// What pointnet.hip (the forward) and pointnet_grad.hip (its adjoint) share: the walk over the flat parameter buffer, the
-// forward's workspace, the size check of both entries, the arguments of the forward's two kernels and their launches (defined
-// in pointnet.hip, which owns the kernels), and the last layer of a round with the winners the adjoint needs.
+// What pointnet.hip (the forward), pointnet_train.hip (the training-mode forward) and pointnet_grad.hip (the adjoint) share.
+// On the host: the walk over the flat parameter buffer, the forward's workspace, the size check of the entries, the
+// arguments of the forward's two kernels per round (set_round, stn_head, feat_head) and their launches (defined in
+// pointnet.hip, which owns the kernels).  On the device: a round's layer chain (round_trunk, with its tile loads), the slab
+// walk with an epilogue on the accumulators (for_each_slab; conv_final_win, the last layer with the winners the adjoint
+// needs, is one body of it) and the head's phases (head_pool .. head_finish).
 #pragma once
 #include <climits>
 
@@ -120,11 +123,41 @@ inline fx3d_status check_sizes(const char *fn, int32_t N, int32_t B, int32_t nc)
     return FX3D_OK;
 }
 
-inline HeadArgs stn_head(const Stn &s, int K, const float *tmax, int ntiles, float *mat, float *mat_user) {
+// a workspace as typed arrays at the offsets of its plan
+struct WsView {
+    char *base;
+    float *f32(size_t at) const { return reinterpret_cast<float *>(base + at); }
+    int32_t *i32(size_t at) const { return reinterpret_cast<int32_t *>(base + at); }
+    double *f64(size_t at) const { return reinterpret_cast<double *>(base + at); }
+};
+
+// ---- the three rounds, mode 0 = stn, 1 = fstn, 2 = feat: what each gives the forward's two kernels ----------------------------
+// the round's convolutions and the transform in front of them: stn reads x; fstn x T, through conv_block1 (kept as h); feat h F
+inline void set_round(PointArgs &p, const Net &n, int mode, const float *T, const float *F) {
+    const Stn &s = mode == 0 ? n.stn : n.fstn;
+    p.tf = mode == 0 ? nullptr : mode == 1 ? T : F;
+    p.c0 = n.block1;
+    p.c1 = s.c1;
+    p.c2 = mode == 2 ? n.f1 : s.c2;
+    p.c3 = mode == 2 ? n.f2 : s.c3;
+}
+// the head of stn (mode 0: the (3, 3) input transform T) or fstn (mode 1: the (64, 64) feature transform F); mat_user: the
+// caller's copy of the matrix, or NULL
+inline HeadArgs stn_head(const Net &n, int mode, const float *tmax, int ntiles, float *T, float *F, float *mat_user) {
+    const Stn &s = mode == 0 ? n.stn : n.fstn;
+    const int K = mode == 0 ? 3 : 64;
     HeadArgs h{};
     h.tmax = tmax; h.ntiles = ntiles;
     h.d1 = s.d1; h.d2 = s.d2; h.d3 = s.d3; h.bn2 = s.bn;
-    h.n3 = K * K; h.K = K; h.mat = mat; h.mat_user = mat_user;
+    h.n3 = K * K; h.K = K; h.mat = mode == 0 ? T : F; h.mat_user = mat_user;
+    return h;
+}
+// the classifier's head: feat's dense layers, cls, softmax
+inline HeadArgs feat_head(const Net &n, int nc, const float *tmax, int ntiles, float *pooled, float *logits, float *probs) {
+    HeadArgs h{};
+    h.tmax = tmax; h.ntiles = ntiles;
+    h.d1 = n.fd1; h.bn1 = n.fbn1; h.d2 = n.fd2; h.bn2 = n.fbn2; h.d3 = n.cls;
+    h.n3 = nc; h.K = 1; h.pooled = pooled; h.logits = logits; h.probs = probs;
     return h;
 }
 
@@ -133,25 +166,47 @@ inline HeadArgs stn_head(const Stn &s, int K, const float *tmax, int ntiles, flo
 fx3d_status launch_points(int mode, bool win, const PointArgs &a, int B, hipStream_t st);
 fx3d_status launch_head(bool feat, const HeadArgs &a, int B, hipStream_t st);
 
+__device__ __forceinline__ float bn_sd(const Bn &bn, int o) { return sqrtf(bn.v[o] + kBnEps); }
 // what the last layer's BatchNorm is given: relu(acc + bias) for kReluBn, acc + bias for kBnOnly
 template <int EPI>
 __device__ __forceinline__ float before_bn(float acc, float bias) { return EPI == kReluBn ? relu(acc + bias) : acc + bias; }
+
+// ---- the tile loads: rows beyond the cloud's last point are zeros (they are computed and take part in nothing) ---------------
+// the tile of x (3, N, B) as xs[p][3]
+__device__ __forceinline__ void load_xs(float *xs, const float *x, int b, int N, int p0, int nvalid) {
+    const float *xb = x + ((size_t)b * N + p0) * 3;
+    for (int i = threadIdx.x; i < kTile * 3; i += kPtThreads) xs[i] = i < nvalid * 3 ? xb[i] : 0.0f;
+}
+// the tile of a (64, N, B) array into columns 0 .. 63 of an image
+__device__ __forceinline__ void load_tile64(float *img, const float *src, int b, int N, int p0, int nvalid) {
+    const float *sb = src + ((size_t)b * N + p0) * 64;
+    for (int i = threadIdx.x; i < kTile * 64; i += kPtThreads) img[(i >> 6) * kLd + (i & 63)] = i < nvalid * 64 ? sb[i] : 0.0f;
+}
+
+// ---- conv_mfma's walk over the slabs of 32 output channels, with the epilogue left to the caller -----------------------------
+// body(o, h, acc0, acc1) while the slab of `in` (row stride kLd) times W (CIN, cout) is in the accumulators: o is the lane's
+// channel, acc0 / acc1 its 16 points mfma_row(r, h) of the tile's two 32-point halves.  All 4 waves call it.
+template <int CIN, class Body>
+__device__ __forceinline__ void for_each_slab(const float *in, const float *__restrict__ W, int cout, Body body) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const float *a0 = in + j * kLd + h, *a1 = a0 + 32 * kLd;
+    for (int sl = wave; sl < cout / 32; sl += kPtThreads / 64) {
+        const int o = sl * 32 + j;
+        f32x16 acc0 = {0}, acc1 = {0};
+        mfma_slab<CIN>(a0, a1, W + (size_t)CIN * o, h, acc0, acc1);
+        body(o, h, acc0, acc1);
+    }
+}
 
 // conv_mfma<128, EPI, true> -- the same slabs, epilogue and fold, so the same tmax -- that also finds, while the slab's values
 // are still in the accumulators, the first of the tile's valid points whose value EQUALS the tile's maximum (Float32 ==, so
 // -0 equals +0; a NaN maximum equals nothing: kNoPoint), and keeps what the BatchNorm was given there.  p0: the tile's first
 // point.  A lane's rows mfma_row(r, h) ascend with r, the second half's follow the first's.
 template <int EPI>
-__device__ __forceinline__ void conv_final_win(const float *in, const float *__restrict__ W, const float *__restrict__ bias,
-                                               const Bn bn, int nvalid, int p0, float *__restrict__ tmax,
+__device__ __forceinline__ void conv_final_win(const float *in, const Conv &c, int nvalid, int p0, float *__restrict__ tmax,
                                                int32_t *__restrict__ tfirst, float *__restrict__ tpre) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    const float *a0 = in + j * kLd + h, *a1 = a0 + 32 * kLd;
-    for (int sl = wave; sl < kFeat / 32; sl += kPtThreads / 64) {
-        const int o = sl * 32 + j;
-        f32x16 acc0 = {0}, acc1 = {0};
-        mfma_slab<128>(a0, a1, W + (size_t)128 * o, h, acc0, acc1);
-        const float bi = bias[o], g = bn.g[o], be = bn.b[o], mu = bn.m[o], sd = sqrtf(bn.v[o] + kBnEps);
+    for_each_slab<128>(in, c.W, kFeat, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
+        const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = bn_sd(c.bn, o);
         float m = __int_as_float(0xff800000);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -179,7 +234,103 @@ __device__ __forceinline__ void conv_final_win(const float *in, const float *__r
             tfirst[o] = min(first, ofirst);
             tpre[o] = ofirst < first ? opre : pre;
         }
+    });
+}
+
+// ---- a round's layers, once ---------------------------------------------------------------------------------------------------
+// One block = 64 points of cloud b from p0 on, 4 waves, lds of kPtLds bytes: the tile load, then the round's layers in order,
+// each into the image the next reads.  The BatchNorm layers of a round count from 0 (MODE 0, stn: conv1, conv2, conv3; MODE 1,
+// fstn: conv_block1, conv1, conv2, conv3; MODE 2, feat: conv1, conv2); layer STOP is not computed here but handed to
+// tail(in, conv, Layer<CIN, COUT, EPI>{}): its input image, its parameters and its shape.  STOP = kLastLayer[MODE] with the
+// fold over the tile as the tail is the forward's pointnet_points_kernel; a smaller STOP with the statistics epilogue is
+// pointnet_stats_kernel, so the layers below a BatchNorm are the same calls in both.  KEEP_H: MODE 1 stores conv_block1's
+// output to a.h.
+template <int CIN_, int COUT_, int EPI_>
+struct Layer { static constexpr int CIN = CIN_, COUT = COUT_, EPI = EPI_; };
+constexpr int kLastLayer[3] = {2, 3, 1};
+
+template <int MODE, int STOP, bool KEEP_H, class Tail>
+__device__ __forceinline__ void round_trunk(const PointArgs &a, float *lds, int b, int p0, int nvalid, Tail tail) {
+    float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
+    const int tid = threadIdx.x;
+    if (MODE != 2) load_xs(xs, a.x, b, a.N, p0, nvalid);
+    else load_tile64(bufA, a.h, b, a.N, p0, nvalid);
+    __syncthreads();
+    if constexpr (MODE == 0) {
+        if constexpr (STOP == 0) return tail(xs, a.c1, Layer<3, 64, kReluBn>{});
+        conv3<kReluBn>(xs, bufA, kLd, 64, a.c1.W, a.c1.b, a.c1.bn);
+        __syncthreads();
+        if constexpr (STOP == 1) return tail(bufA, a.c2, Layer<64, 128, kReluBn>{});
+        conv_mfma<64, kReluBn, false>(bufA, bufB, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        tail(bufB, a.c3, Layer<128, kFeat, kReluBn>{});
+    } else if constexpr (MODE == 1) {
+        conv3<kNone>(xs, xt, 3, 3, a.tf + (size_t)b * 9, nullptr, Bn{});
+        __syncthreads();
+        if constexpr (STOP == 0) return tail(xt, a.c0, Layer<3, 64, kBnRelu>{});
+        conv3<kBnRelu>(xt, bufA, kLd, 64, a.c0.W, a.c0.b, a.c0.bn);
+        __syncthreads();
+        if constexpr (STOP == 1) return tail(bufA, a.c1, Layer<64, 64, kReluBn>{});
+        if (KEEP_H) {
+            float *hb = a.h + ((size_t)b * a.N + p0) * 64;
+            for (int i = tid; i < nvalid * 64; i += kPtThreads) hb[i] = bufA[(i >> 6) * kLd + (i & 63)];
+        }
+        conv_mfma<64, kReluBn, false>(bufA, bufB, 64, a.c1.W, a.c1.b, a.c1.bn, nvalid, nullptr);
+        __syncthreads();
+        if constexpr (STOP == 2) return tail(bufB, a.c2, Layer<64, 128, kReluBn>{});
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        tail(bufA, a.c3, Layer<128, kFeat, kReluBn>{});
+    } else {
+        conv_mfma<64, kNone, false>(bufA, bufB, 64, a.tf + (size_t)b * 4096, nullptr, Bn{}, nvalid, nullptr);
+        __syncthreads();
+        if constexpr (STOP == 0) return tail(bufB, a.c2, Layer<64, 128, kReluBn>{});
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        tail(bufA, a.c3, Layer<128, kFeat, kBnOnly>{});
     }
+}
+
+// ---- the head, phase by phase: one block of kHeadThreads per cloud b, thread tid = one element of each vector -------------------
+// Every dense layer is dense_chain over its input in LDS (ascending, from +0.0f).  pointnet_head_kernel is all phases in
+// one block; the training-mode heads (pointnet_train.hip) cut them at the BatchNorms; the adjoint's head (pointnet_grad.hip)
+// runs the dense phases again and keeps the relus' outputs (its pool also finds the winners).
+// MaxPool over the cloud's points into v0 (kFeat), with the classifier's optional copy
+template <bool FEAT>
+__device__ __forceinline__ void head_pool(const HeadArgs &a, int b, float *v0) {
+    const float m = fold_tile_maxima(a.tmax, a.ntiles, b);
+    v0[threadIdx.x] = m;
+    if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + threadIdx.x] = m;
+}
+// relu(dense1): in = v0 (kFeat), NOUT = 512; relu(dense2): in = v1 (512), NOUT = 256; this thread's output, tid < NOUT
+template <int NOUT>
+__device__ __forceinline__ float head_relu_dense(const Dense &d, const float *in) {
+    return relu(dense_chain(in, 2 * NOUT, d.W, NOUT, threadIdx.x) + d.b[threadIdx.x]);
+}
+// dense3 of v2 (256), output o < n3
+__device__ __forceinline__ float head_dense3(const Dense &d, const float *v2, int n3, int o) {
+    return dense_chain(v2, 256, d.W, n3, o) + d.b[o];
+}
+// a head's BatchNorm of this thread's element
+__device__ __forceinline__ float head_bn(const Bn &bn, float v) {
+    const int tid = threadIdx.x;
+    return batchnorm(v, bn.g[tid], bn.b[tid], bn.m[tid], bn_sd(bn, tid));
+}
+// dense3 of v2 as the transposed (K, K) matrix (T[i,j] = d[j + K i] at i + K j) with the caller's optional copy, or cls, relu
+// and the softmax
+template <bool FEAT>
+__device__ __forceinline__ void head_finish(const HeadArgs &a, int b, const float *v2) {
+    for (int o = threadIdx.x; o < a.n3; o += kHeadThreads) {
+        const float v = head_dense3(a.d3, v2, a.n3, o);
+        if (FEAT) {
+            a.logits[(size_t)b * a.n3 + o] = relu(v);
+        } else {
+            const size_t at = (size_t)b * a.n3 + (o / a.K) + (size_t)a.K * (o % a.K);
+            a.mat[at] = v;
+            if (a.mat_user) a.mat_user[at] = v;
+        }
+    }
+    if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
 }
 
 }  // namespace pointnet

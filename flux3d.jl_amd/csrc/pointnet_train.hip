@@ -5,14 +5,14 @@
 // A Bn holds four pointers and the test-mode kernels read the mean and the variance through bn.m / bn.v, so a layer whose batch
 // statistics exist IS the test-mode layer with m / v pointed at the statistics buffer (pointnet_net.h: with_batch_stats).  What is
 // new is producing the statistics in dependency order.  Per round (stn, fstn, feat) and BatchNorm L of the round:
-//   pointnet_stats_kernel<MODE, L>: the forward's tile (one block = 64 points of one cloud, the same LDS images, conv3 /
-//     conv_mfma for the layers below L with the statistics already known), then layer L's contraction; while its slab is in
+//   pointnet_stats_kernel<MODE, L>: the forward's tile (one block = 64 points of one cloud; round_trunk of pointnet_net.h runs
+//     the layers below L, whose statistics are known, as the forward does), then layer L's contraction; while its slab is in
 //     the accumulators, what the BatchNorm is given (before_bn) is summed per channel over the tile's valid rows in Float64,
 //     S1 = sum v and S2 = sum v v, and both are stored with plain stores to sums (2, C, ntiles, B).  Layer L itself goes nowhere else.
 //   pointnet_stat_finish_kernel: folds the tile sums of a layer over (tile, cloud) and writes the mean, the variance and the
 //     updated running statistics.
 //   then the forward's own pointnet_points_kernel<MODE> (launch_points) gives the per-tile maxima (and h in the fstn round).
-// The heads split at their BatchNorms, which need all B clouds: head_a (maxima, dense1, relu; stn / fstn: dense2, relu too),
+// The heads are the forward's phases (pointnet_net.h) cut at their BatchNorms, which need all B clouds: head_a (maxima, dense1, relu; stn / fstn: dense2, relu too),
 // feat only head_b (BatchNorm, dense2, relu, the dropout multiplier), head_c (BatchNorm, dense3 / cls, relu + softmax), with
 // pointnet_dense_stats_kernel in between: one thread per channel sums the (C, B) activations in ascending b.
 // No atomics anywhere: every sum has one owner and one order, which depends on (N, B) alone.
@@ -71,16 +71,11 @@ __device__ __forceinline__ void store_tile_sum(double *sums, int o, double s1, d
     sums[2 * o + 1] = s2;
 }
 
-// layer L = a convolution on the MFMA: conv_mfma's slabs with the statistics epilogue.  sums: the tile's (2, cout).
+// layer L = a convolution on the MFMA: conv_mfma's slabs (for_each_slab) with the statistics epilogue.  sums: the tile's (2, cout).
 template <int CIN, int EPI>
 __device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const float *__restrict__ W, const float *__restrict__ bias,
                                                int nvalid, double *__restrict__ sums) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    const float *a0 = in + j * kLd + h, *a1 = a0 + 32 * kLd;
-    for (int sl = wave; sl < cout / 32; sl += kPtThreads / 64) {
-        const int o = sl * 32 + j;
-        f32x16 acc0 = {0}, acc1 = {0};
-        mfma_slab<CIN>(a0, a1, W + (size_t)CIN * o, h, acc0, acc1);
+    for_each_slab<CIN>(in, W, cout, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
         const float bi = bias[o];
         TileSum t;
 #pragma unroll
@@ -91,7 +86,7 @@ __device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const 
             if (mfma_row(r, h) + 32 < nvalid) t.add(before_bn<EPI>(acc1[r], bi));
         const double o1 = __shfl_xor(t.s1, 32, 64), o2 = __shfl_xor(t.s2, 32, 64);
         if (h == 0) store_tile_sum(sums, o, t.s1 + o1, t.s2 + o2);
-    }
+    });
 }
 
 // layer L = a convolution of 3 input channels (conv3's chain) to 64: waves 0 and 1 are the two chains of a channel
@@ -124,56 +119,20 @@ struct StatArgs {
     double *sums;  // (2, C, ntiles, B) for the C channels of the layer
 };
 
-// the round's BatchNorms in the order they run: MODE 0 (stn) bn1, bn2, bn3; MODE 1 (fstn) conv_block1.bn, bn1, bn2, bn3;
-// MODE 2 (feat) bn1, bn2.  The layers below L are pointnet_points_kernel<MODE>'s, call for call (h is not written here).
+// BatchNorm L of the round, in the order they run (round_trunk, pointnet_net.h): the layers below L are the forward's own
+// calls (h is not written here), layer L's width and epilogue come with it.
 template <int MODE, int L>
 __global__ __launch_bounds__(kPtThreads) void pointnet_stats_kernel(const StatArgs s) {
-    const PointArgs &a = s.p;
     extern __shared__ float lds[];
-    float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
-    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int tile = blockIdx.x, b = blockIdx.y;
     const int p0 = tile * kTile;
-    const int nvalid = min(kTile, a.N - p0);
-    constexpr int C = (MODE == 0 ? (L == 0 ? 64 : L == 1 ? 128 : kFeat)
-                       : MODE == 1 ? (L <= 1 ? 64 : L == 2 ? 128 : kFeat) : (L == 0 ? 128 : kFeat));
-    double *sums = s.sums + 2 * ((size_t)b * a.ntiles + tile) * C;
-    if (MODE != 2) {
-        const float *xb = a.x + ((size_t)b * a.N + p0) * 3;
-        for (int i = tid; i < kTile * 3; i += kPtThreads) xs[i] = i < nvalid * 3 ? xb[i] : 0.0f;
-    } else {
-        const float *hb = a.h + ((size_t)b * a.N + p0) * 64;
-        for (int i = tid; i < kTile * 64; i += kPtThreads) bufA[(i >> 6) * kLd + (i & 63)] = i < nvalid * 64 ? hb[i] : 0.0f;
-    }
-    __syncthreads();
-    if (MODE == 0) {
-        if (L == 0) { conv_stat3<kReluBn>(xs, a.c1.W, a.c1.b, nvalid, sums); return; }
-        conv3<kReluBn>(xs, bufA, kLd, 64, a.c1.W, a.c1.b, a.c1.bn);
-        __syncthreads();
-        if (L == 1) { conv_stat_mfma<64, kReluBn>(bufA, 128, a.c2.W, a.c2.b, nvalid, sums); return; }
-        conv_mfma<64, kReluBn, false>(bufA, bufB, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
-        __syncthreads();
-        conv_stat_mfma<128, kReluBn>(bufB, kFeat, a.c3.W, a.c3.b, nvalid, sums);
-    } else if (MODE == 1) {
-        conv3<kNone>(xs, xt, 3, 3, a.tf + (size_t)b * 9, nullptr, Bn{});
-        __syncthreads();
-        if (L == 0) { conv_stat3<kBnRelu>(xt, a.c0.W, a.c0.b, nvalid, sums); return; }
-        conv3<kBnRelu>(xt, bufA, kLd, 64, a.c0.W, a.c0.b, a.c0.bn);
-        __syncthreads();
-        if (L == 1) { conv_stat_mfma<64, kReluBn>(bufA, 64, a.c1.W, a.c1.b, nvalid, sums); return; }
-        conv_mfma<64, kReluBn, false>(bufA, bufB, 64, a.c1.W, a.c1.b, a.c1.bn, nvalid, nullptr);
-        __syncthreads();
-        if (L == 2) { conv_stat_mfma<64, kReluBn>(bufB, 128, a.c2.W, a.c2.b, nvalid, sums); return; }
-        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
-        __syncthreads();
-        conv_stat_mfma<128, kReluBn>(bufA, kFeat, a.c3.W, a.c3.b, nvalid, sums);
-    } else {
-        conv_mfma<64, kNone, false>(bufA, bufB, 64, a.tf + (size_t)b * 4096, nullptr, Bn{}, nvalid, nullptr);
-        __syncthreads();
-        if (L == 0) { conv_stat_mfma<64, kReluBn>(bufB, 128, a.c2.W, a.c2.b, nvalid, sums); return; }
-        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
-        __syncthreads();
-        conv_stat_mfma<128, kBnOnly>(bufA, kFeat, a.c3.W, a.c3.b, nvalid, sums);
-    }
+    const int nvalid = min(kTile, s.p.N - p0);
+    round_trunk<MODE, L, false>(s.p, lds, b, p0, nvalid, [&](const float *in, const Conv &c, auto layer) {
+        using Ly = decltype(layer);
+        double *sums = s.sums + 2 * ((size_t)b * s.p.ntiles + tile) * Ly::COUT;
+        if constexpr (Ly::CIN == 3) conv_stat3<Ly::EPI>(in, c.W, c.b, nvalid, sums);
+        else conv_stat_mfma<Ly::CIN, Ly::EPI>(in, Ly::COUT, c.W, c.b, nvalid, sums);
+    });
 }
 
 // Folds sums (2, C, T) over the T = ntiles B tile sums t = tile + ntiles b of a layer: kFinishGroups chains, chain g over
@@ -223,18 +182,16 @@ __global__ __launch_bounds__(kHeadThreads) void pointnet_train_head_a_kernel(con
     const HeadArgs &a = t.h;
     __shared__ float v0[kFeat], v1[512];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float m = fold_tile_maxima(a.tmax, a.ntiles, b);
-    v0[tid] = m;
-    if (FEAT && a.pooled) a.pooled[(size_t)b * kFeat + tid] = m;
+    head_pool<FEAT>(a, b, v0);
     __syncthreads();
     if (tid < 512) {
-        const float v = relu(dense_chain(v0, kFeat, a.d1.W, 512, tid) + a.d1.b[tid]);
+        const float v = head_relu_dense<512>(a.d1, v0);
         if (FEAT) t.a1[(size_t)b * 512 + tid] = v;
         else v1[tid] = v;
     }
     if (FEAT) return;
     __syncthreads();
-    if (tid < 256) t.a2[(size_t)b * 256 + tid] = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
+    if (tid < 256) t.a2[(size_t)b * 256 + tid] = head_relu_dense<256>(a.d2, v1);
 }
 
 // feat: BatchNorm(512) at the batch statistics, relu(dense2), the dropout multiplier
@@ -242,36 +199,24 @@ __global__ __launch_bounds__(512) void pointnet_train_head_b_kernel(const TrainH
     const HeadArgs &a = t.h;
     __shared__ float v1[512];
     const int b = blockIdx.x, tid = threadIdx.x;
-    v1[tid] = batchnorm(t.a1[(size_t)b * 512 + tid], a.bn1.g[tid], a.bn1.b[tid], a.bn1.m[tid], sqrtf(a.bn1.v[tid] + kBnEps));
+    v1[tid] = head_bn(a.bn1, t.a1[(size_t)b * 512 + tid]);
     __syncthreads();
     if (tid < 256) {
-        float v = relu(dense_chain(v1, 512, a.d2.W, 256, tid) + a.d2.b[tid]);
+        float v = head_relu_dense<256>(a.d2, v1);
         if (t.dropout) v = v * t.dropout[(size_t)b * 256 + tid];
         t.a2[(size_t)b * 256 + tid] = v;
     }
 }
 
-// BatchNorm(256) at the batch statistics, then the test-mode head's end: dense3 as the transposed (K, K) matrix, or cls,
-// relu and the softmax
+// BatchNorm(256) at the batch statistics, then the head's end
 template <bool FEAT>
 __global__ __launch_bounds__(kHeadThreads) void pointnet_train_head_c_kernel(const TrainHeadArgs t) {
     const HeadArgs &a = t.h;
     __shared__ float v2[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (tid < 256)
-        v2[tid] = batchnorm(t.a2[(size_t)b * 256 + tid], a.bn2.g[tid], a.bn2.b[tid], a.bn2.m[tid], sqrtf(a.bn2.v[tid] + kBnEps));
+    if (tid < 256) v2[tid] = head_bn(a.bn2, t.a2[(size_t)b * 256 + tid]);
     __syncthreads();
-    for (int o = tid; o < a.n3; o += kHeadThreads) {
-        const float v = dense_chain(v2, 256, a.d3.W, a.n3, o) + a.d3.b[o];
-        if (FEAT) {
-            a.logits[(size_t)b * a.n3 + o] = relu(v);
-        } else {
-            const size_t at = (size_t)b * a.n3 + (o / a.K) + (size_t)a.K * (o % a.K);
-            a.mat[at] = v;
-            if (a.mat_user) a.mat_user[at] = v;
-        }
-    }
-    if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
+    head_finish<FEAT>(a, b, v2);
 }
 
 template <int MODE, int L>
@@ -387,8 +332,10 @@ fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_cla
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", fn);
     const Net run = layout(params_dev, num_classes);  // the running statistics, read for `running` alone
     const Net n = with_batch_stats(run, batch_stats);
-    // the 13 BatchNorms in forward order: their slots of the statistics buffers and their running values
+    // the 13 BatchNorms in forward order, which is the order they run in: their slots of the statistics buffers, their running
+    // values and their widths
     StatOut so[kNumBn];
+    int width[kNumBn];
     {
         int i = 0;
         size_t at = 0;
@@ -398,66 +345,49 @@ fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_cla
             so[i].new_m = running ? running + at : nullptr; so[i].new_v = running ? running + at + C : nullptr;
             so[i].mtm = momentum;
             so[i].m = (long long)N * B;
+            width[i] = C;
             at += 2 * (size_t)C;
             ++i;
         });
         for (int k : {3, 8, 11, 12}) so[k].m = B;  // the BatchNorms after a dense layer
     }
     hipStream_t st = as_stream(s);
-    char *wsb = static_cast<char *>(ws);
-    float *h = reinterpret_cast<float *>(wsb + w.h), *tmax = reinterpret_cast<float *>(wsb + w.tmax);
-    float *T = reinterpret_cast<float *>(wsb + w.T), *F = reinterpret_cast<float *>(wsb + w.F);
-    float *lg = logits ? logits : reinterpret_cast<float *>(wsb + w.logits);
-    double *sums = reinterpret_cast<double *>(wsb + tp.sums);
-    float *a1 = reinterpret_cast<float *>(wsb + tp.a1), *a2 = reinterpret_cast<float *>(wsb + tp.a2);
+    const WsView v{static_cast<char *>(ws)};
+    float *tmax = v.f32(w.tmax), *T = v.f32(w.T), *F = v.f32(w.F);
     const long long ntl = (long long)w.ntiles * B;
 
     StatArgs sa{};
     PointArgs &p = sa.p;
-    sa.sums = sums;
-    p.x = x; p.h = h; p.tmax = tmax; p.N = N; p.ntiles = w.ntiles;
-    fx3d_status r;
-    // the round's point BatchNorms in order (slot `first` on, widths C[]), then the round's closing full pass
-    auto run_round = [&](int mode, int first, std::initializer_list<int> widths) -> fx3d_status {
-        int L = 0;
-        for (int C : widths) {
-            if ((r = launch_stats(mode, L, sa, B, st)) != FX3D_OK) return r;
-            if ((r = launch_finish(sums, C, ntl, so[first + L], st)) != FX3D_OK) return r;
-            ++L;
-        }
-        return launch_points(mode, false, p, B, st);
-    };
-    // a stn / fstn head: relu(dense2), its BatchNorm's statistics, the (K, K) matrix
-    auto stn_heads = [&](const Stn &sn, int K, int slot, float *mat, float *mat_user) -> fx3d_status {
-        TrainHeadArgs t{};
-        t.h = stn_head(sn, K, tmax, w.ntiles, mat, mat_user);
-        t.a2 = a2;
-        if ((r = launch_train_head(0, false, t, B, st)) != FX3D_OK) return r;
-        if ((r = launch_dense_stats(a2, 256, B, so[slot], st)) != FX3D_OK) return r;
-        return launch_train_head(2, false, t, B, st);
-    };
-    // stn: the (3, 3) input transform of every cloud
-    p.c1 = n.stn.c1; p.c2 = n.stn.c2; p.c3 = n.stn.c3;
-    if ((r = run_round(0, 0, {64, 128, kFeat})) != FX3D_OK) return r;
-    if ((r = stn_heads(n.stn, 3, 3, T, stn)) != FX3D_OK) return r;
-    // input transform, conv_block1 (kept as h by the closing pass), fstn: the (64, 64) feature transform
-    p.tf = T; p.c0 = n.block1; p.c1 = n.fstn.c1; p.c2 = n.fstn.c2; p.c3 = n.fstn.c3;
-    if ((r = run_round(1, 4, {64, 64, 128, kFeat})) != FX3D_OK) return r;
-    if ((r = stn_heads(n.fstn, 64, 8, F, fstn)) != FX3D_OK) return r;
-    // feature transform, feat, cls, softmax
-    p.tf = F; p.c2 = n.f1; p.c3 = n.f2;
-    if ((r = run_round(2, 9, {128, kFeat})) != FX3D_OK) return r;
+    sa.sums = v.f64(tp.sums);
+    p.x = x; p.h = v.f32(w.h); p.tmax = tmax; p.N = N; p.ntiles = w.ntiles;
     TrainHeadArgs t{};
-    HeadArgs &hd = t.h;
-    hd.tmax = tmax; hd.ntiles = w.ntiles;
-    hd.d1 = n.fd1; hd.bn1 = n.fbn1; hd.d2 = n.fd2; hd.bn2 = n.fbn2; hd.d3 = n.cls;
-    hd.n3 = num_classes; hd.K = 1; hd.pooled = pooled; hd.logits = lg; hd.probs = probs;
-    t.a1 = a1; t.a2 = a2; t.dropout = dropout;
-    if ((r = launch_train_head(0, true, t, B, st)) != FX3D_OK) return r;
-    if ((r = launch_dense_stats(a1, 512, B, so[11], st)) != FX3D_OK) return r;
-    if ((r = launch_train_head(1, true, t, B, st)) != FX3D_OK) return r;
-    if ((r = launch_dense_stats(a2, 256, B, so[12], st)) != FX3D_OK) return r;
-    return launch_train_head(2, true, t, B, st);
+    t.a1 = v.f32(tp.a1); t.a2 = v.f32(tp.a2); t.dropout = dropout;
+    fx3d_status r;
+    int slot = 0;
+    // stn: T (3, 3) of every cloud; x T, conv_block1, fstn: F (64, 64); h F, feat, cls, softmax
+    for (int mode = 0; mode < 3; ++mode) {
+        const bool feat = mode == 2;
+        set_round(p, n, mode, T, F);
+        // the round's point BatchNorms in order, then the round's closing full pass (which keeps conv_block1 as h)
+        for (int L = 0; L <= kLastLayer[mode]; ++L, ++slot) {
+            if ((r = launch_stats(mode, L, sa, B, st)) != FX3D_OK) return r;
+            if ((r = launch_finish(sa.sums, width[slot], ntl, so[slot], st)) != FX3D_OK) return r;
+        }
+        if ((r = launch_points(mode, false, p, B, st)) != FX3D_OK) return r;
+        // the head: relu(dense1) and for feat its BatchNorm's statistics, relu(dense2) and its BatchNorm's statistics, the end
+        t.h = feat ? feat_head(n, num_classes, tmax, w.ntiles, pooled, logits ? logits : v.f32(w.logits), probs)
+                   : stn_head(n, mode, tmax, w.ntiles, T, F, mode == 0 ? stn : fstn);
+        if ((r = launch_train_head(0, feat, t, B, st)) != FX3D_OK) return r;
+        if (feat) {
+            if ((r = launch_dense_stats(t.a1, width[slot], B, so[slot], st)) != FX3D_OK) return r;
+            if ((r = launch_train_head(1, true, t, B, st)) != FX3D_OK) return r;
+            ++slot;
+        }
+        if ((r = launch_dense_stats(t.a2, width[slot], B, so[slot], st)) != FX3D_OK) return r;
+        if ((r = launch_train_head(2, feat, t, B, st)) != FX3D_OK) return r;
+        ++slot;
+    }
+    return FX3D_OK;
 }
 
 }  // extern "C"

@@ -87,8 +87,9 @@ def edgeconv_param_shapes(layers):
 
 class _Model:
     """What the models share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy, the
-    check of the input clouds and the classifiers' forward.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``, and ``_count_args()`` where
-    the count is not a function of ``num_classes``."""
+    check of the input clouds and the classifiers' forward.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``, ``_count_args()`` where
+    the count is not a function of ``num_classes``, and a classifier ``_WHY`` (the layer that fixes its 3 input channels) and
+    ``_grad_call`` for the shared ``grad`` / ``flat_grad`` / ``crossentropy_grad`` bodies."""
 
     def _count_args(self):
         return (self.num_classes,)
@@ -171,9 +172,7 @@ class _Model:
         ``fx3d_{entry}_workspace_bytes(*size_args)``.  Probabilities, or the dict of all outputs, where the input lives."""
         pts, N, B, on_dev = clouds
         x = self._on_device(pts, N, B, on_dev)
-        out = {"probs": DeviceArray.empty((self.num_classes, B), np.float32)}
-        if intermediates:
-            out.update({k: DeviceArray.empty(shape, dtype) for k, (shape, dtype) in optional.items()})
+        out = self._outputs(B, optional, intermediates)
         ws = workspace(_lib.query_bytes(f"fx3d_{entry}_workspace_bytes", *size_args), tag=entry)
         opt = [out[k].ptr if intermediates else None for k in optional]
         _lib.call(f"fx3d_{entry}_forward", self._params_dev().ptr, *lead, x.ptr, N, B, out["probs"].ptr, *opt, ws.ptr, ws.nbytes,
@@ -182,6 +181,12 @@ class _Model:
             out = {k: v.to_host() for k, v in out.items()}
         return out if intermediates else out["probs"]
 
+    def _outputs(self, B, optional, intermediates):
+        """``probs`` and, with ``intermediates``, the optional outputs of the table ``optional``, new on the device."""
+        out = {"probs": DeviceArray.empty((self.num_classes, B), np.float32)}
+        if intermediates:
+            out.update({k: DeviceArray.empty(shape, dtype) for k, (shape, dtype) in optional.items()})
+        return out
 
     @staticmethod
     def _like(a, name, shape, dtype, on_dev):
@@ -243,6 +248,28 @@ class _Model:
         onehot[y, cols] = 1
         return loss, np.asfortranarray(((probs - onehot).astype(np.float32) / np.float32(B)).astype(np.float32))
 
+    def _grads(self, named, X, glogits, input_grad, intermediates, **fwd):
+        """What a classifier's ``grad`` (``named``) and ``flat_grad`` return, from its ``_grad_call(X, glogits, input_grad,
+        intermediates, **fwd)``: the parameter gradients as named views or as the flat buffer, ``gx`` and, with
+        ``intermediates``, ``mid``, all where ``X`` lives."""
+        gp, gx, mid, on_dev = self._grad_call(X, glogits, input_grad, intermediates, **fwd)
+        if not on_dev:
+            gx = None if gx is None else gx.to_host()
+            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
+        g = self._grad_views(gp, on_dev) if named else (gp if on_dev else gp.to_host())
+        return (g, gx, mid) if intermediates else (g, gx)
+
+    def _crossentropy_grad(self, X, labels, with_fwd):
+        """A classifier's ``crossentropy_grad``: one forward (``with_fwd``: with its intermediates, which :meth:`grad` is then
+        given as ``fwd``), the loss and ``glogits`` on the host (:meth:`_crossentropy`), then :meth:`grad`."""
+        _, N, B, on_dev = self._clouds(X, self._WHY)
+        y = self._labels(labels, B)
+        fwd = self.forward(X, intermediates=with_fwd)
+        probs = fwd["probs"] if with_fwd else fwd
+        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
+        grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits, **({"fwd": fwd} if with_fwd else {}))
+        return loss, grads, gx
+
 
 class PointNet(_Model):
     """``PointNet(num_classes=10, K=64)`` (src/models/pointnet.jl:41-60).
@@ -260,7 +287,7 @@ class PointNet(_Model):
     forward -- BatchNorm at the batch statistics, Dropout as a given mask, the updated running statistics -- is
     :meth:`forward_train` (include/flux3d_hip.h "PointNet training-mode forward"); it is not differentiated yet."""
 
-    _NAME, _COUNT_FN = "PointNet", "fx3d_pointnet_param_count"
+    _NAME, _COUNT_FN, _WHY = "PointNet", "fx3d_pointnet_param_count", "stnKD(3)"
 
     def __init__(self, num_classes=10, K=64, seed=0):
         if int(K) != 64:
@@ -278,12 +305,15 @@ class PointNet(_Model):
         """Class probabilities ``(num_classes, B)`` of the clouds ``X``: a PointCloud, a device array or a numpy array,
         ``(3, N, B)`` or ``(3, N)`` (one cloud).  The result lives where the input lives.  ``intermediates=True``: a dict
         with ``probs``, ``logits`` (num_classes, B), ``stn`` (3, 3, B), ``fstn`` (64, 64, B) and ``pooled`` (1024, B)."""
-        _, N, B, _ = clouds = self._clouds(X, "stnKD(3)")
-        nc, f32 = self.num_classes, np.float32
-        optional = {"logits": ((nc, B), f32), "stn": ((3, 3, B), f32), "fstn": ((64, 64, B), f32), "pooled": ((1024, B), f32)}
-        return self._classify(clouds, "pointnet", (nc,), (N, B, nc), optional, intermediates)
+        _, N, B, _ = clouds = self._clouds(X, self._WHY)
+        return self._classify(clouds, "pointnet", (self.num_classes,), (N, B, self.num_classes), self._optional(B), intermediates)
 
     __call__ = forward
+
+    def _optional(self, B):
+        """The forward entries' optional outputs in their argument order: name -> (shape, dtype)."""
+        f32 = np.float32
+        return {"logits": ((self.num_classes, B), f32), "stn": ((3, 3, B), f32), "fstn": ((64, 64, B), f32), "pooled": ((1024, B), f32)}
 
     @staticmethod
     def dropout_mask(B, seed, p=0.4):
@@ -320,7 +350,7 @@ class PointNet(_Model):
         ``update=True`` writes ``running`` into the model's parameters, on the host (which reads them back: not inside a graph
         capture) and in the kept device copy: the next :meth:`forward` is the test-mode network after one training step's worth
         of statistics.  The gradient of this forward is not built."""
-        pts, N, B, on_dev = self._clouds(X, "stnKD(3)")
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
         nc, f32 = self.num_classes, np.float32
         if B < 2:
             raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
@@ -342,10 +372,8 @@ class PointNet(_Model):
         x = self._on_device(pts, N, B, on_dev)
         slots = self._stat_slots()
         nstat = slots[-1][2] + 2 * slots[-1][1]
-        out = {"probs": DeviceArray.empty((nc, B), f32)}
-        if intermediates:
-            out.update({"logits": DeviceArray.empty((nc, B), f32), "stn": DeviceArray.empty((3, 3, B), f32),
-                        "fstn": DeviceArray.empty((64, 64, B), f32), "pooled": DeviceArray.empty((1024, B), f32)})
+        optional = self._optional(B)
+        out = self._outputs(B, optional, intermediates)
         stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
         if intermediates or update:
             stats["running"] = DeviceArray.empty((nstat,), f32)
@@ -353,7 +381,7 @@ class PointNet(_Model):
         ws = workspace(nb, tag="pointnet_train")
         stream = current_stream().handle
         _lib.call("fx3d_pointnet_forward_train", params.ptr, nc, x.ptr, N, B, mask.ptr if mask is not None else None, momentum,
-                  out["probs"].ptr, *(out[k].ptr if intermediates else None for k in ("logits", "stn", "fstn", "pooled")),
+                  out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
                   stats["batch_stats"].ptr, stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
         if update:
             run = stats["running"]
@@ -378,7 +406,7 @@ class PointNet(_Model):
     def _grad_call(self, X, glogits, input_grad, intermediates):
         """fx3d_pointnet_grad after the argument checks: (the flat gradient, gx or None, the intermediates or None) on the
         device, and whether ``X`` lives there."""
-        pts, N, B, on_dev = self._clouds(X, "stnKD(3)")
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
         nc, f32 = self.num_classes, np.float32
         nb = _lib.query_bytes("fx3d_pointnet_grad_workspace_bytes", N, B, nc)  # (the library's own size limits)
         g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
@@ -397,11 +425,7 @@ class PointNet(_Model):
         """``(gflat, gx)``: the gradient of ``sum(glogits * logits)`` with respect to the parameters as ONE flat Float32 buffer
         with the layout of :meth:`flat_params` (the ``mu`` / ``sigma2`` slots are zero), and the gradient with respect to ``X``
         (``None`` with ``input_grad=False``).  Arguments, ``intermediates`` and placement as :meth:`grad`."""
-        gp, gx, mid, on_dev = self._grad_call(X, glogits, input_grad, intermediates)
-        if not on_dev:
-            gp, gx = gp.to_host(), (None if gx is None else gx.to_host())
-            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
-        return (gp, gx, mid) if intermediates else (gp, gx)
+        return self._grads(False, X, glogits, input_grad, intermediates)
 
     def grad(self, X, glogits, input_grad=True, intermediates=False):
         """``(grads, gx)``: the gradients of ``sum(glogits * logits)`` with respect to every parameter of the network and to
@@ -413,24 +437,14 @@ class PointNet(_Model):
         ``(grads, gx, mid)`` with ``mid`` a dict of ``gstn`` (3, 3, B) and ``gfstn`` (64, 64, B), the gradients at the two
         transforms, ``gh`` (64, N, B), the gradient at conv_block1's output, and ``gxt`` (3, N, B), the gradient at the
         transformed points.  Everything lives where ``X`` lives."""
-        gp, gx, mid, on_dev = self._grad_call(X, glogits, input_grad, intermediates)
-        grads = self._grad_views(gp, on_dev)
-        if not on_dev:
-            gx = None if gx is None else gx.to_host()
-            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
-        return (grads, gx, mid) if intermediates else (grads, gx)
+        return self._grads(True, X, glogits, input_grad, intermediates)
 
     def crossentropy_grad(self, X, labels):
         """``(loss, grads, gx)`` for ``Flux.crossentropy(m(X), onehot(labels))``, the mean over the batch: ``labels`` are B
         integers in [0, num_classes), 0-based.  One :meth:`forward` for ``probs``, which are read back to the host; ``loss =
         -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) / Float32(B)``
         with one Float32 subtraction and one Float32 division, then :meth:`grad`, inside which the forward runs again."""
-        _, N, B, on_dev = self._clouds(X, "stnKD(3)")
-        y = self._labels(labels, B)
-        probs = self.forward(X)
-        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
-        grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits)
-        return loss, grads, gx
+        return self._crossentropy_grad(X, labels, with_fwd=False)
 
 
 class DGCNN(_Model):
@@ -450,7 +464,7 @@ class DGCNN(_Model):
     EdgeConv stages inside are :meth:`EdgeConv.grad`'s kernel on the ``ec2.`` and ``ec1.`` parameters, bit for bit.  Training-mode
     BatchNorm (batch statistics) and Dropout in training mode are not differentiated."""
 
-    _NAME, _COUNT_FN = "DGCNN", "fx3d_dgcnn_param_count"
+    _NAME, _COUNT_FN, _WHY = "DGCNN", "fx3d_dgcnn_param_count", "EdgeConv([3, 32, 64, 64], K)"
 
     def __init__(self, num_classes=10, K=10, npoints=1024, seed=0):
         if int(num_classes) < 1:
@@ -463,15 +477,20 @@ class DGCNN(_Model):
     def _shapes(self):
         return dgcnn_param_shapes(self.num_classes)
 
+    def _clouds(self, X, why, F=3):
+        """:meth:`_Model._clouds` for clouds of ``npoints`` points."""
+        clouds = super()._clouds(X, why, F)
+        if clouds[1] != self.npoints:
+            raise ValueError(f"DGCNN(num_classes, K, npoints={self.npoints}) takes clouds of npoints points, got N={clouds[1]}: "
+                             "MaxPool((npoints,)) is the maximum over a whole cloud only then")
+        return clouds
+
     def forward(self, X, intermediates=False):
         """Class probabilities ``(num_classes, B)`` of the clouds ``X``: a PointCloud, a device array or a numpy array,
         ``(3, npoints, B)`` or ``(3, npoints)`` (one cloud).  The result lives where the input lives.
         ``intermediates=True``: a dict with ``probs``, ``logits`` (num_classes, B), ``idx1`` and ``idx2`` (K, N, B) int32,
         0-based, ``x1`` (64, N, B), ``x2`` (256, N, B) and ``pooled`` (1024, B)."""
-        _, N, B, _ = clouds = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
-        if N != self.npoints:
-            raise ValueError(f"DGCNN(num_classes, K, npoints={self.npoints}) takes clouds of npoints points, got N={N}: "
-                             "MaxPool((npoints,)) is the maximum over a whole cloud only then")
+        _, N, B, _ = clouds = self._clouds(X, self._WHY)
         nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
         optional = {"logits": ((nc, B), f32), "idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32),
                     "x2": ((256, N, B), f32), "pooled": ((1024, B), f32)}
@@ -481,13 +500,10 @@ class DGCNN(_Model):
 
     _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
 
-    def _grad_call(self, X, glogits, fwd, input_grad, intermediates):
+    def _grad_call(self, X, glogits, input_grad, intermediates, fwd=None):
         """fx3d_dgcnn_grad after the argument checks: (the flat gradient, gx or None, gx2 and gx1 or None) on the device, and
         whether ``X`` lives there."""
-        pts, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
-        if N != self.npoints:
-            raise ValueError(f"DGCNN(num_classes, K, npoints={self.npoints}) takes clouds of npoints points, got N={N}: "
-                             "MaxPool((npoints,)) is the maximum over a whole cloud only then")
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
         nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
         nb = _lib.query_bytes("fx3d_dgcnn_grad_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
         g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
@@ -519,11 +535,7 @@ class DGCNN(_Model):
         """``(gflat, gx)``: the gradient of ``sum(glogits * logits)`` with respect to the parameters as ONE flat Float32 buffer
         with the layout of :meth:`flat_params` (the ``mu`` / ``sigma2`` slots are zero), and the gradient with respect to ``X``
         (``None`` with ``input_grad=False``).  Arguments, ``intermediates`` and placement as :meth:`grad`."""
-        gp, gx, mid, on_dev = self._grad_call(X, glogits, fwd, input_grad, intermediates)
-        if not on_dev:
-            gp, gx = gp.to_host(), (None if gx is None else gx.to_host())
-            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
-        return (gp, gx, mid) if intermediates else (gp, gx)
+        return self._grads(False, X, glogits, input_grad, intermediates, fwd=fwd)
 
     def grad(self, X, glogits, fwd=None, input_grad=True, intermediates=False):
         """``(grads, gx)``: the gradients of ``sum(glogits * logits)`` with respect to every parameter of the network and to
@@ -535,24 +547,14 @@ class DGCNN(_Model):
         ``gx`` is ``(3, N, B)``, or ``None`` with ``input_grad=False``.  ``intermediates=True``: ``(grads, gx, mid)`` with
         ``mid`` a dict of ``gx2`` (256, N, B) and ``gx1`` (64, N, B), the gradients at ``x2`` and ``x1``.  Everything lives where
         ``X`` lives."""
-        gp, gx, mid, on_dev = self._grad_call(X, glogits, fwd, input_grad, intermediates)
-        grads = self._grad_views(gp, on_dev)
-        if not on_dev:
-            gx = None if gx is None else gx.to_host()
-            mid = None if mid is None else {k: v.to_host() for k, v in mid.items()}
-        return (grads, gx, mid) if intermediates else (grads, gx)
+        return self._grads(True, X, glogits, input_grad, intermediates, fwd=fwd)
 
     def crossentropy_grad(self, X, labels):
         """``(loss, grads, gx)`` for ``Flux.crossentropy(m(X), onehot(labels))``, the mean over the batch: ``labels`` are B
         integers in [0, num_classes), 0-based.  One ``forward(X, intermediates=True)``; its ``probs`` are read back to the host,
         ``loss = -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) /
         Float32(B)`` with one Float32 subtraction and one Float32 division, then :meth:`grad` with that forward."""
-        _, N, B, on_dev = self._clouds(X, "EdgeConv([3, 32, 64, 64], K)")
-        y = self._labels(labels, B)
-        fwd = self.forward(X, intermediates=True)
-        loss, glogits = self._crossentropy(fwd["probs"].to_host() if on_dev else fwd["probs"], y, B)
-        grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits, fwd=fwd)
-        return loss, grads, gx
+        return self._crossentropy_grad(X, labels, with_fwd=True)
 
 
 class EdgeConv(_Model):
@@ -650,24 +652,8 @@ class EdgeConv(_Model):
     __call__ = forward
 
     def _like_out(self, a, name, N, B, on_dev):
-        """``gout`` / ``out`` after its checks, as (cL, N, B): a device array, or a Float32 host array still to be uploaded.
-        It must live where ``X`` lives."""
-        cL = self.layers[-1]
-        ok = ((cL, N, B),) + (((cL, N),) if B == 1 else ())
-        if is_device(a) != on_dev:
-            raise TypeError(f"{name} must live where X lives ({'the device' if on_dev else 'the host'})")
-        if on_dev:
-            if a.dtype != np.float32:
-                raise TypeError(f"device {name} must be Float32, got {a.dtype}")
-            if tuple(a.shape) not in ok:
-                raise ValueError(f"{name} must be ({cL}, {N}, {B}), got {tuple(a.shape)}")
-            return a.reshape(cL, N, B)
-        a = np.asarray(a)
-        if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
-            raise TypeError(f"{name} must hold real numbers, got {a.dtype}")
-        if a.shape not in ok:
-            raise ValueError(f"{name} must be ({cL}, {N}, {B}), got {a.shape}")
-        return np.asfortranarray(a.reshape(cL, N, B, order="F").astype(np.float32))
+        """``gout`` / ``out`` after its checks (:meth:`_like`), as (cL, N, B)."""
+        return self._like(a, name, (self.layers[-1], N, B), np.float32, on_dev)
 
     def _adjoint_call(self, entry, X, gout, idx, out, results):
         """``fx3d_{entry}`` on the checked ``(X, gout, idx, out)`` of :meth:`input_grad`, everything on the device, with the
