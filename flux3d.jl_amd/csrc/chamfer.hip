@@ -479,15 +479,24 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     //      included, and everything that decides a result -- the exact distances, the 64-bit (distance, ORIGINAL index) minima --
     //      is as before.  The image order of candidates inside a cell is the arrival order of LDS atomics (it only moves a
     //      candidate between lane tiles); the order of the QUERIES is made unique (cell, then index), because it decides which
-    //      block and lane a query's term of the loss is summed in.  The rows (x, y, z, original index) of both orders go to the
-    //      block's scratch: the exact phase reads candidates by image position from there, the passes read their queries. ----
-    [[maybe_unused]] float4 *cs = nullptr, *qsw = nullptr;
+    //      block and lane a query's term of the loss is summed in.  Both orders go to the block's scratch as 16-bit ORIGINAL
+    //      INDICES (a permutation is all a block produces; rows of (x, y, z, index) left 20.5 MB dirty in the L2s at C2 for the
+    //      launch's end to write back: profiles/nn1_scratch_boundary.txt): the exact phase and the passes read the index by image /
+    //      window position and the point from the input cloud by index.  NO ADDRESS IS FORMED FROM A SLOT THIS LAUNCH DID NOT WRITE:
+    //      every reader either clamps its position below cnt (qwlen) or stays below cnt_pad + 64, which the staging fills. ----
+    [[maybe_unused]] unsigned short *cs = nullptr, *qsw = nullptr;  // slot = original index of the point at an image / window position
+    // a candidate by image position: its slot, then the point itself from the cloud (the Float32 values the image was built from)
+    [[maybe_unused]] auto cand_at = [&](int pos, float &x, float &y, float &z, unsigned int &id) {
+        id = cs[pos];
+        const P3 v = *reinterpret_cast<const P3 *>(cb + (size_t)id * 3);
+        x = v.x; y = v.y; z = v.z;
+    };
     [[maybe_unused]] bool sorted_c = false;
     [[maybe_unused]] int qwlen = 0;
     [[maybe_unused]] float4 *boxes = nullptr;
     if constexpr (PRUNE) {
         cs = p.pscr + (size_t)blockIdx.x * p.pscr_stride;
-        qsw = cs + kHChunkMax;
+        qsw = cs + kHScrCand;
         boxes = reinterpret_cast<float4 *>(wq + (kHThreads / 64) * 96);  // [64 lane tiles] x (lo, hi): 2 KiB behind the waves' scratch
         // (the waves' scratch is idle here: 20.5 of its 22 KiB hold the counters)  Cells are numbered t = ux | uy << 3 | uz << 6; the
         // SCANS walk them along the Hilbert curve (kHilbertCell), so the image order is the curve's order of the cells at two shifts per point.
@@ -710,7 +719,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                         const unsigned int t = qcr[e] >> 16;
                         const int rank = (int)(qtot[t] + ((qwh[wv * 256 + (t >> 1)] >> (16u * (t & 1u))) & 0xffffu) + (qcr[e] & 0xffffu));
                         if (rank >= qw0 && rank < qw1) {
-                            qsw[rank - qw0] = float4{qv[e].x, qv[e].y, qv[e].z, __builtin_bit_cast(float, qp)};
+                            qsw[rank - qw0] = (unsigned short)qp;  // (the ranks are a permutation: every slot of the window is written)
                             group_box(rank - qw0, qv[e].x, qv[e].y, qv[e].z);
                         }
                     }
@@ -723,7 +732,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
             for (int q0 = qw0 + wv * 64; q0 < qw1; q0 += kHThreads) {
                 const int qp = q0 + lane;
                 const P3 r = *reinterpret_cast<const P3 *>(qb + (size_t)(qp < qw1 ? qp : qw1 - 1) * 3);  // (lanes past the window repeat its last row)
-                if (qp < qw1) qsw[qp - qw0] = float4{r.x, r.y, r.z, __builtin_bit_cast(float, qp)};
+                if (qp < qw1) qsw[qp - qw0] = (unsigned short)qp;
                 const int kx = fkey((r.x - mu[0]) * sc), ky = fkey((r.y - mu[1]) * sc), kz = fkey((r.z - mu[2]) * sc);
                 const int lx = row_mm_key<false>(kx), ly = row_mm_key<false>(ky), lz = row_mm_key<false>(kz);
                 const int hx = row_mm_key<true>(kx), hy = row_mm_key<true>(ky), hz = row_mm_key<true>(kz);
@@ -781,13 +790,16 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                     if (kFull || pt < cnt) {
                         pieces(r4[k].x, r4[k].y, r4[k].z, pt, p0, p1);
                         const int id = sorted_c ? __builtin_bit_cast(int, r4[k].w) : j0 + pt;
-                        cs[pt] = float4{r4[k].x, r4[k].y, r4[k].z, __builtin_bit_cast(float, id)};
+                        cs[pt] = (unsigned short)id;
                         const float b3[3] = {(r4[k].x - mu[0]) * sc, (r4[k].y - mu[1]) * sc, (r4[k].z - mu[2]) * sc};
 #pragma unroll
                         for (int d = 0; d < 3; ++d) { lo3[d] = vmin(lo3[d], b3[d]); hi3[d] = vmax(hi3[d], b3[d]); }
                     } else {
                         make_pieces(0.f, 0.f, 0.f, p0, p1);
                         p1[7] = (_Float16)kPadF16;
+                        // (a slot is an index the exact phase forms an address from before it masks the row: the slots from cnt to
+                        //  cnt_pad + 64 -- the image's padding blocks included -- name point 0, whatever the workspace held)
+                        if (pt < kHScrCand) cs[pt] = 0;
                     }
                     imgp[i0] = p0;
                     imgp[i0 + 32] = p1;
@@ -815,6 +827,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                         const int pt = tl * 64 + k * 16 + (tid & 15), i0 = ((pt >> 5) * 2) * 32 + (pt & 31);
                         imgp[i0] = p0;
                         imgp[i0 + 32] = p1;
+                        if (pt < kHScrCand) cs[pt] = 0;  // (as in the ragged tile)
                     }
                     if ((tid & 15) == 0 && tl < 64) {
                         boxes[tl * 2] = float4{INFINITY, INFINITY, INFINITY, 0.0f};
@@ -863,9 +876,11 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 qi = (tile * tpb + tp) * QB + wv * 32 + jq;
                 if constexpr (PRUNE) {  // row (tp QB + wave's 32 + jq) of the block's window of the query cloud, in processing order
                     const int wpos = tp * QB + wv * 32 + jq;
-                    const float4 q4 = qsw[wpos < qwlen ? wpos : qwlen - 1];  // (lanes past the window: a valid query, no output)
-                    qr[0] = q4.x; qr[1] = q4.y; qr[2] = q4.z;
-                    qi = wpos < qwlen ? __builtin_bit_cast(int, q4.w) : NQ;
+                    const int wslot = wpos < qwlen ? wpos : qwlen - 1;  // (lanes past the window: a valid query, no output)
+                    const unsigned int qid = qsw[wslot];  // (a slot below qwlen: written by this block, an index below NQ)
+                    const P3 q3 = *reinterpret_cast<const P3 *>(qb + (size_t)qid * 3);
+                    qr[0] = q3.x; qr[1] = q3.y; qr[2] = q3.z;
+                    qi = wpos < qwlen ? (int)qid : NQ;
                 } else if (tp == 0) {  // requested before the bounding-box pass
 #pragma unroll
                     for (int d = 0; d < 3; ++d) qr[d] = qpre[d];
@@ -1217,8 +1232,9 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                                     if constexpr (PRUNE) {
 #pragma unroll
                                         for (int r = 0; r < 4; ++r) {
-                                            const float4 v = cs[jl0 + r < cnt ? jl0 + r : cnt - 1];
-                                            cx[u][r] = v.x; cy[u][r] = v.y; cz[u][r] = v.z; cid[u][r] = __builtin_bit_cast(int, v.w);
+                                            unsigned int id;  // (the position is clamped below cnt: a slot the staging wrote)
+                                            cand_at(jl0 + r < cnt ? jl0 + r : cnt - 1, cx[u][r], cy[u][r], cz[u][r], id);
+                                            cid[u][r] = (int)id;
                                         }
                                     } else if (vec && jl0 + 4 <= cnt) {
                                         load4pts(cb, j0 + jl0, cx[u], cy[u], cz[u]);
@@ -1326,13 +1342,17 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                             float cx[4], cy[4], cz[4];
                             [[maybe_unused]] int cid[4];
                             if constexpr (PRUNE) {
+                                // (round 6: no clamp -- slots up to cnt_pad <= kHChunkMax lie inside the block's scratch, the staging wrote the
+                                //  ones past cnt with index 0 and they are masked below -- and the key form chosen once per wave: the exact
+                                //  phase issues ~700 VALU per wave and pass, the SIMDs' busiest stretch; same-box A/B 43.0 -> 41.5 us kernel)
+                                // the run's four indices are one 8-byte load (jl0 is a multiple of 4), the points 12-byte loads from the cloud;
+                                // requesting the next trip's index words a trip ahead measured WORSE (+ 0.2 us: profiles/nn1_scratch_ab.txt)
+                                const uint2 w4 = *reinterpret_cast<const uint2 *>(cs + jl0);
+                                cid[0] = (int)(w4.x & 0xffffu); cid[1] = (int)(w4.x >> 16); cid[2] = (int)(w4.y & 0xffffu); cid[3] = (int)(w4.y >> 16);
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
-                                    // (round 6: no clamp -- rows up to cnt_pad <= kHChunkMax lie inside the block's scratch, the ones past cnt hold
-                                    //  whatever they held and are masked below -- and the key form chosen once per wave: the exact phase issues
-                                    //  ~700 VALU per wave and pass, the SIMDs' busiest stretch; same-box A/B 43.0 -> 41.5 us kernel)
-                                    const float4 v = cs[jl0 + r];
-                                    cx[r] = v.x; cy[r] = v.y; cz[r] = v.z; cid[r] = __builtin_bit_cast(int, v.w);
+                                    const P3 v = *reinterpret_cast<const P3 *>(cb + (size_t)(unsigned int)cid[r] * 3);
+                                    cx[r] = v.x; cy[r] = v.y; cz[r] = v.z;
                                 }
                             } else if (vec && jl0 + 4 <= cnt) {
                                 load4pts(cb, j0 + jl0, cx, cy, cz);
@@ -1407,8 +1427,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                                     float cc3[3];
                                     unsigned int cidx = (unsigned int)(j0 + jc);
                                     if constexpr (PRUNE) {
-                                        const float4 v = cs[jc];
-                                        cc3[0] = v.x; cc3[1] = v.y; cc3[2] = v.z; cidx = __builtin_bit_cast(unsigned int, v.w);
+                                        cand_at(jc, cc3[0], cc3[1], cc3[2], cidx);  // (jc < cnt: a slot the staging wrote)
                                     } else {
                                         const float *src = cb + (size_t)(j0 + jc) * 3;
                                         cc3[0] = src[0]; cc3[1] = src[1]; cc3[2] = src[2];
@@ -1429,8 +1448,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                         float cc3[3];
                         unsigned int cidx = (unsigned int)(j0 + jc);
                         if constexpr (PRUNE) {
-                            const float4 v = cs[jc];
-                            cc3[0] = v.x; cc3[1] = v.y; cc3[2] = v.z; cidx = __builtin_bit_cast(unsigned int, v.w);
+                            cand_at(jc, cc3[0], cc3[1], cc3[2], cidx);  // (the far list holds image positions below cnt)
                         } else {
                             const float *src = cb + (size_t)(j0 + jc) * 3;
                             cc3[0] = src[0]; cc3[1] = src[1]; cc3[2] = src[2];

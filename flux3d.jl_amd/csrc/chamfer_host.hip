@@ -233,14 +233,15 @@ const char *plan_kernel_name(const Plan &pl, int D) {
 }
 
 // Spatial pruning (nn1_f16_kernel<.., PRUNE>): one-chunk plans of the fp16 kernel without split or tail, clouds of at least 1024
-// points.  Rows of scratch per block: the candidate cloud in image order + the block's window of the query cloud.
+// points.  Slots of scratch per block (a 16-bit original index each): the candidate cloud in image order + the block's window of
+// the query cloud.
 int prune_rows_per_block(const Plan &pl, int N, int M, int D) {
     const int maxc = N > M ? N : M;
     if (plan_kernel(pl, D) != NN1_F16 || pl.nsplit != 1 || pl.tail != 0 || maxc > pl.chunk || maxc < 1024 || !opt(OPT_NN1_PRUNE)) return 0;
     if ((pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 16 + 2 > kHGroupsMax - 1) return 0;  // (the query groups' boxes: LDS for eight passes per block)
     // one pass per block does not repay the sort (measured at B = 8 .. 16 x 4096: 36 against 30 us; two passes -- C2 -- 46 against 53)
     if ((pl.tpb < pl.tpb_y ? pl.tpb : pl.tpb_y) < 2) return 0;
-    return kHChunkMax + (pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 512 + kHTail;
+    return kHScrCand + (pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 512 + kHTail;
 }
 
 // The caller's workspace, as byte offsets: the per-block partial sums at 0 (`tiles` per (direction, cloud): the plan's, or the
@@ -259,7 +260,7 @@ Workspace workspace_layout(const Plan &pl, int N, int M, int B, int D) {
     w.gres = w.sums + 2 * sizeof(double);
     w.need = w.gres + (pl.nsplit > 1 ? (size_t)pl.nsplit * 2 * B * maxq * sizeof(unsigned long long) : 0);
     w.pscr = (w.need + 255) & ~(size_t)255;
-    const size_t ps = (size_t)prune_rows_per_block(pl, N, M, D) * pl.grid * sizeof(float4);
+    const size_t ps = (size_t)prune_rows_per_block(pl, N, M, D) * pl.grid * sizeof(unsigned short);
     w.total = ps ? w.pscr + ps : w.need;
     return w;
 }
@@ -344,7 +345,7 @@ fx3d_status chamfer_forward(const float *x, int N, const float *y, int M, int B,
         return nn1_split_finalize_launch(p, w.tiles, st);
     }
     // spatial pruning when the workspace holds the blocks' scratch behind the partial sums (fx3d_chamfer_workspace_bytes asks for it)
-    if (w.total > w.need && ws_bytes >= w.total) p.pscr = reinterpret_cast<float4 *>(base + w.pscr);
+    if (w.total > w.need && ws_bytes >= w.total) p.pscr = reinterpret_cast<unsigned short *>(base + w.pscr);
     rc = run_nn1(p, D, pl, st);
     if (rc || p.ticket) return rc;
     const FinalizeParams f{p.partials, B, pl.tiles, pl.tiles_x, pl.tiles_y, p.sums_out, loss_dev, N, M, D, Bg, w1, w2};

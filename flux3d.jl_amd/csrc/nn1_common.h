@@ -40,9 +40,10 @@ struct Nn1Params {
     int fuse_split;              // 1: the last block of a query tile's chunk subsets merges their rows itself (arrival counters in the ticket slot's spare words)
     int tail;                    // > 0: a cloud of chunk + (1 .. tail) points is ONE chunk + a tail every query evaluates exactly
     // spatial pruning (round 6, nn1_f16_kernel<.., PRUNE = true>): per-block scratch in the caller's workspace -- the block's candidate
-    // cloud in image order and its window of the query cloud in processing order, as (x, y, z, original index) rows
-    float4 *pscr;                // nullptr: the launch runs the PRUNE = false instantiation
-    int pscr_stride;             // rows per block: kHChunkMax candidates + the query window (passes x 512 + kHTail)
+    // cloud in image order and its window of the query cloud in processing order, as 16-bit ORIGINAL INDICES (a pruned launch holds
+    // either cloud in one chunk of at most kHChunkMax points); the readers fetch the points themselves from x / y by index
+    unsigned short *pscr;        // nullptr: the launch runs the PRUNE = false instantiation
+    int pscr_stride;             // slots per block: kHScrCand candidates + the query window (passes x 512 + kHTail)
 };
 
 // The kernel a launch plan runs (chamfer_host.hip: plan_kernel) and the units' launchers.  Grid and dynamic LDS are the plan's;
@@ -103,6 +104,7 @@ constexpr int kHChunkMax = 4096;  // 32 B per candidate => 128 KiB
 constexpr int kHTail = 64;        // a cloud of up to kHChunkMax + kHTail points stays one LDS image: the last <= 64 candidates are
                                   // compared exactly by every query (N = M = 4097 was 2.1 x N = M = 4096: two half-empty chunks,
                                   // three rounds of blocks), and <= 64 queries beyond a block's passes are one more pass of one wave
+constexpr int kHScrCand = kHChunkMax + 64;  // (PRUNE) candidate slots of a block's scratch: the image's positions, its two padding blocks included
 constexpr int kHGroupsMax = 8 * 16 + 2 + 1;  // (PRUNE) 32-query groups of a block's window: up to eight passes + the folded remainder; + one slot: the query cloud's box
 
 // nn1_tiny_kernel's geometry (nn1_exact.hip)

@@ -132,7 +132,10 @@ FX3D_API fx3d_status fx3d_nn1(const float *x, int32_t N, const float *y, int32_t
  * and last the kernel: f16, tiny, small_d or generic): for tools and bug reports. */
 FX3D_API fx3d_status fx3d_nn1_plan_describe(int32_t N, int32_t M, int32_t B, int32_t D, char *buf, size_t n);
 
-/* Scratch needed by the chamfer entry points below (bytes). */
+/* Scratch needed by the chamfer entry points below (bytes).  While nn1_prune is on, a shape that takes the pruned launch asks for
+ * the blocks' scratch on top of the partial sums: 16-bit point indices, two bytes per candidate and per query of a block's window
+ * (2.7 MB at B = 32, N = M = 4096).  A workspace of at least this size runs pruned, a smaller one that still holds the partial
+ * sums (the size reported with nn1_prune = 0) runs unpruned; both give the same indices. */
 FX3D_API fx3d_status fx3d_chamfer_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D,
                                                   size_t *bytes);
 

@@ -26,9 +26,10 @@ def main():
         "correction": "gfx950 FETCH_SIZE counts 128-B requests as 64 B (MI355X_MICROARCH.md HBM section): read side doubled; WRITE_SIZE uncorrected",
         "nn1_hbm_bytes_per_launch": int(round(2 * fetch_kb * 1024 + write_kb * 1024)),
         "algorithmic_bytes_per_launch": 4 * 3 * 32 * 8192 + 8 * 2 * 32 * 8,
-        "traffic_note": "since round 6 (spatial pruning) a block writes its candidate cloud in image order and its query window as 16-byte rows to "
-                        "scratch in the workspace (256 blocks x (4096 + 1088) rows = 21 MB) and the exact phase reads rows back: WRITE_SIZE ~ 20 MB, "
-                        "FETCH ~ 14.5 MB at C2 -- 0.84 TB/s over the kernel, a tenth of the HBM peak; the kernel is issue bound",
+        "traffic_note": "since round 6 (spatial pruning) a block writes its candidate cloud's image order and its query window to scratch in the "
+                        "workspace; as 16-bit original indices (256 blocks x (4160 + 1088) slots x 2 B = 2.7 MB) since profiles/nn1_scratch_ab.txt, and "
+                        "the exact phase gathers the points from the input clouds by index: WRITE_SIZE ~ 2.6 MB, FETCH ~ 5.1 MB at C2 (as 16-byte rows: "
+                        "20.5 and 13 MB); a few percent of the HBM peak; the kernel is issue bound",
     }
     for c in ("SQ_INSTS_MFMA", "SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_INSTS_SALU", "SQ_WAVE_CYCLES",
               "SQ_BUSY_CYCLES", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_VALU", "SQ_WAIT_ANY"):
