@@ -124,6 +124,8 @@ SIGNATURES = {
     "fx3d_pointnet_stat_count": [C.POINTER(c_i64)],
     "fx3d_pointnet_train_workspace_bytes": [c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_pointnet_forward_train": [vp, c_i32, vp, c_i32, c_i32, vp, c_f32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "fx3d_pointnet_grad_train_workspace_bytes": [c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_pointnet_grad_train": [vp, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_dgcnn_param_count": [c_i32, C.POINTER(c_i64)],
     "fx3d_dgcnn_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_dgcnn_forward": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],

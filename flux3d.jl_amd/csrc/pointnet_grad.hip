@@ -260,49 +260,6 @@ __device__ __forceinline__ void column_pass(float *g, const float *r, const Bn &
     part_b[2 * cout + o] = sbe;
 }
 
-// out[c + cin o] = the chain from +0 over the tile's 64 rows, ascending, of fmaf(A[p][c], D[p][o], acc); cin and cout multiples
-// of 32.  v_mfma_f32_32x32x2_f32 takes two rows per instruction, the lower first: lane (h, j) gives A[p + h][c0 + j] and
-// D[p + h][o0 + j], and holds the result's rows c0 + mfma_row(r, h) of column o0 + j.  Rows beyond the cloud have D = +0.
-__device__ __forceinline__ void hsum_mfma(const float *A, const float *D, int cin, int cout, float *__restrict__ out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    const int nci = cin / 32, nt = nci * (cout / 32);
-    for (int t = wave; t < nt; t += kPtThreads / 64) {
-        const int c0 = (t % nci) * 32, o0 = (t / nci) * 32;
-        const float *ap = A + h * kLd + c0 + j, *dp = D + h * kLd + o0 + j;
-        f32x16 acc = {0};
-#pragma unroll 8
-        for (int p = 0; p < kTile; p += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[p * kLd], dp[p * kLd], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[c0 + mfma_row(r, h) + (size_t)cin * (o0 + j)] = acc[r];
-    }
-}
-
-// out[p][c] = the chain from +0 over o < COUT, ascending, of fmaf(dz[p][o], W[c + cin o], acc) for the tile's 64 rows and
-// c < cin (a multiple of 32), W as the forward reads it.  A wave owns (32 channels) x (one 32-point half) at a time.
-template <int COUT>
-__device__ __forceinline__ void back_mfma(const float *dz, float *out, int cin, const float *__restrict__ W) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    for (int t = wave; t < 2 * (cin / 32); t += kPtThreads / 64) {
-        const int half = t & 1, c = (t >> 1) * 32 + j;
-        const float *ap = dz + (half * 32 + j) * kLd + h, *wp = W + c + (size_t)cin * h;
-        f32x16 acc = {0};
-#pragma unroll 8
-        for (int o = 0; o < COUT; o += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[o], wp[(size_t)cin * o], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[(half * 32 + mfma_row(r, h)) * kLd + c] = acc[r];
-    }
-}
-
-// H[c + 3 o] = the chain over the tile's valid rows of fmaf(xs[p][c], d[p][o], acc), c < 3, o < 64: threads first .. first + 191
-__device__ __forceinline__ void hsum3(const float *xs, const float *d, int nvalid, int first, float *__restrict__ out) {
-    const int e = threadIdx.x - first;
-    if (e < 0 || e >= 192) return;
-    const int o = e / 3, c = e - 3 * o;
-    float acc = 0.0f;
-    for (int p = 0; p < nvalid; ++p) acc = fmaf(xs[p * 3 + c], d[p * kLd + o], acc);
-    out[e] = acc;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(kPtThreads) void pointnet_trunk_bwd_kernel(const TrunkArgs a) {
     extern __shared__ float lds[];
@@ -429,9 +386,6 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_trunk_bwd_kernel(const Tr
 }
 
 // ---- the last convolution's parameter sums -----------------------------------------------------------------------------------------
-// the gradient's block of a conv layer with its BatchNorm: W | b | gamma | beta | mu | var
-struct GradBlock { float *W, *b, *g, *be, *m, *v; };
-
 // one block per output channel c, thread i owns dW[i, c]: one chain over the clouds that have a winner, b ascending
 __global__ __launch_bounds__(128) void pointnet_conv3_pgrad_kernel(const float *__restrict__ awin, const int32_t *__restrict__ nstar,
                                                                    const float *__restrict__ dc3, const float *__restrict__ gy3,
@@ -460,9 +414,6 @@ __global__ __launch_bounds__(128) void pointnet_conv3_pgrad_kernel(const float *
 // ---- the finishing kernels -----------------------------------------------------------------------------------------------------
 // dst[e] = the chain of Float32 additions from +0 over the tile partials (b ascending, tile ascending) for e < n; +0 for the nz
 // elements after them (a BatchNorm's mu and var).  blockIdx.y: the segment.
-struct Seg { int at; float *dst; int n, nz; };
-constexpr int kMaxSegs = 3;
-struct ReduceArgs { const float *part; Seg s[kMaxSegs]; int psize, nparts; };
 __global__ __launch_bounds__(256) void pointnet_reduce_kernel(const ReduceArgs a) {
     const Seg s = blockIdx.y == 0 ? a.s[0] : blockIdx.y == 1 ? a.s[1] : a.s[2];
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -525,10 +476,6 @@ __global__ __launch_bounds__(256) void bn_sums_kernel(const float *__restrict__ 
     g.m[o] = 0.0f;
     g.v[o] = 0.0f;
 }
-
-float *mut(const float *p) { return const_cast<float *>(p); }
-GradBlock grad_block(const Conv &c) { return GradBlock{mut(c.W), mut(c.b), mut(c.bn.g), mut(c.bn.b), mut(c.bn.m), mut(c.bn.v)}; }
-GradBlock grad_block(const Bn &bn) { return GradBlock{nullptr, nullptr, mut(bn.g), mut(bn.b), mut(bn.m), mut(bn.v)}; }
 
 // The workspace: the forward's h, T, F and per round the tile maxima, first points and BatchNorm inputs | the head's vectors
 // (used by the rounds in turn) | the winners' rows | the tile partials (the widest round's) | conv_block1's sums | the feat
@@ -603,6 +550,34 @@ Seg layer_seg(int at, const Conv &g, int cin, int cout) { return Seg{at, mut(g.W
 
 }  // namespace
 
+namespace fx3d {
+namespace mlp {
+namespace pointnet {
+
+fx3d_status launch_reduce(const ReduceArgs &ra, int nsegs, hipStream_t st) {
+    int widest = 0;
+    for (int k = 0; k < nsegs; ++k) widest = ra.s[k].n + ra.s[k].nz > widest ? ra.s[k].n + ra.s[k].nz : widest;
+    hipLaunchKernelGGL(pointnet_reduce_kernel, dim3(blocks(widest).x, nsegs), dim3(256), 0, st, ra);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+fx3d_status launch_cloud_reduce(const float *part, int psize, int at, int ntiles, int n, int B, float *dst, hipStream_t st) {
+    hipLaunchKernelGGL(pointnet_cloud_reduce_kernel, dim3(blocks(n).x, B), dim3(256), 0, st, part, psize, at, ntiles, n, dst);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+fx3d_status launch_dense_sums(const DenseSums &q, hipStream_t st) {
+    hipLaunchKernelGGL(dense_sums_kernel, blocks((long long)(q.nin + 1) * q.nout), dim3(256), 0, st, q);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+}  // namespace pointnet
+}  // namespace mlp
+}  // namespace fx3d
+
 extern "C" {
 
 fx3d_status fx3d_pointnet_grad_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes) {
@@ -676,8 +651,7 @@ fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, con
         const DenseSums s1{hb.dd1, hb.pooled, kFeat, 512, B, mut(g.d1.W), mut(g.d1.b)}, s2{hb.dd2, hb.a1, 512, 256, B, mut(g.d2.W), mut(g.d2.b)},
             s3{hb.dd3, hb.a2, 256, g.n3, B, mut(g.d3.W), mut(g.d3.b)};
         for (const DenseSums &q : {s1, s2, s3}) {
-            hipLaunchKernelGGL(dense_sums_kernel, blocks((long long)(q.nin + 1) * q.nout), dim3(256), 0, st, q);
-            FX3D_LAUNCH_CHECK();
+            if ((r = launch_dense_sums(q, st)) != FX3D_OK) return r;
         }
         if (k == 2) {
             hipLaunchKernelGGL(bn_sums_kernel, blocks(512), dim3(256), 0, st, hb.gy1, hb.xh1, 512, B, grad_block(g.bn1));
@@ -690,19 +664,12 @@ fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, con
     auto reduce = [&](std::initializer_list<Seg> segs, int psize) -> fx3d_status {
         ReduceArgs ra{};
         ra.part = t.part; ra.psize = psize; ra.nparts = nt * B;
-        int k = 0, widest = 0;
-        for (const Seg &q : segs) {
-            ra.s[k++] = q;
-            widest = q.n + q.nz > widest ? q.n + q.nz : widest;
-        }
-        hipLaunchKernelGGL(pointnet_reduce_kernel, dim3(blocks(widest).x, k), dim3(256), 0, st, ra);
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
+        int k = 0;
+        for (const Seg &q : segs) ra.s[k++] = q;
+        return launch_reduce(ra, k, st);
     };
     auto cloud_reduce = [&](int psize, int at, int cnt, float *dst) -> fx3d_status {
-        hipLaunchKernelGGL(pointnet_cloud_reduce_kernel, dim3(blocks(cnt).x, B), dim3(256), 0, st, t.part, psize, at, nt, cnt, dst);
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
+        return launch_cloud_reduce(t.part, psize, at, nt, cnt, B, dst, st);
     };
 
     // feat and cls

@@ -1,4 +1,7 @@
-// What pointnet.hip (the forward), pointnet_train.hip (the training-mode forward) and pointnet_grad.hip (the adjoint) share.
+// What pointnet.hip (the forward), pointnet_train.hip (the training-mode forward), pointnet_grad.hip (the adjoint) and
+// pointnet_grad_train.hip (the training-mode adjoint) share.  At the end, what only some of them share: the fold of a BatchNorm's
+// Float64 tile sums (the two training-mode units), and the adjoints' MFMA chains over a tile (hsum_mfma, back_mfma, hsum3) with the
+// launches of pointnet_grad.hip's finishing kernels.
 // On the host: the walk over the flat parameter buffer, the forward's workspace, the size check of the entries, the
 // arguments of the forward's two kernels per round (set_round, stn_head, feat_head) and their launches (defined in
 // pointnet.hip, which owns the kernels).  On the device: a round's layer chain (round_trunk, with its tile loads), the slab
@@ -331,6 +334,97 @@ __device__ __forceinline__ void head_finish(const HeadArgs &a, int b, const floa
         }
     }
     if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
+}
+
+// ---- the fold of a convolution BatchNorm's Float64 tile sums (pointnet_train.hip's statistics, pointnet_grad_train.hip's dbeta / dgamma)
+constexpr int kFinishGroups = FX3D_POINTNET_STAT_GROUPS;  // interleaved partial sums over (tile, cloud), the header's order
+constexpr int kFinishChannels = 16;                       // channels of one finishing block: 256 contiguous bytes per read
+constexpr int kFinishThreads = kFinishGroups * kFinishChannels;
+// Folds sums (2, C, T) over the T = ntiles B tile sums t = tile + ntiles b of a layer: kFinishGroups chains, chain g over
+// t = g, g + kFinishGroups, ... ascending from +0.0, then the chains in ascending g from +0.0; finish(c, s1, s2) in the thread
+// that owns channel c.  One block of kFinishThreads = 16 channels (C is a multiple of 16).
+template <class Finish>
+__device__ __forceinline__ void fold_tile_sums(const double *__restrict__ sums, int C, long long T, Finish finish) {
+    __shared__ double p1[kFinishGroups][kFinishChannels], p2[kFinishGroups][kFinishChannels];
+    const int cl = threadIdx.x % kFinishChannels, g = threadIdx.x / kFinishChannels;
+    const int c = blockIdx.x * kFinishChannels + cl;
+    double s1 = 0.0, s2 = 0.0;
+    for (long long t = g; t < T; t += kFinishGroups) {
+        const double *at = sums + 2 * ((size_t)t * C + c);
+        s1 = s1 + at[0];
+        s2 = s2 + at[1];
+    }
+    p1[g][cl] = s1;
+    p2[g][cl] = s2;
+    __syncthreads();
+    if (g != 0) return;
+    s1 = 0.0; s2 = 0.0;
+    for (int k = 0; k < kFinishGroups; ++k) {
+        s1 = s1 + p1[k][cl];
+        s2 = s2 + p2[k][cl];
+    }
+    finish(c, s1, s2);
+}
+
+// ---- what the two adjoints (pointnet_grad.hip, pointnet_grad_train.hip) share ------------------------------------------------------
+// the gradient's block of a conv layer with its BatchNorm: W | b | gamma | beta | mu | var
+struct GradBlock { float *W, *b, *g, *be, *m, *v; };
+
+// a segment of a tile partial and where its chain over the partials goes ("PointNet adjoint": b ascending, tile ascending)
+struct Seg { int at; float *dst; int n, nz; };
+constexpr int kMaxSegs = 3;
+struct ReduceArgs { const float *part; Seg s[kMaxSegs]; int psize, nparts; };
+inline float *mut(const float *p) { return const_cast<float *>(p); }
+inline GradBlock grad_block(const Conv &c) { return GradBlock{mut(c.W), mut(c.b), mut(c.bn.g), mut(c.bn.b), mut(c.bn.m), mut(c.bn.v)}; }
+inline GradBlock grad_block(const Bn &bn) { return GradBlock{nullptr, nullptr, mut(bn.g), mut(bn.b), mut(bn.m), mut(bn.v)}; }
+
+// pointnet_grad.hip's finishing kernels on st: the chains over `nparts` partials of `psize` floats for the nsegs segments of ra;
+// the same per cloud (dst[e + n b] over the cloud's ntiles partials); a dense layer's sums over the clouds
+fx3d_status launch_reduce(const ReduceArgs &ra, int nsegs, hipStream_t st);
+fx3d_status launch_cloud_reduce(const float *part, int psize, int at, int ntiles, int n, int B, float *dst, hipStream_t st);
+fx3d_status launch_dense_sums(const DenseSums &q, hipStream_t st);
+
+// out[c + cin o] = the chain from +0 over the tile's 64 rows, ascending, of fmaf(A[p][c], D[p][o], acc); cin and cout multiples
+// of 32.  v_mfma_f32_32x32x2_f32 takes two rows per instruction, the lower first: lane (h, j) gives A[p + h][c0 + j] and
+// D[p + h][o0 + j], and holds the result's rows c0 + mfma_row(r, h) of column o0 + j.  Rows beyond the cloud have D = +0.
+__device__ __forceinline__ void hsum_mfma(const float *A, const float *D, int cin, int cout, float *__restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const int nci = cin / 32, nt = nci * (cout / 32);
+    for (int t = wave; t < nt; t += kPtThreads / 64) {
+        const int c0 = (t % nci) * 32, o0 = (t / nci) * 32;
+        const float *ap = A + h * kLd + c0 + j, *dp = D + h * kLd + o0 + j;
+        f32x16 acc = {0};
+#pragma unroll 8
+        for (int p = 0; p < kTile; p += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[p * kLd], dp[p * kLd], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[c0 + mfma_row(r, h) + (size_t)cin * (o0 + j)] = acc[r];
+    }
+}
+
+// out[p][c] = the chain from +0 over o < COUT, ascending, of fmaf(dz[p][o], W[c + cin o], acc) for the tile's 64 rows and
+// c < cin (a multiple of 32), W as the forward reads it.  A wave owns (32 channels) x (one 32-point half) at a time.
+template <int COUT>
+__device__ __forceinline__ void back_mfma(const float *dz, float *out, int cin, const float *__restrict__ W) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    for (int t = wave; t < 2 * (cin / 32); t += kPtThreads / 64) {
+        const int half = t & 1, c = (t >> 1) * 32 + j;
+        const float *ap = dz + (half * 32 + j) * kLd + h, *wp = W + c + (size_t)cin * h;
+        f32x16 acc = {0};
+#pragma unroll 8
+        for (int o = 0; o < COUT; o += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[o], wp[(size_t)cin * o], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[(half * 32 + mfma_row(r, h)) * kLd + c] = acc[r];
+    }
+}
+
+// H[c + 3 o] = the chain over the tile's valid rows of fmaf(xs[p][c], d[p][o], acc), c < 3, o < 64: threads first .. first + 191
+__device__ __forceinline__ void hsum3(const float *xs, const float *d, int nvalid, int first, float *__restrict__ out) {
+    const int e = threadIdx.x - first;
+    if (e < 0 || e >= 192) return;
+    const int o = e / 3, c = e - 3 * o;
+    float acc = 0.0f;
+    for (int p = 0; p < nvalid; ++p) acc = fmaf(xs[p * 3 + c], d[p * kLd + o], acc);
+    out[e] = acc;
 }
 
 }  // namespace pointnet

@@ -26,9 +26,6 @@ using namespace fx3d::mlp::pointnet;
 
 namespace {
 
-constexpr int kFinishGroups = FX3D_POINTNET_STAT_GROUPS;  // interleaved partial sums over (tile, cloud), the header's order
-constexpr int kFinishChannels = 16;                       // channels of one finishing block: 256 contiguous bytes per read
-constexpr int kFinishThreads = kFinishGroups * kFinishChannels;
 constexpr int kDenseStatThreads = 256;
 
 // one BatchNorm's statistics: where they go, and the running values they update
@@ -135,29 +132,10 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_stats_kernel(const StatAr
     });
 }
 
-// Folds sums (2, C, T) over the T = ntiles B tile sums t = tile + ntiles b of a layer: kFinishGroups chains, chain g over
-// t = g, g + kFinishGroups, ... ascending from +0.0, then the chains in ascending g from +0.0.  One block = 16 channels.
+// the fold of a layer's tile sums (fold_tile_sums, pointnet_net.h), then the mean, the variance and the running statistics
 __global__ __launch_bounds__(kFinishThreads) void pointnet_stat_finish_kernel(const double *__restrict__ sums, int C, long long T,
                                                                             const StatOut o) {
-    __shared__ double p1[kFinishGroups][kFinishChannels], p2[kFinishGroups][kFinishChannels];
-    const int cl = threadIdx.x % kFinishChannels, g = threadIdx.x / kFinishChannels;
-    const int c = blockIdx.x * kFinishChannels + cl;  // C is a multiple of 16
-    double s1 = 0.0, s2 = 0.0;
-    for (long long t = g; t < T; t += kFinishGroups) {
-        const double *at = sums + 2 * ((size_t)t * C + c);
-        s1 = s1 + at[0];
-        s2 = s2 + at[1];
-    }
-    p1[g][cl] = s1;
-    p2[g][cl] = s2;
-    __syncthreads();
-    if (g != 0) return;
-    s1 = 0.0; s2 = 0.0;
-    for (int k = 0; k < kFinishGroups; ++k) {
-        s1 = s1 + p1[k][cl];
-        s2 = s2 + p2[k][cl];
-    }
-    finish_channel(o, c, s1, s2);
+    fold_tile_sums(sums, C, T, [&](int c, double s1, double s2) { finish_channel(o, c, s1, s2); });
 }
 
 // a dense BatchNorm: thread c sums channel c of act (C, B) over the clouds in ascending b from +0.0, and finishes it

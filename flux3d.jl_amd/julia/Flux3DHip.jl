@@ -1660,6 +1660,41 @@ function pointnet_gradient(m::PointNet, X::HipArray{Float32,3}, glogits::HipArra
     return gflat, gx
 end
 
+# The same for the TRAINING-mode network (include/flux3d_hip.h "PointNet training-mode adjoint"): the gradients of
+# sum(glogits .* logits) for the logits of pointnet_forward_train(m, X; dropout), μ and σ² of every BatchNorm functions of the
+# batch, the dropout multipliers constants.  batch_stats: what pointnet_forward_train returned for the same (m, X, dropout);
+# without it that forward runs first.  Returns (gflat, gx) as pointnet_gradient does.  B >= 2.
+function pointnet_gradient_train(m::PointNet, X::HipArray{Float32,3}, glogits::HipArray{Float32,2};
+                                 dropout::Union{Nothing,HipArray{Float32,2}} = nothing,
+                                 batch_stats::Union{Nothing,HipArray{Float32,1}} = nothing, input_grad::Bool = true)
+    size(X, 1) == 3 || error("PointNet takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    (N >= 1 && B >= 2) || error("PointNet in training mode needs at least one point and two clouds")
+    nc = size(_dense_wb(m.cls)[1], 1)
+    size(_dense_wb(m.fstn[12])[1], 1) == 64 * 64 ||
+        error("PointNet(num_classes, K) needs K = 64: conv_block1 has 64 output channels whatever K is (src/models/pointnet.jl:41-60)")
+    size(glogits) == (nc, B) || error("glogits must be ($nc, $B), got $(size(glogits))")
+    (dropout === nothing || size(dropout) == (256, B)) || error("dropout must be (256, $B), got $(size(dropout))")
+    nstat = pointnet_stat_count()
+    (batch_stats === nothing || length(batch_stats) == nstat) || error("batch_stats must hold $nstat floats, got $(length(batch_stats))")
+    stats = batch_stats === nothing ? pointnet_forward_train(m, X; dropout = dropout).batch_stats : batch_stats
+    params = pointnet_params(m)
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_pointnet_grad_train_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(nc)::Int32,
+                                                              nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    gflat = HipArray{Float32}(undef, length(params))
+    gx = input_grad ? HipArray{Float32}(undef, 3, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_pointnet_grad_train(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, X.ptr::Ptr{Cvoid}, Int32(N)::Int32,
+                                              Int32(B)::Int32, opt(dropout)::Ptr{Cvoid}, stats.ptr::Ptr{Cvoid},
+                                              glogits.ptr::Ptr{Cvoid}, gflat.ptr::Ptr{Cvoid}, opt(gx)::Ptr{Cvoid}, C_NULL::Ptr{Cvoid},
+                                              C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid},
+                                              length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    return gflat, gx
+end
+
 # ---- DGCNN inference: (m::DGCNN)(X) (src/models/dgcnn.jl:113-147) in test mode --------------------------------------------
 # As for PointNet: the Flux layers' arrays flattened in forward order (include/flux3d_hip.h "DGCNN inference") on every call,
 # running statistics, Dropout as the identity.  An EdgeConv's mlp is a Chain of conv_bn_blocks, each a Chain(Conv, BatchNorm,

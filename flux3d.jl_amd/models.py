@@ -7,7 +7,8 @@ fx3d_pointnet_forward / fx3d_dgcnn_forward / fx3d_edgeconv_forward reads, and ch
 launch.  EdgeConv has its input gradient and its parameter gradients, and DGCNN and PointNet the gradients of the
 whole network with respect to every parameter and to the input points (``DGCNN.grad`` over fx3d_dgcnn_grad, "DGCNN adjoint";
 ``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode.  PointNet also has its
-training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_train, "PointNet training-mode forward")."""
+training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_train, "PointNet training-mode forward") and that
+forward's gradients (``PointNet.grad_train`` over fx3d_pointnet_grad_train, "PointNet training-mode adjoint")."""
 import ctypes as C
 
 import numpy as np
@@ -285,7 +286,9 @@ class PointNet(_Model):
     one library call (include/flux3d_hip.h "PointNet adjoint"), :meth:`flat_grad` the same as one flat buffer,
     :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  The training-mode
     forward -- BatchNorm at the batch statistics, Dropout as a given mask, the updated running statistics -- is
-    :meth:`forward_train` (include/flux3d_hip.h "PointNet training-mode forward"); it is not differentiated yet."""
+    :meth:`forward_train` (include/flux3d_hip.h "PointNet training-mode forward"), and its gradients -- mu and sigma2 functions of
+    the batch -- are :meth:`grad_train`, :meth:`flat_grad_train` and :meth:`crossentropy_grad_train` (include/flux3d_hip.h
+    "PointNet training-mode adjoint")."""
 
     _NAME, _COUNT_FN, _WHY = "PointNet", "fx3d_pointnet_param_count", "stnKD(3)"
 
@@ -349,7 +352,7 @@ class PointNet(_Model):
         step (``momentum``; computed from the model's ``mu`` / ``sigma2``).  Everything lives where ``X`` lives.
         ``update=True`` writes ``running`` into the model's parameters, on the host (which reads them back: not inside a graph
         capture) and in the kept device copy: the next :meth:`forward` is the test-mode network after one training step's worth
-        of statistics.  The gradient of this forward is not built."""
+        of statistics.  The gradient of this forward is :meth:`grad_train`."""
         pts, N, B, on_dev = self._clouds(X, self._WHY)
         nc, f32 = self.num_classes, np.float32
         if B < 2:
@@ -358,14 +361,7 @@ class PointNet(_Model):
         momentum = float(momentum)
         if not (np.isfinite(momentum) and 0.0 <= momentum <= 1.0):
             raise ValueError(f"momentum must be finite and in [0, 1], got {momentum}")
-        mask = None
-        if dropout is not None:
-            if isinstance(dropout, (int, np.integer)):
-                mask = self.dropout_mask(B, int(dropout))
-            else:
-                if is_device(dropout) and not on_dev:
-                    raise TypeError("a device dropout mask needs X on the device")
-                mask = self._like(dropout, "dropout", (256, B), f32, is_device(dropout))
+        mask = self._train_mask(dropout, B, on_dev)
         nb = _lib.query_bytes("fx3d_pointnet_train_workspace_bytes", N, B, nc)  # (the library's own size limits)
         if mask is not None and not is_device(mask):
             mask = DeviceArray.from_host(mask)
@@ -403,22 +399,70 @@ class PointNet(_Model):
 
     _MID = {"gstn": (3, 3), "gfstn": (64, 64), "gh": (64, None), "gxt": (3, None)}  # fx3d_pointnet_grad's optional outputs, in order
 
-    def _grad_call(self, X, glogits, input_grad, intermediates):
-        """fx3d_pointnet_grad after the argument checks: (the flat gradient, gx or None, the intermediates or None) on the
-        device, and whether ``X`` lives there."""
+    def _train_mask(self, dropout, B, on_dev):
+        """``dropout`` of the training-mode methods after its checks: ``None``, or the ``(256, B)`` multipliers (an ``int``: the
+        seed of :meth:`dropout_mask`) as a device array, or as a host array still to be uploaded."""
+        if dropout is None:
+            return None
+        if isinstance(dropout, (int, np.integer)):
+            return self.dropout_mask(B, int(dropout))
+        if is_device(dropout) and not on_dev:
+            raise TypeError("a device dropout mask needs X on the device")
+        return self._like(dropout, "dropout", (256, B), np.float32, is_device(dropout))
+
+    def _grad_call(self, X, glogits, input_grad, intermediates, train=False, dropout=None, fwd=None):
+        """fx3d_pointnet_grad (``train``: fx3d_pointnet_grad_train, with the dropout multipliers and the batch statistics of
+        ``fwd``, or of a :meth:`forward_train` run here) after the argument checks: (the flat gradient, gx or None, the
+        intermediates or None) on the device, and whether ``X`` lives there."""
         pts, N, B, on_dev = self._clouds(X, self._WHY)
         nc, f32 = self.num_classes, np.float32
-        nb = _lib.query_bytes("fx3d_pointnet_grad_workspace_bytes", N, B, nc)  # (the library's own size limits)
+        entry = "fx3d_pointnet_grad_train" if train else "fx3d_pointnet_grad"
+        extra = ()
+        if train:
+            if B < 2:
+                raise ValueError(f"training-mode BatchNorm needs at least two clouds, got B={B}")
+            mask = self._train_mask(dropout, B, on_dev)
+            slots = self._stat_slots()
+            nstat = slots[-1][2] + 2 * slots[-1][1]
+            if fwd is not None:
+                if not isinstance(fwd, dict) or "batch_stats" not in fwd:
+                    raise TypeError("fwd must be the dict of forward_train(..., intermediates=True)")
+                named = fwd["batch_stats"]
+                if [k for k in named] != [bn + f for bn, *_ in slots for f in (".mu", ".sigma2")]:
+                    raise ValueError("fwd['batch_stats'] must hold mu and sigma2 of the 13 BatchNorms in forward order")
+                for (bn, C, _, _) in slots:
+                    for f in (".mu", ".sigma2"):
+                        v = named[bn + f]
+                        if is_device(v) != on_dev:
+                            raise TypeError("fwd must live where X lives")
+                        if tuple(v.shape) != (C,) or v.dtype != f32:
+                            raise ValueError(f"fwd['batch_stats'][{bn + f!r}] must be Float32 ({C},), got {v.dtype} {tuple(v.shape)}")
+        nb = _lib.query_bytes(entry + "_workspace_bytes", N, B, nc)  # (the library's own size limits)
         g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
         if not on_dev:
             g = DeviceArray.from_host(g)
         x = self._on_device(pts, N, B, on_dev)
+        stream = current_stream().handle
+        if train:
+            if mask is not None and not is_device(mask):
+                mask = DeviceArray.from_host(mask)
+            # the 13 BatchNorms' statistics (views of forward_train's buffer, or the caller's arrays) as one buffer in the layout's order
+            stats = self.forward_train(x, dropout=mask, intermediates=True)["batch_stats"] if fwd is None else fwd["batch_stats"]
+            if on_dev or fwd is None:
+                stats_dev = DeviceArray.empty((nstat,), f32)
+                for bn, C, at, _ in slots:
+                    for fld, o in ((".mu", at), (".sigma2", at + C)):
+                        _lib.call("fx3d_memcpy_d2d", stats_dev.ptr + 4 * o, stats[bn + fld].ptr, 4 * C, stream)
+            else:
+                stats_dev = DeviceArray.from_host(np.concatenate([np.asarray(stats[bn + fld], f32) for bn, *_ in slots
+                                                                  for fld in (".mu", ".sigma2")]))
+            extra = (mask.ptr if mask is not None else None, stats_dev.ptr)
         gp = DeviceArray.empty((self.param_count,), f32)
         gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
         mid = {k: DeviceArray.empty((r, N if c is None else c, B), f32) for k, (r, c) in self._MID.items()} if intermediates else None
-        ws = workspace(nb, tag="pointnet_grad")
-        _lib.call("fx3d_pointnet_grad", self._params_dev().ptr, nc, x.ptr, N, B, g.ptr, gp.ptr, gx.ptr if gx is not None else None,
-                  *(mid[k].ptr if mid else None for k in self._MID), ws.ptr, ws.nbytes, current_stream().handle)
+        ws = workspace(nb, tag="pointnet_grad_train" if train else "pointnet_grad")
+        _lib.call(entry, self._params_dev().ptr, nc, x.ptr, N, B, *extra, g.ptr, gp.ptr, gx.ptr if gx is not None else None,
+                  *(mid[k].ptr if mid else None for k in self._MID), ws.ptr, ws.nbytes, stream)
         return gp, gx, mid, on_dev
 
     def flat_grad(self, X, glogits, input_grad=True, intermediates=False):
@@ -439,12 +483,42 @@ class PointNet(_Model):
         transformed points.  Everything lives where ``X`` lives."""
         return self._grads(True, X, glogits, input_grad, intermediates)
 
+    def grad_train(self, X, glogits, dropout=None, fwd=None, input_grad=True, intermediates=False):
+        """:meth:`grad` for the TRAINING-mode network: the gradients of ``sum(glogits * logits)`` for the logits of
+        :meth:`forward_train` ``(X, dropout)``, with every BatchNorm's mean and variance functions of the batch and the dropout
+        multipliers constants: include/flux3d_hip.h "PointNet training-mode adjoint".  ``dropout`` as in :meth:`forward_train`.
+        ``fwd``: the dict of ``forward_train(X, dropout, intermediates=True)`` for the same ``X`` and ``dropout``, whose batch
+        statistics are then used; without it :meth:`forward_train` runs first.  Returns what :meth:`grad` returns (the ``mu`` /
+        ``sigma2`` entries are zero: the running statistics do not enter this forward).  At least two clouds."""
+        return self._grads(True, X, glogits, input_grad, intermediates, train=True, dropout=dropout, fwd=fwd)
+
+    def flat_grad_train(self, X, glogits, dropout=None, fwd=None, input_grad=True, intermediates=False):
+        """:meth:`grad_train` with the parameter gradients as one flat buffer, as :meth:`flat_grad`."""
+        return self._grads(False, X, glogits, input_grad, intermediates, train=True, dropout=dropout, fwd=fwd)
+
     def crossentropy_grad(self, X, labels):
         """``(loss, grads, gx)`` for ``Flux.crossentropy(m(X), onehot(labels))``, the mean over the batch: ``labels`` are B
         integers in [0, num_classes), 0-based.  One :meth:`forward` for ``probs``, which are read back to the host; ``loss =
         -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) / Float32(B)``
         with one Float32 subtraction and one Float32 division, then :meth:`grad`, inside which the forward runs again."""
         return self._crossentropy_grad(X, labels, with_fwd=False)
+
+    def crossentropy_grad_train(self, X, labels, dropout=None):
+        """:meth:`crossentropy_grad` on :meth:`forward_train`'s probabilities: ``(loss, grads, gx)`` of
+        ``Flux.crossentropy(m(X), onehot(labels))`` with the network in training mode under the multipliers ``dropout`` (as in
+        :meth:`forward_train`; an ``int`` seed is drawn once).  One :meth:`forward_train` with its intermediates, the loss and
+        ``glogits`` on the host as in :meth:`crossentropy_grad`, then :meth:`grad_train` with that forward's statistics."""
+        _, N, B, on_dev = self._clouds(X, self._WHY)
+        y = self._labels(labels, B)
+        if isinstance(dropout, (int, np.integer)):
+            dropout = self.dropout_mask(B, int(dropout))
+            if on_dev:
+                dropout = DeviceArray.from_host(dropout)
+        fwd = self.forward_train(X, dropout=dropout, intermediates=True)
+        probs = fwd["probs"]
+        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
+        grads, gx = self.grad_train(X, DeviceArray.from_host(glogits) if on_dev else glogits, dropout=dropout, fwd=fwd)
+        return loss, grads, gx
 
 
 class DGCNN(_Model):

@@ -1158,6 +1158,53 @@ FX3D_API fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_
                                                  float *stn, float *fstn, float *pooled, float *batch_stats, float *running,
                                                  void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- PointNet training-mode adjoint: the gradients of fx3d_pointnet_forward_train with respect to its parameters and to X --------
+ * gparams = d sum(glogits . logits) / d params for logits = fx3d_pointnet_forward_train(x, dropout), and, if gx != NULL, gx (3,N,B).
+ * mu and var of all 13 BatchNorms are functions of the batch (their slots of gparams are written as +0: the running statistics do not
+ * enter this forward), the dropout multipliers are constants.  params_dev .. B, dropout: the forward's.  batch_stats (required,
+ * fx3d_pointnet_stat_count floats): what fx3d_pointnet_forward_train returned for the same (params_dev, x, dropout); the statistics
+ * are not computed again.  glogits, gparams, gx, gstn, gfstn, gh, gxt: as in fx3d_pointnet_grad.  The call runs the forward's three
+ * rounds itself with the test-mode kernels at batch_stats, which is what the training-mode forward's closing passes are: the
+ * activations are the forward's bit for bit.
+ * Everything "PointNet adjoint" states and this section does not change holds verbatim: the relu's mask on its OUTPUT, the way back
+ * as one chain over ALL outputs ascending, the transforms' gT / gF and the sums of paths in their order, n*(c,b) the first point that
+ * EQUALS the pooled value, no "pooled > 0" condition, every operation rounded to Float32, sd = sqrtf(var + 1f-5).
+ *   BatchNorm, given v (m values per channel: N B after a convolution, B after a dense layer), xh = (v - mu) / sd, upstream gy:
+ *     dbeta64 = sum (double)gy,  dgamma64 = sum (double)gy (double)xh  (the product is exact), chains from +0.0, one rounding per
+ *     addition; dbeta = Float32(dbeta64), dgamma = Float32(dgamma64).  Orders:
+ *       a convolution's BatchNorm below a round's last one, and conv_block1.bn:  "PointNet training-mode forward"'s order of S1 / S2
+ *         verbatim (two chains per tile of 64, the tile sums in FX3D_POINTNET_STAT_GROUPS interleaved chains);
+ *       a dense layer's BatchNorm:  one chain over b ascending;
+ *       a round's last BatchNorm (gy is the head's gradient at the winner n*(c,b), +0 elsewhere):  one chain over b ascending over
+ *         the clouds that have a winner, xh the winner's.
+ *     The gradient at v:  mb = Float32(dbeta64 / m), mg = Float32(dgamma64 / m) (Float64 divisions);  t = gy - mb;  t = t - (xh mg),
+ *       a multiplication and a subtraction, nothing fused;  gv = (t gamma) / sd.  At a round's last BatchNorm gy = +0 at a point that
+ *       does not win the channel, so every point has a gv: the last convolution's input gradient is dense, not a gather.
+ *   relu below a BatchNorm (stn / fstn conv1..3, dense2, feat.conv1, dense1, dense2):  d = r > 0 ? gv : +0 with r the relu's own output.
+ *     feat.conv2 (BatchNorm only): d = gv.  conv_block1 (BatchNorm, then relu): gy = h > 0 ? gh : +0, v = conv + bias, d = gv; its
+ *     families are plain sums here: dW[c,o] the chain of fmaf(x_t[c], d[o], acc), db = sum d (nothing is formed after the sums).
+ *   Dropout (feat, between relu(dense2) and its BatchNorm):  the gradient below the multiplier is gv mask, one Float32 multiplication;
+ *     the relu below masks on its own output.  dropout = NULL: no multiplication.
+ *   The rounds' last convolutions (stn / fstn conv3, feat.conv2), sums over ALL points:  per cloud ONE chain over its points n
+ *     ascending -- dW[i,o]: fmaf(a_in[i,n], d[o,n], acc); db[o]: Float32 additions -- from +0, then one sum of Float32 additions from
+ *     +0 over b ascending (FX3D_POINTNET_GRAD_TRAIN_CLOUD_CHAINS: the cloud is the chain, not the 64-point tile).
+ *   Every other parameter sum (the convolutions below, conv_block1, gT, gF; the dense layers: one chain over b) keeps
+ *     "PointNet adjoint"'s Float32 tile orders.
+ * The orders depend on (N, B, num_classes) alone; no atomics; gparams, gx and the four optional outputs are bit-identical to the
+ * restatement tests/pointnet_grad_train_ref.py and from run to run.  An all-1.0f dropout gives the bits of dropout = NULL.
+ * Refusals, FX3D_ERR_INVALID_ARG, each before any device work: a NULL required pointer (params_dev, x, batch_stats, glogits, gparams,
+ * ws); fx3d_pointnet_forward's size limits; B < 2; a short workspace or one not 256-byte aligned.
+ * Launches on `s` only, no host synchronisation, no host memory read after the argument check (graph-capturable).
+ * ws: fx3d_pointnet_grad_train_workspace_bytes(N, B, num_classes) -- fx3d_pointnet_grad's forward part and head vectors; the Float64
+ * tile sums (2,128,ntiles,B); the last convolution's input and the gradient at it, (128,N,B) each; two (64,N,B) gradients, the feat
+ * path's gradient at h; dW and db of the last convolution per cloud, (128,1024,B) and (1024,B); one partial per tile and cloud. */
+#define FX3D_POINTNET_GRAD_TRAIN_CLOUD_CHAINS 1 /* chains per cloud of a last convolution's dW / db ("PointNet training-mode adjoint") */
+FX3D_API fx3d_status fx3d_pointnet_grad_train_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t num_classes, const float *x, int32_t N, int32_t B,
+                                              const float *dropout, const float *batch_stats, const float *glogits, float *gparams,
+                                              float *gx, float *gstn, float *gfstn, float *gh, float *gxt, void *ws, size_t ws_bytes,
+                                              fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
