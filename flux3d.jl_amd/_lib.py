@@ -129,11 +129,17 @@ SIGNATURES = {
     "fx3d_dgcnn_param_count": [c_i32, C.POINTER(c_i64)],
     "fx3d_dgcnn_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_dgcnn_forward": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "fx3d_dgcnn_stat_count": [C.POINTER(c_i64)],
+    "fx3d_dgcnn_train_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_dgcnn_forward_train": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, c_f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_dgcnn_grad_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_dgcnn_grad": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_edgeconv_param_count": [C.POINTER(c_i32), c_i32, C.POINTER(c_i64)],
     "fx3d_edgeconv_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_edgeconv_forward": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, sz, vp],
+    "fx3d_edgeconv_stat_count": [C.POINTER(c_i32), c_i32, C.POINTER(c_i64)],
+    "fx3d_edgeconv_train_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_edgeconv_forward_train": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, c_f32, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_edgeconv_bwd_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_edgeconv_bwd": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_edgeconv_grad_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],

@@ -63,26 +63,22 @@ __global__ __launch_bounds__(kHeadThreads) void dgcnn_head_kernel(const HeadArgs
     softmax_of_logits(z, pr, a.nc);
 }
 
-// the workspace: x1 (64, N, B) | x2 (256, N, B) | per-tile maxima (1024, ntiles, B) | logits (num_classes, B) | one EdgeConv
-// workspace, the larger of the two stages'
-struct WsPlan { size_t x1, x2, tmax, logits, ec, total; int ntiles; };
-fx3d_status ws_plan(int N, int B, int K, int nc, WsPlan *w) {
-    w->ntiles = (N + kTile - 1) / kTile;
-    WsBump ws;
-    w->x1 = ws.put((size_t)64 * N * B * sizeof(float));
-    w->x2 = ws.put((size_t)256 * N * B * sizeof(float));
-    w->tmax = ws.put((size_t)kFeat * w->ntiles * B * sizeof(float));
-    w->logits = ws.put((size_t)nc * B * sizeof(float));
-    size_t e1 = 0, e2 = 0;
-    fx3d_status rc;
-    if ((rc = edgeconv_workspace_bytes(kEc1[0], N, B, K, &e1)) != FX3D_OK) return rc;
-    if ((rc = edgeconv_workspace_bytes(kEc2[0], N, B, K, &e2)) != FX3D_OK) return rc;
-    w->ec = ws.put(e1 > e2 ? e1 : e2);
-    w->total = ws.at;
+}  // namespace
+
+namespace fx3d {
+namespace mlp {
+
+fx3d_status launch_conv3(const float *x2, const Conv &c3, float *tmax, int N, int ntiles, int B, hipStream_t st, const char *label) {
+    const fx3d_status r = ensure_dynamic_lds(reinterpret_cast<const void *>(&dgcnn_conv3_kernel), (int)kConv3Lds, "dgcnn_conv3_kernel");
+    if (r != FX3D_OK) return r;
+    ProfileScope prof(label, st);
+    hipLaunchKernelGGL(dgcnn_conv3_kernel, dim3(ntiles, B), dim3(kPtThreads), kConv3Lds, st, x2, c3, tmax, N, ntiles);
+    FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
 
-}  // namespace
+}  // namespace mlp
+}  // namespace fx3d
 
 extern "C" {
 
@@ -97,8 +93,8 @@ fx3d_status fx3d_dgcnn_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t 
     FX3D_REQUIRE(bytes != nullptr, "fx3d_dgcnn_workspace_bytes: bytes is NULL");
     fx3d_status rc = dgcnn_check_sizes("fx3d_dgcnn_workspace_bytes", N, B, K, num_classes);
     if (rc != FX3D_OK) return rc;
-    WsPlan w;
-    if ((rc = ws_plan(N, B, K, num_classes, &w)) != FX3D_OK) return rc;
+    DgcnnWsPlan w;
+    if ((rc = dgcnn_ws_plan(N, B, K, num_classes, &w)) != FX3D_OK) return rc;
     *bytes = w.total;
     return FX3D_OK;
 }
@@ -110,8 +106,8 @@ fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_classes, int
     FX3D_REQUIRE(params_dev && x && probs && ws, "%s: params_dev, x, probs and ws must not be NULL", fn);
     fx3d_status r = dgcnn_check_sizes(fn, N, B, K, num_classes);
     if (r != FX3D_OK) return r;
-    WsPlan w;
-    if ((r = ws_plan(N, B, K, num_classes, &w)) != FX3D_OK) return r;
+    DgcnnWsPlan w;
+    if ((r = dgcnn_ws_plan(N, B, K, num_classes, &w)) != FX3D_OK) return r;
     FX3D_REQUIRE(ws_bytes >= w.total, "%s: workspace of %zu bytes, fx3d_dgcnn_workspace_bytes says %zu", fn, ws_bytes, w.total);
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
     FX3D_REQUIRE(!x1 || (reinterpret_cast<uintptr_t>(x1) & 15) == 0, "%s: x1 must be 16-byte aligned", fn);
@@ -126,12 +122,7 @@ fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_classes, int
     if ((r = edgeconv_run(n.ec1, kEc1, 4, K, x, N, B, nullptr, f1, idx1, wsb + w.ec, s, "dgcnn_edgeconv1")) != FX3D_OK) return r;
     if ((r = edgeconv_run(n.ec2, kEc2, 3, K, f1, N, B, nullptr, f2, idx2, wsb + w.ec, s, "dgcnn_edgeconv2")) != FX3D_OK) return r;
     // conv_3 + the maximum over the points, per tile
-    if ((r = ensure_dynamic_lds(reinterpret_cast<const void *>(&dgcnn_conv3_kernel), (int)kConv3Lds, "dgcnn_conv3_kernel")) != FX3D_OK) return r;
-    {
-        ProfileScope prof("dgcnn_conv3", st);
-        hipLaunchKernelGGL(dgcnn_conv3_kernel, dim3(w.ntiles, B), dim3(kPtThreads), kConv3Lds, st, f2, n.c3, tmax, N, w.ntiles);
-        FX3D_LAUNCH_CHECK();
-    }
+    if ((r = launch_conv3(f2, n.c3, tmax, N, w.ntiles, B, st, "dgcnn_conv3")) != FX3D_OK) return r;
     HeadArgs hd{};
     hd.tmax = tmax; hd.ntiles = w.ntiles;
     hd.d4 = n.d4; hd.bn4 = n.bn4; hd.d5 = n.d5; hd.bn5 = n.bn5; hd.d6 = n.d6;

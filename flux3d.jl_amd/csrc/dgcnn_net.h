@@ -1,5 +1,6 @@
-// What dgcnn.hip (the forward) and dgcnn_grad.hip (its adjoint) share: the layers of the two EdgeConv stages, conv_3's LDS image
-// of a 64-point tile of x2, the walk over the flat parameter buffer and the size check of both entries.
+// What dgcnn.hip (the forward), dgcnn_train.hip (the training-mode forward) and dgcnn_grad.hip (the adjoint) share: the layers of
+// the two EdgeConv stages, conv_3's LDS image of a 64-point tile of x2, the walk over the flat parameter buffer, the size check
+// of the entries, and the forward's workspace and conv_3 launch.
 #pragma once
 #include "mlp_common.h"
 
@@ -43,6 +44,29 @@ inline fx3d_status dgcnn_check_sizes(const char *fn, int32_t N, int32_t B, int32
     FX3D_REQUIRE(nc >= 1 && nc <= (1 << 20), "%s: num_classes must be in [1, 2^20], got %d", fn, nc);
     return check_edgeconv_sizes(fn, N, B, K);
 }
+
+// the forward's workspace: x1 (64, N, B) | x2 (256, N, B) | per-tile maxima (1024, ntiles, B) | logits (num_classes, B) | one
+// EdgeConv workspace, the larger of the two stages'
+struct DgcnnWsPlan { size_t x1, x2, tmax, logits, ec, total; int ntiles; };
+inline fx3d_status dgcnn_ws_plan(int N, int B, int K, int nc, DgcnnWsPlan *w) {
+    w->ntiles = (N + kTile - 1) / kTile;
+    WsBump ws;
+    w->x1 = ws.put((size_t)64 * N * B * sizeof(float));
+    w->x2 = ws.put((size_t)256 * N * B * sizeof(float));
+    w->tmax = ws.put((size_t)kFeat * w->ntiles * B * sizeof(float));
+    w->logits = ws.put((size_t)nc * B * sizeof(float));
+    size_t e1 = 0, e2 = 0;
+    fx3d_status rc;
+    if ((rc = edgeconv_workspace_bytes(kEc1[0], N, B, K, &e1)) != FX3D_OK) return rc;
+    if ((rc = edgeconv_workspace_bytes(kEc2[0], N, B, K, &e2)) != FX3D_OK) return rc;
+    w->ec = ws.put(e1 > e2 ? e1 : e2);
+    w->total = ws.at;
+    return FX3D_OK;
+}
+
+// dgcnn.hip: dgcnn_conv3_kernel on st -- conv_3 + BatchNorm + relu of x2 (256, N, B) reduced to the per-tile maxima tmax
+// (1024, ntiles, B); label: the launch's name in the library's profile
+fx3d_status launch_conv3(const float *x2, const Conv &c3, float *tmax, int N, int ntiles, int B, hipStream_t st, const char *label);
 
 }  // namespace mlp
 }  // namespace fx3d

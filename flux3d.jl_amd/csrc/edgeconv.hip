@@ -21,60 +21,15 @@
 //   An output width that is no multiple of 32 leaves the last slab partial: its lanes beyond the width read the parameters of
 //     the last channel (inside the buffer), run the wave's MFMAs with them and write nothing.
 //   Rows beyond the cloud's last point are zeros: computed, never written.  After the last k, plain stores (fold_store).
-#include "mlp_common.h"
+// The kernel's arguments, a hidden layer (conv_rt), the loop over k with its last layer left to the caller (edge_trunk), the LDS
+// plan and the workspace are in edgeconv_net.h, which the training-mode forward (edgeconv_train.hip) shares: its statistics
+// passes are that loop stopped at a BatchNorm.
+#include "edgeconv_net.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
 
 namespace {
-
-struct EdgeConvArgs {
-    const float *x;      // (F, N, B)
-    const int32_t *idx;  // (K, N, B), 0-based
-    float *out;          // (cL, N, B)
-    Conv c[kMaxLayers];
-    int w[kMaxLayers + 1];  // F, c1, ..., cL
-    int nl, cout;           // L, cL
-    int N, K;
-    int img0, img1;         // offsets of the two hidden images from `rows` (floats)
-    int shared_rows;        // img1 is `rows`: the x_n half is gathered with every k
-};
-
-// Who computes what of a layer of `cout` channels.  Beyond 64 channels a wave owns the slabs wave, wave + 4, ... of 32 channels
-// for both 32-point halves of the tile (one weight load feeds four MFMAs).  Up to 64 channels there are two slabs at most, and
-// two of the four waves would idle: there a wave owns ONE half of one slab -- slab wave / 2, half wave % 2.
-__device__ __forceinline__ bool split_halves(int cout) { return cout <= 64; }
-
-// one slab (NH = 2) or one half of it (NH = 1, half `half`) of a hidden layer:
-// out[p][o] = relu(BN(sum_c in[p][c] W[c + cin o] + b[o])) for o < cout
-template <int LD, int NH>
-__device__ __forceinline__ void conv_item(const float *in, float *out, int cin, int cout, const Conv &c, int sl, int half) {
-    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
-    const int o = sl * 32 + j, oc = min(o, cout - 1);  // oc: what a lane beyond a partial slab reads
-    f32x16 acc[NH];
-#pragma unroll
-    for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
-    mfma_slab_rt<LD, NH>(in + half * 32 * LD, c.W + (size_t)cin * oc, cin, h, j, acc);
-    const float bi = c.b[oc], g = c.bn.g[oc], be = c.bn.b[oc], mu = c.bn.m[oc], sd = sqrtf(c.bn.v[oc] + kBnEps);
-    if (o < cout) {
-        float *ob = out + (half * 32) * LD + o;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int t = 0; t < NH; ++t) ob[(t * 32 + mfma_row(r, h)) * LD] = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd);
-    }
-}
-
-// one hidden layer, from image to image, for the tile's 64 points
-template <int LD>
-__device__ __forceinline__ void conv_rt(const float *in, float *out, int cin, int cout, const Conv &c) {
-    const int wave = threadIdx.x >> 6;
-    if (split_halves(cout)) {
-        if ((wave >> 1) * 32 < cout) conv_item<LD, 1>(in, out, cin, cout, c, wave >> 1, wave & 1);
-    } else {
-        for (int sl = wave; sl * 32 < cout; sl += kPtThreads / 64) conv_item<LD, 2>(in, out, cin, cout, c, sl, 0);
-    }
-}
 
 // the last layer for the current k, folded into the wave's running maxima (split_halves: into rm0[0] alone)
 template <int NS, int LD>
@@ -115,73 +70,21 @@ __device__ __forceinline__ void fold_store_half(float *ob, int cout, int nvalid,
 template <int NS, int LD>
 __global__ __launch_bounds__(kPtThreads) void edgeconv_kernel(const EdgeConvArgs a) {
     extern __shared__ float lds[];
-    float *rows = lds, *img0 = lds + a.img0, *img1 = lds + a.img1;
     const int tile = blockIdx.x, b = blockIdx.y;
     const int p0 = tile * kTile;
     const int nvalid = min(kTile, a.N - p0);
-    const int F = a.w[0], L = a.nl, cout = a.cout;
-    const float *xb = a.x + (size_t)b * a.N * F;
-    const int32_t *ib = a.idx + ((size_t)b * a.N + p0) * a.K;
+    const int cout = a.cout;
     f32x16 rm0[NS], rm1[NS];
     fold_init<NS>(rm0, rm1);
-    if (!a.shared_rows) gather_centre(rows, LD, xb, F, p0, nvalid);
-    __syncthreads();
-    for (int k = 0; k < a.K; ++k) {
-        if (a.shared_rows) gather_centre(rows, LD, xb, F, p0, nvalid);  // (gather_diff reads what the same thread wrote)
-        gather_diff(rows, LD, xb, ib, F, a.N, a.K, k, p0, nvalid);
-        __syncthreads();
-        // the layers: one copy of the code, its layer picked by wave-uniform selects among the kernel arguments (a constant
-        // index in every access, so that a.c[] and a.w[] stay in scalar registers)
-        const float *src = rows;
-        float *dst = img0;
-        int cin = 2 * F;
-        for (int i = 0; i + 1 < L; ++i) {
-            const Conv c = i == 0 ? a.c[0] : i == 1 ? a.c[1] : a.c[2];
-            const int co = i == 0 ? a.w[1] : i == 1 ? a.w[2] : a.w[3];
-            conv_rt<LD>(src, dst, cin, co, c);
-            __syncthreads();
-            src = dst;
-            dst = i == 0 ? img1 : img0;
-            cin = co;
-        }
-        conv_rt_fold<NS, LD>(src, cin, cout, L == 1 ? a.c[0] : L == 2 ? a.c[1] : L == 3 ? a.c[2] : a.c[3], rm0, rm1);
-        // The next k's writes.  `rows` was last read by the first layer, before a barrier above -- unless the fold itself read it
-        // (L = 1) or img1, which the fold of L = 3 read, is `rows`: then the waves meet here first.  img0 / img1 are written
-        // again only after the barrier that follows the next gather, which a wave reaches after its fold.
-        if (L == 1 || (L == 3 && a.shared_rows)) __syncthreads();
-    }
+    // the loop over k (edge_trunk, edgeconv_net.h), its last layer folded into the running maxima
+    edge_trunk<LD>(a, lds, b, p0, nvalid,
+                   [&](const float *src, int cin, int co, const Conv &c) { conv_rt_fold<NS, LD>(src, cin, co, c, rm0, rm1); });
     float *ob = a.out + ((size_t)b * a.N + p0) * cout;
     if (NS == 1 && split_halves(cout)) fold_store_half(ob, cout, nvalid, rm0[0]);
     else fold_store<NS>(ob, cout, nvalid, rm0, rm1);
 }
 
-// ---- the host side -------------------------------------------------------------------------------------------------
-// the LDS images: one stride for all, from the widest layer input
-void lds_plan(const int32_t *layers, int nlayers, EdgeConvArgs *a, int *ld, size_t *bytes) {
-    int widest = 2 * layers[0];
-    for (int i = 1; i + 1 < nlayers; ++i) widest = layers[i] > widest ? layers[i] : widest;
-    *ld = edge_stride(widest);
-    const int L = nlayers - 1, image = kTile * *ld;
-    int nimg = L >= 3 ? 3 : L;
-    a->shared_rows = (size_t)nimg * image * sizeof(float) > kMaxLds;
-    if (a->shared_rows) nimg = 2;
-    a->img0 = L >= 2 ? image : 0;
-    a->img1 = L >= 3 && !a->shared_rows ? 2 * image : 0;
-    *bytes = (size_t)nimg * image * sizeof(float);
-}
-
-// the workspace: the neighbour lists (K, N, B) | the neighbour search's scratch
-struct WsPlan { size_t idx, knn, knn_bytes, total; };
-fx3d_status ws_plan(int F, int N, int B, int K, WsPlan *w) {
-    WsBump ws;
-    w->idx = ws.put((size_t)K * N * B * sizeof(int32_t));
-    const fx3d_status rc = fx3d_knn_workspace_bytes(N, N, B, F, K, 1, &w->knn_bytes);
-    if (rc != FX3D_OK) return rc;
-    w->knn = ws.put(w->knn_bytes);
-    w->total = ws.at;
-    return FX3D_OK;
-}
-
+// ---- the host side (the LDS plan, the workspace and a pass's arguments: edgeconv_net.h) ------------------------------------------
 template <int NS, int LD>
 fx3d_status launch(const EdgeConvArgs &a, size_t lds_bytes, int B, hipStream_t st, const char *label) {
     const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&edgeconv_kernel<NS, LD>), (int)kMaxLds, "edgeconv_kernel");
@@ -210,41 +113,42 @@ long long edgeconv_layout(const float *params, const int32_t *layers, int nlayer
 }
 
 fx3d_status edgeconv_workspace_bytes(int F, int N, int B, int K, size_t *bytes) {
-    WsPlan w;
-    const fx3d_status rc = ws_plan(F, N, B, K, &w);
+    EdgeWsPlan w;
+    const fx3d_status rc = edge_ws_plan(F, N, B, K, &w);
     if (rc != FX3D_OK) return rc;
     *bytes = w.total;
     return FX3D_OK;
 }
 
+fx3d_status edgeconv_neighbours(const float *x, int F, int N, int B, int K, const int32_t *idx_in, int32_t *idx_out, void *ws,
+                                fx3d_stream_t s, const int32_t **idx) {
+    *idx = idx_in;
+    if (idx_in) return FX3D_OK;
+    EdgeWsPlan w;
+    const fx3d_status r = edge_ws_plan(F, N, B, K, &w);
+    if (r != FX3D_OK) return r;
+    char *wsb = static_cast<char *>(ws);
+    int32_t *found = idx_out ? idx_out : reinterpret_cast<int32_t *>(wsb + w.idx);
+    *idx = found;
+    return fx3d_knn_ws(x, N, x, N, B, F, K, 1, found, nullptr, w.knn_bytes ? wsb + w.knn : nullptr, w.knn_bytes, s);
+}
+
+fx3d_status edgeconv_launch(const EdgePass &p, int B, hipStream_t st, const char *label) {
+    const EdgeConvArgs &a = p.a;
+    const bool wide = a.cout > 128;  // two slabs of running maxima per wave
+    switch (p.ld) {
+        case 66: return wide ? launch<2, 66>(a, p.lds_bytes, B, st, label) : launch<1, 66>(a, p.lds_bytes, B, st, label);
+        case kLd: return wide ? launch<2, kLd>(a, p.lds_bytes, B, st, label) : launch<1, kLd>(a, p.lds_bytes, B, st, label);
+        default: return wide ? launch<2, 258>(a, p.lds_bytes, B, st, label) : launch<1, 258>(a, p.lds_bytes, B, st, label);
+    }
+}
+
 fx3d_status edgeconv_run(const float *params_dev, const int32_t *layers, int nlayers, int K, const float *x, int N, int B,
                          const int32_t *idx_in, float *out, int32_t *idx_out, void *ws, fx3d_stream_t s, const char *label) {
-    EdgeConvArgs a{};
-    edgeconv_layout(params_dev, layers, nlayers, a.c);
-    for (int i = 0; i < nlayers; ++i) a.w[i] = layers[i];
-    a.nl = nlayers - 1; a.cout = layers[nlayers - 1];
-    a.N = N; a.K = K; a.x = x; a.out = out;
-    size_t lds_bytes = 0;
-    int ld = 0;
-    lds_plan(layers, nlayers, &a, &ld, &lds_bytes);
-    if (idx_in) {
-        a.idx = idx_in;
-    } else {
-        WsPlan w;
-        fx3d_status r = ws_plan(layers[0], N, B, K, &w);
-        if (r != FX3D_OK) return r;
-        char *wsb = static_cast<char *>(ws);
-        int32_t *idx = idx_out ? idx_out : reinterpret_cast<int32_t *>(wsb + w.idx);
-        if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, idx, nullptr, w.knn_bytes ? wsb + w.knn : nullptr, w.knn_bytes, s)) != FX3D_OK) return r;
-        a.idx = idx;
-    }
-    hipStream_t st = as_stream(s);
-    const bool wide = a.cout > 128;  // two slabs of running maxima per wave
-    switch (ld) {
-        case 66: return wide ? launch<2, 66>(a, lds_bytes, B, st, label) : launch<1, 66>(a, lds_bytes, B, st, label);
-        case kLd: return wide ? launch<2, kLd>(a, lds_bytes, B, st, label) : launch<1, kLd>(a, lds_bytes, B, st, label);
-        default: return wide ? launch<2, 258>(a, lds_bytes, B, st, label) : launch<1, 258>(a, lds_bytes, B, st, label);
-    }
+    const int32_t *idx = nullptr;
+    const fx3d_status r = edgeconv_neighbours(x, layers[0], N, B, K, idx_in, idx_out, ws, s, &idx);
+    if (r != FX3D_OK) return r;
+    return edgeconv_launch(edge_pass(params_dev, nullptr, layers, nlayers, K, x, N, idx, out), B, as_stream(s), label);
 }
 
 }  // namespace mlp

@@ -4,6 +4,7 @@
 // the edge rows and fold of the last layer, the two ends of a classifier head, and on the host the walk over the flat
 // parameter buffer, the workspace allocator, the size limits of the neighbour search, the EdgeConv envelope, LDS budget and row stride, and the EdgeConv entry DGCNN and the adjoints run on.
 // What only the adjoints share is in edgeconv_adjoint.h.
+// What the EdgeConv forward and its training-mode forward share -- the kernel's arguments and its loop over k -- is in edgeconv_net.h.
 // include/flux3d_hip.h ("PointNet inference") states the arithmetic; pointnet.hip's header comment the tile and its LDS banks.
 #pragma once
 #include <cmath>

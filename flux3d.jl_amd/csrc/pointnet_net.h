@@ -1,6 +1,7 @@
 // What pointnet.hip (the forward), pointnet_train.hip (the training-mode forward), pointnet_grad.hip (the adjoint) and
 // pointnet_grad_train.hip (the training-mode adjoint) share.  At the end, what only some of them share: the fold of a BatchNorm's
-// Float64 tile sums (the two training-mode units), and the adjoints' MFMA chains over a tile (hsum_mfma, back_mfma, hsum3) with the
+// Float64 tile sums (the two training-mode units) and a BatchNorm's batch statistics (pointnet_train.hip, and with it the
+// training-mode forwards of DGCNN and EdgeConv), and the adjoints' MFMA chains over a tile (hsum_mfma, back_mfma, hsum3) with the
 // launches of pointnet_grad.hip's finishing kernels.
 // On the host: the walk over the flat parameter buffer, the forward's workspace, the size check of the entries, the
 // arguments of the forward's two kernels per round (set_round, stn_head, feat_head) and their launches (defined in
@@ -187,12 +188,12 @@ __device__ __forceinline__ void load_tile64(float *img, const float *src, int b,
 }
 
 // ---- conv_mfma's walk over the slabs of 32 output channels, with the epilogue left to the caller -----------------------------
-// body(o, h, acc0, acc1) while the slab of `in` (row stride kLd) times W (CIN, cout) is in the accumulators: o is the lane's
+// body(o, h, acc0, acc1) while the slab of `in` (row stride LD) times W (CIN, cout) is in the accumulators: o is the lane's
 // channel, acc0 / acc1 its 16 points mfma_row(r, h) of the tile's two 32-point halves.  All 4 waves call it.
-template <int CIN, class Body>
+template <int CIN, int LD = kLd, class Body>
 __device__ __forceinline__ void for_each_slab(const float *in, const float *__restrict__ W, int cout, Body body) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    const float *a0 = in + j * kLd + h, *a1 = a0 + 32 * kLd;
+    const float *a0 = in + j * LD + h, *a1 = a0 + 32 * LD;
     for (int sl = wave; sl < cout / 32; sl += kPtThreads / 64) {
         const int o = sl * 32 + j;
         f32x16 acc0 = {0}, acc1 = {0};
@@ -336,28 +337,31 @@ __device__ __forceinline__ void head_finish(const HeadArgs &a, int b, const floa
     if (FEAT) softmax_of_logits(a.logits + (size_t)b * a.n3, a.probs + (size_t)b * a.n3, a.n3);
 }
 
-// ---- the fold of a convolution BatchNorm's Float64 tile sums (pointnet_train.hip's statistics, pointnet_grad_train.hip's dbeta / dgamma)
+// ---- the fold of a convolution BatchNorm's Float64 tile sums (pointnet_train.hip's and the DGCNN / EdgeConv training-mode
+// forward's statistics, pointnet_grad_train.hip's dbeta / dgamma)
 constexpr int kFinishGroups = FX3D_POINTNET_STAT_GROUPS;  // interleaved partial sums over (tile, cloud), the header's order
 constexpr int kFinishChannels = 16;                       // channels of one finishing block: 256 contiguous bytes per read
 constexpr int kFinishThreads = kFinishGroups * kFinishChannels;
 // Folds sums (2, C, T) over the T = ntiles B tile sums t = tile + ntiles b of a layer: kFinishGroups chains, chain g over
 // t = g, g + kFinishGroups, ... ascending from +0.0, then the chains in ascending g from +0.0; finish(c, s1, s2) in the thread
-// that owns channel c.  One block of kFinishThreads = 16 channels (C is a multiple of 16).
+// that owns channel c.  One block of kFinishThreads = 16 channels; the threads of the last block beyond channel C - 1 (an
+// EdgeConv width that is no multiple of 16) read nothing and finish nothing.
 template <class Finish>
 __device__ __forceinline__ void fold_tile_sums(const double *__restrict__ sums, int C, long long T, Finish finish) {
     __shared__ double p1[kFinishGroups][kFinishChannels], p2[kFinishGroups][kFinishChannels];
     const int cl = threadIdx.x % kFinishChannels, g = threadIdx.x / kFinishChannels;
     const int c = blockIdx.x * kFinishChannels + cl;
     double s1 = 0.0, s2 = 0.0;
-    for (long long t = g; t < T; t += kFinishGroups) {
-        const double *at = sums + 2 * ((size_t)t * C + c);
-        s1 = s1 + at[0];
-        s2 = s2 + at[1];
-    }
+    if (c < C)
+        for (long long t = g; t < T; t += kFinishGroups) {
+            const double *at = sums + 2 * ((size_t)t * C + c);
+            s1 = s1 + at[0];
+            s2 = s2 + at[1];
+        }
     p1[g][cl] = s1;
     p2[g][cl] = s2;
     __syncthreads();
-    if (g != 0) return;
+    if (g != 0 || c >= C) return;
     s1 = 0.0; s2 = 0.0;
     for (int k = 0; k < kFinishGroups; ++k) {
         s1 = s1 + p1[k][cl];
@@ -365,6 +369,74 @@ __device__ __forceinline__ void fold_tile_sums(const double *__restrict__ sums, 
     }
     finish(c, s1, s2);
 }
+
+// ---- a BatchNorm's batch statistics (pointnet_train.hip; dgcnn_train.hip and edgeconv_train.hip for DGCNN and EdgeConv) ---------
+// one BatchNorm's statistics: where they go, and the running values they update
+struct StatOut {
+    const float *run_m, *run_v;  // the running mean and variance in the parameter buffer
+    float *mu, *var;             // the batch statistics buffer
+    float *new_m, *new_v;        // the updated running statistics, or NULL
+    float mtm;
+    long long m;                 // values per channel: N B after a convolution (K N B in an EdgeConv), B after a dense layer
+};
+
+// the header's "mean and variance" and "running statistics", for channel c with the sums S1, S2 over its m values
+__device__ __forceinline__ void finish_channel(const StatOut &o, int c, double S1, double S2) {
+    const double dm = (double)o.m;
+    const double mu64 = S1 / dm;
+    double v64 = S2 / dm - mu64 * mu64;
+    v64 = v64 < 0.0 ? 0.0 : v64;  // (a NaN stays)
+    const float mu = (float)mu64, var = (float)v64;
+    o.mu[c] = mu;
+    o.var[c] = var;
+    if (o.new_m) {
+        const float keep = 1.0f - o.mtm;
+        o.new_m[c] = (keep * o.run_m[c]) + (o.mtm * mu);
+        o.new_v[c] = (keep * o.run_v[c]) + (((o.mtm * (float)o.m) / (float)(o.m - 1)) * var);
+    }
+}
+
+// a tile's sums of one channel: the rows p of the tile with bit 2 of p equal to h are one chain in ascending p (what a lane
+// of half-wave h holds of a slab, mfma_row), and the tile's sum is chain(0) + chain(1).  (An EdgeConv's chains are per 32-point
+// half and run over the neighbour rank as well: edgeconv_train.hip.)
+struct TileSum {
+    double s1 = 0.0, s2 = 0.0;
+    __device__ __forceinline__ void add(float v) {
+        const double d = (double)v;
+        s1 = s1 + d;
+        s2 = s2 + d * d;  // the product of two Float32 is exact in Float64
+    }
+};
+__device__ __forceinline__ void store_tile_sum(double *sums, int o, double s1, double s2) {
+    sums[2 * o] = s1;
+    sums[2 * o + 1] = s2;
+}
+
+// a convolution on the MFMA whose BatchNorm's statistics are wanted: conv_mfma's slabs (for_each_slab) with the statistics
+// epilogue.  sums: the tile's (2, cout).
+template <int CIN, int EPI, int LD = kLd>
+__device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const float *__restrict__ W, const float *__restrict__ bias,
+                                               int nvalid, double *__restrict__ sums) {
+    for_each_slab<CIN, LD>(in, W, cout, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
+        const float bi = bias[o];
+        TileSum t;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (mfma_row(r, h) < nvalid) t.add(before_bn<EPI>(acc0[r], bi));
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (mfma_row(r, h) + 32 < nvalid) t.add(before_bn<EPI>(acc1[r], bi));
+        const double o1 = __shfl_xor(t.s1, 32, 64), o2 = __shfl_xor(t.s2, 32, 64);
+        if (h == 0) store_tile_sum(sums, o, t.s1 + o1, t.s2 + o2);
+    });
+}
+
+// pointnet_train.hip's two finishing kernels on st.  launch_stat_finish: the fold of a layer's tile sums (2, C, T), T = ntiles B,
+// then mean, variance and running statistics of its C channels.  launch_dense_stats: a dense BatchNorm, thread c sums channel c
+// of act (C, B), C a multiple of 256, over the clouds in ascending b from +0.0 and finishes it.  label: the launch's name in the
+// library's profile.
+fx3d_status launch_stat_finish(const double *sums, int C, long long T, const StatOut &o, hipStream_t st, const char *label);
+fx3d_status launch_dense_stats(const float *act, int C, int B, const StatOut &o, hipStream_t st, const char *label);
 
 // ---- what the two adjoints (pointnet_grad.hip, pointnet_grad_train.hip) share ------------------------------------------------------
 // the gradient's block of a conv layer with its BatchNorm: W | b | gamma | beta | mu | var

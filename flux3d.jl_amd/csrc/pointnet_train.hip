@@ -16,6 +16,9 @@
 // feat only head_b (BatchNorm, dense2, relu, the dropout multiplier), head_c (BatchNorm, dense3 / cls, relu + softmax), with
 // pointnet_dense_stats_kernel in between: one thread per channel sums the (C, B) activations in ascending b.
 // No atomics anywhere: every sum has one owner and one order, which depends on (N, B) alone.
+// What a statistic is made of -- the Float64 tile sums and their epilogue on the MFMA (TileSum, conv_stat_mfma), the fold, mean,
+// variance and running update (fold_tile_sums, finish_channel) -- is in pointnet_net.h; the two finishing kernels below are launched
+// through it (launch_stat_finish, launch_dense_stats) by the training-mode forwards of DGCNN and EdgeConv as well.
 #include <initializer_list>
 
 #include "pointnet_net.h"
@@ -27,64 +30,6 @@ using namespace fx3d::mlp::pointnet;
 namespace {
 
 constexpr int kDenseStatThreads = 256;
-
-// one BatchNorm's statistics: where they go, and the running values they update
-struct StatOut {
-    const float *run_m, *run_v;  // the running mean and variance in the parameter buffer
-    float *mu, *var;             // the batch statistics buffer
-    float *new_m, *new_v;        // the updated running statistics, or NULL
-    float mtm;
-    long long m;                 // values per channel: N B after a convolution, B after a dense layer
-};
-
-// the header's "mean and variance" and "running statistics", for channel c with the sums S1, S2 over its m values
-__device__ __forceinline__ void finish_channel(const StatOut &o, int c, double S1, double S2) {
-    const double dm = (double)o.m;
-    const double mu64 = S1 / dm;
-    double v64 = S2 / dm - mu64 * mu64;
-    v64 = v64 < 0.0 ? 0.0 : v64;  // (a NaN stays)
-    const float mu = (float)mu64, var = (float)v64;
-    o.mu[c] = mu;
-    o.var[c] = var;
-    if (o.new_m) {
-        const float keep = 1.0f - o.mtm;
-        o.new_m[c] = (keep * o.run_m[c]) + (o.mtm * mu);
-        o.new_v[c] = (keep * o.run_v[c]) + (((o.mtm * (float)o.m) / (float)(o.m - 1)) * var);
-    }
-}
-
-// a tile's sums of one channel: the rows p of the tile with bit 2 of p equal to h are one chain in ascending p (what a lane
-// of half-wave h holds of a slab, mfma_row), and the tile's sum is chain(0) + chain(1)
-struct TileSum {
-    double s1 = 0.0, s2 = 0.0;
-    __device__ __forceinline__ void add(float v) {
-        const double d = (double)v;
-        s1 = s1 + d;
-        s2 = s2 + d * d;  // the product of two Float32 is exact in Float64
-    }
-};
-__device__ __forceinline__ void store_tile_sum(double *sums, int o, double s1, double s2) {
-    sums[2 * o] = s1;
-    sums[2 * o + 1] = s2;
-}
-
-// layer L = a convolution on the MFMA: conv_mfma's slabs (for_each_slab) with the statistics epilogue.  sums: the tile's (2, cout).
-template <int CIN, int EPI>
-__device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const float *__restrict__ W, const float *__restrict__ bias,
-                                               int nvalid, double *__restrict__ sums) {
-    for_each_slab<CIN>(in, W, cout, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
-        const float bi = bias[o];
-        TileSum t;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (mfma_row(r, h) < nvalid) t.add(before_bn<EPI>(acc0[r], bi));
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (mfma_row(r, h) + 32 < nvalid) t.add(before_bn<EPI>(acc1[r], bi));
-        const double o1 = __shfl_xor(t.s1, 32, 64), o2 = __shfl_xor(t.s2, 32, 64);
-        if (h == 0) store_tile_sum(sums, o, t.s1 + o1, t.s2 + o2);
-    });
-}
 
 // layer L = a convolution of 3 input channels (conv3's chain) to 64: waves 0 and 1 are the two chains of a channel
 template <int EPI>
@@ -223,20 +168,6 @@ fx3d_status launch_stats(int mode, int L, const StatArgs &s, int B, hipStream_t 
     }
 }
 
-fx3d_status launch_finish(const double *sums, int C, long long T, const StatOut &o, hipStream_t st) {
-    ProfileScope prof("pointnet_train_finish", st);
-    hipLaunchKernelGGL(pointnet_stat_finish_kernel, dim3(C / kFinishChannels), dim3(kFinishThreads), 0, st, sums, C, T, o);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
-fx3d_status launch_dense_stats(const float *act, int C, int B, const StatOut &o, hipStream_t st) {
-    ProfileScope prof("pointnet_train_dense_stats", st);
-    hipLaunchKernelGGL(pointnet_dense_stats_kernel, dim3(C / kDenseStatThreads), dim3(kDenseStatThreads), 0, st, act, C, B, o);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
 // part 0 = head_a, 1 = head_b (feat), 2 = head_c
 fx3d_status launch_train_head(int part, bool feat, const TrainHeadArgs &t, int B, hipStream_t st) {
     ProfileScope prof("pointnet_train_head", st);
@@ -276,6 +207,30 @@ fx3d_status check_train_sizes(const char *fn, int32_t N, int32_t B, int32_t nc) 
 }
 
 }  // namespace
+
+// ---- the finishing kernels the training-mode forwards share (pointnet_net.h) ----------------------------------------------------
+namespace fx3d {
+namespace mlp {
+namespace pointnet {
+
+fx3d_status launch_stat_finish(const double *sums, int C, long long T, const StatOut &o, hipStream_t st, const char *label) {
+    ProfileScope prof(label, st);
+    hipLaunchKernelGGL(pointnet_stat_finish_kernel, dim3((C + kFinishChannels - 1) / kFinishChannels), dim3(kFinishThreads), 0, st,
+                       sums, C, T, o);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+fx3d_status launch_dense_stats(const float *act, int C, int B, const StatOut &o, hipStream_t st, const char *label) {
+    ProfileScope prof(label, st);
+    hipLaunchKernelGGL(pointnet_dense_stats_kernel, dim3(C / kDenseStatThreads), dim3(kDenseStatThreads), 0, st, act, C, B, o);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
+}  // namespace pointnet
+}  // namespace mlp
+}  // namespace fx3d
 
 extern "C" {
 
@@ -349,7 +304,7 @@ fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_cla
         // the round's point BatchNorms in order, then the round's closing full pass (which keeps conv_block1 as h)
         for (int L = 0; L <= kLastLayer[mode]; ++L, ++slot) {
             if ((r = launch_stats(mode, L, sa, B, st)) != FX3D_OK) return r;
-            if ((r = launch_finish(sa.sums, width[slot], ntl, so[slot], st)) != FX3D_OK) return r;
+            if ((r = launch_stat_finish(sa.sums, width[slot], ntl, so[slot], st, "pointnet_train_finish")) != FX3D_OK) return r;
         }
         if ((r = launch_points(mode, false, p, B, st)) != FX3D_OK) return r;
         // the head: relu(dense1) and for feat its BatchNorm's statistics, relu(dense2) and its BatchNorm's statistics, the end
@@ -357,11 +312,11 @@ fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_cla
                    : stn_head(n, mode, tmax, w.ntiles, T, F, mode == 0 ? stn : fstn);
         if ((r = launch_train_head(0, feat, t, B, st)) != FX3D_OK) return r;
         if (feat) {
-            if ((r = launch_dense_stats(t.a1, width[slot], B, so[slot], st)) != FX3D_OK) return r;
+            if ((r = launch_dense_stats(t.a1, width[slot], B, so[slot], st, "pointnet_train_dense_stats")) != FX3D_OK) return r;
             if ((r = launch_train_head(1, true, t, B, st)) != FX3D_OK) return r;
             ++slot;
         }
-        if ((r = launch_dense_stats(t.a2, width[slot], B, so[slot], st)) != FX3D_OK) return r;
+        if ((r = launch_dense_stats(t.a2, width[slot], B, so[slot], st, "pointnet_train_dense_stats")) != FX3D_OK) return r;
         if ((r = launch_train_head(2, feat, t, B, st)) != FX3D_OK) return r;
         ++slot;
     }

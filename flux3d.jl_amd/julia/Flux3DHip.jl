@@ -1744,6 +1744,61 @@ function dgcnn_forward(m::DGCNN, X::HipArray{Float32,3}; intermediates::Bool = f
 end
 (m::DGCNN)(X::HipArray{Float32,3}) = dgcnn_forward(m, X)
 
+# The same network in TRAINING mode (include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward"): all 8 BatchNorms normalise by
+# the statistics of the current batch, `dropout` is nothing (the identity) or the pair of multipliers (512, B), (256, B) of the
+# Dropout(0.5) after fc_4 and fc_5, and the running statistics Flux's BatchNorm would hold after the step come back as one flat
+# buffer.  The parameters are flattened as for dgcnn_forward; their μ / σ² are the running statistics and are not written.
+# batch_stats and running have dgcnn_stat_count() floats: per BatchNorm in forward order μ (C), then σ² (C).  B >= 2.
+function dgcnn_stat_count()
+    cnt = Ref{Int64}(0)
+    check(@ccall LIB.fx3d_dgcnn_stat_count(cnt::Ref{Int64})::Int32)
+    return Int(cnt[])
+end
+function dgcnn_forward_train(m::DGCNN, X::HipArray{Float32,3};
+                             dropout::Union{Nothing,Tuple{HipArray{Float32,2},HipArray{Float32,2}}} = nothing,
+                             momentum::Real = 0.1f0, intermediates::Bool = false)
+    size(X, 1) == 3 || error("DGCNN takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    B >= 2 || error("DGCNN in training mode needs at least two clouds")
+    K = m.EdgeConv1.K
+    m.EdgeConv2.K == K || error("DGCNN: both EdgeConvs must use the same K")
+    npoints = m.maxpool_3.k[1]
+    N == npoints || error("DGCNN(num_classes, K, npoints = $npoints) takes clouds of npoints points, got $N: MaxPool((npoints,)) is the maximum over a whole cloud only then")
+    (1 <= K && K + 1 <= N) || error("DGCNN needs 1 <= K <= N - 1, got K = $K, N = $N")
+    (dropout === nothing || (size(dropout[1]) == (512, B) && size(dropout[2]) == (256, B))) ||
+        error("dropout must be a pair of (512, $B) and (256, $B) arrays")
+    nc = size(_dense_wb(m.fc_6)[1], 1)
+    params = dgcnn_params(m)
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_dgcnn_train_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(K)::Int32, Int32(nc)::Int32,
+                                                      nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    nstat = dgcnn_stat_count()
+    probs = HipArray{Float32}(undef, nc, B)
+    batch_stats = HipArray{Float32}(undef, nstat)
+    running = HipArray{Float32}(undef, nstat)
+    logits = intermediates ? HipArray{Float32}(undef, nc, B) : nothing
+    idx1 = intermediates ? HipArray{Int32}(undef, K, N, B) : nothing
+    x1 = intermediates ? HipArray{Float32}(undef, 64, N, B) : nothing
+    idx2 = intermediates ? HipArray{Int32}(undef, K, N, B) : nothing
+    x2 = intermediates ? HipArray{Float32}(undef, 256, N, B) : nothing
+    pooled = intermediates ? HipArray{Float32}(undef, 1024, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    d4 = dropout === nothing ? C_NULL : dropout[1].ptr
+    d5 = dropout === nothing ? C_NULL : dropout[2].ptr
+    check(@ccall LIB.fx3d_dgcnn_forward_train(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, Int32(K)::Int32, X.ptr::Ptr{Cvoid},
+                                              Int32(N)::Int32, Int32(B)::Int32, d4::Ptr{Cvoid}, d5::Ptr{Cvoid},
+                                              Float32(momentum)::Float32, probs.ptr::Ptr{Cvoid}, opt(logits)::Ptr{Cvoid},
+                                              opt(idx1)::Ptr{Cvoid}, opt(x1)::Ptr{Cvoid}, opt(idx2)::Ptr{Cvoid},
+                                              opt(x2)::Ptr{Cvoid}, opt(pooled)::Ptr{Cvoid}, batch_stats.ptr::Ptr{Cvoid},
+                                              running.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                              DEFAULT_STREAM::Stream)::Int32)
+    return intermediates ? (probs = probs, logits = logits, idx1 = idx1, x1 = x1, idx2 = idx2, x2 = x2, pooled = pooled,
+                            batch_stats = batch_stats, running = running) :
+                           (probs = probs, batch_stats = batch_stats, running = running)
+end
+
 # The gradients of sum(glogits .* logits) with respect to every parameter of m and to X (include/flux3d_hip.h "DGCNN adjoint"):
 # test mode as dgcnn_forward (running statistics, Dropout the identity), the neighbours constants.  glogits (num_classes, B) is
 # the gradient with respect to the LOGITS: the softmax stays with the caller.  fwd: dgcnn_forward(m, X; intermediates = true),
@@ -1826,6 +1881,40 @@ function edgeconv_forward(m::EdgeConv, X::HipArray{Float32,3}; idx::Union{Nothin
     return return_idx ? (out, idx === nothing ? found : idx) : out
 end
 (m::EdgeConv)(X::HipArray{Float32,3}) = edgeconv_forward(m, X)
+
+# The same layer in TRAINING mode (include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward"): every BatchNorm normalises by
+# the statistics of what it is given over the K N B edge rows of the batch.  Returns (out, batch_stats, running) -- with
+# return_idx, idx too: the statistics buffers have edgeconv_stat_count(m) floats, per BatchNorm in forward order μ (C), then σ² (C);
+# running is what Flux's BatchNorm would hold after the step.  The parameters' μ / σ² are the running statistics and are not written.
+function edgeconv_stat_count(m::EdgeConv)
+    layers = Int32.(collect(m.layers))
+    cnt = Ref{Int64}(0)
+    check(@ccall LIB.fx3d_edgeconv_stat_count(layers::Ptr{Int32}, Int32(length(layers))::Int32, cnt::Ref{Int64})::Int32)
+    return Int(cnt[])
+end
+function edgeconv_forward_train(m::EdgeConv, X::HipArray{Float32,3}; idx::Union{Nothing,HipArray{Int32,3}} = nothing,
+                                momentum::Real = 0.1f0, return_idx::Bool = false)
+    layers, nl, F, N, B, K = _edgeconv_setup(m, X, idx)
+    params = edgeconv_params(m)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_edgeconv_train_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
+                                                         Int32(B)::Int32, nb::Ref{Csize_t})::Int32)
+    pd = hip(params)
+    ws = workspace(nb[])
+    nstat = edgeconv_stat_count(m)
+    out = HipArray{Float32}(undef, Int(layers[end]), N, B)
+    batch_stats = HipArray{Float32}(undef, nstat)
+    running = HipArray{Float32}(undef, nstat)
+    found = (return_idx && idx === nothing) ? HipArray{Int32}(undef, K, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_edgeconv_forward_train(pd.ptr::Ptr{Cvoid}, layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32,
+                                                 X.ptr::Ptr{Cvoid}, Int32(N)::Int32, Int32(B)::Int32, opt(idx)::Ptr{Cvoid},
+                                                 Float32(momentum)::Float32, out.ptr::Ptr{Cvoid}, opt(found)::Ptr{Cvoid},
+                                                 batch_stats.ptr::Ptr{Cvoid}, running.ptr::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid},
+                                                 length(ws)::Csize_t, DEFAULT_STREAM::Stream)::Int32)
+    return return_idx ? (out = out, idx = idx === nothing ? found : idx, batch_stats = batch_stats, running = running) :
+                        (out = out, batch_stats = batch_stats, running = running)
+end
 
 # The gradient of sum(gout .* m(X)) with respect to X (include/flux3d_hip.h "EdgeConv input adjoint"): test-mode BatchNorm, the
 # neighbours constants as CreateSingleKNNGraph is @nograd.  idx, out: the forward's lists and result (edgeconv_forward with

@@ -8,7 +8,8 @@ launch.  EdgeConv has its input gradient and its parameter gradients, and DGCNN 
 whole network with respect to every parameter and to the input points (``DGCNN.grad`` over fx3d_dgcnn_grad, "DGCNN adjoint";
 ``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode.  PointNet also has its
 training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_train, "PointNet training-mode forward") and that
-forward's gradients (``PointNet.grad_train`` over fx3d_pointnet_grad_train, "PointNet training-mode adjoint")."""
+forward's gradients (``PointNet.grad_train`` over fx3d_pointnet_grad_train, "PointNet training-mode adjoint"); DGCNN and EdgeConv have their training-mode forwards (``DGCNN.forward_train`` over
+fx3d_dgcnn_forward_train, ``EdgeConv.forward_train`` over fx3d_edgeconv_forward_train, "DGCNN / EdgeConv training-mode forward")."""
 import ctypes as C
 
 import numpy as np
@@ -227,6 +228,43 @@ class _Model:
             at += n
         return grads
 
+    def _stat_slots(self):
+        """(BatchNorm name, C, offset in the statistics layout, offset of its ``mu`` in the flat parameter buffer) for the
+        model's BatchNorms in forward order; in both buffers ``sigma2`` (C) follows ``mu`` (C) directly."""
+        slots, at, flat = [], 0, 0
+        for name, shape in self._shapes().items():
+            if name.endswith(".mu"):
+                slots.append((name[:-3], shape[0], at, flat))
+                at += 2 * shape[0]
+            flat += int(np.prod(shape))
+        return slots
+
+    @staticmethod
+    def _momentum(momentum):
+        """``momentum`` of the training-mode forwards after its check, a float."""
+        momentum = float(momentum)
+        if not (np.isfinite(momentum) and 0.0 <= momentum <= 1.0):
+            raise ValueError(f"momentum must be finite and in [0, 1], got {momentum}")
+        return momentum
+
+    def _adopt_running(self, run, slots, stream):
+        """``update=True`` of the training-mode forwards: the flat ``running`` buffer into the model's parameters, on the host
+        (which reads it back: not inside a graph capture) and in the kept device copy."""
+        host, params = run.to_host(), self._params_dev()
+        for name, C, at, flat in slots:  # mu then sigma2, adjacent in both layouts
+            self.params[name + ".mu"], self.params[name + ".sigma2"] = host[at:at + C].copy(), host[at + C:at + 2 * C].copy()
+            _lib.call("fx3d_memcpy_d2d", params.ptr + 4 * flat, run.ptr + 4 * at, 8 * C, stream)
+
+    @staticmethod
+    def _named_stats(buf, slots, on_dev):
+        """A flat statistics buffer on the device as name -> array under the ``...bnK.mu`` / ``.sigma2`` names: views of the
+        buffer on the device, of its host copy otherwise."""
+        named, host = {}, (None if on_dev else buf.to_host())
+        for name, C, at, _ in slots:
+            for f, o in ((".mu", at), (".sigma2", at + C)):
+                named[name + f] = (DeviceArray(buf.ptr + 4 * o, (C,), np.float32, owned=False, keep=buf) if on_dev else host[o:o + C])
+        return named
+
     def _labels(self, labels, B):
         """``labels`` of ``crossentropy_grad`` after their checks: B integers in [0, num_classes)."""
         y = np.asarray(labels)
@@ -330,17 +368,6 @@ class PointNet(_Model):
         u = np.random.default_rng(seed).random((256, int(B)))
         return np.asfortranarray(np.where(u > p, np.float32(1.0 / (1.0 - float(p))), np.float32(0.0)).astype(np.float32))
 
-    def _stat_slots(self):
-        """(BatchNorm name, C, offset in the statistics layout, offset of its ``mu`` in the flat parameter buffer) for the 13
-        BatchNorms in forward order; in both buffers ``sigma2`` (C) follows ``mu`` (C) directly."""
-        slots, at, flat = [], 0, 0
-        for name, shape in self._shapes().items():
-            if name.endswith(".mu"):
-                slots.append((name[:-3], shape[0], at, flat))
-                at += 2 * shape[0]
-            flat += int(np.prod(shape))
-        return slots
-
     def forward_train(self, X, dropout=None, momentum=0.1, update=False, intermediates=False):
         """Class probabilities ``(num_classes, B)`` of the clouds ``X`` (as in :meth:`forward`, at least two clouds) with the
         network in TRAINING mode: include/flux3d_hip.h "PointNet training-mode forward".  Every BatchNorm normalises by the
@@ -358,9 +385,7 @@ class PointNet(_Model):
         if B < 2:
             raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
                              f"B - 1), got B={B}")
-        momentum = float(momentum)
-        if not (np.isfinite(momentum) and 0.0 <= momentum <= 1.0):
-            raise ValueError(f"momentum must be finite and in [0, 1], got {momentum}")
+        momentum = self._momentum(momentum)
         mask = self._train_mask(dropout, B, on_dev)
         nb = _lib.query_bytes("fx3d_pointnet_train_workspace_bytes", N, B, nc)  # (the library's own size limits)
         if mask is not None and not is_device(mask):
@@ -380,19 +405,11 @@ class PointNet(_Model):
                   out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
                   stats["batch_stats"].ptr, stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
         if update:
-            run = stats["running"]
-            host = run.to_host()
-            for name, C, at, flat in slots:  # mu then sigma2, adjacent in both layouts
-                self.params[name + ".mu"], self.params[name + ".sigma2"] = host[at:at + C].copy(), host[at + C:at + 2 * C].copy()
-                _lib.call("fx3d_memcpy_d2d", params.ptr + 4 * flat, run.ptr + 4 * at, 8 * C, stream)
+            self._adopt_running(stats["running"], slots, stream)
         if not intermediates:
             return out["probs"] if on_dev else out["probs"].to_host()
         for key, buf in stats.items():
-            named, host = {}, (None if on_dev else buf.to_host())
-            for name, C, at, _ in slots:
-                for f, o in ((".mu", at), (".sigma2", at + C)):
-                    named[name + f] = (DeviceArray(buf.ptr + 4 * o, (C,), f32, owned=False, keep=buf) if on_dev else host[o:o + C])
-            out[key] = named
+            out[key] = self._named_stats(buf, slots, on_dev)
         if not on_dev:
             out = {k: (v if isinstance(v, dict) else v.to_host()) for k, v in out.items()}
         return out
@@ -535,8 +552,9 @@ class DGCNN(_Model):
     neighbour lists are constants): :meth:`grad` gives the gradient of ``sum(glogits * logits)`` with respect to every parameter
     and to the input points from one library call (include/flux3d_hip.h "DGCNN adjoint"), :meth:`flat_grad` the same as one
     flat buffer, :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  The two
-    EdgeConv stages inside are :meth:`EdgeConv.grad`'s kernel on the ``ec2.`` and ``ec1.`` parameters, bit for bit.  Training-mode
-    BatchNorm (batch statistics) and Dropout in training mode are not differentiated."""
+    EdgeConv stages inside are :meth:`EdgeConv.grad`'s kernel on the ``ec2.`` and ``ec1.`` parameters, bit for bit.  The
+    training-mode forward -- BatchNorm at the batch statistics, the two Dropouts as given masks, the updated running statistics --
+    is :meth:`forward_train` (include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward"); it is not differentiated yet."""
 
     _NAME, _COUNT_FN, _WHY = "DGCNN", "fx3d_dgcnn_param_count", "EdgeConv([3, 32, 64, 64], K)"
 
@@ -565,12 +583,97 @@ class DGCNN(_Model):
         ``intermediates=True``: a dict with ``probs``, ``logits`` (num_classes, B), ``idx1`` and ``idx2`` (K, N, B) int32,
         0-based, ``x1`` (64, N, B), ``x2`` (256, N, B) and ``pooled`` (1024, B)."""
         _, N, B, _ = clouds = self._clouds(X, self._WHY)
-        nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
-        optional = {"logits": ((nc, B), f32), "idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32),
-                    "x2": ((256, N, B), f32), "pooled": ((1024, B), f32)}
-        return self._classify(clouds, "dgcnn", (nc, K), (N, B, K, nc), optional, intermediates)
+        nc, K = self.num_classes, self.K
+        return self._classify(clouds, "dgcnn", (nc, K), (N, B, K, nc), self._optional(N, B), intermediates)
 
     __call__ = forward
+
+    def _optional(self, N, B):
+        """The forward entries' optional outputs in their argument order: name -> (shape, dtype)."""
+        nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
+        return {"logits": ((nc, B), f32), "idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32),
+                "x2": ((256, N, B), f32), "pooled": ((1024, B), f32)}
+
+    @staticmethod
+    def dropout_masks(B, seed, p=0.5):
+        """The two arrays of multipliers, ``(512, B)`` and ``(256, B)`` Float32, of the ``Dropout(p)`` after ``fc_4`` and after
+        ``fc_5`` in training mode for :meth:`forward_train`, from one numpy generator seeded with ``seed`` (the first mask is
+        drawn first): Flux's ``rand > p ? T(1 / (1 - p)) : 0`` per entry, so every entry is 0 or ``np.float32(1.0 / (1.0 - p))``
+        (``np.float32(2.0)`` for p = 0.5).  The draws are numpy's, not Julia's."""
+        if not 0.0 <= float(p) < 1.0:
+            raise ValueError(f"p must be in [0, 1), got {p}")
+        if int(B) < 1:
+            raise ValueError(f"B must be positive, got {B}")
+        rng = np.random.default_rng(seed)
+        keep = np.float32(1.0 / (1.0 - float(p)))
+        return tuple(np.asfortranarray(np.where(rng.random((C_, int(B))) > p, keep, np.float32(0.0)).astype(np.float32))
+                     for C_ in (512, 256))
+
+    def _train_masks(self, dropout, B, on_dev):
+        """``dropout`` of :meth:`forward_train` after its checks: ``(None, None)``, or the ``(512, B)`` and ``(256, B)``
+        multipliers (an ``int``: the seed of :meth:`dropout_masks`), each a device array or a host array still to be uploaded."""
+        if dropout is None:
+            return None, None
+        if isinstance(dropout, (int, np.integer)):
+            return self.dropout_masks(B, int(dropout))
+        if isinstance(dropout, (str, bytes)) or is_device(dropout) or isinstance(dropout, np.ndarray):
+            raise TypeError("dropout must be None, an int seed or a pair of arrays (512, B) and (256, B)")
+        try:
+            m4, m5 = dropout
+        except (TypeError, ValueError):
+            raise TypeError("dropout must be None, an int seed or a pair of arrays (512, B) and (256, B)") from None
+        masks = []
+        for m, C_, name in ((m4, 512, "dropout[0]"), (m5, 256, "dropout[1]")):
+            if is_device(m) and not on_dev:
+                raise TypeError("a device dropout mask needs X on the device")
+            masks.append(self._like(m, name, (C_, B), np.float32, is_device(m)))
+        return tuple(masks)
+
+    def forward_train(self, X, dropout=None, momentum=0.1, update=False, intermediates=False):
+        """Class probabilities ``(num_classes, B)`` of the clouds ``X`` (as in :meth:`forward`, at least two clouds) with the
+        network in TRAINING mode: include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward".  All 8 BatchNorms normalise by
+        the mean and uncorrected variance of the current batch (over the K N B edge rows in the EdgeConvs, the N B points at
+        conv_3, the B clouds in the head); EdgeConv2's neighbours are searched on the training-mode ``x1``.  ``dropout`` is
+        ``None`` (the identity), a pair of arrays of multipliers ``(512, B)`` and ``(256, B)`` for the outputs of ``fc_4`` and
+        ``fc_5`` (numpy, or device arrays beside a device ``X``), or an ``int`` seed for :meth:`dropout_masks`.
+        ``intermediates=True``: a dict with ``probs``, ``logits``, ``idx1``, ``x1``, ``idx2``, ``x2``, ``pooled`` as
+        :meth:`forward` gives them, ``batch_stats`` and ``running``: dicts name -> array with the ``...bn.mu`` / ``.sigma2`` names
+        of :func:`dgcnn_param_shapes`, the batch statistics and the running statistics Flux's BatchNorm would hold after this
+        step (``momentum``; computed from the model's ``mu`` / ``sigma2``).  Everything lives where ``X`` lives.
+        ``update=True`` writes ``running`` into the model's parameters, on the host (which reads them back: not inside a graph
+        capture) and in the kept device copy: the next :meth:`forward` is the test-mode network after one training step's worth
+        of statistics."""
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
+        nc, K, f32 = self.num_classes, self.K, np.float32
+        if B < 2:
+            raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
+                             f"B - 1), got B={B}")
+        momentum = self._momentum(momentum)
+        masks = self._train_masks(dropout, B, on_dev)
+        nb = _lib.query_bytes("fx3d_dgcnn_train_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
+        masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
+        x = self._on_device(pts, N, B, on_dev)
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        optional = self._optional(N, B)
+        out = self._outputs(B, optional, intermediates)
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if intermediates or update:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        ws = workspace(nb, tag="dgcnn_train")
+        stream = current_stream().handle
+        _lib.call("fx3d_dgcnn_forward_train", self._params_dev().ptr, nc, K, x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
+                  momentum, out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
+                  stats["batch_stats"].ptr, stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
+        if update:
+            self._adopt_running(stats["running"], slots, stream)
+        if not intermediates:
+            return out["probs"] if on_dev else out["probs"].to_host()
+        for key, buf in stats.items():
+            out[key] = self._named_stats(buf, slots, on_dev)
+        if not on_dev:
+            out = {k: (v if isinstance(v, dict) else v.to_host()) for k, v in out.items()}
+        return out
 
     _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
 
@@ -724,6 +827,44 @@ class EdgeConv(_Model):
         return (out, used) if return_idx else out
 
     __call__ = forward
+
+    def forward_train(self, X, idx=None, momentum=0.1, update=False, return_idx=False, intermediates=False):
+        """:meth:`forward` with the layer in TRAINING mode: include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward".  Every
+        BatchNorm normalises by the mean and uncorrected variance of what it is given over the K N B edge rows of the batch (one
+        cloud is enough).  ``X``, ``idx``, ``return_idx`` and the placement of the results as in :meth:`forward`.
+        ``intermediates=True``: a dict with ``out``, ``idx`` (the lists that were used), ``batch_stats`` and ``running``: dicts
+        name -> array with the ``bnK.mu`` / ``.sigma2`` names of :func:`edgeconv_param_shapes`, the batch statistics and the
+        running statistics Flux's BatchNorm would hold after this step (``momentum``; computed from the layer's ``mu`` /
+        ``sigma2``).  ``update=True`` writes ``running`` into the layer's parameters, on the host (which reads them back: not
+        inside a graph capture) and in the kept device copy."""
+        F, K, f32 = self.layers[0], self.K, np.float32
+        pts, N, B, on_dev, layers, nl = self._head(X)
+        momentum = self._momentum(momentum)
+        nb = _lib.query_bytes("fx3d_edgeconv_train_workspace_bytes", layers, nl, K, N, B)  # (the library's own size limits)
+        given = None if idx is None else self._neighbours(idx, N, B)
+        x = self._on_device(pts, N, B, on_dev, F)
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        out = DeviceArray.empty((self.layers[-1], N, B), f32)
+        found = DeviceArray.empty((K, N, B), np.int32) if (return_idx or intermediates) and given is None else None
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if intermediates or update:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        ws = workspace(nb, tag="edgeconv_train")
+        stream = current_stream().handle
+        _lib.call("fx3d_edgeconv_forward_train", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr if given else None,
+                  momentum, out.ptr, found.ptr if found else None, stats["batch_stats"].ptr,
+                  stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
+        if update:
+            self._adopt_running(stats["running"], slots, stream)
+        used = given if given is not None else found
+        if not on_dev:
+            out, used = out.to_host(), (used.to_host() if used is not None else None)
+        if intermediates:
+            res = {"out": out, "idx": used}
+            res.update({key: self._named_stats(buf, slots, on_dev) for key, buf in stats.items()})
+            return res
+        return (out, used) if return_idx else out
 
     def _like_out(self, a, name, N, B, on_dev):
         """``gout`` / ``out`` after its checks (:meth:`_like`), as (cL, N, B)."""

@@ -1205,6 +1205,71 @@ FX3D_API fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t n
                                               float *gx, float *gstn, float *gfstn, float *gh, float *gxt, void *ws, size_t ws_bytes,
                                               fx3d_stream_t s);
 
+/* ---- DGCNN / EdgeConv training-mode forward: (m::DGCNN)(X) and (m::EdgeConv)(X) with Flux's BatchNorm and Dropout(0.5) in training mode --
+ * The networks, the layouts and all arithmetic but BatchNorm's statistics are "DGCNN inference" / "EdgeConv inference" above.  Every
+ * block is conv-or-dense, BatchNorm, relu, so the value v a BatchNorm is given is always the Float32 conv + bias or dense + bias,
+ * before the relu.  Every BatchNorm normalises by the mean and the uncorrected variance of v over the current batch, and the running
+ * statistics Flux would then hold are returned.
+ * Sums, mean and variance, running update: "PointNet training-mode forward"'s, word for word.  Float64 S1 = sum (double)v,
+ *   S2 = sum (double)v (double)v (exact products), every chain from +0.0 with one rounding per addition;  mu64 = S1 / m;
+ *   var64 = S2 / m - mu64 mu64, and 0 where that is below 0 (a NaN stays);  mu = Float32(mu64), var = Float32(var64);  the
+ *   normalisation is the inference BatchNorm at (mu, sqrtf(var + 1f-5));  in Float32, one rounding per operation, nothing fused,
+ *   mu' = ((1 - mtm) mu_run) + (mtm mu),  var' = ((1 - mtm) var_run) + (((mtm Float32(m)) / Float32(m - 1)) var).
+ * m per BatchNorm: K N B for an EdgeConv's BatchNorms (every edge row (k, n, b) is one value) -- DGCNN's ec1.bn1 .. bn3 (32, 64, 64
+ *   channels) and ec2.bn1, bn2 (128, 256);  N B for conv3.bn (1024);  B for fc4.bn (512) and fc5.bn (256).
+ * Orders of the sums.  They depend on (layers, K, N, B) alone, never on the launch shape; no atomics.  A tile is 64 consecutive
+ *   points of one cloud (tile t: points 64 t .. 64 t + 63); rows beyond the cloud's last point take no part.
+ *   An EdgeConv BatchNorm, per channel:  within a tile the rows p = 0 .. 63 with p div 32 = q and bit 2 of p equal to h form the
+ *     chain (q, h), q, h = 0, 1: it runs over the neighbour rank k ascending and, within a k, over its 16 rows in ascending p.  The
+ *     tile's sum is (chain(0,0) + chain(0,1)) + (chain(1,0) + chain(1,1)).  (A layer of up to 64 channels has the two q on
+ *     different waves, a wider one in one lane: the order is the same.)  The tile sums t = tile + ntiles b are folded as
+ *     "PointNet training-mode forward" folds them: FX3D_POINTNET_STAT_GROUPS chains, chain g over t = g, g + 32, ... ascending,
+ *     added in ascending g.
+ *   conv3.bn: "PointNet training-mode forward"'s order of a convolution's BatchNorm, verbatim (chains h = 0, 1 by bit 2 of p over
+ *     the tile's 64 rows ascending, chain(0) + chain(1), the same fold).
+ *   fc4.bn, fc5.bn: one chain over the clouds in ascending b.
+ * Dropout: Dropout(0.5) follows relu(BN(fc_4)) and relu(BN(fc_5)) (src/models/dgcnn.jl:105-108,136-139).  dropout4 (512,B) and
+ *   dropout5 (256,B) are the Float32 multipliers, applied with one Float32 multiplication each; NULL: the identity.  No random
+ *   numbers are drawn on the device.  fc5.bn's statistics are therefore those of fc_5's dense layer on dropout4 . relu(BN(fc_4)).
+ * Neighbours: an EdgeConv's lists are fx3d_knn_ws's on its input, as in inference, and constants (the reference's @nograd).  DGCNN's
+ *   idx1 is therefore the test-mode list; idx2 is searched on the training-mode x1 and differs from test mode.
+ * Statistics layout (batch_stats and running): per BatchNorm in forward order mu (C), then var (C).  EdgeConv: bn1 .. bnL,
+ *   fx3d_edgeconv_stat_count = 2 (c1 + ... + cL) floats.  DGCNN: ec1.bn1 .. bn3, ec2.bn1, bn2, conv3.bn, fc4.bn, fc5.bn -- the order
+ *   of the mu / var slots of params_dev -- 2336 channels, fx3d_dgcnn_stat_count = 4672 floats; its ec1 / ec2 slices are the two
+ *   stages' own buffers.
+ * batch_stats is required; running is optional and is computed from the mu / var slots of params_dev, which is not written.
+ * fx3d_edgeconv_forward_train: params_dev .. idx_in, out, idx_out as in fx3d_edgeconv_forward, over its whole envelope (1 <= L <= 4,
+ *   F <= 128, widths <= 256, no multiple of 4 or 32 required, lists searched or given).  B = 1 is allowed: K + 1 <= N gives m >= 2.
+ * fx3d_dgcnn_forward_train: params_dev .. B and probs (required), logits, idx1, x1, idx2, x2, pooled (optional) as in
+ *   fx3d_dgcnn_forward.  Its two stages are fx3d_edgeconv_forward_train on the ec1 / ec2 slices, bit for bit.
+ * out, idx, logits, idx1, x1, idx2, x2, pooled, batch_stats and running are bit-identical to the restatement
+ * tests/dgcnn_train_ref.py and from run to run.  fx3d_dgcnn_forward / fx3d_edgeconv_forward on parameters whose mu / var slots
+ * hold batch_stats give, with the dropouts NULL, the same outputs bit for bit: the closing passes are those kernels.
+ * Refusals, each before any device work: the forward's own limits with its status codes (FX3D_ERR_UNSUPPORTED for layers outside
+ * the envelope, FX3D_ERR_INVALID_ARG for sizes);  FX3D_ERR_INVALID_ARG for a NULL required pointer (params_dev, x, probs / out,
+ * batch_stats, ws), B < 2 for DGCNN (a dense BatchNorm's running variance divides by B - 1), momentum not finite or outside [0, 1],
+ * a short workspace or one not 256-byte aligned.
+ * Launches on `s` only, no host synchronisation, no host memory other than `layers` read and none after the argument check
+ * (graph-capturable).  Per EdgeConv: the search where idx_in is NULL, per BatchNorm a statistics pass (the forward's loop over k
+ * stopped at that layer, the sums taken in the MFMA accumulators: no (K N, C, B) array in memory) and a finishing kernel, then the
+ * forward's kernel at the statistics.  DGCNN: that twice, conv_3's statistics pass, finishing kernel and maxima kernel, and the head
+ * in three kernels with two dense-statistics kernels between them: 20 launches besides the two searches.
+ * ws: fx3d_edgeconv_train_workspace_bytes / fx3d_dgcnn_train_workspace_bytes -- the forward's workspace, the Float64 tile sums
+ * (2,C,ntiles,B) of the widest layer, and for DGCNN the head's (512,B) and (256,B) dense outputs. */
+FX3D_API fx3d_status fx3d_edgeconv_stat_count(const int32_t *layers, int32_t nlayers, int64_t *count);
+FX3D_API fx3d_status fx3d_edgeconv_train_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
+                                                         size_t *bytes);
+FX3D_API fx3d_status fx3d_edgeconv_forward_train(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
+                                                 const float *x, int32_t N, int32_t B, const int32_t *idx_in, float momentum,
+                                                 float *out, int32_t *idx_out, float *batch_stats, float *running, void *ws,
+                                                 size_t ws_bytes, fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_dgcnn_stat_count(int64_t *count);
+FX3D_API fx3d_status fx3d_dgcnn_train_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_dgcnn_forward_train(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N,
+                                              int32_t B, const float *dropout4, const float *dropout5, float momentum, float *probs,
+                                              float *logits, int32_t *idx1, float *x1, int32_t *idx2, float *x2, float *pooled,
+                                              float *batch_stats, float *running, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
