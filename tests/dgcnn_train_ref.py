@@ -16,7 +16,7 @@ bit (pointnet_train_ref's note)."""
 import numpy as np
 
 import dgcnn_ref as ref
-from pointnet_train_ref import GROUPS, TILE, dense_sums, mean_var, point_sums, running_update  # noqa: F401
+from pointnet_train_ref import GROUPS, TILE, dense_sums, mean_var, point_sums, raw_var, running_update  # noqa: F401
 
 F32, F64 = np.float32, np.float64
 BN_ORDER = ["ec1.bn1", "ec1.bn2", "ec1.bn3", "ec2.bn1", "ec2.bn2", "conv3.bn", "fc4.bn", "fc5.bn"]
@@ -65,7 +65,7 @@ class _Train:
 
     def __init__(self, P, momentum):
         self.P, self.Q, self.momentum = P, dict(P), momentum
-        self.batch_stats, self.running, self.bn_inputs = {}, {}, {}
+        self.batch_stats, self.running, self.bn_inputs, self.raw_var = {}, {}, {}, {}
 
     def bn(self, v, name):
         """v: (B, K, N, C) in an EdgeConv, (B, N, C) after conv_3, (B, C) after a dense layer."""
@@ -73,6 +73,7 @@ class _Train:
         s1, s2 = (edge_sums, point_sums, dense_sums)[4 - v.ndim](v)
         m = int(np.prod(v.shape[:-1]))
         mu, var = mean_var(s1, s2, m)
+        self.raw_var[name] = raw_var(s1, s2, m)
         self.bn_inputs[name] = v
         self.batch_stats[name + ".mu"], self.batch_stats[name + ".sigma2"] = mu, var
         self.running[name + ".mu"], self.running[name + ".sigma2"] = running_update(
@@ -96,7 +97,8 @@ def edgeconv_forward_train(X, P, layers, K, idx=None, momentum=0.1):
     """EdgeConv(layers, K) in training mode.  X (F, N, B) or (F, N); P: name -> array in Flux's shapes with edgeconv_ref's names
     (its mu / sigma2 are the running statistics); idx: (K, N, B) 0-based lists to use instead of the search.  A dict: ``idx``
     (K, N, B) int32 and ``out`` (cL, N, B) laid out as the library returns them; ``batch_stats`` and ``running``: name -> (C,)
-    under the ``bnK.mu`` / ``.sigma2`` names; ``bn_inputs``: BatchNorm name -> what it was given, (B, K, N, C)."""
+    under the ``bnK.mu`` / ``.sigma2`` names; ``bn_inputs``: BatchNorm name -> what it was given, (B, K, N, C); ``raw_var``:
+    BatchNorm name -> (C,) Float64, the variance before the clamp."""
     X = np.asarray(X, F32)
     if X.ndim == 2:
         X = X[:, :, None]
@@ -107,15 +109,16 @@ def edgeconv_forward_train(X, P, layers, K, idx=None, momentum=0.1):
     t = _Train(P, momentum)
     idx, y = _edgeconv(x, t, "", len(layers) - 1, K, idx)
     return {"idx": np.asfortranarray(idx.astype(np.int32)), "out": np.asfortranarray(np.transpose(y, (2, 1, 0))),
-            "batch_stats": t.batch_stats, "running": t.running, "bn_inputs": t.bn_inputs}
+            "batch_stats": t.batch_stats, "running": t.running, "bn_inputs": t.bn_inputs, "raw_var": t.raw_var}
 
 
 def forward_train(X, P, K, dropout=None, momentum=0.1):
     """DGCNN in training mode.  X (3, N, B) with B >= 2; P: name -> array in Flux's shapes (its mu / sigma2 are the running
     statistics); dropout: None or the pair of multipliers (512, B), (256, B).  A dict as dgcnn_ref.forward's -- ``idx1``, ``idx2``,
     ``x1``, ``x2``, ``pooled``, ``logits``, ``probs`` laid out as the library returns them -- with ``batch_stats`` and ``running``:
-    name -> (C,) under the ``...bn.mu`` / ``.sigma2`` names; ``bn_inputs``: BatchNorm name -> what it was given; ``d4`` (B, 512):
-    fc_4's output after its dropout multiplier, fc_5's input."""
+    name -> (C,) under the ``...bn.mu`` / ``.sigma2`` names; ``bn_inputs``: BatchNorm name -> what it was given; ``raw_var``:
+    BatchNorm name -> (C,) Float64, the variance before the clamp; ``d4`` (B, 512): fc_4's output after its dropout multiplier,
+    fc_5's input."""
     X = np.asarray(X, F32)
     assert X.ndim == 3 and X.shape[2] >= 2
     B = X.shape[2]
@@ -142,7 +145,7 @@ def forward_train(X, P, K, dropout=None, momentum=0.1):
     r["pooled"] = np.asfortranarray(pooled.T)
     r["logits"] = np.asfortranarray(logits.T)
     r["probs"] = ref.softmax32(r["logits"])
-    r["batch_stats"], r["running"], r["bn_inputs"] = t.batch_stats, t.running, t.bn_inputs
+    r["batch_stats"], r["running"], r["bn_inputs"], r["raw_var"] = t.batch_stats, t.running, t.bn_inputs, t.raw_var
     assert [k[:-3] for k in t.batch_stats if k.endswith(".mu")] == BN_ORDER  # the BatchNorms ran in the layout's order
     return r
 

@@ -38,15 +38,21 @@ sigma2_edges_last  EdgeConv only: the same edit on the LAST BatchNorm alone, so 
 sigma2_zero      sigma2 = 0 alone (sd = sqrt(eps), a factor 316) on the same two channels of every BatchNorm: all finite, so unlike
                  the two draws above it reaches every chain of the adjoints; the host test also holds it to float64 autograd.
 constant_cloud   every point of a cloud is the same finite point (one per cloud); random_params.  EdgeConv and DGCNN only.
+
+The training-mode entry points -- PointNet forward_train / grad_train, EdgeConv and DGCNN forward_train -- have a section of their
+own below (train_families, draw_train, upstream, check_train): the same draws plus one_point and variance_overflow, held to
+conditions on the batch statistics; tests/test_gpu_model_draws_train.py compares the device.
 """
 import numpy as np
 
 import dgcnn_grad_ref
 import dgcnn_ref
+import dgcnn_train_ref
 import edgeconv_bwd_ref
 import edgeconv_pgrad_ref
 import edgeconv_ref
 import pointnet_ref
+import pointnet_train_ref
 from pointnet_ref import BN_EPS, F32
 
 TINY = float(np.finfo(np.float32).tiny)   # the smallest normal Float32
@@ -152,8 +158,12 @@ def _edit_sigma2(P, bns, kinds):
 
 def draw(family, net, N, B):
     """One seeded draw of the family for the network: dict(X, P, g, ...)."""
+    assert family in families(net[0]), (family, net[0])
+    return _draw(family, net, N, B)
+
+
+def _draw(family, net, N, B):
     kind = net[0]
-    assert family in families(kind), (family, kind)
     rng = np.random.default_rng([SEEDS.index(family), N, B, in_channels(net)])
     F = in_channels(net)
     P = base_params(net)
@@ -329,6 +339,217 @@ def check_grads(family, net, d, G, gx, tag=""):
             assert np.all(np.isfinite(G[n][rest])), n
         assert np.all(np.isfinite(G[f"conv{L}.weight"][0][:, rest]))
         assert not np.all(np.isfinite(G[f"conv{L}.weight"][0][:, list(ch["nan"])]))
+
+
+# ---- training mode: batch-statistic BatchNorm --------------------------------------------------------------------------------
+# PointNet forward_train / grad_train, EdgeConv and DGCNN forward_train.  Every BatchNorm takes its mean and variance from Float64
+# sums over the batch, rounded to Float32 once; the families below put subnormal, +0, +Inf and NaN values into those statistics.
+# The draws are draw()'s wherever the family exists there; what is new:
+#
+# constant_cloud     for PointNet too: one point per cloud and two clouds, so a convolution BatchNorm sees two values.
+# one_point          every point of every cloud is one seeded point: every BatchNorm's input is constant, S2 / m - mu64 mu64 is
+#                    pure rounding residue -- negative (clamped to +0) or positive (a tiny sigma2 whose bits depend on the order
+#                    of the chain).
+# variance_overflow  X x 1e25 for PointNet (x 1e20, `large`'s scale, for EdgeConv and DGCNN): the first BatchNorm's Float64 variance
+#                    is beyond Float32, sigma2 = +Inf with a finite mu, (v - mu) / Inf = 0 and every later BatchNorm sees beta.
+# overflow           PointNet takes overflow_scales_train's factors in training mode (see there).
+# The sigma2_* families stay out: in training mode the running statistics of the parameters enter `running` only.
+TRAIN_FAMILIES = ("subnormal_mid", "subnormal_input", "decades", "decades_small", "decades_edge", "large", "overflow",
+                  "negative_gamma", "constant_cloud", "one_point", "variance_overflow")   # a family's place here seeds a new draw
+TRAIN_ONLY = ("one_point", "variance_overflow")    # the families draw() does not have
+VARIANCE_OVERFLOW = {"edgeconv": 1e20, "dgcnn": 1e20, "pointnet": 1e25}
+
+
+def overflow_scales_train(net):
+    """overflow_scales for the training-mode networks.  EdgeConv and DGCNN keep the test-mode factors: the first BatchNorm's
+    statistics then hold finite, +Inf and NaN values together (DGCNN ec1.bn1: mu 6 % +Inf, sigma2 94 % +Inf and 6 % NaN).
+    PointNet at the test-mode 3.5e9 is finite everywhere once every layer is renormalised, so it takes factors of its own,
+    chosen on the host (tests/test_model_draws_host.py prints the shares): see POINTNET_OVERFLOW_TRAIN."""
+    return POINTNET_OVERFLOW_TRAIN if net[0] == "pointnet" else overflow_scales(net)
+
+
+# X x 1e30, stn.conv1 and conv_block1.conv x 1e8.  The first BatchNorm, stn.bn1, then holds all three kinds: mu is finite in 50 %
+# of its 64 channels and +Inf in 50 % (a channel with one +Inf value after the relu), sigma2 is +Inf in the first half (S2 / m
+# beyond Float32 with a finite mean) and NaN in the second (Inf - Inf); every later statistic and every output is NaN.  Measured
+# at X x 1e30 with the weights x 1e6, 1e7, 3e7: mu all finite, sigma2 all +Inf, no NaN, outputs finite (variance_overflow's
+# picture); x 3e8: 3 % / 97 %; x 1e9: mu all +Inf, sigma2 all NaN.  No pair gives a FINITE sigma2 next to a +Inf one in one
+# BatchNorm: that needs values below 1.8e19 and above 3.4e38 in one layer, a spread the weights do not have.
+POINTNET_OVERFLOW_TRAIN = (1e30, 1e8)
+
+
+def train_families(kind):
+    """The families that apply to a network kind in training mode."""
+    assert kind in PARAM_SEED, kind
+    return list(TRAIN_FAMILIES)
+
+
+def draw_train(family, net, N, B):
+    """One seeded draw of a training-mode family: draw()'s own arrays wherever draw() has the family."""
+    kind = net[0]
+    assert family in train_families(kind), (family, kind)
+    if family not in TRAIN_ONLY and not (family == "overflow" and kind == "pointnet"):
+        return _draw(family, net, N, B)          # constant_cloud for PointNet: the same code, which draw() only refuses
+    F = in_channels(net)
+    rng = np.random.default_rng([1000 + TRAIN_FAMILIES.index(family), N, B, F])
+    P = base_params(net)
+    X = rng.standard_normal((F, N, B))
+    gshape = upstream_shape(net, N, B)
+    g = None if gshape is None else rng.standard_normal(gshape)
+    if family == "one_point":
+        X = np.broadcast_to(X[:, :1, :1], (F, N, B))
+    elif family == "variance_overflow":
+        X = X * VARIANCE_OVERFLOW[kind]
+    else:
+        xs, ws = overflow_scales_train(net)
+        X = X * xs
+        _scale(P, first_weights(net), ws)
+    with np.errstate(all="ignore"):
+        return dict(X=np.asfortranarray(np.asarray(X).astype(F32)), P=P, g=None if g is None else np.asfortranarray(g.astype(F32)))
+
+
+def upstream(family, net, N, B):
+    """glogits (nc, B) for PointNet's adjoints, from a generator of its own (draw() gives PointNet none, and a shape from
+    upstream_shape would shift the generator under the existing draws).  DGCNN's rule: unit scale, except under decades (every
+    element x 10 ** integers(-6, 7)) and under decades_small / decades_edge (small on the even clouds, unit scale on the odd)."""
+    kind, nc = net
+    assert kind == "pointnet", kind
+    names = FAMILIES + TRAIN_ONLY
+    rng = np.random.default_rng([2000 + names.index(family), N, B, nc])
+    g = rng.standard_normal((nc, B))
+    if family == "decades":
+        g = g * 10.0 ** rng.integers(-6, 7, g.shape)
+    elif family in ("decades_small", "decades_edge"):
+        lo, hi = (-44, -29) if family == "decades_small" else (-41, -35)
+        small = g * 10.0 ** rng.integers(lo, hi, g.shape)
+        g[:, 0::2] = small[:, 0::2]
+    with np.errstate(all="ignore"):
+        return np.asfortranarray(g.astype(F32))
+
+
+def train_batchnorms(net):
+    """(every BatchNorm in forward order, those that follow a convolution)."""
+    kind, arg = net
+    if kind == "edgeconv":
+        bns = [f"bn{i}" for i in range(1, len(arg))]
+        return bns, bns
+    if kind == "dgcnn":
+        bns = list(dgcnn_train_ref.BN_ORDER)
+        return bns, [b for b in bns if not b.startswith("fc")]
+    bns = list(pointnet_train_ref.BN_ORDER)
+    return bns, [b for b in bns if b not in pointnet_train_ref.DENSE_BN]
+
+
+def train_outputs(net):
+    """The arrays the training-mode conditions speak of."""
+    return {"edgeconv": ("out",), "dgcnn": ("x1", "x2", "pooled", "logits"), "pointnet": ("stn", "fstn", "pooled", "logits")}[net[0]]
+
+
+def stat_shares(a):
+    """(subnormal, +0 or -0, +Inf, NaN) shares of a Float32 statistics array."""
+    a = np.asarray(a, F32)
+    with np.errstate(all="ignore"):
+        mag = np.abs(a)
+        return (float(np.mean((mag > 0) & (mag < TINY))), float(np.mean(a == 0)), float(np.mean(a == np.inf)), float(np.mean(np.isnan(a))))
+
+
+def _plus_zero(a):
+    return np.ascontiguousarray(np.asarray(a, F32)).view(np.uint32) == 0
+
+
+def check_train(family, net, d, fwd, tag=""):
+    """The family's condition on the restatement's own training-mode forward (a dict with batch_stats, bn_inputs, raw_var and the
+    outputs).  Prints, per BatchNorm, the subnormal / zero / +Inf / NaN shares of mu and sigma2 (and under one_point the negative
+    / zero / positive shares of the variance before the clamp).  The floors are the measured values rounded down; the host test
+    prints the values themselves."""
+    kind = net[0]
+    bns, convs = train_batchnorms(net)
+    st = fwd["batch_stats"]
+    assert [k for k in st] == [f"{bn}.{f}" for bn in bns for f in ("mu", "sigma2")]
+    sh = {}
+    for bn in bns:
+        for f in ("mu", "sigma2"):
+            s = sh[f"{bn}.{f}"] = stat_shares(st[f"{bn}.{f}"])
+            print(f"{tag}{family} {kind} {bn}.{f}: subnormal {s[0]:.2f}, zero {s[1]:.2f}, +Inf {s[2]:.2f}, NaN {s[3]:.2f} of {st[f'{bn}.{f}'].size}")
+    outs = {k: describe(f"{tag}{family} {kind} {k}", fwd[k]) for k in train_outputs(net)}
+    every = np.concatenate([np.asarray(v, F32).ravel() for v in st.values()])
+    finite_out = all(s[2] == 1 for s in outs.values())
+    first, later = bns[0], bns[1:]
+    if family == "subnormal_input":
+        x0 = fwd["bn_inputs"][first]
+        assert sh[first + ".mu"][0] >= 0.5, (first, sh[first + ".mu"])
+        assert np.all(_plus_zero(st[first + ".sigma2"])) and np.count_nonzero(x0) > 0, first
+        best = max(sh[bn + ".sigma2"][0] for bn in later)
+        print(f"{tag}{family} {kind}: the largest subnormal share of a later sigma2 {best:.2f}")
+        if kind == "dgcnn":   # measured: fc5.bn.sigma2 0.92
+            assert best >= 0.25, best
+        else:
+            # measured: 0.00 for the three EdgeConv tables and for PointNet, where EVERY sigma2 is +0.  A BatchNorm with
+            # sigma2 = +0 multiplies by gamma / sqrt(eps), about 300, and a Float32 variance leaves zero only from values of
+            # 1e-23: an EdgeConv of two or three blocks is too shallow, and PointNet multiplies by x, of order 1e-39, again
+            # after each transform net.  They are held to that picture instead (PointNet's subnormal statistics are its means:
+            # measured 0.124 of all its batch statistics, with stn.bn1, conv_block1.bn and feat.bn2 subnormal in every channel).
+            assert all(np.all(_plus_zero(st[bn + ".sigma2"])) for bn in later)
+            if kind == "pointnet":
+                assert stat_shares(every)[0] >= 0.05 and sh["feat.bn2.mu"][0] >= 0.5, stat_shares(every)
+        assert np.all(np.isfinite(every)) and finite_out
+    elif family in ("subnormal_mid", "decades_edge"):
+        sub = stat_shares(every)[0]
+        print(f"{tag}{family} {kind}: subnormal share of all {every.size} batch statistics {sub:.3f}")
+        # measured: subnormal_mid 0.057 (DGCNN), 0.11 .. 0.19 (EdgeConv), 0.12 (PointNet); decades_edge 0.124 (DGCNN), 0.12
+        # (PointNet), but for EdgeConv 0.063 / 0.073 at [5, 33, 70] (search / given lists), 0.006 / 0.053 at [3, 32, 64, 64] and
+        # 0.009 / 0.042 at [64, 128, 256]: one BatchNorm after the small values, and the search picks neighbours whose
+        # differences cancel.  An EdgeConv under decades_edge is held to one subnormal statistic at the least.
+        assert sub >= 0.05 or (kind == "edgeconv" and family == "decades_edge" and sub > 0), sub
+        assert np.all(np.isfinite(every)) and finite_out
+    elif family == "variance_overflow" or (family == "large" and kind != "pointnet"):
+        assert sh[first + ".sigma2"][2] >= 0.9 and np.all(np.isfinite(st[first + ".mu"])), (first, sh[first + ".sigma2"])
+        assert finite_out, outs
+        best = max(sh[bn + ".sigma2"][1] for bn in convs if bn != first)
+        print(f"{tag}{family} {kind}: the largest share of sigma2 = 0 in a later convolution BatchNorm {best:.2f}")
+        assert best > 0.5, best
+    elif family == "one_point":
+        assert finite_out and np.all(np.isfinite(every)), outs
+        moved, neg_any, pos32 = 0, False, False
+        for bn in convs:
+            raw = fwd["raw_var"][bn]
+            neg, zero, pos = float(np.mean(raw < 0)), float(np.mean(raw == 0)), float(np.mean(raw > 0))
+            print(f"{tag}{family} {kind} {bn}: variance before the clamp negative {neg:.2f}, zero {zero:.2f}, positive {pos:.2f}; "
+                  f"largest magnitude {np.abs(raw).max():.3e}")
+            moved += (neg + pos) >= 0.05
+            neg_any |= neg > 0
+            pos32 |= bool(np.any(st[bn + ".sigma2"] > 0))
+            assert np.all(st[bn + ".sigma2"][raw < 0] == 0) and np.all(_plus_zero(st[bn + ".sigma2"][raw < 0]))
+        assert moved >= min(3, len(convs)), moved   # (two of the EdgeConv tables have two BatchNorms in all)
+        # measured: [64, 128, 256] at N = 64 (full tiles: every chain is 48 equal terms, every fold a power of two of them) has
+        # 0.09 / 0.08 negative and NO positive residue in its two BatchNorms, so it is held to a negative one, as PointNet is;
+        # the other EdgeConv tables and DGCNN have 0.09 .. 0.33 positive in every EdgeConv BatchNorm.
+        full_tiles = kind == "edgeconv" and d["X"].shape[1] % 64 == 0
+        assert neg_any if kind == "pointnet" or full_tiles else pos32, (neg_any, pos32)
+    elif family == "overflow":
+        assert np.any(every == np.inf) and np.any(np.isnan(every)), stat_shares(every)
+        both = np.concatenate([st[first + ".mu"], st[first + ".sigma2"]])   # the first BatchNorm holds all three kinds
+        assert np.any(np.isfinite(both)) and np.any(both == np.inf) and np.any(np.isnan(both)), (first, stat_shares(both))
+        assert all(s[3] == 1 for s in outs.values()), outs
+    else:   # decades, decades_small, negative_gamma, constant_cloud, and large for PointNet: finite, and not empty
+        assert np.all(np.isfinite(every)) and finite_out and all(s[1] > 0 for s in outs.values()), outs
+    if family in ("one_point", "constant_cloud") and kind != "pointnet":
+        for k in [n for n in ("idx", "idx1", "idx2") if n in fwd and not fwd.get("given")]:
+            idx = np.asarray(fwd[k])
+            K = idx.shape[0]   # check_forward's note: every distance is 0, the ranks are the points, rank 0 is dropped
+            assert np.array_equal(idx, np.broadcast_to(np.arange(1, K + 1, dtype=np.int32)[:, None, None], idx.shape)), k
+    return sh
+
+
+def restate_forward_train(net, d, K=None, idx=None, dropout=None):
+    """The training-mode restatement's forward as a dict of the arrays the device returns, with bn_inputs and raw_var."""
+    kind, arg = net
+    if kind == "edgeconv":
+        r = dgcnn_train_ref.edgeconv_forward_train(d["X"], d["P"], arg, K, idx=idx)
+        r["given"] = idx is not None
+        return r
+    if kind == "dgcnn":
+        return dgcnn_train_ref.forward_train(d["X"], d["P"], K, dropout=dropout)
+    return pointnet_train_ref.forward_train(d["X"], d["P"], dropout=dropout)
 
 
 # ---- the restatements, one call per entry point ------------------------------------------------------------------------------

@@ -68,12 +68,19 @@ def dense_sums(v):
     return s1, s2
 
 
-def mean_var(s1, s2, m):
-    """(mu, var) Float32 from the Float64 sums over m values per channel."""
+def raw_var(s1, s2, m):
+    """S2 / m - mu64 mu64 in Float64, the variance before the clamp: on a constant channel pure rounding residue of either sign."""
     with np.errstate(all="ignore"):
         dm = F64(m)
         mu64 = s1 / dm
-        var64 = s2 / dm - mu64 * mu64
+        return s2 / dm - mu64 * mu64
+
+
+def mean_var(s1, s2, m):
+    """(mu, var) Float32 from the Float64 sums over m values per channel."""
+    with np.errstate(all="ignore"):
+        mu64 = s1 / F64(m)
+        var64 = raw_var(s1, s2, m)
         var64 = np.where(var64 < 0, F64(0), var64)  # a NaN stays
         return mu64.astype(F32), var64.astype(F32)
 
@@ -94,7 +101,7 @@ class _Train:
 
     def __init__(self, P, momentum):
         self.P, self.Q, self.momentum = P, dict(P), momentum
-        self.batch_stats, self.running, self.bn_inputs = {}, {}, {}
+        self.batch_stats, self.running, self.bn_inputs, self.raw_var = {}, {}, {}, {}
 
     def bn(self, v, name):
         v = np.asarray(v, F32)
@@ -105,6 +112,7 @@ class _Train:
             s1, s2 = dense_sums(v)
             m = v.shape[0]
         mu, var = mean_var(s1, s2, m)
+        self.raw_var[name] = raw_var(s1, s2, m)
         self.bn_inputs[name] = v
         self.batch_stats[name + ".mu"], self.batch_stats[name + ".sigma2"] = mu, var
         self.running[name + ".mu"], self.running[name + ".sigma2"] = running_update(
@@ -131,7 +139,7 @@ def forward_train(X, P, dropout=None, momentum=0.1):
     """X (3, N, B) with B >= 2, P: name -> array in Flux's shapes (its mu / sigma2 are the running statistics), dropout: None
     or (256, B) multipliers.  Returns every intermediate; ``logits``, ``stn``, ``fstn``, ``pooled`` and ``probs`` laid out as the
     library returns them; ``batch_stats`` and ``running``: name -> (C,) with the ``...bnK.mu`` / ``.sigma2`` names; ``bn_inputs``:
-    BatchNorm name -> what it was given."""
+    BatchNorm name -> what it was given; ``raw_var``: BatchNorm name -> (C,) Float64, the variance before the clamp."""
     X = np.asarray(X, F32)
     assert X.ndim == 3 and X.shape[2] >= 2
     x = np.ascontiguousarray(np.transpose(X, (2, 1, 0)))  # (B, N, 3)
@@ -159,7 +167,7 @@ def forward_train(X, P, dropout=None, momentum=0.1):
     r["pooled"] = np.asfortranarray(pooled.T)
     r["logits"] = np.asfortranarray(logits.T)
     r["probs"] = ref.softmax32(r["logits"])
-    r["batch_stats"], r["running"], r["bn_inputs"] = t.batch_stats, t.running, t.bn_inputs
+    r["batch_stats"], r["running"], r["bn_inputs"], r["raw_var"] = t.batch_stats, t.running, t.bn_inputs, t.raw_var
     assert [k[:-3] for k in t.batch_stats if k.endswith(".mu")] == BN_ORDER  # the BatchNorms ran in the layout's order
     return r
 

@@ -2,7 +2,9 @@
 restatements for every layer table and network that tests/test_gpu_model_draws.py runs (the shares -- subnormal, non-zero,
 finite, NaN -- are printed); under negative gamma and under sigma2 = 0 the three adjoint restatements are still the gradient
 (torch float64 autograd, the siblings' bound: at most 8 x torch-float32's error); and pointnet_ref.fma32 agrees bit for bit with
-the compiled fmaf chain on subnormal and many-decade operands, where the module's own self-check draws exponents in [-3, 3]."""
+the compiled fmaf chain on subnormal and many-decade operands, where the module's own self-check draws exponents in [-3, 3].
+The training-mode families (model_draws.train_families) meet check_train on the training-mode restatements: the shares of
+subnormal, zero, +Inf and NaN batch statistics per BatchNorm are printed, and the variance before the clamp under one_point."""
 import os
 import subprocess
 import sys
@@ -16,6 +18,7 @@ import edgeconv_bwd_ref as bref
 import edgeconv_pgrad_ref as pref
 import edgeconv_ref as ref
 import model_draws as md
+import pointnet_grad_train_ref
 import pointnet_ref
 from pointnet_ref import F32
 
@@ -53,6 +56,71 @@ def test_the_family_meets_its_condition(net, N, B, K, family):
             given = md.restate_forward(net, d, K, idx=md.given_lists(N, B, K))
             md.check_forward(family, net, d, given, tag="given lists: ")
             md.check_grads(family, net, d, *md.restate_grads(net, d, K, given)[:2], tag="given lists: ")
+
+
+TRAIN_PAIRS = [(net, N, B, K, f) for net, N, B, K in NETS for f in md.train_families(net[0])]
+
+
+@pytest.mark.parametrize("net,N,B,K,family", TRAIN_PAIRS, ids=_id)
+def test_the_train_family_meets_its_condition(net, N, B, K, family):
+    """The training-mode restatement's own batch statistics and outputs (check_train prints the shares per BatchNorm), with its
+    own search and (EdgeConv) with given lists; for PointNet the training-mode adjoint's restatement as well, finite outside
+    overflow.  A family that draw() has is draw()'s arrays, bit for bit."""
+    kind = net[0]
+    d = md.draw_train(family, net, N, B)
+    if family in md.families(kind) and not (family == "overflow" and kind == "pointnet"):
+        same = md.draw(family, net, N, B)
+        assert np.array_equal(_bits(d["X"]), _bits(same["X"])) and all(np.array_equal(_bits(d["P"][n]), _bits(same["P"][n])) for n in d["P"])
+        assert (d["g"] is None and same["g"] is None) or np.array_equal(_bits(d["g"]), _bits(same["g"]))
+    again = md.draw_train(family, net, N, B)
+    assert np.array_equal(_bits(d["X"]), _bits(again["X"])) and all(np.array_equal(_bits(d["P"][n]), _bits(again["P"][n])) for n in d["P"])
+    if family == "one_point":
+        assert all(np.array_equal(_bits(d["X"][:, n, b]), _bits(d["X"][:, 0, 0])) for n in range(N) for b in range(B))
+    if family == "constant_cloud":
+        assert all(np.array_equal(_bits(d["X"][:, n, :]), _bits(d["X"][:, 0, :])) for n in range(N))
+        assert not np.array_equal(_bits(d["X"][:, 0, 0]), _bits(d["X"][:, 0, 1]))   # two values per BatchNorm channel
+    fwd = md.restate_forward_train(net, d, K)
+    md.check_train(family, net, d, fwd)
+    if kind == "edgeconv":
+        given = md.restate_forward_train(net, d, K, idx=md.given_lists(N, B, K))
+        md.check_train(family, net, d, given, tag="given lists: ")
+    if kind != "pointnet":
+        return
+    glogits = md.upstream(family, net, N, B)
+    assert glogits.shape == (net[1], B) and np.array_equal(_bits(glogits), _bits(md.upstream(family, net, N, B)))
+    G, gx, mid = pointnet_grad_train_ref.grad_train(d["X"], d["P"], glogits)
+    fam = {f: pointnet_grad_train_ref.family(G, f) for f in pointnet_grad_train_ref.FAMILIES}
+    stats = {f: md.describe(f"{family} pointnet grad_train {f}", a) for f, a in fam.items()}
+    sx = md.describe(f"{family} pointnet grad_train gx", gx)
+    for k, v in mid.items():
+        md.describe(f"{family} pointnet grad_train {k}", v)
+    if family == "overflow":
+        assert sx[3] > 0 and all(s[3] > 0 for s in stats.values()), (sx, stats)
+        return
+    assert sx[2] == 1 and all(s[2] == 1 for s in stats.values()) and all(np.all(np.isfinite(v)) for v in mid.values()), (sx, stats)
+    if family == "variance_overflow":   # sd = +Inf in stn.bn1 and conv_block1.bn: nothing reaches X, the later layers still learn
+        assert not gx.any() and stats["dW"][1] > 0.25, (sx, stats)
+    else:
+        assert stats["dW"][1] > 0, stats
+
+
+@pytest.mark.parametrize("family", md.families("pointnet") + list(md.TRAIN_ONLY))
+def test_the_pointnet_upstream_gradient(family):
+    """upstream(): seeded, Float32, finite and non-zero; over many decades under decades, small (subnormal values among them) on
+    the even clouds alone under decades_small and decades_edge, unit scale elsewhere."""
+    N, B, nc = md.POINTNET
+    g = md.upstream(family, ("pointnet", nc), N, B)
+    assert g.shape == (nc, B) and g.dtype == F32 and np.all(np.isfinite(g)) and np.isfortran(g)
+    assert np.array_equal(_bits(g), _bits(md.upstream(family, ("pointnet", nc), N, B)))
+    mag = np.abs(g.astype(np.float64))
+    if family == "decades":
+        assert mag.max() / mag[mag > 0].min() > 1e6
+    elif family in ("decades_small", "decades_edge"):
+        assert mag[:, 0::2].max() < 1e-28 and mag[:, 1::2].max() > 0.1 and np.count_nonzero(g[:, 0::2]) > 0
+    else:
+        assert 0.1 < mag.max() < 10 and np.count_nonzero(g) == g.size
+    other = [f for f in md.families("pointnet") if f != family][0]
+    assert not np.array_equal(_bits(g), _bits(md.upstream(other, ("pointnet", nc), N, B)))
 
 
 def test_constant_cloud_gives_everything_to_the_first_k_and_point_0():
