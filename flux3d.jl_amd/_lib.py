@@ -144,6 +144,8 @@ SIGNATURES = {
     "fx3d_edgeconv_bwd": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_edgeconv_grad_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_edgeconv_grad": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, sz, vp],
+    "fx3d_edgeconv_grad_train_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_edgeconv_grad_train": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_sample_points_explicit": [vp, c_i32, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp],
     "fx3d_sample_points_workspace_bytes": [c_i32, c_i32, C.POINTER(sz)],
     "fx3d_sample_points": [vp, c_i32, vp, c_i32, vp, c_i32, c_i32, c_f64, c_u64, vp, vp, vp, vp,

@@ -2,6 +2,8 @@
 // returns gx) share: the chain per neighbour rank k, step by step, the kernel arguments of the chain, and on the host the
 // workspace prefix and everything an entry point does between its NULL check and its launch.  Both kernels call the steps below
 // in the order of their header comments, so the two compute gx with the same instructions in the same order.
+// The training-mode adjoint (edgeconv_grad_train.hip) calls the same steps in their training mode (TrainBn below), its closing pass
+// through the parameter adjoint's kernel (edgeconv_pgrad_net.h).
 //
 // A tile is 32 NH points of one cloud in LDS images of row stride LD; a lane owns one channel (j of the wave's slab of 32) and
 // the 16 rows mfma_row(r, h) of each 32-point half; wave w owns the slabs w, w + 4, ... of every layer, NS of them at most of the
@@ -37,6 +39,38 @@ struct NoSink {  // for last_compare's sink(sl, d) and back_layer's sink(l, sl, 
 };
 
 __device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+
+// The mode of the steps that cross a BatchNorm (last_compare, hidden_bwd, back_layer).  EvalBn: test mode, mu and var constants, what
+// goes below a BatchNorm is (d gamma) / sd row by row.  TrainBn ("EdgeConv training-mode adjoint", edgeconv_grad_train.hip): the
+// BatchNorms at the batch statistics (the caller puts them where a.c[].bn.m / .v point), every BatchNorm a cut:
+//   gy = the gradient at the BatchNorm's output (gout where chosen; below, d where the relu let through), xh = ((z + b) - mu) / sd of
+//   EVERY row, the forward's bits: of layer L from the compare's accumulators, of a hidden layer from one more forward slab on the
+//   image below it, which the parameter adjoint's LDS plan keeps (the lane that owns channel c of d owns c of the slab, same rows);
+//   gv = (((gy - mb) - (xh mg)) gamma) / sd takes dz's place, +0 in the rows beyond the cloud's last point;
+//   means: Float32(dbeta64 / m), then Float32(dgamma64 / m) per layer, in the statistics buffer's layout, finished for the layers
+//   above `stop`; stop: the layer whose (gy, gy xh) sums this pass takes -- the walk ends there and nothing is written for it --
+//   or 0: the closing pass.
+// A training-mode sink is sink(sl, gy, xh, gv): at the stop layer gy and xh as they enter the sums (+0 in the rows that add
+// nothing: beyond the cloud, and at layer L every row but the chosen one), gv elsewhere.  Only the images of edgeconv_pgrad.hip's
+// plan (32 rows, image l - 2 alive while layer l walks back) serve this mode.
+struct EvalBn {
+    static constexpr bool kTrain = false;
+};
+struct TrainBn {
+    static constexpr bool kTrain = true;
+    const float *means;
+    int stop, nvalid;
+};
+// where layer l's (1-based) block of a buffer in the statistics layout begins: 2 (c1 + .. + c_{l-1})
+__device__ __forceinline__ int stat_offset(const int (&w)[kMaxLayers + 1], int l) {
+    return 2 * ((l > 1 ? w[1] : 0) + (l > 2 ? w[2] : 0) + (l > 3 ? w[3] : 0));
+}
+// gv of one element; valid: the row is one of the cloud's
+__device__ __forceinline__ float train_gv(float gy, float xh, float mb, float mg, float g, float sd, bool valid) {
+    float t = gy - mb;
+    t = t - (xh * mg);
+    return valid ? (t * g) / sd : 0.0f;
+}
 
 // gather_centre and gather_diff in one pass, for a tile of T points: both halves are written with every k
 template <int T>
@@ -102,9 +136,11 @@ __device__ __forceinline__ const float *hidden_fwd_chain(const AdjointArgs &a, f
 // up: the upstream values.  SCALED (the input adjoint): (gout gamma_L) / sd_L, computed once per tile, is what dz_L is where k is
 // chosen.  Else (the parameter adjoint, which needs d_L itself and has no registers for both): gout, scaled here.  dz0:
 // (+0 gamma_L) / sd_L, what dz_L is elsewhere.  The sink gets the slab's `up` where chosen, +0 elsewhere: d_L unless SCALED.
-template <int LD, int NH, int NS, bool SCALED, class Sink>
+// Mode::kTrain: `up` is gout (SCALED and dz0 have no part), moff: layer L's stat_offset; stopped: L is the stop layer (else gv_L into dzl).
+template <int LD, int NH, int NS, bool SCALED, class Sink, class Mode = EvalBn>
 __device__ __forceinline__ void last_compare(const float *src, float *dzl, const Conv &cl, int cinl, int cout, int wave, int h, int j,
-                                             f32x16 (&tgt)[NS][NH], const f32x16 (&up)[NS][NH], const float (&dz0)[NS], Sink &&sink) {
+                                             f32x16 (&tgt)[NS][NH], const f32x16 (&up)[NS][NH], const float (&dz0)[NS], Sink &&sink,
+                                             const Mode &m = Mode{}, int moff = 0, bool stopped = false) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const int sl = wave + s * kWaves;
@@ -115,26 +151,56 @@ __device__ __forceinline__ void last_compare(const float *src, float *dzl, const
         for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
         mfma_slab_rt<LD, NH>(src, cl.W + (size_t)cinl * oc, cinl, h, j, acc);
         const float bi = cl.b[oc], g = cl.bn.g[oc], be = cl.bn.b[oc], mu = cl.bn.m[oc], sd = sqrtf(cl.bn.v[oc] + kBnEps);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int t = 0; t < NH; ++t) {
-                const bool first = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd) == tgt[s][t][r];
-                const float u = up[s][t][r];
-                if (o < cout) dzl[(t * 32 + mfma_row(r, h)) * LD + o] = first ? (SCALED ? u : (u * g) / sd) : dz0[s];
-                d[t][r] = first ? u : 0.0f;
-                tgt[s][t][r] = first ? quiet_nan() : tgt[s][t][r];
+        if constexpr (Mode::kTrain) {
+            const bool stop = stopped;
+            float mb = 0.0f, mg = 0.0f;
+            if (!stop) {
+                mb = m.means[moff + oc];
+                mg = m.means[moff + cout + oc];
             }
-        sink(sl, d);
+            f32x16 xs[NH], gv[NH];
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    const float xh = ((acc[t][r] + bi) - mu) / sd;  // epilogue<kBnRelu>'s own operations, xh kept
+                    const bool first = relu((g * xh) + be) == tgt[s][t][r];
+                    const float gy = first ? up[s][t][r] : 0.0f;
+                    tgt[s][t][r] = first ? quiet_nan() : tgt[s][t][r];
+                    d[t][r] = gy;
+                    xs[t][r] = first ? xh : 0.0f;
+                    gv[t][r] = 0.0f;
+                    if (!stop) {
+                        gv[t][r] = train_gv(gy, xh, mb, mg, g, sd, t * 32 + mfma_row(r, h) < m.nvalid);
+                        if (o < cout) dzl[(t * 32 + mfma_row(r, h)) * LD + o] = gv[t][r];
+                    }
+                }
+            sink(sl, d, xs, gv);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    const bool first = epilogue<kBnRelu>(acc[t][r], bi, g, be, mu, sd) == tgt[s][t][r];
+                    const float u = up[s][t][r];
+                    if (o < cout) dzl[(t * 32 + mfma_row(r, h)) * LD + o] = first ? (SCALED ? u : (u * g) / sd) : dz0[s];
+                    d[t][r] = first ? u : 0.0f;
+                    tgt[s][t][r] = first ? quiet_nan() : tgt[s][t][r];
+                }
+            sink(sl, d);
+        }
     }
 }
 
 // one hidden layer backward: d[p][c] = the chain over o < cout of dz[p][o] Wt[o + cout c] for c < cin, then in a's place
 // dz'[p][c] = ((a[p][c] > 0 ? d : +0) gamma[c]) / sd[c] with the BatchNorm of the layer that made a
 // sink(sl, d): d before gamma and sd; what the lanes beyond cin hold there is not d.
-template <int LD, int NH, class Sink>
+// Mode::kTrain: fw, ain, cprev: the convolution that made a, its input image and width, for xh; moff: its layer's stat_offset;
+// stopped: it is the stop layer (a stays as it is).
+template <int LD, int NH, class Sink, class Mode = EvalBn>
 __device__ __forceinline__ void hidden_bwd(const float *dz, float *a, int cout, int cin, const float *__restrict__ wt, const Bn &bn,
-                                           Sink &&sink) {
+                                           Sink &&sink, const Mode &m = Mode{}, const Conv *fw = nullptr, const float *ain = nullptr,
+                                           int cprev = 0, int moff = 0, bool stopped = false) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
     for (int sl = wave; sl * 32 < cin; sl += kWaves) {
         const int c = sl * 32 + j, cc = min(c, cin - 1);
@@ -143,18 +209,48 @@ __device__ __forceinline__ void hidden_bwd(const float *dz, float *a, int cout, 
         for (int t = 0; t < NH; ++t) acc[t] = f32x16{0};
         mfma_slab_rt<LD, NH>(dz, wt + (size_t)cout * cc, cout, h, j, acc);
         const float g = bn.g[cc], sd = sqrtf(bn.v[cc] + kBnEps);
-        if (c < cin) {
+        if constexpr (Mode::kTrain) {
+            f32x16 v[NH], xs[NH], gv[NH];
+#pragma unroll
+            for (int t = 0; t < NH; ++t) v[t] = xs[t] = gv[t] = f32x16{0};
+            mfma_slab_rt<LD, NH>(ain, fw->W + (size_t)cprev * cc, cprev, h, j, v);  // z of the layer that made a: the forward's slab
+            const float bi = fw->b[cc], mu = bn.m[cc];
+            float mb = 0.0f, mg = 0.0f;
+            if (!stopped) {
+                mb = m.means[moff + cc];
+                mg = m.means[moff + cin + cc];
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r)
 #pragma unroll
                 for (int t = 0; t < NH; ++t) {
                     float *e = a + (t * 32 + mfma_row(r, h)) * LD + c;
-                    const float d = *e > 0.0f ? acc[t][r] : 0.0f;
-                    acc[t][r] = d;
-                    *e = (d * g) / sd;
+                    const bool valid = t * 32 + mfma_row(r, h) < m.nvalid;
+                    const float al = c < cin ? *e : 0.0f;
+                    const float gy = al > 0.0f ? acc[t][r] : 0.0f;
+                    const float xh = ((v[t][r] + bi) - mu) / sd;
+                    acc[t][r] = valid ? gy : 0.0f;
+                    xs[t][r] = valid ? xh : 0.0f;
+                    if (!stopped) {
+                        gv[t][r] = train_gv(gy, xh, mb, mg, g, sd, valid);
+                        if (c < cin) *e = gv[t][r];
+                    }
                 }
+            sink(sl, acc, xs, gv);
+        } else {
+            if (c < cin) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+#pragma unroll
+                    for (int t = 0; t < NH; ++t) {
+                        float *e = a + (t * 32 + mfma_row(r, h)) * LD + c;
+                        const float d = *e > 0.0f ? acc[t][r] : 0.0f;
+                        acc[t][r] = d;
+                        *e = (d * g) / sd;
+                    }
+            }
+            sink(sl, acc);
         }
-        sink(sl, acc);
     }
 }
 
@@ -162,15 +258,25 @@ __device__ __forceinline__ void hidden_bwd(const float *dz, float *a, int cout, 
 // dzl), d_{l-1} over ALL o of dz_l with Wt_l, masked by a_{l-1} > 0, to sink(l, sl, d), then times gamma_{l-1}, divided by
 // sd_{l-1}, into a_{l-1}'s place in img[l-1]; then a barrier.  The layer by wave-uniform selects among the kernel arguments,
 // which fold where the caller's loop is unrolled (the parameter adjoint's, whose sink needs l as a constant).
-template <int LD, int NH, class Sink>
-__device__ __forceinline__ void back_layer(const AdjointArgs &a, float *lds, const float *dzl, int L, int l, Sink &&sink) {
+// Mode::kTrain: layer l - 1 is cut at its BatchNorm (hidden_bwd); sink(l, sl, gy, xh, gv).
+template <int LD, int NH, class Sink, class Mode = EvalBn>
+__device__ __forceinline__ void back_layer(const AdjointArgs &a, float *lds, const float *dzl, int L, int l, Sink &&sink,
+                                           const Mode &m = Mode{}) {
     constexpr int IMG = 32 * NH * LD;
     const float *dz = l == L ? dzl : lds + l * IMG;
     const int co = l == 2 ? a.w[2] : l == 3 ? a.w[3] : a.w[4];
     const int ci = l == 2 ? a.w[1] : l == 3 ? a.w[2] : a.w[3];
     const float *wt = l == 2 ? a.wt[1] : l == 3 ? a.wt[2] : a.wt[3];
     const Bn bn = l == 2 ? a.c[0].bn : l == 3 ? a.c[1].bn : a.c[2].bn;
-    hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn, [&](int sl, const f32x16(&d)[NH]) { sink(l, sl, d); });
+    if constexpr (Mode::kTrain) {
+        const Conv fw = l == 2 ? a.c[0] : l == 3 ? a.c[1] : a.c[2];
+        const int cprev = l == 2 ? 2 * a.w[0] : l == 3 ? a.w[1] : a.w[2];
+        hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn,
+                           [&](int sl, const f32x16(&gy)[NH], const f32x16(&xh)[NH], const f32x16(&gv)[NH]) { sink(l, sl, gy, xh, gv); },
+                           m, &fw, lds + (l - 2) * IMG, cprev, stat_offset(a.w, l - 1), m.stop == l - 1);
+    } else {
+        hidden_bwd<LD, NH>(dz, lds + (l - 1) * IMG, co, ci, wt, bn, [&](int sl, const f32x16(&d)[NH]) { sink(l, sl, d); });
+    }
     __syncthreads();
 }
 
@@ -242,11 +348,12 @@ fx3d_status edgeconv_adjoint_plan(const char *fn, const int32_t *layers, int nla
 // What an adjoint entry `fn` does between its plan (w; need: its whole workspace, what `size_fn` reports) and its launch: the
 // size and alignment refusals, the chain's arguments a from the entry's own, the forward and / or the search where the caller
 // gives no out / idx (edgeconv_run and fx3d_knn_ws, as fx3d_edgeconv_forward runs them: the search is deterministic), and the
-// transposed weights.
+// transposed weights.  stats (the training-mode adjoint): the batch statistics, in the layout of "DGCNN / EdgeConv training-mode
+// forward"; the chain's BatchNorms then read their mean and variance there, and so does the forward where the caller gives no out.
 fx3d_status edgeconv_adjoint_prepare(const char *fn, const char *size_fn, const AdjointWs &w, size_t need, const float *params_dev,
                                      const int32_t *layers, int nlayers, int K, const float *x, int N, int B, const int32_t *idx,
                                      const float *out, const float *gout, float *gx, void *ws, size_t ws_bytes, fx3d_stream_t s,
-                                     AdjointArgs *a);
+                                     AdjointArgs *a, const float *stats = nullptr);
 
 }  // namespace mlp
 }  // namespace fx3d

@@ -27,6 +27,7 @@
 //   A slab beyond a width's last channel: its lanes read the last channel's parameters, run the wave's MFMAs and write nothing.
 //   Rows beyond the cloud's last point are zeros with tgt = NaN: computed, never written.
 #include "edgeconv_adjoint.h"
+#include "edgeconv_net.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
@@ -178,7 +179,7 @@ fx3d_status edgeconv_adjoint_plan(const char *fn, const int32_t *layers, int nla
 fx3d_status edgeconv_adjoint_prepare(const char *fn, const char *size_fn, const AdjointWs &w, size_t need, const float *params_dev,
                                      const int32_t *layers, int nlayers, int K, const float *x, int N, int B, const int32_t *idx,
                                      const float *out, const float *gout, float *gx, void *ws, size_t ws_bytes, fx3d_stream_t s,
-                                     AdjointArgs *a) {
+                                     AdjointArgs *a, const float *stats) {
     FX3D_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, %s says %zu", fn, ws_bytes, size_fn, need);
     FX3D_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: ws must be 256-byte aligned", fn);
     char *wsb = static_cast<char *>(ws);
@@ -190,7 +191,14 @@ fx3d_status edgeconv_adjoint_prepare(const char *fn, const char *size_fn, const 
     int32_t *ws_idx = reinterpret_cast<int32_t *>(wsb + w.idx);
     float *ws_out = reinterpret_cast<float *>(wsb + w.out);
     fx3d_status r = FX3D_OK;
-    if (!out) {
+    if (stats) {  // edge_pass puts the statistics in the BatchNorms' place: the closing pass of the training-mode forward
+        const int32_t *used = nullptr;
+        if ((r = edgeconv_neighbours(x, layers[0], N, B, K, idx, ws_idx, wsb + w.fwd, s, &used)) != FX3D_OK) return r;
+        const EdgePass p = edge_pass(params_dev, stats, layers, nlayers, K, x, N, used, ws_out);
+        for (int i = 0; i + 1 < nlayers; ++i) a->c[i].bn = p.a.c[i].bn;
+        if (!out && (r = edgeconv_launch(p, B, as_stream(s), "edgeconv_grad_train_forward")) != FX3D_OK) return r;
+        idx = used;
+    } else if (!out) {
         if ((r = edgeconv_run(params_dev, layers, nlayers, K, x, N, B, idx, ws_out, idx ? nullptr : ws_idx, wsb + w.fwd, s, "edgeconv")) != FX3D_OK) return r;
     } else if (!idx) {
         if ((r = fx3d_knn_ws(x, N, x, N, B, layers[0], K, 1, ws_idx, nullptr, wsb + w.fwd, w.fwd_bytes, s)) != FX3D_OK) return r;

@@ -69,15 +69,6 @@ __device__ __forceinline__ void finish_bn(const BnOut &o, int c, double s1, doub
     o.mg[c] = (float)(s2 / dm);
 }
 
-struct PairSum {  // TileSum of pointnet_train.hip for (gy, gy xh); the product of two Float32 is exact in Float64
-    double s1 = 0.0, s2 = 0.0;
-    __device__ __forceinline__ void add(float gy, float xh) {
-        const double d = (double)gy;
-        s1 = s1 + d;
-        s2 = s2 + d * (double)xh;
-    }
-};
-
 // ---- the head ----------------------------------------------------------------------------------------------------------------------
 struct HeadGtArgs : HeadArgs {  // the forward's head of the round at the batch statistics
     const int32_t *tfirst;  // (1024, ntiles, B)

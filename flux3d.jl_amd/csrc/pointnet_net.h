@@ -407,6 +407,15 @@ struct TileSum {
         s2 = s2 + d * d;  // the product of two Float32 is exact in Float64
     }
 };
+// TileSum for (gy, gy xh), the sums of a training-mode adjoint's dbeta and dgamma (pointnet_grad_train.hip, edgeconv_grad_train.hip)
+struct PairSum {
+    double s1 = 0.0, s2 = 0.0;
+    __device__ __forceinline__ void add(float gy, float xh) {
+        const double d = (double)gy;
+        s1 = s1 + d;
+        s2 = s2 + d * (double)xh;  // the product of two Float32 is exact in Float64
+    }
+};
 __device__ __forceinline__ void store_tile_sum(double *sums, int o, double s1, double s2) {
     sums[2 * o] = s1;
     sums[2 * o + 1] = s2;

@@ -1964,5 +1964,32 @@ function edgeconv_gradient(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{F
     return gflat, gx
 end
 
+# The gradients of sum(gout .* edgeconv_forward_train(m, X).out) with respect to m's parameters and to X (include/flux3d_hip.h
+# "EdgeConv training-mode adjoint"): the function that is trained, the gradient going through the batch mean and variance.
+# batch_stats: what edgeconv_forward_train returned for the same (m, X, idx); idx, out: its lists and result, either may be left
+# out and is then computed again.  Returns (gflat, gx) as edgeconv_gradient does; the mu / sigma2 slots are zero.
+function edgeconv_grad_train(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray{Float32,3}, batch_stats::HipArray{Float32,1};
+                             idx::Union{Nothing,HipArray{Int32,3}} = nothing, out::Union{Nothing,HipArray{Float32,3}} = nothing,
+                             input_grad::Bool = true)
+    layers, nl, F, N, B, K = _edgeconv_setup(m, X, idx; gout = gout, out = out)
+    length(batch_stats) == edgeconv_stat_count(m) ||
+        throw(ArgumentError("batch_stats must hold $(edgeconv_stat_count(m)) floats, got $(length(batch_stats))"))
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_edgeconv_grad_train_workspace_bytes(layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32, Int32(N)::Int32,
+                                                              Int32(B)::Int32, nb::Ref{Csize_t})::Int32)
+    params = edgeconv_params(m)
+    pd = hip(params)
+    ws = workspace(nb[])
+    gflat = HipArray{Float32}(undef, length(params))
+    gx = input_grad ? HipArray{Float32}(undef, F, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_edgeconv_grad_train(pd.ptr::Ptr{Cvoid}, layers::Ptr{Int32}, Int32(nl)::Int32, Int32(K)::Int32,
+                                              X.ptr::Ptr{Cvoid}, Int32(N)::Int32, Int32(B)::Int32, opt(idx)::Ptr{Cvoid},
+                                              opt(out)::Ptr{Cvoid}, batch_stats.ptr::Ptr{Cvoid}, gout.ptr::Ptr{Cvoid},
+                                              gflat.ptr::Ptr{Cvoid}, opt(gx)::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                              DEFAULT_STREAM::Stream)::Int32)
+    return gflat, gx
+end
+
 
 end # module

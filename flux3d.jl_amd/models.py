@@ -9,7 +9,8 @@ whole network with respect to every parameter and to the input points (``DGCNN.g
 ``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode.  PointNet also has its
 training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_train, "PointNet training-mode forward") and that
 forward's gradients (``PointNet.grad_train`` over fx3d_pointnet_grad_train, "PointNet training-mode adjoint"); DGCNN and EdgeConv have their training-mode forwards (``DGCNN.forward_train`` over
-fx3d_dgcnn_forward_train, ``EdgeConv.forward_train`` over fx3d_edgeconv_forward_train, "DGCNN / EdgeConv training-mode forward")."""
+fx3d_dgcnn_forward_train, ``EdgeConv.forward_train`` over fx3d_edgeconv_forward_train, "DGCNN / EdgeConv training-mode forward"), and EdgeConv that
+forward's gradients (``EdgeConv.grad_train`` over fx3d_edgeconv_grad_train, "EdgeConv training-mode adjoint")."""
 import ctypes as C
 
 import numpy as np
@@ -928,4 +929,73 @@ class EdgeConv(_Model):
         bit for bit, or ``None`` with ``input_grad=False``.  ``X``, ``gout``, ``idx`` and ``out`` as in :meth:`input_grad`;
         everything lives where ``X`` lives."""
         gp, gx, on_dev = self._grad_call(X, gout, idx, out, input_grad)
+        return self._grad_views(gp, on_dev), (gx if on_dev or gx is None else gx.to_host())
+
+    def _train_grad_call(self, X, gout, idx, fwd, input_grad):
+        """fx3d_edgeconv_grad_train after the checks of :meth:`input_grad` and of ``fwd``: (the flat gradient, gx or None) on the
+        device, and whether ``X`` lives there.  Every refusal comes before any device work."""
+        F, K, f32 = self.layers[0], self.K, np.float32
+        pts, N, B, on_dev, layers, nl = self._head(X)
+        nb = _lib.query_bytes("fx3d_edgeconv_grad_train_workspace_bytes", layers, nl, K, N, B)
+        g = self._like_out(gout, "gout", N, B, on_dev)
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        names = [bn + f for bn, *_ in slots for f in (".mu", ".sigma2")]
+        if fwd is not None:
+            if not isinstance(fwd, dict) or any(k not in fwd for k in ("out", "idx", "batch_stats")):
+                raise TypeError("fwd must be the dict of forward_train(..., intermediates=True)")
+            named = fwd["batch_stats"]
+            if [k for k in named] != names:
+                raise ValueError(f"fwd['batch_stats'] must hold mu and sigma2 of the {len(slots)} BatchNorms in forward order")
+            for (bn, C, _, _) in slots:
+                for f in (".mu", ".sigma2"):
+                    v = named[bn + f]
+                    if is_device(v) != on_dev:
+                        raise TypeError("fwd must live where X lives")
+                    if tuple(v.shape) != (C,) or v.dtype != f32:
+                        raise ValueError(f"fwd['batch_stats'][{bn + f!r}] must be Float32 ({C},), got {v.dtype} {tuple(v.shape)}")
+            o = self._like_out(fwd["out"], "fwd['out']", N, B, on_dev)
+            given = self._neighbours(fwd["idx"] if idx is None else idx, N, B)
+        else:
+            given = None if idx is None else self._neighbours(idx, N, B)
+        x = self._on_device(pts, N, B, on_dev, F)
+        stream = current_stream().handle
+        if fwd is None:
+            made = self.forward_train(x, idx=given, intermediates=True)
+            o, given, named = made["out"], made["idx"], made["batch_stats"]
+        if not on_dev:
+            g = DeviceArray.from_host(g)
+            if fwd is not None:
+                o = DeviceArray.from_host(o)
+        # the BatchNorms' statistics (views of forward_train's buffer, or the caller's arrays) as one buffer in the layout's order
+        if on_dev or fwd is None:
+            stats = DeviceArray.empty((nstat,), f32)
+            for bn, C, at, _ in slots:
+                for fld, off in ((".mu", at), (".sigma2", at + C)):
+                    _lib.call("fx3d_memcpy_d2d", stats.ptr + 4 * off, named[bn + fld].ptr, 4 * C, stream)
+        else:
+            stats = DeviceArray.from_host(np.concatenate([np.asarray(named[k], f32) for k in names]))
+        gp = DeviceArray.empty((self.param_count,), f32)
+        gx = DeviceArray.empty((F, N, B), f32) if input_grad else None
+        ws = workspace(nb, tag="edgeconv_grad_train")
+        _lib.call("fx3d_edgeconv_grad_train", self._params_dev().ptr, layers, nl, K, x.ptr, N, B, given.ptr, o.ptr, stats.ptr, g.ptr,
+                  gp.ptr, gx.ptr if gx is not None else None, ws.ptr, ws.nbytes, stream)
+        return gp, gx, on_dev
+
+    def flat_grad_train(self, X, gout, idx=None, fwd=None, input_grad=True):
+        """:meth:`grad_train` with the parameter gradients as one flat buffer, as :meth:`flat_grad`."""
+        gp, gx, on_dev = self._train_grad_call(X, gout, idx, fwd, input_grad)
+        if not on_dev:
+            gp, gx = gp.to_host(), (None if gx is None else gx.to_host())
+        return gp, gx
+
+    def grad_train(self, X, gout, idx=None, fwd=None, input_grad=True):
+        """:meth:`grad` for the layer in TRAINING mode: ``(grads, gx)``, the gradients of ``sum(gout * forward_train(X))`` with
+        every BatchNorm's mean and variance functions of the batch: include/flux3d_hip.h "EdgeConv training-mode adjoint".  The
+        neighbours are constants.  ``fwd``: the dict of ``forward_train(X, idx, intermediates=True)`` for the same ``X`` -- its
+        ``out``, ``idx`` (unless ``idx`` is given here) and ``batch_stats`` are used; without it :meth:`forward_train` runs first,
+        on ``idx`` if given.  ``grads`` and ``gx`` as :meth:`grad` returns them (the ``mu`` / ``sigma2`` entries are zero: the
+        running statistics do not enter this forward); ``gx`` is ``None`` with ``input_grad=False``.  Everything lives where
+        ``X`` lives."""
+        gp, gx, on_dev = self._train_grad_call(X, gout, idx, fwd, input_grad)
         return self._grad_views(gp, on_dev), (gx if on_dev or gx is None else gx.to_host())

@@ -1270,6 +1270,56 @@ FX3D_API fx3d_status fx3d_dgcnn_forward_train(const float *params_dev, int32_t n
                                               float *logits, int32_t *idx1, float *x1, int32_t *idx2, float *x2, float *pooled,
                                               float *batch_stats, float *running, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- EdgeConv training-mode adjoint: the gradients of fx3d_edgeconv_forward_train with respect to its parameters, and to X ------
+ * gparams = d sum(gout . out) / d params for out = fx3d_edgeconv_forward_train(x): the function that is trained, every BatchNorm
+ * at the statistics of the batch, the gradient going through mu and var.  gparams and gx as in "EdgeConv parameter adjoint" (the
+ * layout of params_dev; gx (F,N,B) optional); the mu / var slots of gparams are written as +0: the running statistics do not
+ * enter this forward.  The neighbours are constants.
+ * batch_stats (required): fx3d_edgeconv_stat_count floats in the forward's layout, what fx3d_edgeconv_forward_train returned for the
+ * same (params_dev, x, idx).  idx == NULL: the search runs as in the forward.  out == NULL: the forward's closing pass
+ * (fx3d_edgeconv_forward's kernel at batch_stats) runs first, into the workspace.
+ * Notation of "EdgeConv parameter adjoint"; mu_l, var_l are batch_stats', sd_l = sqrtf(var_l + 1f-5), m = K N B.  Every operation
+ * is rounded to Float32 and nothing is fused unless it says fmaf.
+ * Forward quantities, for every edge row (b, n, k) and layer l, the forward's bits (its closing pass is fx3d_edgeconv_forward's
+ * kernel at batch_stats):
+ *   v_l = z_l + b_l;   xh_l = (v_l - mu_l) / sd_l;   a_l = relu((gamma_l xh_l) + beta_l).
+ * The maximum:  gy_L[k,n,o] = gout[o,n] at the smallest k with a_L[k,n,o] == out[o,n], where out[o,n] > 0, else +0 -- verbatim
+ *   "EdgeConv input adjoint", including what it says about NaN and non-positive out.
+ * Per layer, l = L .. 1:
+ *   dbeta64_l[o] = sum (double)gy_l,  dgamma64_l[o] = sum (double)gy_l (double)xh_l (the product of two Float32 is exact), Float64
+ *     sums in the order below, every chain from +0.0 with one rounding per addition.  Rows beyond a cloud's last point add nothing.
+ *     At layer L a row that is not the chosen one adds nothing (a select: its xh does not enter).  At a hidden layer every valid row
+ *     takes part, with gy = +0 where a_l is not positive.  gparams gets dbeta_l = Float32(dbeta64_l), dgamma_l = Float32(dgamma64_l).
+ *   mb = Float32(dbeta64 / m), mg = Float32(dgamma64 / m), Float64 divisions.
+ *   t = gy - mb;  t = t - (xh mg);  gv_l = (t gamma_l) / sd_l, for EVERY row of the cloud, those the relu zeroed too;  gv of a row
+ *     beyond a cloud's last point is +0.
+ *   dW_l[c,o] = the chain acc = fmaf(a_{l-1}[c], gv_l[o], acc);  db_l[o] = the sum of gv_l[o] -- in exactly the orders "EdgeConv
+ *     parameter adjoint" gives H_l and h_l (chunks of FX3D_EDGECONV_GRAD_CHUNK, tiles, k, the permutation, the two h chains, then the
+ *     chunks as one chain over (b, chunk)), and written as they come out of that sum.  (Every bias sits under a batch-statistic
+ *     BatchNorm: db is the rounding noise of a sum whose exact value is 0.)
+ *   for l >= 2:  d_{l-1}[c] = one fmaf chain from +0.0f over ALL o ascending of gv_l[o] W_l[c,o];  gy_{l-1} = a_{l-1} > 0 ? d_{l-1} : +0.
+ * gx from d_0 (the chain of gv_1 with W_1) as "EdgeConv input adjoint" forms it: S over k ascending, then S[f] - S[F+f].
+ * Order of the Float64 sums.  It depends on (layers, K, N, B) alone.  A half-tile is 32 consecutive points of one cloud (half-tile
+ *   t: points 32 t .. 32 t + 31).  Per (channel, half-tile, cloud) two chains, selected by bit 2 of the point's position p in the
+ *   half-tile; each runs over the neighbour rank k ascending and, within a k, over its 16 rows in ascending p; the half-tile's
+ *   value is chain(0) + chain(1).  The values t = half-tile + nhalf b, nhalf = ceil(N / 32), are folded as "PointNet training-mode
+ *   forward" folds tile sums: FX3D_POINTNET_STAT_GROUPS chains, chain g over t = g, g + 32, ... ascending, added in ascending g.
+ * gparams and gx are bit-identical to the restatement tests/edgeconv_grad_train_ref.py and from run to run; no atomics, no
+ * (K N, ., B) array in memory.
+ * Envelope, refusals, their order, status codes and messages are fx3d_edgeconv_grad's, with batch_stats among the required
+ * pointers (params_dev, layers, x, batch_stats, gout, gparams, ws); B = 1 is allowed, as in the forward.  Every refusal comes
+ * before any device work.  Launches on `s` only (the search and / or the closing forward where idx / out are NULL, the weight
+ * transpose, per layer a sums pass and a finishing kernel, the closing pass, the chain over the chunks), no host synchronisation,
+ * no host memory other than `layers` read (graph-capturable).
+ * ws: fx3d_edgeconv_grad_train_workspace_bytes -- the input adjoint's, one partial of param_count floats per chunk and cloud, the
+ * Float64 half-tile sums (2,C,nhalf,B) of the widest layer, and the means. */
+FX3D_API fx3d_status fx3d_edgeconv_grad_train_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N,
+                                                              int32_t B, size_t *bytes);
+FX3D_API fx3d_status fx3d_edgeconv_grad_train(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
+                                              const float *x, int32_t N, int32_t B, const int32_t *idx, const float *out,
+                                              const float *batch_stats, const float *gout, float *gparams, float *gx, void *ws,
+                                              size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
