@@ -17,6 +17,19 @@
  *     builds CartesianIndex), shaped (N,B).
  *   - pointers named *_dev / documented "device" are device pointers (from fx3d_malloc or any
  *     HIP allocation of the same process, e.g. a torch tensor's data_ptr); "host" are host.
+ *   - alignment: every array argument needs the alignment of its ELEMENT TYPE and no more -- 4 bytes for const float * /
+ *     int32_t * / uint32_t *, 8 for int64_t * / uint64_t * / double *, 1 for uint8_t * -- so a batch shard of an odd-N cloud
+ *     (x + 3 N b), a column range of a packed mesh (v + 3 off), a slice of a flat parameter or gradient buffer (p + at), a Julia
+ *     view or a torch slice are valid arguments as they are.  Results do not depend on the pointers' low bits: where a kernel has
+ *     a 16-byte path it is chosen from the address and its scalar twin gives the same bits (DESIGN.md 2.1 lists every such site
+ *     and the test that holds it).  The exceptions, each refused before any launch:
+ *       workspaces (`ws`)            scratch is laid out from the pointer as given: pass fx3d_malloc's alignment (256 bytes).
+ *                                    The model entry points check it -- 16 bytes for fx3d_pointnet_forward / _forward_train,
+ *                                    256 bytes for the others -- and answer FX3D_ERR_INVALID_ARG; fx3d_knn_ws takes a
+ *                                    workspace that is not 256-byte aligned as no workspace (it then is fx3d_knn);
+ *       x1 of fx3d_dgcnn_forward /
+ *       fx3d_dgcnn_forward_train     16 bytes: FX3D_ERR_INVALID_ARG.
+ *     (fx3d_knn_ws builds its pre-pass image only for 16-byte aligned clouds; others run the kernels of fx3d_knn: same results.)
  *   - the caller owns every buffer; the library keeps no pointer past return.
  *   - ops are asynchronous on `stream` (NULL = the device's default stream) unless they have a
  *     host output, which makes them synchronise that stream before returning.
