@@ -134,6 +134,8 @@ SIGNATURES = {
     "fx3d_dgcnn_forward_train": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, c_f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_dgcnn_grad_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_dgcnn_grad": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "fx3d_dgcnn_grad_train_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_dgcnn_grad_train": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_edgeconv_param_count": [C.POINTER(c_i32), c_i32, C.POINTER(c_i64)],
     "fx3d_edgeconv_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_edgeconv_forward": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, sz, vp],

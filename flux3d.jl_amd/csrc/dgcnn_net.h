@@ -1,4 +1,5 @@
-// What dgcnn.hip (the forward), dgcnn_train.hip (the training-mode forward) and dgcnn_grad.hip (the adjoint) share: the layers of
+// What dgcnn.hip (the forward), dgcnn_train.hip (the training-mode forward), dgcnn_grad.hip (the adjoint) and dgcnn_grad_train.hip
+// (the training-mode adjoint) share: the layers of
 // the two EdgeConv stages, conv_3's LDS image of a 64-point tile of x2, the walk over the flat parameter buffer, the size check
 // of the entries, and the forward's workspace and conv_3 launch.
 #pragma once
@@ -16,6 +17,13 @@ constexpr int32_t kEc1[] = {3, 32, 64, 64}, kEc2[] = {64, 128, 256};  // the lay
 __device__ __forceinline__ void load_x2_tile(float *lds, const float *__restrict__ x2, int b, int N, int p0, int nvalid) {
     const float *xb = x2 + ((size_t)b * N + p0) * 256;
     for (int i = threadIdx.x; i < kTile * 256; i += kPtThreads) lds[(i >> 8) * kLd3 + (i & 255)] = i < nvalid * 256 ? xb[i] : 0.0f;
+}
+
+// a training-mode head block's BatchNorm and relu of this thread's element v = dense + bias (dgcnn_train.hip's head kernels, and
+// dgcnn_grad_train.hip, which computes them again)
+__device__ __forceinline__ float head_bn_relu(const Bn &bn, float v) {
+    const int tid = threadIdx.x;
+    return relu(batchnorm(v, bn.g[tid], bn.b[tid], bn.m[tid], sqrtf(bn.v[tid] + kBnEps)));
 }
 
 // ---- the flat parameter buffer in forward order (flux3d_hip.h) ----------------------------------------------------------
@@ -43,6 +51,15 @@ inline Net dgcnn_layout(const float *params, int num_classes) {
 inline fx3d_status dgcnn_check_sizes(const char *fn, int32_t N, int32_t B, int32_t K, int32_t nc) {
     FX3D_REQUIRE(nc >= 1 && nc <= (1 << 20), "%s: num_classes must be in [1, 2^20], got %d", fn, nc);
     return check_edgeconv_sizes(fn, N, B, K);
+}
+
+// the training-mode entries' (dgcnn_train.hip, dgcnn_grad_train.hip) sizes
+inline fx3d_status dgcnn_check_train_sizes(const char *fn, int32_t N, int32_t B, int32_t K, int32_t nc) {
+    const fx3d_status rc = dgcnn_check_sizes(fn, N, B, K, nc);
+    if (rc != FX3D_OK) return rc;
+    FX3D_REQUIRE(B >= 2, "%s: training-mode BatchNorm needs B >= 2 clouds (a Dense BatchNorm's running variance divides by B - 1), got %d",
+                 fn, B);
+    return FX3D_OK;
 }
 
 // the forward's workspace: x1 (64, N, B) | x2 (256, N, B) | per-tile maxima (1024, ntiles, B) | logits (num_classes, B) | one

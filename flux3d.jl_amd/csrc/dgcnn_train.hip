@@ -50,11 +50,6 @@ struct TrainHeadArgs {
     float *logits, *probs;
 };
 
-__device__ __forceinline__ float head_bn_relu(const Bn &bn, float v) {
-    const int tid = threadIdx.x;
-    return relu(batchnorm(v, bn.g[tid], bn.b[tid], bn.m[tid], sqrtf(bn.v[tid] + kBnEps)));
-}
-
 // MaxPool over the cloud's points, fc_4's dense layer
 __global__ __launch_bounds__(kHeadThreads) void dgcnn_train_head_a_kernel(const TrainHeadArgs a) {
     __shared__ float v0[kFeat];
@@ -107,14 +102,6 @@ fx3d_status train_plan(int N, int B, int K, int nc, TrainPlan *t) {
     return FX3D_OK;
 }
 
-fx3d_status check_train_sizes(const char *fn, int32_t N, int32_t B, int32_t K, int32_t nc) {
-    const fx3d_status rc = dgcnn_check_sizes(fn, N, B, K, nc);
-    if (rc != FX3D_OK) return rc;
-    FX3D_REQUIRE(B >= 2, "%s: training-mode BatchNorm needs B >= 2 clouds (a Dense BatchNorm's running variance divides by B - 1), got %d",
-                 fn, B);
-    return FX3D_OK;
-}
-
 // one BatchNorm's slot of the statistics buffers, `at` floats in, and the running values it updates
 StatOut stat_out(const Bn &run, int C, size_t at, float *batch_stats, float *running, float momentum, long long m) {
     StatOut o{};
@@ -139,7 +126,7 @@ fx3d_status fx3d_dgcnn_stat_count(int64_t *count) {
 fx3d_status fx3d_dgcnn_train_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes) {
     const char *fn = "fx3d_dgcnn_train_workspace_bytes";
     FX3D_REQUIRE(bytes != nullptr, "%s: bytes is NULL", fn);
-    fx3d_status rc = check_train_sizes(fn, N, B, K, num_classes);
+    fx3d_status rc = dgcnn_check_train_sizes(fn, N, B, K, num_classes);
     if (rc != FX3D_OK) return rc;
     TrainPlan t;
     if ((rc = train_plan(N, B, K, num_classes, &t)) != FX3D_OK) return rc;
@@ -153,7 +140,7 @@ fx3d_status fx3d_dgcnn_forward_train(const float *params_dev, int32_t num_classe
                                      float *running, void *ws, size_t ws_bytes, fx3d_stream_t s) {
     const char *fn = "fx3d_dgcnn_forward_train";
     FX3D_REQUIRE(params_dev && x && probs && batch_stats && ws, "%s: params_dev, x, probs, batch_stats and ws must not be NULL", fn);
-    fx3d_status r = check_train_sizes(fn, N, B, K, num_classes);
+    fx3d_status r = dgcnn_check_train_sizes(fn, N, B, K, num_classes);
     if (r != FX3D_OK) return r;
     FX3D_REQUIRE(std::isfinite(momentum) && momentum >= 0.0f && momentum <= 1.0f, "%s: momentum must be finite and in [0, 1], got %g",
                  fn, (double)momentum);

@@ -46,29 +46,6 @@ static_assert(kLayerLds <= 160 * 1024, "the layer adjoint's LDS");
 static_assert(kGroup == 32 * (kPtThreads / 64), "one slab per wave");
 static_assert(FX3D_POINTNET_GRAD_TRAIN_CLOUD_CHAINS == 1, "dW / db of a last convolution: one chain per cloud (last_pgrad)");
 
-// the header's "gradient at the BatchNorm's input": every operation rounded, nothing fused (-ffp-contract=off)
-__device__ __forceinline__ float bn_gv(float gy, float xh, float mb, float mg, float gam, float sd) {
-    float t = gy - mb;
-    t = t - (xh * mg);
-    return (t * gam) / sd;
-}
-
-// one BatchNorm's sums: where dgamma, dbeta and the +0 of mu / var go, and the two means the layer below needs
-struct BnOut {
-    GradBlock g;
-    float *mb, *mg;  // (C) each: Float32(dbeta64 / m), Float32(dgamma64 / m)
-    long long m;
-};
-__device__ __forceinline__ void finish_bn(const BnOut &o, int c, double s1, double s2) {
-    const double dm = (double)o.m;
-    o.g.be[c] = (float)s1;
-    o.g.g[c] = (float)s2;
-    o.g.m[c] = 0.0f;
-    o.g.v[c] = 0.0f;
-    o.mb[c] = (float)(s1 / dm);
-    o.mg[c] = (float)(s2 / dm);
-}
-
 // ---- the head ----------------------------------------------------------------------------------------------------------------------
 struct HeadGtArgs : HeadArgs {  // the forward's head of the round at the batch statistics
     const int32_t *tfirst;  // (1024, ntiles, B)
@@ -228,33 +205,6 @@ struct LastArgs {
     float *g;              // (128, N, B): the gradient at it
     float *Hc, *hc;        // (128, 1024, B), (1024, B): dW and db of each cloud
     int N, ntiles;
-};
-
-// a lane's channel of the last layer: its constants, and d of a point from the accumulator's value
-template <int EPI>
-struct LastChannel {
-    float bi, gam, mu, sd, mb, mg, gy;
-    int win;  // the winner's row in this tile (any other value: not in this tile)
-    __device__ __forceinline__ LastChannel(const Conv &c, const LastArgs &a, int o, int b, int p0) {
-        bi = c.b[o]; gam = c.bn.g[o]; mu = c.bn.m[o]; sd = bn_sd(c.bn, o); mb = a.mb[o]; mg = a.mg[o];
-        gy = a.gy3[(size_t)b * kFeat + o];
-        const int n = a.nstar[(size_t)b * kFeat + o];
-        win = n < 0 ? -1 : n - p0;
-    }
-    __device__ __forceinline__ float d(float acc, int p) const {
-        const float pre = before_bn<EPI>(acc, bi);
-        const float g = bn_gv(p == win ? gy : 0.0f, (pre - mu) / sd, mb, mg, gam, sd);
-        return (EPI == kReluBn && !(pre > 0.0f)) ? 0.0f : g;
-    }
-    // the slab's d of the tile's valid rows (+0 beyond them) into column `col` of the image D
-    __device__ __forceinline__ void store(float *D, int col, int h, int nvalid, const f32x16 &acc0, const f32x16 &acc1) const {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int p = mfma_row(r, h);
-            D[p * kLd + col] = p < nvalid ? d(acc0[r], p) : 0.0f;
-            D[(p + 32) * kLd + col] = p + 32 < nvalid ? d(acc1[r], p + 32) : 0.0f;
-        }
-    }
 };
 
 template <int MODE>
@@ -640,6 +590,18 @@ fx3d_status launch_last_pgrad(int mode, const LastArgs &a, int B, hipStream_t st
 
 }  // namespace
 
+namespace fx3d {
+namespace mlp {
+namespace pointnet {
+fx3d_status launch_cloud_sums(const float *gy, const float *xh, const int32_t *nstar, int C, int B, const BnOut &o, hipStream_t st) {
+    hipLaunchKernelGGL(pointnet_gt_cloud_sums_kernel, dim3(C / 256), dim3(256), 0, st, gy, xh, nstar, C, B, o);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+}  // namespace pointnet
+}  // namespace mlp
+}  // namespace fx3d
+
 extern "C" {
 
 fx3d_status fx3d_pointnet_grad_train_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes) {
@@ -692,10 +654,8 @@ fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t num_classe
         return k == 2 ? feat_head(net, num_classes, tmax, nt, nullptr, nullptr, nullptr) : stn_head(net, k, tmax, nt, T, F, nullptr);
     };
     auto bn_out = [&](const Bn &g, long long m) { return BnOut{grad_block(g), mb, mg, m}; };
-    auto cloud_sums = [&](const float *gy, const float *xh, const int32_t *ns, int C, const BnOut &o) -> fx3d_status {
-        hipLaunchKernelGGL(pointnet_gt_cloud_sums_kernel, dim3(C / 256), dim3(256), 0, st, gy, xh, ns, C, B, o);
-        FX3D_LAUNCH_CHECK();
-        return FX3D_OK;
+    auto cloud_sums = [&](const float *gy, const float *xh, const int32_t *ns, int C, const BnOut &o) {
+        return launch_cloud_sums(gy, xh, ns, C, B, o, st);
     };
     // round k's head: its adjoint cut at the dense BatchNorms, down to gy of the round's last BatchNorm and that BatchNorm's sums;
     // then the dense layers' sums over the clouds

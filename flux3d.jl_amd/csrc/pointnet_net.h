@@ -2,7 +2,8 @@
 // pointnet_grad_train.hip (the training-mode adjoint) share.  At the end, what only some of them share: the fold of a BatchNorm's
 // Float64 tile sums (the two training-mode units) and a BatchNorm's batch statistics (pointnet_train.hip, and with it the
 // training-mode forwards of DGCNN and EdgeConv), and the adjoints' MFMA chains over a tile (hsum_mfma, back_mfma, hsum3) with the
-// launches of pointnet_grad.hip's finishing kernels.
+// launches of pointnet_grad.hip's finishing kernels; and what the training-mode adjoints of PointNet and DGCNN share (bn_gv, BnOut,
+// LastChannel, the cloud-sums launch).
 // On the host: the walk over the flat parameter buffer, the forward's workspace, the size check of the entries, the
 // arguments of the forward's two kernels per round (set_round, stn_head, feat_head) and their launches (defined in
 // pointnet.hip, which owns the kernels).  On the device: a round's layer chain (round_trunk, with its tile loads), the slab
@@ -507,6 +508,65 @@ __device__ __forceinline__ void hsum3(const float *xs, const float *d, int nvali
     for (int p = 0; p < nvalid; ++p) acc = fmaf(xs[p * 3 + c], d[p * kLd + o], acc);
     out[e] = acc;
 }
+
+// ---- what the training-mode adjoints (pointnet_grad_train.hip, dgcnn_grad_train.hip) share ------------------------------------------
+// the header's "gradient at the BatchNorm's input": every operation rounded, nothing fused (-ffp-contract=off)
+__device__ __forceinline__ float bn_gv(float gy, float xh, float mb, float mg, float gam, float sd) {
+    float t = gy - mb;
+    t = t - (xh * mg);
+    return (t * gam) / sd;
+}
+
+// one BatchNorm's sums: where dgamma, dbeta and the +0 of mu / var go, and the two means the layer below needs
+struct BnOut {
+    GradBlock g;
+    float *mb, *mg;  // (C) each: Float32(dbeta64 / m), Float32(dgamma64 / m)
+    long long m;
+};
+__device__ __forceinline__ void finish_bn(const BnOut &o, int c, double s1, double s2) {
+    const double dm = (double)o.m;
+    o.g.be[c] = (float)s1;
+    o.g.g[c] = (float)s2;
+    o.g.m[c] = 0.0f;
+    o.g.v[c] = 0.0f;
+    o.mb[c] = (float)(s1 / dm);
+    o.mg[c] = (float)(s2 / dm);
+}
+
+// pointnet_grad_train.hip's pointnet_gt_cloud_sums_kernel on st: a BatchNorm whose values are (C, B), C a multiple of 256: thread c,
+// one Float64 chain over b ascending; with nstar (C, B) over the clouds that have a winner (nstar >= 0)
+fx3d_status launch_cloud_sums(const float *gy, const float *xh, const int32_t *nstar, int C, int B, const BnOut &o, hipStream_t st);
+
+// A lane's channel o of a maximum's last convolution (1024 outputs), cloud b, tile from point p0: its constants, and d of a point
+// from the accumulator's value.  a: the kernel's arguments with nstar, gy3 (1024, B) and mb, mg (1024).  EPI: kReluBn / kBnOnly
+// (PointNet's rounds: relu below the BatchNorm masks d) or kBnRelu (DGCNN's conv_3: the relu is above the BatchNorm and already
+// in gy3, what the BatchNorm is given is conv + bias).
+template <int EPI>
+struct LastChannel {
+    float bi, gam, mu, sd, mb, mg, gy;
+    int win;  // the winner's row in this tile (any other value: not in this tile)
+    template <class Args>
+    __device__ __forceinline__ LastChannel(const Conv &c, const Args &a, int o, int b, int p0) {
+        bi = c.b[o]; gam = c.bn.g[o]; mu = c.bn.m[o]; sd = bn_sd(c.bn, o); mb = a.mb[o]; mg = a.mg[o];
+        gy = a.gy3[(size_t)b * kFeat + o];
+        const int n = a.nstar[(size_t)b * kFeat + o];
+        win = n < 0 ? -1 : n - p0;
+    }
+    __device__ __forceinline__ float d(float acc, int p) const {
+        const float pre = before_bn<EPI>(acc, bi);
+        const float g = bn_gv(p == win ? gy : 0.0f, (pre - mu) / sd, mb, mg, gam, sd);
+        return (EPI == kReluBn && !(pre > 0.0f)) ? 0.0f : g;
+    }
+    // the slab's d of the tile's valid rows (+0 beyond them) into column `col` of the image D (row stride kLd)
+    __device__ __forceinline__ void store(float *D, int col, int h, int nvalid, const f32x16 &acc0, const f32x16 &acc1) const {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int p = mfma_row(r, h);
+            D[p * kLd + col] = p < nvalid ? d(acc0[r], p) : 0.0f;
+            D[(p + 32) * kLd + col] = p + 32 < nvalid ? d(acc1[r], p + 32) : 0.0f;
+        }
+    }
+};
 
 }  // namespace pointnet
 }  // namespace mlp

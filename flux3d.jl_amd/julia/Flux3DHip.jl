@@ -1832,6 +1832,47 @@ function dgcnn_gradient(m::DGCNN, X::HipArray{Float32,3}, glogits::HipArray{Floa
     return gflat, gx
 end
 
+# dgcnn_gradient for the TRAINING-mode network (include/flux3d_hip.h "DGCNN training-mode adjoint"): the gradients of
+# sum(glogits .* logits) for the logits of dgcnn_forward_train(m, X; dropout), μ and σ² of all 8 BatchNorms functions of the batch,
+# the multipliers and the neighbours constants.  fwd: dgcnn_forward_train(m, X; dropout, intermediates = true) for the same X and
+# dropout, whose idx1, x1, idx2, x2, pooled and batch_stats are used.  Returns (gflat, gx) as dgcnn_gradient does.
+function dgcnn_grad_train(m::DGCNN, X::HipArray{Float32,3}, glogits::HipArray{Float32,2}, fwd;
+                          dropout::Union{Nothing,Tuple{HipArray{Float32,2},HipArray{Float32,2}}} = nothing, input_grad::Bool = true)
+    size(X, 1) == 3 || error("DGCNN takes 3 channels per point, got $(size(X, 1))")
+    _, N, B = size(X)
+    B >= 2 || error("DGCNN in training mode needs at least two clouds")
+    K = m.EdgeConv1.K
+    m.EdgeConv2.K == K || error("DGCNN: both EdgeConvs must use the same K")
+    npoints = m.maxpool_3.k[1]
+    N == npoints || error("DGCNN(num_classes, K, npoints = $npoints) takes clouds of npoints points, got $N: MaxPool((npoints,)) is the maximum over a whole cloud only then")
+    (1 <= K && K + 1 <= N) || error("DGCNN needs 1 <= K <= N - 1, got K = $K, N = $N")
+    (dropout === nothing || (size(dropout[1]) == (512, B) && size(dropout[2]) == (256, B))) ||
+        error("dropout must be a pair of (512, $B) and (256, $B) arrays")
+    nc = size(_dense_wb(m.fc_6)[1], 1)
+    size(glogits) == (nc, B) || error("glogits must be ($nc, $B), got $(size(glogits))")
+    length(fwd.batch_stats) == dgcnn_stat_count() ||
+        throw(ArgumentError("fwd.batch_stats must hold $(dgcnn_stat_count()) floats, got $(length(fwd.batch_stats))"))
+    params = dgcnn_params(m)
+    pd = hip(params)
+    nb = Ref{Csize_t}(0)
+    check(@ccall LIB.fx3d_dgcnn_grad_train_workspace_bytes(Int32(N)::Int32, Int32(B)::Int32, Int32(K)::Int32, Int32(nc)::Int32,
+                                                           nb::Ref{Csize_t})::Int32)
+    ws = workspace(nb[])
+    gflat = HipArray{Float32}(undef, length(params))
+    gx = input_grad ? HipArray{Float32}(undef, 3, N, B) : nothing
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    d4 = dropout === nothing ? C_NULL : dropout[1].ptr
+    d5 = dropout === nothing ? C_NULL : dropout[2].ptr
+    check(@ccall LIB.fx3d_dgcnn_grad_train(pd.ptr::Ptr{Cvoid}, Int32(nc)::Int32, Int32(K)::Int32, X.ptr::Ptr{Cvoid},
+                                           Int32(N)::Int32, Int32(B)::Int32, d4::Ptr{Cvoid}, d5::Ptr{Cvoid},
+                                           fwd.idx1.ptr::Ptr{Cvoid}, fwd.x1.ptr::Ptr{Cvoid}, fwd.idx2.ptr::Ptr{Cvoid},
+                                           fwd.x2.ptr::Ptr{Cvoid}, fwd.pooled.ptr::Ptr{Cvoid}, fwd.batch_stats.ptr::Ptr{Cvoid},
+                                           glogits.ptr::Ptr{Cvoid}, gflat.ptr::Ptr{Cvoid}, opt(gx)::Ptr{Cvoid}, C_NULL::Ptr{Cvoid},
+                                           C_NULL::Ptr{Cvoid}, ws.ptr::Ptr{Cvoid}, length(ws)::Csize_t,
+                                           DEFAULT_STREAM::Stream)::Int32)
+    return gflat, gx
+end
+
 
 # ---- EdgeConv inference: (m::EdgeConv)(X) (src/models/dgcnn.jl:11-71) in test mode, any layer widths -----------------------
 # EdgeConv(layers, K) as a layer in its own right (include/flux3d_hip.h "EdgeConv inference"): m.layers = [F, c1, ..., cL] goes

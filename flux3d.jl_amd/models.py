@@ -9,8 +9,9 @@ whole network with respect to every parameter and to the input points (``DGCNN.g
 ``PointNet.grad`` over fx3d_pointnet_grad, "PointNet adjoint"), all with BatchNorm in test mode.  PointNet also has its
 training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_train, "PointNet training-mode forward") and that
 forward's gradients (``PointNet.grad_train`` over fx3d_pointnet_grad_train, "PointNet training-mode adjoint"); DGCNN and EdgeConv have their training-mode forwards (``DGCNN.forward_train`` over
-fx3d_dgcnn_forward_train, ``EdgeConv.forward_train`` over fx3d_edgeconv_forward_train, "DGCNN / EdgeConv training-mode forward"), and EdgeConv that
-forward's gradients (``EdgeConv.grad_train`` over fx3d_edgeconv_grad_train, "EdgeConv training-mode adjoint")."""
+fx3d_dgcnn_forward_train, ``EdgeConv.forward_train`` over fx3d_edgeconv_forward_train, "DGCNN / EdgeConv training-mode forward") and those
+forwards' gradients (``EdgeConv.grad_train`` over fx3d_edgeconv_grad_train, "EdgeConv training-mode adjoint"; ``DGCNN.grad_train`` over
+fx3d_dgcnn_grad_train, "DGCNN training-mode adjoint")."""
 import ctypes as C
 
 import numpy as np
@@ -555,7 +556,9 @@ class DGCNN(_Model):
     flat buffer, :meth:`crossentropy_grad` the loss ``Flux.crossentropy(m(X), onehot(labels))`` with its gradients.  The two
     EdgeConv stages inside are :meth:`EdgeConv.grad`'s kernel on the ``ec2.`` and ``ec1.`` parameters, bit for bit.  The
     training-mode forward -- BatchNorm at the batch statistics, the two Dropouts as given masks, the updated running statistics --
-    is :meth:`forward_train` (include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward"); it is not differentiated yet."""
+    is :meth:`forward_train` (include/flux3d_hip.h "DGCNN / EdgeConv training-mode forward"), and its gradients -- mu and sigma2
+    functions of the batch -- are :meth:`grad_train`, :meth:`flat_grad_train` and :meth:`crossentropy_grad_train`
+    (include/flux3d_hip.h "DGCNN training-mode adjoint")."""
 
     _NAME, _COUNT_FN, _WHY = "DGCNN", "fx3d_dgcnn_param_count", "EdgeConv([3, 32, 64, 64], K)"
 
@@ -678,18 +681,40 @@ class DGCNN(_Model):
 
     _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
 
-    def _grad_call(self, X, glogits, input_grad, intermediates, fwd=None):
-        """fx3d_dgcnn_grad after the argument checks: (the flat gradient, gx or None, gx2 and gx1 or None) on the device, and
-        whether ``X`` lives there."""
+    def _grad_call(self, X, glogits, input_grad, intermediates, fwd=None, train=False, dropout=None):
+        """fx3d_dgcnn_grad (``train``: fx3d_dgcnn_grad_train, with the dropout multipliers and with the intermediates and batch
+        statistics of ``fwd``, or of a :meth:`forward_train` run here) after the argument checks: (the flat gradient, gx or None,
+        gx2 and gx1 or None) on the device, and whether ``X`` lives there.  Every refusal comes before any device work."""
         pts, N, B, on_dev = self._clouds(X, self._WHY)
         nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
-        nb = _lib.query_bytes("fx3d_dgcnn_grad_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
+        entry = "fx3d_dgcnn_grad_train" if train else "fx3d_dgcnn_grad"
+        if train:
+            if B < 2:
+                raise ValueError(f"training-mode BatchNorm needs at least two clouds, got B={B}")
+            masks = self._train_masks(dropout, B, on_dev)
+            slots = self._stat_slots()
+            nstat = slots[-1][2] + 2 * slots[-1][1]
+            names = [bn + f for bn, *_ in slots for f in (".mu", ".sigma2")]
+            if fwd is not None:
+                if not isinstance(fwd, dict) or "batch_stats" not in fwd:
+                    raise TypeError("fwd must be the dict of forward_train(..., intermediates=True)")
+                named = fwd["batch_stats"]
+                if not isinstance(named, dict) or [k for k in named] != names:
+                    raise ValueError(f"fwd['batch_stats'] must hold mu and sigma2 of the {len(slots)} BatchNorms in forward order")
+                for (bn, C_, _, _) in slots:
+                    for f in (".mu", ".sigma2"):
+                        v = named[bn + f]
+                        if is_device(v) != on_dev:
+                            raise TypeError("fwd must live where X lives")
+                        if tuple(v.shape) != (C_,) or v.dtype != f32:
+                            raise ValueError(f"fwd['batch_stats'][{bn + f!r}] must be Float32 ({C_},), got {v.dtype} {tuple(v.shape)}")
+        nb = _lib.query_bytes(entry + "_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
         g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
         given = [None] * len(self._FWD_KEYS)
         if fwd is not None:
             missing = [k for k in self._FWD_KEYS if k not in fwd]
             if missing:
-                raise ValueError(f"fwd must be the dict of forward(X, intermediates=True): it has no {missing}")
+                raise ValueError(f"fwd must be the dict of forward{'_train' if train else ''}(X, intermediates=True): it has no {missing}")
             shapes = {"idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32), "x2": ((256, N, B), f32),
                       "pooled": ((1024, B), f32)}
             given = [self._like(fwd[k], f"fwd['{k}']", *shapes[k], on_dev) for k in self._FWD_KEYS]
@@ -700,13 +725,29 @@ class DGCNN(_Model):
             g = DeviceArray.from_host(g)
             given = [None if a is None else DeviceArray.from_host(a) for a in given]
         x = self._on_device(pts, N, B, on_dev)
+        stream = current_stream().handle
+        lead = ()
+        if train:
+            masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
+            if fwd is None:
+                made = self.forward_train(x, dropout=None if dropout is None else tuple(masks), intermediates=True)
+                given, named = [made[k] for k in self._FWD_KEYS], made["batch_stats"]
+            # the 8 BatchNorms' statistics (views of forward_train's buffer, or the caller's arrays) as one buffer in the layout's order
+            if on_dev or fwd is None:
+                stats = DeviceArray.empty((nstat,), f32)
+                for bn, C_, at, _ in slots:
+                    for fld, off in ((".mu", at), (".sigma2", at + C_)):
+                        _lib.call("fx3d_memcpy_d2d", stats.ptr + 4 * off, named[bn + fld].ptr, 4 * C_, stream)
+            else:
+                stats = DeviceArray.from_host(np.concatenate([np.asarray(named[k], f32) for k in names]))
+            lead = tuple(m.ptr if m is not None else None for m in masks)
         gp = DeviceArray.empty((self.param_count,), f32)
         gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
         mid = {"gx2": DeviceArray.empty((256, N, B), f32), "gx1": DeviceArray.empty((64, N, B), f32)} if intermediates else None
-        ws = workspace(nb, tag="dgcnn_grad")
-        _lib.call("fx3d_dgcnn_grad", self._params_dev().ptr, nc, K, x.ptr, N, B, *(None if a is None else a.ptr for a in given),
-                  g.ptr, gp.ptr, gx.ptr if gx is not None else None, mid["gx2"].ptr if mid else None,
-                  mid["gx1"].ptr if mid else None, ws.ptr, ws.nbytes, current_stream().handle)
+        ws = workspace(nb, tag=entry[5:])
+        _lib.call(entry, self._params_dev().ptr, nc, K, x.ptr, N, B, *lead, *(None if a is None else a.ptr for a in given),
+                  *((stats.ptr,) if train else ()), g.ptr, gp.ptr, gx.ptr if gx is not None else None,
+                  mid["gx2"].ptr if mid else None, mid["gx1"].ptr if mid else None, ws.ptr, ws.nbytes, stream)
         return gp, gx, mid, on_dev
 
     def flat_grad(self, X, glogits, fwd=None, input_grad=True, intermediates=False):
@@ -733,6 +774,38 @@ class DGCNN(_Model):
         ``loss = -mean_b log(probs[y_b, b])`` in float64 (a Python float), ``glogits[o, b] = (probs[o, b] - [o == y_b]) /
         Float32(B)`` with one Float32 subtraction and one Float32 division, then :meth:`grad` with that forward."""
         return self._crossentropy_grad(X, labels, with_fwd=True)
+
+    def grad_train(self, X, glogits, dropout=None, fwd=None, input_grad=True, intermediates=False):
+        """:meth:`grad` for the TRAINING-mode network: the gradients of ``sum(glogits * logits)`` for the logits of
+        :meth:`forward_train` ``(X, dropout)``, with every BatchNorm's mean and variance functions of the batch and the dropout
+        multipliers and both neighbour lists constants: include/flux3d_hip.h "DGCNN training-mode adjoint".  ``dropout`` as in
+        :meth:`forward_train`.  ``fwd``: the dict of ``forward_train(X, dropout, intermediates=True)`` for the same ``X`` and
+        ``dropout``, whose ``idx1``, ``x1``, ``idx2``, ``x2``, ``pooled`` and ``batch_stats`` are then used; without it
+        :meth:`forward_train` runs first.  Returns what :meth:`grad` returns (the ``mu`` / ``sigma2`` entries are zero: the
+        running statistics do not enter this forward); ``intermediates=True`` adds ``mid`` with ``gx2`` and ``gx1``.  The two
+        EdgeConv stages inside are :meth:`EdgeConv.grad_train`'s kernels, bit for bit.  At least two clouds."""
+        return self._grads(True, X, glogits, input_grad, intermediates, fwd=fwd, train=True, dropout=dropout)
+
+    def flat_grad_train(self, X, glogits, dropout=None, fwd=None, input_grad=True, intermediates=False):
+        """:meth:`grad_train` with the parameter gradients as one flat buffer, as :meth:`flat_grad`."""
+        return self._grads(False, X, glogits, input_grad, intermediates, fwd=fwd, train=True, dropout=dropout)
+
+    def crossentropy_grad_train(self, X, labels, dropout=None):
+        """:meth:`crossentropy_grad` on :meth:`forward_train`'s probabilities: ``(loss, grads, gx)`` of
+        ``Flux.crossentropy(m(X), onehot(labels))`` with the network in training mode under the multipliers ``dropout`` (as in
+        :meth:`forward_train`; an ``int`` seed is drawn once).  One :meth:`forward_train` with its intermediates, the loss and
+        ``glogits`` on the host as in :meth:`crossentropy_grad`, then :meth:`grad_train` with that forward."""
+        _, N, B, on_dev = self._clouds(X, self._WHY)
+        y = self._labels(labels, B)
+        if isinstance(dropout, (int, np.integer)):
+            dropout = self.dropout_masks(B, int(dropout))
+            if on_dev:
+                dropout = tuple(DeviceArray.from_host(m) for m in dropout)
+        fwd = self.forward_train(X, dropout=dropout, intermediates=True)
+        probs = fwd["probs"]
+        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
+        grads, gx = self.grad_train(X, DeviceArray.from_host(glogits) if on_dev else glogits, dropout=dropout, fwd=fwd)
+        return loss, grads, gx
 
 
 class EdgeConv(_Model):

@@ -1333,6 +1333,56 @@ FX3D_API fx3d_status fx3d_edgeconv_grad_train(const float *params_dev, const int
                                               const float *batch_stats, const float *gout, float *gparams, float *gx, void *ws,
                                               size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- DGCNN training-mode adjoint: the gradients of fx3d_dgcnn_forward_train with respect to its parameters and to X --------------
+ * gparams = d sum(glogits . logits) / d params for logits = fx3d_dgcnn_forward_train(x, dropout4, dropout5), and, if gx != NULL, gx
+ * (3,N,B).  mu and var of all 8 BatchNorms are functions of the batch (their slots of gparams are written as +0: the running
+ * statistics do not enter this forward); the dropout multipliers and both neighbour lists are constants.  params_dev .. B, dropout4,
+ * dropout5 (either or both may be NULL): the forward's.  idx1, x1, idx2, x2, pooled and batch_stats (fx3d_dgcnn_stat_count floats,
+ * the forward's layout) are required: what fx3d_dgcnn_forward_train returned for the same (params_dev, x, dropout4, dropout5);
+ * nothing of the forward is computed again but the head's vectors.  glogits (num_classes,B); gx2 (256,N,B) and gx1 (64,N,B): the
+ * gradients at x2 and x1, optional outputs.  Float32 throughout, Float64 for the BatchNorm sums; every operation is rounded and
+ * nothing is fused unless it says fmaf; sd = sqrtf(var + 1f-5) at batch_stats' var.
+ *   BatchNorm back, given v (m values per channel), xh = (v - mu) / sd and the upstream gy -- "PointNet training-mode adjoint"'s:
+ *     dbeta64 = sum (double)gy, dgamma64 = sum (double)gy (double)xh (exact products), chains from +0.0;  dbeta = Float32(dbeta64),
+ *     dgamma = Float32(dgamma64);  mb = Float32(dbeta64 / m), mg = Float32(dgamma64 / m);  t = gy - mb;  t = t - (xh mg);
+ *     gv = (t gamma) / sd.
+ *   1. The head.  Every block is dense, BatchNorm, relu, then the multiplier.  v4 = fc_4's dense + bias of pooled, r4 = relu(BN(v4)),
+ *     in5 = r4 dropout4;  v5, r5, in6 likewise from in5: the forward's bits (its fmaf chains over the inputs ascending).  The gradient
+ *     at in6 is one fmaf chain over the classes ascending of glogits[o] W6[o,i];  it is multiplied by dropout5 (one multiplication),
+ *     then masked by the relu's own output: gy5 = r5 > 0 ? . : +0.  xh5 = (v5 - mu) / sd;  fc5.bn's sums are one chain over b
+ *     ascending, m = B;  gv5.  The gradient at in5 is one fmaf chain over fc_5's 256 outputs ascending of gv5[o] W5[o,i];  times
+ *     dropout4, masked by r4: gy4;  fc4.bn likewise with v4;  gv4.  gp[c] = one fmaf chain over fc_4's 512 outputs of gv4[o] W4[o,c].
+ *     dW[o,i] = the fmaf chain over b ascending of gv[o,b] in[i,b], db[o] = the Float32 sum over b ascending of gv[o,b], for fc_4
+ *     (gv4, pooled), fc_5 (gv5, in5) and fc_6 (glogits, in6), written as they come out: gv already carries gamma / sd.
+ *   2. The maximum.  n*(c,b) is "DGCNN adjoint"'s: the first point n with relu(BN(conv_3(x2)))[c,n,b] == pooled[c,b] where
+ *     pooled[c,b] > 0, otherwise no winner.  gy3[c,n,b] = gp[c,b] at n = n*(c,b), +0 everywhere else (the relu above conv3.bn
+ *     passes at a winner: pooled > 0).  xh3 = (v3 - mu) / sd with v3 = conv_3 + bias, the forward's bits.  conv3.bn's sums are one
+ *     chain over the clouds that have a winner, ascending b, of gp and gp xh3(n*);  m = N B.
+ *   3. conv_3, dense.  gv3[c,n,b] = the BatchNorm back of (gy3, xh3) for EVERY point of every cloud: non-zero at the points that do
+ *     not win and in the clouds without a winner; +0 beyond a cloud's last point.  No relu mask below it.
+ *     gx2[i,n,b] = one fmaf chain from +0 over ALL 1024 outputs c ascending of gv3[c,n,b] W3[i,c].
+ *     dW3[i,c]: per cloud ONE fmaf chain from +0 over its points n ascending of x2[i,n,b] gv3[c,n,b];  db3[c]: per cloud one chain of
+ *     Float32 additions over n ascending;  then one sum of Float32 additions from +0 over b ascending
+ *     (FX3D_POINTNET_GRAD_TRAIN_CLOUD_CHAINS, as PointNet's last convolutions).
+ *   4. The stages.  fx3d_edgeconv_grad_train on (ec2, x1, idx2, out = x2, gout = gx2), which gives gx1, then on (ec1, x, idx1,
+ *     out = x1, gout = gx1), which gives gx; each on its slice of params_dev, batch_stats and gparams, bit for bit.
+ * The orders depend on (N, B, K, num_classes) alone; no atomics; gparams, gx, gx2 and gx1 are bit-identical to the restatement
+ * tests/dgcnn_grad_train_ref.py and from run to run.  All-1.0f multipliers give the bits of NULL.
+ * Refusals, FX3D_ERR_INVALID_ARG, each before any device work: a NULL required pointer (params_dev, x, idx1, x1, idx2, x2, pooled,
+ * batch_stats, glogits, gparams, ws); fx3d_dgcnn_forward_train's size limits, B < 2 among them; a short workspace or one not
+ * 256-byte aligned.  Launches on `s` only, no host synchronisation, no host memory read after the argument check
+ * (graph-capturable): the winners' kernel, the head in three kernels with a cloud-sums kernel after each, three dense-sums kernels,
+ * conv_3's two dense kernels and two chains over the clouds, then the two stages' launches.
+ * ws: fx3d_dgcnn_grad_train_workspace_bytes(N, B, K, num_classes) -- the per-tile first matches (1024,ntiles,B) with what conv3.bn
+ * was given there; the head's vectors; dW3 and db3 per cloud, (256,1024,B) and (1024,B); gx2 and gx1; one scratch region, the
+ * larger of the two stages' fx3d_edgeconv_grad_train workspaces. */
+FX3D_API fx3d_status fx3d_dgcnn_grad_train_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
+FX3D_API fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N,
+                                           int32_t B, const float *dropout4, const float *dropout5, const int32_t *idx1,
+                                           const float *x1, const int32_t *idx2, const float *x2, const float *pooled,
+                                           const float *batch_stats, const float *glogits, float *gparams, float *gx, float *gx2,
+                                           float *gx1, void *ws, size_t ws_bytes, fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
