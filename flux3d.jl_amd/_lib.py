@@ -136,6 +136,9 @@ SIGNATURES = {
     "fx3d_dgcnn_grad": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "fx3d_dgcnn_grad_train_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_dgcnn_grad_train": [vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "fx3d_crossentropy": [vp, vp, c_i32, c_i32, vp, vp, vp, vp],
+    "fx3d_dropout_mask": [c_i64, c_f64, c_u64, vp, c_i32, vp, vp],
+    "fx3d_adam_step": [c_i64, c_f64, c_f64, c_f64, c_f64, vp, vp, vp, vp, vp, vp, vp, c_i64, vp],
     "fx3d_edgeconv_param_count": [C.POINTER(c_i32), c_i32, C.POINTER(c_i64)],
     "fx3d_edgeconv_workspace_bytes": [C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(sz)],
     "fx3d_edgeconv_forward": [vp, C.POINTER(c_i32), c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, sz, vp],

@@ -14,6 +14,7 @@
 
 #include "fx3d_common.h"
 #include "mesh_host.h"
+#include "philox.h"
 #include "sample_gather.h"
 #include "mesh_reg.h"
 
@@ -424,17 +425,6 @@ __global__ __launch_bounds__(kCdfThreads) void cdf_mb_final_kernel(int Fmax, dou
             const int c = k / kChunk;
             out[k] = ((out[W.boff() + c / (kChunk * kChunk)] + out[W.e1() + c / kChunk]) + out[W.e0() + c]) + out[k];
         }
-    }
-}
-
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
 }
 

@@ -399,6 +399,12 @@ class DeviceArray:
     def item(self):
         return self.to_host().reshape(-1)[0]
 
+    def __float__(self):
+        """The one element of the array as a Python float: a copy to the host on the current stream, which waits for it."""
+        if self.size != 1:
+            raise TypeError(f"only an array of one element converts to a float, got shape {self.shape}")
+        return float(self.item())
+
     def __del__(self):
         if getattr(self, "_owned", False) and self.ptr:
             try:

@@ -2032,5 +2032,49 @@ function edgeconv_grad_train(m::EdgeConv, X::HipArray{Float32,3}, gout::HipArray
     return gflat, gx
 end
 
+# ---- the training step (include/flux3d_hip.h "Training step") -------------------------------------------------------------------
+# Flux.crossentropy(probs, onehot(labels)) with its gradient at the logits: probs (num_classes, B), labels B Int32 on the device,
+# 0-based.  Returns (loss, glogits, counts): a 1-element Float64 device array, (num_classes, B) Float32 and the two Int32 counts
+# (clouds classified correctly, labels out of range), all on the device: nothing is read back.
+function crossentropy_dev(probs::HipArray{Float32,2}, labels::HipArray{Int32,1})
+    nc, B = size(probs)
+    length(labels) == B || throw(ArgumentError("labels must hold $B integers, got $(length(labels))"))
+    glogits = HipArray{Float32}(undef, nc, B)
+    loss = HipArray{Float64}(undef, 1)
+    counts = HipArray{Int32}(undef, 2)
+    check(@ccall LIB.fx3d_crossentropy(probs.ptr::Ptr{Cvoid}, labels.ptr::Ptr{Cvoid}, Int32(nc)::Int32, Int32(B)::Int32,
+                                       glogits.ptr::Ptr{Cvoid}, loss.ptr::Ptr{Cvoid}, counts.ptr::Ptr{Cvoid},
+                                       DEFAULT_STREAM::Stream)::Int32)
+    return loss, glogits, counts
+end
+
+# The multipliers of Dropout(p) in training mode drawn on the device into `out`: Philox under seed + counter[] (a device UInt64,
+# advanced with counter_add!), stream_id telling the masks of one step apart.
+function dropout_mask!(out::HipArray{Float32}, p::Real, seed::Integer; counter = C_NULL, stream_id::Integer = 0)
+    check(@ccall LIB.fx3d_dropout_mask(length(out)::Int64, Float64(p)::Float64, UInt64(seed)::UInt64,
+                                       (counter isa HipArray ? counter.ptr : counter)::Ptr{Cvoid}, Int32(stream_id)::Int32,
+                                       out.ptr::Ptr{Cvoid}, DEFAULT_STREAM::Stream)::Int32)
+    return out
+end
+
+# Flux.Optimise.ADAM(eta, beta) on one flat device buffer in one call: x, the state m and v (zero before the first step) and betap
+# (two Float64 on the device, beta before the first step) are updated in place.  running / stat_map: x[stat_map[i] + 1] = running[i]
+# in the same call (0-based indices: a model's running statistics into their mu / sigma2 slots).
+function adam_step!(x::HipArray{Float32}, g::HipArray{Float32}, m::HipArray{Float32}, v::HipArray{Float32}, betap::HipArray{Float64};
+                    eta = 0.001, beta = (0.9, 0.999), eps = 1e-8, running::Union{Nothing,HipArray{Float32}} = nothing,
+                    stat_map::Union{Nothing,HipArray{Int32}} = nothing)
+    (length(g) == length(x) && length(m) == length(x) && length(v) == length(x) && length(betap) == 2) ||
+        throw(ArgumentError("g, m and v must have the length of x, betap two elements"))
+    (running === nothing) == (stat_map === nothing) || throw(ArgumentError("running and stat_map go together"))
+    nstat = running === nothing ? 0 : length(running)
+    (stat_map === nothing || length(stat_map) == nstat) || throw(ArgumentError("running and stat_map must have one length"))
+    opt(a) = a === nothing ? C_NULL : a.ptr
+    check(@ccall LIB.fx3d_adam_step(length(x)::Int64, Float64(eta)::Float64, Float64(beta[1])::Float64, Float64(beta[2])::Float64,
+                                    Float64(eps)::Float64, g.ptr::Ptr{Cvoid}, m.ptr::Ptr{Cvoid}, v.ptr::Ptr{Cvoid},
+                                    betap.ptr::Ptr{Cvoid}, x.ptr::Ptr{Cvoid}, opt(running)::Ptr{Cvoid}, opt(stat_map)::Ptr{Cvoid},
+                                    Int64(nstat)::Int64, DEFAULT_STREAM::Stream)::Int32)
+    return x
+end
+
 
 end # module

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _lib
 from .device import DeviceArray, current_stream, is_device, workspace
+from .device import stream as stream_scope
 from .rep import PointCloud
 
 
@@ -111,7 +112,7 @@ class _Model:
                 self.params[name] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
             else:
                 self.params[name] = np.full(shape, 1.0 if field in ("gamma", "sigma2") else 0.0, np.float32)
-        self._dev = None
+        self._dev, self._stale, self._smap = None, False, None
         count = C.c_int64(0)
         _lib.call(self._COUNT_FN, *self._count_args(), C.byref(count))
         self.param_count = count.value
@@ -128,11 +129,14 @@ class _Model:
             if a.shape != shape:
                 raise ValueError(f"{name} must be {shape}, got {a.shape}")
             new[name] = np.array(a, dtype=np.float32)
-        self.params, self._dev = new, None
+        self.params, self._dev, self._stale = new, None, False
         return self
 
     def flat_params(self):
-        """The flat Float32 buffer the forward entry point reads: every array column-major, in forward order."""
+        """The flat Float32 buffer the forward entry point reads: every array column-major, in forward order.  After a
+        :meth:`train_step` the device copy is the authority: it is pulled into ``params`` first (:meth:`pull_params`)."""
+        if self._stale:
+            self.pull_params()
         flat = np.concatenate([self.params[n].ravel(order="F") for n in self._shapes()]).astype(np.float32)
         assert flat.size == self.param_count, (flat.size, self.param_count)
         return flat
@@ -141,6 +145,18 @@ class _Model:
         if self._dev is None:
             self._dev = DeviceArray.from_host(self.flat_params())
         return self._dev
+
+    def pull_params(self):
+        """Read the kept device copy of the parameters back into ``params`` (which :meth:`train_step` leaves stale: it updates the
+        device copy only) and return ``params``.  Synchronises the current stream."""
+        if self._dev is not None:
+            flat, at = self._dev.to_host(), 0
+            for name, shape in self._shapes().items():
+                n = int(np.prod(shape))
+                self.params[name] = flat[at:at + n].reshape(shape, order="F").copy(order="F")
+                at += n
+        self._stale = False
+        return self.params
 
     def _clouds(self, X, why, F=3):
         """(the points, N, B, whether they are on the device) after the shape checks; nothing is uploaded yet.  F: the
@@ -311,6 +327,137 @@ class _Model:
         grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits, **({"fwd": fwd} if with_fwd else {}))
         return loss, grads, gx
 
+    # ---- the training step (include/flux3d_hip.h "Training step"): a classifier sets _STAT_FN, _DROPOUT (rows of each mask, p),
+    #      _GRAD_NEEDS_FWD and has _masks_of, _train_bytes, _forward_train_call and _grad_train_call
+    def _stat_map(self):
+        """The device int32 map of fx3d_adam_step: for every element of the flat statistics buffer its index in the flat parameter
+        buffer.  Built from the names: only ``mu`` / ``sigma2`` slots, the only ones whose gradient is always +0."""
+        if self._smap is None:
+            idx, at = [], 0
+            for name, shape in self._shapes().items():
+                n = int(np.prod(shape))
+                if name.endswith((".mu", ".sigma2")):
+                    idx.extend(range(at, at + n))
+                at += n
+            count = C.c_int64(0)
+            _lib.call(self._STAT_FN, C.byref(count))
+            slots = self._stat_slots()
+            if len(idx) != count.value or any(idx[s] != f or idx[s + 2 * c - 1] != f + 2 * c - 1 for _, c, s, f in slots):
+                raise AssertionError("the mu / sigma2 slots of the parameters do not match the statistics layout")
+            self._smap = DeviceArray.from_host(np.array(idx, np.int32))
+        return self._smap
+
+    def _step_labels(self, labels, B):
+        """``labels`` of :meth:`train_step` / :meth:`evaluate` after their checks: a device int32 ``(B,)`` array as it is (its values
+        are checked on the device: ``counts[1]``), or host integers in [0, num_classes) as int32, still to be uploaded."""
+        if is_device(labels):
+            if labels.dtype != np.int32 or tuple(labels.shape) != (B,):
+                raise TypeError(f"device labels must be int32 ({B},), got {labels.dtype} {tuple(labels.shape)}")
+            return labels
+        return self._labels(labels, B).astype(np.int32)
+
+    def _step_masks(self, dropout, B, on_dev):
+        """``dropout`` of :meth:`train_step` after its checks: ``("device", seed, counter or None)``, or one entry per Dropout
+        layer as :meth:`forward_train` takes them (``None``, a device array, or a host array still to be uploaded)."""
+        if isinstance(dropout, tuple) and len(dropout) == 3 and isinstance(dropout[0], str):
+            kind, seed, counter = dropout
+            if kind != "device" or not isinstance(seed, (int, np.integer)):
+                raise ValueError('dropout drawn on the device is ("device", seed, counter) with an int seed')
+            if counter is not None and not (is_device(counter) and counter.dtype == np.uint64 and counter.size == 1):
+                raise TypeError("the dropout counter must be a device UInt64 array of one element, or None")
+            return ("device", int(seed) & 0xFFFFFFFFFFFFFFFF, counter)
+        return list(self._masks_of(dropout, B, on_dev))
+
+    def _crossentropy_dev(self, probs, y, B):
+        """fx3d_crossentropy on device ``probs`` and labels: (loss (1,) Float64, glogits, counts (2,) int32), all on the device."""
+        loss, counts = DeviceArray.empty((1,), np.float64), DeviceArray.empty((2,), np.int32)
+        glogits = DeviceArray.empty((self.num_classes, B), np.float32)
+        _lib.call("fx3d_crossentropy", probs.ptr, y.ptr, self.num_classes, B, glogits.ptr, loss.ptr, counts.ptr, current_stream().handle)
+        return loss, glogits, counts
+
+    def train_step(self, X, labels, opt, dropout=None, momentum=0.1, intermediates=False):
+        """One step of the reference's training loop (examples/pointnet_classification.jl, dgcnn_classification.jl) on the device:
+        :meth:`forward_train` with its running statistics, ``Flux.crossentropy`` (fx3d_crossentropy), :meth:`grad_train` given that
+        forward, then ``opt.update`` (:class:`ADAM`: fx3d_adam_step) on the kept device parameters, the running statistics
+        written into their ``mu`` / ``sigma2`` slots by the same call.  ``X`` as in :meth:`forward_train`; ``labels``: B host
+        integers in [0, num_classes) or a device int32 array; ``dropout``: ``None``, multipliers as in :meth:`forward_train`, or
+        ``("device", seed, counter)`` for masks drawn by fx3d_dropout_mask under ``seed`` plus the device UInt64 ``counter``
+        (``None``: 0), one stream id per Dropout layer in forward order.  Returns a :class:`StepResult`: ``loss`` (1,) Float64 and
+        ``counts`` (2,) int32 stay on the device until they are read.  ``intermediates=True`` adds, as device arrays, ``probs``,
+        ``logits``, ``glogits``, ``grad`` (the flat gradient), ``batch_stats`` and ``running`` (the flat buffers) and ``dropout``
+        (the list of masks used).  Nothing is read back, uploaded or waited for unless ``X``, ``labels`` or the masks are host
+        arrays, so the step can be captured (:class:`TrainStepGraph`).  Afterwards the device copy of the parameters is the
+        authority: :meth:`pull_params` brings ``params`` up to date (``flat_params`` does so itself)."""
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
+        if B < 2:
+            raise ValueError(f"training-mode BatchNorm needs at least two clouds, got B={B}")
+        if not callable(getattr(opt, "update", None)):
+            raise TypeError("opt must be an optimiser with update(x, g, running, stat_map), such as ADAM")
+        momentum = self._momentum(momentum)
+        y = self._step_labels(labels, B)
+        masks = self._step_masks(dropout, B, on_dev)
+        nb = self._train_bytes(N, B)  # (the library's own size limits)
+        smap, params = self._stat_map(), self._params_dev()
+        x = self._on_device(pts, N, B, on_dev)
+        if not is_device(y):
+            y = DeviceArray.from_host(y)
+        stream = current_stream().handle
+        if isinstance(masks, tuple):  # drawn here, stream id = the Dropout layer's position
+            _, seed, counter = masks
+            masks = [DeviceArray.empty((rows, B), np.float32) for rows in self._DROPOUT[0]]
+            for sid, mk in enumerate(masks):
+                _lib.call("fx3d_dropout_mask", mk.size, self._DROPOUT[1], seed, counter.ptr if counter is not None else None, sid,
+                          mk.ptr, stream)
+        else:
+            masks = [mk if mk is None or is_device(mk) else DeviceArray.from_host(mk) for mk in masks]
+        out, stats = self._forward_train_call(x, N, B, masks, momentum, nb, intermediates or self._GRAD_NEEDS_FWD, True)
+        loss, glogits, counts = self._crossentropy_dev(out["probs"], y, B)
+        gp = self._grad_train_call(x, N, B, masks, out, stats["batch_stats"], glogits)
+        opt.update(params, gp, running=stats["running"], stat_map=smap)
+        self._stale = True
+        extra = None
+        if intermediates:
+            extra = dict(probs=out["probs"], logits=out["logits"], glogits=glogits, grad=gp, batch_stats=stats["batch_stats"],
+                         running=stats["running"], dropout=masks)
+        return StepResult(loss, counts, current_stream(), extra)
+
+    def evaluate(self, X, labels):
+        """The tutorial's ``accuracy`` and loss on one batch: the test-mode :meth:`forward`, then fx3d_crossentropy.  The
+        :class:`StepResult` of :meth:`train_step` (``loss``, ``correct``), read lazily."""
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
+        y = self._step_labels(labels, B)
+        probs = self.forward(self._on_device(pts, N, B, on_dev))
+        if not is_device(y):
+            y = DeviceArray.from_host(y)
+        loss, _, counts = self._crossentropy_dev(probs, y, B)
+        return StepResult(loss, counts, current_stream())
+
+
+class StepResult:
+    """What :meth:`train_step` and :meth:`evaluate` return.  ``loss`` (1,) Float64 and ``counts`` (2,) int32 -- the clouds
+    classified correctly, the labels out of range -- are device arrays; ``float(result)`` / ``float(result.loss)`` and
+    ``result.correct`` copy them to the host, which waits for the step, and nothing else does.  With ``intermediates`` the
+    further device arrays are attributes too."""
+
+    def __init__(self, loss, counts, on, extra=None):
+        self.loss, self.counts, self._on = loss, counts, on
+        self.__dict__.update(extra or {})
+
+    def _read(self, a):
+        with stream_scope(self._on):  # the copy is ordered behind the step on the stream the step ran on
+            return a.to_host()
+
+    def __float__(self):
+        return float(self._read(self.loss)[0])
+
+    @property
+    def correct(self):
+        """The number of clouds whose most probable class is their label; raises if a label was outside [0, num_classes)."""
+        counts = self._read(self.counts)
+        if counts[1]:
+            raise ValueError(f"{int(counts[1])} labels are outside [0, num_classes): the loss is NaN")
+        return int(counts[0])
+
 
 class PointNet(_Model):
     """``PointNet(num_classes=10, K=64)`` (src/models/pointnet.jl:41-60).
@@ -394,20 +541,9 @@ class PointNet(_Model):
             mask = DeviceArray.from_host(mask)
         x = self._on_device(pts, N, B, on_dev)
         slots = self._stat_slots()
-        nstat = slots[-1][2] + 2 * slots[-1][1]
-        optional = self._optional(B)
-        out = self._outputs(B, optional, intermediates)
-        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
-        if intermediates or update:
-            stats["running"] = DeviceArray.empty((nstat,), f32)
-        params = self._params_dev()
-        ws = workspace(nb, tag="pointnet_train")
-        stream = current_stream().handle
-        _lib.call("fx3d_pointnet_forward_train", params.ptr, nc, x.ptr, N, B, mask.ptr if mask is not None else None, momentum,
-                  out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
-                  stats["batch_stats"].ptr, stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
+        out, stats = self._forward_train_call(x, N, B, [mask], momentum, nb, intermediates, intermediates or update)
         if update:
-            self._adopt_running(stats["running"], slots, stream)
+            self._adopt_running(stats["running"], slots, current_stream().handle)
         if not intermediates:
             return out["probs"] if on_dev else out["probs"].to_host()
         for key, buf in stats.items():
@@ -417,6 +553,40 @@ class PointNet(_Model):
         return out
 
     _MID = {"gstn": (3, 3), "gfstn": (64, 64), "gh": (64, None), "gxt": (3, None)}  # fx3d_pointnet_grad's optional outputs, in order
+    _STAT_FN, _DROPOUT, _GRAD_NEEDS_FWD = "fx3d_pointnet_stat_count", ((256,), 0.4), False  # (train_step)
+
+    def _masks_of(self, dropout, B, on_dev):
+        return (self._train_mask(dropout, B, on_dev),)
+
+    def _train_bytes(self, N, B):
+        return _lib.query_bytes("fx3d_pointnet_train_workspace_bytes", N, B, self.num_classes)
+
+    def _forward_train_call(self, x, N, B, masks, momentum, nb, intermediates, running):
+        """fx3d_pointnet_forward_train on the device arrays ``x`` and ``masks[0]`` (or ``None``) with a workspace of ``nb`` bytes:
+        ``(out, stats)`` -- ``probs`` and, with ``intermediates``, the optional outputs; the flat ``batch_stats`` and, with
+        ``running``, the flat ``running``."""
+        nc, f32 = self.num_classes, np.float32
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        optional = self._optional(B)
+        out = self._outputs(B, optional, intermediates)
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if running:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        ws = workspace(nb, tag="pointnet_train")
+        _lib.call("fx3d_pointnet_forward_train", self._params_dev().ptr, nc, x.ptr, N, B, masks[0].ptr if masks[0] is not None else None,
+                  momentum, out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
+                  stats["batch_stats"].ptr, stats["running"].ptr if running else None, ws.ptr, ws.nbytes, current_stream().handle)
+        return out, stats
+
+    def _grad_train_call(self, x, N, B, masks, out, batch_stats, glogits):
+        """fx3d_pointnet_grad_train on device arrays, the flat ``batch_stats`` as the forward wrote it: the flat gradient."""
+        nc = self.num_classes
+        ws = workspace(_lib.query_bytes("fx3d_pointnet_grad_train_workspace_bytes", N, B, nc), tag="pointnet_grad_train")
+        gp = DeviceArray.empty((self.param_count,), np.float32)
+        _lib.call("fx3d_pointnet_grad_train", self._params_dev().ptr, nc, x.ptr, N, B, masks[0].ptr if masks[0] is not None else None,
+                  batch_stats.ptr, glogits.ptr, gp.ptr, None, None, None, None, None, ws.ptr, ws.nbytes, current_stream().handle)
+        return gp
 
     def _train_mask(self, dropout, B, on_dev):
         """``dropout`` of the training-mode methods after its checks: ``None``, or the ``(256, B)`` multipliers (an ``int``: the
@@ -658,19 +828,9 @@ class DGCNN(_Model):
         masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
         x = self._on_device(pts, N, B, on_dev)
         slots = self._stat_slots()
-        nstat = slots[-1][2] + 2 * slots[-1][1]
-        optional = self._optional(N, B)
-        out = self._outputs(B, optional, intermediates)
-        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
-        if intermediates or update:
-            stats["running"] = DeviceArray.empty((nstat,), f32)
-        ws = workspace(nb, tag="dgcnn_train")
-        stream = current_stream().handle
-        _lib.call("fx3d_dgcnn_forward_train", self._params_dev().ptr, nc, K, x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
-                  momentum, out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
-                  stats["batch_stats"].ptr, stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
+        out, stats = self._forward_train_call(x, N, B, masks, momentum, nb, intermediates, intermediates or update)
         if update:
-            self._adopt_running(stats["running"], slots, stream)
+            self._adopt_running(stats["running"], slots, current_stream().handle)
         if not intermediates:
             return out["probs"] if on_dev else out["probs"].to_host()
         for key, buf in stats.items():
@@ -680,6 +840,42 @@ class DGCNN(_Model):
         return out
 
     _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
+    _STAT_FN, _DROPOUT, _GRAD_NEEDS_FWD = "fx3d_dgcnn_stat_count", ((512, 256), 0.5), True  # (train_step)
+
+    def _masks_of(self, dropout, B, on_dev):
+        return self._train_masks(dropout, B, on_dev)
+
+    def _train_bytes(self, N, B):
+        return _lib.query_bytes("fx3d_dgcnn_train_workspace_bytes", N, B, self.K, self.num_classes)
+
+    def _forward_train_call(self, x, N, B, masks, momentum, nb, intermediates, running):
+        """fx3d_dgcnn_forward_train on the device arrays ``x`` and ``masks`` (two, each possibly ``None``) with a workspace of ``nb``
+        bytes: ``(out, stats)`` -- ``probs`` and, with ``intermediates``, the optional outputs; the flat ``batch_stats`` and, with
+        ``running``, the flat ``running``."""
+        nc, K, f32 = self.num_classes, self.K, np.float32
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        optional = self._optional(N, B)
+        out = self._outputs(B, optional, intermediates)
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if running:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        ws = workspace(nb, tag="dgcnn_train")
+        _lib.call("fx3d_dgcnn_forward_train", self._params_dev().ptr, nc, K, x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
+                  momentum, out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
+                  stats["batch_stats"].ptr, stats["running"].ptr if running else None, ws.ptr, ws.nbytes, current_stream().handle)
+        return out, stats
+
+    def _grad_train_call(self, x, N, B, masks, out, batch_stats, glogits):
+        """fx3d_dgcnn_grad_train on device arrays, the forward's intermediates ``out`` and its flat ``batch_stats`` as it wrote
+        them: the flat gradient."""
+        nc, K = self.num_classes, self.K
+        ws = workspace(_lib.query_bytes("fx3d_dgcnn_grad_train_workspace_bytes", N, B, K, nc), tag="dgcnn_grad_train")
+        gp = DeviceArray.empty((self.param_count,), np.float32)
+        _lib.call("fx3d_dgcnn_grad_train", self._params_dev().ptr, nc, K, x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
+                  *(out[k].ptr for k in self._FWD_KEYS), batch_stats.ptr, glogits.ptr, gp.ptr, None, None, None, ws.ptr, ws.nbytes,
+                  current_stream().handle)
+        return gp
 
     def _grad_call(self, X, glogits, input_grad, intermediates, fwd=None, train=False, dropout=None):
         """fx3d_dgcnn_grad (``train``: fx3d_dgcnn_grad_train, with the dropout multipliers and with the intermediates and batch

@@ -1383,6 +1383,60 @@ FX3D_API fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_
                                            const float *batch_stats, const float *glogits, float *gparams, float *gx, float *gx2,
                                            float *gx1, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
+/* ---- Training step: what the loop of examples/pointnet_classification.jl / dgcnn_classification.jl does around the model ------------
+ *   loss(x, y) = crossentropy(m(x), y);  opt = Flux.ADAM(lr);  gs = gradient(ps) do ... end;  Flux.update!(opt, ps, gs)
+ * Three entry points between and after fx3d_*_forward_train and fx3d_*_grad_train.  Nothing is fused (-ffp-contract=off), every
+ * operation below is rounded once, in the precision named.  Float32 and int32 arrays may be aligned to 4 bytes only; the Float64
+ * and UInt64 arrays (loss, betap, counter_dev) must be 8-byte aligned, FX3D_ERR_INVALID_ARG otherwise.  Launches on `s` only: no
+ * host synchronisation, no allocation, no host memory or environment read (graph-capturable).  Plain stores, no atomics; the results
+ * are the same bits from run to run and those of the restatement tests/train_step_ref.py (the loss up to the device's log).
+ *
+ * fx3d_crossentropy: Flux.crossentropy(probs, onehot(labels)) with its gradient at the logits, and the tutorial's accuracy count.
+ *   probs (num_classes,B): a classifier's output.  labels: B int32 on the device, 0-based.
+ *   glogits[o,b] = (probs[o,b] - [o == labels[b]]) / Float32(B): one Float32 subtraction (of 1.0f or of +0.0f), one Float32 division.
+ *   loss (one Float64) = (-(sum_b log((double)probs[labels[b],b]))) / (double)B, the sum one chain from +0.0 in ascending b; log is
+ *     the device's double log (not pinned to a bit pattern, as the softmax's exp is not).  probs = 0 at a label gives +Inf.
+ *   counts[0]: the clouds whose first maximum over the classes is the label -- the scan best = 0; for o = 1 .. : probs[o,b] >
+ *     probs[best,b] moves best to o (Julia's argmax on a column without NaN: the lowest index on a tie).
+ *   counts[1]: the labels outside [0, num_classes).  Such a label adds NaN to the loss, subtracts +0.0f everywhere in its column,
+ *     is never used as an index into probs and does not count in counts[0].
+ *   One launch of one block.  Refusals (FX3D_ERR_INVALID_ARG): a NULL pointer, num_classes < 1, B < 1, loss not 8-byte aligned.
+ *
+ * fx3d_dropout_mask: the multipliers of Dropout(p) in training mode, drawn on the device: Flux's rand > p ? T(1 / q) : T(0).
+ *   Element e takes word e mod 4 of philox4x32_10 on the counter (e div 4, stream_id, 0, 0) under the key (low, high half of
+ *   seed + (counter_dev ? *counter_dev : 0)), the convention of fx3d_sample_points_draw;  u = (float)(word >> 8) 2^-24;
+ *   out[e] = ((double)u > p) ? (float)(1.0 / (1.0 - p)) : 0.0f.  The draws are the library's, not Julia's.  fx3d_counter_add
+ *   advances counter_dev between steps; stream_id tells the masks of one step apart.
+ *   Refusals: out NULL, n < 0 or n > 2^34, p outside [0, 1) or NaN, stream_id < 0, counter_dev not 8-byte aligned.  n = 0: nothing is done.
+ *
+ * fx3d_adam_step: Flux.Optimise.ADAM(eta, (beta1, beta2)) over one flat buffer of n elements, what Flux's broadcast computes with
+ *   Float64 hyper-parameters and Float32 arrays.  g: the gradient.  m, v: the optimiser's state, zero before the first step.
+ *   betap: two Float64 on the device, (beta1, beta2) before the first step.  x: the parameters.  Flux's eps is 1e-8.  Per element:
+ *     m <- Float32((beta1 (double)m) + ((1 - beta1) (double)g))             1 - beta1 in Float64; product, product, sum
+ *     v <- Float32((beta2 (double)v) + ((1 - beta2) (double)(g (*) g)))     g (*) g the FLOAT32 product (Julia's g^2 on a Float32 array)
+ *     d <- Float32((((double)m / (1 - betap[0])) / (sqrt((double)v / (1 - betap[1])) + eps)) eta)     the new m and v, as stored
+ *     x <- x - d                                                            Float32
+ *   with the Float64 divisions and the square root correctly rounded.  After all elements: betap <- betap .* (beta1, beta2), a
+ *   running Float64 product, not a power.  So g = +0 on zero state gives d = +0 and leaves every bit of x (-0.0 too); g = 1e30f
+ *   makes g (*) g, hence v, +Inf and d = 0; NaN propagates.
+ *   running, stat_map, nstat (optional; nstat = 0: ignored): x[stat_map[i]] = running[i] for i < nstat -- the running statistics
+ *   fx3d_*_forward_train returned, written into the mu / var slots of the parameters.  The gradient at those slots is +0 (the
+ *   training-mode adjoints write it so), so ADAM's own result there is the old value; the write of `running` comes after it:
+ *   The entry is two launches: the elements (betap is only read), then a finishing launch, ordered behind the first by the stream,
+ *   which writes the mapped slots and advances betap.  No block reads betap while another thread writes it, and a mapped slot ends
+ *   as running[i] whatever ADAM computed there.  An index of stat_map outside [0, n) is skipped.
+ *   The element launch moves 28 bytes per element, as float4 where the four arrays reach a 16-byte boundary after the same number
+ *   of elements (those and the tail go one by one), one by one otherwise.
+ *   Refusals: n < 0, nstat < 0, a NULL g, m, v, betap or x, nstat > 0 without running and stat_map, betap not 8-byte aligned.
+ *   n = 0: betap advances and nothing else happens. */
+FX3D_API fx3d_status fx3d_crossentropy(const float *probs, const int32_t *labels, int32_t num_classes, int32_t B, float *glogits,
+                                       double *loss, int32_t *counts, fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_dropout_mask(int64_t n, double p, uint64_t seed, const uint64_t *counter_dev, int32_t stream_id, float *out,
+                                       fx3d_stream_t s);
+FX3D_API fx3d_status fx3d_adam_step(int64_t n, double eta, double beta1, double beta2, double eps, const float *g, float *m, float *v,
+                                    double *betap, float *x, const float *running, const int32_t *stat_map, int64_t nstat,
+                                    fx3d_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
