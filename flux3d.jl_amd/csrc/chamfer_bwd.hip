@@ -696,6 +696,9 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
     for (int k = 0; k < 2; ++k) ordered = ordered && (!side[k]->gverts || (side[k]->vf_rowptr && sg::sg_fits(side[k]->Fmax, cnt[k])));
     FX3D_REQUIRE(!step_x.vel || (ordered && ax.gverts), "%s: the optimiser step needs the ordered form (vertex -> face table, draws that fit "
                  "fx3d_sample_points_bwd_ordered)", fn);
+    // (refused before any device work: the regularisers' stand-alone adjoint below writes gverts_x and total_dev)
+    const SampledWs W = SampledWs::plan(N, M, B, ax.Fmax, ax.gverts != nullptr);
+    if (ordered) FX3D_TRY(ws_check(fn, "workspace", ws, ws_bytes, W.total));
     // the fit iteration's regularisers (fx3d_mesh_reg): their adjoint writes gverts_x, the sampling adjoint then accumulates on top
     meshreg::Ride ride_v{};
     const meshreg::Ride *ride = nullptr;
@@ -717,8 +720,6 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
         // was built and measured equal inside the fit loop's graph, 104 against 105 us per iteration: the gather's tables, 7 us, do
         // overlap the rows there, but its tail -- acquire, staging, walk: ~9 us -- does not shrink; not kept: a bounded spin and a
         // dispatch-order argument for nothing.)
-        const SampledWs W = SampledWs::plan(N, M, B, ax.Fmax, ax.gverts != nullptr);
-        FX3D_TRY(ws_check(fn, "workspace", ws, ws_bytes, W.total));
         unsigned char *w = static_cast<unsigned char *>(ws);
         float *const gs[2] = {reinterpret_cast<float *>(w + W.gsx), reinterpret_cast<float *>(w + W.gsy)};
         unsigned char *tb[2] = {w + W.tbx, w + W.tby};

@@ -33,7 +33,24 @@
  *   - the caller owns every buffer; the library keeps no pointer past return.
  *   - ops are asynchronous on `stream` (NULL = the device's default stream) unless they have a
  *     host output, which makes them synchronise that stream before returning.
- *   - scratch is caller-provided: query the size with the matching *_workspace_bytes().
+ *   - scratch is caller-provided: query the size with the matching *_workspace_bytes().  A workspace is recycled memory of exactly
+ *     that size: its contents on entry are ARBITRARY (a call reads no workspace word that it, or the documented earlier call of its
+ *     pair, has not written; results do not depend on what the bytes held), and no byte at or after ws + the queried size is
+ *     written.  What a workspace carries from one call to the next, same ws, same sizes, same stream, nothing else run on it in
+ *     between: fx3d_voxel_mesh_count -> _emit;  fx3d_edges_dev_count -> _emit;  fx3d_sample_points_cdf / _cdf_pair -> _draw /
+ *     _draw_pair / _draw_pair_reg (the CDF; it stays valid while the vertices do);  fx3d_mesh_losses -> fx3d_mesh_losses_bwd with
+ *     reuse_forward != 0, and fx3d_mesh_reg.ws from fx3d_sample_points_draw_pair_reg to fx3d_chamfer_sampled_bwd_step_reg (the
+ *     Laplacian's unit rows).  fx3d_chamfer_sums -> fx3d_chamfer_finalize[_many] carry sums_dev, not the workspace.  Nothing else
+ *     survives a call.  A workspace that is NULL where the query is positive, or shorter than the query, is refused before any
+ *     device work, outputs and workspace untouched: FX3D_ERR_WORKSPACE by the chamfer entry points (fx3d_chamfer_sums, _fwd,
+ *     _fwd_bwd, _fwd_sharded[_async], _loss_pairwise_f32, _sampled_bwd[_step[_reg]]), fx3d_segment_minmax, fx3d_normalize, the
+ *     normals adjoints, fx3d_index_upload, the mesh losses (fx3d_edge_loss, fx3d_laplacian_loss, fx3d_mesh_losses[_bwd],
+ *     fx3d_mesh_reg.ws) and the sampler (fx3d_sample_points[_cdf[_pair] / _draw[_pair[_reg]]]); FX3D_ERR_INVALID_ARG by the
+ *     models (PointNet, DGCNN, EdgeConv: every entry point), the device topology builders (fx3d_edges_dev_*,
+ *     fx3d_laplacian_dev_csr, fx3d_vertex_faces_dev, fx3d_faces_padded_to_packed_dev) and the voxel entry points
+ *     (fx3d_pointcloud_to_voxel, fx3d_trimesh_to_voxel, fx3d_voxel_mesh_count / _emit).  Two entry points fall back instead, with
+ *     the same results: fx3d_knn_ws (it then is fx3d_knn) and the pruned tier of the chamfer forward (see
+ *     fx3d_chamfer_workspace_bytes).  DESIGN.md 2.2 lists every entry point and the test that holds it.
  *   - floating point is Float32 without fused multiply-add on the result-defining path
  *     (distance, area, sampling), so results are bit-identical to the CPU restatement.
  */
