@@ -270,13 +270,14 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
             }
         }
     }
-    if constexpr (PRUNE) {  // the sort's counters (in the waves' scratch, idle until the passes) and the query groups' boxes: the cloud pass's barrier orders this
+    // (PRUNE) the query cloud's box as keys (lo keys, -, hi keys, -): 32 bytes behind the lane tiles' boxes
+    [[maybe_unused]] int *const qbb = reinterpret_cast<int *>(wq + (kHThreads / 64) * 96) + 64 * 2 * 4;
+    if constexpr (PRUNE) {  // the sort's counters (in the waves' scratch, idle until the passes) and the query cloud's box: the cloud pass's barrier orders this
         unsigned int *zc = reinterpret_cast<unsigned int *>(wres);
         for (int i = tid; i < 1040 + 16 * 256; i += kHThreads) zc[i] = 0u;
-        int *gb = reinterpret_cast<int *>(wq + (kHThreads / 64) * 96) + 64 * 8;
-        for (int i = tid; i < kHGroupsMax * 8; i += kHThreads) gb[i] = (i & 4) ? (int)0x80000000 : 0x7fffffff;  // lo keys: +max, hi keys: -max
+        if (tid < 8) qbb[tid] = (tid & 4) ? (int)0x80000000 : 0x7fffffff;  // lo keys: +max, hi keys: -max
     }
-    // (PRUNE) The query cloud's bounding box as integer keys, into the spare group slot (`qbb`; initialised with the groups' above): the
+    // (PRUNE) The query cloud's bounding box as integer keys, into `qbb` (initialised above): the
     // frame of the grid the queries are sorted in.  It needs the four rows requested above and nothing of the cloud pass, so it
     // runs between that pass's two barriers, where fifteen waves would otherwise only wait for the first wave's cross-wave
     // reduction -- not in the counting phase behind them, which is bound by the VALU (it stood there: 0.3 us of 34.8 at B = 32,
@@ -284,7 +285,6 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
     // better and spilt two more scalars).  Like the rows it is guarded by the entry loads' condition, not by `sorted_q`, which is
     // not known yet: without a sort the box goes unused.  Rows past the cloud (clamped loads) stay out; NaN keys enter as before.
     [[maybe_unused]] auto query_key_box = [&]() {
-        int *qbb = reinterpret_cast<int *>(wq + (kHThreads / 64) * 96) + (64 * 2 + kHGroupsMax * 2 - 2) * 4;
         int kl[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, kh[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 r4[wv * 4] = lo4; r4[wv * 4 + 1] = hi4; r4[wv * 4 + 2] = st4;
             }
         }
-        FX3D_PROBE_MARK(9);
+        FX3D_PROBE_MARK2(9);
         __syncthreads();
         FX3D_PROBE_MARK(10);
         static_assert(kHThreads / 64 == 16, "the cross-wave reduction below: one wave's row of 16 lanes, one lane per wave");
@@ -519,12 +519,6 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
         const bool sorted_q = do_sort && NQ <= 4 * kHThreads;
         // (its rows qv[e] -- point 256 wave + 64 e + lane -- were requested at the kernel's entry)
         FX3D_PROBE_MARK2(0);
-        int *gbox = reinterpret_cast<int *>(boxes + 64 * 2);  // [groups of 32 window rows] x (lo keys, -, hi keys, -)
-        auto group_box = [&](int wrow, float x, float y, float z) {  // a query of the window: into the box of its group (image frame)
-            int *g = gbox + (wrow >> 5) * 8;
-            atomicMin(g + 0, fkey((x - mu[0]) * sc)); atomicMin(g + 1, fkey((y - mu[1]) * sc)); atomicMin(g + 2, fkey((z - mu[2]) * sc));
-            atomicMax(g + 4, fkey((x - mu[0]) * sc)); atomicMax(g + 5, fkey((y - mu[1]) * sc)); atomicMax(g + 6, fkey((z - mu[2]) * sc));
-        };
         if (do_sort) {
             float4 cv[4];
 #pragma unroll
@@ -618,7 +612,6 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 }
                 count_cells4(cval, ct, ccr, [&](unsigned int c, unsigned int n) { return atomicAdd(&ccnt[c], n); });
             }
-            const int *qbb = reinterpret_cast<const int *>(boxes + 64 * 2 + kHGroupsMax * 2 - 2);  // the query cloud's box as keys (query_key_box, in the cloud pass)
             FX3D_PROBE_MARK2(2);
             __syncthreads();
             FX3D_PROBE_MARK2(3);
@@ -718,30 +711,14 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                     if (qp < NQ) {
                         const unsigned int t = qcr[e] >> 16;
                         const int rank = (int)(qtot[t] + ((qwh[wv * 256 + (t >> 1)] >> (16u * (t & 1u))) & 0xffffu) + (qcr[e] & 0xffffu));
-                        if (rank >= qw0 && rank < qw1) {
-                            qsw[rank - qw0] = (unsigned short)qp;  // (the ranks are a permutation: every slot of the window is written)
-                            group_box(rank - qw0, qv[e].x, qv[e].y, qv[e].z);
-                        }
+                        // (the ranks are a permutation: every slot of the window is written)
+                        if (rank >= qw0 && rank < qw1) qsw[rank - qw0] = (unsigned short)qp;
                     }
                 }
             }
         }
         if (!sorted_q) {  // index order: the block's window of the query cloud as it lies in memory
-            // (the 32 rows of a group are 32 consecutive lanes here: their box by four DPP row steps, two lanes per group go to LDS --
-            //  32 lanes on one LDS address would serialise)
-            for (int q0 = qw0 + wv * 64; q0 < qw1; q0 += kHThreads) {
-                const int qp = q0 + lane;
-                const P3 r = *reinterpret_cast<const P3 *>(qb + (size_t)(qp < qw1 ? qp : qw1 - 1) * 3);  // (lanes past the window repeat its last row)
-                if (qp < qw1) qsw[qp - qw0] = (unsigned short)qp;
-                const int kx = fkey((r.x - mu[0]) * sc), ky = fkey((r.y - mu[1]) * sc), kz = fkey((r.z - mu[2]) * sc);
-                const int lx = row_mm_key<false>(kx), ly = row_mm_key<false>(ky), lz = row_mm_key<false>(kz);
-                const int hx = row_mm_key<true>(kx), hy = row_mm_key<true>(ky), hz = row_mm_key<true>(kz);
-                if ((lane & 15) == 0 && qp < qw1) {
-                    int *g = gbox + ((qp - qw0) >> 5) * 8;
-                    atomicMin(g + 0, lx); atomicMin(g + 1, ly); atomicMin(g + 2, lz);
-                    atomicMax(g + 4, hx); atomicMax(g + 5, hy); atomicMax(g + 6, hz);
-                }
-            }
+            for (int qp = qw0 + tid; qp < qw1; qp += kHThreads) qsw[qp - qw0] = (unsigned short)qp;
         }
         // (the barrier behind the image staging below orders these stores -- and the image's -- before their readers)
         FX3D_PROBE_MARK2(8);
@@ -1056,11 +1033,21 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
             const int nltp = nblk / kHLT;      // lane tiles of the chunk; index nltp = the padding blocks
             float bd = INFINITY;
             {
-                // the box of the wave's 32 queries (group tp 16 + wave of the window): gathered when the window was laid out
-                const int4 *gq = reinterpret_cast<const int4 *>(boxes + 64 * 2) + (tp * (kHThreads / 64) + wv) * 2;
-                const int4 gl = gq[0], gh = gq[1];
-                const float qlx = fkey_inv(gl.x), qly = fkey_inv(gl.y), qlz = fkey_inv(gl.z);
-                const float qhx = fkey_inv(gh.x), qhy = fkey_inv(gh.y), qhz = fkey_inv(gh.z);
+                // the box of the wave's 32 queries (image frame), reduced inside the wave from the rows it has just loaded: lanes l and
+                // l + 32 hold query l, so DPP rows 0 and 1 cover the group and meet in scalar registers.  A lane past the window
+                // repeats the window's last query, one of this group; NaN keys lie beyond the infinities, as in any key reduction here.
+                // (Until profiles/nn1_entry_ab.txt the window's placement gathered these boxes by six LDS atomics per query into 4 KiB
+                //  of LDS, the same Float32 expressions on the same values: the boxes are bit for bit what they were.)
+                int gl[3], gh[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const int k = fkey((qr[d] - mu[d]) * sc);
+                    const int a = row_mm_key<false>(k), b2 = row_mm_key<true>(k);
+                    gl[d] = imm<false>(__builtin_amdgcn_readlane(a, 0), __builtin_amdgcn_readlane(a, 16));
+                    gh[d] = imm<true>(__builtin_amdgcn_readlane(b2, 0), __builtin_amdgcn_readlane(b2, 16));
+                }
+                const float qlx = fkey_inv(gl[0]), qly = fkey_inv(gl[1]), qlz = fkey_inv(gl[2]);
+                const float qhx = fkey_inv(gh[0]), qhy = fkey_inv(gh[1]), qhz = fkey_inv(gh[2]);
                 if (lane < nltp) {
                     const float4 lo = boxes[lane * 2], hi = boxes[lane * 2 + 1];
                     const float gx = fmaxf(fmaxf(lo.x - qhx, qlx - hi.x), 0.0f), gy = fmaxf(fmaxf(lo.y - qhy, qly - hi.y), 0.0f);
@@ -1648,7 +1635,7 @@ namespace fx3d {
 
 size_t nn1_f16_lds_bytes(int chunk) { return (size_t)chunk * 8 * sizeof(float) + kHScratchBytes; }
 
-constexpr size_t kHBoxBytes = 64 * 2 * sizeof(float4) + kHGroupsMax * 32;  // (PRUNE) LDS: the lane tiles' boxes + the query groups' boxes
+constexpr size_t kHBoxBytes = 64 * 2 * sizeof(float4) + 32;  // (PRUNE) LDS: the lane tiles' boxes + the query cloud's key box
 
 // The instantiation a launch runs: pruned when it has scratch (p.pscr), else with the subsets' merge when it was asked for.
 template <bool WANT_IDX>

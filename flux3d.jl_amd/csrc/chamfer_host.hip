@@ -238,7 +238,6 @@ const char *plan_kernel_name(const Plan &pl, int D) {
 int prune_rows_per_block(const Plan &pl, int N, int M, int D) {
     const int maxc = N > M ? N : M;
     if (plan_kernel(pl, D) != NN1_F16 || pl.nsplit != 1 || pl.tail != 0 || maxc > pl.chunk || maxc < 1024 || !opt(OPT_NN1_PRUNE)) return 0;
-    if ((pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 16 + 2 > kHGroupsMax - 1) return 0;  // (the query groups' boxes: LDS for eight passes per block)
     // one pass per block does not repay the sort (measured at B = 8 .. 16 x 4096: 36 against 30 us; two passes -- C2 -- 46 against 53)
     if ((pl.tpb < pl.tpb_y ? pl.tpb : pl.tpb_y) < 2) return 0;
     return kHScrCand + (pl.tpb > pl.tpb_y ? pl.tpb : pl.tpb_y) * 512 + kHTail;

@@ -105,7 +105,6 @@ constexpr int kHTail = 64;        // a cloud of up to kHChunkMax + kHTail points
                                   // compared exactly by every query (N = M = 4097 was 2.1 x N = M = 4096: two half-empty chunks,
                                   // three rounds of blocks), and <= 64 queries beyond a block's passes are one more pass of one wave
 constexpr int kHScrCand = kHChunkMax + 64;  // (PRUNE) candidate slots of a block's scratch: the image's positions, its two padding blocks included
-constexpr int kHGroupsMax = 8 * 16 + 2 + 1;  // (PRUNE) 32-query groups of a block's window: up to eight passes + the folded remainder; + one slot: the query cloud's box
 
 // nn1_tiny_kernel's geometry (nn1_exact.hip)
 constexpr int kTyThreads = 256;

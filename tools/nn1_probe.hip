@@ -106,8 +106,9 @@ int main(int argc, char **argv) {
         std::vector<unsigned long long> p2(256 * 16);
         hipMemcpyFromSymbol(p2.data(), HIP_SYMBOL(g_probe2), p2.size() * 8);
         for (int b = 0; b < 3; ++b) {
+            // (9: the first wave's statistics are in LDS, in front of barrier 1 -- a slot of its own: stamp 9 of the list below is the tail's)
             printf("block %d sort-phase stamps (cycles from the kernel's start):", b);
-            for (int k = 0; k <= 8; ++k) if (p2[b * 16 + k]) printf(" %d:%llu", k, p2[b * 16 + k] - pr[b * 16]);
+            for (int k = 0; k <= 9; ++k) if (p2[b * 16 + k]) printf(" %d:%llu", k, p2[b * 16 + k] - pr[b * 16]);
             printf("\n");
         }
     }
