@@ -7,9 +7,10 @@
 // The maximum over the N points picks ONE point per (channel, cloud), so conv_3's adjoint is a gather: 1024 rows of W3 per cloud
 // for gx2 and 1024 rows of x2 per cloud for H3, not the dense (256 x 1024 x N) contractions.  Per call, after the forward where
 // the caller gives no intermediates:
-//   dgcnn_argmax_kernel: the forward's conv_3 again, block for block (64 points, the x2 tile in one LDS image of stride 258,
-//     mfma_slab<256> and epilogue<kBnRelu>: the forward's bits), compared with pooled where that is positive; per (tile, channel)
-//     the smallest matching point, a lane minimum over its 32 rows and one shuffle across the half-waves (the forward's fold).
+//   dgcnn_argmax_kernel (dgcnn_net.h's conv3_winners, shared with the training-mode adjoint): the forward's conv_3 again, block for
+//     block (64 points, the x2 tile in one LDS image of stride 258, mfma_slab<256> and epilogue<kBnRelu>: the forward's bits),
+//     compared with pooled where that is positive; per (tile, channel) the smallest matching point, a lane minimum over its 32 rows
+//     and one shuffle across the half-waves (the forward's fold).
 //   dgcnn_head_bwd_kernel: one block per cloud.  Thread c folds the tile minima of channel c into n*(c); a4 and a5 are computed
 //     again as the forward's head computes them (dense_chain); then g5, d5, g4, d4 and gp, one thread per element, each one chain
 //     over the layer's outputs (transposed_chain: a thread's weights are one contiguous row of the (out, in) array).  a4, a5, d5,
@@ -19,50 +20,27 @@
 //     that wins nothing gets +0.  No atomics: a point has one owner.
 //   dgcnn_conv3_pgrad_kernel: one block per output channel c, thread i owns H3[i, c]: the chain over the clouds that have a
 //     winner of x2[i, n*(c, b), b] d3[c, b]; then the four families of the channel.
-//   dense_sums_kernel (fc_4, fc_5, fc_6): one thread per element of H and h, the chain over the clouds.  fc_6's go to gparams as
-//     they are.  dense_finish_kernel (fc_4, fc_5): the four families from H and h, one thread per element of the layer's block.
+//   dense_sums_kernel (pointnet_grad.hip's, through launch_dense_sums; fc_4, fc_5, fc_6): one thread per element of H and h, the
+//     chain over the clouds.  fc_6's go to gparams as they are.  dense_finish_kernel (fc_4, fc_5): the four families from H and h,
+//     one thread per element of the layer's block.
 //   fx3d_edgeconv_grad on ec2 (gout = gx2 -> gx1), then on ec1 (gout = gx1 -> gx).
-#include <climits>
-
 #include "dgcnn_net.h"
 
 using namespace fx3d;
 using namespace fx3d::mlp;
+using pointnet::grad_block;
+using pointnet::GradBlock;
+using pointnet::kNoPoint;
+using pointnet::mut;
 
 namespace {
 
-constexpr int kNoPoint = INT_MAX;  // a tile in which no point reproduces pooled
-
+// the winners: dgcnn_net.h's conv3_winners
 __global__ __launch_bounds__(kPtThreads) void dgcnn_argmax_kernel(const float *__restrict__ x2, const Conv c,
                                                                   const float *__restrict__ pooled, int32_t *__restrict__ tfirst,
                                                                   int N, int ntiles) {
     extern __shared__ float lds[];
-    const int tile = blockIdx.x, b = blockIdx.y;
-    const int p0 = tile * kTile;
-    const int nvalid = min(kTile, N - p0);
-    load_x2_tile(lds, x2, b, N, p0, nvalid);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
-    const float *a0 = lds + j * kLd3 + h, *a1 = a0 + 32 * kLd3;
-    int32_t *out = tfirst + ((size_t)b * ntiles + tile) * kFeat;
-    for (int sl = wave; sl < kFeat / 32; sl += kPtThreads / 64) {
-        const int o = sl * 32 + j;
-        f32x16 acc0 = {0}, acc1 = {0};
-        mfma_slab<256>(a0, a1, c.W + (size_t)256 * o, h, acc0, acc1);
-        const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = sqrtf(c.bn.v[o] + kBnEps);
-        const float pv = pooled[(size_t)b * kFeat + o];
-        const float tgt = pv > 0.0f ? pv : __int_as_float(0x7fc00000);  // NaN equals nothing: no winner
-        int first = kNoPoint;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int p = mfma_row(r, h);
-            const float v0 = epilogue<kBnRelu>(acc0[r], bi, g, be, mu, sd), v1 = epilogue<kBnRelu>(acc1[r], bi, g, be, mu, sd);
-            if (p < nvalid && v0 == tgt) first = min(first, p0 + p);
-            if (p + 32 < nvalid && v1 == tgt) first = min(first, p0 + p + 32);
-        }
-        first = min(first, __shfl_xor(first, 32, 64));
-        if (h == 0) out[o] = first;
-    }
+    conv3_winners<false>(lds, x2, c, pooled, tfirst, nullptr, N, ntiles);
 }
 
 struct HeadBwdArgs {
@@ -155,9 +133,6 @@ __global__ __launch_bounds__(kPtThreads) void dgcnn_gx2_kernel(const int32_t *__
     }
 }
 
-// the gradient's block of a conv or dense layer with its BatchNorm: W | b | gamma | beta | mu | var
-struct GradBlock { float *W, *b, *g, *be, *m, *v; };
-
 __global__ __launch_bounds__(256) void dgcnn_conv3_pgrad_kernel(const float *__restrict__ x2, const int32_t *__restrict__ nstar,
                                                                 const float *__restrict__ d3, const Conv c3, const GradBlock g,
                                                                 int N, int B) {
@@ -185,11 +160,6 @@ __global__ __launch_bounds__(256) void dgcnn_conv3_pgrad_kernel(const float *__r
         g.m[c] = 0.0f;
         g.v[c] = 0.0f;
     }
-}
-
-// H[o, i] = the chain over b of d[o, b] a[i, b], h[o] = the sum over b of d[o, b]: one thread per element (dense_sums)
-__global__ __launch_bounds__(256) void dense_sums_kernel(const DenseSums s) {
-    dense_sums(s, (long long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // the four families of a dense layer with BatchNorm from H and h (flux3d_hip.h); mu and var: +0
@@ -220,8 +190,12 @@ __global__ __launch_bounds__(256) void dense_finish_kernel(const DenseFinish f) 
     }
 }
 
-float *mut(const float *p) { return const_cast<float *>(p); }
-GradBlock grad_block(const float *W, const float *b, const Bn &bn) { return GradBlock{mut(W), mut(b), mut(bn.g), mut(bn.b), mut(bn.m), mut(bn.v)}; }
+// the gradient's block of a dense layer with its BatchNorm
+GradBlock dense_block(const Dense &d, const Bn &bn) {
+    GradBlock g = grad_block(bn);
+    g.W = mut(d.W); g.b = mut(d.b);
+    return g;
+}
 
 // The workspace: the forward's intermediates and probabilities (used where the caller gives none) | the per-tile first
 // matches | n* | a4, a5, d5, d4, d3, dz3 | H and h of fc_4 and fc_5 | gx2, gx1 (used where the caller gives none) | one scratch
@@ -295,28 +269,23 @@ fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classes, int32_
     const Net n = dgcnn_layout(params_dev, num_classes), gn = dgcnn_layout(gparams, num_classes);
     hipStream_t st = as_stream(s);
     char *wsb = static_cast<char *>(ws);
-    auto f32 = [&](size_t at) { return reinterpret_cast<float *>(wsb + at); };
-    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(wsb + at); };
+    const pointnet::WsView v{wsb};
 
     if (given == 0) {  // the forward, into the workspace
-        if ((r = fx3d_dgcnn_forward(params_dev, num_classes, K, x, N, B, f32(w.probs), nullptr, i32(w.idx1), f32(w.x1), i32(w.idx2),
-                                    f32(w.x2), f32(w.pooled), wsb + w.scratch, w.fwd_bytes, s)) != FX3D_OK) return r;
-        idx1 = i32(w.idx1); x1 = f32(w.x1); idx2 = i32(w.idx2); x2 = f32(w.x2); pooled = f32(w.pooled);
+        if ((r = fx3d_dgcnn_forward(params_dev, num_classes, K, x, N, B, v.f32(w.probs), nullptr, v.i32(w.idx1), v.f32(w.x1), v.i32(w.idx2),
+                                    v.f32(w.x2), v.f32(w.pooled), wsb + w.scratch, w.fwd_bytes, s)) != FX3D_OK) return r;
+        idx1 = v.i32(w.idx1); x1 = v.f32(w.x1); idx2 = v.i32(w.idx2); x2 = v.f32(w.x2); pooled = v.f32(w.pooled);
     }
-    float *g2 = gx2 ? gx2 : f32(w.gx2), *g1 = gx1 ? gx1 : f32(w.gx1);
+    float *g2 = gx2 ? gx2 : v.f32(w.gx2), *g1 = gx1 ? gx1 : v.f32(w.gx1);
 
     // the point that took the maximum, per tile
-    if ((r = ensure_dynamic_lds(reinterpret_cast<const void *>(&dgcnn_argmax_kernel), (int)kConv3Lds, "dgcnn_argmax_kernel")) != FX3D_OK) return r;
-    {
-        ProfileScope prof("dgcnn_argmax", st);
-        hipLaunchKernelGGL(dgcnn_argmax_kernel, dim3(w.ntiles, B), dim3(kPtThreads), kConv3Lds, st, x2, n.c3, pooled, i32(w.tfirst), N, w.ntiles);
-        FX3D_LAUNCH_CHECK();
-    }
+    if ((r = pointnet::launch_tile(&dgcnn_argmax_kernel, "dgcnn_argmax_kernel", "dgcnn_argmax", kConv3Lds, w.ntiles, B, kPtThreads, st, x2,
+                                   n.c3, pooled, v.i32(w.tfirst), N, w.ntiles)) != FX3D_OK) return r;
     HeadBwdArgs hb{};
-    hb.tfirst = i32(w.tfirst); hb.ntiles = w.ntiles; hb.nc = num_classes; hb.pooled = pooled; hb.glogits = glogits;
+    hb.tfirst = v.i32(w.tfirst); hb.ntiles = w.ntiles; hb.nc = num_classes; hb.pooled = pooled; hb.glogits = glogits;
     hb.c3 = n.c3; hb.d4 = n.d4; hb.d5 = n.d5; hb.d6 = n.d6; hb.bn4 = n.bn4; hb.bn5 = n.bn5;
-    hb.nstar = i32(w.nstar); hb.a4 = f32(w.a4); hb.a5 = f32(w.a5); hb.g5 = f32(w.d5); hb.g4 = f32(w.d4);
-    hb.d3 = f32(w.d3); hb.dz3 = f32(w.dz3);
+    hb.nstar = v.i32(w.nstar); hb.a4 = v.f32(w.a4); hb.a5 = v.f32(w.a5); hb.g5 = v.f32(w.d5); hb.g4 = v.f32(w.d4);
+    hb.d3 = v.f32(w.d3); hb.dz3 = v.f32(w.dz3);
     {
         ProfileScope prof("dgcnn_head_bwd", st);
         hipLaunchKernelGGL(dgcnn_head_bwd_kernel, dim3(B), dim3(kHeadThreads), 0, st, hb);
@@ -331,22 +300,20 @@ fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classes, int32_
     {
         ProfileScope prof("dgcnn_conv3_pgrad", st);
         hipLaunchKernelGGL(dgcnn_conv3_pgrad_kernel, dim3(kFeat), dim3(256), 0, st, x2, hb.nstar, hb.d3, n.c3,
-                           grad_block(gn.c3.W, gn.c3.b, gn.c3.bn), N, B);
+                           grad_block(gn.c3), N, B);
         FX3D_LAUNCH_CHECK();
     }
     // the head's parameter sums over the clouds, and the families from them
     {
-        float *H4 = f32(w.sums), *h4 = H4 + (size_t)kFeat * 512, *H5 = h4 + 512, *h5 = H5 + (size_t)512 * 256;
+        float *H4 = v.f32(w.sums), *h4 = H4 + (size_t)kFeat * 512, *H5 = h4 + 512, *h5 = H5 + (size_t)512 * 256;
         const DenseSums s4{hb.g4, pooled, kFeat, 512, B, H4, h4}, s5{hb.g5, hb.a4, 512, 256, B, H5, h5},
             s6{glogits, hb.a5, 256, num_classes, B, mut(gn.d6.W), mut(gn.d6.b)};
-        const DenseFinish f4{H4, h4, n.d4, n.bn4, kFeat, 512, grad_block(gn.d4.W, gn.d4.b, gn.bn4)},
-            f5{H5, h5, n.d5, n.bn5, 512, 256, grad_block(gn.d5.W, gn.d5.b, gn.bn5)};
+        const DenseFinish f4{H4, h4, n.d4, n.bn4, kFeat, 512, dense_block(gn.d4, gn.bn4)},
+            f5{H5, h5, n.d5, n.bn5, 512, 256, dense_block(gn.d5, gn.bn5)};
         auto blocks = [](long long n) { return dim3((unsigned int)((n + 255) / 256)); };
         ProfileScope prof("dgcnn_dense_pgrad", st);
-        for (const DenseSums &q : {s4, s5, s6}) {
-            hipLaunchKernelGGL(dense_sums_kernel, blocks((long long)(q.nin + 1) * q.nout), dim3(256), 0, st, q);
-            FX3D_LAUNCH_CHECK();
-        }
+        for (const DenseSums &q : {s4, s5, s6})
+            if ((r = pointnet::launch_dense_sums(q, st)) != FX3D_OK) return r;
         for (const DenseFinish &q : {f4, f5}) {
             hipLaunchKernelGGL(dense_finish_kernel, blocks((long long)(q.nin + 5) * q.nout), dim3(256), 0, st, q);
             FX3D_LAUNCH_CHECK();

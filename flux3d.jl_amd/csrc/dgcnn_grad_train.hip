@@ -8,19 +8,18 @@
 // Through a batch-statistic BatchNorm the maximum no longer makes conv_3's adjoint a gather: gv = (((gy - mb) - xh mg) gamma) / sd
 // is non-zero at every row of every cloud, so conv_3's input gradient and its dW are dense contractions (pointnet_grad_train.hip's
 // last layer, with a 256-channel input in the 258-stride image and the block order conv, BatchNorm, relu).  Per call:
-//   dgcnn_gt_argmax_kernel: dgcnn_argmax_kernel (dgcnn_grad.hip) at the batch statistics -- the forward's tile, slabs and epilogue,
-//     compared with pooled where that is positive -- that also keeps conv + bias at the tile's first match.
+//   dgcnn_gt_argmax_kernel: dgcnn_net.h's conv3_winners<true>, the body of dgcnn_argmax_kernel (dgcnn_grad.hip) at the batch
+//     statistics -- the forward's tile, slabs and epilogue, compared with pooled where that is positive -- that also keeps conv +
+//     bias at the tile's first match.
 //   dgcnn_gt_head_{a,b,c}_kernel: the head's adjoint, one block per cloud, cut at fc5.bn and fc4.bn, ended at gy / xh of conv3.bn
 //     at the winners; PointNet's pointnet_gt_cloud_sums_kernel after each (launch_cloud_sums): one Float64 chain over b, the third
 //     over the clouds that have a winner.  Then dense_sums_kernel on fc_4, fc_5, fc_6 with gv in d's place, straight to gparams.
-//   dgcnn_gt_conv3_bwd_kernel: one block = 64 points of one cloud.  The forward's tile (load_x2_tile) and slabs (for_each_slab<256>),
-//     four slabs -- 128 outputs, one per wave -- at a time; LastChannel<kBnRelu> forms gv3 from the accumulators into a second LDS
-//     image; all four waves then carry the 16 (32 x 32) tiles of (256 inputs x 64 points), four per wave, on
-//     v_mfma_f32_32x32x2_f32 (back_mfma's operands), the accumulators kept across the eight groups: one chain over all 1024
-//     outputs ascending.  Stores gx2.
-//   dgcnn_gt_conv3_pgrad_kernel: one block of 8 waves per (cloud, 128 outputs): walks the cloud's tiles, recomputes the group's
-//     slabs (a wave: one slab, one 32-point half, mfma_slab_rt: the forward's chain), forms gv3 again (the same functor) and
-//     carries (256 x 128) of dW3 as one chain over the cloud's points (hsum_mfma's operands, four tiles per wave), db3 as one
+//   dgcnn_gt_conv3_bwd_kernel: one block = 64 points of one cloud.  The forward's tile (load_x2_tile), then pointnet_net.h's
+//     last_back<256, kLd3, kBnRelu>, the body of pointnet_gt_last_bwd_kernel: the slabs four at a time, LastChannel<kBnRelu> forms gv3
+//     from the accumulators into a second LDS image, the 16 (32 x 32) tiles of (256 inputs x 64 points), four per wave, kept across
+//     the eight groups: one chain over all 1024 outputs ascending.  Stores gx2.
+//   dgcnn_gt_conv3_pgrad_kernel: one block of 8 waves per (cloud, 128 outputs): pointnet_net.h's last_pgrad<256, kLd3, kBnRelu>, the
+//     body of pointnet_gt_last_pgrad_kernel: (256 x 128) of dW3 as one chain over the cloud's points, four tiles per wave, db3 as one
 //     Float32 chain.  pointnet_reduce_kernel (launch_reduce) then sums the clouds in ascending b into gparams.
 //   fx3d_edgeconv_grad_train on ec2 (gout = gx2 -> gx1), then on ec1 (gout = gx1 -> gx), sharing one scratch region.
 // One stream, no host synchronisation, no atomics: every sum has one owner and one order, which depends on (N, B, K, num_classes)
@@ -35,53 +34,26 @@ using namespace fx3d;
 using namespace fx3d::mlp;
 using pointnet::BnOut;
 using pointnet::bn_gv;
+using pointnet::kGroup;
 using pointnet::kNoPoint;
-using pointnet::LastChannel;
+using pointnet::kPgradThreads;
+using pointnet::last_back;
+using pointnet::last_pgrad;
+using pointnet::LastArgs;
+using pointnet::launch_tile;
 
 namespace {
 
-constexpr int kGroup = 128;         // conv_3's outputs per step: one slab per wave of a tile kernel
-constexpr int kPgradThreads = 512;  // dgcnn_gt_conv3_pgrad_kernel: 8 waves, two per slab of the group
 constexpr int kImg3 = kTile * kLd3, kImgD = kTile * kLd;
 constexpr size_t kDenseLds = (size_t)(kImg3 + kImgD) * sizeof(float);  // the x2 tile | gv3 of 128 outputs: 99328 bytes
 static_assert(kDenseLds <= 160 * 1024, "conv_3's dense adjoint: the 258-stride image and the 130-stride image of gv");
-static_assert(kGroup == 32 * (kPtThreads / 64), "one slab per wave");
 
-// ---- the winners ---------------------------------------------------------------------------------------------------------------------
-// dgcnn_argmax_kernel with what conv3.bn was given at the first match (tpre; 0 where the tile has none)
+// ---- the winners: dgcnn_net.h's conv3_winners, keeping what conv3.bn was given at the first match (tpre; 0 where the tile has none) ---
 __global__ __launch_bounds__(kPtThreads) void dgcnn_gt_argmax_kernel(const float *__restrict__ x2, const Conv c,
                                                                      const float *__restrict__ pooled, int32_t *__restrict__ tfirst,
                                                                      float *__restrict__ tpre, int N, int ntiles) {
     extern __shared__ float lds[];
-    const int tile = blockIdx.x, b = blockIdx.y;
-    const int p0 = tile * kTile;
-    const int nvalid = min(kTile, N - p0);
-    load_x2_tile(lds, x2, b, N, p0, nvalid);
-    __syncthreads();
-    const size_t out = ((size_t)b * ntiles + tile) * kFeat;
-    pointnet::for_each_slab<256, kLd3>(lds, c.W, kFeat, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
-        const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = pointnet::bn_sd(c.bn, o);
-        const float pv = pooled[(size_t)b * kFeat + o];
-        const float tgt = pv > 0.0f ? pv : __int_as_float(0x7fc00000);  // NaN equals nothing: no winner
-        int first = kNoPoint;
-        float pre = 0.0f;
-#pragma unroll
-        for (int r = 15; r >= 0; --r) {  // descending, the second half first: the last assignment is the smallest point
-            const int p = mfma_row(r, h) + 32;
-            if (p < nvalid && epilogue<kBnRelu>(acc1[r], bi, g, be, mu, sd) == tgt) { first = p0 + p; pre = acc1[r] + bi; }
-        }
-#pragma unroll
-        for (int r = 15; r >= 0; --r) {
-            const int p = mfma_row(r, h);
-            if (p < nvalid && epilogue<kBnRelu>(acc0[r], bi, g, be, mu, sd) == tgt) { first = p0 + p; pre = acc0[r] + bi; }
-        }
-        const int ofirst = __shfl_xor(first, 32, 64);
-        const float opre = __shfl_xor(pre, 32, 64);
-        if (h == 0) {
-            tfirst[out + o] = min(first, ofirst);
-            tpre[out + o] = ofirst < first ? opre : pre;
-        }
-    });
+    conv3_winners<true>(lds, x2, c, pooled, tfirst, tpre, N, ntiles);
 }
 
 // ---- the head ------------------------------------------------------------------------------------------------------------------------
@@ -184,99 +156,20 @@ __global__ __launch_bounds__(kHeadThreads) void dgcnn_gt_head_c_kernel(const Hea
     a.gy3[at] = a.nstar[at] >= 0 ? gp : 0.0f;
 }
 
-// ---- conv_3, dense -------------------------------------------------------------------------------------------------------------------
-struct Conv3Args {
-    const float *x2;       // (256, N, B)
-    Conv c3;               // at the batch statistics
-    const int32_t *nstar;  // (1024, B)
-    const float *gy3;      // (1024, B): the gradient at conv3.bn's output, at the winner
-    const float *mb, *mg;  // (1024)
-    float *gx2;            // (256, N, B)
-    float *Hc, *hc;        // (256, 1024, B), (1024, B): dW3 and db3 of each cloud
-    int N, ntiles;
-};
-
-__global__ __launch_bounds__(kPtThreads) void dgcnn_gt_conv3_bwd_kernel(const Conv3Args a) {
+// ---- conv_3, dense: pointnet_net.h's last_back and last_pgrad at CIN = 256, the image stride kLd3, the block order conv, BatchNorm, relu
+__global__ __launch_bounds__(kPtThreads) void dgcnn_gt_conv3_bwd_kernel(const LastArgs a) {
     extern __shared__ float lds[];
-    float *X = lds, *D = lds + kImg3;
-    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int tile = blockIdx.x, b = blockIdx.y;
     const int p0 = tile * kTile;
     const int nvalid = min(kTile, a.N - p0);
-    load_x2_tile(X, a.x2, b, a.N, p0, nvalid);
+    load_x2_tile(lds, a.in, b, a.N, p0, nvalid);
     __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, j = lane & 31;
-    f32x16 back[4] = {{0}, {0}, {0}, {0}};  // tiles t = wave + 4 u of (8 x 32 input channels) x (2 halves), as back_mfma numbers them
-    pointnet::for_each_slab<256, kLd3>(X, a.c3.W, kFeat, [&](int o, int, const f32x16 &acc0, const f32x16 &acc1) {
-        const int col = o & (kGroup - 1), o0 = o - col;  // every wave is in the same group of 128 outputs
-        LastChannel<kBnRelu>(a.c3, a, o, b, p0).store(D, col, h, nvalid, acc0, acc1);
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = wave + 4 * u, half = t & 1, ci = (t >> 1) * 32 + j;
-            const float *ap = D + (half * 32 + j) * kLd + h, *wp = a.c3.W + ci + (size_t)256 * (o0 + h);
-#pragma unroll 8
-            for (int q = 0; q < kGroup; q += 2)
-                back[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[q], wp[(size_t)256 * q], back[u], 0, 0, 0);
-        }
-        __syncthreads();
-    });
-    float *g = a.gx2 + ((size_t)b * a.N + p0) * 256;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int t = wave + 4 * u, half = t & 1, ci = (t >> 1) * 32 + j;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int p = half * 32 + mfma_row(r, h);
-            if (p < nvalid) g[(size_t)p * 256 + ci] = back[u][r];
-        }
-    }
+    last_back<256, kLd3, kBnRelu>(lds, lds + kImg3, a.c3, a, b, p0, nvalid);
 }
 
-// block (k, b): dW3[i, o] and db3[o] of cloud b for o in [128 k, 128 k + 128): one chain over the cloud's points ascending.  8 waves:
-// wave w recomputes slab w & 3 of the group for the 32-point half w >> 2, and owns the four (32 x 32) tiles of dW3 with the input
-// channels 128 (w >> 2) .. + 127 and the outputs of slab w & 3.
-__global__ __launch_bounds__(kPgradThreads) void dgcnn_gt_conv3_pgrad_kernel(const Conv3Args a) {
+__global__ __launch_bounds__(kPgradThreads) void dgcnn_gt_conv3_pgrad_kernel(const LastArgs a) {
     extern __shared__ float lds[];
-    float *A = lds, *D = lds + kImg3;
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, j = lane & 31, part = wave >> 2;
-    const int o0 = blockIdx.x * kGroup, col = (wave & 3) * 32 + j, o = o0 + col;
-    f32x16 H[4] = {{0}, {0}, {0}, {0}};  // rows 128 part + 32 u + mfma_row(r, h) of column o
-    float sb = 0.0f;
-    for (int tile = 0; tile < a.ntiles; ++tile) {
-        const int p0 = tile * kTile;
-        const int nvalid = min(kTile, a.N - p0);
-        const float *src = a.x2 + ((size_t)b * a.N + p0) * 256;
-        for (int i = tid; i < kTile * 256; i += kPgradThreads) A[(i >> 8) * kLd3 + (i & 255)] = i < nvalid * 256 ? src[i] : 0.0f;
-        __syncthreads();
-        {
-            f32x16 acc[1] = {{0}};
-            mfma_slab_rt<kLd3, 1>(A + part * 32 * kLd3, a.c3.W + (size_t)256 * o, 256, h, j, acc);
-            const LastChannel<kBnRelu> ch(a.c3, a, o, b, p0);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int p = part * 32 + mfma_row(r, h);
-                D[p * kLd + col] = p < nvalid ? ch.d(acc[0][r], p) : 0.0f;
-            }
-        }
-        __syncthreads();
-        if (tid < kGroup)
-            for (int p = 0; p < nvalid; ++p) sb = sb + D[p * kLd + tid];
-        const float *dp = D + h * kLd + col, *ap = A + h * kLd3 + 128 * part + j;
-#pragma unroll 4
-        for (int p = 0; p < kTile; p += 2) {
-            const float d = dp[p * kLd];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) H[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[p * kLd3 + 32 * u], d, H[u], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    float *out = a.Hc + ((size_t)b * kFeat + o) * 256 + 128 * part;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[32 * u + mfma_row(r, h)] = H[u][r];
-    if (tid < kGroup) a.hc[(size_t)b * kFeat + o0 + tid] = sb;
+    last_pgrad<256, kLd3, kBnRelu>(lds, a);
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------------
@@ -309,16 +202,6 @@ fx3d_status gt_ws(int N, int B, int K, GtWs *w) {
     if ((rc = fx3d_edgeconv_grad_train_workspace_bytes(kEc2, 3, K, N, B, &w->ec2_bytes)) != FX3D_OK) return rc;
     w->scratch = ws.put(w->ec1_bytes > w->ec2_bytes ? w->ec1_bytes : w->ec2_bytes);
     w->total = ws.at;
-    return FX3D_OK;
-}
-
-template <class Kern, class A>
-fx3d_status launch_dense(Kern kernel, const char *name, const char *label, dim3 grid, int threads, const A &a, hipStream_t st) {
-    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)kDenseLds, name);
-    if (rc != FX3D_OK) return rc;
-    ProfileScope prof(label, st);
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), kDenseLds, st, a);
-    FX3D_LAUNCH_CHECK();
     return FX3D_OK;
 }
 
@@ -367,13 +250,8 @@ fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_classes, 
     const int nt = w.ntiles;
 
     // the point that took the maximum, per tile, with what conv3.bn was given there
-    if ((r = ensure_dynamic_lds(reinterpret_cast<const void *>(&dgcnn_gt_argmax_kernel), (int)kConv3Lds, "dgcnn_gt_argmax_kernel")) != FX3D_OK) return r;
-    {
-        ProfileScope prof("dgcnn_gt_argmax", st);
-        hipLaunchKernelGGL(dgcnn_gt_argmax_kernel, dim3(nt, B), dim3(kPtThreads), kConv3Lds, st, x2, n.c3, pooled, v.i32(w.tfirst),
-                           v.f32(w.tpre), N, nt);
-        FX3D_LAUNCH_CHECK();
-    }
+    if ((r = launch_tile(&dgcnn_gt_argmax_kernel, "dgcnn_gt_argmax_kernel", "dgcnn_gt_argmax", kConv3Lds, nt, B, kPtThreads, st, x2, n.c3,
+                         pooled, v.i32(w.tfirst), v.f32(w.tpre), N, nt)) != FX3D_OK) return r;
 
     // the head's adjoint, cut at fc5.bn and fc4.bn, down to gy of conv3.bn and that BatchNorm's sums; then the dense layers' sums
     HeadGtArgs hb{};
@@ -403,13 +281,13 @@ fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_classes, 
     }
 
     // conv_3: the gradient at x2 (all points), then dW3 and db3 per cloud and their sums over b ascending
-    Conv3Args ca{};
-    ca.x2 = x2; ca.c3 = n.c3; ca.nstar = hb.nstar; ca.gy3 = hb.gy3; ca.mb = mb; ca.mg = mg; ca.gx2 = g2;
+    LastArgs ca{};
+    ca.in = x2; ca.c3 = n.c3; ca.nstar = hb.nstar; ca.gy3 = hb.gy3; ca.mb = mb; ca.mg = mg; ca.g = g2;
     ca.Hc = v.f32(w.Hc); ca.hc = v.f32(w.hc); ca.N = N; ca.ntiles = nt;
-    if ((r = launch_dense(&dgcnn_gt_conv3_bwd_kernel, "dgcnn_gt_conv3_bwd_kernel", "dgcnn_gt_conv3_bwd", dim3(nt, B), kPtThreads, ca,
-                          st)) != FX3D_OK) return r;
-    if ((r = launch_dense(&dgcnn_gt_conv3_pgrad_kernel, "dgcnn_gt_conv3_pgrad_kernel", "dgcnn_gt_conv3_pgrad", dim3(kFeat / kGroup, B),
-                          kPgradThreads, ca, st)) != FX3D_OK) return r;
+    if ((r = launch_tile(&dgcnn_gt_conv3_bwd_kernel, "dgcnn_gt_conv3_bwd_kernel", "dgcnn_gt_conv3_bwd", kDenseLds, nt, B, kPtThreads, st,
+                         ca)) != FX3D_OK) return r;
+    if ((r = launch_tile(&dgcnn_gt_conv3_pgrad_kernel, "dgcnn_gt_conv3_pgrad_kernel", "dgcnn_gt_conv3_pgrad", kDenseLds, kFeat / kGroup, B,
+                         kPgradThreads, st, ca)) != FX3D_OK) return r;
     {
         ProfileScope prof("dgcnn_gt_reduce", st);
         pointnet::ReduceArgs ra{};

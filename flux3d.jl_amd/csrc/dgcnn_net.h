@@ -1,9 +1,10 @@
 // What dgcnn.hip (the forward), dgcnn_train.hip (the training-mode forward), dgcnn_grad.hip (the adjoint) and dgcnn_grad_train.hip
 // (the training-mode adjoint) share: the layers of
-// the two EdgeConv stages, conv_3's LDS image of a 64-point tile of x2, the walk over the flat parameter buffer, the size check
-// of the entries, and the forward's workspace and conv_3 launch.
+// the two EdgeConv stages, conv_3's LDS image of a 64-point tile of x2, the winners of the maximum over the points (the two
+// adjoints), the walk over the flat parameter buffer, the size check of the entries, and the forward's workspace and conv_3 launch.
 #pragma once
 #include "mlp_common.h"
+#include "pointnet_net.h"
 
 namespace fx3d {
 namespace mlp {
@@ -17,6 +18,57 @@ constexpr int32_t kEc1[] = {3, 32, 64, 64}, kEc2[] = {64, 128, 256};  // the lay
 __device__ __forceinline__ void load_x2_tile(float *lds, const float *__restrict__ x2, int b, int N, int p0, int nvalid) {
     const float *xb = x2 + ((size_t)b * N + p0) * 256;
     for (int i = threadIdx.x; i < kTile * 256; i += kPtThreads) lds[(i >> 8) * kLd3 + (i & 255)] = i < nvalid * 256 ? xb[i] : 0.0f;
+}
+
+// The winners of the maximum over the points, one block = 64 points of one cloud, lds of kConv3Lds bytes: the forward's conv_3
+// again, block for block (the x2 tile, mfma_slab<256> and epilogue<kBnRelu>: the forward's bits), compared with pooled where that
+// is positive; per (tile, channel) the smallest matching point into tfirst (1024, ntiles, B), kNoPoint where the tile has none -- a
+// lane minimum over its 32 rows and one shuffle across the half-waves --, and with PRE what conv3.bn was given there (conv + bias;
+// 0 where there is none) into tpre, picked from the accumulators once the lane's minimum is known.  dgcnn_argmax_kernel
+// (dgcnn_grad.hip) is PRE = false, dgcnn_gt_argmax_kernel (dgcnn_grad_train.hip, at the batch statistics) PRE = true.  The slab
+// walk is pointnet::for_each_slab<256, kLd3>'s, written out: with the body as a lambda PRE = false takes 90 VGPRs for 80, which is
+// 5 waves per SIMD for 6.
+template <bool PRE>
+__device__ __forceinline__ void conv3_winners(float *lds, const float *__restrict__ x2, const Conv &c, const float *__restrict__ pooled,
+                                              int32_t *__restrict__ tfirst, float *__restrict__ tpre, int N, int ntiles) {
+    const int tile = blockIdx.x, b = blockIdx.y;
+    const int p0 = tile * kTile;
+    const int nvalid = min(kTile, N - p0);
+    load_x2_tile(lds, x2, b, N, p0, nvalid);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    const float *a0 = lds + j * kLd3 + h, *a1 = a0 + 32 * kLd3;
+    const size_t out = ((size_t)b * ntiles + tile) * kFeat;
+    for (int sl = wave; sl < kFeat / 32; sl += kPtThreads / 64) {
+        const int o = sl * 32 + j;
+        f32x16 acc0 = {0}, acc1 = {0};
+        mfma_slab<256>(a0, a1, c.W + (size_t)256 * o, h, acc0, acc1);
+        const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = pointnet::bn_sd(c.bn, o);
+        const float pv = pooled[(size_t)b * kFeat + o];
+        const float tgt = pv > 0.0f ? pv : __int_as_float(0x7fc00000);  // NaN equals nothing: no winner
+        int first = pointnet::kNoPoint;  // the lane's smallest matching point: a minimum, no branch
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int p = mfma_row(r, h);
+            const float v0 = epilogue<kBnRelu>(acc0[r], bi, g, be, mu, sd), v1 = epilogue<kBnRelu>(acc1[r], bi, g, be, mu, sd);
+            if (p < nvalid && v0 == tgt) first = min(first, p0 + p);
+            if (p + 32 < nvalid && v1 == tgt) first = min(first, p0 + p + 32);
+        }
+        float pre = 0.0f;
+        if (PRE) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int p = p0 + mfma_row(r, h);
+                pre = p == first ? acc0[r] + bi : p + 32 == first ? acc1[r] + bi : pre;
+            }
+        }
+        const int ofirst = __shfl_xor(first, 32, 64);
+        const float opre = __shfl_xor(pre, 32, 64);
+        if (h == 0) {
+            tfirst[out + o] = min(first, ofirst);
+            if (PRE) tpre[out + o] = ofirst < first ? opre : pre;
+        }
+    }
 }
 
 // a training-mode head block's BatchNorm and relu of this thread's element v = dense + bias (dgcnn_train.hip's head kernels, and

@@ -10,16 +10,14 @@
 //   pointnet_gt_head_{a,b,c}_kernel: the head's adjoint, one block per cloud, cut at the head's dense BatchNorms (and ended at the
 //     round's last BatchNorm, whose gy lives at the winners only); pointnet_gt_cloud_sums_kernel between them: one thread per channel,
 //     one Float64 chain over b.
-//   pointnet_gt_last_bwd_kernel<MODE>: one block = 64 points of one cloud.  round_trunk up to the last layer's input; the last layer's
-//     slabs (for_each_slab) four at a time -- 128 output channels, one slab per wave --; while a slab is in the accumulators the
-//     gradient at the contraction d is formed (dense: every point has one, through dbeta / m and xh dgamma / m) and written to an
-//     LDS image; all four waves then carry the chain over those 128 outputs on v_mfma_f32_32x32x2_f32 (back_mfma's operands), the
-//     accumulators kept across the eight groups, so the chain is one over all 1024 outputs ascending.  Stores the gradient at the last
-//     layer's input (128, N, B) and that input itself.
-//   pointnet_gt_last_pgrad_kernel<EPI>: dW and db of the last layer, one block of 8 waves per (cloud, 128 output channels): walks the
-//     cloud's tiles, recomputes the group's slabs (a wave: one slab, one 32-point half), forms d again (the same function), and carries
-//     (128 x 128) of dW as one chain over the cloud's points (hsum_mfma's operands, two tiles per wave).  pointnet_reduce_kernel then
-//     sums the clouds.
+//   pointnet_gt_last_bwd_kernel<MODE>: one block = 64 points of one cloud.  round_trunk up to the last layer's input, which it stores
+//     (128, N, B); then pointnet_net.h's last_back<128, kLd, EPI>: the last layer's slabs four at a time -- 128 output channels, one slab
+//     per wave --, the gradient at the contraction d formed while a slab is in the accumulators (dense: every point has one, through
+//     dbeta / m and xh dgamma / m), the chain over all 1024 outputs ascending on v_mfma_f32_32x32x2_f32, the gradient at the last
+//     layer's input (128, N, B).
+//   pointnet_gt_last_pgrad_kernel<EPI>: dW and db of the last layer, one block of 8 waves per (cloud, 128 output channels):
+//     pointnet_net.h's last_pgrad<128, kLd, EPI>, one chain over the cloud's points.  pointnet_reduce_kernel then sums the clouds.
+//     (The two bodies live in pointnet_net.h because dgcnn_grad_train.hip's conv_3 kernels are their instantiations at 256 channels.)
 //   pointnet_gt_sums_kernel<MODE, L>: the Float64 tile sums of (gy, gy xh) of BatchNorm L, pointnet_stats_kernel's tile and order with
 //     gy read from the workspace; pointnet_gt_finish_kernel: fold_tile_sums, then dbeta, dgamma and the two means.
 //   pointnet_gt_layer_bwd_kernel<MODE, L>: layer L of the round once its sums are known: the relu's output again (the forward's call),
@@ -40,10 +38,7 @@ constexpr int kImg = kTile * kLd;
 constexpr int kThird = 2 * kImg + 2 * kTile * 3;  // round_trunk's two images, x and x T; then a third image (floats)
 constexpr size_t kLayerLds = (size_t)(kThird + kImg) * sizeof(float);
 constexpr size_t kPgradLds = (size_t)2 * kImg * sizeof(float);
-constexpr int kGroup = 128;  // output channels of the last layer per step: one slab per wave of a tile kernel
-constexpr int kPgradThreads = 512;  // pointnet_gt_last_pgrad_kernel: 8 waves, two per slab of the group
 static_assert(kLayerLds <= 160 * 1024, "the layer adjoint's LDS");
-static_assert(kGroup == 32 * (kPtThreads / 64), "one slab per wave");
 static_assert(FX3D_POINTNET_GRAD_TRAIN_CLOUD_CHAINS == 1, "dW / db of a last convolution: one chain per cloud (last_pgrad)");
 
 // ---- the head ----------------------------------------------------------------------------------------------------------------------
@@ -194,104 +189,30 @@ __global__ __launch_bounds__(256) void pointnet_gt_cloud_sums_kernel(const float
     finish_bn(o, c, t.s1, t.s2);
 }
 
-// ---- the rounds' last layer --------------------------------------------------------------------------------------------------------
-struct LastArgs {
-    PointArgs p;           // the round at the batch statistics (last_bwd)
-    Conv c3;               // the last convolution (last_pgrad)
-    const int32_t *nstar;  // (1024, B)
-    const float *gy3;      // (1024, B): the gradient at the last BatchNorm's output, at the winner
-    const float *mb, *mg;  // (1024)
-    float *a2;             // (128, N, B): the last convolution's input; written by last_bwd, read by last_pgrad
-    float *g;              // (128, N, B): the gradient at it
-    float *Hc, *hc;        // (128, 1024, B), (1024, B): dW and db of each cloud
-    int N, ntiles;
+// ---- the rounds' last layer: pointnet_net.h's last_back and last_pgrad at CIN = 128, the image stride kLd -----------------------------
+struct RoundLastArgs : LastArgs {
+    PointArgs p;  // the round at the batch statistics
+    float *a2;    // (128, N, B): the last convolution's input, written here and read by last_pgrad (LastArgs::in)
 };
 
 template <int MODE>
-__global__ __launch_bounds__(kPtThreads) void pointnet_gt_last_bwd_kernel(const LastArgs a) {
+__global__ __launch_bounds__(kPtThreads) void pointnet_gt_last_bwd_kernel(const RoundLastArgs a) {
     extern __shared__ float lds[];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int p0 = tile * kTile;
     const int nvalid = min(kTile, a.N - p0);
     round_trunk<MODE, kLastLayer[MODE], false>(a.p, lds, b, p0, nvalid, [&](const float *in, const Conv &c, auto layer) {
-        constexpr int EPI = decltype(layer)::EPI;
         float *D = in == lds ? lds + kImg : lds;  // the image the last layer's input does not live in
         const size_t row0 = ((size_t)b * a.N + p0) * 128;
         for (int i = tid; i < nvalid * 128; i += kPtThreads) a.a2[row0 + i] = in[(i >> 7) * kLd + (i & 127)];
-        const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, j = lane & 31;
-        f32x16 back[2] = {{0}, {0}};  // tiles t = wave, wave + 4 of (4 x 32 input channels) x (2 halves), as back_mfma numbers them
-        for_each_slab<128>(in, c.W, kFeat, [&](int o, int, const f32x16 &acc0, const f32x16 &acc1) {
-            const int col = o & (kGroup - 1), o0 = o - col;  // every wave is in the same group of 128 outputs
-            LastChannel<EPI>(c, a, o, b, p0).store(D, col, h, nvalid, acc0, acc1);
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int t = wave + 4 * u, half = t & 1, ci = (t >> 1) * 32 + j;
-                const float *ap = D + (half * 32 + j) * kLd + h, *wp = c.W + ci + (size_t)128 * (o0 + h);
-#pragma unroll 8
-                for (int q = 0; q < kGroup; q += 2)
-                    back[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[q], wp[(size_t)128 * q], back[u], 0, 0, 0);
-            }
-            __syncthreads();
-        });
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = wave + 4 * u, half = t & 1, ci = (t >> 1) * 32 + j;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int p = half * 32 + mfma_row(r, h);
-                if (p < nvalid) a.g[row0 + (size_t)p * 128 + ci] = back[u][r];
-            }
-        }
+        last_back<128, kLd, decltype(layer)::EPI>(in, D, c, a, b, p0, nvalid);
     });
 }
 
-// block (k, b): dW[i, o] and db[o] of cloud b for o in [128 k, 128 k + 128): one chain over the cloud's points ascending.  8 waves:
-// wave w recomputes slab w & 3 of the group for the 32-point half w >> 2 (mfma_slab_rt on one half: the forward's chain), and owns
-// the two (32 x 32) tiles of dW with the input channels 64 (w >> 2) .. + 63 and the outputs of slab w & 3.
 template <int EPI>
 __global__ __launch_bounds__(kPgradThreads) void pointnet_gt_last_pgrad_kernel(const LastArgs a) {
     extern __shared__ float lds[];
-    float *A = lds, *D = lds + kImg;
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, j = lane & 31, part = wave >> 2;
-    const int o0 = blockIdx.x * kGroup, col = (wave & 3) * 32 + j, o = o0 + col;
-    f32x16 H[2] = {{0}, {0}};  // rows 64 part + 32 u + mfma_row(r, h) of column o
-    float sb = 0.0f;
-    for (int tile = 0; tile < a.ntiles; ++tile) {
-        const int p0 = tile * kTile;
-        const int nvalid = min(kTile, a.N - p0);
-        const float *src = a.a2 + ((size_t)b * a.N + p0) * 128;
-        for (int i = tid; i < kTile * 128; i += kPgradThreads) A[(i >> 7) * kLd + (i & 127)] = i < nvalid * 128 ? src[i] : 0.0f;
-        __syncthreads();
-        {
-            f32x16 acc[1] = {{0}};
-            mfma_slab_rt<kLd, 1>(A + part * 32 * kLd, a.c3.W + (size_t)128 * o, 128, h, j, acc);
-            const LastChannel<EPI> ch(a.c3, a, o, b, p0);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int p = part * 32 + mfma_row(r, h);
-                D[p * kLd + col] = p < nvalid ? ch.d(acc[0][r], p) : 0.0f;
-            }
-        }
-        __syncthreads();
-        if (tid < kGroup)
-            for (int p = 0; p < nvalid; ++p) sb = sb + D[p * kLd + tid];
-        const float *dp = D + h * kLd + col, *ap = A + h * kLd + 64 * part + j;
-#pragma unroll 8
-        for (int p = 0; p < kTile; p += 2) {
-            const float d = dp[p * kLd];
-            H[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[p * kLd], d, H[0], 0, 0, 0);
-            H[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[p * kLd + 32], d, H[1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    float *out = a.Hc + ((size_t)b * kFeat + o) * 128 + 64 * part;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[32 * u + mfma_row(r, h)] = H[u][r];
-    if (tid < kGroup) a.hc[(size_t)b * kFeat + o0 + tid] = sb;
+    last_pgrad<128, kLd, EPI>(lds, a);
 }
 
 // ---- the BatchNorms below a round's last: their Float64 tile sums -------------------------------------------------------------------
@@ -556,36 +477,26 @@ fx3d_status check_gt_sizes(const char *fn, int32_t N, int32_t B, int32_t nc) {
     return FX3D_OK;
 }
 
-template <class K, class A>
-fx3d_status launch_tile(K kernel, const char *name, const char *label, size_t lds, int ntiles, int B, const A &a, hipStream_t st,
-                        int threads = kPtThreads) {
-    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)lds, name);
-    if (rc != FX3D_OK) return rc;
-    ProfileScope prof(label, st);
-    hipLaunchKernelGGL(kernel, dim3(ntiles, B), dim3(threads), lds, st, a);
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
 template <int MODE, int L>
 fx3d_status launch_sums(const SumArgs &s, int B, hipStream_t st) {
-    return launch_tile(&pointnet_gt_sums_kernel<MODE, L>, "pointnet_gt_sums_kernel", "pointnet_gt_sums", kPtLds, s.p.ntiles, B, s, st);
+    return launch_tile(&pointnet_gt_sums_kernel<MODE, L>, "pointnet_gt_sums_kernel", "pointnet_gt_sums", kPtLds, s.p.ntiles, B, kPtThreads,
+                       st, s);
 }
 template <int MODE, int L>
 fx3d_status launch_layer(const LayerArgs &a, int B, hipStream_t st) {
     return launch_tile(&pointnet_gt_layer_bwd_kernel<MODE, L>, "pointnet_gt_layer_bwd_kernel", "pointnet_gt_layer_bwd", kLayerLds,
-                       a.p.ntiles, B, a, st);
+                       a.p.ntiles, B, kPtThreads, st, a);
 }
-fx3d_status launch_last(int mode, const LastArgs &a, int B, hipStream_t st) {
+fx3d_status launch_last(int mode, const RoundLastArgs &a, int B, hipStream_t st) {
     const char *nm = "pointnet_gt_last_bwd_kernel", *lb = "pointnet_gt_last_bwd";
-    if (mode == 0) return launch_tile(&pointnet_gt_last_bwd_kernel<0>, nm, lb, kPtLds, a.ntiles, B, a, st);
-    if (mode == 1) return launch_tile(&pointnet_gt_last_bwd_kernel<1>, nm, lb, kPtLds, a.ntiles, B, a, st);
-    return launch_tile(&pointnet_gt_last_bwd_kernel<2>, nm, lb, kPtLds, a.ntiles, B, a, st);
+    if (mode == 0) return launch_tile(&pointnet_gt_last_bwd_kernel<0>, nm, lb, kPtLds, a.ntiles, B, kPtThreads, st, a);
+    if (mode == 1) return launch_tile(&pointnet_gt_last_bwd_kernel<1>, nm, lb, kPtLds, a.ntiles, B, kPtThreads, st, a);
+    return launch_tile(&pointnet_gt_last_bwd_kernel<2>, nm, lb, kPtLds, a.ntiles, B, kPtThreads, st, a);
 }
 fx3d_status launch_last_pgrad(int mode, const LastArgs &a, int B, hipStream_t st) {
     const char *nm = "pointnet_gt_last_pgrad_kernel", *lb = "pointnet_gt_last_pgrad";
-    if (mode == 2) return launch_tile(&pointnet_gt_last_pgrad_kernel<kBnOnly>, nm, lb, kPgradLds, kFeat / kGroup, B, a, st, kPgradThreads);
-    return launch_tile(&pointnet_gt_last_pgrad_kernel<kReluBn>, nm, lb, kPgradLds, kFeat / kGroup, B, a, st, kPgradThreads);
+    if (mode == 2) return launch_tile(&pointnet_gt_last_pgrad_kernel<kBnOnly>, nm, lb, kPgradLds, kFeat / kGroup, B, kPgradThreads, st, a);
+    return launch_tile(&pointnet_gt_last_pgrad_kernel<kReluBn>, nm, lb, kPgradLds, kFeat / kGroup, B, kPgradThreads, st, a);
 }
 
 }  // namespace
@@ -685,8 +596,8 @@ fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t num_classe
         return FX3D_OK;
     };
 
-    LastArgs la{};
-    la.nstar = hb.nstar; la.gy3 = hb.gy3; la.mb = mb; la.mg = mg; la.a2 = v.f32(w.a2); la.g = v.f32(w.g128);
+    RoundLastArgs la{};
+    la.nstar = hb.nstar; la.gy3 = hb.gy3; la.mb = mb; la.mg = mg; la.a2 = v.f32(w.a2); la.in = la.a2; la.g = v.f32(w.g128);
     la.Hc = v.f32(w.Hc); la.hc = v.f32(w.hc); la.N = N; la.ntiles = nt;
     // the round's last layer: the gradient at its input (all points), then dW and db per cloud and their sums over b ascending
     auto last_round = [&](int k, const Conv &c3, const Conv &g3) -> fx3d_status {

@@ -3,7 +3,8 @@
 // Float64 tile sums (the two training-mode units) and a BatchNorm's batch statistics (pointnet_train.hip, and with it the
 // training-mode forwards of DGCNN and EdgeConv), and the adjoints' MFMA chains over a tile (hsum_mfma, back_mfma, hsum3) with the
 // launches of pointnet_grad.hip's finishing kernels; and what the training-mode adjoints of PointNet and DGCNN share (bn_gv, BnOut,
-// LastChannel, the cloud-sums launch).
+// LastChannel, the cloud-sums launch, and the dense adjoint of the 1024-output convolution under a maximum: last_back, last_pgrad,
+// their arguments and launch_tile).
 // On the host: the walk over the flat parameter buffer, the forward's workspace, the size check of the entries, the
 // arguments of the forward's two kernels per round (set_round, stn_head, feat_head) and their launches (defined in
 // pointnet.hip, which owns the kernels).  On the device: a round's layer chain (round_trunk, with its tile loads), the slab
@@ -567,6 +568,122 @@ struct LastChannel {
         }
     }
 };
+
+// ---- the dense adjoint of a maximum's last convolution (CIN -> 1024): PointNet's three rounds (CIN = 128, the image stride kLd) and
+// DGCNN's conv_3 (CIN = 256, kLd3).  pointnet_gt_last_{bwd,pgrad}_kernel and dgcnn_gt_conv3_{bwd,pgrad}_kernel are these two bodies.
+constexpr int kGroup = 128;         // the last layer's outputs per step: one slab per wave of a tile kernel
+constexpr int kPgradThreads = 512;  // last_pgrad: 8 waves, two per slab of the group
+static_assert(kGroup == 32 * (kPtThreads / 64), "one slab per wave");
+
+struct LastArgs {
+    const float *in;       // (CIN, N, B): the last convolution's input (last_pgrad; DGCNN's last_back)
+    Conv c3;               // the last convolution, at the batch statistics
+    const int32_t *nstar;  // (1024, B)
+    const float *gy3;      // (1024, B): the gradient at the last BatchNorm's output, at the winner
+    const float *mb, *mg;  // (1024)
+    float *g;              // (CIN, N, B): the gradient at the last convolution's input
+    float *Hc, *hc;        // (CIN, 1024, B), (1024, B): dW and db of each cloud
+    int N, ntiles;
+};
+
+// The way back, one block = the 64 points of cloud b from p0 on, whose rows of the input are the image `in` (row stride LD): the
+// slabs (for_each_slab) four at a time -- kGroup outputs, one slab per wave --; while a slab is in the accumulators LastChannel
+// forms the gradient at the contraction and writes it to the image D (row stride kLd); all four waves then carry the chain over
+// those 128 outputs on v_mfma_f32_32x32x2_f32 (back_mfma's operands) into the tiles t = wave + 4 u of (CIN / 32 input channels) x
+// (2 halves), as back_mfma numbers them, CIN / 64 per wave, kept across the eight groups: one chain over all 1024 outputs
+// ascending.  Stores a.g.
+template <int CIN, int LD, int EPI>
+__device__ __forceinline__ void last_back(const float *in, float *D, const Conv &c, const LastArgs &a, int b, int p0, int nvalid) {
+    constexpr int NU = CIN / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+    f32x16 back[NU] = {};
+    for_each_slab<CIN, LD>(in, c.W, kFeat, [&](int o, int, const f32x16 &acc0, const f32x16 &acc1) {
+        const int col = o & (kGroup - 1), o0 = o - col;  // every wave is in the same group of 128 outputs
+        LastChannel<EPI>(c, a, o, b, p0).store(D, col, h, nvalid, acc0, acc1);
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int t = wave + 4 * u, half = t & 1, ci = (t >> 1) * 32 + j;
+            const float *ap = D + (half * 32 + j) * kLd + h, *wp = c.W + ci + (size_t)CIN * (o0 + h);
+#pragma unroll 8
+            for (int q = 0; q < kGroup; q += 2)
+                back[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[q], wp[(size_t)CIN * q], back[u], 0, 0, 0);
+        }
+        __syncthreads();
+    });
+    float *g = a.g + ((size_t)b * a.N + p0) * CIN;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const int t = wave + 4 * u, half = t & 1, ci = (t >> 1) * 32 + j;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int p = half * 32 + mfma_row(r, h);
+            if (p < nvalid) g[(size_t)p * CIN + ci] = back[u][r];
+        }
+    }
+}
+
+// Block (k, b) of kPgradThreads: dW[i, o] and db[o] of cloud b for o in [128 k, 128 k + 128): one chain over the cloud's points
+// ascending.  lds: the image of a tile of a.in (row stride LD), then D (kLd).  8 waves: wave w recomputes slab w & 3 of the group for
+// the 32-point half w >> 2 (mfma_slab_rt on one half: the forward's chain), forms d again (LastChannel) and owns the CIN / 64
+// (32 x 32) tiles of dW with the input channels (CIN / 2) (w >> 2) .. + CIN / 2 - 1 and the outputs of slab w & 3 (hsum_mfma's
+// operands); db is one Float32 chain per output.
+template <int CIN, int LD, int EPI>
+__device__ __forceinline__ void last_pgrad(float *lds, const LastArgs &a) {
+    constexpr int NU = CIN / 64, kUnroll = 16 / NU;  // 16 MFMAs in the unrolled body
+    float *A = lds, *D = lds + kTile * LD;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, j = lane & 31, part = wave >> 2;
+    const int o0 = blockIdx.x * kGroup, col = (wave & 3) * 32 + j, o = o0 + col;
+    f32x16 H[NU] = {};  // rows (CIN / 2) part + 32 u + mfma_row(r, h) of column o
+    float sb = 0.0f;
+    for (int tile = 0; tile < a.ntiles; ++tile) {
+        const int p0 = tile * kTile;
+        const int nvalid = min(kTile, a.N - p0);
+        const float *src = a.in + ((size_t)b * a.N + p0) * CIN;
+        for (int i = tid; i < kTile * CIN; i += kPgradThreads) A[((unsigned)i / CIN) * LD + ((unsigned)i % CIN)] = i < nvalid * CIN ? src[i] : 0.0f;
+        __syncthreads();
+        {
+            f32x16 acc[1] = {{0}};
+            mfma_slab_rt<LD, 1>(A + part * 32 * LD, a.c3.W + (size_t)CIN * o, CIN, h, j, acc);
+            const LastChannel<EPI> ch(a.c3, a, o, b, p0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int p = part * 32 + mfma_row(r, h);
+                D[p * kLd + col] = p < nvalid ? ch.d(acc[0][r], p) : 0.0f;
+            }
+        }
+        __syncthreads();
+        if (tid < kGroup)
+            for (int p = 0; p < nvalid; ++p) sb = sb + D[p * kLd + tid];
+        const float *dp = D + h * kLd + col, *ap = A + h * LD + (CIN / 2) * part + j;
+#pragma unroll kUnroll
+        for (int p = 0; p < kTile; p += 2) {
+            const float d = dp[p * kLd];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) H[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[p * LD + 32 * u], d, H[u], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    float *out = a.Hc + ((size_t)b * kFeat + o) * CIN + (CIN / 2) * part;
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[32 * u + mfma_row(r, h)] = H[u][r];
+    if (tid < kGroup) a.hc[(size_t)b * kFeat + o0 + tid] = sb;
+}
+
+// a kernel with dynamic LDS on a (nx, B) grid, under its label in the library's profile
+template <class K, class... A>
+inline fx3d_status launch_tile(K kernel, const char *name, const char *label, size_t lds, int nx, int B, int threads, hipStream_t st,
+                               const A &...a) {
+    const fx3d_status rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)lds, name);
+    if (rc != FX3D_OK) return rc;
+    ProfileScope prof(label, st);
+    hipLaunchKernelGGL(kernel, dim3(nx, B), dim3(threads), lds, st, a...);
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
 
 }  // namespace pointnet
 }  // namespace mlp

@@ -93,8 +93,9 @@ def edgeconv_param_shapes(layers):
 class _Model:
     """What the models share: the parameters (name -> Float32 numpy array in Flux's shapes), their flat device copy, the
     check of the input clouds and the classifiers' forward.  A subclass sets ``_NAME``, ``_COUNT_FN`` and ``_shapes()``, ``_count_args()`` where
-    the count is not a function of ``num_classes``, and a classifier ``_WHY`` (the layer that fixes its 3 input channels) and
-    ``_grad_call`` for the shared ``grad`` / ``flat_grad`` / ``crossentropy_grad`` bodies."""
+    the count is not a function of ``num_classes``, and a classifier ``_WHY`` (the layer that fixes its 3 input channels) and the
+    data of its entry points (below: "the classifiers' training-mode path") for the shared ``forward_train``, ``grad`` /
+    ``flat_grad`` / ``crossentropy_grad`` bodies, their ``_train`` forms and ``train_step``."""
 
     def _count_args(self):
         return (self.num_classes,)
@@ -327,8 +328,154 @@ class _Model:
         grads, gx = self.grad(X, DeviceArray.from_host(glogits) if on_dev else glogits, **({"fwd": fwd} if with_fwd else {}))
         return loss, grads, gx
 
-    # ---- the training step (include/flux3d_hip.h "Training step"): a classifier sets _STAT_FN, _DROPOUT (rows of each mask, p),
-    #      _GRAD_NEEDS_FWD and has _masks_of, _train_bytes, _forward_train_call and _grad_train_call
+    # ---- the classifiers' training-mode path and adjoint calls.  A classifier sets _ENTRY (the stem of its fx3d_{entry}_* entry
+    #      points), _FWD_KEYS (the forward's intermediates its adjoints take, in argument order) and _MID (the adjoints' optional
+    #      outputs: name -> (rows, columns or None for N)), and has _lead() (the entries' arguments between the parameters and x),
+    #      _sizes(N, B) (the workspace queries' arguments), _optional(N, B) and _masks_of(dropout, B, on_dev) (``dropout`` after its
+    #      checks: one entry per Dropout layer, each None, a device array, or a host array still to be uploaded)
+    def _train_bytes(self, N, B):
+        return _lib.query_bytes(f"fx3d_{self._ENTRY}_train_workspace_bytes", *self._sizes(N, B))
+
+    def _as_dropout(self, masks):
+        """Checked masks in the form the public ``dropout`` argument takes them: the array where the model has one Dropout layer."""
+        return masks[0] if len(self._DROPOUT[0]) == 1 else tuple(masks)
+
+    def _forward_train(self, X, dropout, momentum, update, intermediates):
+        """A classifier's :meth:`forward_train`."""
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
+        if B < 2:
+            raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
+                             f"B - 1), got B={B}")
+        momentum = self._momentum(momentum)
+        masks = self._masks_of(dropout, B, on_dev)
+        nb = self._train_bytes(N, B)  # (the library's own size limits)
+        masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
+        x = self._on_device(pts, N, B, on_dev)
+        slots = self._stat_slots()
+        out, stats = self._forward_train_call(x, N, B, masks, momentum, nb, intermediates, intermediates or update)
+        if update:
+            self._adopt_running(stats["running"], slots, current_stream().handle)
+        if not intermediates:
+            return out["probs"] if on_dev else out["probs"].to_host()
+        for key, buf in stats.items():
+            out[key] = self._named_stats(buf, slots, on_dev)
+        if not on_dev:
+            out = {k: (v if isinstance(v, dict) else v.to_host()) for k, v in out.items()}
+        return out
+
+    def _forward_train_call(self, x, N, B, masks, momentum, nb, intermediates, running):
+        """fx3d_{entry}_forward_train on the device arrays ``x`` and ``masks`` (each possibly ``None``) with a workspace of ``nb``
+        bytes: ``(out, stats)`` -- ``probs`` and, with ``intermediates``, the optional outputs; the flat ``batch_stats`` and, with
+        ``running``, the flat ``running``."""
+        f32 = np.float32
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        optional = self._optional(N, B)
+        out = self._outputs(B, optional, intermediates)
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if running:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        ws = workspace(nb, tag=f"{self._ENTRY}_train")
+        _lib.call(f"fx3d_{self._ENTRY}_forward_train", self._params_dev().ptr, *self._lead(), x.ptr, N, B,
+                  *(m.ptr if m is not None else None for m in masks), momentum, out["probs"].ptr,
+                  *(out[k].ptr if intermediates else None for k in optional), stats["batch_stats"].ptr,
+                  stats["running"].ptr if running else None, ws.ptr, ws.nbytes, current_stream().handle)
+        return out, stats
+
+    def _grad_train_call(self, x, N, B, masks, out, batch_stats, glogits):
+        """fx3d_{entry}_grad_train on device arrays, the forward's intermediates ``out`` and its flat ``batch_stats`` as it wrote
+        them: the flat gradient."""
+        entry = f"{self._ENTRY}_grad_train"
+        ws = workspace(_lib.query_bytes(f"fx3d_{entry}_workspace_bytes", *self._sizes(N, B)), tag=entry)
+        gp = DeviceArray.empty((self.param_count,), np.float32)
+        _lib.call(f"fx3d_{entry}", self._params_dev().ptr, *self._lead(), x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
+                  *(out[k].ptr for k in self._FWD_KEYS), batch_stats.ptr, glogits.ptr, gp.ptr, *([None] * (1 + len(self._MID))),
+                  ws.ptr, ws.nbytes, current_stream().handle)
+        return gp
+
+    def _grad_call(self, X, glogits, input_grad, intermediates, fwd=None, train=False, dropout=None):
+        """fx3d_{entry}_grad (``train``: fx3d_{entry}_grad_train, with the dropout multipliers and with the intermediates and batch
+        statistics of ``fwd``, or of a :meth:`forward_train` run here) after the argument checks: (the flat gradient, gx or None,
+        the intermediates or None) on the device, and whether ``X`` lives there.  Every refusal comes before any device work."""
+        pts, N, B, on_dev = self._clouds(X, self._WHY)
+        nc, f32 = self.num_classes, np.float32
+        entry = f"fx3d_{self._ENTRY}_grad" + ("_train" if train else "")
+        if train:
+            if B < 2:
+                raise ValueError(f"training-mode BatchNorm needs at least two clouds, got B={B}")
+            masks = self._masks_of(dropout, B, on_dev)
+            slots = self._stat_slots()
+            nstat = slots[-1][2] + 2 * slots[-1][1]
+            names = [bn + f for bn, *_ in slots for f in (".mu", ".sigma2")]
+            if fwd is not None:
+                if not isinstance(fwd, dict) or "batch_stats" not in fwd:
+                    raise TypeError("fwd must be the dict of forward_train(..., intermediates=True)")
+                named = fwd["batch_stats"]
+                if not isinstance(named, dict) or [k for k in named] != names:
+                    raise ValueError(f"fwd['batch_stats'] must hold mu and sigma2 of the {len(slots)} BatchNorms in forward order")
+                for (bn, C_, _, _) in slots:
+                    for f in (".mu", ".sigma2"):
+                        v = named[bn + f]
+                        if is_device(v) != on_dev:
+                            raise TypeError("fwd must live where X lives")
+                        if tuple(v.shape) != (C_,) or v.dtype != f32:
+                            raise ValueError(f"fwd['batch_stats'][{bn + f!r}] must be Float32 ({C_},), got {v.dtype} {tuple(v.shape)}")
+        nb = _lib.query_bytes(entry + "_workspace_bytes", *self._sizes(N, B))  # (the library's own size limits)
+        g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
+        given = [None] * len(self._FWD_KEYS)
+        if fwd is not None:
+            missing = [k for k in self._FWD_KEYS if k not in fwd]
+            if missing:
+                raise ValueError(f"fwd must be the dict of forward{'_train' if train else ''}(X, intermediates=True): it has no {missing}")
+            shapes = self._optional(N, B)
+            given = [self._like(fwd[k], f"fwd['{k}']", *shapes[k], on_dev) for k in self._FWD_KEYS]
+            for k, a in zip(self._FWD_KEYS, given):
+                if not on_dev and a.dtype == np.int32 and a.size and (a.min() < 0 or a.max() >= N):
+                    raise ValueError(f"fwd['{k}'] must hold 0-based indices in [0, {N}), got values from {a.min()} to {a.max()}")
+        if not on_dev:
+            g = DeviceArray.from_host(g)
+            given = [None if a is None else DeviceArray.from_host(a) for a in given]
+        x = self._on_device(pts, N, B, on_dev)
+        stream = current_stream().handle
+        lead = ()
+        if train:
+            masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
+            if fwd is None:
+                fwd_made = self.forward_train(x, dropout=None if dropout is None else self._as_dropout(masks), intermediates=True)
+                given, named = [fwd_made[k] for k in self._FWD_KEYS], fwd_made["batch_stats"]
+            # the BatchNorms' statistics (views of forward_train's buffer, or the caller's arrays) as one buffer in the layout's order
+            if on_dev or fwd is None:
+                stats = DeviceArray.empty((nstat,), f32)
+                for bn, C_, at, _ in slots:
+                    for fld, off in ((".mu", at), (".sigma2", at + C_)):
+                        _lib.call("fx3d_memcpy_d2d", stats.ptr + 4 * off, named[bn + fld].ptr, 4 * C_, stream)
+            else:
+                stats = DeviceArray.from_host(np.concatenate([np.asarray(named[k], f32) for k in names]))
+            lead = tuple(m.ptr if m is not None else None for m in masks)
+        gp = DeviceArray.empty((self.param_count,), f32)
+        gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
+        mid = {k: DeviceArray.empty((r, N if c is None else c, B), f32) for k, (r, c) in self._MID.items()} if intermediates else None
+        ws = workspace(nb, tag=entry[5:])
+        _lib.call(entry, self._params_dev().ptr, *self._lead(), x.ptr, N, B, *lead, *(None if a is None else a.ptr for a in given),
+                  *((stats.ptr,) if train else ()), g.ptr, gp.ptr, gx.ptr if gx is not None else None,
+                  *(mid[k].ptr if mid else None for k in self._MID), ws.ptr, ws.nbytes, stream)
+        return gp, gx, mid, on_dev
+
+    def _crossentropy_grad_train(self, X, labels, dropout):
+        """A classifier's :meth:`crossentropy_grad_train`."""
+        _, N, B, on_dev = self._clouds(X, self._WHY)
+        y = self._labels(labels, B)
+        if isinstance(dropout, (int, np.integer)):  # drawn once, for the forward and the adjoint
+            masks = self._masks_of(int(dropout), B, on_dev)
+            dropout = self._as_dropout([DeviceArray.from_host(m) for m in masks] if on_dev else masks)
+        fwd = self.forward_train(X, dropout=dropout, intermediates=True)
+        probs = fwd["probs"]
+        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
+        grads, gx = self.grad_train(X, DeviceArray.from_host(glogits) if on_dev else glogits, dropout=dropout, fwd=fwd)
+        return loss, grads, gx
+
+    # ---- the training step (include/flux3d_hip.h "Training step"): a classifier sets _STAT_FN, _DROPOUT (rows of each mask, p)
+    #      and _GRAD_NEEDS_FWD
     def _stat_map(self):
         """The device int32 map of fx3d_adam_step: for every element of the flat statistics buffer its index in the flat parameter
         buffer.  Built from the names: only ``mu`` / ``sigma2`` slots, the only ones whose gradient is always +0."""
@@ -477,7 +624,7 @@ class PointNet(_Model):
     the batch -- are :meth:`grad_train`, :meth:`flat_grad_train` and :meth:`crossentropy_grad_train` (include/flux3d_hip.h
     "PointNet training-mode adjoint")."""
 
-    _NAME, _COUNT_FN, _WHY = "PointNet", "fx3d_pointnet_param_count", "stnKD(3)"
+    _NAME, _COUNT_FN, _WHY, _ENTRY = "PointNet", "fx3d_pointnet_param_count", "stnKD(3)", "pointnet"
 
     def __init__(self, num_classes=10, K=64, seed=0):
         if int(K) != 64:
@@ -496,11 +643,17 @@ class PointNet(_Model):
         ``(3, N, B)`` or ``(3, N)`` (one cloud).  The result lives where the input lives.  ``intermediates=True``: a dict
         with ``probs``, ``logits`` (num_classes, B), ``stn`` (3, 3, B), ``fstn`` (64, 64, B) and ``pooled`` (1024, B)."""
         _, N, B, _ = clouds = self._clouds(X, self._WHY)
-        return self._classify(clouds, "pointnet", (self.num_classes,), (N, B, self.num_classes), self._optional(B), intermediates)
+        return self._classify(clouds, self._ENTRY, self._lead(), self._sizes(N, B), self._optional(N, B), intermediates)
 
     __call__ = forward
 
-    def _optional(self, B):
+    def _lead(self):
+        return (self.num_classes,)
+
+    def _sizes(self, N, B):
+        return (N, B, self.num_classes)
+
+    def _optional(self, N, B):
         """The forward entries' optional outputs in their argument order: name -> (shape, dtype)."""
         f32 = np.float32
         return {"logits": ((self.num_classes, B), f32), "stn": ((3, 3, B), f32), "fstn": ((64, 64, B), f32), "pooled": ((1024, B), f32)}
@@ -529,130 +682,21 @@ class PointNet(_Model):
         ``update=True`` writes ``running`` into the model's parameters, on the host (which reads them back: not inside a graph
         capture) and in the kept device copy: the next :meth:`forward` is the test-mode network after one training step's worth
         of statistics.  The gradient of this forward is :meth:`grad_train`."""
-        pts, N, B, on_dev = self._clouds(X, self._WHY)
-        nc, f32 = self.num_classes, np.float32
-        if B < 2:
-            raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
-                             f"B - 1), got B={B}")
-        momentum = self._momentum(momentum)
-        mask = self._train_mask(dropout, B, on_dev)
-        nb = _lib.query_bytes("fx3d_pointnet_train_workspace_bytes", N, B, nc)  # (the library's own size limits)
-        if mask is not None and not is_device(mask):
-            mask = DeviceArray.from_host(mask)
-        x = self._on_device(pts, N, B, on_dev)
-        slots = self._stat_slots()
-        out, stats = self._forward_train_call(x, N, B, [mask], momentum, nb, intermediates, intermediates or update)
-        if update:
-            self._adopt_running(stats["running"], slots, current_stream().handle)
-        if not intermediates:
-            return out["probs"] if on_dev else out["probs"].to_host()
-        for key, buf in stats.items():
-            out[key] = self._named_stats(buf, slots, on_dev)
-        if not on_dev:
-            out = {k: (v if isinstance(v, dict) else v.to_host()) for k, v in out.items()}
-        return out
+        return self._forward_train(X, dropout, momentum, update, intermediates)
 
     _MID = {"gstn": (3, 3), "gfstn": (64, 64), "gh": (64, None), "gxt": (3, None)}  # fx3d_pointnet_grad's optional outputs, in order
-    _STAT_FN, _DROPOUT, _GRAD_NEEDS_FWD = "fx3d_pointnet_stat_count", ((256,), 0.4), False  # (train_step)
+    _FWD_KEYS, _STAT_FN, _DROPOUT, _GRAD_NEEDS_FWD = (), "fx3d_pointnet_stat_count", ((256,), 0.4), False  # (train_step)
 
     def _masks_of(self, dropout, B, on_dev):
-        return (self._train_mask(dropout, B, on_dev),)
-
-    def _train_bytes(self, N, B):
-        return _lib.query_bytes("fx3d_pointnet_train_workspace_bytes", N, B, self.num_classes)
-
-    def _forward_train_call(self, x, N, B, masks, momentum, nb, intermediates, running):
-        """fx3d_pointnet_forward_train on the device arrays ``x`` and ``masks[0]`` (or ``None``) with a workspace of ``nb`` bytes:
-        ``(out, stats)`` -- ``probs`` and, with ``intermediates``, the optional outputs; the flat ``batch_stats`` and, with
-        ``running``, the flat ``running``."""
-        nc, f32 = self.num_classes, np.float32
-        slots = self._stat_slots()
-        nstat = slots[-1][2] + 2 * slots[-1][1]
-        optional = self._optional(B)
-        out = self._outputs(B, optional, intermediates)
-        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
-        if running:
-            stats["running"] = DeviceArray.empty((nstat,), f32)
-        ws = workspace(nb, tag="pointnet_train")
-        _lib.call("fx3d_pointnet_forward_train", self._params_dev().ptr, nc, x.ptr, N, B, masks[0].ptr if masks[0] is not None else None,
-                  momentum, out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
-                  stats["batch_stats"].ptr, stats["running"].ptr if running else None, ws.ptr, ws.nbytes, current_stream().handle)
-        return out, stats
-
-    def _grad_train_call(self, x, N, B, masks, out, batch_stats, glogits):
-        """fx3d_pointnet_grad_train on device arrays, the flat ``batch_stats`` as the forward wrote it: the flat gradient."""
-        nc = self.num_classes
-        ws = workspace(_lib.query_bytes("fx3d_pointnet_grad_train_workspace_bytes", N, B, nc), tag="pointnet_grad_train")
-        gp = DeviceArray.empty((self.param_count,), np.float32)
-        _lib.call("fx3d_pointnet_grad_train", self._params_dev().ptr, nc, x.ptr, N, B, masks[0].ptr if masks[0] is not None else None,
-                  batch_stats.ptr, glogits.ptr, gp.ptr, None, None, None, None, None, ws.ptr, ws.nbytes, current_stream().handle)
-        return gp
-
-    def _train_mask(self, dropout, B, on_dev):
-        """``dropout`` of the training-mode methods after its checks: ``None``, or the ``(256, B)`` multipliers (an ``int``: the
-        seed of :meth:`dropout_mask`) as a device array, or as a host array still to be uploaded."""
+        """``dropout`` of the training-mode methods after its checks, as a 1-tuple: ``None``, or the ``(256, B)`` multipliers (an
+        ``int``: the seed of :meth:`dropout_mask`) as a device array, or as a host array still to be uploaded."""
         if dropout is None:
-            return None
+            return (None,)
         if isinstance(dropout, (int, np.integer)):
-            return self.dropout_mask(B, int(dropout))
+            return (self.dropout_mask(B, int(dropout)),)
         if is_device(dropout) and not on_dev:
             raise TypeError("a device dropout mask needs X on the device")
-        return self._like(dropout, "dropout", (256, B), np.float32, is_device(dropout))
-
-    def _grad_call(self, X, glogits, input_grad, intermediates, train=False, dropout=None, fwd=None):
-        """fx3d_pointnet_grad (``train``: fx3d_pointnet_grad_train, with the dropout multipliers and the batch statistics of
-        ``fwd``, or of a :meth:`forward_train` run here) after the argument checks: (the flat gradient, gx or None, the
-        intermediates or None) on the device, and whether ``X`` lives there."""
-        pts, N, B, on_dev = self._clouds(X, self._WHY)
-        nc, f32 = self.num_classes, np.float32
-        entry = "fx3d_pointnet_grad_train" if train else "fx3d_pointnet_grad"
-        extra = ()
-        if train:
-            if B < 2:
-                raise ValueError(f"training-mode BatchNorm needs at least two clouds, got B={B}")
-            mask = self._train_mask(dropout, B, on_dev)
-            slots = self._stat_slots()
-            nstat = slots[-1][2] + 2 * slots[-1][1]
-            if fwd is not None:
-                if not isinstance(fwd, dict) or "batch_stats" not in fwd:
-                    raise TypeError("fwd must be the dict of forward_train(..., intermediates=True)")
-                named = fwd["batch_stats"]
-                if [k for k in named] != [bn + f for bn, *_ in slots for f in (".mu", ".sigma2")]:
-                    raise ValueError("fwd['batch_stats'] must hold mu and sigma2 of the 13 BatchNorms in forward order")
-                for (bn, C, _, _) in slots:
-                    for f in (".mu", ".sigma2"):
-                        v = named[bn + f]
-                        if is_device(v) != on_dev:
-                            raise TypeError("fwd must live where X lives")
-                        if tuple(v.shape) != (C,) or v.dtype != f32:
-                            raise ValueError(f"fwd['batch_stats'][{bn + f!r}] must be Float32 ({C},), got {v.dtype} {tuple(v.shape)}")
-        nb = _lib.query_bytes(entry + "_workspace_bytes", N, B, nc)  # (the library's own size limits)
-        g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
-        if not on_dev:
-            g = DeviceArray.from_host(g)
-        x = self._on_device(pts, N, B, on_dev)
-        stream = current_stream().handle
-        if train:
-            if mask is not None and not is_device(mask):
-                mask = DeviceArray.from_host(mask)
-            # the 13 BatchNorms' statistics (views of forward_train's buffer, or the caller's arrays) as one buffer in the layout's order
-            stats = self.forward_train(x, dropout=mask, intermediates=True)["batch_stats"] if fwd is None else fwd["batch_stats"]
-            if on_dev or fwd is None:
-                stats_dev = DeviceArray.empty((nstat,), f32)
-                for bn, C, at, _ in slots:
-                    for fld, o in ((".mu", at), (".sigma2", at + C)):
-                        _lib.call("fx3d_memcpy_d2d", stats_dev.ptr + 4 * o, stats[bn + fld].ptr, 4 * C, stream)
-            else:
-                stats_dev = DeviceArray.from_host(np.concatenate([np.asarray(stats[bn + fld], f32) for bn, *_ in slots
-                                                                  for fld in (".mu", ".sigma2")]))
-            extra = (mask.ptr if mask is not None else None, stats_dev.ptr)
-        gp = DeviceArray.empty((self.param_count,), f32)
-        gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
-        mid = {k: DeviceArray.empty((r, N if c is None else c, B), f32) for k, (r, c) in self._MID.items()} if intermediates else None
-        ws = workspace(nb, tag="pointnet_grad_train" if train else "pointnet_grad")
-        _lib.call(entry, self._params_dev().ptr, nc, x.ptr, N, B, *extra, g.ptr, gp.ptr, gx.ptr if gx is not None else None,
-                  *(mid[k].ptr if mid else None for k in self._MID), ws.ptr, ws.nbytes, stream)
-        return gp, gx, mid, on_dev
+        return (self._like(dropout, "dropout", (256, B), np.float32, is_device(dropout)),)
 
     def flat_grad(self, X, glogits, input_grad=True, intermediates=False):
         """``(gflat, gx)``: the gradient of ``sum(glogits * logits)`` with respect to the parameters as ONE flat Float32 buffer
@@ -697,17 +741,7 @@ class PointNet(_Model):
         ``Flux.crossentropy(m(X), onehot(labels))`` with the network in training mode under the multipliers ``dropout`` (as in
         :meth:`forward_train`; an ``int`` seed is drawn once).  One :meth:`forward_train` with its intermediates, the loss and
         ``glogits`` on the host as in :meth:`crossentropy_grad`, then :meth:`grad_train` with that forward's statistics."""
-        _, N, B, on_dev = self._clouds(X, self._WHY)
-        y = self._labels(labels, B)
-        if isinstance(dropout, (int, np.integer)):
-            dropout = self.dropout_mask(B, int(dropout))
-            if on_dev:
-                dropout = DeviceArray.from_host(dropout)
-        fwd = self.forward_train(X, dropout=dropout, intermediates=True)
-        probs = fwd["probs"]
-        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
-        grads, gx = self.grad_train(X, DeviceArray.from_host(glogits) if on_dev else glogits, dropout=dropout, fwd=fwd)
-        return loss, grads, gx
+        return self._crossentropy_grad_train(X, labels, dropout)
 
 
 class DGCNN(_Model):
@@ -730,7 +764,7 @@ class DGCNN(_Model):
     functions of the batch -- are :meth:`grad_train`, :meth:`flat_grad_train` and :meth:`crossentropy_grad_train`
     (include/flux3d_hip.h "DGCNN training-mode adjoint")."""
 
-    _NAME, _COUNT_FN, _WHY = "DGCNN", "fx3d_dgcnn_param_count", "EdgeConv([3, 32, 64, 64], K)"
+    _NAME, _COUNT_FN, _WHY, _ENTRY = "DGCNN", "fx3d_dgcnn_param_count", "EdgeConv([3, 32, 64, 64], K)", "dgcnn"
 
     def __init__(self, num_classes=10, K=10, npoints=1024, seed=0):
         if int(num_classes) < 1:
@@ -757,10 +791,15 @@ class DGCNN(_Model):
         ``intermediates=True``: a dict with ``probs``, ``logits`` (num_classes, B), ``idx1`` and ``idx2`` (K, N, B) int32,
         0-based, ``x1`` (64, N, B), ``x2`` (256, N, B) and ``pooled`` (1024, B)."""
         _, N, B, _ = clouds = self._clouds(X, self._WHY)
-        nc, K = self.num_classes, self.K
-        return self._classify(clouds, "dgcnn", (nc, K), (N, B, K, nc), self._optional(N, B), intermediates)
+        return self._classify(clouds, self._ENTRY, self._lead(), self._sizes(N, B), self._optional(N, B), intermediates)
 
     __call__ = forward
+
+    def _lead(self):
+        return (self.num_classes, self.K)
+
+    def _sizes(self, N, B):
+        return (N, B, self.K, self.num_classes)
 
     def _optional(self, N, B):
         """The forward entries' optional outputs in their argument order: name -> (shape, dtype)."""
@@ -783,7 +822,7 @@ class DGCNN(_Model):
         return tuple(np.asfortranarray(np.where(rng.random((C_, int(B))) > p, keep, np.float32(0.0)).astype(np.float32))
                      for C_ in (512, 256))
 
-    def _train_masks(self, dropout, B, on_dev):
+    def _masks_of(self, dropout, B, on_dev):
         """``dropout`` of :meth:`forward_train` after its checks: ``(None, None)``, or the ``(512, B)`` and ``(256, B)``
         multipliers (an ``int``: the seed of :meth:`dropout_masks`), each a device array or a host array still to be uploaded."""
         if dropout is None:
@@ -817,134 +856,11 @@ class DGCNN(_Model):
         ``update=True`` writes ``running`` into the model's parameters, on the host (which reads them back: not inside a graph
         capture) and in the kept device copy: the next :meth:`forward` is the test-mode network after one training step's worth
         of statistics."""
-        pts, N, B, on_dev = self._clouds(X, self._WHY)
-        nc, K, f32 = self.num_classes, self.K, np.float32
-        if B < 2:
-            raise ValueError(f"training-mode BatchNorm needs at least two clouds (a Dense BatchNorm's running variance divides by "
-                             f"B - 1), got B={B}")
-        momentum = self._momentum(momentum)
-        masks = self._train_masks(dropout, B, on_dev)
-        nb = _lib.query_bytes("fx3d_dgcnn_train_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
-        masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
-        x = self._on_device(pts, N, B, on_dev)
-        slots = self._stat_slots()
-        out, stats = self._forward_train_call(x, N, B, masks, momentum, nb, intermediates, intermediates or update)
-        if update:
-            self._adopt_running(stats["running"], slots, current_stream().handle)
-        if not intermediates:
-            return out["probs"] if on_dev else out["probs"].to_host()
-        for key, buf in stats.items():
-            out[key] = self._named_stats(buf, slots, on_dev)
-        if not on_dev:
-            out = {k: (v if isinstance(v, dict) else v.to_host()) for k, v in out.items()}
-        return out
+        return self._forward_train(X, dropout, momentum, update, intermediates)
 
     _FWD_KEYS = ("idx1", "x1", "idx2", "x2", "pooled")
+    _MID = {"gx2": (256, None), "gx1": (64, None)}  # fx3d_dgcnn_grad's optional outputs, in order
     _STAT_FN, _DROPOUT, _GRAD_NEEDS_FWD = "fx3d_dgcnn_stat_count", ((512, 256), 0.5), True  # (train_step)
-
-    def _masks_of(self, dropout, B, on_dev):
-        return self._train_masks(dropout, B, on_dev)
-
-    def _train_bytes(self, N, B):
-        return _lib.query_bytes("fx3d_dgcnn_train_workspace_bytes", N, B, self.K, self.num_classes)
-
-    def _forward_train_call(self, x, N, B, masks, momentum, nb, intermediates, running):
-        """fx3d_dgcnn_forward_train on the device arrays ``x`` and ``masks`` (two, each possibly ``None``) with a workspace of ``nb``
-        bytes: ``(out, stats)`` -- ``probs`` and, with ``intermediates``, the optional outputs; the flat ``batch_stats`` and, with
-        ``running``, the flat ``running``."""
-        nc, K, f32 = self.num_classes, self.K, np.float32
-        slots = self._stat_slots()
-        nstat = slots[-1][2] + 2 * slots[-1][1]
-        optional = self._optional(N, B)
-        out = self._outputs(B, optional, intermediates)
-        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
-        if running:
-            stats["running"] = DeviceArray.empty((nstat,), f32)
-        ws = workspace(nb, tag="dgcnn_train")
-        _lib.call("fx3d_dgcnn_forward_train", self._params_dev().ptr, nc, K, x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
-                  momentum, out["probs"].ptr, *(out[k].ptr if intermediates else None for k in optional),
-                  stats["batch_stats"].ptr, stats["running"].ptr if running else None, ws.ptr, ws.nbytes, current_stream().handle)
-        return out, stats
-
-    def _grad_train_call(self, x, N, B, masks, out, batch_stats, glogits):
-        """fx3d_dgcnn_grad_train on device arrays, the forward's intermediates ``out`` and its flat ``batch_stats`` as it wrote
-        them: the flat gradient."""
-        nc, K = self.num_classes, self.K
-        ws = workspace(_lib.query_bytes("fx3d_dgcnn_grad_train_workspace_bytes", N, B, K, nc), tag="dgcnn_grad_train")
-        gp = DeviceArray.empty((self.param_count,), np.float32)
-        _lib.call("fx3d_dgcnn_grad_train", self._params_dev().ptr, nc, K, x.ptr, N, B, *(m.ptr if m is not None else None for m in masks),
-                  *(out[k].ptr for k in self._FWD_KEYS), batch_stats.ptr, glogits.ptr, gp.ptr, None, None, None, ws.ptr, ws.nbytes,
-                  current_stream().handle)
-        return gp
-
-    def _grad_call(self, X, glogits, input_grad, intermediates, fwd=None, train=False, dropout=None):
-        """fx3d_dgcnn_grad (``train``: fx3d_dgcnn_grad_train, with the dropout multipliers and with the intermediates and batch
-        statistics of ``fwd``, or of a :meth:`forward_train` run here) after the argument checks: (the flat gradient, gx or None,
-        gx2 and gx1 or None) on the device, and whether ``X`` lives there.  Every refusal comes before any device work."""
-        pts, N, B, on_dev = self._clouds(X, self._WHY)
-        nc, K, f32, i32 = self.num_classes, self.K, np.float32, np.int32
-        entry = "fx3d_dgcnn_grad_train" if train else "fx3d_dgcnn_grad"
-        if train:
-            if B < 2:
-                raise ValueError(f"training-mode BatchNorm needs at least two clouds, got B={B}")
-            masks = self._train_masks(dropout, B, on_dev)
-            slots = self._stat_slots()
-            nstat = slots[-1][2] + 2 * slots[-1][1]
-            names = [bn + f for bn, *_ in slots for f in (".mu", ".sigma2")]
-            if fwd is not None:
-                if not isinstance(fwd, dict) or "batch_stats" not in fwd:
-                    raise TypeError("fwd must be the dict of forward_train(..., intermediates=True)")
-                named = fwd["batch_stats"]
-                if not isinstance(named, dict) or [k for k in named] != names:
-                    raise ValueError(f"fwd['batch_stats'] must hold mu and sigma2 of the {len(slots)} BatchNorms in forward order")
-                for (bn, C_, _, _) in slots:
-                    for f in (".mu", ".sigma2"):
-                        v = named[bn + f]
-                        if is_device(v) != on_dev:
-                            raise TypeError("fwd must live where X lives")
-                        if tuple(v.shape) != (C_,) or v.dtype != f32:
-                            raise ValueError(f"fwd['batch_stats'][{bn + f!r}] must be Float32 ({C_},), got {v.dtype} {tuple(v.shape)}")
-        nb = _lib.query_bytes(entry + "_workspace_bytes", N, B, K, nc)  # (the library's own size limits)
-        g = self._like(glogits, "glogits", (nc, B), f32, on_dev)
-        given = [None] * len(self._FWD_KEYS)
-        if fwd is not None:
-            missing = [k for k in self._FWD_KEYS if k not in fwd]
-            if missing:
-                raise ValueError(f"fwd must be the dict of forward{'_train' if train else ''}(X, intermediates=True): it has no {missing}")
-            shapes = {"idx1": ((K, N, B), i32), "x1": ((64, N, B), f32), "idx2": ((K, N, B), i32), "x2": ((256, N, B), f32),
-                      "pooled": ((1024, B), f32)}
-            given = [self._like(fwd[k], f"fwd['{k}']", *shapes[k], on_dev) for k in self._FWD_KEYS]
-            for k, a in zip(self._FWD_KEYS, given):
-                if not on_dev and a.dtype == i32 and a.size and (a.min() < 0 or a.max() >= N):
-                    raise ValueError(f"fwd['{k}'] must hold 0-based indices in [0, {N}), got values from {a.min()} to {a.max()}")
-        if not on_dev:
-            g = DeviceArray.from_host(g)
-            given = [None if a is None else DeviceArray.from_host(a) for a in given]
-        x = self._on_device(pts, N, B, on_dev)
-        stream = current_stream().handle
-        lead = ()
-        if train:
-            masks = [m if m is None or is_device(m) else DeviceArray.from_host(m) for m in masks]
-            if fwd is None:
-                made = self.forward_train(x, dropout=None if dropout is None else tuple(masks), intermediates=True)
-                given, named = [made[k] for k in self._FWD_KEYS], made["batch_stats"]
-            # the 8 BatchNorms' statistics (views of forward_train's buffer, or the caller's arrays) as one buffer in the layout's order
-            if on_dev or fwd is None:
-                stats = DeviceArray.empty((nstat,), f32)
-                for bn, C_, at, _ in slots:
-                    for fld, off in ((".mu", at), (".sigma2", at + C_)):
-                        _lib.call("fx3d_memcpy_d2d", stats.ptr + 4 * off, named[bn + fld].ptr, 4 * C_, stream)
-            else:
-                stats = DeviceArray.from_host(np.concatenate([np.asarray(named[k], f32) for k in names]))
-            lead = tuple(m.ptr if m is not None else None for m in masks)
-        gp = DeviceArray.empty((self.param_count,), f32)
-        gx = DeviceArray.empty((3, N, B), f32) if input_grad else None
-        mid = {"gx2": DeviceArray.empty((256, N, B), f32), "gx1": DeviceArray.empty((64, N, B), f32)} if intermediates else None
-        ws = workspace(nb, tag=entry[5:])
-        _lib.call(entry, self._params_dev().ptr, nc, K, x.ptr, N, B, *lead, *(None if a is None else a.ptr for a in given),
-                  *((stats.ptr,) if train else ()), g.ptr, gp.ptr, gx.ptr if gx is not None else None,
-                  mid["gx2"].ptr if mid else None, mid["gx1"].ptr if mid else None, ws.ptr, ws.nbytes, stream)
-        return gp, gx, mid, on_dev
 
     def flat_grad(self, X, glogits, fwd=None, input_grad=True, intermediates=False):
         """``(gflat, gx)``: the gradient of ``sum(glogits * logits)`` with respect to the parameters as ONE flat Float32 buffer
@@ -991,17 +907,7 @@ class DGCNN(_Model):
         ``Flux.crossentropy(m(X), onehot(labels))`` with the network in training mode under the multipliers ``dropout`` (as in
         :meth:`forward_train`; an ``int`` seed is drawn once).  One :meth:`forward_train` with its intermediates, the loss and
         ``glogits`` on the host as in :meth:`crossentropy_grad`, then :meth:`grad_train` with that forward."""
-        _, N, B, on_dev = self._clouds(X, self._WHY)
-        y = self._labels(labels, B)
-        if isinstance(dropout, (int, np.integer)):
-            dropout = self.dropout_masks(B, int(dropout))
-            if on_dev:
-                dropout = tuple(DeviceArray.from_host(m) for m in dropout)
-        fwd = self.forward_train(X, dropout=dropout, intermediates=True)
-        probs = fwd["probs"]
-        loss, glogits = self._crossentropy(probs.to_host() if on_dev else probs, y, B)
-        grads, gx = self.grad_train(X, DeviceArray.from_host(glogits) if on_dev else glogits, dropout=dropout, fwd=fwd)
-        return loss, grads, gx
+        return self._crossentropy_grad_train(X, labels, dropout)
 
 
 class EdgeConv(_Model):
