@@ -312,6 +312,8 @@ fx3d_status chamfer_forward(const float *x, int N, const float *y, int M, int B,
         set_error("%s: workspace too small (%zu < %zu bytes)", fn, ws ? ws_bytes : (size_t)0, w.need);
         return FX3D_ERR_WORKSPACE;
     }
+    // the split plan's two-launch form ends in nn1_split_finalize_launch, whose grid holds both directions of every cloud in y
+    if (pl.nsplit > 1 && 2ll * B * pl.tiles > kSplitFuseMax) FX3D_REQUIRE_GRID_Y(fn, B, 2);
     char *const base = static_cast<char *>(ws);
     Nn1Params p{};
     p.x = x; p.y = y; p.N = N; p.M = M; p.B = B;

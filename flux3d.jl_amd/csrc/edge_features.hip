@@ -230,6 +230,7 @@ fx3d_status fx3d_edge_features(const float *x, int32_t N, int32_t B, int32_t F, 
     FX3D_REQUIRE(x && idx && out, "fx3d_edge_features: null pointer");
     FX3D_REQUIRE(N > 0 && B > 0 && F > 0 && k > 0, "fx3d_edge_features: bad sizes");
     FX3D_REQUIRE(layout == 0 || layout == 1, "fx3d_edge_features: layout must be 0 (2F,K,N,B) or 1 (K*N,2F,B)");
+    if (layout == 1) FX3D_REQUIRE_GRID_Y("fx3d_edge_features", B, 1);  // (the layout-1 kernels take the cloud from blockIdx.y)
     ProfileScope prof("edge_features", as_stream(s));
     if (layout == 0) {
         const long long total = (long long)B * N * k * 2 * F;

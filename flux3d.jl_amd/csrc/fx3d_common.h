@@ -33,6 +33,12 @@ inline fx3d_status hip_fail(hipError_t e, const char *what, const char *file, in
         }                                        \
     } while (0)
 
+// An entry point whose launches put the batch on gridDim.y refuses a batch the grid cannot take with its other arguments, before
+// any memset or launch (fn: its name; per: grid rows per cloud, 1 or 2); the message names B.
+constexpr int kMaxGridY = 65535;
+#define FX3D_REQUIRE_GRID_Y(fn, B, per) \
+    FX3D_REQUIRE((B) <= fx3d::kMaxGridY / (per), "%s: B = %d exceeds the grid's y range (at most %d)", fn, (int)(B), fx3d::kMaxGridY / (per))
+
 // checks the launch itself (configuration errors); execution errors surface at the next sync
 #define FX3D_LAUNCH_CHECK() FX3D_HIP(hipGetLastError())
 

@@ -858,6 +858,7 @@ fx3d_status fx3d_edgeconv_graph(const float *x, int32_t N, int32_t B, int32_t F,
         ProfileScope prof("edgeconv_graph", as_stream(s));
         return knn_d3_launch(x, N, x, N, B, k, 1, idx, nullptr, as_stream(s), out, layout, 1);
     }
+    if (layout == 1) FX3D_REQUIRE_GRID_Y("fx3d_edgeconv_graph", B, 1);  // (fx3d_edge_features' limit, before the search runs)
     fx3d_status rc = fx3d_knn(x, N, x, N, B, F, k, 1, idx, nullptr, s);
     if (rc != FX3D_OK) return rc;
     return fx3d_edge_features(x, N, B, F, k, idx, layout, out, s);

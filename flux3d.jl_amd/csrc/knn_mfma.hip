@@ -260,8 +260,8 @@ __device__ __forceinline__ void knn_stage_chunk(const float *__restrict__ yb, in
 // Pre-pass of the feature-space kNN (fx3d_knn_ws): the per-cloud statistics and the fp16 image are built ONCE per cloud
 // instead of by every block of the cloud (8 blocks per cloud at C4': the scale pass alone was 8 us of the 78, bound by the
 // L2 -- every block read the whole cloud -- and the producers' conversion VALU delayed the consumers' MFMAs in both phases).
-//   knn_pre_stats_kernel   grid (kPreParts, B): minima / maxima / sums per dimension of one eighth of the cloud's rows
-//   knn_pre_image_kernel   grid (kPreParts, B): combines the eight parts (every block the same arithmetic: identical centre
+//   knn_pre_stats_kernel   grid (kPreParts * B): minima / maxima / sums per dimension of one eighth of the cloud's rows
+//   knn_pre_image_kernel   grid (kPreParts * B): combines the eight parts (every block the same arithmetic: identical centre
 //                          and scale), robust centre as in knn_mfma_kernel, converts its rows: fp16 image [Mpad][DP], scaled
 //                          row norms (the candidate's error share folded in, upwards / downwards), largest norm of the part
 // knn_mfma_kernel then reads the header, and its producer waves bring image chunks and norms in with direct-to-LDS loads (no
@@ -363,7 +363,7 @@ __device__ __forceinline__ void knn_pre_stats_body(const float *__restrict__ y, 
 }
 __global__ __launch_bounds__(kPreThreads) void knn_pre_stats_kernel(const float *__restrict__ y, int M, int D, int DP, KnnPre pre) {
     __shared__ float red[(kPreThreads / 64) * 32 * 12];
-    knn_pre_stats_body(y, M, D, DP, pre, blockIdx.x, blockIdx.y, red);
+    knn_pre_stats_body(y, M, D, DP, pre, blockIdx.x % kPreParts, blockIdx.x / kPreParts, red);
 }
 
 // mu: [DP] floats, sh: 4 words of LDS ([0] bits of the extent  [1] skew flag  [2] bits of the bulk radius  [3] largest norm of the part)
@@ -534,7 +534,7 @@ template <int DK>
 __global__ __launch_bounds__(kPreThreads) void knn_pre_image_kernel(const float *__restrict__ y, int M, int D, int two_norms, KnnPre pre) {
     __shared__ float mu[DK * 32];
     __shared__ unsigned int sh[4];
-    knn_pre_image_body<DK>(y, M, D, two_norms, pre, blockIdx.x, blockIdx.y, mu, sh);
+    knn_pre_image_body<DK>(y, M, D, two_norms, pre, blockIdx.x % kPreParts, blockIdx.x / kPreParts, mu, sh);
 }
 // (Two launches: one 1024-thread block per cloud for the whole pre-pass measured slower)
 
@@ -2283,8 +2283,9 @@ fx3d_status knn_mfma_launch(const float *x, int N, const float *y, int M, int B,
     const int bpad = B >= 8 ? (B + 7) / 8 * 8 : B;
     if (use_pre) {
         const KnnPre pre = KnnPre::make(pre_ws, M, DP);
-        hipLaunchKernelGGL(knn_pre_stats_kernel, dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, DP, pre);
-        hipLaunchKernelGGL(pre_image[di], dim3(kPreParts, B), dim3(kPreThreads), 0, st, y, M, D, p.two_norms, pre);
+        // (the batch in x with the parts, like the search kernel's: grid y stops at 65535 clouds)
+        hipLaunchKernelGGL(knn_pre_stats_kernel, dim3(kPreParts * (unsigned int)B), dim3(kPreThreads), 0, st, y, M, D, DP, pre);
+        hipLaunchKernelGGL(pre_image[di], dim3(kPreParts * (unsigned int)B), dim3(kPreThreads), 0, st, y, M, D, p.two_norms, pre);
     }
     const KnnMfmaArgs args{x, N, y, M, B, D, k, drop, idx, dist, p.CH, p.img, p.keep_norms, p.two_norms, p.srl, p.csl, use_pre ? pre_ws : nullptr, xdiv};
     hipLaunchKernelGGL(kernel, dim3(nbx * bpad), dim3(kMThreads), p.lds, st, args);

@@ -610,6 +610,9 @@ int cdf_variant(int Vmax, int Fmax, size_t *lds) {
 fx3d_status cdf_check(const CdfArgs &a, const char *fn) {
     FX3D_REQUIRE(a.verts_padded && a.faces_padded && a.faces_len, "%s: null pointer", fn);
     FX3D_REQUIRE(a.Vmax > 0 && a.Fmax > 0 && a.B > 0, "%s: bad sizes", fn);
+    size_t lds = 0;
+    // the multi-block path has the meshes on the grid's y (a pair: both batches are checked before either is launched)
+    if (cdf_variant(a.Vmax, a.Fmax, &lds) == 0) FX3D_REQUIRE_GRID_Y(fn, a.B, 1);
     return ws_check(fn, "workspace", a.ws, a.ws_bytes, ws_bytes_needed(a.Fmax, a.B), "");
 }
 
@@ -627,7 +630,7 @@ fx3d_status cdf_launch(const CdfArgs &a, const CdfArgs *b, double eps, hipStream
         const CdfWs W = CdfWs::make(a.Fmax);
         const int nb = (W.nchp / kChunk + kChunk - 1) / kChunk, nsub = (W.Fp + kCdfSub - 1) / kCdfSub;
         FX3D_REQUIRE(nb <= kChunk * kChunk, "fx3d_sample_points_cdf: more than 33 554 432 faces per mesh");
-        FX3D_REQUIRE(a.B <= 65535, "fx3d_sample_points_cdf: more than 65535 meshes in one batch");
+        // (a.B <= 65535: cdf_check)
         hipLaunchKernelGGL(cdf_mb_areas_kernel, dim3(nsub, a.B), dim3(kCdfThreads), 0, st, a.verts_padded, a.Vmax, a.faces_padded, a.faces_len, a.Fmax, cdf);
         hipLaunchKernelGGL(cdf_mb_top_kernel<false>, dim3(a.B), dim3(kCdfThreads), 0, st, a.Fmax, eps, cdf);
         hipLaunchKernelGGL(cdf_mb_prob_kernel, dim3(nsub, a.B), dim3(kCdfThreads), 0, st, a.Fmax, cdf);

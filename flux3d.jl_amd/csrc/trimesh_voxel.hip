@@ -306,6 +306,7 @@ fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vmax, const
     FX3D_REQUIRE(Vmax > 0 && Vmax <= INT32_MAX / 3 && Fmax >= 0 && B > 0 && res > 0 && res <= 1024 &&
                      (long long)B * (chunks(Fmax) + 1) < INT32_MAX,
                  "fx3d_trimesh_to_voxel: bad sizes");
+    FX3D_REQUIRE_GRID_Y("fx3d_trimesh_to_voxel", B, 1);  // (tv_count_kernel; before the memset of `voxels`)
     const Layout l = ws_layout(Fmax, B);
     FX3D_REQUIRE(ws_bytes >= l.total, "fx3d_trimesh_to_voxel: workspace too small");
     hipStream_t st = as_stream(s);

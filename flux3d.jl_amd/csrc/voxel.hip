@@ -91,6 +91,7 @@ fx3d_status fx3d_pointcloud_to_voxel(const float *points, int32_t N, int32_t B, 
                                      void *ws, size_t ws_bytes, fx3d_stream_t s) {
     FX3D_REQUIRE(points && voxels && ws, "fx3d_pointcloud_to_voxel: null pointer");
     FX3D_REQUIRE(N > 0 && B > 0 && res > 0 && res <= 1024, "fx3d_pointcloud_to_voxel: bad sizes");
+    FX3D_REQUIRE_GRID_Y("fx3d_pointcloud_to_voxel", B, 1);  // (voxel_scatter_kernel; before the memset of `voxels`)
     FX3D_REQUIRE(ws_bytes >= sizeof(float) * 2 * (size_t)B, "fx3d_pointcloud_to_voxel: workspace too small");
     hipStream_t st = as_stream(s);
     float *range = static_cast<float *>(ws);

@@ -153,6 +153,7 @@ FX3D_API fx3d_status fx3d_profile_kernel_stats(const char *name, double *avg_ms,
  * direct-difference distance, lowest index on ties.  x:(D,N,B) y:(D,M,B) device.
  * idx_x:(N,B) int32 0-based index into y ; idx_y:(M,B) into x ; dmin_* squared distances.
  * Any of the four outputs may be NULL. */
+/* Batch axis: fx3d_nn1: B <= 536870911 -- the batch lies on the grid's x; B * 2 * ceil(max(N, M) / 256) < 2^30 is all that binds it. */
 FX3D_API fx3d_status fx3d_nn1(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
                               int32_t D, int32_t *idx_x, int32_t *idx_y, float *dmin_x,
                               float *dmin_y, fx3d_stream_t s);
@@ -160,18 +161,23 @@ FX3D_API fx3d_status fx3d_nn1(const float *x, int32_t N, const float *y, int32_t
 /* The launch plan fx3d_nn1 / fx3d_chamfer_* take for this problem size on the current device, as text (kernel variant,
  * candidates per LDS image, chunk subsets per query tile, query passes per block, query tiles, grid, queries per thread R,
  * and last the kernel: f16, tiny, small_d or generic): for tools and bug reports. */
+/* Batch axis: fx3d_nn1_plan_describe: unbounded -- a host query; it does not apply the entry points' limit. */
 FX3D_API fx3d_status fx3d_nn1_plan_describe(int32_t N, int32_t M, int32_t B, int32_t D, char *buf, size_t n);
 
 /* Scratch needed by the chamfer entry points below (bytes).  While nn1_prune is on, a shape that takes the pruned launch asks for
  * the blocks' scratch on top of the partial sums: 16-bit point indices, two bytes per candidate and per query of a block's window
  * (2.7 MB at B = 32, N = M = 4096).  A workspace of at least this size runs pruned, a smaller one that still holds the partial
  * sums (the size reported with nn1_prune = 0) runs unpruned; both give the same indices. */
+/* Batch axis: fx3d_chamfer_workspace_bytes: unbounded -- a host query; it does not apply the entry points' limit. */
 FX3D_API fx3d_status fx3d_chamfer_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D,
                                                   size_t *bytes);
 
 /* Partial sums of _chamfer_distance (src/metrics/pcloud.jl:47-48) for this batch (shard):
  *   sums_dev[0] = sum_b sum_i ||x_i - y_nn(i)||^2 ,  sums_dev[1] = sum_b sum_j ||y_j - x_nn(j)||^2
  * (double, device, deterministic reduction order).  idx_x/idx_y optional (NULL to skip). */
+/* Batch axis: fx3d_chamfer_sums: B <= 536870911 -- as fx3d_nn1.  The split plan's two-launch form (few clouds of many thousands of
+ * points) has both directions of every cloud on the grid's y and refuses B > 32767 before any launch; no shape with that many
+ * clouds plans it today. */
 FX3D_API fx3d_status fx3d_chamfer_sums(const float *x, int32_t N, const float *y, int32_t M,
                                        int32_t B, int32_t D, double *sums_dev, int32_t *idx_x,
                                        int32_t *idx_y, void *ws, size_t ws_bytes,
@@ -214,6 +220,8 @@ FX3D_API fx3d_status fx3d_chamfer_finalize_many(const double *sums_dev, int32_t 
 #define FX3D_NORMALIZE_EPS_MAX 1 /* TriMesh:    (x - c) / max(s, EPS), Julia's max (NaN wins)   mesh_func.jl:99-113 */
 #define FX3D_SCALE 0             /* y = factor * x       (lmul!, pcloud_func.jl:62-66, mesh_func.jl:154-160) */
 #define FX3D_TRANSLATE 1         /* y = x + t[row]       (mesh_func.jl:331-339), D = 3 */
+/* Batch axis: fx3d_transform_plan_describe, fx3d_transform_workspace_bytes, fx3d_segment_minmax, fx3d_normalize, fx3d_realign,
+ * fx3d_rotate: B <= 65535 -- a segment is a row of the grid's y; refused by the argument check, the queries included. */
 FX3D_API fx3d_status fx3d_transform_plan_describe(int32_t D, int64_t n_max, int32_t B, char *buf, size_t n);
 FX3D_API fx3d_status fx3d_transform_workspace_bytes(int32_t D, int64_t n_max, int32_t B, size_t *bytes);
 /* minimum / maximum(x, dims = 2) per segment with Julia's min / max (NaN propagates, min(-0.0, 0.0) = -0.0,
@@ -248,6 +256,7 @@ FX3D_API fx3d_status fx3d_scale_translate(const float *x, int64_t n, int32_t mod
 
 /* _chamfer_distance(A,B,w1,w2) forward in one call (src/metrics/pcloud.jl:39-52). loss_dev
  * device float; loss_host optional host float (non-NULL => stream is synchronised). */
+/* Batch axis: fx3d_chamfer_fwd, fx3d_chamfer_bwd: B <= 536870911 -- as fx3d_nn1 (fx3d_chamfer_fwd: and as fx3d_chamfer_sums). */
 FX3D_API fx3d_status fx3d_chamfer_fwd(const float *x, int32_t N, const float *y, int32_t M,
                                       int32_t B, int32_t D, float w1, float w2, float *loss_dev,
                                       float *loss_host, int32_t *idx_x, int32_t *idx_y,
@@ -266,6 +275,7 @@ FX3D_API fx3d_status fx3d_chamfer_bwd(const float *x, int32_t N, const float *y,
  * and fx3d_chamfer_bwd are queued back to back on the stream; the nearest-neighbour indices stay in the scratch unless
  * idx_x (N,B) / idx_y (M,B) are given.  gx (D,N,B), gy (D,M,B) overwritten.  loss_host non-NULL => the stream is
  * synchronised.  ws: fx3d_chamfer_fwd_bwd_workspace_bytes. */
+/* Batch axis: fx3d_chamfer_fwd_bwd_workspace_bytes: unbounded -- a host query.  fx3d_chamfer_fwd_bwd: B <= 536870911 -- as fx3d_nn1. */
 FX3D_API fx3d_status fx3d_chamfer_fwd_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, size_t *bytes);
 FX3D_API fx3d_status fx3d_chamfer_fwd_bwd(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D,
                                           float w1, float w2, float gout, int64_t B_global, float *loss_dev,
@@ -284,6 +294,8 @@ FX3D_API fx3d_status fx3d_chamfer_fwd_bwd(const float *x, int32_t N, const float
  * gather); ws: fx3d_chamfer_sampled_bwd_workspace_bytes.  NULL tables (or a mesh beyond the limits): ONE launch that scatters the rows
  * with global float atomics (sums in arrival order), ws unused -- ~9 us per call faster at one mesh of 5000 draws as a single call (inside
  * a fit iteration the ordered form is the faster one), slower at eight meshes, not reproducible. */
+/* Batch axis: fx3d_chamfer_sampled_bwd_workspace_bytes: unbounded -- a host query.  fx3d_chamfer_sampled_bwd,
+ * fx3d_chamfer_sampled_bwd_step, fx3d_chamfer_sampled_bwd_step_reg: B <= 536870911 -- as fx3d_nn1, and 2 B nsplit < 2^30. */
 FX3D_API fx3d_status fx3d_chamfer_sampled_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_chamfer_sampled_bwd(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
                                               const int32_t *idx_x, const int32_t *idx_y, float w1, float w2, float gout,
@@ -333,6 +345,7 @@ typedef struct fx3d_mesh_reg {
     void *ws;
     size_t ws_bytes;
 } fx3d_mesh_reg;
+/* Batch axis: fx3d_sample_points_draw_pair_reg: unbounded -- B0 and B1 as fx3d_sample_points_draw. */
 FX3D_API fx3d_status fx3d_sample_points_draw_pair_reg(const float *verts0, int32_t Vmax0, const int32_t *faces0, int32_t Fmax0,
                                                       const int32_t *faces_len0, int32_t B0, int32_t n0, uint64_t seed0, const void *cdf_ws0,
                                                       size_t ws_bytes0, float *out0, int32_t *face_out0, float *r1_out0, float *r2_out0,
@@ -361,6 +374,12 @@ FX3D_API fx3d_status fx3d_chamfer_sampled_bwd_step_reg(const float *x, int32_t N
  * sort after +Inf, so every returned index is valid; fx3d_nn1 / the chamfer entry points use the same order.  The distance is
  * the Float32 one AS ROUNDED: where the squares underflow (a cloud of extent 1e-20: subnormal distances of a few bits; 1e-29:
  * every distance +0) the ties this makes are ordered by index, like those of +Inf distances at the other end. */
+/* Batch axis: fx3d_knn, fx3d_knn_workspace_bytes, fx3d_knn_ws: unbounded -- on the matrix-core routes (D = 3 with M >= 64 and
+ * k + drop_first <= 32, or <= 64 on larger clouds; 4 <= D <= 128 with M >= 64 and k + drop_first <= 32), which fold the batch,
+ * padded to a multiple of 8, into the grid's x, the pre-pass of fx3d_knn_ws included.  Every other shape takes a kernel with the
+ * batch on the grid's y: B <= 65535 there, refused before any launch with a message that names B.  The candidate slices of
+ * fx3d_knn_ws are planned only while B x slices <= 65535; beyond that the query returns the unsliced plan's size and the call
+ * runs it, so query and call agree on both sides. */
 FX3D_API fx3d_status fx3d_knn(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
                               int32_t D, int32_t k, int32_t drop_first, int32_t *idx,
                               float *dist, fx3d_stream_t s);
@@ -380,6 +399,10 @@ FX3D_API fx3d_status fx3d_knn_ws(const float *x, int32_t N, const float *y, int3
                                  int32_t drop_first, int32_t *idx, float *dist, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 /* X[:, idxs] gather -> (F,k,N,B)  (src/models/dgcnn.jl:6 `X[:, knn(...)]`, cat at :36). */
+/* Batch axis: fx3d_knn_gather, fx3d_edge_features, fx3d_edge_features_bwd, fx3d_edgeconv_graph: unbounded -- grid-stride kernels
+ * over all elements.  Layout 1 of fx3d_edge_features has the cloud on the grid's y: B <= 65535 there, and so for
+ * fx3d_edgeconv_graph at layout 1 wherever it is not the fused F = 3 kernel; fx3d_edgeconv_graph off the matrix-core routes is
+ * bound as fx3d_knn.  Each is refused before any launch, the search of fx3d_edgeconv_graph included. */
 FX3D_API fx3d_status fx3d_knn_gather(const float *x, int32_t N, int32_t B, int32_t F, int32_t k,
                                      const int32_t *idx, float *out, fx3d_stream_t s);
 
@@ -428,6 +451,7 @@ FX3D_API fx3d_status fx3d_index_upload(const void *src_host, int32_t index_type,
 FX3D_API fx3d_status fx3d_faces_areas_packed(const float *verts, int64_t V, const int32_t *faces,
                                              int64_t F, float *areas, fx3d_stream_t s);
 /* compute_faces_areas_padded (src/rep/mesh.jl:799-808): areas (1,Fmax,B), zero padded. */
+/* Batch axis: fx3d_faces_areas_padded: unbounded -- a grid-stride kernel over B * Fmax faces. */
 FX3D_API fx3d_status fx3d_faces_areas_padded(const float *verts_padded, int32_t Vmax,
                                              const int32_t *faces_padded, int32_t Fmax,
                                              const int32_t *faces_len, int32_t B, float *areas,
@@ -479,6 +503,11 @@ FX3D_API fx3d_status fx3d_faces_normals_bwd(const float *verts, int64_t V, const
 
 /* _sample_points + _rand_barycentric_coords (src/transforms/mesh_func.jl:60-82) with the random
  * draws supplied: face_idx (n,B) int32 mesh-local 0-based, r1,r2 (n,B) in [0,1).  out (3,n,B). */
+/* Batch axis: fx3d_sample_points_explicit, fx3d_sample_points_workspace_bytes, fx3d_sample_points, fx3d_sample_points_cdf,
+ * fx3d_sample_points_draw, fx3d_sample_points_cdf_pair, fx3d_sample_points_draw_pair: unbounded -- one block per mesh on the
+ * grid's x (the CDF) and grid-stride kernels over B * n samples (the draws).  Beyond 32768 faces per mesh (or the option cdf_multiblock_from) the CDF is built by
+ * several blocks per mesh with the meshes on the grid's y: B <= 65535 there, refused by the argument check (of a pair: for both
+ * batches before either is launched). */
 FX3D_API fx3d_status fx3d_sample_points_explicit(const float *verts_padded, int32_t Vmax,
                                                  const int32_t *faces_padded, int32_t Fmax,
                                                  int32_t B, int32_t n, const int32_t *face_idx,
@@ -543,9 +572,11 @@ FX3D_API fx3d_status fx3d_sample_points_draw_pair(const float *verts0, int32_t V
  * ascending, of (0 + sum over the face's draws k, ascending, of w_corner(k) * gout[k]) in unfused Float32 -- no float atomics, the
  * same bits on every run (one block per mesh: draws bucketed by face and staged in LDS).
  * NULL tables, or a mesh beyond those limits: scatter with global float atomics (sums in arrival order). */
+/* Batch axis: fx3d_build_vertex_faces: unbounded -- a host loop over the meshes. */
 FX3D_API fx3d_status fx3d_build_vertex_faces(const int32_t *faces_padded_host, const int32_t *faces_len_host, int32_t Vmax,
                                              int32_t Fmax, int32_t B, int32_t *vf_rowptr_host, int32_t *vf_ent_host);
 FX3D_API fx3d_status fx3d_sample_points_bwd_ordered(int32_t Fmax, int32_t n, int32_t *ordered);
+/* Batch axis: fx3d_sample_points_bwd: B <= 67108863 -- 16 B < 2^30 (the ordered form's grid); the batch lies on the grid's x. */
 FX3D_API fx3d_status fx3d_sample_points_bwd(const int32_t *faces_padded, int32_t Vmax,
                                             int32_t Fmax, int32_t B, int32_t n,
                                             const int32_t *face_idx, const float *r1,
@@ -569,6 +600,7 @@ FX3D_API fx3d_status fx3d_momentum_step_offset(int64_t n, float rho, float eta, 
                                                const float *base, float *out, uint64_t *ctr, uint64_t inc, fx3d_stream_t s);
 /* _packed_to_padded / _padded_to_packed for (3,*) Float32 vertex arrays without leaving the device
  * (src/rep/utils.jl:119-181).  verts_len is a HOST array of B lengths. */
+/* Batch axis: fx3d_packed_to_padded, fx3d_padded_to_packed: unbounded -- one device copy per mesh, no kernel. */
 FX3D_API fx3d_status fx3d_packed_to_padded(const float *packed, const int64_t *verts_len_host, int32_t B,
                                            int32_t Vmax, float *padded, fx3d_stream_t s);
 FX3D_API fx3d_status fx3d_padded_to_packed(const float *padded, const int64_t *verts_len_host, int32_t B,
@@ -646,6 +678,8 @@ FX3D_API fx3d_status fx3d_mesh_losses_bwd(const float *verts, int64_t V, const i
  * lattice centre lies within sqrt(0.6)/res after normalising the cloud by its scalar min/max; Float64
  * distance test exactly as at :125-129 (lattice (i+0.5)/res for i = 1..res, first array dimension = the
  * reference's innermost loop variable z).  ws: fx3d_voxel_workspace_bytes(B). */
+/* Batch axis: fx3d_voxel_workspace_bytes: unbounded -- a host query.  fx3d_pointcloud_to_voxel: B <= 65535 -- the scatter kernel
+ * has the cloud on the grid's y; refused by the argument check, before `voxels` is cleared, with a message that names B. */
 FX3D_API fx3d_status fx3d_voxel_workspace_bytes(int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_pointcloud_to_voxel(const float *points, int32_t N, int32_t B, int32_t res,
                                               float *voxels, void *ws, size_t ws_bytes, fx3d_stream_t s);
@@ -659,6 +693,8 @@ FX3D_API fx3d_status fx3d_pointcloud_to_voxel(const float *points, int32_t N, in
  * no vertices, a face id outside [0, verts_len)) is COUNTED in *bad_dev (optional, caller-zeroed device counter) and its
  * grid stays zero.  1 <= res <= 1024.  No host synchronisation (graph-capturable).
  * ws: fx3d_trimesh_voxel_workspace_bytes(Vmax, Fmax, B, res). */
+/* Batch axis: fx3d_trimesh_voxel_workspace_bytes: unbounded -- a host query.  fx3d_trimesh_to_voxel: B <= 65535 -- the counting
+ * kernel has the mesh on the grid's y; refused by the argument check, before `voxels` is cleared, with a message that names B. */
 FX3D_API fx3d_status fx3d_trimesh_voxel_workspace_bytes(int32_t Vmax, int32_t Fmax, int32_t B, int32_t res, size_t *bytes);
 FX3D_API fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vmax, const int32_t *verts_len,
                                            const int32_t *faces_padded, int32_t Fmax, const int32_t *faces_len,
@@ -679,6 +715,8 @@ FX3D_API fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vm
  *   faces_padded (3,Fmax,B) int32 0-based mesh-local, optional (NULL: none): cube j of a grid gets the reference's 12
  *   faces + 8j; entries behind a grid's 12 K faces are 0.  A grid with 12 K > Fmax gets no faces.  8 K must stay below
  *   2^31 (int32 face ids).  No entry point synchronises the host.  ws: fx3d_voxel_mesh_workspace_bytes(res, B). */
+/* Batch axis: fx3d_voxel_mesh_workspace_bytes, fx3d_voxel_mesh_count, fx3d_voxel_mesh_emit: B <= 16777216 -- the batch lies on the
+ * grid's x; 2^24 grids, and tiles per grid x B < 2^31. */
 FX3D_API fx3d_status fx3d_voxel_mesh_workspace_bytes(int32_t res, int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_voxel_mesh_count(const float *voxels, int32_t res, int32_t B, float thresh, int64_t *cubes_dev,
                                            uint32_t *bad_dev, void *ws, size_t ws_bytes, fx3d_stream_t s);
@@ -691,6 +729,8 @@ FX3D_API fx3d_status fx3d_voxel_mesh_emit(int32_t res, int32_t B, int64_t max_cu
  * src/metrics/pcloud.jl:47-50) -- bit for bit oracle/flux3d_oracle.c: fx3d_oracle_chamfer_loss_pairwise.  fx3d_chamfer_fwd
  * sums in Float64 (one rounding, order independent); this entry point is for a host that wants the reference's last bit.
  * Three small launches on `s`; loss_host optional (blocks).  ws: fx3d_chamfer_pairwise_workspace_bytes. */
+/* Batch axis: fx3d_chamfer_pairwise_workspace_bytes: unbounded -- a host query.  fx3d_chamfer_loss_pairwise_f32: B <= 536870911 --
+ * as fx3d_nn1. */
 FX3D_API fx3d_status fx3d_chamfer_pairwise_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, size_t *bytes);
 FX3D_API fx3d_status fx3d_chamfer_loss_pairwise_f32(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
                                                     int32_t D, const int32_t *idx_x, const int32_t *idx_y, float w1,
@@ -753,6 +793,7 @@ FX3D_API fx3d_status fx3d_chamfer_fwd_sharded_async(fx3d_comm_t comm, const floa
  * fast: the PCIe copies are inside the call.  Indices 0-based int32 as everywhere at this boundary.
  * fx3d_chamfer_distance_host: any of loss / idx_x / idx_y may be NULL (not all).  fx3d_knn_host: y == NULL -> self
  * search (M ignored); dist optional.  Faces / edges / CSR as for the device entry points above. */
+/* Batch axis: fx3d_chamfer_distance_host, fx3d_knn_host, fx3d_sample_points_host: unbounded -- host loops, no device. */
 FX3D_API fx3d_status fx3d_chamfer_distance_host(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D,
                                                 float w1, float w2, float *loss, int32_t *idx_x, int32_t *idx_y);
 FX3D_API fx3d_status fx3d_knn_host(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D, int32_t k,
@@ -833,6 +874,8 @@ FX3D_API fx3d_status fx3d_laplacian_dev_csr(const int32_t *edges, int64_t E, int
  * mesh has Fmax faces); vf_rowptr (Vmax+1,B), vf_ent (3 Fmax,B): the entries of a vertex are face * 4 + corner ascending, padding faces are ignored,
  * the slots of a column behind vf_rowptr[Vmax,b] are 0.  The packed table is the B = 1 call over faces_packed.  bad_dev
  * optional: ids outside [0, Vmax) in live faces and lengths outside [0, Fmax].  ws: fx3d_vertex_faces_dev_workspace_bytes. */
+/* Batch axis: fx3d_vertex_faces_dev_workspace_bytes, fx3d_vertex_faces_dev: B <= 715827882 -- grid-stride kernels; 3 Fmax B and
+ * Vmax B stay below 2^31. */
 FX3D_API fx3d_status fx3d_vertex_faces_dev_workspace_bytes(int32_t Vmax, int32_t Fmax, int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_vertex_faces_dev(const int32_t *faces_padded, const int32_t *faces_len, int32_t Vmax, int32_t Fmax,
                                            int32_t B, int32_t *vf_rowptr, int32_t *vf_ent, uint32_t *bad_dev, void *ws,
@@ -840,6 +883,8 @@ FX3D_API fx3d_status fx3d_vertex_faces_dev(const int32_t *faces_padded, const in
 /* _compute_faces_packed (src/rep/mesh.jl:884-896) from the padded device faces: faces_packed (3,sumF), mesh after mesh, each
  * id plus the vertex count of the meshes before it (nverts (B) int32).  sumF: capacity of faces_packed in faces (the sum of
  * faces_len); a mesh that would end behind it is not written.  ws: fx3d_faces_padded_to_packed_dev_workspace_bytes(B). */
+/* Batch axis: fx3d_faces_padded_to_packed_dev_workspace_bytes, fx3d_faces_padded_to_packed_dev: unbounded -- one scanning block
+ * and a grid-stride kernel. */
 FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev_workspace_bytes(int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev(const int32_t *faces_padded, const int32_t *faces_len,
                                                      const int32_t *nverts, int32_t Fmax, int32_t B, int64_t sumF,
@@ -880,6 +925,8 @@ FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev(const int32_t *faces_padded
  * (NULL: not written).  Six launches on `s`, no host synchronisation, no host memory read after the argument check
  * (graph-capturable).  ws: fx3d_pointnet_workspace_bytes(N, B, num_classes), 16-byte aligned. */
 FX3D_API fx3d_status fx3d_pointnet_param_count(int32_t num_classes, int64_t *count);
+/* Batch axis: fx3d_pointnet_workspace_bytes, fx3d_pointnet_forward: B <= 65535 -- the point kernels have the cloud on the grid's y;
+ * refused by the size check, the query included, with a message that names B. */
 FX3D_API fx3d_status fx3d_pointnet_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_classes, const float *x, int32_t N,
                                            int32_t B, float *probs, float *logits, float *stn, float *fstn,
@@ -919,6 +966,8 @@ FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_
  * ws: fx3d_dgcnn_workspace_bytes(N, B, K, num_classes) -- x1, x2, per-tile maxima, the logits and one EdgeConv workspace (the
  * neighbour lists and the search's scratch), the larger of the two stages', which they use in turn. */
 FX3D_API fx3d_status fx3d_dgcnn_param_count(int32_t num_classes, int64_t *count);
+/* Batch axis: fx3d_dgcnn_workspace_bytes, fx3d_dgcnn_forward: B <= 65535 -- the EdgeConv and point kernels have the cloud on the
+ * grid's y; refused by the size check, the query included, with a message that names B. */
 FX3D_API fx3d_status fx3d_dgcnn_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N,
                                         int32_t B, float *probs, float *logits, int32_t *idx1, float *x1, int32_t *idx2,
@@ -952,6 +1001,8 @@ FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_cla
  * than `layers` read, and none after the argument check (graph-capturable).  ws: fx3d_edgeconv_workspace_bytes(layers, nlayers,
  * K, N, B) -- the neighbour lists and the search's scratch. */
 FX3D_API fx3d_status fx3d_edgeconv_param_count(const int32_t *layers, int32_t nlayers, int64_t *count);
+/* Batch axis: fx3d_edgeconv_workspace_bytes, fx3d_edgeconv_forward: B <= 65535 -- the EdgeConv kernel has the cloud on the grid's
+ * y; refused by the size check, the query included, with a message that names B. */
 FX3D_API fx3d_status fx3d_edgeconv_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
                                                    size_t *bytes);
 FX3D_API fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
@@ -989,6 +1040,7 @@ FX3D_API fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_
  * transposed in the workspace, the adjoint kernel), no host synchronisation, no host memory other than `layers` read, and none
  * after the argument check (graph-capturable).  ws: fx3d_edgeconv_bwd_workspace_bytes(layers, nlayers, K, N, B) -- the forward's
  * workspace, the lists, out and the transposed weights. */
+/* Batch axis: fx3d_edgeconv_bwd_workspace_bytes, fx3d_edgeconv_bwd: B <= 65535 -- as fx3d_edgeconv_forward. */
 FX3D_API fx3d_status fx3d_edgeconv_bwd_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
                                                        size_t *bytes);
 FX3D_API fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
@@ -1030,6 +1082,7 @@ FX3D_API fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *l
  * gout, gparams, ws); every refusal comes before any device work.  Launches on `s` only (the search and / or the forward where
  * idx / out are NULL, the weight transpose, the kernel, two finishing kernels), no host synchronisation (graph-capturable).
  * ws: fx3d_edgeconv_grad_workspace_bytes -- the input adjoint's, one partial of param_count floats per chunk and cloud, and the sums. */#define FX3D_EDGECONV_GRAD_CHUNK 128 /* points of one cloud whose rows are summed as one chain ("EdgeConv parameter adjoint") */
+/* Batch axis: fx3d_edgeconv_grad_workspace_bytes, fx3d_edgeconv_grad: B <= 65535 -- as fx3d_edgeconv_forward. */
 FX3D_API fx3d_status fx3d_edgeconv_grad_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
                                                         size_t *bytes);
 FX3D_API fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K, const float *x,
@@ -1081,6 +1134,7 @@ FX3D_API fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *
  * points, channel) the first point that reproduces pooled; n*, a4, a5, d5, d4, d3, dz3; H and h of fc_4 and fc_5; gx2 and gx1; and
  * one scratch region, the largest of fx3d_dgcnn_workspace_bytes and the two stages' fx3d_edgeconv_grad_workspace_bytes, which
  * use it in turn. */
+/* Batch axis: fx3d_dgcnn_grad_workspace_bytes, fx3d_dgcnn_grad: B <= 65535 -- as fx3d_dgcnn_forward. */
 FX3D_API fx3d_status fx3d_dgcnn_grad_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N, int32_t B,
                                      const int32_t *idx1, const float *x1, const int32_t *idx2, const float *x2,
@@ -1142,6 +1196,7 @@ FX3D_API fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classe
  * and the BatchNorm's input there; the head's vectors; the last convolution's input rows at the winners (128,1024,B); one partial
  * per tile and cloud; the feat path's gradient at h; gxt, gT and gF. */
 #define FX3D_POINTNET_GRAD_TILE 64 /* points of one cloud whose rows are summed as one chain ("PointNet adjoint") */
+/* Batch axis: fx3d_pointnet_grad_workspace_bytes, fx3d_pointnet_grad: B <= 65535 -- as fx3d_pointnet_forward. */
 FX3D_API fx3d_status fx3d_pointnet_grad_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_classes, const float *x, int32_t N, int32_t B,
                                         const float *glogits, float *gparams, float *gx, float *gstn, float *gfstn, float *gh,
@@ -1182,6 +1237,7 @@ FX3D_API fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_cla
  * (2,1024,ntiles,B) Float64, and the heads' (512,B) and (256,B) activations. */
 #define FX3D_POINTNET_STAT_GROUPS 32 /* chains the tile sums of a layer are folded in ("PointNet training-mode forward") */
 FX3D_API fx3d_status fx3d_pointnet_stat_count(int64_t *count);
+/* Batch axis: fx3d_pointnet_train_workspace_bytes, fx3d_pointnet_forward_train: B <= 65535 -- as fx3d_pointnet_forward. */
 FX3D_API fx3d_status fx3d_pointnet_train_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_t num_classes, const float *x, int32_t N,
                                                  int32_t B, const float *dropout, float momentum, float *probs, float *logits,
@@ -1229,6 +1285,7 @@ FX3D_API fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_
  * tile sums (2,128,ntiles,B); the last convolution's input and the gradient at it, (128,N,B) each; two (64,N,B) gradients, the feat
  * path's gradient at h; dW and db of the last convolution per cloud, (128,1024,B) and (1024,B); one partial per tile and cloud. */
 #define FX3D_POINTNET_GRAD_TRAIN_CLOUD_CHAINS 1 /* chains per cloud of a last convolution's dW / db ("PointNet training-mode adjoint") */
+/* Batch axis: fx3d_pointnet_grad_train_workspace_bytes, fx3d_pointnet_grad_train: B <= 65535 -- as fx3d_pointnet_forward. */
 FX3D_API fx3d_status fx3d_pointnet_grad_train_workspace_bytes(int32_t N, int32_t B, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t num_classes, const float *x, int32_t N, int32_t B,
                                               const float *dropout, const float *batch_stats, const float *glogits, float *gparams,
@@ -1287,6 +1344,8 @@ FX3D_API fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t n
  * ws: fx3d_edgeconv_train_workspace_bytes / fx3d_dgcnn_train_workspace_bytes -- the forward's workspace, the Float64 tile sums
  * (2,C,ntiles,B) of the widest layer, and for DGCNN the head's (512,B) and (256,B) dense outputs. */
 FX3D_API fx3d_status fx3d_edgeconv_stat_count(const int32_t *layers, int32_t nlayers, int64_t *count);
+/* Batch axis: fx3d_edgeconv_train_workspace_bytes, fx3d_edgeconv_forward_train, fx3d_dgcnn_train_workspace_bytes,
+ * fx3d_dgcnn_forward_train: B <= 65535 -- as fx3d_edgeconv_forward and fx3d_dgcnn_forward. */
 FX3D_API fx3d_status fx3d_edgeconv_train_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
                                                          size_t *bytes);
 FX3D_API fx3d_status fx3d_edgeconv_forward_train(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
@@ -1343,6 +1402,7 @@ FX3D_API fx3d_status fx3d_dgcnn_forward_train(const float *params_dev, int32_t n
  * no host memory other than `layers` read (graph-capturable).
  * ws: fx3d_edgeconv_grad_train_workspace_bytes -- the input adjoint's, one partial of param_count floats per chunk and cloud, the
  * Float64 half-tile sums (2,C,nhalf,B) of the widest layer, and the means. */
+/* Batch axis: fx3d_edgeconv_grad_train_workspace_bytes, fx3d_edgeconv_grad_train: B <= 65535 -- as fx3d_edgeconv_forward. */
 FX3D_API fx3d_status fx3d_edgeconv_grad_train_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N,
                                                               int32_t B, size_t *bytes);
 FX3D_API fx3d_status fx3d_edgeconv_grad_train(const float *params_dev, const int32_t *layers, int32_t nlayers, int32_t K,
@@ -1393,6 +1453,7 @@ FX3D_API fx3d_status fx3d_edgeconv_grad_train(const float *params_dev, const int
  * ws: fx3d_dgcnn_grad_train_workspace_bytes(N, B, K, num_classes) -- the per-tile first matches (1024,ntiles,B) with what conv3.bn
  * was given there; the head's vectors; dW3 and db3 per cloud, (256,1024,B) and (1024,B); gx2 and gx1; one scratch region, the
  * larger of the two stages' fx3d_edgeconv_grad_train workspaces. */
+/* Batch axis: fx3d_dgcnn_grad_train_workspace_bytes, fx3d_dgcnn_grad_train: B <= 65535 -- as fx3d_dgcnn_forward. */
 FX3D_API fx3d_status fx3d_dgcnn_grad_train_workspace_bytes(int32_t N, int32_t B, int32_t K, int32_t num_classes, size_t *bytes);
 FX3D_API fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_classes, int32_t K, const float *x, int32_t N,
                                            int32_t B, const float *dropout4, const float *dropout5, const int32_t *idx1,
@@ -1446,6 +1507,7 @@ FX3D_API fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_
  *   of elements (those and the tail go one by one), one by one otherwise.
  *   Refusals: n < 0, nstat < 0, a NULL g, m, v, betap or x, nstat > 0 without running and stat_map, betap not 8-byte aligned.
  *   n = 0: betap advances and nothing else happens. */
+/* Batch axis: fx3d_crossentropy: unbounded -- one block walks the batch. */
 FX3D_API fx3d_status fx3d_crossentropy(const float *probs, const int32_t *labels, int32_t num_classes, int32_t B, float *glogits,
                                        double *loss, int32_t *counts, fx3d_stream_t s);
 FX3D_API fx3d_status fx3d_dropout_mask(int64_t n, double p, uint64_t seed, const uint64_t *counter_dev, int32_t stream_id, float *out,
