@@ -541,6 +541,31 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
                 off[d] = -flo * inv[d];
                 cfl[d] = flo; cfh[d] = fhi;
             }
+            // The queries' grid frame (qinv, qoff below) is the same on every lane of every wave: it is computed ONCE per block, here
+            // -- the query cloud's key box `qbb` is final behind the cloud pass's second barrier --, by three waves on three SIMDs, a
+            // dimension each, and handed over in the padding of two waves' rows of `red` (rows 8 and 9: written by nobody else, and
+            // beyond what the robust range uses), where every thread picks it up behind the counting phase's barrier.  It stood behind
+            // that barrier on all sixteen waves: three IEEE divisions, some 85 VALU per wave in the phase the VALU bounds, 1 000 cycles
+            // of a block at B = 32, N = M = 4096 (0.38 us of 32.65: DESIGN.md 3.1, "One-wave stretches").  ONE wave with all three
+            // dimensions reached the barrier 400 cycles behind the others and gave half of that back.  Without a sorted query cloud
+            // nothing is computed, stored or read.
+            constexpr int kHFrameWave = 8;
+            float *const qfr = red + 4 * (4 * kHFrameWave + 3);  // (qinv, -); 16 floats on: (qoff, -)
+            if (sorted_q && wv >= kHFrameWave && wv < kHFrameWave + 3) {
+                const int d = wv - kHFrameWave;
+                const float cl = d == 0 ? cfl[0] : d == 1 ? cfl[1] : cfl[2], ch = d == 0 ? cfh[0] : d == 1 ? cfh[1] : cfh[2];
+                // ... the queries' own box, clipped to the candidates' frame grown by its largest extent on every side: queries farther out
+                // than that (a stray far point would squeeze all others into one cell) fall into border cells
+                const float ext = fmaxf(fmaxf(cfh[0] - cfl[0], cfh[1] - cfl[1]), cfh[2] - cfl[2]);
+                // (a query box more than four times the candidates' extent in this dimension -- a far outlier among the queries --: grown by a
+                //  quarter only, so that the bulk, which then sits where the candidates are, is not squeezed into the middle cells)
+                const float ql = fkey_inv(qbb[d]), qh = fkey_inv(qbb[4 + d]);
+                const float grow = qh - ql > 4.0f * ext ? 0.25f * ext : ext;
+                const float lo = fmaxf(ql, cl - grow), hi = fminf(qh, ch + grow);  // (fmaxf / fminf drop a NaN bound)
+                const float qi = hi > lo && hi - lo < INFINITY ? 8.0f / (hi - lo) : 0.0f;  // (no extent, or not finite: one cell in this dimension)
+                const float qo = qi != 0.0f ? -lo * qi : 0.0f;
+                if (lane == 0) { qfr[d] = qi; qfr[16 + d] = qo; }
+            }
             auto cell = [&](float x, float y, float z) -> unsigned int {  // the 8 x 8 x 8 cell of a point (outside the box: a border cell)
                 const unsigned int ux = (unsigned int)(int)fminf(fmaxf(__builtin_fmaf(x, inv[0], off[0]), 0.0f), 7.0f);
                 const unsigned int uy = (unsigned int)(int)fminf(fmaxf(__builtin_fmaf(y, inv[1], off[1]), 0.0f), 7.0f);
@@ -616,20 +641,10 @@ __global__ __launch_bounds__(kHThreads, 4) void nn1_f16_kernel(Nn1Params p) {
             __syncthreads();
             FX3D_PROBE_MARK2(3);
             float qinv[3] = {0.f, 0.f, 0.f}, qoff[3] = {0.f, 0.f, 0.f};
-            if (sorted_q) {
-                // ... clipped to the candidates' frame grown by its largest extent on every side: queries farther out than that (a stray
-                // far point would squeeze all others into one cell) fall into border cells
-                const float ext = fmaxf(fmaxf(cfh[0] - cfl[0], cfh[1] - cfl[1]), cfh[2] - cfl[2]);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    // (a query box more than four times the candidates' extent in this dimension -- a far outlier among the queries --: grown by a
-                    //  quarter only, so that the bulk, which then sits where the candidates are, is not squeezed into the middle cells)
-                    const float ql = fkey_inv(qbb[d]), qh = fkey_inv(qbb[4 + d]);
-                    const float grow = qh - ql > 4.0f * ext ? 0.25f * ext : ext;
-                    const float lo = fmaxf(ql, cfl[d] - grow), hi = fminf(qh, cfh[d] + grow);  // (fmaxf / fminf drop a NaN bound)
-                    qinv[d] = hi > lo && hi - lo < INFINITY ? 8.0f / (hi - lo) : 0.0f;  // (no extent, or not finite: one cell in this dimension)
-                    qoff[d] = qinv[d] != 0.0f ? -lo * qinv[d] : 0.0f;
-                }
+            if (sorted_q) {  // the frame waves' six floats (above): block-uniform, into scalar registers
+                const float4 fi = reinterpret_cast<const float4 *>(qfr)[0], fo = reinterpret_cast<const float4 *>(qfr)[4];
+                qinv[0] = uni(fi.x); qinv[1] = uni(fi.y); qinv[2] = uni(fi.z);
+                qoff[0] = uni(fo.x); qoff[1] = uni(fo.y); qoff[2] = uni(fo.z);
             }
             auto qcell = [&](float x, float y, float z) -> unsigned int {
                 const unsigned int ux = (unsigned int)(int)fminf(fmaxf(__builtin_fmaf(x, qinv[0], qoff[0]), 0.0f), 7.0f);
