@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: Chamfer point-pairs/sec (B x N x M) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            the headline figure, and nothing that it does not need
+  python bench.py --gpus N --steps K --warmup W --full     the same steps, then everything else the full record carries
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one forward chamfer_distance over one batch of synthetic clouds already resident in
@@ -15,7 +16,14 @@ steps -> barrier + device sync -> EXACTLY K timed steps -> device sync + barrier
 
 Rank 0 prints ONE JSON result line on stdout, last: the contract fields (metric, value, unit, n_gpus, steps, warmup, ms_per_step, ...)
 and the headline roofline (bound, achieved, peak, unit, frac, kernel_avg_ms) -- a short line that survives the tail of a log.  Before it,
-the FULL record goes to stderr as one JSON line: the same fields plus
+the FULL record goes to stderr as one JSON line: the same fields plus the objects below.
+
+A plain run (no --full) sets up, runs the protocol above, writes --dump-outputs and prints its two lines.  Its `roofline` takes the
+kernel's duration from the launches it bracketed among the K steps (every 5th; none below 5 steps, the figures are then null) and the
+counters from the committed profiles/pmc_latest.json; `protocol`, `configs`, `reference_harness`, `hbm_bound_kernels`, `cpu_baseline`,
+`modes` and `roofline.traffic_live` are absent.  --full adds, all after the K steps: 60 more bracketed launches when fewer than 50
+were bracketed, the live counter passes, those objects (--no-extras / --no-cpu-baseline leave their parts out again), and with
+several ranks or --force-dist the other placements of the collective.
   roofline             -- bound "mfma": `achieved` = the ALGORITHMIC f16 flops of one launch (SURVEY.md 8(d) MFMA clause: every
                           ordered pair at the K = 16 of the fp16-split filter, 2 * 2BNM * 16 = 34.36 GFLOP) / the dominant
                           kernel's average duration in THIS run (HIP events on its stream), `peak` 2500 TF dense f16,
@@ -33,8 +41,8 @@ the FULL record goes to stderr as one JSON line: the same fields plus
                           N=1024 shard, C2's shape on surface samples of real meshes), each with its own SURVEY 8(d)
                           roofline; reference_harness: benchmarks/metrics.jl's full sweep n = 2^6 .. 2^14 (chamfer,
                           edge_loss, laplacian_loss; forward and forward+backward)
-  cpu_baseline         -- the oracle's KD-tree twin of the reference CPU path, timed on this host (N=1 only)
-Everything beyond the timed K steps runs after them (N=1, rank 0) and does not enter `value`.
+  cpu_baseline         -- the oracle's KD-tree twin of the reference CPU path, timed on the host (N=1 only)
+Everything beyond the timed K steps runs after them (N=1, rank 0), under --full only, and does not enter `value`.
 
 --dump-outputs DIR: rank 0 writes what the timed path returned in its last step -- the Float32 loss of chamfer_distance(A, B), the
 global loss with N GPUs, read back right after the K steps (`--launcher inproc`: one more evaluation of the same step) -- as
@@ -50,7 +58,7 @@ EVALUATION (north_star: "RCCL all-reduce of the scalar loss"), either on a secon
 overlaps the next evaluation's kernel (`overlap`) or on the compute stream (`serial`); the default `auto` times 40 steps
 of each before the protocol starts and runs the faster one on this node (the overlapped form needs more host work per
 step and loses on a host with few free cores; world size 1: serial 50.6 vs overlap 57.6 us).  The other placements and
-`deferred` (one collective per 32 evaluations) are timed right after the K steps and printed as `modes`.
+`deferred` (one collective per 32 evaluations) are timed right after the K steps and printed as `modes` (--full).
 """
 import argparse
 import hashlib
@@ -292,11 +300,11 @@ def run_inproc(args, why, value_1=None):
         md.enqueue(xs, ys, Bg)
     md.synchronize()
     t1 = time.perf_counter()
+    avg, mn, mx, cnt = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)   # (read before the switch-off, which drops the records)
+    _lib.call("fx3d_profile_kernel_stats", b"nn1", C.byref(avg), C.byref(mn), C.byref(mx), C.byref(cnt))
     _lib.call("fx3d_profile_enable", 0)
     if args.dump_outputs:   # the timed steps leave the loss on the devices without a read-back: one more evaluation of the same step
         dump_outputs(args.dump_outputs, md.chamfer_distance(xs, ys, Bg))
-    avg, mn, mx, cnt = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
-    _lib.call("fx3d_profile_kernel_stats", b"nn1", C.byref(avg), C.byref(mn), C.byref(mx), C.byref(cnt))
     elapsed = t1 - t0
     value = Bg * NPTS * MPTS * args.steps / elapsed
     kern_s = avg.value * 1e-3 if cnt.value else None
@@ -329,8 +337,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the protocol / configs measurements after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything else the full record carries: the kernel average over >= 50 "
+                         "launches for short runs, live HBM counters, the protocol / configs / reference-harness / HBM-bound "
+                         "figures, the CPU baseline, and with several ranks the other placements of the collective (`modes`).  "
+                         "Off by default: a plain run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the live counters and the protocol / configs measurements after the timed steps")
     ap.add_argument("--burn-ms", type=float, default=80.0,
                     help="milliseconds of the same launches before the counted warm-up (steady clocks); 0 = none")
     ap.add_argument("--comm", choices=["torch", "native"], default="native",
@@ -523,6 +537,12 @@ def main():
             return float(t.item())
         return v
 
+    def nn1_kernel_stats():
+        """(average, minimum, maximum in ms, count) of the nn1 launches bracketed by HIP events since profiling was last switched."""
+        avg, mn, mx, cnt = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
+        _lib.call("fx3d_profile_kernel_stats", b"nn1", C.byref(avg), C.byref(mn), C.byref(mx), C.byref(cnt))
+        return avg, mn, mx, cnt
+
     def run_timed(runner, steps, warmup, profile_every=0):
         step, sync_all, read_loss, s, desc = runner
         for _ in range(warmup):
@@ -541,10 +561,11 @@ def main():
         sync_all()
         barrier()
         t1 = time.perf_counter()
+        kstats = nn1_kernel_stats()   # before the switch-off below, which drops the bracketed launches' records
         _lib.call("fx3d_profile_enable", 0)
         elapsed = max_over_ranks(t1 - t0)
         return {"elapsed": elapsed, "t_local": t1 - t0, "loss": read_loss(), "event_ms": e0.elapsed_ms(e1), "desc": desc,
-                "runner": (step, sync_all, s)}
+                "runner": (step, sync_all, s), "kernel_stats": kstats}
 
     def timed(mode, steps, warmup, profile_every=0, burn_ms=0.0, cold=False):
         runner = make_runner(mode)
@@ -571,21 +592,20 @@ def main():
         main_mode = min(calibration, key=calibration.get)   # (max-over-ranks times: every rank picks the same one)
     res = timed(main_mode, args.steps, args.warmup, 0 if os.environ.get("FX3D_BENCH_NOPROFILE") else 5,
                 burn_ms=args.burn_ms, cold=True)
-    avg, mn, mx, cnt = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
-    _lib.call("fx3d_profile_kernel_stats", b"nn1", C.byref(avg), C.byref(mn), C.byref(mx), C.byref(cnt))
-    _lib.call("fx3d_profile_enable", 0)
+    avg, mn, mx, cnt = res["kernel_stats"]
     step, sync_all, bench_stream = res["runner"]
-    if cnt.value < 50 and not os.environ.get("FX3D_BENCH_NOPROFILE"):
-        # short runs (--steps 20): the kernel average still comes from >= 50 launches, timed outside the K steps
+    if args.full and cnt.value < 50 and not os.environ.get("FX3D_BENCH_NOPROFILE"):
+        # short runs (--steps 20): the kernel average comes from >= 50 launches, timed outside the K steps (a plain run keeps
+        # the average of the launches it bracketed among the K steps; none below 5 steps, and the roofline figures are null)
         _lib.call("fx3d_profile_enable", 1)
         for _ in range(60):
             step()
         sync_all()
-        _lib.call("fx3d_profile_kernel_stats", b"nn1", C.byref(avg), C.byref(mn), C.byref(mx), C.byref(cnt))
+        avg, mn, mx, cnt = nn1_kernel_stats()
         _lib.call("fx3d_profile_enable", 0)
 
     modes = None
-    if use_dist:  # the other ways of placing the collective, same steps, right after (every rank takes part)
+    if use_dist and args.full:  # the other ways of placing the collective, same steps, right after (every rank takes part)
         modes = {main_mode: {"ms_per_step": res["elapsed"] * 1e3 / args.steps, "collective": res["desc"]}}
         if world == 1:  # --force-dist on one device: the plain single-launch loss of the same data is the reference every mode must equal
             plain = timed("single_plain", 2, 1)
@@ -661,7 +681,7 @@ def main():
         "hbm_frac": (abytes / kern_s / 1e9 / HBM_PEAK_GBS) if kern_s else None,
         "algorithmic_f16_flops_per_launch": hw_flops,
         "algorithmic_flops_per_launch": flops, "algorithmic_bytes_per_launch": abytes,
-        "kernel": "nn1_f16_kernel<false, false, true> (spatial pruning)", "kernel_avg_ms": avg.value, "kernel_min_ms": mn.value, "launches_timed": cnt.value,
+        "kernel": "nn1_f16_kernel<false, false, true> (spatial pruning)", "kernel_avg_ms": avg.value if cnt.value else None, "kernel_min_ms": mn.value if cnt.value else None, "launches_timed": cnt.value,
         "main_loop_issue_bound": ub,
         "note": "bound = the f16 matrix pipe.  achieved = the ALGORITHMIC f16 flops of the launch (SURVEY.md 8(d), MFMA clause: "
                 "2*(2*B*N*M)*K with K = 16, i.e. one v_mfma_f32_32x32x16_f16 per 32 x 32 pairs and direction) / the kernel's average "
@@ -706,7 +726,7 @@ def main():
         pmc_note = f"profiles/pmc_latest.json unusable: {e}"
     if pmc_note:
         roof["counters_note"] = pmc_note
-    if world == 1 and not use_dist and not args.no_extras and not os.environ.get("FX3D_BENCH_NO_LIVE_PMC"):
+    if args.full and world == 1 and not use_dist and not args.no_extras and not os.environ.get("FX3D_BENCH_NO_LIVE_PMC"):
         live = live_pmc_traffic()   # (round 5) the HBM traffic of one launch measured IN THIS RUN, not read from a committed file
         if live.get("bytes_per_launch"):
             roof["traffic_committed_profile"] = roof.get("traffic")
@@ -727,6 +747,7 @@ def main():
         "cold_ms_per_step": res.get("cold_ms_per_step"), "burn_in_steps": res.get("burn_steps"),
         "stream_event_ms_per_step": res["event_ms"] / args.steps,
     }
+    out["full"] = bool(args.full)
     out["launcher"] = "procs (one process per GPU)" if use_dist else "single process, one GPU"
     if value_1 is not None:
         out["value_1gpu_same_run"] = value_1
@@ -735,12 +756,14 @@ def main():
         out["comm"] = comm_info
     if modes is not None:
         out["modes"] = modes
-    if world == 1 and not use_dist and not args.no_extras:
+    elif calibration is not None:   # a plain run: what `auto` measured before the protocol, without the other placements
+        out["auto_calibration_ms_per_step"] = calibration
+    if args.full and world == 1 and not use_dist and not args.no_extras:
         out["protocol"] = protocol_numbers(fx, x, y)
         out["configs"] = config_one_liners(fx)
         out["reference_harness"] = reference_harness(fx)
         out["hbm_bound_kernels"] = hbm_bound_kernels()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(fx)
     emit(out)
     if dist is not None:

@@ -1092,14 +1092,15 @@ def test_bench_line_force_dist_equals_plain_and_roofline_is_a_fraction(gpu_fx, t
     """(a) the bench line's `roofline.frac` is the fraction of the bound it names (f16 MFMA pipe, peak 2500 TF;
     no field called *frac above 1; the algorithmic-fp32 figure only as a named extra); (b) `--gpus 1 --force-dist` (RCCL
     communicator + collectives at world size 1) reports the same loss, n_gpus and workload as the plain line; (c) `--gpus 2`
-    on this one-GPU box ends non-zero without printing a line.  The short result line (last on stdout) repeats the full
+    on this one-GPU box ends non-zero without printing a line.  Both lines are --full runs (the kernel average over >= 50 launches
+    and `modes` are measured after the timed steps; test_bench_plain_run_is_lean has the run without it).  The short result line (last on stdout) repeats the full
     record's (stderr) contract fields; --dump-outputs writes the loss of the last timed step."""
     import json
     import subprocess
     import sys
     bench = os.path.join(ROOT, "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    common = ["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extras", "--burn-ms", "20"]
+    common = ["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras", "--burn-ms", "20"]
 
     def line(extra):
         r = subprocess.run([sys.executable, bench, "--gpus", "1"] + common + extra, env=env, capture_output=True, text=True, timeout=600)
@@ -1141,6 +1142,42 @@ def test_bench_line_force_dist_equals_plain_and_roofline_is_a_fraction(gpu_fx, t
     if gpu_fx.device_count() < 2:
         r = subprocess.run([sys.executable, bench, "--gpus", "2"] + common, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode != 0 and "n_gpus" not in r.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean(gpu_fx, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the same result line and --dump-outputs as with it, and nothing
+    measured beyond the protocol -- no CPU baseline, no other configs, no live counter passes, no launches after the K steps
+    (the kernel average comes from those of the 20 steps that were bracketed).  The whole process, start to exit, stays inside the
+    30 s a plain run may spend outside its steps (the 25 steps themselves are about a millisecond)."""
+    import json
+    import subprocess
+    import sys
+    import time
+    bench = os.path.join(ROOT, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    short = json.loads(r.stdout.splitlines()[-1])
+    full = json.loads([ln for ln in r.stderr.splitlines() if ln.startswith("{")][-1])
+    print(f"plain bench run: {wall:.2f} s start to exit, {short['ms_per_step']:.5f} ms per step")
+    assert full["full"] is False
+    for k in ("protocol", "configs", "reference_harness", "hbm_bound_kernels", "cpu_baseline", "modes"):
+        assert k not in full, k
+    assert "traffic_live" not in full["roofline"] and 1 <= full["roofline"]["launches_timed"] <= 20
+    assert short["metric"] == "chamfer_point_pairs_per_sec" and short["unit"] == "pairs/s" and short["higher_is_better"] is True
+    assert short["dtype"] == "f32" and short["n_gpus"] == 1 and short["steps"] == 20 and short["warmup"] == 5
+    assert short["ms_per_step"] > 0 and abs(short["value"] - 32 * 4096 * 4096 / (short["ms_per_step"] * 1e-3)) <= 1e-9 * short["value"]
+    roof = short["roofline"]
+    assert roof["bound"] == "mfma" and 0.05 < roof["frac"] <= 1.0 and abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-12
+    fx = gpu_fx
+    here = fx.chamfer_distance(fx.gpu(fx.synth.uniform_cloud(fx.synth.SEED_A, 3, 4096, 32)), fx.gpu(fx.synth.uniform_cloud(fx.synth.SEED_B, 3, 4096, 32)))
+    dumped = np.load(tmp_path / "loss.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (1,) and dumped[0] == np.float32(short["loss"]) == np.float32(here)
+    assert wall < 30.0, wall
 
 
 @pytest.mark.parametrize("N,M,B,D", [(1000, 500, 2, 3), (64, 64, 1, 3), (4096, 4096, 4, 3), (9000, 12000, 1, 3), (300, 200, 3, 2), (50, 70, 2, 5)])

@@ -435,6 +435,25 @@ def test_bench_refuses_more_gpus_than_visible():
     assert r.returncode == 0 and r.stdout.strip() == "", (r.returncode, r.stdout, r.stderr)
 
 
+def test_bench_full_is_an_option():
+    """bench.py's measurements beyond the timed steps sit behind --full: the option is documented and parses, with and without the
+    two switches that trim it, and a misspelt option still ends the run before anything is printed.  (What a run without it leaves
+    out is checked on the device: test_gpu_hardening.py::test_bench_plain_run_is_lean.)"""
+    import subprocess
+    import sys
+    bench = os.path.join(ROOT, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, bench, "--help"], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    # --gpus 0 is refused after the command line has parsed: the status and the message tell a parse error (2, "usage:") from it
+    for extra in ([], ["--full"], ["--full", "--no-extras", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, bench, "--gpus", "0", "--steps", "1", "--warmup", "0"] + extra, env=env,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 1 and "need >= 1" in r.stderr and "usage:" not in r.stderr and r.stdout == "", (extra, r.returncode, r.stderr)
+    r = subprocess.run([sys.executable, bench, "--gpus", "0", "--fulll"], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "usage:" in r.stderr and r.stdout == "", (r.returncode, r.stderr)
+
+
 def test_vertex_face_table_and_the_oracles_sampling_adjoint(fx, oracle):
     """fx3d_build_vertex_faces (host C++): a CSR over the vertices of every mesh of a padded batch whose entries face * 4 + corner
     ascend -- against numpy; and the oracle's ordered sampling adjoint (the order the device reproduces) against a float64

@@ -48,7 +48,7 @@ rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_hbm_fetch" -o r -- python "$ROOT/tools/h
 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_hbm_write" -o r -- python "$ROOT/tools/hbm_roofline.py" --reps 5 > /dev/null 2>&1
 python "$ROOT/tools/rocprof_summary.py" pmc "$OUT"/pmc_hbm_*/r_results.db > "$OUT/pmc_hbm.txt" 2>&1
 cp "$OUT/pmc_nn1.txt" "$OUT/pmc.txt"
-python "$ROOT/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python "$ROOT/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 python "$ROOT/tools/bench_ops.py" --cpu > "$OUT/bench_ops.jsonl" 2> "$OUT/bench_ops.err"
 rm -rf "$OUT"/kt/*.db "$OUT"/kt_ops/*.db "$OUT"/kt_hbm/*.db "$OUT"/pmc_*/*.db 2>/dev/null
 ls -la "$OUT"
