@@ -752,7 +752,7 @@ fx3d_status chamfer_sampled_bwd_impl(const char *fn, const float *x, int32_t N, 
     }
     if (!accumulate)
         for (int k = 0; k < 2; ++k)
-            if (side[k]->gverts) FX3D_HIP(hipMemsetAsync(side[k]->gverts, 0, sizeof(float) * 3 * (size_t)side[k]->Vmax * B, st));
+            if (side[k]->gverts) FX3D_FILL(side[k]->gverts, 0, sizeof(float) * 3 * (size_t)side[k]->Vmax * B, st);
     // sides beyond kBgChunk samples (the reference's default is 5000): the accumulators between the rounds live in LDS
     const int maxr = N > M ? N : M;
     const size_t dyn = maxr > kBgChunk ? sizeof(P3) * (size_t)((maxr + nsplit - 1) / nsplit) : 0;

@@ -73,6 +73,15 @@ unsigned int *ticket_slot(fx3d_status *rc, hipStream_t st);
 constexpr int kTicketGroups = 16;
 constexpr int kTicketStride = 16 * (kTicketGroups + 1);
 fx3d_status ensure_dynamic_lds(const void *kernel, int bytes, const char *name);
+// dst[0 .. bytes) = byte, on `st`, by a kernel of the library's own (runtime.hip): what every launching entry point clears with.
+// Not hipMemsetAsync: recorded by a stream capture that becomes a memset NODE, and the nodes of a replayed graph were seen to
+// write another value than the recorded one; a kernel node carries its value in its arguments.
+fx3d_status fill_bytes(void *dst, int byte, size_t bytes, hipStream_t st);
+#define FX3D_FILL(dst, byte, bytes, st)                                                     \
+    do {                                                                                    \
+        const fx3d_status frc__ = fx3d::fill_bytes((dst), (byte), (bytes), (st));           \
+        if (frc__) return frc__;                                                            \
+    } while (0)
 // chamfer_host.hip's argument check and forward driver (the two sums and / or the loss with batch size Bg, optional indices), for
 // chamfer_bwd.hip and chamfer_pairwise.hip
 fx3d_status chamfer_check_shapes(const char *fn, const void *x, int N, const void *y, int M, int B, int D);

@@ -102,7 +102,7 @@ fx3d_status fx3d_packed_to_padded(const float *packed, const int64_t *verts_len_
                                   float *padded, fx3d_stream_t s) {
     FX3D_REQUIRE(packed && verts_len_host && padded && B > 0 && Vmax > 0, "fx3d_packed_to_padded: bad argument");
     hipStream_t st = as_stream(s);
-    FX3D_HIP(hipMemsetAsync(padded, 0, sizeof(float) * 3 * (size_t)Vmax * B, st));  // pad value 0
+    FX3D_FILL(padded, 0, sizeof(float) * 3 * (size_t)Vmax * B, st);  // pad value 0
     size_t cur = 0;
     for (int b = 0; b < B; ++b) {
         const size_t n = (size_t)verts_len_host[b];

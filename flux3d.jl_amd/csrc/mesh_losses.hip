@@ -375,7 +375,7 @@ fx3d_status fx3d_edge_loss_bwd(const float *verts, int64_t V, const int32_t *edg
     FX3D_REQUIRE(verts && edges && gverts, "fx3d_edge_loss_bwd: null pointer");
     FX3D_REQUIRE(V > 0 && E > 0, "fx3d_edge_loss_bwd: bad sizes");
     hipStream_t st = as_stream(s);
-    if (!accumulate) FX3D_HIP(hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)V, st));
+    if (!accumulate) FX3D_FILL(gverts, 0, sizeof(float) * 3 * (size_t)V, st);
     hipLaunchKernelGGL(edge_loss_bwd_kernel, dim3(mesh_grid_for(E)), dim3(kThreads), 0, st, verts, edges,
                        edges + E, (long long)E, target, gout / (float)E, gverts);
     FX3D_LAUNCH_CHECK();
@@ -454,7 +454,7 @@ fx3d_status fx3d_mesh_losses_bwd(const float *verts, int64_t V, const int32_t *r
     hipStream_t st = as_stream(s);
     float4 *u = MeshLossWs(ws).u;
     if (g_lap == 0.0f && g_edge == 0.0f) {  // both terms dropped: the gradient is exactly zero; never read the (possibly unbuilt) unit rows
-        if (!accumulate) FX3D_HIP(hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)V, st));
+        if (!accumulate) FX3D_FILL(gverts, 0, sizeof(float) * 3 * (size_t)V, st);
         return FX3D_OK;
     }
     if (!reuse_forward && g_lap != 0.0f) {  // no fx3d_mesh_losses on the same vertices and workspace before this call: build the unit rows
@@ -491,7 +491,7 @@ fx3d_status fx3d_laplacian_loss_bwd(const float *verts, int64_t V, const int32_t
     FX3D_REQUIRE(verts && rowptr && colind && vals && gverts, "fx3d_laplacian_loss_bwd: null pointer");
     FX3D_REQUIRE(V > 0, "fx3d_laplacian_loss_bwd: bad V");
     hipStream_t st = as_stream(s);
-    if (!accumulate) FX3D_HIP(hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)V, st));
+    if (!accumulate) FX3D_FILL(gverts, 0, sizeof(float) * 3 * (size_t)V, st);
     hipLaunchKernelGGL(laplacian_loss_bwd_kernel, dim3(mesh_grid_for(V)), dim3(kThreads), 0, st, verts,
                        (long long)V, rowptr, colind, vals, gout / (float)V, gverts);
     FX3D_LAUNCH_CHECK();

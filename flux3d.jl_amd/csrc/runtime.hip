@@ -278,8 +278,7 @@ fx3d_status fx3d_memcpy_d2d(void *dst, const void *src, size_t bytes, fx3d_strea
 fx3d_status fx3d_memset(void *dst, int32_t byte, size_t bytes, fx3d_stream_t s) {
     if (bytes == 0) return FX3D_OK;
     FX3D_REQUIRE(dst, "fx3d_memset: null pointer");
-    FX3D_HIP(hipMemsetAsync(dst, byte, bytes, as_stream(s)));
-    return FX3D_OK;
+    return fill_bytes(dst, byte, bytes, as_stream(s));
 }
 
 fx3d_status fx3d_stream_create(fx3d_stream_t *s) {
@@ -308,29 +307,43 @@ fx3d_status fx3d_graph_begin_capture(fx3d_stream_t s) {
     return FX3D_OK;
 }
 
+// A recorded graph (fx3d_graph_t): the executable and the graph it was instantiated from.  The graph lives exactly as long as the
+// executable; fx3d_graph_destroy frees both.
+namespace {
+struct RecordedGraph {
+    hipGraphExec_t exec;
+    hipGraph_t graph;
+};
+}  // namespace
+
 fx3d_status fx3d_graph_end_capture(fx3d_stream_t s, fx3d_graph_t *g) {
     FX3D_REQUIRE(s && g, "fx3d_graph_end_capture: bad argument");
     hipGraph_t graph = nullptr;
     FX3D_HIP(hipStreamEndCapture(as_stream(s), &graph));
     hipGraphExec_t exec = nullptr;
     const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
     if (e != hipSuccess) {
+        (void)hipGraphDestroy(graph);
         set_error("fx3d_graph_end_capture: hipGraphInstantiate failed: %s", hipGetErrorString(e));
         return FX3D_ERR_HIP;
     }
-    *g = exec;
+    *g = new RecordedGraph{exec, graph};
     return FX3D_OK;
 }
 
 fx3d_status fx3d_graph_launch(fx3d_graph_t g, fx3d_stream_t s) {
     FX3D_REQUIRE(g, "fx3d_graph_launch: null graph");
-    FX3D_HIP(hipGraphLaunch(reinterpret_cast<hipGraphExec_t>(g), as_stream(s)));
+    FX3D_HIP(hipGraphLaunch(static_cast<RecordedGraph *>(g)->exec, as_stream(s)));
     return FX3D_OK;
 }
 
 fx3d_status fx3d_graph_destroy(fx3d_graph_t g) {
-    if (g) FX3D_HIP(hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(g)));
+    if (!g) return FX3D_OK;
+    RecordedGraph *const r = static_cast<RecordedGraph *>(g);
+    const hipError_t e = hipGraphExecDestroy(r->exec);
+    (void)hipGraphDestroy(r->graph);
+    delete r;
+    FX3D_HIP(e);
     return FX3D_OK;
 }
 
@@ -397,6 +410,35 @@ fx3d_status fx3d_event_elapsed_ms(fx3d_event_t a, fx3d_event_t b, float *ms) {
 }  // extern "C"
 
 namespace fx3d {
+namespace {
+// dst[0 .. head) and dst[head + 16 mid .. head + 16 mid + tail) byte by byte (block 0; head, tail < 16), the 16-byte aligned
+// middle as `mid` uint4 stores, grid-stride.  Every address lies in [dst, dst + head + 16 mid + tail).
+__global__ __launch_bounds__(256) void fill_bytes_kernel(unsigned char *dst, unsigned int head, unsigned long long mid, unsigned int tail,
+                                                        unsigned int word) {
+    uint4 *const m = reinterpret_cast<uint4 *>(dst + head);
+    const uint4 v = make_uint4(word, word, word, word);
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < mid; i += (unsigned long long)gridDim.x * 256) m[i] = v;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < head) dst[threadIdx.x] = (unsigned char)word;
+        if (threadIdx.x < tail) dst[head + 16 * mid + threadIdx.x] = (unsigned char)word;
+    }
+}
+}  // namespace
+
+fx3d_status fill_bytes(void *dst, int byte, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return FX3D_OK;
+    const size_t to_line = (16 - reinterpret_cast<uintptr_t>(dst) % 16) % 16;
+    const unsigned int head = (unsigned int)(to_line < bytes ? to_line : bytes);
+    const unsigned long long mid = (bytes - head) / 16;
+    const unsigned int tail = (unsigned int)(bytes - head - 16 * mid);
+    const unsigned long long blocks = (mid + 255) / 256;
+    const unsigned int grid = blocks < 1 ? 1u : (blocks > 4096 ? 4096u : (unsigned int)blocks);
+    hipLaunchKernelGGL(fill_bytes_kernel, dim3(grid), dim3(256), 0, st, static_cast<unsigned char *>(dst), head, mid, tail,
+                       0x01010101u * (unsigned int)(byte & 0xFF));
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
+
 fx3d_status ensure_dynamic_lds(const void *kernel, int bytes, const char *name) {
     static std::mutex mu;
     static std::set<std::pair<const void *, int>> done;

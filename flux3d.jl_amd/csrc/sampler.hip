@@ -798,7 +798,7 @@ fx3d_status fx3d_sample_points_bwd(const int32_t *faces_padded, int32_t Vmax, in
     if (vf_rowptr && sg::sg_fits(Fmax, n))  // ordered: bit-reproducible, no memset, no float atomics
         return sg::launch_sample_bwd_gather(faces_padded, Vmax, Fmax, B, n, face_idx, r1, r2, gout, vf_rowptr, vf_ent, gverts, accumulate,
                                             sg::SgStep{}, st);
-    if (!accumulate) FX3D_HIP(hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)Vmax * B, st));
+    if (!accumulate) FX3D_FILL(gverts, 0, sizeof(float) * 3 * (size_t)Vmax * B, st);
     hipLaunchKernelGGL(sample_bwd_kernel, dim3(sample_grid_for((long long)B * n)), dim3(kThreads), 0, st,
                        faces_padded, Vmax, Fmax, B, n, face_idx, r1, r2, gout, gverts);
     FX3D_LAUNCH_CHECK();

@@ -508,7 +508,7 @@ fx3d_status fx3d_edges_dev_count(const int32_t *faces_packed, int64_t F, int64_t
     char *w = static_cast<char *>(ws);
     auto *a = reinterpret_cast<u64 *>(w + l.a), *b = reinterpret_cast<u64 *>(w + l.b);
     auto *flag = reinterpret_cast<uint32_t *>(w + l.flag);
-    FX3D_HIP(hipMemsetAsync(bad_dev, 0, sizeof(uint32_t), st));
+    FX3D_FILL(bad_dev, 0, sizeof(uint32_t), st);
     ProfileScope prof("edges_dev_count", st);
     hipLaunchKernelGGL(td_edge_keys_kernel, dim3(grid_for(F)), dim3(kThreads), 0, st, faces_packed, (long long)F, (long long)V, a, bad_dev);
     const int vb = bits_for((u64)V - 1);
@@ -562,7 +562,7 @@ fx3d_status fx3d_laplacian_dev_csr(const int32_t *edges, int64_t E, int64_t V, i
     char *w = static_cast<char *>(ws);
     auto *a = reinterpret_cast<u64 *>(w + l.s.a), *b = reinterpret_cast<u64 *>(w + l.s.b);
     auto *flag = reinterpret_cast<uint32_t *>(w + l.s.flag), *raw = reinterpret_cast<uint32_t *>(w + l.raw);
-    if (bad_dev) FX3D_HIP(hipMemsetAsync(bad_dev, 0, sizeof(uint32_t), st));
+    if (bad_dev) FX3D_FILL(bad_dev, 0, sizeof(uint32_t), st);
     ProfileScope prof("laplacian_dev_csr", st);
     hipLaunchKernelGGL(td_lap_keys_kernel, dim3(grid_for(E + V)), dim3(kThreads), 0, st, edges, (long long)E, (long long)V, a, bad_dev);
     const int vb = bits_for((u64)V - 1);
@@ -596,7 +596,7 @@ fx3d_status fx3d_vertex_faces_dev(const int32_t *faces_padded, const int32_t *fa
     char *w = static_cast<char *>(ws);
     auto *a = reinterpret_cast<u64 *>(w + l.s.a), *b = reinterpret_cast<u64 *>(w + l.s.b);
     auto *mstart = reinterpret_cast<uint32_t *>(w + l.mstart);
-    if (bad_dev) FX3D_HIP(hipMemsetAsync(bad_dev, 0, sizeof(uint32_t), st));
+    if (bad_dev) FX3D_FILL(bad_dev, 0, sizeof(uint32_t), st);
     ProfileScope prof("vertex_faces_dev", st);
     hipLaunchKernelGGL(td_vf_keys_kernel, dim3(grid_for((long long)Fmax * B)), dim3(kThreads), 0, st, faces_padded, faces_len, Vmax, Fmax, B, a, bad_dev);
     const u64 *sorted = radix_sort(a, b, n, 0, bits_for((u64)Vmax * (u64)B), reinterpret_cast<uint32_t *>(w + l.s.hist),

@@ -33,7 +33,7 @@
 //             at every level, and emits a node's three midpoints only when its remaining path digits are all zero (each
 //             node exactly once).  The bound is an estimate: a path node that tests "dropped" ends the slot, and a slot
 //             node that still tests "kept" explores its subtree depth first -- no work is ever dropped.
-// Every write is a plain store of 1.0f into a grid zeroed by hipMemsetAsync: no atomics, no float sums, deterministic.
+// Every write is a plain store of 1.0f into a grid zeroed by fill_bytes: no atomics, no float sums, deterministic.
 #include "fx3d_common.h"
 #include "scan_common.h"
 
@@ -318,7 +318,7 @@ fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vmax, const
     const int nch = chunks(Fmax);
     const double r = 1.0 / (double)res;
     const double thr = r * r;  // smallest_side = (1.0 / resolution)^2 (:153)
-    FX3D_HIP(hipMemsetAsync(voxels, 0, sizeof(float) * (size_t)res * res * res * B, st));
+    FX3D_FILL(voxels, 0, sizeof(float) * (size_t)res * res * res * B, st);
     ProfileScope prof("trimesh_to_voxel", st);
     hipLaunchKernelGGL(tv_range_kernel, dim3(B), dim3(kPlanThreads), 0, st, verts_padded, Vmax, verts_len, info, bad_dev);
     if (nch > 0)

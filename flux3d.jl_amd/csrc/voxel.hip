@@ -95,7 +95,7 @@ fx3d_status fx3d_pointcloud_to_voxel(const float *points, int32_t N, int32_t B, 
     FX3D_REQUIRE(ws_bytes >= sizeof(float) * 2 * (size_t)B, "fx3d_pointcloud_to_voxel: workspace too small");
     hipStream_t st = as_stream(s);
     float *range = static_cast<float *>(ws);
-    FX3D_HIP(hipMemsetAsync(voxels, 0, sizeof(float) * (size_t)res * res * res * B, st));
+    FX3D_FILL(voxels, 0, sizeof(float) * (size_t)res * res * res * B, st);
     ProfileScope prof("pointcloud_to_voxel", st);
     hipLaunchKernelGGL(cloud_range_kernel, dim3(B), dim3(kVoxThreads), 0, st, points, N, range);
     hipLaunchKernelGGL(voxel_scatter_kernel, dim3((N + kVoxThreads - 1) / kVoxThreads, B), dim3(kVoxThreads), 0, st,

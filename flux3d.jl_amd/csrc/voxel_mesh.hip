@@ -289,8 +289,8 @@ fx3d_status fx3d_voxel_mesh_count(const float *voxels, int32_t res, int32_t B, f
     auto *cnt = reinterpret_cast<int32_t *>(w + l.cnt);
     auto *start = reinterpret_cast<long long *>(w + l.start);
     auto *gmax = reinterpret_cast<int32_t *>(w + l.gmax);
-    FX3D_HIP(hipMemsetAsync(bad_dev, 0, sizeof(uint32_t) * (size_t)B, st));
-    FX3D_HIP(hipMemsetAsync(gmax, 0, sizeof(int32_t) * (size_t)B, st));
+    FX3D_FILL(bad_dev, 0, sizeof(uint32_t) * (size_t)B, st);
+    FX3D_FILL(gmax, 0, sizeof(int32_t) * (size_t)B, st);
     const long long words = d.wpg * B;
     const long long want = (words + kBinUnroll * (kThreads / kWave) - 1) / (kBinUnroll * (kThreads / kWave));
     const int bin_blocks = (int)(want < 8ll * device_cus() ? want : 8ll * device_cus());

@@ -109,6 +109,17 @@ FX3D_API fx3d_status fx3d_device_identity(int32_t dev, char *pci_bus_id, size_t 
 FX3D_API fx3d_status fx3d_device_sync(void);
 FX3D_API fx3d_status fx3d_malloc(void **dev_ptr, size_t bytes);
 FX3D_API fx3d_status fx3d_free(void *dev_ptr);
+/* Capture and replay.  Every entry point that takes a stream carries a Capture note: `replayed` -- it may be recorded by
+ * fx3d_graph_begin_capture / _end_capture on a created stream and replayed, after one eager call of the same sequence (the library
+ * sets its arrival counters and per-kernel attributes up on eager calls); a recorded call has its addresses and host arguments
+ * frozen, finds in its workspace what the last replay left, and a host pointer it takes (loss_host) must be NULL; or the reason it
+ * cannot be recorded: `copies to the host` (it synchronises), `host code` (it enqueues no work of its own: stream and graph
+ * management), `collective` (RCCL; not attempted).  tests/test_gpu_replay.py holds every `replayed` one to its reference as a
+ * replayed graph.
+ * Capture: fx3d_memcpy_h2d, fx3d_memcpy_d2h: copies to the host -- pageable host memory, the call waits for the copy.
+ * fx3d_memcpy_d2d, fx3d_memset, fx3d_counter_add: replayed.  fx3d_stream_destroy, fx3d_stream_sync, fx3d_graph_begin_capture,
+ * fx3d_graph_end_capture, fx3d_graph_launch, fx3d_event_record, fx3d_stream_wait_event: host code -- the capture's own machinery
+ * (record and wait are the fork and join of a capture over two streams). */
 FX3D_API fx3d_status fx3d_memcpy_h2d(void *dst_dev, const void *src_host, size_t bytes, fx3d_stream_t s);
 FX3D_API fx3d_status fx3d_memcpy_d2h(void *dst_host, const void *src_dev, size_t bytes, fx3d_stream_t s);
 FX3D_API fx3d_status fx3d_memcpy_d2d(void *dst_dev, const void *src_dev, size_t bytes, fx3d_stream_t s);
@@ -120,7 +131,7 @@ FX3D_API fx3d_status fx3d_stream_sync(fx3d_stream_t s);
  * No reference counterpart (the reference runs op by op through CUDA.jl); it serves the launch-bound fit_mesh
  * iteration (examples/fit_mesh.jl:98-110).  Capture needs a created stream; the captured calls must not allocate
  * through hipMalloc-synchronising paths or copy to the host (warm the loop up once before capturing). */
-typedef void *fx3d_graph_t; /* hipGraphExec_t */
+typedef void *fx3d_graph_t; /* opaque: the instantiated hipGraphExec_t and the hipGraph_t it came from, kept alive with it */
 FX3D_API fx3d_status fx3d_graph_begin_capture(fx3d_stream_t s);
 FX3D_API fx3d_status fx3d_graph_end_capture(fx3d_stream_t s, fx3d_graph_t *g);
 FX3D_API fx3d_status fx3d_graph_launch(fx3d_graph_t g, fx3d_stream_t s);
@@ -153,6 +164,7 @@ FX3D_API fx3d_status fx3d_profile_kernel_stats(const char *name, double *avg_ms,
  * direct-difference distance, lowest index on ties.  x:(D,N,B) y:(D,M,B) device.
  * idx_x:(N,B) int32 0-based index into y ; idx_y:(M,B) into x ; dmin_* squared distances.
  * Any of the four outputs may be NULL. */
+/* Capture: fx3d_nn1: replayed. */
 /* Batch axis: fx3d_nn1: B <= 536870911 -- the batch lies on the grid's x; B * 2 * ceil(max(N, M) / 256) < 2^30 is all that binds it. */
 FX3D_API fx3d_status fx3d_nn1(const float *x, int32_t N, const float *y, int32_t M, int32_t B,
                               int32_t D, int32_t *idx_x, int32_t *idx_y, float *dmin_x,
@@ -175,6 +187,7 @@ FX3D_API fx3d_status fx3d_chamfer_workspace_bytes(int32_t N, int32_t M, int32_t 
 /* Partial sums of _chamfer_distance (src/metrics/pcloud.jl:47-48) for this batch (shard):
  *   sums_dev[0] = sum_b sum_i ||x_i - y_nn(i)||^2 ,  sums_dev[1] = sum_b sum_j ||y_j - x_nn(j)||^2
  * (double, device, deterministic reduction order).  idx_x/idx_y optional (NULL to skip). */
+/* Capture: fx3d_chamfer_sums, fx3d_chamfer_finalize, fx3d_chamfer_finalize_many: replayed. */
 /* Batch axis: fx3d_chamfer_sums: B <= 536870911 -- as fx3d_nn1.  The split plan's two-launch form (few clouds of many thousands of
  * points) has both directions of every cloud on the grid's y and refuses B > 32767 before any launch; no shape with that many
  * clouds plans it today. */
@@ -220,6 +233,8 @@ FX3D_API fx3d_status fx3d_chamfer_finalize_many(const double *sums_dev, int32_t 
 #define FX3D_NORMALIZE_EPS_MAX 1 /* TriMesh:    (x - c) / max(s, EPS), Julia's max (NaN wins)   mesh_func.jl:99-113 */
 #define FX3D_SCALE 0             /* y = factor * x       (lmul!, pcloud_func.jl:62-66, mesh_func.jl:154-160) */
 #define FX3D_TRANSLATE 1         /* y = x + t[row]       (mesh_func.jl:331-339), D = 3 */
+/* Capture: fx3d_segment_minmax, fx3d_normalize, fx3d_realign, fx3d_rotate, fx3d_scale_translate: replayed -- the host vectors
+ * (scale, translation, one rotation matrix) are read while recording. */
 /* Batch axis: fx3d_transform_plan_describe, fx3d_transform_workspace_bytes, fx3d_segment_minmax, fx3d_normalize, fx3d_realign,
  * fx3d_rotate: B <= 65535 -- a segment is a row of the grid's y; refused by the argument check, the queries included. */
 FX3D_API fx3d_status fx3d_transform_plan_describe(int32_t D, int64_t n_max, int32_t B, char *buf, size_t n);
@@ -256,6 +271,8 @@ FX3D_API fx3d_status fx3d_scale_translate(const float *x, int64_t n, int32_t mod
 
 /* _chamfer_distance(A,B,w1,w2) forward in one call (src/metrics/pcloud.jl:39-52). loss_dev
  * device float; loss_host optional host float (non-NULL => stream is synchronised). */
+/* Capture: fx3d_chamfer_fwd, fx3d_chamfer_bwd: replayed -- fx3d_chamfer_fwd with loss_host NULL (a loss_host makes it wait for a
+ * copy to the host). */
 /* Batch axis: fx3d_chamfer_fwd, fx3d_chamfer_bwd: B <= 536870911 -- as fx3d_nn1 (fx3d_chamfer_fwd: and as fx3d_chamfer_sums). */
 FX3D_API fx3d_status fx3d_chamfer_fwd(const float *x, int32_t N, const float *y, int32_t M,
                                       int32_t B, int32_t D, float w1, float w2, float *loss_dev,
@@ -275,6 +292,7 @@ FX3D_API fx3d_status fx3d_chamfer_bwd(const float *x, int32_t N, const float *y,
  * and fx3d_chamfer_bwd are queued back to back on the stream; the nearest-neighbour indices stay in the scratch unless
  * idx_x (N,B) / idx_y (M,B) are given.  gx (D,N,B), gy (D,M,B) overwritten.  loss_host non-NULL => the stream is
  * synchronised.  ws: fx3d_chamfer_fwd_bwd_workspace_bytes. */
+/* Capture: fx3d_chamfer_fwd_bwd: replayed -- with loss_host NULL. */
 /* Batch axis: fx3d_chamfer_fwd_bwd_workspace_bytes: unbounded -- a host query.  fx3d_chamfer_fwd_bwd: B <= 536870911 -- as fx3d_nn1. */
 FX3D_API fx3d_status fx3d_chamfer_fwd_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, size_t *bytes);
 FX3D_API fx3d_status fx3d_chamfer_fwd_bwd(const float *x, int32_t N, const float *y, int32_t M, int32_t B, int32_t D,
@@ -294,6 +312,7 @@ FX3D_API fx3d_status fx3d_chamfer_fwd_bwd(const float *x, int32_t N, const float
  * gather); ws: fx3d_chamfer_sampled_bwd_workspace_bytes.  NULL tables (or a mesh beyond the limits): ONE launch that scatters the rows
  * with global float atomics (sums in arrival order), ws unused -- ~9 us per call faster at one mesh of 5000 draws as a single call (inside
  * a fit iteration the ordered form is the faster one), slower at eight meshes, not reproducible. */
+/* Capture: fx3d_chamfer_sampled_bwd, fx3d_chamfer_sampled_bwd_step: replayed. */
 /* Batch axis: fx3d_chamfer_sampled_bwd_workspace_bytes: unbounded -- a host query.  fx3d_chamfer_sampled_bwd,
  * fx3d_chamfer_sampled_bwd_step, fx3d_chamfer_sampled_bwd_step_reg: B <= 536870911 -- as fx3d_nn1, and 2 B nsplit < 2^30. */
 FX3D_API fx3d_status fx3d_chamfer_sampled_bwd_workspace_bytes(int32_t N, int32_t M, int32_t B, size_t *bytes);
@@ -345,6 +364,8 @@ typedef struct fx3d_mesh_reg {
     void *ws;
     size_t ws_bytes;
 } fx3d_mesh_reg;
+/* Capture: fx3d_sample_points_draw_pair_reg, fx3d_chamfer_sampled_bwd_step_reg: replayed -- the fx3d_mesh_reg structure is read
+ * while recording. */
 /* Batch axis: fx3d_sample_points_draw_pair_reg: unbounded -- B0 and B1 as fx3d_sample_points_draw. */
 FX3D_API fx3d_status fx3d_sample_points_draw_pair_reg(const float *verts0, int32_t Vmax0, const int32_t *faces0, int32_t Fmax0,
                                                       const int32_t *faces_len0, int32_t B0, int32_t n0, uint64_t seed0, const void *cdf_ws0,
@@ -374,6 +395,7 @@ FX3D_API fx3d_status fx3d_chamfer_sampled_bwd_step_reg(const float *x, int32_t N
  * sort after +Inf, so every returned index is valid; fx3d_nn1 / the chamfer entry points use the same order.  The distance is
  * the Float32 one AS ROUNDED: where the squares underflow (a cloud of extent 1e-20: subnormal distances of a few bits; 1e-29:
  * every distance +0) the ties this makes are ordered by index, like those of +Inf distances at the other end. */
+/* Capture: fx3d_knn, fx3d_knn_ws: replayed. */
 /* Batch axis: fx3d_knn, fx3d_knn_workspace_bytes, fx3d_knn_ws: unbounded -- on the matrix-core routes (D = 3 with M >= 64 and
  * k + drop_first <= 32, or <= 64 on larger clouds; 4 <= D <= 128 with M >= 64 and k + drop_first <= 32), which fold the batch,
  * padded to a multiple of 8, into the grid's x, the pre-pass of fx3d_knn_ws included.  Every other shape takes a kernel with the
@@ -399,6 +421,7 @@ FX3D_API fx3d_status fx3d_knn_ws(const float *x, int32_t N, const float *y, int3
                                  int32_t drop_first, int32_t *idx, float *dist, void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 /* X[:, idxs] gather -> (F,k,N,B)  (src/models/dgcnn.jl:6 `X[:, knn(...)]`, cat at :36). */
+/* Capture: fx3d_knn_gather, fx3d_edge_features, fx3d_edge_features_bwd, fx3d_edgeconv_graph: replayed. */
 /* Batch axis: fx3d_knn_gather, fx3d_edge_features, fx3d_edge_features_bwd, fx3d_edgeconv_graph: unbounded -- grid-stride kernels
  * over all elements.  Layout 1 of fx3d_edge_features has the cloud on the grid's y: B <= 65535 there, and so for
  * fx3d_edgeconv_graph at layout 1 wherever it is not the fused F = 3 kernel; fx3d_edgeconv_graph off the matrix-core routes is
@@ -439,6 +462,8 @@ FX3D_API fx3d_status fx3d_edgeconv_graph(const float *x, int32_t N, int32_t B, i
  * fx3d_index_upload: src is HOST memory (count elements); staged through ws (fx3d_index_upload_workspace_bytes, device)
  * and converted there; blocking like fx3d_memcpy_h2d.  fx3d_index_convert: src is device memory. */
 typedef enum { FX3D_IDX_I32 = 0, FX3D_IDX_U32 = 1, FX3D_IDX_I64 = 2 } fx3d_index_type;
+/* Capture: fx3d_index_convert: replayed.  fx3d_index_upload: copies to the host -- the other way: it stages the caller's pageable
+ * array through the workspace and waits for that copy. */
 FX3D_API fx3d_status fx3d_index_convert(const void *src_dev, int32_t index_type, int32_t index_base, int64_t count,
                                         int32_t clamp_pad, int64_t limit, int32_t *dst_dev, uint32_t *bad_dev,
                                         fx3d_stream_t s);
@@ -448,6 +473,7 @@ FX3D_API fx3d_status fx3d_index_upload(const void *src_host, int32_t index_type,
                                        void *ws, size_t ws_bytes, fx3d_stream_t s);
 
 /* compute_faces_areas_packed (src/rep/mesh.jl:765-780): areas (sumF). */
+/* Capture: fx3d_faces_areas_packed, fx3d_faces_areas_padded: replayed. */
 FX3D_API fx3d_status fx3d_faces_areas_packed(const float *verts, int64_t V, const int32_t *faces,
                                              int64_t F, float *areas, fx3d_stream_t s);
 /* compute_faces_areas_padded (src/rep/mesh.jl:799-808): areas (1,Fmax,B), zero padded. */
@@ -488,6 +514,7 @@ FX3D_API fx3d_status fx3d_faces_areas_padded(const float *verts_padded, int32_t 
  * padded / list forms (:640-670, :719-746): fx3d_packed_to_padded of the packed result with verts_len / faces_len.
  * V < 2^31, F < 2^29. */
 FX3D_API fx3d_status fx3d_normals_workspace_bytes(int64_t V, int64_t F, size_t *bytes);
+/* Capture: fx3d_verts_normals_packed, fx3d_verts_normals_bwd, fx3d_faces_normals_packed, fx3d_faces_normals_bwd: replayed. */
 FX3D_API fx3d_status fx3d_verts_normals_packed(const float *verts, int64_t V, const int32_t *faces, int64_t F,
                                                const int32_t *vf_rowptr, const int32_t *vf_ent, float *normals,
                                                uint8_t *winner_mask, fx3d_stream_t s);
@@ -503,6 +530,9 @@ FX3D_API fx3d_status fx3d_faces_normals_bwd(const float *verts, int64_t V, const
 
 /* _sample_points + _rand_barycentric_coords (src/transforms/mesh_func.jl:60-82) with the random
  * draws supplied: face_idx (n,B) int32 mesh-local 0-based, r1,r2 (n,B) in [0,1).  out (3,n,B). */
+/* Capture: fx3d_sample_points_explicit, fx3d_sample_points, fx3d_sample_points_cdf, fx3d_sample_points_draw,
+ * fx3d_sample_points_cdf_pair, fx3d_sample_points_draw_pair: replayed -- the seed is frozen; *seed_dev, read on the device when the
+ * graph runs, is what moves it from one replay to the next. */
 /* Batch axis: fx3d_sample_points_explicit, fx3d_sample_points_workspace_bytes, fx3d_sample_points, fx3d_sample_points_cdf,
  * fx3d_sample_points_draw, fx3d_sample_points_cdf_pair, fx3d_sample_points_draw_pair: unbounded -- one block per mesh on the
  * grid's x (the CDF) and grid-stride kernels over B * n samples (the draws).  Beyond 32768 faces per mesh (or the option cdf_multiblock_from) the CDF is built by
@@ -576,6 +606,7 @@ FX3D_API fx3d_status fx3d_sample_points_draw_pair(const float *verts0, int32_t V
 FX3D_API fx3d_status fx3d_build_vertex_faces(const int32_t *faces_padded_host, const int32_t *faces_len_host, int32_t Vmax,
                                              int32_t Fmax, int32_t B, int32_t *vf_rowptr_host, int32_t *vf_ent_host);
 FX3D_API fx3d_status fx3d_sample_points_bwd_ordered(int32_t Fmax, int32_t n, int32_t *ordered);
+/* Capture: fx3d_sample_points_bwd: replayed. */
 /* Batch axis: fx3d_sample_points_bwd: B <= 67108863 -- 16 B < 2^30 (the ordered form's grid); the batch lies on the grid's x. */
 FX3D_API fx3d_status fx3d_sample_points_bwd(const int32_t *faces_padded, int32_t Vmax,
                                             int32_t Fmax, int32_t B, int32_t n,
@@ -587,6 +618,8 @@ FX3D_API fx3d_status fx3d_sample_points_bwd(const int32_t *faces_padded, int32_t
 /* out[i] = a*x[i] + b*y[i] (+ c*z[i] when z != NULL), Float32, unfused.  The device-side arithmetic of
  * the fit_mesh loop: offset!(m, delta) is verts + delta (src/transforms/mesh_func.jl:409-416, a = b = 1),
  * the sum of the three loss gradients, and the Momentum update (examples/fit_mesh.jl:87-110). */
+/* Capture: fx3d_lincomb, fx3d_momentum_step, fx3d_momentum_step_offset, fx3d_packed_to_padded, fx3d_padded_to_packed: replayed --
+ * verts_len_host is read while recording. */
 FX3D_API fx3d_status fx3d_lincomb(int64_t n, float a, const float *x, float b, const float *y, float c,
                                   const float *z, float *out, fx3d_stream_t s);
 /* Flux.Optimise.Momentum(eta, rho) on device arrays (examples/fit_mesh.jl:87-88,110): v <- rho*v - eta*g, then
@@ -611,6 +644,8 @@ FX3D_API fx3d_status fx3d_mesh_loss_workspace_bytes(int64_t count, size_t *bytes
 
 /* edge_loss(m, target) (src/metrics/mesh.jl:24-32).  edges (E,2) int32 0-based packed vertex
  * ids, column-major (first E entries = column 1).  loss_dev device float; loss_host optional. */
+/* Capture: fx3d_edge_loss, fx3d_edge_loss_bwd, fx3d_edge_loss_bwd_adj, fx3d_laplacian_loss, fx3d_laplacian_loss_bwd,
+ * fx3d_laplacian_loss_bwd_sym, fx3d_mesh_losses, fx3d_mesh_losses_bwd: replayed -- the two losses with loss_host NULL. */
 FX3D_API fx3d_status fx3d_edge_loss(const float *verts, int64_t V, const int32_t *edges,
                                     int64_t E, float target, float *loss_dev, float *loss_host,
                                     void *ws, size_t ws_bytes, fx3d_stream_t s);
@@ -678,6 +713,7 @@ FX3D_API fx3d_status fx3d_mesh_losses_bwd(const float *verts, int64_t V, const i
  * lattice centre lies within sqrt(0.6)/res after normalising the cloud by its scalar min/max; Float64
  * distance test exactly as at :125-129 (lattice (i+0.5)/res for i = 1..res, first array dimension = the
  * reference's innermost loop variable z).  ws: fx3d_voxel_workspace_bytes(B). */
+/* Capture: fx3d_pointcloud_to_voxel: replayed. */
 /* Batch axis: fx3d_voxel_workspace_bytes: unbounded -- a host query.  fx3d_pointcloud_to_voxel: B <= 65535 -- the scatter kernel
  * has the cloud on the grid's y; refused by the argument check, before `voxels` is cleared, with a message that names B. */
 FX3D_API fx3d_status fx3d_voxel_workspace_bytes(int32_t B, size_t *bytes);
@@ -691,7 +727,7 @@ FX3D_API fx3d_status fx3d_pointcloud_to_voxel(const float *points, int32_t N, in
  * unlike fx3d_pointcloud_to_voxel.  Bit-identical to the reference's _voxelize (midpoint subdivision until every side^2
  * <= (1/res)^2, then trunc(p * (res-1))).  A mesh the reference cannot voxelise (zero extent, a NaN / Inf coordinate,
  * no vertices, a face id outside [0, verts_len)) is COUNTED in *bad_dev (optional, caller-zeroed device counter) and its
- * grid stays zero.  1 <= res <= 1024.  No host synchronisation (graph-capturable).
+ * grid stays zero.  1 <= res <= 1024.  No host synchronisation (Capture: fx3d_trimesh_to_voxel: replayed).
  * ws: fx3d_trimesh_voxel_workspace_bytes(Vmax, Fmax, B, res). */
 /* Batch axis: fx3d_trimesh_voxel_workspace_bytes: unbounded -- a host query.  fx3d_trimesh_to_voxel: B <= 65535 -- the counting
  * kernel has the mesh on the grid's y; refused by the argument check, before `voxels` is cleared, with a message that names B. */
@@ -715,6 +751,8 @@ FX3D_API fx3d_status fx3d_trimesh_to_voxel(const float *verts_padded, int32_t Vm
  *   faces_padded (3,Fmax,B) int32 0-based mesh-local, optional (NULL: none): cube j of a grid gets the reference's 12
  *   faces + 8j; entries behind a grid's 12 K faces are 0.  A grid with 12 K > Fmax gets no faces.  8 K must stay below
  *   2^31 (int32 face ids).  No entry point synchronises the host.  ws: fx3d_voxel_mesh_workspace_bytes(res, B). */
+/* Capture: fx3d_voxel_mesh_count, fx3d_voxel_mesh_emit: replayed -- each in a graph of its own where the caller reads cubes_dev
+ * between them. */
 /* Batch axis: fx3d_voxel_mesh_workspace_bytes, fx3d_voxel_mesh_count, fx3d_voxel_mesh_emit: B <= 16777216 -- the batch lies on the
  * grid's x; 2^24 grids, and tiles per grid x B < 2^31. */
 FX3D_API fx3d_status fx3d_voxel_mesh_workspace_bytes(int32_t res, int32_t B, size_t *bytes);
@@ -729,6 +767,7 @@ FX3D_API fx3d_status fx3d_voxel_mesh_emit(int32_t res, int32_t B, int64_t max_cu
  * src/metrics/pcloud.jl:47-50) -- bit for bit oracle/flux3d_oracle.c: fx3d_oracle_chamfer_loss_pairwise.  fx3d_chamfer_fwd
  * sums in Float64 (one rounding, order independent); this entry point is for a host that wants the reference's last bit.
  * Three small launches on `s`; loss_host optional (blocks).  ws: fx3d_chamfer_pairwise_workspace_bytes. */
+/* Capture: fx3d_chamfer_loss_pairwise_f32: replayed -- with loss_host NULL. */
 /* Batch axis: fx3d_chamfer_pairwise_workspace_bytes: unbounded -- a host query.  fx3d_chamfer_loss_pairwise_f32: B <= 536870911 --
  * as fx3d_nn1. */
 FX3D_API fx3d_status fx3d_chamfer_pairwise_workspace_bytes(int32_t N, int32_t M, int32_t B, int32_t D, size_t *bytes);
@@ -761,6 +800,8 @@ FX3D_API fx3d_status fx3d_comm_exchange_id(uint8_t *id128, int32_t nranks, int32
  * (ncclGetVersion); any output may be NULL, comm may be NULL when only the version is asked for. */
 FX3D_API fx3d_status fx3d_comm_info(fx3d_comm_t comm, int32_t *nranks, int32_t *rank, int32_t *rccl_version);
 FX3D_API fx3d_status fx3d_comm_destroy(fx3d_comm_t comm);
+/* Capture: fx3d_comm_allreduce_sum_f64, fx3d_comm_allreduce_max_f64, fx3d_chamfer_fwd_sharded, fx3d_chamfer_fwd_sharded_async:
+ * collective -- an RCCL all-reduce inside a capture is not attempted. */
 FX3D_API fx3d_status fx3d_comm_allreduce_sum_f64(fx3d_comm_t comm, double *buf_dev, int64_t count,
                                                  fx3d_stream_t s);
 /* all-reduce(max): the control plane of a timing harness (max over ranks of an elapsed time; with any buffer: a barrier) */
@@ -855,6 +896,8 @@ FX3D_API fx3d_status fx3d_build_laplacian_csr(const int64_t *edges, int64_t E, i
  *   faces_to_edges (F,3) column-major, optional (NULL: none; faces_packed is read only for it): edge ids in the reference's
  *   column order (e23, e31, e12) (:946).  ws: fx3d_edges_dev_workspace_bytes(F, V). */
 FX3D_API fx3d_status fx3d_edges_dev_workspace_bytes(int64_t F, int64_t V, size_t *bytes);
+/* Capture: fx3d_edges_dev_count, fx3d_edges_dev_emit, fx3d_laplacian_dev_csr, fx3d_vertex_faces_dev,
+ * fx3d_faces_padded_to_packed_dev: replayed -- count and emit each in a graph of its own where the caller reads E_dev between them. */
 FX3D_API fx3d_status fx3d_edges_dev_count(const int32_t *faces_packed, int64_t F, int64_t V, int64_t *E_dev,
                                           uint32_t *bad_dev, void *ws, size_t ws_bytes, fx3d_stream_t s);
 FX3D_API fx3d_status fx3d_edges_dev_emit(const int32_t *faces_packed, int64_t F, int64_t V, int64_t E, int32_t *edges,
@@ -923,7 +966,7 @@ FX3D_API fx3d_status fx3d_faces_padded_to_packed_dev(const int32_t *faces_padded
  *   fx3d_pointnet_param_count(num_classes) is its length in floats.
  * probs (num_classes,B) is required; logits (num_classes,B), stn (3,3,B), fstn (64,64,B), pooled (1024,B) are optional
  * (NULL: not written).  Six launches on `s`, no host synchronisation, no host memory read after the argument check
- * (graph-capturable).  ws: fx3d_pointnet_workspace_bytes(N, B, num_classes), 16-byte aligned. */
+ * (Capture: fx3d_pointnet_forward: replayed).  ws: fx3d_pointnet_workspace_bytes(N, B, num_classes), 16-byte aligned. */
 FX3D_API fx3d_status fx3d_pointnet_param_count(int32_t num_classes, int64_t *count);
 /* Batch axis: fx3d_pointnet_workspace_bytes, fx3d_pointnet_forward: B <= 65535 -- the point kernels have the cloud on the grid's y;
  * refused by the size check, the query included, with a message that names B. */
@@ -962,7 +1005,7 @@ FX3D_API fx3d_status fx3d_pointnet_forward(const float *params_dev, int32_t num_
  * probs (num_classes,B) is required; logits (num_classes,B), idx1 and idx2 (K,N,B) int32, x1 (64,N,B; 16-byte aligned),
  * x2 (256,N,B) and pooled (1024,B) are optional (NULL: not written).  Launches on `s` only (per EdgeConv what
  * fx3d_edgeconv_forward below launches -- the search through fx3d_knn_ws and the EdgeConv kernel --, then conv_3 and the
- * head), no host synchronisation, no host memory read after the argument check (graph-capturable).
+ * head), no host synchronisation, no host memory read after the argument check (Capture: fx3d_dgcnn_forward: replayed).
  * ws: fx3d_dgcnn_workspace_bytes(N, B, K, num_classes) -- x1, x2, per-tile maxima, the logits and one EdgeConv workspace (the
  * neighbour lists and the search's scratch), the larger of the two stages', which they use in turn. */
 FX3D_API fx3d_status fx3d_dgcnn_param_count(int32_t num_classes, int64_t *count);
@@ -998,7 +1041,7 @@ FX3D_API fx3d_status fx3d_dgcnn_forward(const float *params_dev, int32_t num_cla
  * required pointer (params_dev, layers, x, out, ws), a short workspace or one not 256-byte aligned is FX3D_ERR_INVALID_ARG.
  * Every refusal comes before any device work and names the offending value in fx3d_last_error.
  * Launches on `s` only (the search through fx3d_knn_ws, one EdgeConv kernel), no host synchronisation, no host memory other
- * than `layers` read, and none after the argument check (graph-capturable).  ws: fx3d_edgeconv_workspace_bytes(layers, nlayers,
+ * than `layers` read, and none after the argument check (Capture: fx3d_edgeconv_forward: replayed).  ws: fx3d_edgeconv_workspace_bytes(layers, nlayers,
  * K, N, B) -- the neighbour lists and the search's scratch. */
 FX3D_API fx3d_status fx3d_edgeconv_param_count(const int32_t *layers, int32_t nlayers, int64_t *count);
 /* Batch axis: fx3d_edgeconv_workspace_bytes, fx3d_edgeconv_forward: B <= 65535 -- the EdgeConv kernel has the cloud on the grid's
@@ -1038,7 +1081,7 @@ FX3D_API fx3d_status fx3d_edgeconv_forward(const float *params_dev, const int32_
  * index outside [0, N) reads the point itself, as in the forward.
  * Launches on `s` only (the search and / or the forward where idx / out are NULL, one small kernel that lays the weights out
  * transposed in the workspace, the adjoint kernel), no host synchronisation, no host memory other than `layers` read, and none
- * after the argument check (graph-capturable).  ws: fx3d_edgeconv_bwd_workspace_bytes(layers, nlayers, K, N, B) -- the forward's
+ * after the argument check (Capture: fx3d_edgeconv_bwd: replayed).  ws: fx3d_edgeconv_bwd_workspace_bytes(layers, nlayers, K, N, B) -- the forward's
  * workspace, the lists, out and the transposed weights. */
 /* Batch axis: fx3d_edgeconv_bwd_workspace_bytes, fx3d_edgeconv_bwd: B <= 65535 -- as fx3d_edgeconv_forward. */
 FX3D_API fx3d_status fx3d_edgeconv_bwd_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
@@ -1080,7 +1123,7 @@ FX3D_API fx3d_status fx3d_edgeconv_bwd(const float *params_dev, const int32_t *l
  * (K N, ., B) array in memory.  gx is fx3d_edgeconv_bwd's, bit for bit.
  * Envelope, refusals, their order, status codes and messages are fx3d_edgeconv_bwd's (required pointers: params_dev, layers, x,
  * gout, gparams, ws); every refusal comes before any device work.  Launches on `s` only (the search and / or the forward where
- * idx / out are NULL, the weight transpose, the kernel, two finishing kernels), no host synchronisation (graph-capturable).
+ * idx / out are NULL, the weight transpose, the kernel, two finishing kernels), no host synchronisation (Capture: fx3d_edgeconv_grad: replayed).
  * ws: fx3d_edgeconv_grad_workspace_bytes -- the input adjoint's, one partial of param_count floats per chunk and cloud, and the sums. */#define FX3D_EDGECONV_GRAD_CHUNK 128 /* points of one cloud whose rows are summed as one chain ("EdgeConv parameter adjoint") */
 /* Batch axis: fx3d_edgeconv_grad_workspace_bytes, fx3d_edgeconv_grad: B <= 65535 -- as fx3d_edgeconv_forward. */
 FX3D_API fx3d_status fx3d_edgeconv_grad_workspace_bytes(const int32_t *layers, int32_t nlayers, int32_t K, int32_t N, int32_t B,
@@ -1129,7 +1172,7 @@ FX3D_API fx3d_status fx3d_edgeconv_grad(const float *params_dev, const int32_t *
  * workspace or one not 256-byte aligned is FX3D_ERR_INVALID_ARG; each comes before any device work.
  * Launches on `s` only (the forward where no intermediates are given, the argmax recomputation of conv_3, the head's adjoint, the
  * two gathers, the sums over the clouds and their finishing, the two fx3d_edgeconv_grad calls), no host synchronisation, no host
- * memory read after the argument check (graph-capturable).
+ * memory read after the argument check (Capture: fx3d_dgcnn_grad: replayed).
  * ws: fx3d_dgcnn_grad_workspace_bytes(N, B, K, num_classes) -- the forward's intermediates and probabilities; per (tile of 64
  * points, channel) the first point that reproduces pooled; n*, a4, a5, d5, d4, d3, dz3; H and h of fc_4 and fc_5; gx2 and gx1; and
  * one scratch region, the largest of fx3d_dgcnn_workspace_bytes and the two stages' fx3d_edgeconv_grad_workspace_bytes, which
@@ -1191,7 +1234,7 @@ FX3D_API fx3d_status fx3d_dgcnn_grad(const float *params_dev, int32_t num_classe
  * 256-byte aligned (fx3d_dgcnn_grad's alignment) is FX3D_ERR_INVALID_ARG; each comes before any device work.
  * Launches on `s` only (the forward's five launches below the classifier's head; per round the head's adjoint, the trunk's
  * adjoint, the last convolution's sums, the head's sums over the clouds, the chains over the tile partials), no host
- * synchronisation, no host memory read after the argument check (graph-capturable).
+ * synchronisation, no host memory read after the argument check (Capture: fx3d_pointnet_grad: replayed).
  * ws: fx3d_pointnet_grad_workspace_bytes(N, B, num_classes) -- h, T, F; per round and (tile, channel) the maximum, its first point
  * and the BatchNorm's input there; the head's vectors; the last convolution's input rows at the winners (128,1024,B); one partial
  * per tile and cloud; the feat path's gradient at h; gxt, gT and gF. */
@@ -1233,7 +1276,7 @@ FX3D_API fx3d_status fx3d_pointnet_grad(const float *params_dev, int32_t num_cla
  * Refusals, FX3D_ERR_INVALID_ARG, before any device work: a NULL required pointer; fx3d_pointnet_forward's size limits;
  * B < 2 (a dense BatchNorm's running variance divides by B - 1); momentum not finite or outside [0, 1]; a short workspace or
  * one not 16-byte aligned.  32 launches on `s`, no host synchronisation, no host memory read after the argument check
- * (graph-capturable).  ws: fx3d_pointnet_train_workspace_bytes(N, B, num_classes) -- the forward's workspace, the tile sums
+ * (Capture: fx3d_pointnet_forward_train: replayed).  ws: fx3d_pointnet_train_workspace_bytes(N, B, num_classes) -- the forward's workspace, the tile sums
  * (2,1024,ntiles,B) Float64, and the heads' (512,B) and (256,B) activations. */
 #define FX3D_POINTNET_STAT_GROUPS 32 /* chains the tile sums of a layer are folded in ("PointNet training-mode forward") */
 FX3D_API fx3d_status fx3d_pointnet_stat_count(int64_t *count);
@@ -1280,7 +1323,8 @@ FX3D_API fx3d_status fx3d_pointnet_forward_train(const float *params_dev, int32_
  * restatement tests/pointnet_grad_train_ref.py and from run to run.  An all-1.0f dropout gives the bits of dropout = NULL.
  * Refusals, FX3D_ERR_INVALID_ARG, each before any device work: a NULL required pointer (params_dev, x, batch_stats, glogits, gparams,
  * ws); fx3d_pointnet_forward's size limits; B < 2; a short workspace or one not 256-byte aligned.
- * Launches on `s` only, no host synchronisation, no host memory read after the argument check (graph-capturable).
+ * Launches on `s` only, no host synchronisation, no host memory read after the argument check (Capture: fx3d_pointnet_grad_train:
+ * replayed).
  * ws: fx3d_pointnet_grad_train_workspace_bytes(N, B, num_classes) -- fx3d_pointnet_grad's forward part and head vectors; the Float64
  * tile sums (2,128,ntiles,B); the last convolution's input and the gradient at it, (128,N,B) each; two (64,N,B) gradients, the feat
  * path's gradient at h; dW and db of the last convolution per cloud, (128,1024,B) and (1024,B); one partial per tile and cloud. */
@@ -1337,7 +1381,7 @@ FX3D_API fx3d_status fx3d_pointnet_grad_train(const float *params_dev, int32_t n
  * batch_stats, ws), B < 2 for DGCNN (a dense BatchNorm's running variance divides by B - 1), momentum not finite or outside [0, 1],
  * a short workspace or one not 256-byte aligned.
  * Launches on `s` only, no host synchronisation, no host memory other than `layers` read and none after the argument check
- * (graph-capturable).  Per EdgeConv: the search where idx_in is NULL, per BatchNorm a statistics pass (the forward's loop over k
+ * (Capture: fx3d_edgeconv_forward_train, fx3d_dgcnn_forward_train: replayed).  Per EdgeConv: the search where idx_in is NULL, per BatchNorm a statistics pass (the forward's loop over k
  * stopped at that layer, the sums taken in the MFMA accumulators: no (K N, C, B) array in memory) and a finishing kernel, then the
  * forward's kernel at the statistics.  DGCNN: that twice, conv_3's statistics pass, finishing kernel and maxima kernel, and the head
  * in three kernels with two dense-statistics kernels between them: 20 launches besides the two searches.
@@ -1399,7 +1443,7 @@ FX3D_API fx3d_status fx3d_dgcnn_forward_train(const float *params_dev, int32_t n
  * pointers (params_dev, layers, x, batch_stats, gout, gparams, ws); B = 1 is allowed, as in the forward.  Every refusal comes
  * before any device work.  Launches on `s` only (the search and / or the closing forward where idx / out are NULL, the weight
  * transpose, per layer a sums pass and a finishing kernel, the closing pass, the chain over the chunks), no host synchronisation,
- * no host memory other than `layers` read (graph-capturable).
+ * no host memory other than `layers` read (Capture: fx3d_edgeconv_grad_train: replayed).
  * ws: fx3d_edgeconv_grad_train_workspace_bytes -- the input adjoint's, one partial of param_count floats per chunk and cloud, the
  * Float64 half-tile sums (2,C,nhalf,B) of the widest layer, and the means. */
 /* Batch axis: fx3d_edgeconv_grad_train_workspace_bytes, fx3d_edgeconv_grad_train: B <= 65535 -- as fx3d_edgeconv_forward. */
@@ -1448,7 +1492,7 @@ FX3D_API fx3d_status fx3d_edgeconv_grad_train(const float *params_dev, const int
  * Refusals, FX3D_ERR_INVALID_ARG, each before any device work: a NULL required pointer (params_dev, x, idx1, x1, idx2, x2, pooled,
  * batch_stats, glogits, gparams, ws); fx3d_dgcnn_forward_train's size limits, B < 2 among them; a short workspace or one not
  * 256-byte aligned.  Launches on `s` only, no host synchronisation, no host memory read after the argument check
- * (graph-capturable): the winners' kernel, the head in three kernels with a cloud-sums kernel after each, three dense-sums kernels,
+ * (Capture: fx3d_dgcnn_grad_train: replayed) -- the winners' kernel, the head in three kernels with a cloud-sums kernel after each, three dense-sums kernels,
  * conv_3's two dense kernels and two chains over the clouds, then the two stages' launches.
  * ws: fx3d_dgcnn_grad_train_workspace_bytes(N, B, K, num_classes) -- the per-tile first matches (1024,ntiles,B) with what conv3.bn
  * was given there; the head's vectors; dW3 and db3 per cloud, (256,1024,B) and (1024,B); gx2 and gx1; one scratch region, the
@@ -1466,7 +1510,8 @@ FX3D_API fx3d_status fx3d_dgcnn_grad_train(const float *params_dev, int32_t num_
  * Three entry points between and after fx3d_*_forward_train and fx3d_*_grad_train.  Nothing is fused (-ffp-contract=off), every
  * operation below is rounded once, in the precision named.  Float32 and int32 arrays may be aligned to 4 bytes only; the Float64
  * and UInt64 arrays (loss, betap, counter_dev) must be 8-byte aligned, FX3D_ERR_INVALID_ARG otherwise.  Launches on `s` only: no
- * host synchronisation, no allocation, no host memory or environment read (graph-capturable).  Plain stores, no atomics; the results
+ * host synchronisation, no allocation, no host memory or environment read (Capture: fx3d_crossentropy, fx3d_dropout_mask,
+ * fx3d_adam_step: replayed).  Plain stores, no atomics; the results
  * are the same bits from run to run and those of the restatement tests/train_step_ref.py (the loss up to the device's log).
  *
  * fx3d_crossentropy: Flux.crossentropy(probs, onehot(labels)) with its gradient at the logits, and the tutorial's accuracy count.

@@ -1,7 +1,7 @@
 """One statement of every kernel family's C-ABI call and of the reference it is held to.
 
-tests/test_gpu_alignment.py (pointers aligned to 4 bytes only) and tests/test_gpu_workspace.py (dirty, exact-size scratch) run
-the same families: each family builds its arrays, states the call as a closure ``call(p, ws, ws_bytes)`` over the placed
+tests/test_gpu_alignment.py (pointers aligned to 4 bytes only), tests/test_gpu_workspace.py (dirty, exact-size scratch) and
+tests/test_gpu_replay.py (the call recorded into a graph and replayed, on the recorded and on other data) run the same families: each family builds its arrays, states the call as a closure ``call(p, ws, ws_bytes)`` over the placed
 pointers, hands both to the ``hold`` driver of the file that runs it and compares what ``hold`` returns -- the outputs of the
 plain call -- with the family's reference exactly as the family's own test checks it (the oracle, the tests/*_ref.py
 restatements, the golden known answers; the one tolerance is LOSS_RTOL, chamfer loss against the oracle, as everywhere).
@@ -69,12 +69,17 @@ class Calls:
     """What a driver may hang on every C-ABI call a family makes through ``_abi``: ``before(name)`` / ``after(name)`` run around
     the call (the workspace driver checks its guard pads after each call of a carried pair), ``before`` returning False leaves the
     call out; ``refused(name, error)`` returning True swallows an error status other than FX3D_ERR_HIP (the refusal driver
-    records it)."""
-    before = after = refused = None
+    records it).  ``stream``: the families state every call on the default stream, a literal None as the last argument; a driver
+    that runs them on a stream of its own (tests/test_gpu_replay.py: a capture needs a created stream) puts its handle here, and
+    it takes the place of that trailing None wherever the entry point's last parameter is a pointer -- in every call a family
+    makes through ``_abi`` that is the stream."""
+    before = after = refused = stream = None
 
 
 def _abi(fx, name):
     def f(*args):
+        if Calls.stream is not None and args and args[-1] is None and fx._lib.SIGNATURES[name][-1] is fx._lib.vp:
+            args = args[:-1] + (Calls.stream,)
         if Calls.before and Calls.before(name) is False:
             return
         try:
