@@ -37,7 +37,7 @@ from .graph import (create_knn_graph, edge_features, edge_features_grad, edgecon
                     knn_gather)
 from .conversions import (pointcloud_from_voxels, pointcloud_to_voxel, trimesh_from_pointcloud,  # noqa: E402
                           trimesh_from_voxels, trimesh_to_voxel, voxel_to_trimesh)
-from .models import DGCNN, EdgeConv, PointNet, StepResult  # noqa: E402
+from .models import DGCNN, EdgeConv, PointNet, StepResult, stnKD  # noqa: E402
 from .optim import ADAM, TrainStepGraph  # noqa: E402
 from . import synth  # noqa: E402
 

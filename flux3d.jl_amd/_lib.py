@@ -1,4 +1,4 @@
-"""ctypes binding of libflux3d_hip.so (include/flux3d_hip.h).
+"""ctypes binding of libflux3d_hip.so (include/flux3d_hip.h, include/flux3d_hip_layers.h).
 
 This is the Python twin of julia/Flux3DHip.jl's ``@ccall`` layer: one thin wrapper per C-ABI entry
 point, status codes turned into exceptions.  There is NO fallback: if the shared library is
@@ -222,6 +222,14 @@ SIGNATURES = {
     "fx3d_faces_padded_to_packed_dev_workspace_bytes": [c_i32, C.POINTER(sz)],
     "fx3d_faces_padded_to_packed_dev": [vp, vp, vp, c_i32, c_i32, c_i64, vp, vp, sz, vp],
 }
+# include/flux3d_hip_layers.h: the models' building blocks as layers of their own, bound like SIGNATURES
+LAYER_SIGNATURES = {
+    "fx3d_stnkd_param_count": [c_i32, C.POINTER(c_i64)],
+    "fx3d_stnkd_workspace_bytes": [c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_stnkd_forward": [vp, c_i32, vp, c_i32, c_i32, vp, vp, vp, sz, vp],
+    "fx3d_stnkd_train_workspace_bytes": [c_i32, c_i32, c_i32, C.POINTER(sz)],
+    "fx3d_stnkd_forward_train": [vp, c_i32, vp, c_i32, c_i32, c_f32, vp, vp, vp, vp, vp, sz, vp],
+}
 _RESTYPES = {"fx3d_version": C.c_char_p, "fx3d_last_error": sz, "fx3d_option_count": c_i32, "fx3d_option_name": C.c_char_p}
 
 _lib = None
@@ -237,7 +245,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             f"g.build()'` or `make -C flux3d.jl_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, args in {**SIGNATURES, **LAYER_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_i32)

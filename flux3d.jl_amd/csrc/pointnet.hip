@@ -18,7 +18,8 @@
 //     per half.  The last layer (128 -> 1024) is never stored: each slab is reduced to the tile's maximum per channel
 //     (Julia's max) and written to the workspace with plain stores.
 //     MODE 0 = stn (X -> 64 -> 128 -> 1024), 1 = fstn (X * T -> conv_block1 -> stored as h (64, N, B) -> 64 -> 128 -> 1024),
-//     2 = feat (h * F -> 128 -> 1024, no relu on the last).
+//     2 = feat (h * F -> 128 -> 1024, no relu on the last), 3 = stnKD(K) for a K known at run time only (stnkd.hip: MODE 0's
+//     layers, the first on mfma_slab_rt over the tile of x (K, N, B) in columns 0 .. K - 1 of an image).
 //   pointnet_head_kernel<FEAT>: one block per cloud folds the per-tile maxima, then the dense layers with one thread per
 //     output element (W (out, in) column-major: consecutive threads read consecutive weights), BatchNorm, and for the
 //     classifier relu + softmax.  stn / fstn write their (K, K) matrix already transposed (T[i,j] = d[j + K i] at i + K j),
@@ -89,6 +90,13 @@ namespace mlp {
 namespace pointnet {
 
 fx3d_status launch_points(int mode, bool win, const PointArgs &a, int B, hipStream_t st) {
+    if (mode == 3) {  // stnKD(K), stnkd.hip: it has no adjoint, so no instantiation with the winners
+        if (win) {
+            set_error("launch_points: stnKD(K) has no winners' instantiation");
+            return FX3D_ERR_UNSUPPORTED;
+        }
+        return launch_points_of<3, false>(a, B, st);
+    }
     if (win) return mode == 0 ? launch_points_of<0, true>(a, B, st) : mode == 1 ? launch_points_of<1, true>(a, B, st) : launch_points_of<2, true>(a, B, st);
     return mode == 0 ? launch_points_of<0, false>(a, B, st) : mode == 1 ? launch_points_of<1, false>(a, B, st) : launch_points_of<2, false>(a, B, st);
 }

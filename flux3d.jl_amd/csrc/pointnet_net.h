@@ -5,6 +5,7 @@
 // launches of pointnet_grad.hip's finishing kernels; and what the training-mode adjoints of PointNet and DGCNN share (bn_gv, BnOut,
 // LastChannel, the cloud-sums launch, and the dense adjoint of the 1024-output convolution under a maximum: last_back, last_pgrad,
 // their arguments and launch_tile).
+// stnkd.hip, stnKD(K) as a layer of its own, is round_trunk's MODE 3 on these kernels: it adds a host walk, no trunk of its own.
 // On the host: the walk over the flat parameter buffer, the forward's workspace, the size check of the entries, the
 // arguments of the forward's two kernels per round (set_round, stn_head, feat_head) and their launches (defined in
 // pointnet.hip, which owns the kernels).  On the device: a round's layer chain (round_trunk, with its tile loads), the slab
@@ -23,7 +24,7 @@ constexpr size_t kPtLds = (size_t)(2 * kTile * kLd + 2 * kTile * 3) * sizeof(flo
 constexpr int kNoPoint = INT_MAX;  // a tile in which no point reproduces its maximum (a NaN maximum)
 
 struct PointArgs {
-    const float *x;   // (3, N, B): MODE 0, 1
+    const float *x;   // (3, N, B): MODE 0, 1; (K, N, B): MODE 3
     float *h;         // workspace (64, N, B): written by MODE 1, read by MODE 2
     const float *tf;  // the cloud's transform, (3, 3, B) for MODE 1, (64, 64, B) for MODE 2
     Conv c0;          // MODE 1: conv_block1
@@ -32,6 +33,7 @@ struct PointArgs {
     int N, ntiles;
     int32_t *tfirst;  // the adjoint's launches (WIN): (1024, ntiles, B), the first point of the tile that equals the tile's maximum
     float *tpre;      //   and what the last layer's BatchNorm was given at that point
+    int K;            // MODE 3: the channels of x, 1 .. 128
 };
 
 struct HeadArgs {
@@ -192,16 +194,39 @@ __device__ __forceinline__ void load_tile64(float *img, const float *src, int b,
 // ---- conv_mfma's walk over the slabs of 32 output channels, with the epilogue left to the caller -----------------------------
 // body(o, h, acc0, acc1) while the slab of `in` (row stride LD) times W (CIN, cout) is in the accumulators: o is the lane's
 // channel, acc0 / acc1 its 16 points mfma_row(r, h) of the tile's two 32-point halves.  All 4 waves call it.
+// CIN = 0: the width is `cin`, known at run time only (MODE 3's first layer): mfma_slab_rt on both halves, so cin needs no padding
+// and is never padded (mlp_common.h); W is then read 4-byte aligned (W4: W + cin o is 16-byte aligned for no odd cin).
 template <int CIN, int LD = kLd, class Body>
-__device__ __forceinline__ void for_each_slab(const float *in, const float *__restrict__ W, int cout, Body body) {
+__device__ __forceinline__ void for_each_slab(const float *in, const float *__restrict__ W, int cout, Body body, int cin = CIN) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
     const float *a0 = in + j * LD + h, *a1 = a0 + 32 * LD;
     for (int sl = wave; sl < cout / 32; sl += kPtThreads / 64) {
         const int o = sl * 32 + j;
-        f32x16 acc0 = {0}, acc1 = {0};
-        mfma_slab<CIN>(a0, a1, W + (size_t)CIN * o, h, acc0, acc1);
-        body(o, h, acc0, acc1);
+        if constexpr (CIN == 0) {
+            f32x16 acc[2] = {{0}, {0}};
+            mfma_slab_rt<LD, 2>(in, W + (size_t)cin * o, cin, h, j, acc);
+            body(o, h, acc[0], acc[1]);
+        } else {
+            f32x16 acc0 = {0}, acc1 = {0};
+            mfma_slab<CIN>(a0, a1, W + (size_t)CIN * o, h, acc0, acc1);
+            body(o, h, acc0, acc1);
+        }
     }
+}
+
+// conv_mfma<cin, EPI, false> for a width known at run time only (for_each_slab<0>): out[p][o] = epilogue(sum_c in[p][c] W[c + cin o]),
+// o < cout (a multiple of 32); `in` and `out` are two images
+template <int EPI, int LD = kLd>
+__device__ __forceinline__ void conv_first_rt(const float *in, float *out, int cin, int cout, const Conv &c) {
+    for_each_slab<0, LD>(in, c.W, cout, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
+        const float bi = c.b[o], g = c.bn.g[o], be = c.bn.b[o], mu = c.bn.m[o], sd = bn_sd(c.bn, o);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int p = mfma_row(r, h);
+            out[p * LD + o] = epilogue<EPI>(acc0[r], bi, g, be, mu, sd);
+            out[(p + 32) * LD + o] = epilogue<EPI>(acc1[r], bi, g, be, mu, sd);
+        }
+    }, cin);
 }
 
 // conv_mfma<128, EPI, true> -- the same slabs, epilogue and fold, so the same tmax -- that also finds, while the slab's values
@@ -246,20 +271,23 @@ __device__ __forceinline__ void conv_final_win(const float *in, const Conv &c, i
 // ---- a round's layers, once ---------------------------------------------------------------------------------------------------
 // One block = 64 points of cloud b from p0 on, 4 waves, lds of kPtLds bytes: the tile load, then the round's layers in order,
 // each into the image the next reads.  The BatchNorm layers of a round count from 0 (MODE 0, stn: conv1, conv2, conv3; MODE 1,
-// fstn: conv_block1, conv1, conv2, conv3; MODE 2, feat: conv1, conv2); layer STOP is not computed here but handed to
+// fstn: conv_block1, conv1, conv2, conv3; MODE 2, feat: conv1, conv2; MODE 3, stnKD(K) for a.K known at run time only
+// (stnkd.hip): MODE 0's layers on x (K, N, B), the tile in columns 0 .. K - 1 of an image and conv1 on mfma_slab_rt, handed to
+// the tail as a Layer with CIN = 0); layer STOP is not computed here but handed to
 // tail(in, conv, Layer<CIN, COUT, EPI>{}): its input image, its parameters and its shape.  STOP = kLastLayer[MODE] with the
 // fold over the tile as the tail is the forward's pointnet_points_kernel; a smaller STOP with the statistics epilogue is
 // pointnet_stats_kernel, so the layers below a BatchNorm are the same calls in both.  KEEP_H: MODE 1 stores conv_block1's
 // output to a.h.
 template <int CIN_, int COUT_, int EPI_>
 struct Layer { static constexpr int CIN = CIN_, COUT = COUT_, EPI = EPI_; };
-constexpr int kLastLayer[3] = {2, 3, 1};
+constexpr int kLastLayer[4] = {2, 3, 1, 2};
 
 template <int MODE, int STOP, bool KEEP_H, class Tail>
 __device__ __forceinline__ void round_trunk(const PointArgs &a, float *lds, int b, int p0, int nvalid, Tail tail) {
     float *bufA = lds, *bufB = lds + kTile * kLd, *xs = bufB + kTile * kLd, *xt = xs + kTile * 3;
     const int tid = threadIdx.x;
-    if (MODE != 2) load_xs(xs, a.x, b, a.N, p0, nvalid);
+    if constexpr (MODE == 3) gather_centre(bufA, kLd, a.x + (size_t)b * a.N * a.K, a.K, p0, nvalid);
+    else if (MODE != 2) load_xs(xs, a.x, b, a.N, p0, nvalid);
     else load_tile64(bufA, a.h, b, a.N, p0, nvalid);
     __syncthreads();
     if constexpr (MODE == 0) {
@@ -284,6 +312,14 @@ __device__ __forceinline__ void round_trunk(const PointArgs &a, float *lds, int 
         conv_mfma<64, kReluBn, false>(bufA, bufB, 64, a.c1.W, a.c1.b, a.c1.bn, nvalid, nullptr);
         __syncthreads();
         if constexpr (STOP == 2) return tail(bufB, a.c2, Layer<64, 128, kReluBn>{});
+        conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
+        __syncthreads();
+        tail(bufA, a.c3, Layer<128, kFeat, kReluBn>{});
+    } else if constexpr (MODE == 3) {
+        if constexpr (STOP == 0) return tail(bufA, a.c1, Layer<0, 64, kReluBn>{});
+        conv_first_rt<kReluBn>(bufA, bufB, a.K, 64, a.c1);
+        __syncthreads();
+        if constexpr (STOP == 1) return tail(bufB, a.c2, Layer<64, 128, kReluBn>{});
         conv_mfma<64, kReluBn, false>(bufB, bufA, 128, a.c2.W, a.c2.b, a.c2.bn, nvalid, nullptr);
         __syncthreads();
         tail(bufA, a.c3, Layer<128, kFeat, kReluBn>{});
@@ -424,10 +460,10 @@ __device__ __forceinline__ void store_tile_sum(double *sums, int o, double s1, d
 }
 
 // a convolution on the MFMA whose BatchNorm's statistics are wanted: conv_mfma's slabs (for_each_slab) with the statistics
-// epilogue.  sums: the tile's (2, cout).
+// epilogue.  sums: the tile's (2, cout).  CIN = 0: the width is `cin` (for_each_slab).
 template <int CIN, int EPI, int LD = kLd>
 __device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const float *__restrict__ W, const float *__restrict__ bias,
-                                               int nvalid, double *__restrict__ sums) {
+                                               int nvalid, double *__restrict__ sums, int cin = CIN) {
     for_each_slab<CIN, LD>(in, W, cout, [&](int o, int h, const f32x16 &acc0, const f32x16 &acc1) {
         const float bi = bias[o];
         TileSum t;
@@ -439,7 +475,7 @@ __device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const 
             if (mfma_row(r, h) + 32 < nvalid) t.add(before_bn<EPI>(acc1[r], bi));
         const double o1 = __shfl_xor(t.s1, 32, 64), o2 = __shfl_xor(t.s2, 32, 64);
         if (h == 0) store_tile_sum(sums, o, t.s1 + o1, t.s2 + o2);
-    });
+    }, cin);
 }
 
 // pointnet_train.hip's two finishing kernels on st.  launch_stat_finish: the fold of a layer's tile sums (2, C, T), T = ntiles B,
@@ -448,6 +484,21 @@ __device__ __forceinline__ void conv_stat_mfma(const float *in, int cout, const 
 // library's profile.
 fx3d_status launch_stat_finish(const double *sums, int C, long long T, const StatOut &o, hipStream_t st, const char *label);
 fx3d_status launch_dense_stats(const float *act, int C, int B, const StatOut &o, hipStream_t st, const char *label);
+
+// pointnet_train.hip's statistics pass and its heads cut at their BatchNorms, for stnkd.hip as well
+struct StatArgs {
+    PointArgs p;
+    double *sums;  // (2, C, ntiles, B) for the C channels of the layer
+};
+struct TrainHeadArgs {
+    HeadArgs h;            // the test-mode head's arguments, bn1 / bn2 at the batch statistics
+    float *a1, *a2;        // workspace: relu(dense1) (512, B), FEAT only; relu(dense2) [times the dropout multiplier] (256, B)
+    const float *dropout;  // FEAT: (256, B) multipliers or NULL
+};
+// pointnet_stats_kernel<mode, L> on st: the tile sums of BatchNorm L of round `mode` (round_trunk's modes, 3 = stnKD(K))
+fx3d_status launch_stats(int mode, int L, const StatArgs &s, int B, hipStream_t st);
+// part 0 = head_a (MaxPool, relu(dense1); stn / fstn: relu(dense2) too), 1 = head_b (feat), 2 = head_c (BatchNorm(256), the end)
+fx3d_status launch_train_head(int part, bool feat, const TrainHeadArgs &t, int B, hipStream_t st);
 
 // ---- what the two adjoints (pointnet_grad.hip, pointnet_grad_train.hip) share ------------------------------------------------------
 // the gradient's block of a conv layer with its BatchNorm: W | b | gamma | beta | mu | var

@@ -18,7 +18,9 @@
 // No atomics anywhere: every sum has one owner and one order, which depends on (N, B) alone.
 // What a statistic is made of -- the Float64 tile sums and their epilogue on the MFMA (TileSum, conv_stat_mfma), the fold, mean,
 // variance and running update (fold_tile_sums, finish_channel) -- is in pointnet_net.h; the two finishing kernels below are launched
-// through it (launch_stat_finish, launch_dense_stats) by the training-mode forwards of DGCNN and EdgeConv as well.
+// through it (launch_stat_finish, launch_dense_stats) by the training-mode forwards of DGCNN and EdgeConv as well.  stnKD(K) as a
+// layer of its own (stnkd.hip) is round_trunk's MODE 3 -- MODE 0's layers with the input width at run time -- on the statistics
+// kernel and the heads of this file (launch_stats, launch_train_head, declared in pointnet_net.h too).
 #include <initializer_list>
 
 #include "pointnet_net.h"
@@ -56,11 +58,6 @@ __device__ __forceinline__ void conv_stat3(const float *xs, const float *__restr
     if (h == 0) store_tile_sum(sums, o, t.s1 + other[0][o], t.s2 + other[1][o]);
 }
 
-struct StatArgs {
-    PointArgs p;
-    double *sums;  // (2, C, ntiles, B) for the C channels of the layer
-};
-
 // BatchNorm L of the round, in the order they run (round_trunk, pointnet_net.h): the layers below L are the forward's own
 // calls (h is not written here), layer L's width and epilogue come with it.
 template <int MODE, int L>
@@ -73,7 +70,7 @@ __global__ __launch_bounds__(kPtThreads) void pointnet_stats_kernel(const StatAr
         using Ly = decltype(layer);
         double *sums = s.sums + 2 * ((size_t)b * s.p.ntiles + tile) * Ly::COUT;
         if constexpr (Ly::CIN == 3) conv_stat3<Ly::EPI>(in, c.W, c.b, nvalid, sums);
-        else conv_stat_mfma<Ly::CIN, Ly::EPI>(in, Ly::COUT, c.W, c.b, nvalid, sums);
+        else conv_stat_mfma<Ly::CIN, Ly::EPI>(in, Ly::COUT, c.W, c.b, nvalid, sums, Ly::CIN == 0 ? s.p.K : Ly::CIN);
     });
 }
 
@@ -92,12 +89,6 @@ __global__ __launch_bounds__(kDenseStatThreads) void pointnet_dense_stats_kernel
     for (int b = 0; b < B; ++b) t.add(act[(size_t)b * C + c]);
     finish_channel(o, c, t.s1, t.s2);
 }
-
-struct TrainHeadArgs {
-    HeadArgs h;            // the test-mode head's arguments, bn1 / bn2 at the batch statistics
-    float *a1, *a2;        // workspace: relu(dense1) (512, B), FEAT only; relu(dense2) [times the dropout multiplier] (256, B)
-    const float *dropout;  // FEAT: (256, B) multipliers or NULL
-};
 
 // up to the head's first BatchNorm: MaxPool, relu(dense1); stn / fstn have no BatchNorm there and go on through relu(dense2)
 template <bool FEAT>
@@ -153,37 +144,6 @@ fx3d_status launch_stats_of(const StatArgs &s, int B, bool last, hipStream_t st)
     return FX3D_OK;
 }
 
-// BatchNorm L of round `mode`; `last`: the round's 1024-channel layer (a label of its own in the library's profile)
-fx3d_status launch_stats(int mode, int L, const StatArgs &s, int B, hipStream_t st) {
-    switch (mode * 4 + L) {
-        case 0: return launch_stats_of<0, 0>(s, B, false, st);
-        case 1: return launch_stats_of<0, 1>(s, B, false, st);
-        case 2: return launch_stats_of<0, 2>(s, B, true, st);
-        case 4: return launch_stats_of<1, 0>(s, B, false, st);
-        case 5: return launch_stats_of<1, 1>(s, B, false, st);
-        case 6: return launch_stats_of<1, 2>(s, B, false, st);
-        case 7: return launch_stats_of<1, 3>(s, B, true, st);
-        case 8: return launch_stats_of<2, 0>(s, B, false, st);
-        default: return launch_stats_of<2, 1>(s, B, true, st);
-    }
-}
-
-// part 0 = head_a, 1 = head_b (feat), 2 = head_c
-fx3d_status launch_train_head(int part, bool feat, const TrainHeadArgs &t, int B, hipStream_t st) {
-    ProfileScope prof("pointnet_train_head", st);
-    if (part == 0) {
-        if (feat) hipLaunchKernelGGL(pointnet_train_head_a_kernel<true>, dim3(B), dim3(kHeadThreads), 0, st, t);
-        else hipLaunchKernelGGL(pointnet_train_head_a_kernel<false>, dim3(B), dim3(kHeadThreads), 0, st, t);
-    } else if (part == 1) {
-        hipLaunchKernelGGL(pointnet_train_head_b_kernel, dim3(B), dim3(512), 0, st, t);
-    } else {
-        if (feat) hipLaunchKernelGGL(pointnet_train_head_c_kernel<true>, dim3(B), dim3(kHeadThreads), 0, st, t);
-        else hipLaunchKernelGGL(pointnet_train_head_c_kernel<false>, dim3(B), dim3(kHeadThreads), 0, st, t);
-    }
-    FX3D_LAUNCH_CHECK();
-    return FX3D_OK;
-}
-
 // the forward's workspace, then the tile sums of the widest layer, relu(dense1) of feat and relu(dense2) of every head
 struct TrainPlan { WsPlan fwd; size_t sums, a1, a2, total; };
 TrainPlan train_plan(int N, int B, int nc) {
@@ -208,10 +168,44 @@ fx3d_status check_train_sizes(const char *fn, int32_t N, int32_t B, int32_t nc) 
 
 }  // namespace
 
-// ---- the finishing kernels the training-mode forwards share (pointnet_net.h) ----------------------------------------------------
+// ---- what the training-mode forwards share (pointnet_net.h): the statistics pass and the heads (stnkd.hip), the finishing kernels
 namespace fx3d {
 namespace mlp {
 namespace pointnet {
+
+// BatchNorm L of round `mode`; `last`: the round's 1024-channel layer (a label of its own in the library's profile)
+fx3d_status launch_stats(int mode, int L, const StatArgs &s, int B, hipStream_t st) {
+    switch (mode * 4 + L) {
+        case 0: return launch_stats_of<0, 0>(s, B, false, st);
+        case 1: return launch_stats_of<0, 1>(s, B, false, st);
+        case 2: return launch_stats_of<0, 2>(s, B, true, st);
+        case 4: return launch_stats_of<1, 0>(s, B, false, st);
+        case 5: return launch_stats_of<1, 1>(s, B, false, st);
+        case 6: return launch_stats_of<1, 2>(s, B, false, st);
+        case 7: return launch_stats_of<1, 3>(s, B, true, st);
+        case 8: return launch_stats_of<2, 0>(s, B, false, st);
+        case 9: return launch_stats_of<2, 1>(s, B, true, st);
+        case 12: return launch_stats_of<3, 0>(s, B, false, st);
+        case 13: return launch_stats_of<3, 1>(s, B, false, st);
+        default: return launch_stats_of<3, 2>(s, B, true, st);
+    }
+}
+
+// part 0 = head_a, 1 = head_b (feat), 2 = head_c
+fx3d_status launch_train_head(int part, bool feat, const TrainHeadArgs &t, int B, hipStream_t st) {
+    ProfileScope prof("pointnet_train_head", st);
+    if (part == 0) {
+        if (feat) hipLaunchKernelGGL(pointnet_train_head_a_kernel<true>, dim3(B), dim3(kHeadThreads), 0, st, t);
+        else hipLaunchKernelGGL(pointnet_train_head_a_kernel<false>, dim3(B), dim3(kHeadThreads), 0, st, t);
+    } else if (part == 1) {
+        hipLaunchKernelGGL(pointnet_train_head_b_kernel, dim3(B), dim3(512), 0, st, t);
+    } else {
+        if (feat) hipLaunchKernelGGL(pointnet_train_head_c_kernel<true>, dim3(B), dim3(kHeadThreads), 0, st, t);
+        else hipLaunchKernelGGL(pointnet_train_head_c_kernel<false>, dim3(B), dim3(kHeadThreads), 0, st, t);
+    }
+    FX3D_LAUNCH_CHECK();
+    return FX3D_OK;
+}
 
 fx3d_status launch_stat_finish(const double *sums, int C, long long T, const StatOut &o, hipStream_t st, const char *label) {
     ProfileScope prof(label, st);

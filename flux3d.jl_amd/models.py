@@ -11,7 +11,8 @@ training-mode forward (``PointNet.forward_train`` over fx3d_pointnet_forward_tra
 forward's gradients (``PointNet.grad_train`` over fx3d_pointnet_grad_train, "PointNet training-mode adjoint"); DGCNN and EdgeConv have their training-mode forwards (``DGCNN.forward_train`` over
 fx3d_dgcnn_forward_train, ``EdgeConv.forward_train`` over fx3d_edgeconv_forward_train, "DGCNN / EdgeConv training-mode forward") and those
 forwards' gradients (``EdgeConv.grad_train`` over fx3d_edgeconv_grad_train, "EdgeConv training-mode adjoint"; ``DGCNN.grad_train`` over
-fx3d_dgcnn_grad_train, "DGCNN training-mode adjoint")."""
+fx3d_dgcnn_grad_train, "DGCNN training-mode adjoint").  ``stnKD(K)`` (src/models/pointnet.jl:3-20) is a layer of its own as well,
+forward and training-mode forward (:class:`stnKD` over fx3d_stnkd_forward / fx3d_stnkd_forward_train, include/flux3d_hip_layers.h)."""
 import ctypes as C
 
 import numpy as np
@@ -1174,3 +1175,118 @@ class EdgeConv(_Model):
         ``X`` lives."""
         gp, gx, on_dev = self._train_grad_call(X, gout, idx, fwd, input_grad)
         return self._grad_views(gp, on_dev), (gx if on_dev or gx is None else gx.to_host())
+
+
+def stnkd_layer_spec(K):
+    """stnKD(K)'s layers that carry parameters, in forward order: :func:`_stn_spec` without a prefix (``conv1`` ... ``dense3``)."""
+    return [(name[1:], kind, ch) for name, kind, ch in _stn_spec("", int(K))]
+
+
+def stnkd_param_shapes(K):
+    """stnKD(K): name -> shape of every parameter array, in the order of the flat buffer (Flux's shapes, :func:`_shapes`)."""
+    return _shapes(stnkd_layer_spec(K))
+
+
+class stnKD(_Model):
+    """``stnKD(K)`` (src/models/pointnet.jl:3-20), the spatial-transformer block as a layer in its own right, in test mode and in
+    training mode: include/flux3d_hip_layers.h "stnKD(K)" states the layer, its arithmetic and the envelope.  Three 1x1
+    convolutions K => 64 => 128 => 1024 (relu, BatchNorm), the maximum over the points, Dense 1024 => 512 => 256 (relu), BatchNorm,
+    Dense 256 => K K, returned as the (K, K) matrix per cloud in the orientation of PointNet's ``stn`` / ``fstn``.  1 <= K <= 128.
+
+    The input is ``(K, N, B)``, channels first like every model here; the reference's Chain takes the permuted ``(N, K, B)``.
+    ``params`` (:func:`stnkd_param_shapes`: ``conv1.weight`` ... ``dense3.bias``), ``load``, ``flat_params`` and the seeded
+    initialisation are the classifiers'.  The ``stn.`` / ``fstn.`` arrays of a PointNet, with that prefix dropped, are the
+    parameters of ``stnKD(3)`` / ``stnKD(64)``: :meth:`from_pointnet`.  Gradients are not there yet."""
+
+    _NAME, _COUNT_FN = "stnKD", "fx3d_stnkd_param_count"
+    MAX_K = 128
+
+    def __init__(self, K, seed=0):
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
+            raise TypeError(f"K must be an integer, got {K!r}")
+        if not 1 <= int(K) <= self.MAX_K:
+            raise ValueError(f"stnKD(K) needs K in [1, {self.MAX_K}], got {K}")
+        self.K = int(K)
+        self._init_params(seed)
+
+    @classmethod
+    def from_pointnet(cls, model, which):
+        """The ``stn`` (K = 3) or ``fstn`` (K = 64) block of the PointNet ``model`` as a layer of its own, its parameters copied."""
+        if not isinstance(model, PointNet):
+            raise TypeError(f"model must be a PointNet, got {type(model).__name__}")
+        if which not in ("stn", "fstn"):
+            raise ValueError(f"which must be 'stn' or 'fstn', got {which!r}")
+        if model._stale:
+            model.pull_params()
+        layer = cls(3 if which == "stn" else 64)
+        return layer.load({name: model.params[f"{which}.{name}"] for name in layer._shapes()})
+
+    def _count_args(self):
+        return (self.K,)
+
+    def _shapes(self):
+        return stnkd_param_shapes(self.K)
+
+    def _head(self, X):
+        """The checks every call begins with: a PointCloud only for K = 3, then the clouds (:meth:`_clouds`)."""
+        if isinstance(X, PointCloud) and self.K != 3:
+            raise ValueError(f"a PointCloud has 3 channels per point, stnKD({self.K}) takes {self.K}")
+        return self._clouds(X, f"stnKD({self.K})", self.K)
+
+    def forward(self, X, intermediates=False):
+        """The transforms ``(K, K, B)`` of the clouds ``X``: a device array or a numpy array, ``(K, N, B)`` or ``(K, N)`` (one
+        cloud); a PointCloud when K = 3.  The result lives where the input lives.  ``intermediates=True``: a dict with ``out``
+        and ``pooled`` (1024, B), the maximum over the points."""
+        K = self.K
+        pts, N, B, on_dev = self._head(X)
+        nb = _lib.query_bytes("fx3d_stnkd_workspace_bytes", N, B, K)  # (the library's own size limits)
+        x = self._on_device(pts, N, B, on_dev, K)
+        out = {"out": DeviceArray.empty((K, K, B), np.float32)}
+        if intermediates:
+            out["pooled"] = DeviceArray.empty((1024, B), np.float32)
+        ws = workspace(nb, tag="stnkd")
+        _lib.call("fx3d_stnkd_forward", self._params_dev().ptr, K, x.ptr, N, B, out["out"].ptr,
+                  out["pooled"].ptr if intermediates else None, ws.ptr, ws.nbytes, current_stream().handle)
+        if not on_dev:
+            out = {k: v.to_host() for k, v in out.items()}
+        return out if intermediates else out["out"]
+
+    __call__ = forward
+
+    def forward_train(self, X, momentum=0.1, update=False, intermediates=False):
+        """:meth:`forward` with the layer in TRAINING mode (at least two clouds): include/flux3d_hip_layers.h "stnKD(K),
+        training-mode forward".  Each of the four BatchNorms normalises by the mean and uncorrected variance of the current batch.
+        ``intermediates=True``: a dict with ``out``, ``pooled``, ``batch_stats`` and ``running``: dicts name -> array with the
+        ``bnK.mu`` / ``.sigma2`` names of :func:`stnkd_param_shapes`, the batch statistics and the running statistics Flux's
+        BatchNorm would hold after this step (``momentum``; computed from the layer's ``mu`` / ``sigma2``).  Everything lives
+        where ``X`` lives.  ``update=True`` writes ``running`` into the layer's parameters, on the host (which reads them back: not
+        inside a graph capture) and in the kept device copy."""
+        K, f32 = self.K, np.float32
+        pts, N, B, on_dev = self._head(X)
+        if B < 2:
+            raise ValueError(f"training-mode BatchNorm needs at least two clouds (the dense BatchNorm's running variance divides by "
+                             f"B - 1), got B={B}")
+        momentum = self._momentum(momentum)
+        nb = _lib.query_bytes("fx3d_stnkd_train_workspace_bytes", N, B, K)  # (the library's own size limits)
+        x = self._on_device(pts, N, B, on_dev, K)
+        slots = self._stat_slots()
+        nstat = slots[-1][2] + 2 * slots[-1][1]
+        out = {"out": DeviceArray.empty((K, K, B), f32)}
+        if intermediates:
+            out["pooled"] = DeviceArray.empty((1024, B), f32)
+        stats = {"batch_stats": DeviceArray.empty((nstat,), f32)}
+        if intermediates or update:
+            stats["running"] = DeviceArray.empty((nstat,), f32)
+        ws = workspace(nb, tag="stnkd_train")
+        stream = current_stream().handle
+        _lib.call("fx3d_stnkd_forward_train", self._params_dev().ptr, K, x.ptr, N, B, momentum, out["out"].ptr,
+                  out["pooled"].ptr if intermediates else None, stats["batch_stats"].ptr,
+                  stats["running"].ptr if "running" in stats else None, ws.ptr, ws.nbytes, stream)
+        if update:
+            self._adopt_running(stats["running"], slots, stream)
+        if not on_dev:
+            out = {k: v.to_host() for k, v in out.items()}
+        if not intermediates:
+            return out["out"]
+        out.update({key: self._named_stats(buf, slots, on_dev) for key, buf in stats.items()})
+        return out
